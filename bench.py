@@ -9,7 +9,7 @@ N > 1 -- by the RCCL all-gather of ``sensordata`` + the 16-double metrics all-re
 issued on a side stream so that they overlap the next launch.  Inputs are resident in HBM before the timed region.
 Rank 0 prints ONE JSON line.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--config 2|3|5] [--substeps S] [--envs E] [--lanes G]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--config 2|3|5] [--substeps S] [--envs E] [--lanes G] [--dump-outputs DIR]
 
 With N > 1 and no torch.distributed environment the script spawns its own ranks (one process per GPU through
 ``python -m torch.distributed.run`` on 127.0.0.1); under torchrun it uses the environment it is given.
@@ -162,6 +162,36 @@ def _free_port():
     p = s.getsockname()[1]
     s.close()
     return p
+
+
+DUMP_MAX_BYTES = 64 << 20   # --dump-outputs: the whole dump stays under this
+DUMP_SAMPLE_SEED = 20240601  # the env rows kept when a dump would exceed it (fixed: two runs keep the same rows)
+
+
+def dump_outputs(path, per_env, other=None, max_bytes=DUMP_MAX_BYTES):
+    """--dump-outputs DIR: what the timed path handed its caller after its last step, one float64 DIR/<name>.npy per array.
+    ``per_env`` arrays have one row per env (env-major, all with the same number of rows); ``other`` arrays are written whole.
+    ``env_index.npy`` names the env of every row.  When everything would exceed ``max_bytes``, a fixed, seeded, sorted sample of
+    env rows -- the same rows for every per-env array -- is written instead of all of them."""
+    os.makedirs(path, exist_ok=True)
+    per_env = {k: np.ascontiguousarray(v, dtype=np.float64) for k, v in per_env.items() if np.asarray(v).size}
+    other = {k: np.ascontiguousarray(v, dtype=np.float64) for k, v in (other or {}).items()}
+    rows = {a.shape[0] for a in per_env.values()}
+    if len(rows) > 1:
+        raise ValueError(f"dump_outputs: per-env arrays disagree on the env count {sorted(rows)}")
+    nenv = rows.pop() if rows else 0
+    fixed = sum(a.nbytes for a in other.values())
+    row_bytes = sum(a.nbytes // max(nenv, 1) for a in per_env.values()) + 8   # (+ the row's entry of env_index)
+    keep = nenv
+    if fixed + nenv * row_bytes > max_bytes:
+        keep = max(0, min(nenv, (max_bytes - fixed - 4096 * (len(per_env) + len(other) + 1)) // row_bytes))   # (4 KB per .npy header, generous)
+    idx = np.arange(nenv) if keep == nenv else np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(nenv, size=keep, replace=False))
+    np.save(os.path.join(path, "env_index.npy"), idx.astype(np.float64))
+    for k, a in per_env.items():
+        np.save(os.path.join(path, f"{k}.npy"), a if keep == nenv else np.ascontiguousarray(a[idx]))
+    for k, a in other.items():
+        np.save(os.path.join(path, f"{k}.npy"), a)
+    return keep
 
 
 def _load_json(*names):
@@ -359,11 +389,16 @@ def main():
     ap.add_argument("--dry-ranks", type=int, default=0, help="CI: run the N-rank control flow (rendezvous, overlapped exchange, fence, max-over-ranks "
                     "timing, the rank-0 line) under gloo with a stub batch and thread streams -- no GPU, the value means nothing")
     ap.add_argument("--dry-fail-rank", type=int, default=-1, help="(with --dry-ranks) this rank raises inside the timed region: exercises the error line")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write what the last one computed (rank 0's envs: state fields, sensordata, metrics) as "
+                         "DIR/<name>.npy, float64, at most 64 MB (a fixed, seeded sample of envs beyond that); same arguments, same inputs")
     args = ap.parse_args()
     if args.dry_ranks:
         args.gpus = args.dry_ranks
     if args.gpus < 1:
         ap.error("--gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     name = args.model or CONFIG_MODEL[args.config or 2]
 
     # ---- one process per GPU: spawn the ranks ourselves when nobody did (bare `python bench.py --gpus N`)
@@ -508,6 +543,8 @@ def dry_run(args):
 
     elapsed, per_rank = timed_region(args, one_step, fence, dist, world, lambda v: torch.tensor(v, dtype=torch.float64))
     sens_all, m = xch.finish()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"sensordata": sens_all.numpy()}, {"metrics": m.numpy()})
     total = args.warmup + args.steps
     ok = all(bool((sens_all[r * E:(r + 1) * E] == float(1000 * total + r)).all()) for r in range(world))
     ok = ok and float(m[0]) == float(world * E * S * total) and float(m[8]) == float(world - 1)
@@ -605,6 +642,10 @@ def gpu_run(args, name):
         batch.set_stats(True)    # device-side ncon / nefc / iteration counters over everything this rank runs from here on (warm-up included)
     elapsed, per_rank = timed_region(args, one_step, fence, dist, world, lambda v: torch.tensor(v, dtype=torch.float64, device=dev))
     sens_all, met = xch.finish()
+    if args.dump_outputs and rank == 0:   # (before anything below launches the engine again)
+        torch.cuda.synchronize()
+        dump_outputs(args.dump_outputs, {f: batch.get(f) for f in ("qpos", "qvel", "act", "ctrl", "qacc", "time", "energy", "sensordata")},
+                     {"metrics": met.cpu().numpy()})
     noise_mode = batch.noise_mode()
     noise_modes = [noise_mode]
     if world > 1:  # every rank's generator mode: eight side-stream generators + RCCL kernels compete for the CUs the step kernel fills

@@ -101,3 +101,73 @@ def test_a_failing_rank_ends_in_one_error_line_not_a_hang(bad):
     assert len(lines) == 1 and "error" in lines[0] and lines[0]["rank"] == 0
     assert f"injected failure on rank {bad}" in lines[0]["error"]
     assert "value" not in lines[0]
+
+
+# ---- --dump-outputs DIR: what the timed path computed in its last step, as DIR/<name>.npy (float64, <= 64 MB, seeded env sample beyond)
+def _load_dump(d):
+    import numpy as np
+    return {f[:-4]: np.load(os.path.join(d, f)) for f in sorted(os.listdir(d)) if f.endswith(".npy")}
+
+
+@pytest.mark.parametrize("ranks", [1, 2])
+def test_dry_run_dumps_the_last_step(tmp_path, ranks):
+    import numpy as np
+    p, lines = _run_bench("--dry-ranks", str(ranks), "--steps", "3", "--warmup", "1", "--dump-outputs", str(tmp_path / "out"))
+    assert p.returncode == 0 and len(lines) == 1 and lines[0]["steps"] == 3, p.stderr[-3000:]
+    d = _load_dump(tmp_path / "out")
+    assert set(d) == {"env_index", "sensordata", "metrics"} and all(a.dtype == np.float64 for a in d.values())
+    # the stub's launch k writes 1000 k + rank into its shard: the dump holds launch W + K = 4, every rank's envs
+    want = np.repeat(1000.0 * 4 + np.arange(ranks), 64)
+    assert d["sensordata"].shape == (64 * ranks, 8) and np.array_equal(d["sensordata"], np.repeat(want[:, None], 8, axis=1))
+    assert np.array_equal(d["env_index"], np.arange(64 * ranks)) and d["metrics"][0] == ranks * 64 * 10 * 4
+
+
+def test_dump_outputs_samples_the_same_envs_within_the_budget(tmp_path):
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    a, b = np.arange(20000.0).reshape(2000, 10), -np.arange(6000.0).reshape(2000, 3)
+    keep = [bench.dump_outputs(str(tmp_path / k), {"a": a, "b": b, "empty": np.zeros((2000, 0))}, {"m": np.ones(16)}, max_bytes=80000)
+            for k in ("x", "y")]
+    x, y = _load_dump(tmp_path / "x"), _load_dump(tmp_path / "y")
+    assert keep[0] == keep[1] and 0 < keep[0] < 2000 and set(x) == {"env_index", "a", "b", "m"}
+    assert sum(os.path.getsize(tmp_path / "x" / f) for f in os.listdir(tmp_path / "x")) <= 80000
+    i = x["env_index"].astype(int)
+    assert np.array_equal(x["env_index"], y["env_index"]) and np.all(np.diff(i) > 0)     # fixed seed: the same rows every time
+    assert np.array_equal(x["a"], a[i]) and np.array_equal(x["b"], b[i]) and np.array_equal(x["m"], np.ones(16))
+    assert bench.dump_outputs(str(tmp_path / "z"), {"a": a}) == 2000 and np.array_equal(_load_dump(tmp_path / "z")["a"], a)
+
+
+@pytest.mark.gpu
+def test_dump_outputs_is_the_last_timed_step_and_repeats(tmp_path):
+    """Two runs with the same arguments dump the same arrays; their clock says exactly W + K launches of S physics steps ran
+    (--steps sets the timed steps), and the state is what the engine computes for the same inputs outside bench.py."""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    from mujoco_ros_pkgs_amd import engine, mjcf
+    E, S, K, W = 256, 20, 3, 1
+    args = ("--steps", str(K), "--warmup", str(W), "--envs", str(E), "--substeps", str(S), "--no-cpu-baseline", "--no-other-configs")
+    dumps = []
+    for k in range(2):
+        p, lines = _run_bench(*args, "--dump-outputs", str(tmp_path / f"run{k}"), timeout=600)
+        assert p.returncode == 0 and len(lines) == 1 and lines[0]["steps"] == K and lines[0]["ms_per_step"] > 0, p.stderr[-3000:]
+        dumps.append(_load_dump(tmp_path / f"run{k}"))
+    a, b = dumps
+    assert {"qpos", "qvel", "ctrl", "qacc", "time", "sensordata", "metrics", "env_index"} <= set(a) and set(a) == set(b)
+    for k in a:
+        assert np.array_equal(a[k], b[k]) or k == "metrics", k   # (metrics: an on-device reduction, summation order may vary)
+    model = mjcf.load_asset("franka_like")
+    assert a["qpos"].shape == (E, model["nq"]) and np.array_equal(a["env_index"], np.arange(E))
+    np.testing.assert_allclose(a["time"][:, 0], (W + K) * S * model["timestep"][0], rtol=1e-12)
+    model = mjcf.Model(dict(model))
+    model["enableflags"] = int(model["enableflags"]) | 2
+    batch = engine.Batch(engine.CompiledModel(model), E, 0)
+    qpos, qvel = bench.initial_state("franka_like", model, E, seed=1000)
+    batch.set("qpos", qpos)
+    batch.set("qvel", qvel)
+    batch.set_ctrl_noise(bench.WORKLOADS["franka_like"][1], 0.1, 12345, 0)
+    for _ in range(W + K):
+        batch.step(S)
+    np.testing.assert_allclose(batch.get("qpos"), a["qpos"], rtol=0, atol=1e-12)
+    np.testing.assert_allclose(batch.get("qvel"), a["qvel"], rtol=0, atol=1e-10)
