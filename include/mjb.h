@@ -125,7 +125,11 @@ int mjb_version(void);
 int mjb_device_count(void);
 
 /* Validate + copy a model description.  Takes the place of `mj_loadXML`/`mj_loadModel` for the
- * batched path (reference: mujoco_env.cpp:836-843); the arrays are copied, `desc` may be freed. */
+ * batched path (reference: mujoco_env.cpp:836-843); the arrays are copied, `desc` may be freed.
+ * Caps of the one-env-per-wavefront kernels: nv <= 64; nefcmax <= 128 under PGS (64 with elliptic contacts) and a per-env frame within one
+ * CU's LDS (160 KB); nefcmax <= 1024 under Newton / CG, with a frame of any size.  Newton / CG models with more than 256 rows of capacity, or
+ * whose full frame exceeds the LDS budget, run the row-slot solver, and any of their frames that exceeds the budget lives in HBM
+ * (mjb_model_frame_info).  Beyond a cap the call fails with MJB_EUNSUPPORTED. */
 mjb_model *mjb_compile(const mjb_model_desc *desc);
 void mjb_free_model(mjb_model *m); /* mj_deleteModel, mujoco_env.cpp:747 */
 
@@ -282,6 +286,10 @@ int mjb_set_split_step(mjb_batch *b, int mode);
  * launch ran as a split step, *slices (may be NULL) = the env slices it was cut into. */
 int mjb_split_step_info(const mjb_batch *b, int *used_last, int *slices);
 int mjb_model_split_step(const mjb_model *m);
+/* 1: the model runs the row-slot Newton / CG solver (more than 256 rows of capacity, or a full frame beyond one CU's LDS), 0: it does not.
+ * *full_hbm / *fused_hbm (may be NULL) = 1 when the full frame (mjb_forward, mjb_step1 / mjb_step2, frame dumps) / the fused frame of
+ * mjb_step lives in the env's slot of an HBM workspace instead of LDS.  No reference counterpart. */
+int mjb_model_frame_info(const mjb_model *m, int *full_hbm, int *fused_hbm);
 /* >= 0: index of the compiled-in topology the batch's model matches; -2: none compiled in, but the model's structure fits the kernel -- its
  * first eligible launch builds the kernel for it through hiprtc (libhiprtc.so and csrc/mjb_lane_env_kernel.h next to libmjb.so; a few
  * seconds, cached per process); -3: that build was not possible (mjb_lane_env_error says why) and the generic kernels run; -1: the model does not

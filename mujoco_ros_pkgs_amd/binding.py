@@ -215,6 +215,7 @@ def load_library(path=None):
         "mjb_set_split_step": (ci, [vp, ci]),
         "mjb_split_step_info": (ci, [vp, C.POINTER(ci), C.POINTER(ci)]),
         "mjb_model_split_step": (ci, [vp]),
+        "mjb_model_frame_info": (ci, [vp, C.POINTER(ci), C.POINTER(ci)]),
         "mjb_set_stats": (ci, [vp, ci]),
         "mjb_get_stats": (ci, [vp, C.POINTER(C.c_ulonglong)]),
         "mjb_get_stream": (vp, [vp]),

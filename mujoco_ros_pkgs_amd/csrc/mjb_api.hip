@@ -97,6 +97,11 @@ struct mjb_model {
 	// take the two-rows-per-lane solver on LDS instead of the four-rows-per-lane one on the env's block in HBM (launch(), wide policy).
 	FrameLayout Lw{};
 	bool has_wide = false;
+	// the row-slot solver (kernel variants 10 - 13): Newton / CG models beyond the register-row kernels -- more than 256 rows of capacity, or
+	// a full frame larger than one CU's LDS.  Their fused frame holds every row (no efc_Jg, no wide frame); a launch whose frame exceeds
+	// the LDS budget runs it from the env's slot of DevState::frame_ws (variants 12 / 13)
+	bool slot = false;
+	bool hbm_full = false, hbm_fused = false;  // the full / fused frame lives in HBM
 	int le_topo = -1;  // compiled-in topology of the lane = env kernel the model matches (mjb_lane_env.hip); -1: none; -2: eligible, built by hiprtc on first use
 	std::vector<double> le_tape;  // its constant tape (mjb_dev.h), empty without a topology
 	int sm_topo = -1;  // compiled-in topology of the split step's smooth kernel (mjb_smooth.hip) when the model's constraint half fits mjb_cstep_kernel too; -1: none
@@ -241,7 +246,7 @@ void compute_layout(mjb_model *M, FrameLayout &L, bool compact, int jrows_req = 
 	// kernel variant 4 (Newton, more than 128 rows of capacity), fused frame: the first 64 rows of efc_J only; an env-step with
 	// more rows keeps J in the env's block of DevState::efc_Jg (config 5 never has: what lets two of its envs share a CU's LDS)
 	int jrows = d.nefcmax;
-	if (compact && d.solver == MJB_SOL_NEWTON && d.nefcmax > 128) {
+	if (compact && d.solver == MJB_SOL_NEWTON && d.nefcmax > 128 && !M->slot) {
 		jrows = jrows_req > 0 ? std::max(4, std::min(128, jrows_req)) : 64;
 		if (const char *v = getenv("MJB_DEBUG_JROWS")) jrows = std::max(4, std::min(64, atoi(v)));  // test knob: force the HBM path
 	}
@@ -563,6 +568,10 @@ void choose_fused_layout(mjb_model *M)
 	const mjb_model_desc &d = M->h;
 	M->Lw = M->Lc;
 	M->has_wide = false;
+	if (M->slot) {  // (the row-slot kernels: every row in the fused frame)
+		if (getenv("MJB_DEBUG_LAYOUT")) dump_layout(M, M->Lc);
+		return;
+	}
 	if (d.solver == MJB_SOL_NEWTON && d.nefcmax > 128 && getenv("MJB_DEBUG_FRAME_ROWS")) {  // measurement knob: rows of J in THE fused frame
 		compute_layout(M, M->Lc, true, atoi(getenv("MJB_DEBUG_FRAME_ROWS")));
 		M->Lw = M->Lc;
@@ -791,10 +800,10 @@ mjb_model *mjb_compile(const mjb_model_desc *desc)
 			fail(MJB_EUNSUPPORTED, "mjb_compile: unknown solver (PGS = 0, CG = 1, Newton = 2)");
 			return nullptr;
 		}
-		const int rowcap = d.solver != MJB_SOL_PGS ? 256 : ((d.cone == MJB_CONE_ELLIPTIC && d.nconmax > 0) ? 64 : 128);
+		const int rowcap = d.solver != MJB_SOL_PGS ? 1024 : ((d.cone == MJB_CONE_ELLIPTIC && d.nconmax > 0) ? 64 : 128);
 		if (d.nefcmax > rowcap || d.nv > 64) {
 			fail(MJB_EUNSUPPORTED, "mjb_compile: one env per wavefront: nv <= 64 and nefcmax <= 128 (PGS; 64 with elliptic cones) / "
-			                       "256 (Newton / CG, up to 4 rows per lane); got nefcmax = %d, nv = %d", d.nefcmax, d.nv);
+			                       "1024 (Newton / CG; lower <size njmax>); got nefcmax = %d, nv = %d", d.nefcmax, d.nv);
 			return nullptr;
 		}
 		if (!(d.meaninertia[0] > 0)) {
@@ -1322,7 +1331,13 @@ mjb_model *mjb_compile(const mjb_model_desc *desc)
 		}
 	}
 	compute_layout(M, M->L, false);
+	{
+		const bool primal = h.nefcmax > 0 && (h.solver == MJB_SOL_NEWTON || h.solver == MJB_SOL_CG);
+		M->slot = primal && (h.nefcmax > 256 || layout_bytes(M->L) > mjb_max_lds_bytes());
+	}
 	choose_fused_layout(M);
+	M->hbm_full = M->slot && layout_bytes(M->L) > mjb_max_lds_bytes();
+	M->hbm_fused = M->slot && layout_bytes(M->Lc) > mjb_max_lds_bytes();
 	build_sensor_tables(M);
 	// actuators per dof (CSR, ascending actuator id)
 	M->dof_act_adr.assign((size_t)h.nv + 1, 0);
@@ -1353,7 +1368,7 @@ mjb_model *mjb_compile(const mjb_model_desc *desc)
 	}
 	{
 		const int frame_bytes = ((M->L.ndouble * 8 + M->L.nint * 4) + 15) & ~15;
-		if (frame_bytes > mjb_max_lds_bytes()) {
+		if (frame_bytes > mjb_max_lds_bytes() && !M->slot) {  // (the row-slot kernels run such a frame from HBM)
 			fail(MJB_EUNSUPPORTED, "mjb_compile: the per-env working set (%d bytes) exceeds one CU's LDS (%d bytes); "
 			                       "lower nconmax / nefcmax", frame_bytes, mjb_max_lds_bytes());
 			delete M;
@@ -1636,6 +1651,7 @@ mjb_batch *mjb_make_batch(const mjb_model *M, int nenv, int device)
 	ok = ok && s.prof;
 	s.frame_ws = nullptr;
 	s.frame_stride = b->L.ndouble + b->L.nint / 2;
+	if (M->slot) s.frame_stride = std::max(s.frame_stride, M->Lc.ndouble + M->Lc.nint / 2);  // (row-slot kernels: fused frames in HBM live there too)
 	s.use_xfrc = 0;
 	s.env_gravity = nullptr;
 	s.env_geom_friction = nullptr;
@@ -1656,7 +1672,11 @@ mjb_batch *mjb_make_batch(const mjb_model *M, int nenv, int device)
 		s.sched = dev_alloc<int>((size_t)nenv + 1);
 		ok = ok && s.sched;
 	}
-	if (h.solver == MJB_SOL_NEWTON && h.nefcmax > 128) {  // kernel variant 4: row data of the env-steps beyond the fused frame's 64 rows
+	if (M->hbm_full) {  // row-slot kernels: launches on the full frame (and on the fused one, when it is too large too) run in the workspace
+		s.frame_ws = dev_alloc<double>((size_t)nenv * s.frame_stride);
+		ok = ok && s.frame_ws;
+	}
+	if (h.solver == MJB_SOL_NEWTON && h.nefcmax > 128 && !M->slot) {  // kernel variant 4: row data of the env-steps beyond the fused frame's 64 rows
 		// (stride: the kernels index the block with the cone-block stride of the frame THEY run on -- the wide frame of an all-condim-3 model has
 		//  hcs 16 where the default frame has 10: size for the largest of the three layouts)
 		s.efc_Jg_stride = mjb_rowblock_doubles(h.nefcmax, h.nv, h.nconmax, std::max(M->L.hcs, std::max(M->Lc.hcs, M->Lw.hcs)));
@@ -1767,10 +1787,13 @@ static int join_rest(mjb_batch *b)
 	return MJB_OK;
 }
 
-// 0: no constraint rows; 1: PGS (5: PGS with elliptic contacts); 2 / 3 / 4: Newton with 1 / 2 / 4 rows per lane; 6 / 7 / 8: CG
-static int kernel_variant(const mjb_model_desc &h)
+// 0: no constraint rows; 1: PGS (5: PGS with elliptic contacts); 2 / 3 / 4: Newton with 1 / 2 / 4 rows per lane; 6 / 7 / 8: CG;
+// 10 / 11: Newton / CG, the row-slot solver (12 / 13 with the frame in HBM: launch())
+static int kernel_variant(const mjb_model *M)
 {
+	const mjb_model_desc &h = M->h;
 	if (h.nefcmax <= 0) return 0;
+	if (M->slot) return h.solver == MJB_SOL_CG ? 11 : 10;
 	if (h.solver == MJB_SOL_PGS) return (h.cone == MJB_CONE_ELLIPTIC && h.nconmax > 0) ? 5 : 1;
 	return (h.solver == MJB_SOL_CG ? 4 : 0) + (h.nefcmax <= 64 ? 2 : (h.nefcmax <= 128 ? 3 : 4));
 }
@@ -1889,7 +1912,12 @@ static int launch(mjb_batch *b, int mode, int nsteps, int env_lo = 0, int env_hi
 	const bool whole = env_lo == 0 && env_hi == b->nenv;
 	HIP_TRY(hipSetDevice(b->device));
 	const bool compact = mode == MJB_MODE_STEP && !b->st.use_xfrc && !b->st.keep_frame;
-	int variant = kernel_variant(b->model->h);
+	int variant = kernel_variant(b->model);
+	if ((variant == 10 || variant == 11) && (compact ? b->model->hbm_fused : b->model->hbm_full)) {
+		int wrc = ensure_ws(b);
+		if (wrc) return wrc;
+		variant += 2;
+	}
 	// Which fused frame (kernel variant 4 with a wide frame): a long whole-batch launch looks at the row counters of the previous one.
 	// More than a quarter of the env-steps beyond 64 rows: the wide frame (128 rows in LDS, two envs per CU) -- measured on the
 	// power-grasp workload of config 5 (94 % beyond 64 rows): 0.72 -> 2.41 M env-steps/s; fewer than 5 %: back to the default frame
@@ -2778,6 +2806,12 @@ int mjb_split_step_info(const mjb_batch *b, int *used_last, int *slices)
 	return b ? b->model->sm_topo : -1;
 }
 int mjb_model_split_step(const mjb_model *m) { return m ? m->sm_topo : -1; }
+int mjb_model_frame_info(const mjb_model *m, int *full_hbm, int *fused_hbm)
+{
+	if (full_hbm) *full_hbm = m && m->hbm_full ? 1 : 0;
+	if (fused_hbm) *fused_hbm = m && m->hbm_fused ? 1 : 0;
+	return m ? (m->slot ? 1 : 0) : fail(MJB_EINVAL, "null model");
+}
 const char *mjb_lane_env_error(void) { return mjb_lane_env_jit_error(); }
 void mjb_lane_env_jit_counts(int *compiled, int *disk_hits) { mjb_lane_env_jit_stats(compiled, disk_hits); }
 int mjb_model_lane_env(const mjb_model *m) { return m ? m->le_topo : -1; }

@@ -2626,10 +2626,15 @@ template <typename SYNC> DEVI void chol_schur16(double (&Hr)[32], const int lane
 // R == 4 covers the ~200 rows of config 5.
 // JG: efc_J is read from the env's block in HBM (Jg) instead of the frame (kernel variant 4, env-steps with more rows than the
 // frame's share of efc_J; see make_constraint)
-template <int G, int R, bool CGS = false, bool JG = false>  // CGS: conjugate gradient (no Hessian; Polak-Ribiere directions preconditioned by M^-1)
+// SLOT (kernel variants 10 - 13, up to 1024 rows): no per-row registers -- the rows are visited in slots of 64 (row r in lane r % 64,
+// slot r / 64) by #pragma nounroll loops over ceil(nefc / 64) slots, each of which reloads its row's constants from the frame; jaref and
+// jv live in the frame's nwt_row throughout, and a cone leader's line-search constants in its cone block.  The row metadata int keeps
+// its layout with the row's OFFSET from its cone's first row in the low byte (an absolute row index does not fit 8 bits).
+template <int G, int R, bool CGS = false, bool JG = false, bool SLOT = false>  // CGS: conjugate gradient (no Hessian; Polak-Ribiere directions preconditioned by M^-1)
 STAGE void fwd_constraint_newton(CModel m, CLayout L, const EnvLite &e, double *gbase = nullptr)
 {
 	static_assert(G == 64, "the Newton solver maps rows / Hessian columns to the 64 lanes of one wavefront");
+	static_assert(!SLOT || (R == 1 && !JG), "the row-slot solver keeps one row per lane at a time, all of them in the frame");
 	double *f = e.f;
 	int *fi = e.fi;
 	const LaneId lane = e.lane;  // (re-derived at every use: nothing computed from it is hoisted out of the iteration and spilled)
@@ -2723,6 +2728,7 @@ STAGE void fwd_constraint_newton(CModel m, CLayout L, const EnvLite &e, double *
 	bool rowact[R], scalar_row[R], leader[R], bilat[R];
 	int rr[R], cdim[R], rcon[R];
 	double D[R], aref[R], cmu[R], cdmi[R], fl[R];  // fl: force limit of a dry-friction row, 0 for every other row
+	if constexpr (!SLOT)
 #pragma unroll
 	for (int i = 0; i < R; i++) {
 		const int r = lane + 64 * i;
@@ -2744,6 +2750,35 @@ STAGE void fwd_constraint_newton(CModel m, CLayout L, const EnvLite &e, double *
 		// cores): -1 = scalar row (weight hw[r]), else first row of its cone | dim << 8 | contact << 12
 		if (rowact[i]) metap[r] = is_cone ? (fi[L.contact_efc_address + rcon[i]] | (cdim[i] << 8) | (rcon[i] << 12)) : -1;
 	}
+	const int nslot = (nefc + 63) >> 6;
+	// SLOT: the constants of row lane + 64 s into the one-row register arrays (rowact[0] false past nefc)
+	[[maybe_unused]] auto load_slot = [&](int s) {
+		const int r = lane + 64 * s;
+		rowact[0] = r < nefc;
+		rr[0] = rowact[0] ? r : 0;
+		const int rtype = rowact[0] ? typep[r] : 0;
+		rcon[0] = rowact[0] ? idp[r] : 0;
+		const bool is_cone = rowact[0] && rtype == MJB_CNSTR_CONTACT_ELLIPTIC;
+		const int first = is_cone ? fi[L.contact_efc_address + rcon[0]] : 0;
+		scalar_row[0] = rowact[0] && !is_cone;
+		bilat[0] = rowact[0] && rtype == MJB_CNSTR_EQUALITY;
+		leader[0] = is_cone && first == r;
+		cdim[0] = is_cone ? fi[L.contact_dim + rcon[0]] : 0;
+		D[0] = rowact[0] ? Dp[r] : 0.0;
+		fl[0] = (rowact[0] && m.nfriction > 0) ? flp[r] : 0.0;
+		aref[0] = rowact[0] ? arefp[r] : 0.0;
+		cmu[0] = leader[0] ? f[L.contact_friction + 5 * rcon[0]] / sqrt(fmax(MJB_MINVAL, m.impratio[0])) : 1.0;
+		cdmi[0] = 1.0 / (cmu[0] * cmu[0] * (1 + cmu[0] * cmu[0]));
+		return first;
+	};
+	if constexpr (SLOT) {
+#pragma nounroll
+		for (int s = 0; s < nslot; s++) {
+			const int first = load_slot(s);
+			const bool is_cone = rowact[0] && !scalar_row[0];
+			if (rowact[0]) metap[rr[0]] = is_cone ? ((rr[0] - first) | (cdim[0] << 8) | (rcon[0] << 12)) : -1;
+		}
+	}
 
 
 	// J_r . x - aref_r for the lane's rows (x: nv doubles in LDS)
@@ -2757,6 +2792,21 @@ STAGE void fwd_constraint_newton(CModel m, CLayout L, const EnvLite &e, double *
 #pragma unroll 5
 			for (int c = 0; c < nv; c++) s += Jr[c] * x[c];
 			out[i] = s;
+		}
+	};
+
+	// SLOT: J_r . x - sub aref_r of every row into dst[r] (same summation order as row_dots)
+	[[maybe_unused]] auto row_dots_to = [&](const double *x, double sub, double *dst) {
+#pragma nounroll
+		for (int s = 0; s < nslot; s++) {
+			const int r = lane + 64 * s;
+			if (r < nefc) {
+				const double *Jr = Jb + r * nv;
+				double t = -sub * arefp[r];
+#pragma unroll 5
+				for (int c = 0; c < nv; c++) t += Jr[c] * x[c];
+				dst[r] = t;
+			}
 		}
 	};
 
@@ -2833,6 +2883,9 @@ STAGE void fwd_constraint_newton(CModel m, CLayout L, const EnvLite &e, double *
 	auto cone_update_d = [&](auto DIMC, bool hess, const double *jar_s) -> double {
 		constexpr int DMAX = decltype(DIMC)::value;
 		double cost = 0;
+		// (SLOT: one trip per slot of 64 rows, its constants reloaded into the one-row arrays; the register-row kernels: one trip)
+		for (int s_ = 0; s_ < (SLOT ? nslot : 1); s_++) {
+		if constexpr (SLOT) load_slot(s_);
 #pragma unroll
 		for (int i = 0; i < R; i++) {
 			const int r = rr[i];
@@ -2918,6 +2971,7 @@ STAGE void fwd_constraint_newton(CModel m, CLayout L, const EnvLite &e, double *
 				}
 			}
 		}
+		}
 		return cost;
 	};
 	auto cone_update = [&](bool hess, const double *src) -> double {
@@ -2935,7 +2989,33 @@ STAGE void fwd_constraint_newton(CModel m, CLayout L, const EnvLite &e, double *
 	// from then on moves them along the search direction (Ma += alpha Mv, jaref += alpha jv) -- round 3 multiplied again at the top
 	// of every iteration (3.9 k of the 10 k cycles of its gradient step on config 5).
 	double ma, jaref[R];
-	{
+	if constexpr (SLOT) {
+		// (the two candidates' J q - aref straight into jar_s / jv_s; the winner's stay in jar_s)
+		const double *qw = f + L.qacc_warmstart, *qs = f + L.qacc_smooth;
+		const double t0 = m_dot(qw);
+		row_dots_to(qw, 1.0, jar_s);
+		const double t1 = m_dot(qs);
+		row_dots_to(qs, 1.0, jv_s);
+		const double gk0 = dofact ? 0.5 * (t0 - f[L.qfrc_smooth + k]) * (qw[k] - qs[k]) : 0.0;
+		const double gk1 = dofact ? 0.5 * (t1 - f[L.qfrc_smooth + k]) * (qs[k] - qs[k]) : 0.0;
+		sync();
+		const double ck0 = cone_update(false, jar_s);
+		const double ck1 = cone_update(false, jv_s);
+		double sg0 = gk0, sc0 = ck0, sg1 = gk1, sc1 = ck1, sz = 0;
+		wave_sum3(sg0, sc0, sg1);
+		wave_sum3(sc1, sz, sz);
+		const double cost0 = sg0 + sc0, cost1 = sg1 + sc1;
+		const double best = (m.disableflags & MJB_DSBL_WARMSTART) ? 1e300 : cost0;
+		const bool smooth = cost1 < best;  // (wave-uniform)
+		ma = smooth ? t1 : t0;
+		jaref[0] = 0;
+		if (smooth) {
+#pragma nounroll
+			for (int r = lane; r < nefc; r += 64) jar_s[r] = jv_s[r];
+		}
+		if (dofact) qa[k] = smooth ? qs[k] : qw[k];
+		sync();
+	} else {
 		const double *qw = f + L.qacc_warmstart, *qs = f + L.qacc_smooth;
 		double t0, x0[R], t1, x1[R];
 		dots(qw, 1.0, t0, x0);
@@ -2972,6 +3052,7 @@ STAGE void fwd_constraint_newton(CModel m, CLayout L, const EnvLite &e, double *
 		EPROF(30);
 		// forces, cost, gradient at the current Ma = M qacc, jaref = J qacc - aref (carried in registers, see the warmstart)
 		const double gk = dofact ? 0.5 * (ma - f[L.qfrc_smooth + k]) * (qa[k] - f[L.qacc_smooth + k]) : 0.0;
+		if constexpr (!SLOT)  // (SLOT: jaref lives in jar_s)
 #pragma unroll
 		for (int i = 0; i < R; i++)
 			if (rowact[i]) jar_s[rr[i]] = jaref[i];
@@ -3076,7 +3157,7 @@ STAGE void fwd_constraint_newton(CModel m, CLayout L, const EnvLite &e, double *
 				// row's metadata int has arrived
 				const int meta = metap[rc];
 				const bool cone = meta >= 0;
-				const int adr = cone ? (meta & 255) : rc, dim = cone ? ((meta >> 8) & 15) : 1, con = cone ? (meta >> 12) : 0;
+				const int adr = cone ? (SLOT ? rc - (meta & 255) : (meta & 255)) : rc, dim = cone ? ((meta >> 8) & 15) : 1, con = cone ? (meta >> 12) : 0;
 				const double *wp = cone ? hcb(con, adr) + hcd * (rc - adr) : hw + rc;
 				const double *Jc = Jb + adr * nv + (ina ? ca : 0);
 				double wv[6], jv6[6];
@@ -3108,7 +3189,7 @@ STAGE void fwd_constraint_newton(CModel m, CLayout L, const EnvLite &e, double *
 					b1 = (live && in1) ? v1 : 0.0;
 					const int meta = metap[rc];
 					const bool cone = meta >= 0;
-					const int adr = cone ? (meta & 255) : rc, dim = cone ? ((meta >> 8) & 15) : 1, con = cone ? (meta >> 12) : 0;
+					const int adr = cone ? (SLOT ? rc - (meta & 255) : (meta & 255)) : rc, dim = cone ? ((meta >> 8) & 15) : 1, con = cone ? (meta >> 12) : 0;
 					const double *wp = cone ? hcb(con, adr) + hcd * (rc - adr) : hw + rc;
 					const double *Jc = Jb + adr * nv;
 					double wv[DMAX], j0[DMAX], j1[DMAX];
@@ -3323,10 +3404,16 @@ STAGE void fwd_constraint_newton(CModel m, CLayout L, const EnvLite &e, double *
 		sync();
 		// line search along the Newton direction
 		double mv, jv[R];
+		if constexpr (SLOT) {
+			mv = m_dot(srch);
+			row_dots_to(srch, 0.0, jv_s);
+			jv[0] = 0;
+		} else {
 		dots(srch, 0.0, mv, jv);
 #pragma unroll
 		for (int i = 0; i < R; i++)
 			if (rowact[i]) jv_s[rr[i]] = jv[i];
+		}
 		sync();
 #ifdef MJB_PROFILE_LS  // (libmjb_prof_ls.so: slots 20 / 21 / 22 = the line search's M v | J v, its per-contact constants + Gauss terms, its trial points)
 		EPROF(20);
@@ -3334,6 +3421,13 @@ STAGE void fwd_constraint_newton(CModel m, CLayout L, const EnvLite &e, double *
 		// per-contact line-search constants: registers of the leader lane (R == 1), or parked in the contact's cone
 		// block Hc (free once H is built) when a lane owns several rows and registers are scarce
 		ConeLine cl1 = ConeLine{ 0, 0, 0, 0, 0, 0, 0, 0, 1, 0 };
+		// (SLOT: one trip per slot, the row's jaref / jv fetched into the one-row registers; the constants are always parked)
+		for (int s_ = 0; s_ < (SLOT ? nslot : 1); s_++) {
+		if constexpr (SLOT) {
+			load_slot(s_);
+			jaref[0] = jar_s[rr[0]];
+			jv[0] = jv_s[rr[0]];
+		}
 #pragma unroll
 		for (int i = 0; i < R; i++) {
 			if (leader[i]) {
@@ -3357,7 +3451,7 @@ STAGE void fwd_constraint_newton(CModel m, CLayout L, const EnvLite &e, double *
 						c.VV += V * V;
 					}
 				}
-				if constexpr (R == 1) {
+				if constexpr (R == 1 && !SLOT) {
 					cl1 = c;
 				} else {
 					double *o = hcb(rcon[i], rr[i]);
@@ -3365,6 +3459,7 @@ STAGE void fwd_constraint_newton(CModel m, CLayout L, const EnvLite &e, double *
 					o[5] = c.q0b; o[6] = c.q1b; o[7] = c.q2b; o[8] = c.mu; o[9] = c.Dm;
 				}
 			}
+		}
 		}
 		const double g0 = gauss;
 		const double g2 = wave_sum(dofact ? 0.5 * sk * mv : 0.0);
@@ -3375,6 +3470,19 @@ STAGE void fwd_constraint_newton(CModel m, CLayout L, const EnvLite &e, double *
 		auto ls_eval = [&](LsPoint &p) {
 			const double a = p.alpha;
 			double c0 = 0, c1 = 0, c2 = 0;
+			if constexpr (SLOT) {
+#pragma nounroll
+				for (int s_ = 0; s_ < nslot; s_++) {
+					load_slot(s_);
+					ConeLine c = cl1;
+					if (leader[0]) {
+						const double *o = hcb(rcon[0], rr[0]);
+						c = ConeLine{ o[0], o[1], o[2], o[3], o[4], o[5], o[6], o[7], o[8], o[9] };
+					}
+					const double xr = rowact[0] ? jar_s[rr[0]] : 0.0, vr = rowact[0] ? jv_s[rr[0]] : 0.0;
+					ls_row(a, scalar_row[0], bilat[0], leader[0], xr, vr, D[0], fl[0], c, c0, c1, c2);
+				}
+			} else
 #pragma unroll
 			for (int i = 0; i < R; i++) {
 				if (64 * i >= nefc) continue;
@@ -3474,6 +3582,10 @@ STAGE void fwd_constraint_newton(CModel m, CLayout L, const EnvLite &e, double *
 		if (alpha == 0) break;
 		if (dofact) qa[k] += alpha * sk;
 		ma += alpha * mv;
+		if constexpr (SLOT) {
+#pragma nounroll
+			for (int r = lane; r < nefc; r += 64) jar_s[r] += alpha * jv_s[r];
+		} else
 #pragma unroll
 		for (int i = 0; i < R; i++) jaref[i] += alpha * jv[i];
 		iter++;

@@ -59,6 +59,10 @@ typedef const NoiseCfg MJB_AS4 &CNoise;
 #ifndef MJB_GSYNC_LOCAL
 #define MJB_GSYNC_LOCAL 0
 #endif
+// (the row-slot kernels with their frame in HBM, variants 12 / 13, keep this full wavefront-scope form: their lanes exchange frame data
+//  through global memory, and a wavefront's vector-memory operations complete in program order, so a load issued after the sync
+//  sees every store issued before it by any lane of the wave.  A workgroup-scope fence would emit the same code on gfx950 outside
+//  threadgroup-split mode -- no vmcnt wait -- and an agent-scope one costs microseconds per sync.)
 template <int G> DEVI void gsync()
 {
 #if MJB_GSYNC_LOCAL
@@ -3029,6 +3033,9 @@ template <int G, int CON, int DENSE> DEVI void forward_rest(const KernelParams M
 				fwd_constraint_newton<G, 4, false, true>(m, L, e, s.efc_Jg + (size_t)e.env * s.efc_Jg_stride);
 			}
 		});
+	} else if constexpr (CON >= 10 && CON <= 13 && G == 64) {
+		// up to 1024 rows: the row-slot solver (Newton: 10 / 12, CG: 11 / 13), all row data in the frame -- in LDS (10 / 11) or in HBM (12 / 13)
+		VIEW(P, compact, fwd_constraint_newton<G, 1, (CON & 1) != 0, false, true>(m, L, e));
 	} else if constexpr (CON >= 2 && CON <= 3 && G == 64) {
 		VIEW(P, compact, fwd_constraint_newton<G, (CON == 2 ? 1 : 2)>(m, L, e));
 	} else if constexpr (CON >= 6 && CON <= 8 && G == 64) {
@@ -3353,12 +3360,14 @@ template <int G> STAGE void ctrl_noise(CModel m, CLayout L, CNoise nz, const Env
 // chains, which is worth more than the spills cost (config 3: +31 % measured).
 // ROCm 7.2's LLVM can place a spill ahead of an exec restore and lose lanes (tools/check_spill_exec.py, `make lint`
 // guards every build): an earlier revision had to cap these kernels at 256 VGPRs because of it, and the CG variants (CON >= 6,
-// not a BASELINE workload) still are -- at 512 the allocator produced exactly that pattern in the 2-rows-per-lane CG kernel.
+// not a BASELINE workload) still are -- at 512 the allocator produced exactly that pattern in the 2-rows-per-lane CG kernel.  The
+// row-slot Newton kernels (10, 12) take the 512-register budget of the other Newton kernels: capped at 256 they were allocated 196 VGPRs +
+// 128 AGPRs anyway (one wave per SIMD) with 142 / 119 VGPRs spilled; the row-slot CG kernels (11, 13) fit 256.
 template <int G, int CON, int DENSE>
 #ifndef MJB_DEV_OCC
 #define MJB_DEV_OCC 1
 #endif
-__global__ void __launch_bounds__(256, (CON >= 6 ? 2 : (CON ? MJB_DEV_OCC : (G == 64 ? 4 : (G == 32 ? 2 : 1)))))
+__global__ void __launch_bounds__(256, ((CON >= 6 && CON != 10 && CON != 12) ? 2 : (CON ? MJB_DEV_OCC : (G == 64 ? 4 : (G == 32 ? 2 : 1)))))
     mjb_step_kernel(const KernelParams MJB_AS4 *__restrict__ P, const int mode_arg, const int nsteps,
                     const unsigned int step0, const int epb, const int frame_bytes, const int chunk, const int env_lo, const int env_hi)
 {
@@ -3508,8 +3517,12 @@ __global__ void __launch_bounds__(256, (CON >= 6 ? 2 : (CON ? MJB_DEV_OCC : (G =
 			}
 		}
 	}
-	e.f = reinterpret_cast<double *>(smem + (size_t)slot * frame_bytes);
-	e.fi = reinterpret_cast<int *>(e.f + L.ndouble);
+	// (variants 12 / 13: the frame is the env's slot of DevState::frame_ws, set per env below; no dynamic LDS)
+	constexpr bool HBMF = CON == 12 || CON == 13;
+	if constexpr (!HBMF) {
+		e.f = reinterpret_cast<double *>(smem + (size_t)slot * frame_bytes);
+		e.fi = reinterpret_cast<int *>(e.f + L.ndouble);
+	}
 
 	// Constrained kernels, long fused launches (chunk > 0): the K steps of an env are cut into chunks and every (chunk, env) pair is
 	// a work item handed out from a counter in chunk-major order; an item waits for its env's previous chunk (taken nenv items
@@ -3543,8 +3556,14 @@ __global__ void __launch_bounds__(256, (CON >= 6 ? 2 : (CON ? MJB_DEV_OCC : (G =
 		if constexpr (DENSE == 0) e.mp = s.env_mass ? s.env_mass + (size_t)e.env * (7 * m.nbody + m.nv + m.ntendon + 1) : nullptr;
 		else e.mp = nullptr;  // (batches with per-env masses never run the dense kernels)
 		double *ws = s.frame_ws ? s.frame_ws + (size_t)e.env * s.frame_stride : nullptr;
+		if constexpr (HBMF) {
+			e.f = ws;
+			e.fi = reinterpret_cast<int *>(ws + L.ndouble);
+		}
 
-		if (mode == MJB_MODE_STEP2 || (DENSE == 0 && CON != 9 && (mode == MJB_MODE_STEP21 || mode == MJB_MODE_RKMID || mode == MJB_MODE_RKLAST))) {
+		if (HBMF && (mode == MJB_MODE_STEP2 || mode == MJB_MODE_STEP21 || mode == MJB_MODE_RKMID || mode == MJB_MODE_RKLAST)) {
+			// resume: the full frame IS the workspace; the (possibly host-modified) state goes on top below
+		} else if (mode == MJB_MODE_STEP2 || (DENSE == 0 && CON != 9 && (mode == MJB_MODE_STEP21 || mode == MJB_MODE_RKMID || mode == MJB_MODE_RKLAST))) {
 			// resume: full frame from the workspace, then the (possibly host-modified) state on top
 			// (eight loads in flight per lane: the copy is a chain of HBM round trips otherwise -- a split step of ONE callback env
 			//  is pure latency, profiles/r03_callback_path.txt)
@@ -3688,7 +3707,7 @@ __global__ void __launch_bounds__(256, (CON >= 6 ? 2 : (CON ? MJB_DEV_OCC : (G =
 		store_state<G>(m, L, s, e);
 		if (P->hw.n > 0)  // the device-side hwsim stage writes qfrc_applied: keep mjData's view of it current
 			copy_out<G>(s.qfrc_applied + (size_t)e.env * m.nv, e.f + L.qfrc_applied, m.nv, e.lane);
-		if (ws && (mode != MJB_MODE_STEP || s.keep_frame)) {
+		if (!HBMF && ws && (mode != MJB_MODE_STEP || s.keep_frame)) {
 #pragma unroll 8
 			for (int k = e.lane; k < L.ndouble; k += G) ws[k] = e.f[k];
 			int *wsi = reinterpret_cast<int *>(ws + L.ndouble);
@@ -3747,7 +3766,8 @@ int launch_g(const KernelParams *Pdev, const FrameLayout &L, int env_lo, int env
              int epb, void *stream, int chunk = 0)
 {
 	const int nenv = env_hi - env_lo;
-	const int frame_bytes = ((L.ndouble * 8 + L.nint * 4) + 15) & ~15;
+	constexpr bool HBMF = CON == 12 || CON == 13;  // (the frame lives in DevState::frame_ws)
+	const int frame_bytes = HBMF ? 0 : ((L.ndouble * 8 + L.nint * 4) + 15) & ~15;
 	const int maxlds = mjb_max_lds_bytes();
 	int threads = epb * G;
 	if (threads > 256) {
@@ -3781,6 +3801,7 @@ int launch_g(const KernelParams *Pdev, const FrameLayout &L, int env_lo, int env
 // The kernel variants are compiled in slices, one translation unit per slice (-DMJB_GROUP=0..4: minutes of device code
 // generation run in parallel); without MJB_GROUP the whole file is one unit (profiling and development builds).
 //   0: models without constraint rows + the dispatcher   1: PGS (1, 5)   2: Newton 1 / 2 rows per lane   3: Newton 4 rows   4: CG
+//   7 / 8: the row-slot Newton / CG kernels (10, 11 with the frame in LDS; 12, 13 with it in HBM)
 //   5: the 256-register PGS variant (9) on its own: out-of-line helpers shared with the 512-register kernels would be compiled
 //      for their budget and cost it its second wave per SIMD, or spills (760 instead of 576 in the same unit as variants 1 / 5)
 #ifndef MJB_GROUP
@@ -3792,6 +3813,8 @@ int mjb_launch_group2(const KernelParams *Pdev, const FrameLayout &L, int env_lo
 int mjb_launch_group3(const KernelParams *Pdev, const FrameLayout &L, int env_lo, int nenv, int mode, int nsteps, unsigned int step0, int epb, int constrained, void *stream, int chunk);
 int mjb_launch_group4(const KernelParams *Pdev, const FrameLayout &L, int env_lo, int nenv, int mode, int nsteps, unsigned int step0, int epb, int constrained, void *stream, int chunk);
 int mjb_launch_group5(const KernelParams *Pdev, const FrameLayout &L, int env_lo, int nenv, int mode, int nsteps, unsigned int step0, int epb, int constrained, void *stream, int chunk);
+int mjb_launch_group7(const KernelParams *Pdev, const FrameLayout &L, int env_lo, int nenv, int mode, int nsteps, unsigned int step0, int epb, int constrained, void *stream, int chunk);
+int mjb_launch_group8(const KernelParams *Pdev, const FrameLayout &L, int env_lo, int nenv, int mode, int nsteps, unsigned int step0, int epb, int constrained, void *stream, int chunk);
 
 #if !defined(MJB_DEV_ONLY_CON)
 #if MJB_HAS_GROUP(1)
@@ -3826,6 +3849,22 @@ int mjb_launch_group4(const KernelParams *Pdev, const FrameLayout &L, int env_lo
 	if (constrained == 7) return launch_g<64, 7>(Pdev, L, env_lo, nenv, mode, nsteps, step0, epb, stream, chunk);
 	if (constrained == 8) return launch_g<64, 8>(Pdev, L, env_lo, nenv, mode, nsteps, step0, epb, stream, chunk);
 	return launch_g<64, 6>(Pdev, L, env_lo, nenv, mode, nsteps, step0, epb, stream, chunk);
+}
+#endif
+#if MJB_HAS_GROUP(7)
+// the row-slot solver (up to 1024 rows) on a frame in LDS: Newton (10), CG (11)
+int mjb_launch_group7(const KernelParams *Pdev, const FrameLayout &L, int env_lo, int nenv, int mode, int nsteps, unsigned int step0, int epb, int constrained, void *stream, int chunk)
+{
+	if (constrained == 11) return launch_g<64, 11>(Pdev, L, env_lo, nenv, mode, nsteps, step0, epb, stream, chunk);
+	return launch_g<64, 10>(Pdev, L, env_lo, nenv, mode, nsteps, step0, epb, stream, chunk);
+}
+#endif
+#if MJB_HAS_GROUP(8)
+// ... on a frame in HBM (the layout exceeds one CU's LDS): Newton (12), CG (13) -- a slice of its own only to build in parallel
+int mjb_launch_group8(const KernelParams *Pdev, const FrameLayout &L, int env_lo, int nenv, int mode, int nsteps, unsigned int step0, int epb, int constrained, void *stream, int chunk)
+{
+	if (constrained == 13) return launch_g<64, 13>(Pdev, L, env_lo, nenv, mode, nsteps, step0, epb, stream, chunk);
+	return launch_g<64, 12>(Pdev, L, env_lo, nenv, mode, nsteps, step0, epb, stream, chunk);
 }
 #endif
 #endif
@@ -4031,6 +4070,8 @@ int mjb_launch_step(const KernelParams *Pdev, const FrameLayout &L, int env_lo, 
 	if (constrained == 4) return mjb_launch_group3(Pdev, L, env_lo, nenv, mode, nsteps, step0, envs_per_block, constrained, stream, chunk);
 	if (constrained >= 6 && constrained <= 8) return mjb_launch_group4(Pdev, L, env_lo, nenv, mode, nsteps, step0, envs_per_block, constrained, stream, chunk);
 	if (constrained == 9) return mjb_launch_group5(Pdev, L, env_lo, nenv, mode, nsteps, step0, envs_per_block, constrained, stream, chunk);
+	if (constrained == 10 || constrained == 11) return mjb_launch_group7(Pdev, L, env_lo, nenv, mode, nsteps, step0, envs_per_block, constrained, stream, chunk);
+	if (constrained == 12 || constrained == 13) return mjb_launch_group8(Pdev, L, env_lo, nenv, mode, nsteps, step0, envs_per_block, constrained, stream, chunk);
 	return mjb_launch_group1(Pdev, L, env_lo, nenv, mode, nsteps, step0, envs_per_block, constrained, stream, chunk);
 #endif
 }

@@ -60,6 +60,14 @@ class CompiledModel:
     def frame_doubles(self):
         return self.lib.mjb_frame_doubles(self.ptr)
 
+    def frame_info(self):
+        """(the row-slot Newton / CG solver runs, the full frame lives in HBM, the fused frame lives in HBM) -- mjb_model_frame_info."""
+        full, fused = C.c_int(0), C.c_int(0)
+        slot = self.lib.mjb_model_frame_info(self.ptr, C.byref(full), C.byref(fused))
+        if slot < 0:
+            raise EngineError("mjb_model_frame_info failed: " + self.lib.mjb_last_error().decode())
+        return bool(slot), bool(full.value), bool(fused.value)
+
     def close(self):
         if getattr(self, "ptr", None):
             self.lib.mjb_free_model(self.ptr)
