@@ -11,9 +11,19 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
+def no_gpu_spawn_env():
+    """The environment of a bare multi-rank launch whose every rank must reach its own device check.  torch.distributed.run stops the
+    surviving ranks at its first poll after one rank exits (every 0.1 s by default): a rank that reached its check while its sibling was
+    still importing torch got the sibling killed before it could say "no GPU visible" -- on a loaded machine, two launches in 24 printed
+    the message once.  Polling every 30 s (PET_MONITOR_INTERVAL: torchrun's --monitor-interval) lets both ranks get there first."""
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
+    env["PET_MONITOR_INTERVAL"] = "30"
+    return env
+
+
 @pytest.mark.skipif(torch.cuda.is_available(), reason="CPU-only check of the spawn path")
 def test_bare_multi_gpu_launch_spawns_ranks():
-    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
+    env = no_gpu_spawn_env()
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "0"],
                        env=env, capture_output=True, text=True, timeout=300)
     assert p.returncode != 0 and p.returncode != 2
@@ -33,7 +43,7 @@ def test_config_arguments_reach_every_spawned_rank():
     """`python bench.py --config 3 --gpus 2 ...`: the self-spawn forwards the whole command line, so both ranks parse
     `--config 3` (a rank that lost it would still die on "no GPU", so the argument echo is checked through an unknown flag:
     argparse's error names it on every rank)."""
-    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
+    env = no_gpu_spawn_env()
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--config", "3", "--gpus", "2", "--steps", "1", "--warmup", "0"],
                        env=env, capture_output=True, text=True, timeout=300)
     assert p.returncode != 0 and p.stderr.count("no GPU visible; the engine has no CPU fallback") == 2, p.stderr[-2000:]

@@ -10,7 +10,9 @@ import pytest
 from mujoco_ros_pkgs_amd import mjcf
 
 
-def random_model(seed):
+def random_model(seed, large=False):
+    """large: capacities of 96 contacts and 1024 rows (nefcmax > 256: the row-slot Newton / CG solver); without it every seed's XML is
+    what it always was."""
     rng = np.random.default_rng(seed)
     solver = ["Newton", "PGS", "CG"][seed % 3]
     cone = ["pyramidal", "elliptic"][(seed // 3) % 2]
@@ -148,7 +150,7 @@ def random_model(seed):
         integ = "Euler"
     xml = f'''<mujoco model="random{seed}"><compiler angle="radian"/>
 <option timestep="0.002" solver="{solver}" cone="{cone}" integrator="{integ}" iterations="{100 if solver == "CG" else 40}" tolerance="{"1e-10" if solver == "CG" else "0"}"/>
-<size nconmax="16" njmax="120"/>
+<size nconmax="{96 if large else 16}" njmax="{1024 if large else 120}"/>
 <worldbody><geom name="floor" type="plane" size="3 3 0.1"/>{world}</worldbody>
 <tendon>{"".join(tendons)}</tendon><actuator>{"".join(acts)}</actuator><equality>{"".join(eqs)}</equality>
 <contact>{"".join(pairs)}</contact><sensor>{"".join(sens)}</sensor></mujoco>'''
@@ -174,17 +176,51 @@ def test_random_models_load_and_step_on_the_oracle(oracle_built):
     assert kinds == {0, 1, 2, 3}
 
 
+def _compile_unless_pgs_refuses(engine, m):
+    """The compiled model; a PGS model beyond its caps skips, while Newton and CG take every model up to 1024 rows and any frame size."""
+    try:
+        return engine.CompiledModel(m)
+    except engine.EngineError as ex:
+        if int(m["solver"]) == 0 and ("one env per wavefront" in str(ex) or "exceeds one CU" in str(ex)):
+            pytest.skip(str(ex))
+        raise
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("seed", SEEDS)
 def test_gpu_random_model_matches_oracle(oracle_built, seed):
     from mujoco_ros_pkgs_amd import engine
     m = mjcf.compile_xml_string(random_model(seed))
-    try:
-        cm = engine.CompiledModel(m)
-    except engine.EngineError as ex:
-        if "one env per wavefront" in str(ex) or "exceeds one CU" in str(ex):
-            pytest.skip(str(ex))
-        raise
+    _random_model_matches_oracle(oracle_built, engine, m, _compile_unless_pgs_refuses(engine, m), seed)
+
+
+def slot_seeds(generator, count):
+    """The first `count` Newton / CG seeds (seed % 3 != 1) whose large=True model has more than 256 rows of capacity: the row-slot solver.
+    (Models with few geoms cannot: their worst case of contacts is small.)"""
+    seeds, s = [], 0
+    while len(seeds) < count:
+        if s % 3 != 1 and mjcf.compile_xml_string(generator(s, large=True))["nefcmax"] > 256:
+            seeds.append(s)
+        s += 1
+    return seeds
+
+
+# Newton / CG seeds of random_model(large=True): the row-slot solver under every integrator, actuator, tendon, sensor and entry point
+SLOT_SEEDS = slot_seeds(random_model, int(os.environ.get("MJB_RANDOM_SLOT_MODELS", "24")))
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("seed", SLOT_SEEDS)
+def test_gpu_random_model_slot_matches_oracle(oracle_built, seed):
+    from mujoco_ros_pkgs_amd import engine
+    m = mjcf.compile_xml_string(random_model(seed, large=True))
+    assert m["nefcmax"] > 256, m["nefcmax"]
+    cm = engine.CompiledModel(m)
+    assert cm.frame_info()[0]
+    _random_model_matches_oracle(oracle_built, engine, m, cm, seed)
+
+
+def _random_model_matches_oracle(oracle_built, engine, m, cm, seed):
     n = 16
     rng = np.random.default_rng(500 + seed)
     qpos = np.tile(np.asarray(m["qpos0"], float), (n, 1))
@@ -378,13 +414,14 @@ def test_gpu_random_model_matches_oracle(oracle_built, seed):
                 (seed, "env overrides", e, float(np.abs(q5[e] - np.array(de.qpos)).max()), float(np.abs(v5[e] - np.array(de.qvel)).max()))
 
 
-def random_pile(seed):
+def random_pile(seed, large=False):
     """Free bodies dropped into one another over a floor: many contacts of every primitive pair (box - box above all), row counts up to the
-    solvers' capacities -- the lean / wide / row-capped frames of the Newton kernels and the two-rows-per-lane PGS."""
+    solvers' capacities -- the lean / wide / row-capped frames of the Newton kernels and the two-rows-per-lane PGS.  large: 6 - 10 bodies,
+    capacities of 128 contacts and 1024 rows (the row-slot Newton solver); without it every seed's XML is what it always was."""
     rng = np.random.default_rng(10_000 + seed)
     solver = ["Newton", "PGS", "Newton"][seed % 3]
     cone = ["pyramidal", "elliptic"][(seed // 3) % 2]
-    nb = int(rng.integers(3, 9 if solver == "Newton" else 6))
+    nb = int(rng.integers(6, 11) if large else rng.integers(3, 9 if solver == "Newton" else 6))
     bodies = []
     for b in range(nb):
         q = rng.normal(size=4)
@@ -401,9 +438,12 @@ def random_pile(seed):
         bodies.append(f'<body name="p{b}" pos="{rng.uniform(-0.08, 0.08):.3f} {rng.uniform(-0.08, 0.08):.3f} {rng.uniform(0.03, 0.25):.3f}" '
                       f'quat="{q[0]:.4f} {q[1]:.4f} {q[2]:.4f} {q[3]:.4f}"><freejoint/>{g}</body>')
     ncon = int(rng.choice([16, 32, 48]))
+    njmax = int(rng.choice([64, 128, 250]))
+    if large:
+        ncon, njmax = 128, 1024
     return f'''<mujoco model="pile{seed}"><compiler angle="radian"/>
 <option timestep="0.002" solver="{solver}" cone="{cone}" iterations="40" tolerance="0"/>
-<size nconmax="{ncon}" njmax="{int(rng.choice([64, 128, 250]))}"/>
+<size nconmax="{ncon}" njmax="{njmax}"/>
 <worldbody><geom name="floor" type="plane" size="3 3 0.1"/><geom name="wall" type="box" size="0.3 0.02 0.1" pos="0 0.15 0.1"/>{"".join(bodies)}</worldbody></mujoco>'''
 
 
@@ -424,12 +464,25 @@ def test_random_piles_load(oracle_built):
 def test_gpu_random_pile_matches_oracle(oracle_built, seed):
     from mujoco_ros_pkgs_amd import engine
     m = mjcf.compile_xml_string(random_pile(seed))
-    try:
-        cm = engine.CompiledModel(m)
-    except engine.EngineError as ex:
-        if "one env per wavefront" in str(ex) or "exceeds one CU" in str(ex):
-            pytest.skip(str(ex))
-        raise
+    _random_pile_matches_oracle(oracle_built, engine, m, _compile_unless_pgs_refuses(engine, m), seed)
+
+
+# Newton seeds of random_pile(large=True)
+SLOT_PILES = slot_seeds(random_pile, int(os.environ.get("MJB_RANDOM_SLOT_PILES", "16")))
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("seed", SLOT_PILES)
+def test_gpu_random_pile_slot_matches_oracle(oracle_built, seed):
+    from mujoco_ros_pkgs_amd import engine
+    m = mjcf.compile_xml_string(random_pile(seed, large=True))
+    assert m["nefcmax"] > 256, m["nefcmax"]
+    cm = engine.CompiledModel(m)
+    assert cm.frame_info()[0]
+    _random_pile_matches_oracle(oracle_built, engine, m, cm, seed)
+
+
+def _random_pile_matches_oracle(oracle_built, engine, m, cm, seed):
     n = 8
     rng = np.random.default_rng(700 + seed)
     qpos = np.tile(np.asarray(m["qpos0"], float), (n, 1))
