@@ -9,7 +9,11 @@ N > 1 -- by the RCCL all-gather of ``sensordata`` + the 16-double metrics all-re
 issued on a side stream so that they overlap the next launch.  Inputs are resident in HBM before the timed region.
 Rank 0 prints ONE JSON line.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--config 2|3|5] [--substeps S] [--envs E] [--lanes G] [--dump-outputs DIR]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--config 2|3|5] [--substeps S] [--envs E] [--lanes G] [--dump-outputs DIR] [--full]
+
+A plain run does only what the headline needs: set up, W warm-up steps, K timed steps, the dump, the line.  ``--full`` adds what
+takes runs of its own: the `roofline` block (five single-launch kernel samples), the CPU baselines (`cpu_baseline`) and, on a
+default single-GPU run, the other workloads (`other_configs`); ``--no-cpu-baseline`` / ``--no-other-configs`` drop those two again.
 
 With N > 1 and no torch.distributed environment the script spawns its own ranks (one process per GPU through
 ``python -m torch.distributed.run`` on 127.0.0.1); under torchrun it uses the environment it is given.
@@ -287,7 +291,7 @@ def kernel_form(batch):
 
 def measure_other_config(name, device, launches=5, with_cpu=True, envs=None, substeps=None, lane_env=None, tag=None, sens_every=False, split=None):
     """One of the other BASELINE workloads (franka_table = configs[2], shadow_hand_grasp = configs[4]'s per-GPU shard, shadow_hand_like =
-    its light predecessor), measured in this process after the headline timing so that the DRIVER's record carries it (VERDICT r02
+    its light predecessor), measured by a --full run in this process after the headline timing so that its line carries it (VERDICT r02
     #3a): `launches` timed fused launches bracketed by synchronisation (five, like the standalone `--config N` run: config 3's first
     launches after the synthetic start are its heaviest, three of them read 2 % low), then five single-launch kernel samples; the
     device-side ncon / nefc / iteration counters run over exactly the timed launches; the CPU oracle legs on the same workload."""
@@ -383,8 +387,10 @@ def main():
     ap.add_argument("--solver", default="", choices=["", "PGS", "Newton"], help="override the model's constraint solver")
     ap.add_argument("--nefcmax", type=int, default=0, help="override the model's constraint-row capacity")
     ap.add_argument("--nconmax", type=int, default=0, help="override the model's contact capacity")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-other-configs", action="store_true", help="skip the configs 3 / 5 lines a default single-GPU run appends")
+    ap.add_argument("--full", action="store_true", help="after the line's own steps, also measure the roofline block (kernel samples), the CPU "
+                    "baselines and, on a default single-GPU run, the other workloads (other_configs)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(with --full) skip the CPU baselines")
+    ap.add_argument("--no-other-configs", action="store_true", help="(with --full) skip the other_configs lines a default single-GPU run appends")
     ap.add_argument("--dist-timeout", type=float, default=180.0, help="seconds a collective may wait for a missing rank before the run fails with an error line")
     ap.add_argument("--dry-ranks", type=int, default=0, help="CI: run the N-rank control flow (rendezvous, overlapped exchange, fence, max-over-ranks "
                     "timing, the rank-0 line) under gloo with a stub batch and thread streams -- no GPU, the value means nothing")
@@ -554,7 +560,7 @@ def dry_run(args):
             "steps": args.steps, "warmup": args.warmup, "ms_per_step": 1e3 * elapsed / args.steps, "higher_is_better": True,
             "scaling": "weak", "vs_baseline": None, "dtype": "f64", "data": "DRY RUN: stub batch, gloo, thread streams -- no GPU, the value means nothing",
             "dry_ranks": world, "exchange_ok": ok, "rank_ms_per_step": {"min": 1e3 * min(per_rank) / args.steps, "max": 1e3 * max(per_rank) / args.steps},
-            "exchange_ms": xch.last_ms(), "cpu_baseline_leg": world == 1 and not args.no_cpu_baseline,  # (gpu_run's guard: rank 0 at N = 1 only)
+            "exchange_ms": xch.last_ms(), "cpu_baseline_leg": args.full and world == 1 and not args.no_cpu_baseline,  # (gpu_run's guard: --full, rank 0 at N = 1 only)
             "config": {"workload": "dry run", "rccl_ranks": 0, "gloo_ranks": dist.get_world_size(), "shard": [env_lo, env_lo + E]}})
     dist.barrier()
     rt.close()
@@ -664,9 +670,8 @@ def gpu_run(args, name):
     finite = bool(np.all(np.isfinite(batch.get("qpos")))) and bool(torch.isfinite(sens_all).all())
     resets = batch.warning_count()  # mj_check* auto-resets of THIS rank (must be 0 on config 2)
 
-    # dominant-kernel duration measured with HIP events on the engine's own stream: 5 single-launch samples
-    samples = sorted(batch.time_steps(S, 1) for _ in range(5))
-    kern_ms = samples[len(samples) // 2]
+    # (--full) dominant-kernel duration measured with HIP events on the engine's own stream: 5 single-launch samples
+    samples = sorted(batch.time_steps(S, 1) for _ in range(5)) if args.full else None
     kname, kform = kernel_form(batch)
 
     if rank == 0:
@@ -690,8 +695,9 @@ def gpu_run(args, name):
             "rank_ms_per_step": {"min": 1e3 * min(per_rank) / args.steps, "max": 1e3 * max(per_rank) / args.steps},
             "exchange_ms": xch.last_ms(),
             "metrics": metrics,
-            "roofline": roofline_block(name, WORKLOAD_TAG.get(name, str(cfgno)), solver_tag, E, S, samples, kname),
         }
+        if samples is not None:
+            out["roofline"] = roofline_block(name, WORKLOAD_TAG.get(name, str(cfgno)), solver_tag, E, S, samples, kname)
         if stats is not None:
             out["workload_stats"] = stats
             out["config"]["contactfull"], out["config"]["cnstrfull"] = batch.warning("contactfull"), batch.warning("cnstrfull")
@@ -699,7 +705,7 @@ def gpu_run(args, name):
         out["config"]["fused_frame"] = ("default", "default", "wide (up to 128 rows in LDS, two per lane; as many as let three frames share a CU)")[batch.fused_frame()[0]]
         default_run = world == 1 and not (args.config or args.model or args.solver or args.nefcmax or args.nconmax or args.envs or
                                           args.substeps or args.lanes or args.epb or args.lane_env != "auto")
-        if default_run and not args.no_other_configs:
+        if args.full and default_run and not args.no_other_configs:
             # the other BASELINE workloads, same process, same box (configs[2] and the per-GPU shard of configs[4])
             out["other_configs"] = {}
             for xtag, xe, xs, xmode in CONFIG2_EXTRAS:
@@ -717,7 +723,7 @@ def gpu_run(args, name):
                     out["other_configs"][WORKLOAD_TAG[other]] = measure_other_config(other, local_rank, with_cpu=not args.no_cpu_baseline)
                 except Exception as exc:  # never let an extra take the headline line down
                     out["other_configs"][WORKLOAD_TAG[other]] = {"error": f"{type(exc).__name__}: {exc}"}
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(name, model, noise_std)
         emit_line(real_stdout, out)
     if xch.active:

@@ -80,7 +80,7 @@ def _run_bench(*argv, timeout=300):
 
 @pytest.mark.parametrize("ranks", [1, 2, 4, 8])
 def test_dry_ranks_print_one_line_from_rank_zero(ranks):
-    p, lines = _run_bench("--dry-ranks", str(ranks), "--steps", "3", "--warmup", "1")
+    p, lines = _run_bench("--dry-ranks", str(ranks), "--steps", "3", "--warmup", "1", "--full")
     assert p.returncode == 0, p.stderr[-3000:]
     assert len(lines) == 1 and p.stdout.count("\n") == 1      # ONE line on stdout (gloo's banners went to stderr)
     line = lines[0]
@@ -92,6 +92,17 @@ def test_dry_ranks_print_one_line_from_rank_zero(ranks):
     assert abs(line["value"] - ranks * 64 * 10 * 3 / (line["ms_per_step"] * 3e-3)) < 1e-6 * line["value"]   # whole-job aggregate
     assert line["config"]["gloo_ranks"] == ranks              # what the process group says, not the environment variable
     assert line["cpu_baseline_leg"] is (ranks == 1)           # the CPU leg runs on rank 0 at N = 1 only
+
+
+@pytest.mark.parametrize("ranks", [1, 2])
+def test_plain_dry_run_has_no_cpu_leg(ranks):
+    """Without --full the line carries the headline alone: no rank runs the CPU baselines, N = 1 included."""
+    p, lines = _run_bench("--dry-ranks", str(ranks), "--steps", "3", "--warmup", "1")
+    assert p.returncode == 0 and len(lines) == 1, p.stderr[-3000:]
+    line = lines[0]
+    assert line["n_gpus"] == ranks and line["steps"] == 3 and line["warmup"] == 1 and line["exchange_ok"] is True
+    assert line["cpu_baseline_leg"] is False
+    assert abs(line["value"] - ranks * 64 * 10 * 3 / (line["ms_per_step"] * 3e-3)) < 1e-6 * line["value"]
 
 
 def test_world_size_mismatch_fails_the_line():
@@ -146,6 +157,25 @@ def test_dump_outputs_samples_the_same_envs_within_the_budget(tmp_path):
     assert np.array_equal(x["env_index"], y["env_index"]) and np.all(np.diff(i) > 0)     # fixed seed: the same rows every time
     assert np.array_equal(x["a"], a[i]) and np.array_equal(x["b"], b[i]) and np.array_equal(x["m"], np.ones(16))
     assert bench.dump_outputs(str(tmp_path / "z"), {"a": a}) == 2000 and np.array_equal(_load_dump(tmp_path / "z")["a"], a)
+
+
+@pytest.mark.gpu
+def test_plain_run_is_the_headline_alone_and_full_adds_the_rest():
+    """A plain default run prints the headline line without the parts that take runs of their own; --full adds the roofline block
+    from its own five single-launch kernel samples (the CPU baselines and other_configs are dropped here by their flags)."""
+    p, lines = _run_bench("--steps", "1", "--warmup", "0", timeout=600)
+    assert p.returncode == 0 and len(lines) == 1, p.stderr[-3000:]
+    line = lines[0]
+    assert line["metric"] == "env_steps_per_sec" and line["unit"] == "env-steps/s" and line["higher_is_better"] is True and line["dtype"] == "f64"
+    assert line["config"]["envs_per_gpu"] == 4096 and line["config"]["physics_steps_per_launch"] == 1000
+    assert abs(line["value"] - 4096 * 1000 / (line["ms_per_step"] * 1e-3)) < 1e-6 * line["value"]
+    assert not {"roofline", "cpu_baseline", "other_configs"} & set(line)
+    p, lines = _run_bench("--steps", "1", "--warmup", "0", "--envs", "256", "--substeps", "20", "--full", "--no-cpu-baseline",
+                          "--no-other-configs", timeout=600)
+    assert p.returncode == 0 and len(lines) == 1, p.stderr[-3000:]
+    line = lines[0]
+    assert line["roofline"]["kernel_ms_samples"]["n"] == 5 and line["roofline"]["kernel_ms"] > 0
+    assert not {"cpu_baseline", "other_configs"} & set(line)
 
 
 @pytest.mark.gpu

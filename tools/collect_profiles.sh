@@ -8,8 +8,8 @@ args=("$@")
 out=$PWD/gpurun_out/prof_$tag
 rm -rf "$out"; mkdir -p "$out"
 export TMPDIR=/tmp
-python bench.py "${args[@]}" > "$out/bench_line.json" 2> "$out/bench_stderr.log"
-short=(--steps 3 --warmup 1 --no-cpu-baseline "${args[@]}")
+python bench.py --full "${args[@]}" > "$out/bench_line.json" 2> "$out/bench_stderr.log"
+short=(--steps 3 --warmup 1 --full --no-cpu-baseline "${args[@]}")
 rocprofv3 --kernel-trace --stats --output-format csv -d "$out/trace" -o bench -- python bench.py "${short[@]}" > "$out/bench_line_under_rocprof.json" 2> "$out/rocprof_trace.log"
 # counters in their own passes (no tracing domains alongside --pmc)
 rocprofv3 --pmc FETCH_SIZE --output-format csv -d "$out/pmc_fetch" -o p -- python bench.py "${short[@]}" > /dev/null 2> "$out/pmc_fetch.log"

@@ -7,7 +7,7 @@ out=$PWD/gpurun_out/gather_timeline
 rm -rf "$out"; mkdir -p "$out"
 export TMPDIR=/tmp
 MJB_BENCH_FORCE_GATHER=1 MASTER_PORT=29577 rocprofv3 --kernel-trace --memory-copy-trace --output-format csv -d "$out/trace" -o t -- \
-  python bench.py --steps 4 --warmup 1 --substeps 1000 --no-cpu-baseline --no-other-configs > "$out/bench_line.json" 2> "$out/stderr.log"
+  python bench.py --steps 4 --warmup 1 --substeps 1000 --full --no-cpu-baseline --no-other-configs > "$out/bench_line.json" 2> "$out/stderr.log"
 python - "$out" <<'PY'
 import csv, glob, sys
 out = sys.argv[1]

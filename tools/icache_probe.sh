@@ -6,7 +6,7 @@ out=$PWD/gpurun_out/icache; rm -rf "$out"; mkdir -p "$out"
 export TMPDIR=/tmp
 rocprofv3 -L 2>/dev/null | grep -o "SQC_[A-Z_]*\|SQ_IFETCH[A-Z_]*\|SQ_INST_LEVEL[A-Z_]*\|SQ_WAIT_INST[A-Z_]*" | sort -u > "$out/available.txt"
 for cfg in 2 3 5; do
-  short=(--steps 3 --warmup 1 --no-cpu-baseline --no-other-configs --config $cfg)
+  short=(--steps 3 --warmup 1 --full --no-cpu-baseline --no-other-configs --config $cfg)
   rocprofv3 --pmc SQC_ICACHE_REQ SQC_ICACHE_HITS SQC_ICACHE_MISSES SQC_ICACHE_MISSES_DUPLICATE --output-format csv -d "$out/c$cfg" -o p -- python bench.py "${short[@]}" > /dev/null 2> "$out/c$cfg.log"
   rocprofv3 --pmc SQ_IFETCH SQ_WAVE_CYCLES SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_INSTS_VALU SQ_INSTS_SALU --output-format csv -d "$out/d$cfg" -o p -- python bench.py "${short[@]}" > /dev/null 2> "$out/d$cfg.log"
   python - "$out" $cfg <<'PY'

@@ -5,7 +5,7 @@ set -u
 tag=$1; shift
 out=$PWD/gpurun_out/icache_$tag; rm -rf "$out"; mkdir -p "$out"
 export TMPDIR=/tmp
-short=(--steps 2 --warmup 1 --no-cpu-baseline --no-other-configs "$@")
+short=(--steps 2 --warmup 1 --full --no-cpu-baseline --no-other-configs "$@")
 rocprofv3 --pmc SQC_ICACHE_REQ SQC_ICACHE_HITS SQC_ICACHE_MISSES SQC_ICACHE_MISSES_DUPLICATE --output-format csv -d "$out/c" -o p -- python bench.py "${short[@]}" > /dev/null 2> "$out/c.log"
 rocprofv3 --pmc SQ_IFETCH SQ_WAVE_CYCLES SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_INSTS_VALU SQ_INSTS_SALU --output-format csv -d "$out/d" -o p -- python bench.py "${short[@]}" > /dev/null 2> "$out/d.log"
 rocprofv3 --pmc SQ_WAIT_ANY SQ_INSTS_VMEM SQ_INSTS_LDS SQ_INSTS_SMEM SQ_ACTIVE_INST_VALU SQ_WAIT_INST_LDS SQ_INST_CYCLES_VMEM --output-format csv -d "$out/e" -o p -- python bench.py "${short[@]}" > /dev/null 2> "$out/e.log"

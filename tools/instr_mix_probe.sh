@@ -3,7 +3,7 @@ set -u
 tag=$1; shift
 out=$PWD/gpurun_out/mix_$tag; rm -rf "$out"; mkdir -p "$out"
 export TMPDIR=/tmp
-short=(--steps 2 --warmup 1 --no-cpu-baseline --no-other-configs "$@")
+short=(--steps 2 --warmup 1 --full --no-cpu-baseline --no-other-configs "$@")
 i=0
 for pmc in "SQ_INSTS_VALU_INT32 SQ_INSTS_VALU_INT64 SQ_INSTS_VALU_CVT SQ_INSTS_VALU SQ_INSTS_VALU_ADD_F32 SQ_INSTS_VALU_FMA_F32 SQ_INSTS_VALU_MUL_F32 SQ_INSTS_VALU_TRANS_F32" "SQ_INSTS_LDS_LOAD SQ_INSTS_LDS_STORE SQ_INSTS_VSKIPPED SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_ACTIVE_INST_SCA SQ_ACTIVE_INST_MISC SQ_ACTIVE_INST_VMEM"; do
   i=$((i+1))

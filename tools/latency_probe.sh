@@ -6,7 +6,7 @@ set -u
 tag=$1; shift
 out=$PWD/gpurun_out/latency_$tag; rm -rf "$out"; mkdir -p "$out"
 export TMPDIR=/tmp
-short=(--steps 2 --warmup 1 --no-cpu-baseline --no-other-configs "$@")
+short=(--steps 2 --warmup 1 --full --no-cpu-baseline --no-other-configs "$@")
 i=0
 for pmc in "InstrFetchLatency" "LdsLatency" "VmemLatency" "SmemLatency" "SQ_INSTS_BRANCH SQ_INSTS_SALU SQ_INSTS_VALU SQ_WAVE_CYCLES SQ_IFETCH"; do
   i=$((i+1))

@@ -39,7 +39,7 @@ def bench(cfg, lib=None):
     env = dict(os.environ)
     if lib:
         env["MJB_LIBRARY"] = lib
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--config", str(cfg), "--no-cpu-baseline", "--no-other-configs"], env=env, capture_output=True, text=True)
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--config", str(cfg), "--full", "--no-cpu-baseline", "--no-other-configs"], env=env, capture_output=True, text=True)
     d = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])
     return d["roofline"]["kernel_ms"], d["value"], d.get("workload_stats", {})
 

@@ -76,7 +76,7 @@ if summary:
         summary["bench_config"] = cfg
         summary["envs"], summary["substeps"] = cfg.get("envs_per_gpu"), cfg.get("physics_steps_per_launch")
     summary["notes"] = ("rocprofv3 --pmc passes (FETCH_SIZE, WRITE_SIZE and two SQ passes, each its own run, no tracing "
-                        "domains) of `python bench.py --steps 3 --warmup 1 --no-cpu-baseline ...`; means over the step-kernel "
+                        "domains) of `python bench.py --steps 3 --warmup 1 --full --no-cpu-baseline ...`; means over the step-kernel "
                         "dispatches.  FETCH_SIZE / WRITE_SIZE are KiB (HBM bytes = value * 1024); per MI355X_MICROARCH.md "
                         "the gfx950 x2 correction applies to wide (16 B/lane) streaming reads only -- this kernel reads 8 B/lane, "
                         "uncalibrated, so the raw value is reported.")
