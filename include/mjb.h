@@ -38,13 +38,18 @@ enum { MJB_GEOM_PLANE = 0, MJB_GEOM_SPHERE = 2, MJB_GEOM_CAPSULE = 3, MJB_GEOM_B
 enum { MJB_INT_EULER = 0, MJB_INT_RK4 = 1, MJB_INT_IMPLICIT = 2, MJB_INT_IMPLICITFAST = 3 };
 /* mjtIntegrator.  implicitfast: qacc = (M - h D)^-1 (qfrc_smooth + qfrc_constraint) with D = d qfrc_smooth / d qvel without the Coriolis terms
  * (mjd_passive_vel + mjd_actuator_vel) -- accepted when D is a model constant and diagonal: joint damping, and the velocity terms of affine
- * actuator biases on joint transmissions (a velocity term in an affine GAIN, or tendon damping, makes mjb_compile refuse it).  mjINT_IMPLICIT
+ * actuator biases on joint transmissions (a velocity term in an affine GAIN, tendon damping, or a velocity term in the bias of an actuator on a
+ * tendon or a site makes mjb_compile refuse it).  mjINT_IMPLICIT
  * (the Coriolis derivatives, an LU factor) is refused. */
 enum { MJB_CONE_PYRAMIDAL = 0, MJB_CONE_ELLIPTIC = 1 };
 enum { MJB_SOL_PGS = 0, MJB_SOL_CG = 1, MJB_SOL_NEWTON = 2 };
 enum { MJB_GAIN_FIXED = 0, MJB_GAIN_AFFINE = 1 };
 enum { MJB_BIAS_NONE = 0, MJB_BIAS_AFFINE = 1 };
-enum { MJB_TRN_JOINT = 0, MJB_TRN_TENDON = 3 };  /* mjtTrn: joint and (fixed) tendon transmissions; jointinparent / slidercrank / site are refused */
+/* mjtTrn: joint (hinge / slide), fixed-tendon and site transmissions.  jointinparent on a hinge / slide joint is the joint transmission
+ * (the loader maps it); slider-crank (2) and body (5) are refused.  actuator_trnid[i][0] is the joint / tendon / site, actuator_trnid[i][1]
+ * the refsite of a site transmission (-1: none; MuJoCo's slot for it).  A site transmission's moment depends on the configuration: the
+ * kernels compute it at every forward evaluation (mj_transmission, mjTRN_SITE). */
+enum { MJB_TRN_JOINT = 0, MJB_TRN_TENDON = 3, MJB_TRN_SITE = 4 };
 enum { MJB_DYN_NONE = 0, MJB_DYN_INTEGRATOR = 1, MJB_DYN_FILTER = 2 };  /* mjtDyn (mjDYN_MUSCLE = 3, mjDYN_USER = 4 are refused) */
 enum { /* mjtDisableBit */
 	MJB_DSBL_CONSTRAINT = 1 << 0, MJB_DSBL_EQUALITY = 1 << 1, MJB_DSBL_FRICTIONLOSS = 1 << 2,

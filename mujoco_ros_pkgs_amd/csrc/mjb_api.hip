@@ -86,6 +86,7 @@ struct mjb_model {
 	std::vector<double> lim_d;     // [njnt + ntendon][24] limit items in pair_d's slots (mjb_dev.h)
 	std::vector<double> dof_act_mom;  // moment arm of entry t of the per-dof actuator lists (dof_act_adr / dof_act_id)
 	int act_tendon = 0;               // some actuator drives a tendon
+	std::vector<int> site_act;        // actuators with a site transmission, in actuator order (DevModel::site_act)
 	std::vector<double> damp_int;  // [nv] -diag(D) of the integrator's implicit matrix M + h diag(.): dof_damping (Euler) / implicitfast's constant velocity derivative
 	std::vector<int> lim_i;        // [njnt + ntendon][4]
 	int sens_ncopy[3] = { 0, 0, 0 }, sens_nslow[3] = { 0, 0, 0 }, sens_ncopy_max = 0;
@@ -384,6 +385,8 @@ void compute_layout(mjb_model *M, FrameLayout &L, bool compact, int jrows_req = 
 	off += d.nv;
 	L.rk = d.integrator == MJB_INT_RK4 ? off : -1;  // (persistent across the evaluations of one step)
 	off += d.integrator == MJB_INT_RK4 ? d.nq + 4 * d.nv + d.nsensordata + 1 + 2 * d.na : 0;  // X0 | sums | warmstart | the step's sensordata | t0 | act0 | sum B act_dot
+	L.act_mom = off;  // (alive from the transmission stage to actuation, across the overlays of every layout: own storage)
+	off += (int)M->site_act.size() * d.nv;
 	// transient scratch of the constrained kernels: ntri doubles for the packed dense triangle of the L'DL factor (nv <= 16, PGS:
 	// the J M^-1 rows; 16 < nv <= 32: the M^-1 solves of fwd_acceleration / Euler, solve_tri32), 128 for the box - box narrow phase
 	const int ntri = d.nefcmax <= 0 ? 0 : ((d.nv <= 16 && d.solver == MJB_SOL_PGS) ? 128 : ((d.nv > 16 && d.nv <= 32) ? 496 : 0));
@@ -543,7 +546,7 @@ void dump_layout(const mjb_model *M, const FrameLayout &L)
 	const std::pair<int, const char *> extra[] = { { L.MhB, "MhB" }, { L.qH, "qH" }, { L.qHdi, "qHdi" }, { L.nwt_M, "nwt_M" }, { L.nwt_H, "nwt_H" },
 		{ L.nwt_vec, "nwt_vec" }, { L.nwt_row, "nwt_row" }, { L.nwt_hc, "nwt_hc" }, { L.gravity, "gravity" }, { L.gfriction, "gfriction" },
 		{ L.eqparam, "eqparam" }, { L.cwrench, "cwrench" }, { L.kinloc, "kinloc" }, { L.crbbuf, "crbbuf" }, { L.eulerx, "eulerx" },
-		{ L.tri, "tri" }, { L.solvescr, "solvescr" }, { L.bbscr, "bbscr" } };
+		{ L.tri, "tri" }, { L.solvescr, "solvescr" }, { L.bbscr, "bbscr" }, { L.act_mom, "act_mom" } };
 	for (auto &x : extra)
 		if (x.first >= 0) dd.push_back({ x.first, std::string("*") + x.second });
 	ii.push_back({ L.iscratch, "*iscratch" });
@@ -974,13 +977,18 @@ mjb_model *mjb_compile(const mjb_model_desc *desc)
 	}
 	for (int i = 0; i < h.nu; i++) {
 		int j = h.actuator_trnid[2 * i];
+		const int r = h.actuator_trnid[2 * i + 1];
 		const bool okj = h.actuator_trntype[i] == MJB_TRN_JOINT && j >= 0 && j < h.njnt && h.jnt_type[j] >= MJB_JNT_SLIDE;
 		const bool okt = h.actuator_trntype[i] == MJB_TRN_TENDON && j >= 0 && j < h.ntendon;
-		if (!okj && !okt) {
-			fail(MJB_EUNSUPPORTED, "mjb_compile: actuator %d: joint transmission on hinge / slide joints and fixed-tendon transmission are supported", i);
+		// site transmission: the site, and no refsite (-1) or another site
+		const bool oks = h.actuator_trntype[i] == MJB_TRN_SITE && j >= 0 && j < h.nsite && (r == -1 || (r >= 0 && r < h.nsite && r != j));
+		if (!okj && !okt && !oks) {
+			fail(MJB_EUNSUPPORTED, "mjb_compile: actuator %d: joint transmission on hinge / slide joints, fixed-tendon and site transmissions "
+			                       "(refsite -1 or another site) are supported", i);
 			delete M;
 			return nullptr;
 		}
+		if (oks) M->site_act.push_back(i);
 	}
 	// velocity-group start of each dof (hinge/slide: itself; ball: first of 3; free: first of each triple)
 	M->dof_jstart.resize(h.nv);
@@ -1220,6 +1228,14 @@ mjb_model *mjb_compile(const mjb_model_desc *desc)
 			}
 			if (h.disableflags & MJB_DSBL_ACTUATION) continue;
 			const double bv = h.actuator_biastype[i] == MJB_BIAS_AFFINE ? h.actuator_biasprm[3 * i + 2] : 0.0, g = h.actuator_gear[6 * i];
+			if (h.actuator_trntype[i] == MJB_TRN_SITE) {
+				if (bv != 0) {  // (moment' bv moment depends on the configuration and is not diagonal)
+					fail(MJB_EUNSUPPORTED, "mjb_compile: integrator implicitfast with a velocity-dependent actuator on a site is not supported");
+					delete M;
+					return nullptr;
+				}
+				continue;
+			}
 			if (h.actuator_trntype[i] == MJB_TRN_TENDON) {
 				if (bv != 0) {  // (moment' bv moment couples the tendon's joints: not diagonal)
 					fail(MJB_EUNSUPPORTED, "mjb_compile: integrator implicitfast with a velocity-dependent actuator on a tendon is not supported");
@@ -1346,6 +1362,7 @@ mjb_model *mjb_compile(const mjb_model_desc *desc)
 	M->act_tendon = 0;
 	auto each_arm = [&](auto &&fn) {
 		for (int i = 0; i < h.nu; i++) {
+			if (h.actuator_trntype[i] == MJB_TRN_SITE) continue;  // (configuration-dependent: the kernels compute its moment, FrameLayout::act_mom)
 			const int id = h.actuator_trnid[2 * i];
 			if (h.actuator_trntype[i] == MJB_TRN_TENDON) {
 				M->act_tendon = 1;
@@ -1520,7 +1537,7 @@ mjb_batch *mjb_make_batch(const mjb_model *M, int nenv, int device)
 	size_t nt = M->M_rowdof.size() + M->M_coldof.size() + M->dof_depth.size() + M->dof_jstart.size() +
 	            M->body_rec.size() + M->body_rec2.size() + M->dof_rec.size() + M->fac_ops.size() + M->fac_beg.size() +
 	            M->body_dofmask.size() + M->body_submask.size() + M->M_dense.size() + M->M_sym.size() + M->body_anc.size() + M->dof_bodymask.size() + M->body_dofanc.size() + M->dof_rec2.size() + M->jnt_rec.size() + M->flv_hdr.size() + M->flv_rec.size() + M->flv_ent.size() + M->sens_copy.size() + M->sens_slow.size() + M->dof_act_adr.size() +
-	            M->dof_act_id.size() + M->pair_i.size() + M->lim_i.size() + 104;
+	            M->dof_act_id.size() + M->pair_i.size() + M->lim_i.size() + M->site_act.size() + 108;
 	size_t bytes_i = ((ni + nt) * sizeof(int) + 15) & ~size_t(15);
 	// (the lane = env tape starts on a 64-byte boundary of the blob: wide scalar loads)
 	const size_t o_damp = nd + M->pair_d.size() + M->lim_d.size() + M->sub_S.size();
@@ -1548,7 +1565,7 @@ mjb_batch *mjb_make_batch(const mjb_model *M, int nenv, int device)
 	size_t o_row = put(M->M_rowdof), o_col = put(M->M_coldof), o_dep = put(M->dof_depth), o_js = put(M->dof_jstart);
 	size_t o_br = put(M->body_rec), o_br2 = put(M->body_rec2), o_dr = put(M->dof_rec), o_fo = put(M->fac_ops),
 	       o_fb = put(M->fac_beg), o_dm = put(M->body_dofmask), o_sm = put(M->body_submask), o_md = put(M->M_dense), o_ms = put(M->M_sym), o_an = put(M->body_anc), o_db = put(M->dof_bodymask), o_sc = put(M->sens_copy), o_ss = put(M->sens_slow),
-	       o_aa = put(M->dof_act_adr), o_ai = put(M->dof_act_id), o_pi = put(M->pair_i), o_li = put(M->lim_i), o_da = put(M->body_dofanc), o_dr2 = put(M->dof_rec2), o_jr = put(M->jnt_rec), o_fh = put(M->flv_hdr), o_fr = put(M->flv_rec), o_fe = put(M->flv_ent);
+	       o_aa = put(M->dof_act_adr), o_ai = put(M->dof_act_id), o_pi = put(M->pair_i), o_li = put(M->lim_i), o_da = put(M->body_dofanc), o_dr2 = put(M->dof_rec2), o_jr = put(M->jnt_rec), o_fh = put(M->flv_hdr), o_fr = put(M->flv_rec), o_fe = put(M->flv_ent), o_sa = put(M->site_act);
 	if (nd) memcpy(hd, M->hdbl.data(), nd * sizeof(double));
 	memcpy(hd + nd, M->pair_d.data(), M->pair_d.size() * sizeof(double));
 	memcpy(hd + nd + M->pair_d.size(), M->lim_d.data(), M->lim_d.size() * sizeof(double));
@@ -1615,6 +1632,8 @@ mjb_batch *mjb_make_batch(const mjb_model *M, int nenv, int device)
 	dm.dof_damping_int = (mjb_cdptr)(dd + o_damp);
 	dm.dof_act_mom = (mjb_cdptr)(dd + o_mom);
 	dm.act_tendon = M->act_tendon;
+	dm.site_act = (mjb_ciptr)(di + o_sa);
+	dm.nsite_act = (int)M->site_act.size();
 	dm.sub_nt = M->sub_nt;
 	dm.le_tape = M->le_tape.empty() ? (mjb_cdptr) nullptr : (mjb_cdptr)(dd + o_tape);
 	dm.lim_i = (mjb_ciptr)(di + o_li);

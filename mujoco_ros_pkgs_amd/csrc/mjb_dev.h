@@ -81,6 +81,10 @@ struct DevModel {
 	// lane = env kernel (mjb_lane_env.hip): the model's numeric constants as ONE tape in the order the kernel consumes them --
 	// LeTapeHdr, LeTapeBody[nbody], LeTapeAct[nu] -- read by wide scalar loads off a single base address (NULL: no compiled-in topology)
 	mjb_cdptr le_tape;
+	// site transmissions (mjTRN_SITE): their actuators in actuator order.  Their moments depend on the configuration: the transmission stage
+	// computes one row of nv per actuator into the frame (FrameLayout::act_mom) at every forward evaluation (mjb_step.hip, site_transmission)
+	mjb_ciptr site_act;      // [nsite_act] actuator ids
+	int nsite_act;
 };
 
 // (64-byte records: one s_load_dwordx16 per half)
@@ -132,6 +136,7 @@ struct FrameLayout {
 	int hcrow;     // 1: the cone block of a contact sits at nwt_hc + hcd * (its first row) [hcd * rcap doubles]; 0: at nwt_hc + hcs * contact
 	int solvescr;  // [32]      pivot-row scratch of the dense M^-1 solves in fwd_acceleration / Euler (the factorisation uses crbbuf)
 	int bbscr;     // [216]     transient scratch of the box - box narrow phase (alive inside collision only)
+	int act_mom;   // [nsite_act * nv] moment rows of the site transmissions (transmission -> velocity stage -> actuation: own storage, never overlaid)
 	int ndouble;   // doubles per frame
 	int nint;      // ints per frame (follow the doubles)
 	int nstate;    // doubles in the persistent prefix

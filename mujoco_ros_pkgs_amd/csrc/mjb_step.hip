@@ -1621,12 +1621,130 @@ template <int G> DEVI void solve_tri32(CModel m, const Env &e, double *x, const 
 }
 
 // ------------------------------------------------------------------------------------------------
-// transmission (joint) : actuator_length
+// site transmissions (mj_transmission, mjTRN_SITE): lengths and moment rows from the site frames, cdof and subtree_com of the
+// position stage; the rows stay in the frame (act_mom) for the velocity stage and actuation.  Out of line, like rne_post: models
+// without site actuators reach neither these registers nor these instruction-cache lines.
+// ------------------------------------------------------------------------------------------------
+// mju_mat2Quat
+DEVI void mat2quat(double *q, const double *R)
+{
+	if (R[0] + R[4] + R[8] > 0) {
+		q[0] = 0.5 * sqrt(1 + R[0] + R[4] + R[8]);
+		q[1] = 0.25 * (R[7] - R[5]) / q[0];
+		q[2] = 0.25 * (R[2] - R[6]) / q[0];
+		q[3] = 0.25 * (R[3] - R[1]) / q[0];
+	} else if (R[0] > R[4] && R[0] > R[8]) {
+		q[1] = 0.5 * sqrt(1 + R[0] - R[4] - R[8]);
+		q[0] = 0.25 * (R[7] - R[5]) / q[1];
+		q[2] = 0.25 * (R[1] + R[3]) / q[1];
+		q[3] = 0.25 * (R[2] + R[6]) / q[1];
+	} else if (R[4] > R[8]) {
+		q[2] = 0.5 * sqrt(1 - R[0] + R[4] - R[8]);
+		q[0] = 0.25 * (R[2] - R[6]) / q[2];
+		q[1] = 0.25 * (R[1] + R[3]) / q[2];
+		q[3] = 0.25 * (R[5] + R[7]) / q[2];
+	} else {
+		q[3] = 0.5 * sqrt(1 - R[0] - R[4] + R[8]);
+		q[0] = 0.25 * (R[3] - R[1]) / q[3];
+		q[1] = 0.25 * (R[2] + R[6]) / q[3];
+		q[2] = 0.25 * (R[5] + R[7]) / q[3];
+	}
+	normalize4(q);
+}
+
+// column d of the Jacobian of point p on body b: (cdof_ang x (p - subtree_com[root]) + cdof_lin, cdof_ang), zero when dof d does not move b
+DEVI void point_jac(CModel m, CLayout L, const double *f, int b, const double *p, int d, double *jp, double *jr)
+{
+	const unsigned int w = (unsigned int)m.body_dofmask[2 * b + (d >> 5)];
+	if (!((w >> (d & 31)) & 1u)) {
+		jp[0] = jp[1] = jp[2] = jr[0] = jr[1] = jr[2] = 0;
+		return;
+	}
+	double cd[6], rc[3];
+	ld6(cd, f + L.cdof + 6 * d);
+	ld3(rc, f + L.subtree_com + 3 * m.body_rootid[b]);
+	const double off[3] = { p[0] - rc[0], p[1] - rc[1], p[2] - rc[2] };
+	cross3(jp, cd, off);
+	jp[0] += cd[3]; jp[1] += cd[4]; jp[2] += cd[5];
+	jr[0] = cd[0]; jr[1] = cd[1]; jr[2] = cd[2];
+}
+
+template <int G> __device__ __attribute__((noinline)) void site_transmission(CModel m, CLayout L, const EnvLite e)
+{
+	double *f = e.f;
+	const int nv = m.nv, lane = e.lane;
+	// lane = site actuator: length.  0 without a refsite; with one, g[0:3] . R_r' (p_s - p_r) + g[3:6] . subQuat(q_s, q_r), each half only
+	// when its gear is non-zero (the rotational half: DESIGN.md §2, convention from memory)
+	for (int r = lane; r < m.nsite_act; r += G) {
+		const int i = m.site_act[r], s = m.actuator_trnid[2 * i], rs = m.actuator_trnid[2 * i + 1];
+		double g[6];
+		for (int k = 0; k < 6; k++) g[k] = m.actuator_gear[6 * i + k];
+		double len = 0;
+		if (rs >= 0) {
+			double Rr[9];
+			ld9(Rr, f + L.site_xmat + 9 * rs);
+			if (g[0] != 0 || g[1] != 0 || g[2] != 0) {
+				double dp[3], v[3];
+				for (int k = 0; k < 3; k++) dp[k] = f[L.site_xpos + 3 * s + k] - f[L.site_xpos + 3 * rs + k];
+				matTvec3(v, Rr, dp);
+				len += dot3(v, g);
+			}
+			if (g[3] != 0 || g[4] != 0 || g[5] != 0) {
+				double Rs[9], qs[4], qr[4], v[3];
+				ld9(Rs, f + L.site_xmat + 9 * s);
+				mat2quat(qs, Rs);
+				mat2quat(qr, Rr);
+				quat_sub(v, qs, qr);
+				len += dot3(v, g + 3);
+			}
+		}
+		f[L.actuator_length + i] = len;
+	}
+	// lane = (site actuator, dof): moment entries.  The gear is a wrench w = (R g[0:3], R g[3:6]) in the frame R of the site (no refsite)
+	// or of the refsite; moment = (Jp_s - Jp_r)' w[0:3] + (Jr_s - Jr_r)' w[3:6] (no refsite: the site's Jacobian alone).  The refsite's
+	// rotation is not differentiated: moment != d length / d q when it turns (mj_transmission)
+	for (int k = lane; k < m.nsite_act * nv; k += G) {
+		const int r = k / nv, d = k - r * nv;
+		const int i = m.site_act[r], s = m.actuator_trnid[2 * i], rs = m.actuator_trnid[2 * i + 1];
+		double g[6], R[9], p[3], jp[3], jr[3], wl[3], wa[3];
+		for (int c = 0; c < 6; c++) g[c] = m.actuator_gear[6 * i + c];
+		ld9(R, f + L.site_xmat + 9 * (rs >= 0 ? rs : s));
+		ld3(p, f + L.site_xpos + 3 * s);
+		point_jac(m, L, f, m.site_bodyid[s], p, d, jp, jr);
+		if (rs >= 0) {
+			double pr[3], jpr[3], jrr[3];
+			ld3(pr, f + L.site_xpos + 3 * rs);
+			point_jac(m, L, f, m.site_bodyid[rs], pr, d, jpr, jrr);
+			for (int c = 0; c < 3; c++) {
+				jp[c] -= jpr[c];
+				jr[c] -= jrr[c];
+			}
+		}
+		matvec3(wl, R, g);
+		matvec3(wa, R, g + 3);
+		f[L.act_mom + k] = dot3(jp, wl) + dot3(jr, wa);
+	}
+	gsync<G>();
+}
+
+// actuator_velocity of the site actuators: moment . qvel
+template <int G> __device__ __attribute__((noinline)) void site_velocity(CModel m, CLayout L, const EnvLite e)
+{
+	double *f = e.f;
+	for (int r = e.lane; r < m.nsite_act; r += G) {
+		double v = 0;
+		for (int d = 0; d < m.nv; d++) v += f[L.act_mom + r * m.nv + d] * f[L.qvel + d];
+		f[L.actuator_velocity + m.site_act[r]] = v;
+	}
+}
+
+// ------------------------------------------------------------------------------------------------
+// transmission (joint, tendon; site: site_transmission) : actuator_length
 // ------------------------------------------------------------------------------------------------
 template <int G, bool CACHE = false> STAGE void transmission(CModel m, CLayout L, const Env &e)
 {
 	if constexpr (CACHE) {
-		if (!m.act_tendon) {
+		if (!m.act_tendon && !m.nsite_act) {
 			if (e.lane < m.nu) e.f[L.actuator_length + e.lane] = e.f[L.qpos + e.lc.u_qa] * e.lc.u_gear;
 			return;
 		}
@@ -1634,8 +1752,10 @@ template <int G, bool CACHE = false> STAGE void transmission(CModel m, CLayout L
 	for (int i = e.lane; i < m.nu; i += G) {
 		const int j = m.actuator_trnid[2 * i];
 		if (m.act_tendon && m.actuator_trntype[i] == MJB_TRN_TENDON) e.f[L.actuator_length + i] = e.f[L.ten_length + j] * m.actuator_gear[6 * i];  // (mj_tendon ran in com_pos)
+		else if (m.nsite_act && m.actuator_trntype[i] == MJB_TRN_SITE) continue;
 		else e.f[L.actuator_length + i] = e.f[L.qpos + m.jnt_qposadr[j]] * m.actuator_gear[6 * i];
 	}
+	if (m.nsite_act) site_transmission<G>(m, L, lite(e));
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1729,7 +1849,7 @@ template <int G, bool OBL> STAGE void com_vel(CModel m, CLayout L, const Env &e)
 		}
 		st6(f + L.cdof_dot + 6 * d, r);
 	}
-	if (OBL && !m.act_tendon) {
+	if (OBL && !m.act_tendon && !m.nsite_act) {
 		if (lane < m.nu) f[L.actuator_velocity + lane] = e.lc.u_gear * qvel[e.lc.u_da];
 	} else {
 		for (int i = lane; i < m.nu; i += G) {
@@ -1739,9 +1859,12 @@ template <int G, bool OBL> STAGE void com_vel(CModel m, CLayout L, const Env &e)
 				for (int w = m.tendon_adr[j]; w < m.tendon_adr[j] + m.tendon_num[j]; w++)
 					v += m.actuator_gear[6 * i] * m.wrap_prm[w] * qvel[m.jnt_dofadr[m.wrap_objid[w]]];
 				f[L.actuator_velocity + i] = v;
-			} else
+			} else if (m.nsite_act && m.actuator_trntype[i] == MJB_TRN_SITE)
+				continue;
+			else
 				f[L.actuator_velocity + i] = m.actuator_gear[6 * i] * qvel[m.jnt_dofadr[j]];
 		}
+		if (m.nsite_act) site_velocity<G>(m, L, lite(e));
 	}
 	gsync<G>();
 	SPROF(26);
@@ -2487,6 +2610,50 @@ template <int G, bool CACHE = false> STAGE void sensors(CModel m, CLayout L, CSt
 // ------------------------------------------------------------------------------------------------
 // A12 actuation and smooth acceleration
 // ------------------------------------------------------------------------------------------------
+// force of actuator i (mj_fwdActuation): gain * (clamped ctrl, or the activation of a stateful actuator) + bias, clamped to forcerange
+DEVI double actuator_force(CModel m, CLayout L, const double *f, int i)
+{
+	double ctrl = f[L.ctrl + i];
+	if (m.actuator_ctrllimited[i] && !(m.disableflags & MJB_DSBL_CLAMPCTRL)) {
+		const double lo = m.actuator_ctrlrange[2 * i], hi = m.actuator_ctrlrange[2 * i + 1];
+		ctrl = ctrl < lo ? lo : (ctrl > hi ? hi : ctrl);
+	}
+	const double len = f[L.actuator_length + i], vel = f[L.actuator_velocity + i];
+	double gain = m.actuator_gainprm[3 * i], bias = 0;
+	if (m.actuator_gaintype[i] == MJB_GAIN_AFFINE)
+		gain = m.actuator_gainprm[3 * i] + m.actuator_gainprm[3 * i + 1] * len + m.actuator_gainprm[3 * i + 2] * vel;
+	if (m.actuator_biastype[i] == MJB_BIAS_AFFINE)
+		bias = m.actuator_biasprm[3 * i] + m.actuator_biasprm[3 * i + 1] * len + m.actuator_biasprm[3 * i + 2] * vel;
+	double input = ctrl;
+	if (m.na > 0) {  // a stateful actuator's gain multiplies its activation (mj_fwdActuation)
+		const int ja = m.actuator_actadr[i];
+		if (ja >= 0) input = f[L.act + ja];
+	}
+	double force = gain * input + bias;
+	if (m.actuator_forcelimited[i]) {
+		const double lo = m.actuator_forcerange[2 * i], hi = m.actuator_forcerange[2 * i + 1];
+		force = force < lo ? lo : (force > hi ? hi : force);
+	}
+	return force;
+}
+
+// forces of the site actuators, then qfrc_actuator += moment' force over their rows (after the per-dof lists of the other actuators)
+template <int G> __device__ __attribute__((noinline)) void site_actuation(CModel m, CLayout L, const EnvLite e, bool off)
+{
+	double *f = e.f;
+	for (int r = e.lane; r < m.nsite_act; r += G) {
+		const int i = m.site_act[r];
+		f[L.actuator_force + i] = off ? 0.0 : actuator_force(m, L, f, i);
+	}
+	gsync<G>();
+	if (off) return;
+	for (int d = e.lane; d < m.nv; d += G) {
+		double acc = 0;
+		for (int r = 0; r < m.nsite_act; r++) acc += f[L.act_mom + r * m.nv + d] * f[L.actuator_force + m.site_act[r]];
+		f[L.qfrc_actuator + d] += acc;
+	}
+}
+
 template <int G, bool CACHE = false> STAGE void fwd_actuation(CModel m, CLayout L, const Env &e)
 {
 	double *f = e.f;
@@ -2521,33 +2688,14 @@ template <int G, bool CACHE = false> STAGE void fwd_actuation(CModel m, CLayout 
 			const int i = m.dof_act_id[t];
 			double force = 0;
 			if (!off) {
-				double ctrl = f[L.ctrl + i];
-				if (m.actuator_ctrllimited[i] && !(m.disableflags & MJB_DSBL_CLAMPCTRL)) {
-					const double lo = m.actuator_ctrlrange[2 * i], hi = m.actuator_ctrlrange[2 * i + 1];
-					ctrl = ctrl < lo ? lo : (ctrl > hi ? hi : ctrl);
-				}
-				const double len = f[L.actuator_length + i], vel = f[L.actuator_velocity + i];
-				double gain = m.actuator_gainprm[3 * i], bias = 0;
-				if (m.actuator_gaintype[i] == MJB_GAIN_AFFINE)
-					gain = m.actuator_gainprm[3 * i] + m.actuator_gainprm[3 * i + 1] * len + m.actuator_gainprm[3 * i + 2] * vel;
-				if (m.actuator_biastype[i] == MJB_BIAS_AFFINE)
-					bias = m.actuator_biasprm[3 * i] + m.actuator_biasprm[3 * i + 1] * len + m.actuator_biasprm[3 * i + 2] * vel;
-				double input = ctrl;
-				if (m.na > 0) {  // a stateful actuator's gain multiplies its activation (mj_fwdActuation)
-					const int ja = m.actuator_actadr[i];
-					if (ja >= 0) input = f[L.act + ja];
-				}
-				force = gain * input + bias;
-				if (m.actuator_forcelimited[i]) {
-					const double lo = m.actuator_forcerange[2 * i], hi = m.actuator_forcerange[2 * i + 1];
-					force = force < lo ? lo : (force > hi ? hi : force);
-				}
+				force = actuator_force(m, L, f, i);
 				acc += m.dof_act_mom[t] * force;
 			}
 			f[L.actuator_force + i] = force;
 		}
 		f[L.qfrc_actuator + d] = acc;
 	}
+	if (m.nsite_act) site_actuation<G>(m, L, lite(e), off);
 	if (m.na > 0) {
 		// act_dot of the stateful actuators, from the clamped ctrl: integrator ctrl, filter (ctrl - act) / max(mjMINVAL, dynprm[0])
 		for (int i = e.lane; i < m.nu; i += G) {

@@ -578,9 +578,16 @@ class _Compiler:
         t = node.tag
         if "jointinparent" in a and "joint" not in a:
             a = dict(a, joint=a["jointinparent"])   # (identical to joint= for the scalar joints actuators are supported on)
-        if ("joint" in a) == ("tendon" in a):
-            raise MjcfError(f"actuator <{t}> needs exactly one of joint= / tendon= (joint and fixed-tendon transmissions are supported)")
-        act = dict(name=a.get("name", f"actuator{len(self.actuators)}"), joint=a.get("joint"), tendon=a.get("tendon"))
+        for key, what in (("cranksite", "slider-crank"), ("slidersite", "slider-crank"), ("body", "body (adhesion)")):
+            if key in a:
+                raise MjcfError(f"actuator <{t}>: {key}= -- the {what} transmission -- is not supported (joint, fixed-tendon and site transmissions are)")
+        if sum(k in a for k in ("joint", "tendon", "site")) != 1:
+            raise MjcfError(f"actuator <{t}> needs exactly one of joint= / jointinparent= / tendon= / site= "
+                            "(joint, fixed-tendon and site transmissions are supported)")
+        if "refsite" in a and "site" not in a:
+            raise MjcfError(f"actuator <{t}>: refsite= only goes with site=")
+        act = dict(name=a.get("name", f"actuator{len(self.actuators)}"), joint=a.get("joint"), tendon=a.get("tendon"),
+                   site=a.get("site"), refsite=a.get("refsite"))
         gear = np.zeros(6)
         gv = _floats(a.get("gear", "1"))
         gear[:gv.size] = gv
@@ -906,6 +913,20 @@ class _Compiler:
                 trnid[i, 0] = tendon_names.index(a["tendon"])
                 trntype[i] = 3
                 continue
+            if a["site"] is not None:   # mjTRN_SITE: the gear is a wrench in the site frame; with a refsite, the site's pose relative to it
+                sid = m.name2id("site", a["site"])
+                if sid < 0:
+                    raise MjcfError(f"actuator '{a['name']}': unknown site '{a['site']}'")
+                rid = -1
+                if a["refsite"] is not None:
+                    rid = m.name2id("site", a["refsite"])
+                    if rid < 0:
+                        raise MjcfError(f"actuator '{a['name']}': unknown refsite '{a['refsite']}'")
+                    if rid == sid:
+                        raise MjcfError(f"actuator '{a['name']}': refsite must be another site than site")
+                trnid[i] = (sid, rid)
+                trntype[i] = 4
+                continue
             jid = m.name2id("joint", a["joint"])
             if jid < 0:
                 raise MjcfError(f"actuator '{a['name']}': unknown joint '{a['joint']}'")
@@ -979,6 +1000,8 @@ class _Compiler:
                 raise MjcfError("integrator implicitfast with tendon damping is not supported")
             if nu and np.any((m["actuator_trntype"] == 3) & (m["actuator_biastype"] == 1) & (m["actuator_biasprm"][:, 2] != 0)):
                 raise MjcfError("integrator implicitfast with a velocity-dependent actuator on a tendon is not supported")
+            if nu and np.any((m["actuator_trntype"] == 4) & (m["actuator_biastype"] == 1) & (m["actuator_biasprm"][:, 2] != 0)):
+                raise MjcfError("integrator implicitfast with a velocity-dependent actuator on a site is not supported")
             if nu and np.any((m["actuator_gaintype"] == 1) & (m["actuator_gainprm"][:, 2] != 0)):
                 raise MjcfError("integrator implicitfast with a velocity term in an affine actuator gain (<damper>) is not supported")
         self._compile_equalities(m)
