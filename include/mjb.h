@@ -320,6 +320,14 @@ const char *mjb_lane_env_error(void);
  * Measurement / test knob, no reference counterpart. */
 int mjb_lane_env_set_form(int form);
 int mjb_lane_env_last_form(void);
+/* Form 3's root -> leaf sweep runs on three wavefronts (poses | inertias | velocities) or on FOUR (orientations | frames and positions | inertias |
+ * velocities: the pose wavefront's chain cut in two, on the fourth SIMD of the block's CU; csrc/mjb_lane_env_kernel.h, roles 8 - 11).
+ * mjb_lane_env_set_sweep_waves(3 | 4) asks for one of them, 0 = the launcher's rule (default; the environment variable MJB_LANE_ENV_SWEEP_WAVES = 3 / 4
+ * overrides it): four whenever its two extra LDS rings fit the block's 160 KB, three otherwise -- a request for four falls back the same way.  Returns
+ * the previous setting.  mjb_lane_env_last_sweep_waves: 3 or 4 for this process's last lane = env launch when it ran form 3, 0 otherwise.  Both
+ * variants ARE form 3 (mjb_lane_env_last_form); their results agree to rounding.  Measurement / test knob, no reference counterpart. */
+int mjb_lane_env_set_sweep_waves(int waves);
+int mjb_lane_env_last_sweep_waves(void);
 
 /* Stream control: the hipStream_t (as void*) kernels are launched on; default is a stream the
  * batch owns.  mjb_synchronize waits for it. */

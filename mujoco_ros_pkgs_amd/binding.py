@@ -210,6 +210,8 @@ def load_library(path=None):
         "mjb_lane_env_error": (C.c_char_p, []),
         "mjb_lane_env_set_form": (ci, [ci]),
         "mjb_lane_env_last_form": (ci, []),
+        "mjb_lane_env_set_sweep_waves": (ci, [ci]),
+        "mjb_lane_env_last_sweep_waves": (ci, []),
         "mjb_model_lane_env": (ci, [vp]),
         "mjb_lane_env_jit_counts": (None, [C.POINTER(ci), C.POINTER(ci)]),
         "mjb_set_split_step": (ci, [vp, ci]),

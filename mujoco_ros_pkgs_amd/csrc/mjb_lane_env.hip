@@ -65,12 +65,14 @@ __global__ void __launch_bounds__(128) mjb_lane_env_duo2_kernel(const KernelPara
 	lane_env_duo2<T, 160>(P, nsteps, step0, env_lo, env_hi, smem_le);
 }
 
-template <class T>
-__global__ void __launch_bounds__(192) mjb_lane_env_trio_kernel(const KernelParams MJB_AS4 *__restrict__ P, const int nsteps, const unsigned int step0,
-                                                                const int env_lo, const int env_hi)
+// (form 3 under either count of sweep wavefronts, NW = 3 or 4: one name for the tools that look the kernel up by it)
+template <class T, int NW>
+__global__ void __launch_bounds__(64 * NW) mjb_lane_env_trio_kernel(const KernelParams MJB_AS4 *__restrict__ P, const int nsteps, const unsigned int step0,
+                                                                    const int env_lo, const int env_hi)
 {
 	extern __shared__ __attribute__((aligned(16))) unsigned char smem_le[];
-	lane_env_trio<T, 160>(P, nsteps, step0, env_lo, env_hi, smem_le);
+	if constexpr (NW == 4) lane_env_quartet<T, 160>(P, nsteps, step0, env_lo, env_hi, smem_le);
+	else lane_env_trio<T, 160>(P, nsteps, step0, env_lo, env_hi, smem_le);
 }
 
 template <class T> bool topo_matches(const mjb_model_desc &h)
@@ -300,12 +302,12 @@ bool source_fingerprint(const std::string &dir, unsigned long long &hsh)
 	return true;
 }
 
-const JitKernel &jit_get(const mjb_model_desc &h, int lp, int duo)  // duo: 0 solo, 1 two halves, 2 pipelined, 3 three wavefronts
+const JitKernel &jit_get(const mjb_model_desc &h, int lp, int duo)  // duo: 0 solo, 1 two halves, 2 pipelined, 3 three wavefronts, 4 four (form 3 with the pose sweep on two)
 {
 	int dev = 0;
 	(void)hipGetDevice(&dev);
 	const std::string topo = topo_source(h);
-	const std::string key = std::to_string(dev) + "|" + std::to_string(lp) + (duo == 3 ? "t|" : (duo == 2 ? "p|" : (duo ? "d|" : "|"))) + topo;
+	const std::string key = std::to_string(dev) + "|" + std::to_string(lp) + (duo == 4 ? "q|" : duo == 3 ? "t|" : (duo == 2 ? "p|" : (duo ? "d|" : "|"))) + topo;
 	std::lock_guard<std::mutex> lock(jit_mutex);
 	auto it = jit_cache.find(key);
 	if (it != jit_cache.end()) return it->second;
@@ -317,7 +319,10 @@ const JitKernel &jit_get(const mjb_model_desc &h, int lp, int duo)  // duo: 0 so
 	const std::string dir = source_dir();
 	const std::string slp = std::to_string(lp);
 	const std::string src = "#include \"mjb_lane_env_kernel.h\"\n" + topo +
-	                        (duo == 3 ? "extern \"C\" __global__ void __launch_bounds__(192) le_rt(const KernelParams MJB_AS4 *P, int nsteps, unsigned int step0, int lo, int hi)\n{\n"
+	                        (duo == 4 ? "extern \"C\" __global__ void __launch_bounds__(256) le_rt(const KernelParams MJB_AS4 *P, int nsteps, unsigned int step0, int lo, int hi)\n{\n"
+	                                    "\t__shared__ __attribute__((aligned(16))) unsigned char smem[mjb_le::quartet_bytes<LeTopo_rt>()];\n"
+	                                    "\tmjb_le::lane_env_quartet<LeTopo_rt, 160>(P, nsteps, step0, lo, hi, smem);\n}\n"
+	                         : duo == 3 ? "extern \"C\" __global__ void __launch_bounds__(192) le_rt(const KernelParams MJB_AS4 *P, int nsteps, unsigned int step0, int lo, int hi)\n{\n"
 	                                    "\t__shared__ __attribute__((aligned(16))) unsigned char smem[mjb_le::trio_bytes<LeTopo_rt>()];\n"
 	                                    "\tmjb_le::lane_env_trio<LeTopo_rt, 160>(P, nsteps, step0, lo, hi, smem);\n}\n"
 	                         : duo == 2 ? "extern \"C\" __global__ void __launch_bounds__(128) le_rt(const KernelParams MJB_AS4 *P, int nsteps, unsigned int step0, int lo, int hi)\n{\n"
@@ -438,6 +443,13 @@ const char *mjb_lane_env_jit_error(void)
 
 // process-wide choice of the kernel's FORM (include/mjb.h): -1 = by batch size (default; MJB_LANE_ENV_DUO overrides), 0 / 1 / 2
 static std::atomic<int> le_form_override{ -1 }, le_form_last{ -1 };
+// ... and, of form 3, of the wavefronts its root -> leaf sweep runs on: 0 = by the rule below (default; MJB_LANE_ENV_SWEEP_WAVES overrides), 3 / 4
+static std::atomic<int> le_sweep_override{ 0 }, le_sweep_last{ 0 };
+int mjb_lane_env_set_sweep_waves(int waves)
+{
+	return le_sweep_override.exchange((waves == 3 || waves == 4) ? waves : 0);
+}
+int mjb_lane_env_last_sweep_waves(void) { return le_sweep_last; }
 int mjb_lane_env_set_form(int form)
 {
 	return le_form_override.exchange((form >= 0 && form <= 3) ? form : -1);
@@ -536,6 +548,12 @@ int mjb_launch_lane_env(const KernelParams *Pdev, int topo, const mjb_model_desc
 	if (duo && lp == 160 && duo_mode != 1) duo = 2;
 	// ... and THREE wavefronts (the pose chain alone on the first) while three SIMDs per block are there: the same LDS layout, so the same bound
 	if (duo == 2 && duo_mode != 2 && 3 * waves <= 4 * ncu) duo = 3;
+	// ... FOUR when the block still has a SIMD of its CU to itself per wavefront: the pose wavefront's chain cut in two (mjb_lane_env_kernel.h, roles 8 - 11).
+	// MJB_LANE_ENV_SWEEP_WAVES=3 / 4: the measurement knob (mjb_lane_env_set_sweep_waves goes first)
+	static const int sweep_env = [] { const char *v = getenv("MJB_LANE_ENV_SWEEP_WAVES"); const int k = v ? atoi(v) : 0; return (k == 3 || k == 4) ? k : 0; }();
+	const int sweep_set = le_sweep_override.load();
+	const int sweep_ov = sweep_set ? sweep_set : sweep_env;
+	int sweep = duo == 3 ? (sweep_ov ? sweep_ov : (waves <= ncu ? 4 : 3)) : 0;
 	if (duo_mode > 0 && lp < 80) lp = 80, duo = 1;  // (a forced two-wavefront form on a batch that would run four wavefronts per CU: two per CU)
 	if (topo == MJB_LE_TOPO_JIT) {
 		if (!h) return (int)hipErrorInvalidValue;
@@ -552,11 +570,13 @@ int mjb_launch_lane_env(const KernelParams *Pdev, int topo, const mjb_model_desc
 				return MJB_LE_UNAVAILABLE;
 			}
 			if (fit > lp) lp = fit;
+			if (sweep == 4 && need + 5 * ((need - h->nv) / 3) + 18 + (h->nv + 1) / 2 + 1 + h->nbody + 14 > 160) sweep = 3;  // (the quartet's two rings behind the trio's layout)
 			if (duo == 3 && need + 5 * ((need - h->nv) / 3) + 18 + (h->nv + 1) / 2 + 1 + h->nbody > 160) duo = 2;
+			if (duo != 3) sweep = 0;
 			if (duo == 2 && need + 5 * ((need - h->nv) / 3) + 12 + (h->nv + 1) / 2 + 1 > 160) duo = 1;
 			if (duo == 1 && need + (h->nv + 1) / 2 + 1 > lp) duo = 0;
 		}
-		const JitKernel &k = jit_get(*h, lp, duo);
+		const JitKernel &k = jit_get(*h, lp, sweep == 4 ? 4 : duo);
 		if (!k.fn) {
 			set_jit_error(k.error);
 			return MJB_LE_UNAVAILABLE;
@@ -566,7 +586,8 @@ int mjb_launch_lane_env(const KernelParams *Pdev, int topo, const mjb_model_desc
 		unsigned int a_step0 = step0;
 		void *args[] = { (void *)&Pd, (void *)&a_nsteps, (void *)&a_step0, (void *)&a_lo, (void *)&a_hi };
 		le_form_last = duo;
-		return (int)hipModuleLaunchKernel(k.fn, grid.x, 1, 1, duo == 3 ? 192 : (duo ? 128 : block.x), 1, 1, 0, (hipStream_t)stream, args, nullptr);
+		le_sweep_last = sweep;
+		return (int)hipModuleLaunchKernel(k.fn, grid.x, 1, 1, duo == 3 ? 64 * sweep : (duo ? 128 : block.x), 1, 1, 0, (hipStream_t)stream, args, nullptr);
 	}
 #define MJB_LE_GO(T, LPV)                                                                                                                    \
 	{                                                                                                                                         \
@@ -574,7 +595,7 @@ int mjb_launch_lane_env(const KernelParams *Pdev, int topo, const mjb_model_desc
 		constexpr int bytes = Lds<T, LPV>::bytes();                                                                                           \
 		const hipError_t attr = lds_attr_once(reinterpret_cast<const void *>(kern), bytes, cur_dev);                                          \
 		if (attr != hipSuccess) return (int)attr;                                                                                             \
-		le_form_last = 0;                                                                                                                     \
+		le_form_last = 0, le_sweep_last = 0;                                                                                                  \
 		hipLaunchKernelGGL(kern, grid, block, bytes, (hipStream_t)stream, (const KernelParams MJB_AS4 *)Pdev, nsteps, step0, env_lo, env_hi); \
 		return (int)hipGetLastError();                                                                                                        \
 	}
@@ -584,7 +605,7 @@ int mjb_launch_lane_env(const KernelParams *Pdev, int topo, const mjb_model_desc
 		constexpr int bytes = duo_bytes<T, LPV>();                                                                                            \
 		const hipError_t attr = lds_attr_once(reinterpret_cast<const void *>(kern), bytes, cur_dev);                                          \
 		if (attr != hipSuccess) return (int)attr;                                                                                             \
-		le_form_last = 1;                                                                                                                     \
+		le_form_last = 1, le_sweep_last = 0;                                                                                                  \
 		hipLaunchKernelGGL(kern, grid, dim3(128), bytes, (hipStream_t)stream, (const KernelParams MJB_AS4 *)Pdev, nsteps, step0, env_lo, env_hi); \
 		return (int)hipGetLastError();                                                                                                        \
 	}
@@ -594,23 +615,24 @@ int mjb_launch_lane_env(const KernelParams *Pdev, int topo, const mjb_model_desc
 		constexpr int bytes = duo2_bytes<T>();                                                                                                \
 		const hipError_t attr = lds_attr_once(reinterpret_cast<const void *>(kern), bytes, cur_dev);                                          \
 		if (attr != hipSuccess) return (int)attr;                                                                                             \
-		le_form_last = 2;                                                                                                                     \
+		le_form_last = 2, le_sweep_last = 0;                                                                                                  \
 		hipLaunchKernelGGL(kern, grid, dim3(128), bytes, (hipStream_t)stream, (const KernelParams MJB_AS4 *)Pdev, nsteps, step0, env_lo, env_hi); \
 		return (int)hipGetLastError();                                                                                                        \
 	}
-#define MJB_LE_GO_TRIO(T)                                                                                                                   \
-	if constexpr (trio_bytes<T>() <= 160 * 1024) {                                                                                            \
-		auto kern = mjb_lane_env_trio_kernel<T>;                                                                                              \
-		constexpr int bytes = trio_bytes<T>();                                                                                                \
+#define MJB_LE_GO_TRIO(T, NW)                                                                                                               \
+	if constexpr ((NW == 4 ? quartet_bytes<T>() : trio_bytes<T>()) <= 160 * 1024) {                                                           \
+		auto kern = mjb_lane_env_trio_kernel<T, NW>;                                                                                          \
+		constexpr int bytes = NW == 4 ? quartet_bytes<T>() : trio_bytes<T>();                                                                 \
 		const hipError_t attr = lds_attr_once(reinterpret_cast<const void *>(kern), bytes, cur_dev);                                          \
 		if (attr != hipSuccess) return (int)attr;                                                                                             \
-		le_form_last = 3;                                                                                                                     \
-		hipLaunchKernelGGL(kern, grid, dim3(192), bytes, (hipStream_t)stream, (const KernelParams MJB_AS4 *)Pdev, nsteps, step0, env_lo, env_hi); \
+		le_form_last = 3, le_sweep_last = NW;                                                                                                 \
+		hipLaunchKernelGGL(kern, grid, dim3(64 * NW), bytes, (hipStream_t)stream, (const KernelParams MJB_AS4 *)Pdev, nsteps, step0, env_lo, env_hi); \
 		return (int)hipGetLastError();                                                                                                        \
 	}
 #define MJB_LE_X(id, T)                      \
 	if (topo == id) {                        \
-		if (duo == 3) MJB_LE_GO_TRIO(T)      \
+		if (duo == 3 && sweep == 4) MJB_LE_GO_TRIO(T, 4) \
+		if (duo == 3) MJB_LE_GO_TRIO(T, 3)   \
 		if (duo >= 2) MJB_LE_GO_DUO2(T)      \
 		if (duo && lp == 160) MJB_LE_GO_DUO(T, 160) \
 		if (duo && lp == 80) MJB_LE_GO_DUO(T, 80)   \

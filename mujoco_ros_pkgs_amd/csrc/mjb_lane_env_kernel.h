@@ -210,11 +210,19 @@ DEVI void lane_env_body(const KernelParams MJB_AS4 *__restrict__ P, const int ns
 	// (roles 5 / 6 / 7 = the TRIO, three wavefronts per 64 envs: 5 = P runs the pose chain and nothing else; 6 = C follows it through the ring with cinert
 	//  and cdof, then takes the composite-inertia sweep, qM, both factors, the solves and Euler; 7 = V as role 4, with its own cinert of every body.
 	//  P's sweep is the step's critical chain: everything that is not a pose is off it.)
-	constexpr bool DP = ROLE == 0 || ROLE == 1 || ROLE == 3 || ROLE == 6, DV = ROLE == 0 || ROLE == 2 || ROLE == 4 || ROLE == 7, DUO = ROLE != 0;  // this wavefront does the position half (inertias, factors, solves, Euler) / the velocity half
+	// (roles 8 / 9 / 10 / 11 = the QUARTET, the trio with its pose wavefront cut in two, on the CU's fourth SIMD: 8 = O runs the ORIENTATION chain and nothing
+	//  else -- xquat[b] = normalize(xquat[p] body_quat hinge_quat), the one part of a pose the next body's waits for -- with every hinge's half-angle sine and
+	//  cosine one body ahead, and passes the unit quaternion on through a two-deep ring; 9 = X follows one body behind: rotation matrix, the position chain,
+	//  inertial frame, mj_energyPos, frame sensors, the pose ring; 10 = C as role 6 one body behind X, without the sines, and it publishes cdof; 11 = V as
+	//  role 7 one body behind C, with C's cdof instead of its own.  One barrier per MOVING body plus two to drain: sweep phase k has O on the k-th moving
+	//  body, X on the one before, C two and V three before; the bodies at rest are O's and X's own business ahead of the phases.)
+	constexpr bool QUAD = ROLE >= 8;
+	constexpr bool DP = ROLE == 0 || ROLE == 1 || ROLE == 3 || ROLE == 6 || ROLE == 10, DV = ROLE == 0 || ROLE == 2 || ROLE == 4 || ROLE == 7 || ROLE == 11, DUO = ROLE != 0;  // this wavefront does the position half (inertias, factors, solves, Euler) / the velocity half
 	constexpr bool PIPE = ROLE >= 3;
-	constexpr bool POSE = ROLE <= 3 || ROLE == 5, RINGC = ROLE == 4 || ROLE == 6 || ROLE == 7;  // computes the poses / takes them from the ring
-	constexpr bool EPOS = ROLE == 0 || ROLE == 1 || ROLE == 3 || ROLE == 5;                       // gathers mj_energyPos along its pose sweep
-	constexpr bool SENSF = ROLE == 0 || ROLE == 2 || ROLE == 3 || ROLE == 5;  // frame sensors: who holds the poses (and, of two, who has the time)
+	constexpr bool POSE = ROLE <= 3 || ROLE == 5, RINGC = ROLE == 4 || ROLE == 6 || ROLE == 7;  // computes the poses / takes them from the ring (the quartet's roles have a sweep of their own below)
+	constexpr bool VLDS = ROLE == 7 || ROLE == 11;  // V of three / four wavefronts: cinert from C through LDS
+	constexpr bool EPOS = ROLE == 0 || ROLE == 1 || ROLE == 3 || ROLE == 5 || ROLE == 9;                     // gathers mj_energyPos along its pose sweep
+	constexpr bool SENSF = ROLE == 0 || ROLE == 2 || ROLE == 3 || ROLE == 5 || ROLE == 9;  // frame sensors: who holds the poses (and, of two, who has the time)
 	using Q = Tq<T>;
 	constexpr int LPE = PIPE ? (1 << 20) : (DUO ? LP - DuoSlots<NV>::n : LP);
 	using LD = Lds<T, LPE>;
@@ -228,6 +236,7 @@ DEVI void lane_env_body(const KernelParams MJB_AS4 *__restrict__ P, const int ns
 	constexpr int RINGN = ROLE >= 5 ? 3 : 2;  // depth of the pose ring (the trio's V reads two bodies behind P)
 	constexpr int LASTB = [] { for (int c = NB - 1; c >= 1; c--) if (LD::needed(c)) return c; return 0; }();  // the leaf the composite-inertia sweep starts at
 	constexpr int RING = LD::nslots();                                              // (PIPE) 2 x 6 pair slots of the pose ring behind the solo layout
+	constexpr int QR0 = RING + 18 + DuoSlots<NV>::n + NB, CD0 = QR0 + 8;  // (quartet, behind the trio's layout) O's quaternion ring: 2 x (xquat, the frame before the joint); C's cdof ring: 2 x 3
 	constexpr int XS = PIPE ? RING + 6 * RINGN : LD::nslots(), MAIL = XS + (NV + 1) / 2, SC0 = MAIL + 1;  // (trio) SC0 + b: body b's half-angle (sin, cos), from C to P  // (DUO) pair slots of qfrc_smooth, and of P's verdicts for V
 	const int lane_le = DUO ? (int)(threadIdx.x & 63u) : (int)threadIdx.x;
 	Pair *const lp = reinterpret_cast<Pair *>(smem_le) + lane_le;  // pair slot q of this lane: lp[64 * q]
@@ -464,12 +473,13 @@ DEVI void lane_env_body(const KernelParams MJB_AS4 *__restrict__ P, const int ns
 				constexpr int p = T::body_parentid[b], j = T::body_jnt[b];
 				constexpr int ord = (LD::slot(b) - NV) / 3, rg = RING + 6 * (ord % RINGN), c0 = LD::cin_slot(b);
 				static_assert(c0 >= 0, "pipelined forms: every needed body's cinert lives in LDS");
-				double xp[3], xm[9], ci[10];
-				{
+				[[maybe_unused]] double xp[3], xm[9];
+				double ci[10];
+				if constexpr (ROLE != 11) {
 					const Pair a0 = lp[64 * rg], a1 = lp[64 * (rg + 1)], a2 = lp[64 * (rg + 2)], a3 = lp[64 * (rg + 3)], a4 = lp[64 * (rg + 4)], a5 = lp[64 * (rg + 5)];
 					xp[0] = a0.a; xp[1] = a0.b; xp[2] = a1.a; xm[0] = a1.b; xm[1] = a2.a; xm[2] = a2.b; xm[3] = a3.a; xm[4] = a3.b; xm[5] = a4.a; xm[6] = a4.b; xm[7] = a5.a; xm[8] = a5.b;
 				}
-				if constexpr ((ROLE == 4 && b == LASTB) || ROLE == 7) {
+				if constexpr ((ROLE == 4 && b == LASTB) || VLDS) {
 					// the LAST needed body's cinert came with its pose: P computes that one itself and goes from its last pose straight into the
 					// composite-inertia sweep, which starts at this body -- it never waits for V's last phase
 					for (int k = 0; k < 5; k++) {
@@ -521,11 +531,17 @@ DEVI void lane_env_body(const KernelParams MJB_AS4 *__restrict__ P, const int ns
 				if constexpr (j >= 0) {
 					[[maybe_unused]] double qv = 0;
 					if constexpr (DV) qv = lp[64 * j].b;
+					double *cd = cdof[j];
+					constexpr int cq = CD0 + 3 * (ord % 2);  // (quartet) the body's slots of the cdof ring
+					if constexpr (ROLE == 11) {  // (the quartet's V: C's cdof, one phase old)
+						const Pair d0 = lp[64 * cq], d1 = lp[64 * (cq + 1)], d2 = lp[64 * (cq + 2)];
+						cd[0] = d0.a; cd[1] = d0.b; cd[2] = d1.a; cd[3] = d1.b; cd[4] = d2.a; cd[5] = d2.b;
+						if constexpr (T::jnt_type[j] == MJB_JNT_SLIDE) cd[0] = cd[1] = cd[2] = 0;
+					} else {
 					const LeTapeBody MJB_AS4 &tj = tb[b];
 					const double ax[3] = { tj.jaxis[0], tj.jaxis[1], tj.jaxis[2] };
 					double xaxis[3];
 					matvec3(xaxis, xm, ax);
-					double *cd = cdof[j];
 					if constexpr (T::jnt_type[j] == MJB_JNT_SLIDE) {
 						cd[0] = cd[1] = cd[2] = 0;
 						for (int k = 0; k < 3; k++) cd[3 + k] = xaxis[k];
@@ -541,6 +557,12 @@ DEVI void lane_env_body(const KernelParams MJB_AS4 *__restrict__ P, const int ns
 						for (int k = 0; k < 3; k++) off[k] = -xanch[k];  // (root origin - anchor)
 						for (int k = 0; k < 3; k++) cd[k] = xaxis[k];
 						cross3(cd + 3, xaxis, off);
+					}
+					if constexpr (ROLE == 10) {  // (the quartet's C: cdof to V)
+						lp[64 * cq] = Pair{ cd[0], cd[1] };
+						lp[64 * (cq + 1)] = Pair{ cd[2], cd[3] };
+						lp[64 * (cq + 2)] = Pair{ cd[4], cd[5] };
+					}
 					}
 					if constexpr (!DV) {
 					} else if constexpr (p == 0 || !LD::needed(p)) {
@@ -796,8 +818,216 @@ DEVI void lane_env_body(const KernelParams MJB_AS4 *__restrict__ P, const int ns
 				}
 			});
 
+
+			// ============ the quartet's sweep: the same quantities, dealt over four wavefronts in phases (see the roles at the top) ============
+			// A body without a joint on its path to the world never moves and nobody downstream takes anything of it through LDS: O (its quaternion) and
+			// X (its frame, sensors, energy) each compute those bodies for themselves ahead of the phases, which count the NEEDED bodies only.
+			if constexpr (QUAD) {
+				constexpr auto HINGE = [](int c) {
+					if (c < 1 || c >= T::NBODY || T::body_jnt[c < T::NBODY ? (c < 0 ? 0 : c) : 0] < 0) return false;
+					return T::jnt_type[T::body_jnt[c]] == MJB_JNT_HINGE;
+				};
+				constexpr auto NEXTN = [](int c) { for (int q = c + 1; q < T::NBODY; q++) if (LD::needed(q)) return q; return T::NBODY; };  // the needed body after c (NBODY: none)
+				constexpr auto NTH = [](int k) { int c = 0; for (int i = 0; i < k && c < T::NBODY; i++) { c++; while (c < T::NBODY && !LD::needed(c)) c++; } return k < 1 ? T::NBODY : c; };
+				constexpr int KN = [] { int n = 0; for (int c = 1; c < T::NBODY; c++) if (LD::needed(c)) n++; return n; }();
+				constexpr int N1 = NEXTN(0), N2 = NEXTN(N1 < NB ? N1 : NB - 1);
+				[[maybe_unused]] double osn[NB + 1], ocs[NB + 1], oq0[NB + 1];  // O: a hinge's half-angle (sin, cos), computed one phase ahead; its qpos0 and (qpos, qvel), fetched two ahead
+				[[maybe_unused]] Pair opq[NB + 1];
+				// O, body b: the orientation chain (hA[b] is there)
+				auto o_body = [&](auto Bq) {
+					constexpr int b = Bq;
+					constexpr int p = T::body_parentid[b], j = T::body_jnt[b];
+					const double *const A = hA[b];  // pos[3] quat[4] jaxis[3] jpos[3] qpos0
+					constexpr int qr = QR0 + 4 * (((LD::slot(b) - NV) / 3) % 2);
+					double quat[4] = { A[3], A[4], A[5], A[6] };
+					if constexpr (p != 0) {
+						double q[4];
+						qmul(q, xquat[p], quat);
+						for (int k = 0; k < 4; k++) quat[k] = q[k];
+					}
+					if constexpr (j >= 0) {
+						// (an off-centre anchor, wave-uniform: X needs the frame before the joint motion too)
+						if (A[10] != 0 || A[11] != 0 || A[12] != 0) {
+							lp[64 * (qr + 2)] = Pair{ quat[0], quat[1] };
+							lp[64 * (qr + 3)] = Pair{ quat[2], quat[3] };
+						}
+						if constexpr (T::jnt_type[j] == MJB_JNT_HINGE) {
+							double ql[4], q[4];
+							ql[0] = ocs[b]; ql[1] = A[7] * osn[b]; ql[2] = A[8] * osn[b]; ql[3] = A[9] * osn[b];
+							qmul(q, quat, ql);
+							for (int k = 0; k < 4; k++) quat[k] = q[k];
+						}
+					}
+					normalize4_sel(quat);
+					for (int k = 0; k < 4; k++) xquat[b][k] = quat[k];
+					if constexpr (LD::needed(b)) {
+						lp[64 * qr] = Pair{ quat[0], quat[1] };
+						lp[64 * (qr + 1)] = Pair{ quat[2], quat[3] };
+					}
+				};
+				auto o_phase = [&](auto Bq) {
+					constexpr int b = Bq, nx = NEXTN(b), nx2 = NEXTN(nx < NB ? nx : NB - 1);
+					touch_s(hA[b][0]);
+					if constexpr (nx < NB) for (int k = 0; k < 14; k++) hA[nx][k] = reinterpret_cast<const double MJB_AS4 *>(tb + nx)[k];
+					if constexpr (nx < NB && HINGE(nx2)) {
+						opq[nx2] = lp[64 * T::body_jnt[nx2 < NB ? nx2 : 0]];
+						oq0[nx2] = tb[nx2].qpos0;
+					}
+					// (the next hinge's two polynomial chains depend on qpos alone: they fill this body's dependency stalls)
+					if constexpr (HINGE(nx)) sincos_nb((opq[nx].a - oq0[nx]) * 0.5, &osn[nx], &ocs[nx]);
+					o_body(Bq);
+					if constexpr (nx < NB) touch_rec<14>(hA[nx]);
+				};
+				// X, body b: O's quaternion into the frame, the position chain, what hangs on the pose (hA[b], hB[b] are there)
+				auto x_body = [&](auto Bq) {
+					constexpr int b = Bq;
+					constexpr int p = T::body_parentid[b], j = T::body_jnt[b], r = T::body_rootid[b];
+					constexpr int qr = QR0 + 4 * (((LD::slot(b) - NV) / 3) % 2);
+					const double *const A = hA[b];
+					double pos[3] = { A[0], A[1], A[2] }, quat[4] = { A[3], A[4], A[5], A[6] };
+					if constexpr (LD::needed(b)) {
+						const Pair g0 = lp[64 * qr], g1 = lp[64 * (qr + 1)];
+						quat[0] = g0.a; quat[1] = g0.b; quat[2] = g1.a; quat[3] = g1.b;
+					} else {  // (at rest: the same chain O runs for it)
+						if constexpr (p != 0) {
+							double q[4];
+							qmul(q, xquat[p], quat);
+							for (int k = 0; k < 4; k++) quat[k] = q[k];
+						}
+						normalize4_sel(quat);
+					}
+					[[maybe_unused]] Pair sp{ 0, 0 };
+					if constexpr (j >= 0) sp = lp[64 * j];
+					if constexpr (p != 0) {
+						double v[3];
+						matvec3(v, xmat[p], pos);
+						for (int k = 0; k < 3; k++) pos[k] = v[k] + xpos[p][k];
+					}
+					[[maybe_unused]] double xanch[3], qp = 0;
+					[[maybe_unused]] bool offc = false;
+					if constexpr (j >= 0) {
+						qp = sp.a;
+						const double jp[3] = { A[10], A[11], A[12] };
+						offc = jp[0] != 0 || jp[1] != 0 || jp[2] != 0;
+						for (int k = 0; k < 3; k++) xanch[k] = pos[k];
+						if (offc) {
+							const Pair h0 = lp[64 * (qr + 2)], h1 = lp[64 * (qr + 3)];
+							const double q0[4] = { h0.a, h0.b, h1.a, h1.b };
+							double M0[9], v[3];
+							quat2mat_nocheck(M0, q0);
+							matvec3(v, M0, jp);
+							for (int k = 0; k < 3; k++) xanch[k] += v[k];
+						}
+						if (ep_on && pas_on) {  // mj_energyPos: the joint spring
+							const double dqs = qp - tb[b].spring;  // (last step only)
+							pe += 0.5 * tb[b].stiffness * dqs * dqs;
+						}
+					}
+					for (int k = 0; k < 4; k++) xquat[b][k] = quat[k];
+					quat2mat_nocheck(xmat[b], quat);
+					if constexpr (j >= 0) {
+						if constexpr (T::jnt_type[j] == MJB_JNT_SLIDE) {
+							const double ax[3] = { A[7], A[8], A[9] };
+							double xaxis[3];
+							matvec3(xaxis, xmat[b], ax);
+							const double dq = qp - A[13];
+							for (int k = 0; k < 3; k++) pos[k] += xaxis[k] * dq;
+						} else if (offc) {  // correct for off-centre rotation
+							const double jp[3] = { A[10], A[11], A[12] };
+							double v[3];
+							matvec3(v, xmat[b], jp);
+							for (int k = 0; k < 3; k++) pos[k] = xanch[k] - v[k];
+						}
+					}
+					for (int k = 0; k < 3; k++) xpos[b][k] = pos[k];
+					const double *const Bh = hB[b];  // ipos[3] ibody[6] mass
+					double xipos[3];
+					if constexpr (T::body_sameframe[b]) {
+						for (int k = 0; k < 3; k++) xipos[k] = xpos[b][k];
+					} else {
+						double ip[3] = { Bh[0], Bh[1], Bh[2] }, v[3];
+						matvec3(v, xmat[b], ip);
+						for (int k = 0; k < 3; k++) xipos[k] = v[k] + xpos[b][k];
+					}
+					if (eg_on) pe -= Bh[9] * (grav[0] * xipos[0] + grav[1] * xipos[1] + grav[2] * xipos[2]);
+					frame_sensors(Bq, xipos);
+					if constexpr (LD::needed(b)) {  // the pose to C
+						constexpr int ord = (LD::slot(b) - NV) / 3, rg = RING + 6 * (ord % RINGN);
+						const double *xm = xmat[b];
+						double xp[3] = { 0, 0, 0 };  // relative to the tree root's origin: what cdof is taken about
+						if constexpr (r != b) for (int k = 0; k < 3; k++) xp[k] = xpos[b][k] - xpos[r][k];
+						lp[64 * rg] = Pair{ xp[0], xp[1] };
+						lp[64 * (rg + 1)] = Pair{ xp[2], xm[0] };
+						lp[64 * (rg + 2)] = Pair{ xm[1], xm[2] };
+						lp[64 * (rg + 3)] = Pair{ xm[3], xm[4] };
+						lp[64 * (rg + 4)] = Pair{ xm[5], xm[6] };
+						lp[64 * (rg + 5)] = Pair{ xm[7], xm[8] };
+					}
+				};
+				auto x_phase = [&](auto Bq) {
+					constexpr int b = Bq, nx = NEXTN(b);
+					touch_s(hA[b][0]);
+					touch_s(hB[b][0]);
+					if constexpr (nx < NB) {
+						for (int k = 0; k < 14; k++) hA[nx][k] = reinterpret_cast<const double MJB_AS4 *>(tb + nx)[k];
+						for (int k = 0; k < 10; k++) hB[nx][k] = reinterpret_cast<const double MJB_AS4 *>(tb + nx)[16 + k];
+					}
+					x_body(Bq);
+					if constexpr (nx < NB) {
+						touch_rec<14>(hA[nx]);
+						touch_rec<10>(hB[nx]);
+					}
+				};
+				if constexpr (ROLE == 8 || ROLE == 9) {
+					// the bodies at rest, then the first needed body's record
+					sfor<NB>([&](auto Bq) {
+						constexpr int b = Bq;
+						if constexpr (b > 0 && !LD::needed(b)) {
+							for (int k = 0; k < 14; k++) hA[b][k] = reinterpret_cast<const double MJB_AS4 *>(tb + b)[k];
+							if constexpr (ROLE == 9) for (int k = 0; k < 10; k++) hB[b][k] = reinterpret_cast<const double MJB_AS4 *>(tb + b)[16 + k];
+							if constexpr (ROLE == 8) o_body(Bq);
+							else x_body(Bq);
+						}
+					});
+					if constexpr (N1 < NB) {
+						for (int k = 0; k < 14; k++) hA[N1][k] = reinterpret_cast<const double MJB_AS4 *>(tb + N1)[k];
+						if constexpr (ROLE == 9) for (int k = 0; k < 10; k++) hB[N1][k] = reinterpret_cast<const double MJB_AS4 *>(tb + N1)[16 + k];
+					}
+					if constexpr (ROLE == 8) {
+						if constexpr (HINGE(N1)) {
+							opq[N1] = lp[64 * T::body_jnt[N1 < NB ? N1 : 0]];
+							oq0[N1] = tb[N1].qpos0;
+						}
+						if constexpr (N1 < NB && HINGE(N2)) {
+							opq[N2] = lp[64 * T::body_jnt[N2 < NB ? N2 : 0]];
+							oq0[N2] = tb[N2].qpos0;
+						}
+						if constexpr (HINGE(N1)) sincos_nb((opq[N1].a - oq0[N1]) * 0.5, &osn[N1], &ocs[N1]);
+					}
+				}
+				__builtin_amdgcn_sched_barrier(0);
+				// phase k: O on the k-th needed body, X on the one before, C two, V three before; every wavefront takes the KN + 2 barriers, V's last body comes behind the last one
+				sfor<KN + 3>([&](auto Ki) {
+					constexpr int k = Ki + 1;
+					constexpr int kk = k - (ROLE - 8);  // this role's body, counted among the needed ones
+					if constexpr (kk >= 1 && kk <= KN) {
+						constexpr int bb = NTH(kk);
+						if constexpr (ROLE == 8) o_phase(IC<bb>{});
+						else if constexpr (ROLE == 9) x_phase(IC<bb>{});
+						else consume(IC<bb>{});
+					}
+					if constexpr (DV && k == 1) sfor<NV>([&](auto I) { qfa[I] = s.qfrc_applied[ev * NV + I]; });  // (read by the force block behind the sweep: a trip to HBM)
+					if constexpr (k <= KN + 2) {
+						LE_PK(0);
+						le_barrier();
+						LE_PK(2);
+					}
+					__builtin_amdgcn_sched_barrier(0);
+				});
+			}
+
 			LE_PK(0);
-			if constexpr (ROLE >= 5) {  // (the trio: C's cinert of the last body is in LDS; V takes that body now)
+			if constexpr (ROLE >= 5 && !QUAD) {  // (the trio: C's cinert of the last body is in LDS; V takes that body now)
 				le_barrier();
 				if constexpr (ROLE == 7) consume(IC<LASTB>{});
 			}
@@ -949,7 +1179,7 @@ DEVI void lane_env_body(const KernelParams MJB_AS4 *__restrict__ P, const int ns
 				__builtin_amdgcn_sched_barrier(0);
 			});
 			LE_PK(3);
-			if constexpr (ROLE == 5) en_pe = pe;
+			if constexpr (ROLE == 5 || ROLE == 9) en_pe = pe;
 			if constexpr (DUO && !DP) {
 				// ---- V's half ends here: qfrc_smooth to P, then P's verdict on the step (the trio's P: the two rendezvous and the verdict)
 				if constexpr (DV) sfor<(NV + 1) / 2>([&](auto K) {
@@ -1075,7 +1305,7 @@ DEVI void lane_env_body(const KernelParams MJB_AS4 *__restrict__ P, const int ns
 				le_barrier();  // (B, retry) V runs its half again on the reset state
 			}
 		}
-		if constexpr (ROLE == 5) {
+		if constexpr (ROLE == 5 || ROLE == 9) {
 			if (last && (m.enableflags & MJB_ENBL_ENERGY)) s.energy[2 * ev] = en_pe;  // (C stores the kinetic half)
 		}
 		if constexpr (DUO && !DP) {
@@ -1112,7 +1342,7 @@ DEVI void lane_env_body(const KernelParams MJB_AS4 *__restrict__ P, const int ns
 		}
 	}
 #ifdef MJB_LE_PROBE
-	if (env_raw == env_lo) for (int k = 0; k < 8; k++) P->s.sensordata[(ROLE == 4 || ROLE == 2 || ROLE == 6 ? 8 : (ROLE == 7 ? 16 : 0)) + k] = (double)pk_acc[k] / nsteps;
+	if (env_raw == env_lo) for (int k = 0; k < 8; k++) P->s.sensordata[(ROLE == 4 || ROLE == 2 || ROLE == 6 || ROLE == 10 ? 8 : (ROLE == 7 || ROLE == 11 ? 16 : (ROLE == 9 ? 24 : 0))) + k] = (double)pk_acc[k] / nsteps;
 #endif
 
 	// ---- the launch's state back to HBM (store_state of the generic kernels; sensordata went out from the last step)
@@ -1139,6 +1369,8 @@ template <class T, int LP> constexpr int duo_bytes() { return (Lds<T, LP - DuoSl
 
 // ... and of a pipelined DUO block (roles 3 / 4): every needed body's cinert, every dof's cdof, the pose ring, the exchange slots
 template <class T> constexpr int trio_bytes() { return (Lds<T, (1 << 20)>::nslots() + 18 + DuoSlots<T::NV>::n + T::NBODY) * 64 * 16; }
+// ... and of a quartet block: the trio's layout, then O's quaternion ring (2 x 4 pair slots) and C's cdof ring (2 x 3)
+template <class T> constexpr int quartet_bytes() { return trio_bytes<T>() + 14 * 64 * 16; }
 template <class T> constexpr int duo2_bytes() { return (Lds<T, (1 << 20)>::nslots() + 12 + DuoSlots<T::NV>::n) * 64 * 16; }
 template <class T, int LP>
 DEVI void lane_env_duo2(const KernelParams MJB_AS4 *__restrict__ P, const int nsteps, const unsigned int step0, const int env_lo, const int env_hi,
@@ -1157,6 +1389,18 @@ DEVI void lane_env_trio(const KernelParams MJB_AS4 *__restrict__ P, const int ns
 	if (w == 0) lane_env_body<T, LP, 5>(P, nsteps, step0, env_lo, env_hi, smem_le);
 	else if (w == 1) lane_env_body<T, LP, 6>(P, nsteps, step0, env_lo, env_hi, smem_le);
 	else lane_env_body<T, LP, 7>(P, nsteps, step0, env_lo, env_hi, smem_le);
+}
+
+// the QUARTET: wavefront 0 = the orientation chain, 1 = frames and positions, 2 = inertias / factors / solves / Euler, 3 = velocities and forces (blockDim.x = 256)
+template <class T, int LP>
+DEVI void lane_env_quartet(const KernelParams MJB_AS4 *__restrict__ P, const int nsteps, const unsigned int step0, const int env_lo, const int env_hi,
+                           unsigned char *const smem_le)
+{
+	const int w = __builtin_amdgcn_readfirstlane((int)threadIdx.x) >> 6;
+	if (w == 0) lane_env_body<T, LP, 8>(P, nsteps, step0, env_lo, env_hi, smem_le);
+	else if (w == 1) lane_env_body<T, LP, 9>(P, nsteps, step0, env_lo, env_hi, smem_le);
+	else if (w == 2) lane_env_body<T, LP, 10>(P, nsteps, step0, env_lo, env_hi, smem_le);
+	else lane_env_body<T, LP, 11>(P, nsteps, step0, env_lo, env_hi, smem_le);
 }
 
 // the DUO kernel's body: wavefront 0 of the block takes the position half, wavefront 1 the velocity half (blockDim.x = 128)

@@ -321,6 +321,14 @@ class Batch:
     def lane_env_last_form(self):
         return int(self.lib.mjb_lane_env_last_form())
 
+    def set_lane_env_sweep_waves(self, waves):
+        """Process-wide: form 3's sweep on 3 or 4 wavefronts, 0 = the launcher's rule (mjb_lane_env_set_sweep_waves).  Returns the previous setting."""
+        return int(self.lib.mjb_lane_env_set_sweep_waves(int(waves)))
+
+    def lane_env_last_sweep_waves(self):
+        """3 / 4: the sweep wavefronts of the last lane = env launch if it ran form 3, else 0."""
+        return int(self.lib.mjb_lane_env_last_sweep_waves())
+
     def lane_env_error(self):
         """Why the hiprtc build of this process's last lane = env topology was not available ('' if none failed)."""
         return self.lib.mjb_lane_env_error().decode()

@@ -2,7 +2,9 @@
 """lane_env_bench.py -- config 2's fused step at several batch sizes: the 16-lanes-per-env kernel beside the lane = env kernel
 ("run at 4096 / 16 384 / 65 536 / 262 144 envs beside the G = 16 kernel").  Same workload as bench.py's default
 line (franka_like, OU ctrl noise std 43.5, Philox seed 12345), K steps per launch, env-steps/s from HIP-event timing of whole launches
-(mjb_time_steps).  usage: python tools/lane_env_bench.py [K] [sizes...]"""
+(mjb_time_steps).  usage: python tools/lane_env_bench.py [K] [sizes...] [--sweep-waves=3|4] [--lane-env-only]
+--sweep-waves: form 3's sweep on three / four wavefronts (mjb_lane_env_set_sweep_waves; default: the launcher's rule) -- the same-commit A/B of the two;
+--lane-env-only: skip the 16-lanes-per-env kernel."""
 import json
 import os
 import sys
@@ -15,7 +17,11 @@ from tests.conftest import random_franka_state  # noqa: E402
 
 
 def main():
-    argv = [a for a in sys.argv[1:] if a != "--two-arm"]
+    argv = [a for a in sys.argv[1:] if not a.startswith("--")]
+    lib = engine.binding.load_library()
+    for a in sys.argv[1:]:
+        if a.startswith("--sweep-waves="):
+            lib.mjb_lane_env_set_sweep_waves(int(a.split("=")[1]))
     K = int(argv[0]) if argv else 200
     sizes = [int(a) for a in argv[1:]] or [4096, 16384, 65536, 262144]
     if "--two-arm" in sys.argv:  # a 14-dof model that is NOT compiled in: the kernel is built for it by hiprtc at the first launch
@@ -35,6 +41,8 @@ def main():
             qpos, qvel = random_franka_state(model, nenv, 0)
         row = {"envs": nenv, "steps_per_launch": K}
         for mode, tag in ((0, "lanes16"), (1, "lane_env")):
+            if mode == 0 and "--lane-env-only" in sys.argv:
+                continue
             b = engine.Batch(cm, nenv)
             b.set_lane_env(mode)
             b.set("qpos", qpos)
@@ -47,8 +55,11 @@ def main():
             q = b.get("qpos")
             row[tag] = {"ms_per_launch": ms, "env_steps_per_s": nenv * K / (ms * 1e-3), "finite": bool(np.all(np.isfinite(q))),
                         "noise": b.noise_mode(), "resets": int(b.warning_count())}
+            if mode == 1:
+                row[tag].update(form=int(lib.mjb_lane_env_last_form()), sweep_waves=int(lib.mjb_lane_env_last_sweep_waves()))
             b.close()
-        row["ratio"] = row["lane_env"]["env_steps_per_s"] / row["lanes16"]["env_steps_per_s"]
+        if "lanes16" in row:
+            row["ratio"] = row["lane_env"]["env_steps_per_s"] / row["lanes16"]["env_steps_per_s"]
         rows.append(row)
         print(json.dumps(row), flush=True)
 
