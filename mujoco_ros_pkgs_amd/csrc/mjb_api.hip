@@ -54,6 +54,21 @@ const FieldInfo kFields[] = {
 #undef MJB_DI
 };
 
+// the FrameLayout member that holds data field i's offset (MJB_F_*)
+int FrameLayout::*const kFieldSlot[] = {
+#define MJB_DS(name, rows, cols) &FrameLayout::name,
+#define MJB_DD(name, rows, cols) &FrameLayout::name,
+#define MJB_DD2(name, rows, cols) &FrameLayout::name,
+#define MJB_DI(name, rows, cols) &FrameLayout::name,
+#include "../../include/mjb_data_fields.def"
+#undef MJB_DS
+#undef MJB_DD
+#undef MJB_DD2
+#undef MJB_DI
+};
+int &field_slot(FrameLayout &L, int i) { return L.*kFieldSlot[i]; }
+int field_slot(const FrameLayout &L, int i) { return L.*kFieldSlot[i]; }
+
 int size_by_name(const mjb_model_desc &d, const char *n)
 {
 #define MJB_SIZE(name) if (!strcmp(n, #name)) return d.name;
@@ -217,17 +232,6 @@ void compute_layout(mjb_model *M, FrameLayout &L, bool compact, int jrows_req = 
 		int c = size_by_name(d, fi.cols);
 		return r * c;
 	};
-	int *slots[] = {
-#define MJB_DS(name, rows, cols) &L.name,
-#define MJB_DD(name, rows, cols) &L.name,
-#define MJB_DD2(name, rows, cols) &L.name,
-#define MJB_DI(name, rows, cols) &L.name,
-#include "../../include/mjb_data_fields.def"
-#undef MJB_DS
-#undef MJB_DD
-#undef MJB_DD2
-#undef MJB_DI
-	};
 	bool body_sensor = false;
 	for (int i = 0; i < d.nsensor; i++)
 		if (d.sensor_objtype[i] == MJB_OBJ_BODY || d.sensor_reftype[i] == MJB_OBJ_BODY) body_sensor = true;
@@ -298,42 +302,42 @@ void compute_layout(mjb_model *M, FrameLayout &L, bool compact, int jrows_req = 
 		                           idx == MJB_F_xanchor || idx == MJB_F_xaxis || idx == MJB_F_site_xquat ||
 		                           (d.neq == 0 && (idx == MJB_F_xmat || idx == MJB_F_xquat)));
 		if (gone) {
-			*slots[idx] = -1;  // kernels test the offset
+			field_slot(L, idx) = -1;  // kernels test the offset
 			idx++;
 			continue;
 		}
 		if (xl && (idx == MJB_F_cdof || idx == MJB_F_qM || idx == MJB_F_qLD || idx == MJB_F_qLDiagInv || idx == MJB_F_contact_dist ||
 		           idx == MJB_F_contact_pos || idx == MJB_F_contact_frame || idx == MJB_F_contact_includemargin)) {
 			d_members.push_back(idx);
-			*slots[idx] = -1;  // placed below
+			field_slot(L, idx) = -1;  // placed below
 			idx++;
 			continue;
 		}
 		if (xl && (idx == MJB_F_efc_D || idx == MJB_F_efc_aref || idx == MJB_F_efc_b || idx == MJB_F_efc_force || idx == MJB_F_efc_frictionloss)) {
 			p2_members.push_back(idx);
-			*slots[idx] = -1;  // placed below
+			field_slot(L, idx) = -1;  // placed below
 			idx++;
 			continue;
 		}
 		if (in_u && !in_a && !in_b) {
 			if (idx != MJB_F_efc_J) u_members.push_back(idx);
-			*slots[idx] = -1;  // placed below
+			field_slot(L, idx) = -1;  // placed below
 			idx++;
 			continue;
 		}
 		if (no_B) {
 			if (!compact) M->field_size[idx] = n;
-			*slots[idx] = -1;  // kernels test L.efc_B >= 0
+			field_slot(L, idx) = -1;  // kernels test L.efc_B >= 0
 			idx++;
 			continue;
 		}
 		if (fi.kind == 3) {
-			*slots[idx] = ioff;
+			field_slot(L, idx) = ioff;
 			ioff += n;
 		} else if (in_a || in_b) {
-			*slots[idx] = -1;  // placed below
+			field_slot(L, idx) = -1;  // placed below
 		} else {
-			*slots[idx] = off;
+			field_slot(L, idx) = off;
 			off += n;
 			if (fi.kind == 0) nstate = off;
 		}
@@ -395,7 +399,7 @@ void compute_layout(mjb_model *M, FrameLayout &L, bool compact, int jrows_req = 
 	if (compact && xl) {
 		const int x0 = off;
 		for (int id : d_members) {
-			*slots[id] = off;
+			field_slot(L, id) = off;
 			off += fsize[id];
 		}
 		const int a0 = off;  // start of R
@@ -423,7 +427,7 @@ void compute_layout(mjb_model *M, FrameLayout &L, bool compact, int jrows_req = 
 			off += szb;
 		}
 		for (int id : u_members) {
-			*slots[id] = off;
+			field_slot(L, id) = off;
 			off += fsize[id];
 		}
 		int n_p2 = fsize[MJB_F_efc_J];
@@ -440,7 +444,7 @@ void compute_layout(mjb_model *M, FrameLayout &L, bool compact, int jrows_req = 
 		{
 			int o = jstart + fsize[MJB_F_efc_J];
 			for (int id : p2_members) {
-				*slots[id] = o;
+				field_slot(L, id) = o;
 				o += fsize[id];
 			}
 		}
@@ -480,7 +484,7 @@ void compute_layout(mjb_model *M, FrameLayout &L, bool compact, int jrows_req = 
 		}
 		if (u_ok) {
 			for (int id : u_members) {
-				*slots[id] = off;
+				field_slot(L, id) = off;
 				off += fsize[id];
 			}
 			L.efc_J = a0;
@@ -524,25 +528,12 @@ void compute_layout(mjb_model *M, FrameLayout &L, bool compact, int jrows_req = 
 	L.nstate = nstate;
 }
 
-int layout_bytes(const FrameLayout &L) { return ((L.ndouble * 8 + L.nint * 4) + 15) & ~15; }
-
 // development knob MJB_DEBUG_LAYOUT: every field's offset in the fused frame, sorted (doubles, then ints)
 void dump_layout(const mjb_model *M, const FrameLayout &L)
 {
-	const int *slots[] = {
-#define MJB_DS(name, rows, cols) &L.name,
-#define MJB_DD(name, rows, cols) &L.name,
-#define MJB_DD2(name, rows, cols) &L.name,
-#define MJB_DI(name, rows, cols) &L.name,
-#include "../../include/mjb_data_fields.def"
-#undef MJB_DS
-#undef MJB_DD
-#undef MJB_DD2
-#undef MJB_DI
-	};
 	std::vector<std::pair<int, std::string>> dd, ii;
 	for (int i = 0; i < MJB_F_COUNT; i++)
-		if (*slots[i] >= 0) (kFields[i].kind == 3 ? ii : dd).push_back({ *slots[i], kFields[i].name });
+		if (field_slot(L, i) >= 0) (kFields[i].kind == 3 ? ii : dd).push_back({ field_slot(L, i), kFields[i].name });
 	const std::pair<int, const char *> extra[] = { { L.MhB, "MhB" }, { L.qH, "qH" }, { L.qHdi, "qHdi" }, { L.nwt_M, "nwt_M" }, { L.nwt_H, "nwt_H" },
 		{ L.nwt_vec, "nwt_vec" }, { L.nwt_row, "nwt_row" }, { L.nwt_hc, "nwt_hc" }, { L.gravity, "gravity" }, { L.gfriction, "gfriction" },
 		{ L.eqparam, "eqparam" }, { L.cwrench, "cwrench" }, { L.kinloc, "kinloc" }, { L.crbbuf, "crbbuf" }, { L.eulerx, "eulerx" },
@@ -553,7 +544,7 @@ void dump_layout(const mjb_model *M, const FrameLayout &L)
 	ii.push_back({ L.dadr, "*dadr" });
 	std::sort(dd.begin(), dd.end());
 	std::sort(ii.begin(), ii.end());
-	fprintf(stderr, "mjb fused layout: %d bytes, jrows %d, hcs %d, hcd %d, ndouble %d, nint %d, nstate %d\n doubles:", layout_bytes(L), L.jrows, L.hcs,
+	fprintf(stderr, "mjb fused layout: %d bytes, jrows %d, hcs %d, hcd %d, ndouble %d, nint %d, nstate %d\n doubles:", mjb_layout_bytes(L), L.jrows, L.hcs,
 	        L.hcd, L.ndouble, L.nint, L.nstate);
 	for (auto &x : dd) fprintf(stderr, " %s@%d", x.second.c_str(), x.first);
 	fprintf(stderr, "\n ints:");
@@ -590,7 +581,7 @@ void choose_fused_layout(mjb_model *M)
 		compute_layout(M, t, true, jr);
 		// (gfx950 hands out its 160 KB of LDS in 128 granules of 1280 bytes -- measured: a 54000-byte frame runs two to a CU, a
 		//  50272-byte one three; 512-register kernels: one wave per SIMD, four envs per CU at most)
-		return std::min(4, 128 / ((layout_bytes(t) + 1279) / 1280));
+		return std::min(4, 128 / ((mjb_layout_bytes(t) + 1279) / 1280));
 	};
 	const int best = occ(16);
 	int pick = 64;
@@ -607,7 +598,7 @@ void choose_fused_layout(mjb_model *M)
 		if (occ(jr) >= 3) { wrows = jr; break; }
 	if (const char *v = getenv("MJB_WIDE_ROWS")) wrows = std::max(68, std::min(128, atoi(v)));  // measurement knob
 	compute_layout(M, M->Lw, true, wrows);
-	const int wbytes = ((M->Lw.ndouble * 8 + M->Lw.nint * 4) + 15) & ~15;
+	const int wbytes = mjb_layout_bytes(M->Lw);
 	M->has_wide = M->Lw.jrows > M->Lc.jrows && 2 * ((wbytes + 1279) / 1280) <= 128;
 	if (!M->has_wide) M->Lw = M->Lc;
 	compute_layout(M, M->Lc, true, pick);  // (compute_layout also sets model-wide derived fields: leave them as the default frame's)
@@ -1349,11 +1340,11 @@ mjb_model *mjb_compile(const mjb_model_desc *desc)
 	compute_layout(M, M->L, false);
 	{
 		const bool primal = h.nefcmax > 0 && (h.solver == MJB_SOL_NEWTON || h.solver == MJB_SOL_CG);
-		M->slot = primal && (h.nefcmax > 256 || layout_bytes(M->L) > mjb_max_lds_bytes());
+		M->slot = primal && (h.nefcmax > 256 || mjb_layout_bytes(M->L) > mjb_max_lds_bytes());
 	}
 	choose_fused_layout(M);
-	M->hbm_full = M->slot && layout_bytes(M->L) > mjb_max_lds_bytes();
-	M->hbm_fused = M->slot && layout_bytes(M->Lc) > mjb_max_lds_bytes();
+	M->hbm_full = M->slot && mjb_layout_bytes(M->L) > mjb_max_lds_bytes();
+	M->hbm_fused = M->slot && mjb_layout_bytes(M->Lc) > mjb_max_lds_bytes();
 	build_sensor_tables(M);
 	// actuators per dof (CSR, ascending actuator id)
 	M->dof_act_adr.assign((size_t)h.nv + 1, 0);
@@ -1384,7 +1375,7 @@ mjb_model *mjb_compile(const mjb_model_desc *desc)
 		});
 	}
 	{
-		const int frame_bytes = ((M->L.ndouble * 8 + M->L.nint * 4) + 15) & ~15;
+		const int frame_bytes = mjb_layout_bytes(M->L);
 		if (frame_bytes > mjb_max_lds_bytes() && !M->slot) {  // (the row-slot kernels run such a frame from HBM)
 			fail(MJB_EUNSUPPORTED, "mjb_compile: the per-env working set (%d bytes) exceeds one CU's LDS (%d bytes); "
 			                       "lower nconmax / nefcmax", frame_bytes, mjb_max_lds_bytes());
@@ -1411,24 +1402,13 @@ int mjb_frame_bytes(const mjb_model *m, int fused)
 {
 	if (!m) return fail(MJB_EINVAL, "null model");
 	const FrameLayout &L = fused == 2 ? m->Lw : (fused ? m->Lc : m->L);  // (2: the wide fused frame of kernel variant 4, == 1 when the model has none)
-	return ((L.ndouble * 8 + L.nint * 4) + 15) & ~15;
+	return mjb_layout_bytes(L);
 }
 int mjb_frame_offset(const mjb_model *m, int field, int fused)
 {
 	if (!m || field < 0 || field >= MJB_F_COUNT) return fail(MJB_EINVAL, "bad model / field");
 	const FrameLayout &L = fused ? m->Lc : m->L;
-	const int *slots[] = {
-#define MJB_DS(name, rows, cols) &L.name,
-#define MJB_DD(name, rows, cols) &L.name,
-#define MJB_DD2(name, rows, cols) &L.name,
-#define MJB_DI(name, rows, cols) &L.name,
-#include "../../include/mjb_data_fields.def"
-#undef MJB_DS
-#undef MJB_DD
-#undef MJB_DD2
-#undef MJB_DI
-	};
-	return *slots[field];
+	return field_slot(L, field);
 }
 
 void mjb_free_batch(mjb_batch *b)
@@ -1806,15 +1786,27 @@ static int join_rest(mjb_batch *b)
 	return MJB_OK;
 }
 
-// 0: no constraint rows; 1: PGS (5: PGS with elliptic contacts); 2 / 3 / 4: Newton with 1 / 2 / 4 rows per lane; 6 / 7 / 8: CG;
-// 10 / 11: Newton / CG, the row-slot solver (12 / 13 with the frame in HBM: launch())
+// the model's kernel variant (MJB_KV_*, mjb_dev.h) before launch() looks at the frame and the mode
 static int kernel_variant(const mjb_model *M)
 {
 	const mjb_model_desc &h = M->h;
-	if (h.nefcmax <= 0) return 0;
-	if (M->slot) return h.solver == MJB_SOL_CG ? 11 : 10;
-	if (h.solver == MJB_SOL_PGS) return (h.cone == MJB_CONE_ELLIPTIC && h.nconmax > 0) ? 5 : 1;
-	return (h.solver == MJB_SOL_CG ? 4 : 0) + (h.nefcmax <= 64 ? 2 : (h.nefcmax <= 128 ? 3 : 4));
+	const bool cg = h.solver == MJB_SOL_CG;
+	if (h.nefcmax <= 0) return MJB_KV_NONE;
+	if (M->slot) return cg ? MJB_KV_SLOT_CG : MJB_KV_SLOT_NEWTON;
+	if (h.solver == MJB_SOL_PGS) return (h.cone == MJB_CONE_ELLIPTIC && h.nconmax > 0) ? MJB_KV_PGS_ELL : MJB_KV_PGS;
+	if (h.nefcmax <= 64) return cg ? MJB_KV_CG1 : MJB_KV_NEWTON1;
+	if (h.nefcmax <= 128) return cg ? MJB_KV_CG2 : MJB_KV_NEWTON2;
+	return cg ? MJB_KV_CG4 : MJB_KV_NEWTON4;
+}
+
+// the dense-M build of the unconstrained 16-lane kernel (StepLaunch::dense): small Euler models without per-env inertia, not the chained step
+static int dense_build(const mjb_batch *b, int mode)
+{
+	const mjb_model_desc &h = b->model->h;
+	if (!(b->lanes == 16 && !b->env_mass && mode != MJB_MODE_STEP21 && h.integrator == MJB_INT_EULER && h.nefcmax <= 0 && h.nv <= 16 && h.nbody <= 16 && h.nu <= 16 &&
+	      h.njnt <= 16))
+		return 0;
+	return h.nv <= 8 ? 8 : (h.nv <= 12 ? 12 : 16);
 }
 
 static bool stream_capturing(hipStream_t st)
@@ -1833,7 +1825,7 @@ static bool stream_capturing(hipStream_t st)
 // constraint halves.  A slice's launches are ordered by its stream; slices share nothing (no data-path exchange between envs).
 static int split_slices(const mjb_batch *b, int nenv)
 {
-	static const int forced = [] { const char *v = getenv("MJB_SPLIT_SLICES"); return v ? atoi(v) : 0; }();  // measurement knob
+	static const int forced = mjb_env_int("MJB_SPLIT_SLICES", 0);  // measurement knob
 	// (measured on config 3, MI355X, profiles/r06_split_step.txt: two slices are best from 32 768 envs up -- 33.2 M env-steps/s against the fused kernel's
 	//  27.5 M; more slices mean shorter launches, and a launch ends with its slowest env)
 	int n = forced > 0 ? forced : 2;
@@ -1924,72 +1916,250 @@ static int launch_split(mjb_batch *b, int nsteps, int env_lo, int env_hi, hipStr
 	return MJB_OK;
 }
 
-static int launch(mjb_batch *b, int mode, int nsteps, int env_lo = 0, int env_hi = -1, hipStream_t on = nullptr)
+// what one launch() call was asked for: the decisions below read it
+struct LaunchReq {
+	int mode, nsteps, env_lo, env_hi;
+	hipStream_t stream;
+	bool whole;    // the whole batch
+	bool compact;  // runs on the fused frame
+};
+
+// facts more than one decision asks
+static bool no_env_overrides(const mjb_batch *b) { return b->hw.n == 0 && !b->env_mass && !b->env_gravity; }  // no per-env inertia / gravity, no device hwsim stage
+static bool eight_lean_frames_fit(const mjb_model *M) { return 8 * mjb_frame_bytes(M, 1) <= mjb_max_lds_bytes(); }  // ... one CU's LDS
+static bool chained_mode(int mode) { return mode == MJB_MODE_STEP21 || mode == MJB_MODE_RKMID || mode == MJB_MODE_RKLAST; }
+
+// the model's variant on the frame this launch runs on: the row-slot kernels take a frame beyond one CU's LDS from HBM
+static int frame_variant(mjb_batch *b, const LaunchReq &q, int *variant)
 {
-	if (env_hi < 0) env_hi = b->nenv;
-	hipStream_t stream = on ? on : b->stream;
-	const bool whole = env_lo == 0 && env_hi == b->nenv;
-	HIP_TRY(hipSetDevice(b->device));
-	const bool compact = mode == MJB_MODE_STEP && !b->st.use_xfrc && !b->st.keep_frame;
-	int variant = kernel_variant(b->model);
-	if ((variant == 10 || variant == 11) && (compact ? b->model->hbm_fused : b->model->hbm_full)) {
-		int wrc = ensure_ws(b);
-		if (wrc) return wrc;
-		variant += 2;
+	*variant = kernel_variant(b->model);
+	if (mjb_kv_slot(*variant) && (q.compact ? b->model->hbm_fused : b->model->hbm_full)) {
+		if (int wrc = ensure_ws(b)) return wrc;
+		*variant = mjb_kv_hbm(*variant);
 	}
-	// Which fused frame (kernel variant 4 with a wide frame): a long whole-batch launch looks at the row counters of the previous one.
-	// More than a quarter of the env-steps beyond 64 rows: the wide frame (128 rows in LDS, two envs per CU) -- measured on the
-	// power-grasp workload of config 5 (94 % beyond 64 rows): 0.72 -> 2.41 M env-steps/s; fewer than 5 %: back to the default frame
-	// (four envs per CU: the light workload runs 7.8 M on it, 4.2 M on the wide one).  MJB_WIDE_FRAME=0 / 1 pins the choice.
-	bool count_rows = false;
-	if (variant == 4 && b->model->has_wide && b->rowstat_dev) {
-		static const int pinned = [] { const char *v = getenv("MJB_WIDE_FRAME"); return v ? atoi(v) : -1; }();
-		bool want = b->wide;
-		if (pinned >= 0) want = pinned != 0;
-		else if (compact && whole && (nsteps >= 100 || b->probe_now || b->decide_now) && !stream_capturing(stream)) {  // (under stream capture nothing can be waited for: the frame stays)
-			if (b->rowstat_pending) {
-				// (the newest COMPLETED sample: a launch behind a running counting launch does not wait for it -- back-to-back launches stay
-				//  enqueued ahead of the device -- except right behind mjb_step's probe launch, whose whole point is this decision)
-				// Default: WAIT for the previous counting launch's sample (it has ended or is about to) -- the choice is then a function of the
-				// sequence of launches alone, and a rollout reproduces bit for bit.  MJB_WIDE_POLICY_NOWAIT=1: take it only if it has landed
-				// (back-to-back launches stay enqueued ahead of the device; which launch switches frames then depends on timing, results agree to
-				// rounding).  Right behind mjb_step's probe launch the wait is the point.
-				static const bool nowait = [] { const char *v = getenv("MJB_WIDE_POLICY_NOWAIT"); return v && *v == '1'; }();
-				const hipError_t q = (b->decide_now || !nowait) ? hipEventSynchronize(b->ev_rowstat) : hipEventQuery(b->ev_rowstat);
-				if (q == hipSuccess) {
-					b->rowstat_pending = false;
-					b->rowstat_ever = true;
-					const double tot = (double)b->rowstat_host[0], gt64 = (double)b->rowstat_host[1];
-					if (tot > 0) {
-						if (!b->wide && gt64 > 0.25 * tot) want = true;
-						else if (b->wide && gt64 < 0.05 * tot) want = false;
-					}
-				} else if (q != hipErrorNotReady)
-					return fail(MJB_ENODEVICE, "hipEventQuery(row counters): %s", hipGetErrorString(q));
-				else
-					(void)hipGetLastError();
-			}
-			count_rows = !b->rowstat_pending;  // (one sample in flight at a time: the pinned words belong to it)
+	return MJB_OK;
+}
+
+// Which fused frame (kernel variant 4 with a wide frame): a long whole-batch launch looks at the row counters of the previous one.
+// More than a quarter of the env-steps beyond 64 rows: the wide frame (128 rows in LDS, two envs per CU) -- measured on the
+// power-grasp workload of config 5 (94 % beyond 64 rows): 0.72 -> 2.41 M env-steps/s; fewer than 5 %: back to the default frame
+// (four envs per CU: the light workload runs 7.8 M on it, 4.2 M on the wide one).  MJB_WIDE_FRAME=0 / 1 pins the choice.
+// *count_rows: this launch counts its rows for the next one's choice.
+static int choose_fused_frame(mjb_batch *b, const LaunchReq &q, int variant, bool *count_rows)
+{
+	*count_rows = false;
+	if (!(variant == MJB_KV_NEWTON4 && b->model->has_wide && b->rowstat_dev)) return MJB_OK;
+	static const int pinned = mjb_env_int("MJB_WIDE_FRAME", -1);
+	bool want = b->wide;
+	if (pinned >= 0) want = pinned != 0;
+	else if (q.compact && q.whole && (q.nsteps >= 100 || b->probe_now || b->decide_now) && !stream_capturing(q.stream)) {  // (under stream capture nothing can be waited for: the frame stays)
+		if (b->rowstat_pending) {
+			// (the newest COMPLETED sample: a launch behind a running counting launch does not wait for it -- back-to-back launches stay
+			//  enqueued ahead of the device -- except right behind mjb_step's probe launch, whose whole point is this decision)
+			// Default: WAIT for the previous counting launch's sample (it has ended or is about to) -- the choice is then a function of the
+			// sequence of launches alone, and a rollout reproduces bit for bit.  MJB_WIDE_POLICY_NOWAIT=1: take it only if it has landed
+			// (back-to-back launches stay enqueued ahead of the device; which launch switches frames then depends on timing, results agree to
+			// rounding).  Right behind mjb_step's probe launch the wait is the point.
+			static const bool nowait = [] { const char *v = getenv("MJB_WIDE_POLICY_NOWAIT"); return v && *v == '1'; }();
+			const hipError_t e = (b->decide_now || !nowait) ? hipEventSynchronize(b->ev_rowstat) : hipEventQuery(b->ev_rowstat);
+			if (e == hipSuccess) {
+				b->rowstat_pending = false;
+				b->rowstat_ever = true;
+				const double tot = (double)b->rowstat_host[0], gt64 = (double)b->rowstat_host[1];
+				if (tot > 0) {
+					if (!b->wide && gt64 > 0.25 * tot) want = true;
+					else if (b->wide && gt64 < 0.05 * tot) want = false;
+				}
+			} else if (e != hipErrorNotReady)
+				return fail(MJB_ENODEVICE, "hipEventQuery(row counters): %s", hipGetErrorString(e));
+			else
+				(void)hipGetLastError();
 		}
-		if (want != b->wide) {
-			b->wide = want;
-			b->params_dirty = true;
-		}
+		*count_rows = !b->rowstat_pending;  // (one sample in flight at a time: the pinned words belong to it)
 	}
-	// The split step for plain-PGS models whose smooth stages have a lane = env kernel (config 3): fused launches of the whole batch (or, forced, any range)
-	bool use_split = false;
-	if (mode == MJB_MODE_STEP && compact && variant == 1 && b->model->sm_topo >= 0 && b->split_mode != 0 && b->hw.n == 0 && !b->env_mass && !b->env_gravity &&
-	    !b->env_equality && 8 * mjb_frame_bytes(b->model, 1) <= mjb_max_lds_bytes() && !stream_capturing(stream)) {
+	if (want != b->wide) {
+		b->wide = want;
+		b->params_dirty = true;
+	}
+	return MJB_OK;
+}
+
+// The split step for plain-PGS models whose smooth stages have a lane = env kernel (config 3): fused launches of the whole batch (or, forced, any range)
+static int choose_split_step(mjb_batch *b, const LaunchReq &q, int variant, bool *use_split)
+{
+	*use_split = false;
+	if (q.mode == MJB_MODE_STEP && q.compact && variant == MJB_KV_PGS && b->model->sm_topo >= 0 && b->split_mode != 0 && no_env_overrides(b) && !b->env_equality &&
+	    eight_lean_frames_fit(b->model) && !stream_capturing(q.stream)) {
 		// (automatic mode: OFF unless MJB_SPLIT_MIN_ENVS names a batch size.  Measured on config 3 at 32 768 envs, profiles/r06_split_step.txt: +21 % in the
 		//  rollout's light-contact phase, +12 % over steps 1000 - 4000, -5 % over steps 500 - 2000 -- a launch pair per step ends with the slice's slowest env,
 		//  and the heavy phase has the long PGS tails.  Not a rule to apply behind the user's back.)
-		static const int min_envs = [] { const char *v = getenv("MJB_SPLIT_MIN_ENVS"); return v ? atoi(v) : 0; }();
-		use_split = b->split_mode == 1 || (min_envs > 0 && whole && b->nenv >= min_envs);
-		if (use_split) {
-			int src = split_prepare(b);
-			if (src) return src;
+		static const int min_envs = mjb_env_int("MJB_SPLIT_MIN_ENVS", 0);
+		*use_split = b->split_mode == 1 || (min_envs > 0 && q.whole && b->nenv >= min_envs);
+		if (*use_split) return split_prepare(b);
+	}
+	return MJB_OK;
+}
+
+// which build of the plain PGS step
+static int pgs_build(const mjb_batch *b, const LaunchReq &q, int variant)
+{
+	// on the lean frame: when eight envs fit one CU's LDS, the 256-register build runs two waves per SIMD
+	if (variant == MJB_KV_PGS && q.compact && eight_lean_frames_fit(b->model)) variant = MJB_KV_PGS256;
+	static const int forced = mjb_env_int("MJB_DEBUG_VARIANT", -1);  // measurement knob
+	if ((forced == MJB_KV_PGS || forced == MJB_KV_PGS256) && (variant == MJB_KV_PGS || variant == MJB_KV_PGS256)) variant = forced;  // (only the two builds of the same PGS step are interchangeable)
+	if (chained_mode(q.mode) && variant == MJB_KV_PGS256) variant = MJB_KV_PGS;  // (the 256-register build carries no chained-step / cut-RK4 mode)
+	return variant;
+}
+
+// Steps per work item: long fused launches of the constrained kernels hand out (chunk of steps, env) work items dynamically (mjb_step.hip)
+// ... unless every env gets a slot of its own (envs <= resident envs per CU x CUs): then the queue has nothing to even out, an
+// item taken by a wave whose env's previous chunk is still running elsewhere only waits, and the launch is fastest with each
+// env's steps run back to back on its slot.  Measured on config 5 (4 envs per CU = 1024 slots, MI355X), chunked / unchunked:
+// 1024 envs x 100 steps 4.04 / 4.72 M env-steps/s, x 1000 steps 4.20 / 5.00 M, 768 envs 3.40 / 3.75 M; 1280 envs 5.32 / 3.38 M.
+// A chunked launch (*chunk > 0) gets its work counters cleared on the stream.
+static int choose_chunk(mjb_batch *b, const LaunchReq &q, int variant, int *chunk)
+{
+	bool own_slot = false;
+	if (q.compact && variant != MJB_KV_NONE) {
+		int ncu = 0;  // (of THIS batch's device: a process may drive several)
+		if (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, b->device) != hipSuccess) ncu = 0;
+		const int granules = (mjb_frame_bytes(b->model, b->wide ? 2 : 1) + 1279) / 1280;  // (gfx950: 128 LDS granules of 1280 bytes per CU)
+		const int occ = std::min(variant == MJB_KV_PGS256 ? 8 : 4, 128 / std::max(1, granules));  // (512-register kernels: one wave per SIMD)
+		own_slot = ncu > 0 && b->nenv <= occ * ncu;
+	}
+	*chunk = 0;
+	static const int forced = mjb_env_int("MJB_DEBUG_CHUNK", 0);  // measurement knob (also overrides own_slot)
+	if (q.mode == MJB_MODE_STEP && variant != MJB_KV_NONE && q.nsteps >= 100 && b->st.sched && q.whole && (!own_slot || forced > 0)) {
+		static const bool off = mjb_env_flag("MJB_DEBUG_NO_CHUNKS");  // measurement knob
+		if (!off) {
+			// (measured on MI355X: 10 - 40 steps per item are equally good on config 3; config 5 -- three envs per CU, a few heavy envs
+			//  on the critical path -- likes them finer: 3 - 5 steps per item 3.85 M, 10 steps 3.79 M, 20 steps 3.63 M)
+			*chunk = forced > 0 ? forced : (mjb_kv_newton(variant) ? std::max(5, (q.nsteps + 19) / 20) : std::max(10, (q.nsteps + 15) / 16));
+			*chunk = std::min(*chunk, 65535);
+			HIP_TRY(hipMemsetAsync(b->st.sched, 0, ((size_t)b->nenv + 1) * sizeof(int), q.stream));
 		}
 	}
+	return MJB_OK;
+}
+
+// the ctrl-noise buffer grows to `need` doubles per half (two halves when want_double): both streams drain before the old one is freed
+static int grow_noise_buffer(mjb_batch *b, const LaunchReq &q, size_t need, bool want_double)
+{
+	const size_t total = want_double ? 2 * need : need;
+	HIP_TRY(hipStreamSynchronize(q.stream));
+	if (b->noise_stream) HIP_TRY(hipStreamSynchronize(b->noise_stream));
+	if (b->zbuf) hipFree(b->zbuf);
+	b->spec_valid = false;
+	b->zbuf = dev_alloc<double>(total);
+	if (!b->zbuf) {
+		(void)hipGetLastError();
+		b->zfail = total;  // (remembered: a launch of this size or larger generates in the kernel from now on)
+	}
+	b->zcap = b->zbuf ? need : 0;
+	b->zdouble = b->zbuf && want_double;
+	if (!b->zinfo) b->zinfo = dev_alloc<unsigned int>(8);
+	if (b->zinfo) HIP_TRY(hipMemset(b->zinfo, 0xff, 8 * sizeof(unsigned int)));
+	b->zvalid = false;
+	if (b->zdouble && !b->noise_stream) {
+		HIP_TRY(hipStreamCreateWithFlags(&b->noise_stream, hipStreamNonBlocking));
+		HIP_TRY(hipEventCreateWithFlags(&b->ev_noise, hipEventDisableTiming));
+		HIP_TRY(hipEventCreateWithFlags(&b->ev_noise_go, hipEventDisableTiming));
+	}
+	b->st.zbuf = b->zbuf;
+	b->st.zinfo = b->zbuf ? b->zinfo : nullptr;
+	b->st.zhalf = (unsigned long long)b->zcap;
+	b->params_dirty = true;
+	return sync_params(b);
+}
+
+// ctrl noise of a long fused launch: its normals are generated by a throughput kernel (mjb_noise_kernel) instead of inside every
+// step's dependent chain, when they fit the budget (MJB_NOISE_PREGEN_MB = the TOTAL allocation, default 2048; 0: always inside
+// the step kernel -- same values either way).  Unconstrained kernels (one wave per SIMD, 320 VGPRs: a second kernel finds room) get
+// a buffer of two halves: this launch reads one while the other is filled, on a side stream, for the launch expected next (same
+// length, the step counter this one ends at); a launch that finds its normals ready only waits for that event, anything else
+// generates them on its own stream first.  The constrained kernels fill the register file (256 / 512 VGPRs at two / one waves per
+// SIMD): a side-stream generator only finds a slot when the step launch drains (rocprofv3 showed it spanning the whole 130 - 180 ms
+// launch), so they -- and launches whose two halves exceed the budget -- generate one half on their own stream.
+// *zuse: the launch reads pre-generated normals, from half *zhalf of the buffer.
+static int stage_ctrl_noise(mjb_batch *b, const LaunchReq &q, int variant, bool *zuse, int *zhalf)
+{
+	*zuse = false;
+	*zhalf = 0;
+	b->noise_mode = 0;
+	const int nu = b->model->h.nu;
+	if (q.mode == MJB_MODE_STEP && q.whole && b->nz.enabled && q.nsteps >= 16 && nu > 0 && nu <= b->lanes) {
+		static const size_t cap_doubles = [] { const char *v = getenv("MJB_NOISE_PREGEN_MB"); return (size_t)(v ? atol(v) : 2048) * (1u << 20) / sizeof(double); }();
+		const size_t need = (size_t)q.nsteps * b->nenv * nu;
+		const bool want_double = variant == MJB_KV_NONE && 2 * need <= cap_doubles;
+		const size_t total = want_double ? 2 * need : need;
+		if (total <= cap_doubles && total < b->zfail) {
+			if (need > b->zcap || (want_double && !b->zdouble)) {
+				if (int rc = grow_noise_buffer(b, q, need, want_double)) return rc;
+			}
+			if (b->zbuf && b->zinfo) {
+				if (b->spec_valid && b->spec_step0 == b->step_counter && b->spec_nsteps == q.nsteps) {
+					*zhalf = b->spec_half;
+					HIP_TRY(hipStreamWaitEvent(q.stream, b->ev_noise, 0));  // generated while the previous launch ran
+					b->noise_mode = 2;
+				} else {
+					if (b->spec_valid) HIP_TRY(hipStreamWaitEvent(q.stream, b->ev_noise, 0));  // (a generator still writing its half: let it finish first)
+					HIP_TRY(hipMemsetAsync(b->zinfo + 4, 0xff, 4 * sizeof(unsigned int), q.stream));
+					int nrc = mjb_launch_noise(b->params_dev, b->zbuf, b->zinfo, b->nenv, nu, q.nsteps, b->step_counter, q.stream);
+					if (nrc != 0) return fail(MJB_ENODEVICE, "noise kernel launch failed: %s", hipGetErrorString((hipError_t)nrc));
+					b->noise_mode = 1;
+				}
+				b->spec_valid = false;
+				*zuse = b->zvalid = true;
+			}
+		}
+	}
+	if (!*zuse && b->zvalid) {  // (a launch that generates its normals itself must not match a record left by an earlier one)
+		if (b->spec_valid) HIP_TRY(hipStreamWaitEvent(q.stream, b->ev_noise, 0));
+		b->spec_valid = false;
+		HIP_TRY(hipMemsetAsync(b->zinfo, 0xff, 8 * sizeof(unsigned int), q.stream));
+		b->zvalid = false;
+	}
+	return MJB_OK;
+}
+
+// the next launch's normals, into the half this one does not read, beside it (ev_noise_go: recorded ahead of this launch on its stream)
+static int speculate_ctrl_noise(mjb_batch *b, const LaunchReq &q, int zhalf_now)
+{
+	const int other = 1 - zhalf_now;
+	const unsigned int next0 = b->step_counter + (unsigned int)q.nsteps;
+	HIP_TRY(hipStreamWaitEvent(b->noise_stream, b->ev_noise_go, 0));
+	int nrc = mjb_launch_noise(b->params_dev, b->zbuf + (size_t)other * b->zcap, b->zinfo + 4 * other, b->nenv, b->model->h.nu, q.nsteps, next0, b->noise_stream);
+	if (nrc == 0) {
+		HIP_TRY(hipEventRecord(b->ev_noise, b->noise_stream));
+		b->spec_valid = true;
+		b->spec_half = other;
+		b->spec_step0 = next0;
+		b->spec_nsteps = q.nsteps;
+	}
+	return MJB_OK;
+}
+
+// The lane = env kernel (mjb_lane_env.hip) for fused launches of a model whose topology is compiled in: one env per lane, no frame.
+// Per-env model overrides, the device hwsim stage, xfrc_applied and frame dumps keep the generic kernels.
+static bool want_lane_env(const mjb_batch *b, const LaunchReq &q, int variant)
+{
+	if (!(q.mode == MJB_MODE_STEP && q.compact && variant == MJB_KV_NONE && b->model->le_topo != MJB_LE_TOPO_NONE && !b->le_unavailable && b->lane_env_mode != 0 &&
+	      no_env_overrides(b) && !b->st.stats))
+		return false;
+	static const int min_envs = mjb_env_int("MJB_LANE_ENV_MIN_ENVS", 4096);
+	return b->lane_env_mode == 1 || q.env_hi - q.env_lo >= min_envs;  // (also the fused launch of a split step's non-callback envs, mjb_step_rest)
+}
+
+static int launch(mjb_batch *b, int mode, int nsteps, int env_lo = 0, int env_hi = -1, hipStream_t on = nullptr)
+{
+	if (env_hi < 0) env_hi = b->nenv;
+	LaunchReq q = { mode, nsteps, env_lo, env_hi, on ? on : b->stream, env_lo == 0 && env_hi == b->nenv, mode == MJB_MODE_STEP && !b->st.use_xfrc && !b->st.keep_frame };
+	HIP_TRY(hipSetDevice(b->device));
+	int variant, chunk, zhalf_now, rc;
+	bool count_rows, use_split, zuse;
+	if ((rc = frame_variant(b, q, &variant))) return rc;
+	if ((rc = choose_fused_frame(b, q, variant, &count_rows))) return rc;
+	if ((rc = choose_split_step(b, q, variant, &use_split))) return rc;
 	b->split_used = use_split;
 	{  // the kernels count rows (three atomics per env-step on one address) only in the launches whose counters are read
 		unsigned long long *rs = count_rows ? b->rowstat_dev : nullptr;
@@ -1998,162 +2168,43 @@ static int launch(mjb_batch *b, int mode, int nsteps, int env_lo = 0, int env_hi
 			b->params_dirty = true;
 		}
 	}
-	int prc = sync_params(b);
-	if (prc) return prc;
+	if ((rc = sync_params(b))) return rc;
 	if (use_split) {
 		if (b->zvalid) {  // (the pre-generated ctrl-noise buffer names an older launch: this path draws its normals in the smooth kernel)
-			HIP_TRY(hipMemsetAsync(b->zinfo, 0xff, 8 * sizeof(unsigned int), stream));
+			HIP_TRY(hipMemsetAsync(b->zinfo, 0xff, 8 * sizeof(unsigned int), q.stream));
 			b->zvalid = false;
 		}
 		b->lane_env_used = false;
 		b->noise_mode = 0;
-		return launch_split(b, nsteps, env_lo, env_hi, stream);
+		return launch_split(b, nsteps, env_lo, env_hi, q.stream);
 	}
-	const int fused_id = b->wide ? 2 : 1;
-	// plain PGS on the lean frame: when eight envs fit one CU's LDS, the 256-register build runs two waves per SIMD
-	if (variant == 1 && compact && 8 * mjb_frame_bytes(b->model, 1) <= mjb_max_lds_bytes()) variant = 9;
-	{
-		static const int forced = [] { const char *v = getenv("MJB_DEBUG_VARIANT"); return v ? atoi(v) : -1; }();  // measurement knob
-		if ((forced == 1 || forced == 9) && (variant == 1 || variant == 9)) variant = forced;  // (only the two builds of the same PGS step are interchangeable)
-		if ((mode == MJB_MODE_STEP21 || mode == MJB_MODE_RKMID || mode == MJB_MODE_RKLAST) && variant == 9) variant = 1;  // (the 256-register build carries no chained-step / cut-RK4 mode)
-	}
-	// long fused launches of the constrained kernels hand out (chunk of steps, env) work items dynamically (mjb_step.hip)
-	// ... unless every env gets a slot of its own (envs <= resident envs per CU x CUs): then the queue has nothing to even out, an
-	// item taken by a wave whose env's previous chunk is still running elsewhere only waits, and the launch is fastest with each
-	// env's steps run back to back on its slot.  Measured on config 5 (4 envs per CU = 1024 slots, MI355X), chunked / unchunked:
-	// 1024 envs x 100 steps 4.04 / 4.72 M env-steps/s, x 1000 steps 4.20 / 5.00 M, 768 envs 3.40 / 3.75 M; 1280 envs 5.32 / 3.38 M.
-	bool own_slot = false;
-	if (compact && variant != 0) {
-		int ncu = 0;  // (of THIS batch's device: a process may drive several)
-		if (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, b->device) != hipSuccess) ncu = 0;
-		const int granules = (mjb_frame_bytes(b->model, fused_id) + 1279) / 1280;  // (gfx950: 128 LDS granules of 1280 bytes per CU)
-		const int occ = std::min(variant == 9 ? 8 : 4, 128 / std::max(1, granules));  // (512-register kernels: one wave per SIMD)
-		own_slot = ncu > 0 && b->nenv <= occ * ncu;
-	}
-	int chunk = 0;
-	static const int forced_chunk = [] { const char *v = getenv("MJB_DEBUG_CHUNK"); return v ? atoi(v) : 0; }();  // measurement knob (also overrides own_slot)
-	if (mode == MJB_MODE_STEP && variant != 0 && nsteps >= 100 && b->st.sched && whole && (!own_slot || forced_chunk > 0)) {
-		static const bool off = [] { const char *v = getenv("MJB_DEBUG_NO_CHUNKS"); return v && *v && *v != '0'; }();  // measurement knob
-		if (!off) {
-			const int forced = forced_chunk;
-			// (measured on MI355X: 10 - 40 steps per item are equally good on config 3; config 5 -- three envs per CU, a few heavy envs
-			//  on the critical path -- likes them finer: 3 - 5 steps per item 3.85 M, 10 steps 3.79 M, 20 steps 3.63 M)
-			const bool newton = variant >= 2 && variant <= 4;
-			chunk = forced > 0 ? forced : (newton ? std::max(5, (nsteps + 19) / 20) : std::max(10, (nsteps + 15) / 16));
-			chunk = std::min(chunk, 65535);
-			HIP_TRY(hipMemsetAsync(b->st.sched, 0, ((size_t)b->nenv + 1) * sizeof(int), stream));
-		}
-	}
-	// ctrl noise of a long fused launch: its normals are generated by a throughput kernel (mjb_noise_kernel) instead of inside every
-	// step's dependent chain, when they fit the budget (MJB_NOISE_PREGEN_MB = the TOTAL allocation, default 2048; 0: always inside
-	// the step kernel -- same values either way).  Unconstrained kernels (one wave per SIMD, 320 VGPRs: a second kernel finds room) get
-	// a buffer of two halves: this launch reads one while the other is filled, on a side stream, for the launch expected next (same
-	// length, the step counter this one ends at); a launch that finds its normals ready only waits for that event, anything else
-	// generates them on its own stream first.  The constrained kernels fill the register file (256 / 512 VGPRs at two / one waves per
-	// SIMD): a side-stream generator only finds a slot when the step launch drains (rocprofv3 showed it spanning the whole 130 - 180 ms
-	// launch), so they -- and launches whose two halves exceed the budget -- generate one half on their own stream.
-	bool zuse = false;
-	int zhalf_now = 0;
-	b->noise_mode = 0;
-	if (mode == MJB_MODE_STEP && whole && b->nz.enabled && nsteps >= 16 && b->model->h.nu > 0 && b->model->h.nu <= b->lanes) {
-		static const size_t cap_doubles = [] { const char *v = getenv("MJB_NOISE_PREGEN_MB"); return (size_t)(v ? atol(v) : 2048) * (1u << 20) / sizeof(double); }();
-		const size_t need = (size_t)nsteps * b->nenv * b->model->h.nu;
-		const bool want_double = variant == 0 && 2 * need <= cap_doubles;
-		const size_t total = want_double ? 2 * need : need;
-		if (total <= cap_doubles && total < b->zfail) {
-			if (need > b->zcap || (want_double && !b->zdouble)) {
-				HIP_TRY(hipStreamSynchronize(stream));
-				if (b->noise_stream) HIP_TRY(hipStreamSynchronize(b->noise_stream));
-				if (b->zbuf) hipFree(b->zbuf);
-				b->spec_valid = false;
-				b->zbuf = dev_alloc<double>(total);
-				if (!b->zbuf) {
-					(void)hipGetLastError();
-					b->zfail = total;  // (remembered: a launch of this size or larger generates in the kernel from now on)
-				}
-				b->zcap = b->zbuf ? need : 0;
-				b->zdouble = b->zbuf && want_double;
-				if (!b->zinfo) b->zinfo = dev_alloc<unsigned int>(8);
-				if (b->zinfo) HIP_TRY(hipMemset(b->zinfo, 0xff, 8 * sizeof(unsigned int)));
-				b->zvalid = false;
-				if (b->zdouble && !b->noise_stream) {
-					HIP_TRY(hipStreamCreateWithFlags(&b->noise_stream, hipStreamNonBlocking));
-					HIP_TRY(hipEventCreateWithFlags(&b->ev_noise, hipEventDisableTiming));
-					HIP_TRY(hipEventCreateWithFlags(&b->ev_noise_go, hipEventDisableTiming));
-				}
-				b->st.zbuf = b->zbuf;
-				b->st.zinfo = b->zbuf ? b->zinfo : nullptr;
-				b->st.zhalf = (unsigned long long)b->zcap;
-				b->params_dirty = true;
-				prc = sync_params(b);
-				if (prc) return prc;
-			}
-			if (b->zbuf && b->zinfo) {
-				if (b->spec_valid && b->spec_step0 == b->step_counter && b->spec_nsteps == nsteps) {
-					zhalf_now = b->spec_half;
-					HIP_TRY(hipStreamWaitEvent(stream, b->ev_noise, 0));  // generated while the previous launch ran
-					b->noise_mode = 2;
-				} else {
-					if (b->spec_valid) HIP_TRY(hipStreamWaitEvent(stream, b->ev_noise, 0));  // (a generator still writing its half: let it finish first)
-					zhalf_now = 0;
-					HIP_TRY(hipMemsetAsync(b->zinfo + 4, 0xff, 4 * sizeof(unsigned int), stream));
-					int nrc = mjb_launch_noise(b->params_dev, b->zbuf, b->zinfo, b->nenv, b->model->h.nu, nsteps, b->step_counter, stream);
-					if (nrc != 0) return fail(MJB_ENODEVICE, "noise kernel launch failed: %s", hipGetErrorString((hipError_t)nrc));
-					b->noise_mode = 1;
-				}
-				b->spec_valid = false;
-				zuse = b->zvalid = true;
-			}
-		}
-	}
-	if (!zuse && b->zvalid) {  // (a launch that generates its normals itself must not match a record left by an earlier one)
-		if (b->spec_valid) HIP_TRY(hipStreamWaitEvent(stream, b->ev_noise, 0));
-		b->spec_valid = false;
-		HIP_TRY(hipMemsetAsync(b->zinfo, 0xff, 8 * sizeof(unsigned int), stream));
-		b->zvalid = false;
-	}
+	variant = pgs_build(b, q, variant);
+	if ((rc = choose_chunk(b, q, variant, &chunk))) return rc;
+	if ((rc = stage_ctrl_noise(b, q, variant, &zuse, &zhalf_now))) return rc;
 	const bool zspec = zuse && b->zdouble;
-	if (zspec) HIP_TRY(hipEventRecord(b->ev_noise_go, stream));  // (everything before this launch -- the last reader of the other half -- is done)
-	if (count_rows) HIP_TRY(hipMemsetAsync(b->rowstat_dev, 0, 4 * sizeof(unsigned long long), stream));
-	// The lane = env kernel (mjb_lane_env.hip) for fused launches of a model whose topology is compiled in: one env per lane, no frame.
-	// Per-env model overrides, the device hwsim stage, xfrc_applied and frame dumps keep the generic kernels.
-	bool use_le = false;
-	if (mode == MJB_MODE_STEP && compact && variant == 0 && b->model->le_topo != MJB_LE_TOPO_NONE && !b->le_unavailable && b->lane_env_mode != 0 && b->hw.n == 0 && !b->env_mass &&
-	    !b->env_gravity && !b->st.stats) {
-		static const int min_envs = [] { const char *v = getenv("MJB_LANE_ENV_MIN_ENVS"); return v ? atoi(v) : 4096; }();
-		use_le = b->lane_env_mode == 1 || env_hi - env_lo >= min_envs;  // (also the fused launch of a split step's non-callback envs, mjb_step_rest)
-	}
+	if (zspec) HIP_TRY(hipEventRecord(b->ev_noise_go, q.stream));  // (everything before this launch -- the last reader of the other half -- is done)
+	if (count_rows) HIP_TRY(hipMemsetAsync(b->rowstat_dev, 0, 4 * sizeof(unsigned long long), q.stream));
+	bool use_le = want_lane_env(b, q, variant);
 	b->lane_env_used = use_le;
-	int rc;
 	if (use_le) {
-		rc = mjb_launch_lane_env(b->params_dev, b->model->le_topo, &b->model->h, b->nenv, env_lo, env_hi, nsteps, b->step_counter, stream);
+		rc = mjb_launch_lane_env(b->params_dev, b->model->le_topo, &b->model->h, b->nenv, env_lo, env_hi, nsteps, b->step_counter, q.stream);
 		if (rc == MJB_LE_UNAVAILABLE) {  // (no hiprtc / no kernel header / compile error: remembered, the generic kernel runs -- mjb_lane_env_info says why)
 			b->le_unavailable = true;
 			b->lane_env_used = use_le = false;
 		}
 	}
-	if (!use_le)
-	rc = mjb_launch_step(b->params_dev, compact ? (b->wide ? b->model->Lw : b->model->Lc) : b->L, env_lo, env_hi, mode, nsteps, b->step_counter, b->lanes,
-	                         b->epb, variant | (chunk << 8), (b->lanes == 16 && !b->env_mass && mode != MJB_MODE_STEP21 && b->model->h.integrator == MJB_INT_EULER && b->model->h.nefcmax <= 0 && b->model->h.nv <= 16 && b->model->h.nbody <= 16 && b->model->h.nu <= 16 && b->model->h.njnt <= 16) ? (b->model->h.nv <= 8 ? 8 : (b->model->h.nv <= 12 ? 12 : 16)) : 0, stream);
+	if (!use_le) {
+		const StepLaunch a = { b->params_dev, q.compact ? (b->wide ? &b->model->Lw : &b->model->Lc) : &b->L, env_lo, env_hi, mode, nsteps, b->step_counter,
+			                   b->lanes, b->epb, variant, chunk, dense_build(b, mode), q.stream };
+		rc = mjb_launch_step(a);
+	}
 	if (rc != 0) return fail(MJB_ENODEVICE, "kernel launch failed: %s", hipGetErrorString((hipError_t)rc));
 	if (count_rows) {  // this launch's row counters, to pinned host memory behind it
-		HIP_TRY(hipMemcpyAsync(b->rowstat_host, b->rowstat_dev, 4 * sizeof(unsigned long long), hipMemcpyDeviceToHost, stream));
-		HIP_TRY(hipEventRecord(b->ev_rowstat, stream));
+		HIP_TRY(hipMemcpyAsync(b->rowstat_host, b->rowstat_dev, 4 * sizeof(unsigned long long), hipMemcpyDeviceToHost, q.stream));
+		HIP_TRY(hipEventRecord(b->ev_rowstat, q.stream));
 		b->rowstat_pending = true;
 	}
-	if (zspec) {  // the next launch's normals, into the half this one does not read, beside it
-		const int other = 1 - zhalf_now;
-		HIP_TRY(hipStreamWaitEvent(b->noise_stream, b->ev_noise_go, 0));
-		int nrc = mjb_launch_noise(b->params_dev, b->zbuf + (size_t)other * b->zcap, b->zinfo + 4 * other, b->nenv, b->model->h.nu, nsteps,
-		                           b->step_counter + (unsigned int)nsteps, b->noise_stream);
-		if (nrc == 0) {
-			HIP_TRY(hipEventRecord(b->ev_noise, b->noise_stream));
-			b->spec_valid = true;
-			b->spec_half = other;
-			b->spec_step0 = b->step_counter + (unsigned int)nsteps;
-			b->spec_nsteps = nsteps;
-		}
-	}
+	if (zspec) return speculate_ctrl_noise(b, q, zhalf_now);
 	return MJB_OK;
 }
 
@@ -2206,20 +2257,21 @@ int mjb_set_keep_frame(mjb_batch *b, int on)
 	return MJB_OK;
 }
 
-int mjb_step1(mjb_batch *b)
+// a forward pass of the whole batch on the full frame: all of it (mjb_forward) or a step's first half (mjb_step1)
+static int forward_whole(mjb_batch *b, int mode)
 {
 	if (!b) return fail(MJB_EINVAL, "null batch");
-	int rc = ensure_ws(b);
-	if (rc) return rc;
-	rc = join_rest(b);
-	if (rc) return rc;
-	rc = launch(b, MJB_MODE_STEP1, 1);
+	if (int rc = ensure_ws(b)) return rc;
+	if (int rc = join_rest(b)) return rc;
+	int rc = launch(b, mode, 1);
 	if (rc == MJB_OK) {
 		b->frame_valid = true;
 		b->frame_hi = b->nenv;
 	}
 	return rc;
 }
+
+int mjb_step1(mjb_batch *b) { return forward_whole(b, MJB_MODE_STEP1); }
 
 int mjb_step2(mjb_batch *b)
 {
@@ -2287,47 +2339,49 @@ int mjb_step_rest(mjb_batch *b, int ncb)
 	return rc;
 }
 
-int mjb_step2_prefix(mjb_batch *b, int ncb)
+// What the closers of a prefix step share.  Before their launch: a caller that skipped mjb_step_rest -- the rest must not miss the step;
+// and the prefix's first half must have left its frames (who: the function the user called)
+static int prefix_second_half(mjb_batch *b, int ncb, const char *who)
 {
-	if (!b || ncb != b->split_ncb) return fail(MJB_EINVAL, "mjb_step2_prefix without the matching mjb_step1_prefix");
 	int rc = MJB_OK;
-	if (!b->split_rest_done) rc = mjb_step_rest(b, ncb);  // (a caller that skipped it: the rest must not miss the step)
+	if (!b->split_rest_done) rc = mjb_step_rest(b, ncb);
 	if (rc != MJB_OK) return rc;
-	if (ncb > 0) {
-		if (!b->frame_valid || !b->st.frame_ws || b->frame_hi < ncb) return fail(MJB_EINVAL, "mjb_step2_prefix without a preceding mjb_step1_prefix");
-		rc = launch(b, MJB_MODE_STEP2, 1, 0, ncb);
-	}
-	if (b->rest_pending) {  // join: whatever follows on the batch's stream sees the rest's step too
-		HIP_TRY(hipStreamWaitEvent(b->stream, b->ev_join, 0));
-		b->rest_pending = false;
-	}
+	if (ncb > 0 && (!b->frame_valid || !b->st.frame_ws || b->frame_hi < ncb)) return fail(MJB_EINVAL, "%s without a preceding mjb_step1_prefix", who);
+	return MJB_OK;
+}
+
+// ... and behind it (rc: the launch's result): join -- whatever follows on the batch's stream sees the rest's step too --, then the step is counted
+static int prefix_step_done(mjb_batch *b, int rc)
+{
+	if (int jrc = join_rest(b)) return jrc;
 	if (rc == MJB_OK) {
 		b->step_counter += 1;
 		b->steps_taken += 1;
-		b->split_ncb = -1;
 	}
+	return rc;
+}
+
+int mjb_step2_prefix(mjb_batch *b, int ncb)
+{
+	if (!b || ncb != b->split_ncb) return fail(MJB_EINVAL, "mjb_step2_prefix without the matching mjb_step1_prefix");
+	int rc = prefix_second_half(b, ncb, "mjb_step2_prefix");
+	if (rc != MJB_OK) return rc;
+	if (ncb > 0) rc = launch(b, MJB_MODE_STEP2, 1, 0, ncb);
+	rc = prefix_step_done(b, rc);
+	if (rc == MJB_OK) b->split_ncb = -1;
 	return rc;
 }
 
 int mjb_step21_prefix(mjb_batch *b, int ncb)
 {
 	if (!b || ncb != b->split_ncb) return fail(MJB_EINVAL, "mjb_step21_prefix without the matching mjb_step1_prefix");
-	int rc = MJB_OK;
-	if (!b->split_rest_done) rc = mjb_step_rest(b, ncb);
+	int rc = prefix_second_half(b, ncb, "mjb_step21_prefix");
 	if (rc != MJB_OK) return rc;
-	if (ncb > 0) {
-		if (!b->frame_valid || !b->st.frame_ws || b->frame_hi < ncb) return fail(MJB_EINVAL, "mjb_step21_prefix without a preceding mjb_step1_prefix");
-		// (trip 1 of the launch -- the next step's first half -- draws its ctrl noise at step_counter + 1, as mjb_step1_prefix would
-		//  after mjb_step2_prefix advanced the counter)
-		rc = launch(b, MJB_MODE_STEP21, 1, 0, ncb);
-	}
-	if (b->rest_pending) {  // join: whatever follows on the batch's stream sees the rest's step too
-		HIP_TRY(hipStreamWaitEvent(b->stream, b->ev_join, 0));
-		b->rest_pending = false;
-	}
+	// (trip 1 of the launch -- the next step's first half -- draws its ctrl noise at step_counter + 1, as mjb_step1_prefix would
+	//  after mjb_step2_prefix advanced the counter)
+	if (ncb > 0) rc = launch(b, MJB_MODE_STEP21, 1, 0, ncb);
+	rc = prefix_step_done(b, rc);
 	if (rc == MJB_OK) {
-		b->step_counter += 1;
-		b->steps_taken += 1;
 		b->split_ncb = ncb;  // ... and the next split step is open: its first half has run
 		b->split_rest_done = false;
 		b->frame_valid = true;
@@ -2346,37 +2400,16 @@ int mjb_step2_rk_prefix(mjb_batch *b, int ncb, int rk)
 {
 	if (!b || ncb != b->split_ncb || rk < 0 || rk > 3) return fail(MJB_EINVAL, "mjb_step2_rk_prefix without the matching mjb_step1_prefix, or evaluation index outside 0..3");
 	if (b->model->h.integrator != MJB_INT_RK4) return fail(MJB_EINVAL, "mjb_step2_rk_prefix: the model's integrator is not RK4");
-	int rc = MJB_OK;
-	if (!b->split_rest_done) rc = mjb_step_rest(b, ncb);
+	int rc = prefix_second_half(b, ncb, "mjb_step2_rk_prefix");
 	if (rc != MJB_OK) return rc;
-	if (ncb > 0) {
-		if (!b->frame_valid || !b->st.frame_ws || b->frame_hi < ncb) return fail(MJB_EINVAL, "mjb_step2_rk_prefix without a preceding mjb_step1_prefix");
-		rc = launch(b, rk == 3 ? MJB_MODE_RKLAST : MJB_MODE_RKMID, rk, 0, ncb);  // (the evaluation index travels as the kernel's nsteps)
-	}
+	if (ncb > 0) rc = launch(b, rk == 3 ? MJB_MODE_RKLAST : MJB_MODE_RKMID, rk, 0, ncb);  // (the evaluation index travels as the kernel's nsteps)
 	if (rc != MJB_OK || rk < 3) return rc;
-	rc = join_rest(b);
-	if (rc == MJB_OK) {
-		b->step_counter += 1;
-		b->steps_taken += 1;
-		b->split_ncb = -1;
-	}
+	rc = prefix_step_done(b, rc);
+	if (rc == MJB_OK) b->split_ncb = -1;
 	return rc;
 }
 
-int mjb_forward(mjb_batch *b)
-{
-	if (!b) return fail(MJB_EINVAL, "null batch");
-	int rc = ensure_ws(b);
-	if (rc) return rc;
-	rc = join_rest(b);
-	if (rc) return rc;
-	rc = launch(b, MJB_MODE_FORWARD, 1);
-	if (rc == MJB_OK) {
-		b->frame_valid = true;
-		b->frame_hi = b->nenv;
-	}
-	return rc;
-}
+int mjb_forward(mjb_batch *b) { return forward_whole(b, MJB_MODE_FORWARD); }
 
 int mjb_reset(mjb_batch *b, const uint8_t *mask)
 {
@@ -2417,21 +2450,7 @@ static double *state_ptr(mjb_batch *b, int field)
 	}
 }
 
-static int frame_offset(const mjb_batch *b, int field)
-{
-	const int *slots[] = {
-#define MJB_DS(name, rows, cols) &b->L.name,
-#define MJB_DD(name, rows, cols) &b->L.name,
-#define MJB_DD2(name, rows, cols) &b->L.name,
-#define MJB_DI(name, rows, cols) &b->L.name,
-#include "../../include/mjb_data_fields.def"
-#undef MJB_DS
-#undef MJB_DD
-#undef MJB_DD2
-#undef MJB_DI
-	};
-	return *slots[field];
-}
+static int frame_offset(const mjb_batch *b, int field) { return field_slot(b->L, field); }
 
 static int check_range(mjb_batch *b, int field, int lo, int hi)
 {

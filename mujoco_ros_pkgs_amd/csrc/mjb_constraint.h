@@ -1066,16 +1066,16 @@ template <int G, int TAG> STAGE void make_constraint(CModel m, CLayout L, CState
 	int *fi = e.fi;
 	const int lane = e.lane, nv = m.nv;
 	[[maybe_unused]] RowBlock gb{};
-	if constexpr (TAG == 4)
+	if constexpr (TAG == MJB_KV_NEWTON4)
 		if (s.efc_Jg) gb = mjb_rowblock(s.efc_Jg + (size_t)e.env * s.efc_Jg_stride, m.nefcmax, nv, m.nconmax, L.hcs);
 	[[maybe_unused]] double *Jg = gb.J;
 	auto jrow = [&](int r) -> double * {  // row r of efc_J
-		if constexpr (TAG == 4) return r < L.jrows ? f + L.efc_J + r * nv : Jg + (size_t)r * nv;
+		if constexpr (TAG == MJB_KV_NEWTON4) return r < L.jrows ? f + L.efc_J + r * nv : Jg + (size_t)r * nv;
 		else return f + L.efc_J + r * nv;
 	};
 	// the other per-row arrays: rows >= L.rcap (X-layout fused frame of variant 4 only) go to the env's block in HBM
 	auto rstore = [&](int i, double pos, double margin, const RowGain &g, double R) {
-		if constexpr (TAG == 4) {
+		if constexpr (TAG == MJB_KV_NEWTON4) {
 			if (i >= L.rcap) {  // (a lean primal frame: D, and aref / b as row_store parks them)
 				gb.D[i] = 1.0 / R;
 				gb.aref[i] = g.K * g.imp * (pos - margin);
@@ -1086,7 +1086,7 @@ template <int G, int TAG> STAGE void make_constraint(CModel m, CLayout L, CState
 		row_store(L, f, i, pos, margin, g, R);
 	};
 	auto rtag = [&](int i, int type, int id) {
-		if constexpr (TAG == 4) {
+		if constexpr (TAG == MJB_KV_NEWTON4) {
 			if (i >= L.rcap) {
 				gb.type[i] = type;
 				gb.id[i] = id;
@@ -1097,7 +1097,7 @@ template <int G, int TAG> STAGE void make_constraint(CModel m, CLayout L, CState
 		fi[L.efc_type + i] = type;
 	};
 	auto rfl = [&](int i, double v) {
-		if constexpr (TAG == 4) {
+		if constexpr (TAG == MJB_KV_NEWTON4) {
 			if (i >= L.rcap) {
 				gb.fl[i] = v;
 				return;
@@ -1404,7 +1404,7 @@ template <int G, int TAG> STAGE void make_constraint(CModel m, CLayout L, CState
 	EPROF(21);
 #endif
 	for (int r = lane; r < nefc; r += G) {
-		if constexpr (TAG == 4) {
+		if constexpr (TAG == MJB_KV_NEWTON4) {
 			if (r >= L.rcap) {
 				gb.force[r] = 0;
 				continue;
@@ -1504,7 +1504,7 @@ template <int G, int TAG> STAGE void make_constraint(CModel m, CLayout L, CState
 		}
 	}
 	gsync<G>();
-	if constexpr (TAG == 4) {
+	if constexpr (TAG == MJB_KV_NEWTON4) {
 		if (Jg && nefc > L.jrows) {  // (wave-uniform) more rows than the frame holds: the solver reads all of J from HBM
 			MJB_KEEP_BRANCH();
 			for (int t = lane; t < L.jrows * nv; t += G) Jg[t] = f[L.efc_J + t];
@@ -1644,7 +1644,7 @@ template <int G, int TAG> STAGE void reference_constraint(CModel m, CLayout L, C
 		}
 	}
 	};
-	if constexpr (TAG == 4) {  // (see make_constraint: all of J -- on a row-capped frame all row data -- sits in HBM when the rows outnumber the frame's share)
+	if constexpr (TAG == MJB_KV_NEWTON4) {  // (see make_constraint: all of J -- on a row-capped frame all row data -- sits in HBM when the rows outnumber the frame's share)
 		if (st.efc_Jg && nefc > L.jrows) {
 			MJB_KEEP_BRANCH();
 			const RowBlock gb = mjb_rowblock(st.efc_Jg + (size_t)e.env * st.efc_Jg_stride, m.nefcmax, nv, m.nconmax, L.hcs);

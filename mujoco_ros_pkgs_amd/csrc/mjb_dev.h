@@ -282,6 +282,46 @@ struct KernelParams {
 	HwSim hw;
 };
 
+// ---- the step kernel's variants: the value of mjb_step_kernel's template parameter CON (TAG in the constraint stages), of MJB_DEV_ONLY_CON and
+// MJB_DEBUG_VARIANT, and the number DESIGN.md, the tests and the tools call a variant by.  Separate kernels keep each instruction stream and
+// register budget small (mjb_step.hip, "the kernel").  The predicates below are what the kernels and the host ask of a variant; this header is
+// also compiled by hiprtc, so they are plain constexpr functions of int.
+enum {
+	MJB_KV_NONE = 0,                                             // model without constraint rows
+	MJB_KV_PGS = 1,                                              // PGS, 512-register build
+	MJB_KV_NEWTON1 = 2, MJB_KV_NEWTON2 = 3, MJB_KV_NEWTON4 = 4,  // Newton, 1 / 2 / 4 rows per lane in registers (nefcmax <= 64 / 128 / 256); 4: the fused frame
+	                                                             //   holds FrameLayout::jrows rows of efc_J, the rest lives in DevState::efc_Jg
+	MJB_KV_PGS_ELL = 5,                                          // PGS with elliptic cone blocks
+	MJB_KV_CG1 = 6, MJB_KV_CG2 = 7, MJB_KV_CG4 = 8,              // CG (the Newton solver without its Hessian), 1 / 2 / 4 rows per lane
+	MJB_KV_PGS256 = 9,                                           // the plain PGS step under a 256-register cap (eight lean frames fit one CU's LDS: two waves per SIMD)
+	MJB_KV_SLOT_NEWTON = 10, MJB_KV_SLOT_CG = 11,                // the row-slot solver (up to 1024 rows), Newton / CG, frame in LDS
+	MJB_KV_SLOT_NEWTON_HBM = 12, MJB_KV_SLOT_CG_HBM = 13,        // the same with the frame in HBM (DevState::frame_ws)
+};
+constexpr bool mjb_kv_pgs(int v) { return v == MJB_KV_PGS || v == MJB_KV_PGS_ELL || v == MJB_KV_PGS256; }
+constexpr bool mjb_kv_newton(int v) { return v >= MJB_KV_NEWTON1 && v <= MJB_KV_NEWTON4; }  // register-row Newton
+constexpr bool mjb_kv_cg(int v) { return v >= MJB_KV_CG1 && v <= MJB_KV_CG4; }              // register-row CG
+constexpr bool mjb_kv_slot(int v) { return v >= MJB_KV_SLOT_NEWTON && v <= MJB_KV_SLOT_CG_HBM; }
+constexpr bool mjb_kv_slot_cg(int v) { return v == MJB_KV_SLOT_CG || v == MJB_KV_SLOT_CG_HBM; }  // the CG one of a row-slot pair
+constexpr bool mjb_kv_hbm_frame(int v) { return v == MJB_KV_SLOT_NEWTON_HBM || v == MJB_KV_SLOT_CG_HBM; }
+constexpr int mjb_kv_hbm(int v) { return v == MJB_KV_SLOT_NEWTON ? MJB_KV_SLOT_NEWTON_HBM : (v == MJB_KV_SLOT_CG ? MJB_KV_SLOT_CG_HBM : v); }  // its build for a frame in HBM
+constexpr int mjb_kv_rows_per_lane(int v) { return (v == MJB_KV_NEWTON4 || v == MJB_KV_CG4) ? 4 : ((v == MJB_KV_NEWTON2 || v == MJB_KV_CG2) ? 2 : 1); }  // register-row solvers
+// carries the chained-step / cut-RK4 modes (MJB_MODE_STEP21, RKMID, RKLAST); dense: the kernel's DENSE parameter
+constexpr bool mjb_kv_chained(int v, int dense) { return dense == 0 && v != MJB_KV_PGS256; }
+// minimum waves per SIMD of __launch_bounds__: G lanes per env (unconstrained kernels), occ = MJB_DEV_OCC (the 512-register kernels)
+constexpr int mjb_kv_min_waves(int v, int G, int occ) { return v == MJB_KV_NONE ? (G == 64 ? 4 : (G == 32 ? 2 : 1)) : ((mjb_kv_cg(v) || v == MJB_KV_PGS256 || mjb_kv_slot_cg(v)) ? 2 : occ); }
+// the build slice (Makefile: GROUPS, mjb_step.hip: MJB_GROUP) a variant is compiled in; slice 6 is the split step's constraint kernel
+constexpr int mjb_kv_slice(int v) { return v == MJB_KV_NONE ? 0 : (v == MJB_KV_PGS256 ? 5 : (mjb_kv_pgs(v) ? 1 : (v == MJB_KV_NEWTON4 ? 3 : (mjb_kv_newton(v) ? 2 : (mjb_kv_cg(v) ? 4 : (mjb_kv_hbm_frame(v) ? 8 : 7)))))); }
+
+constexpr int mjb_max_lds_bytes() { return 160 * 1024; }  // LDS of one gfx950 CU
+inline int mjb_layout_bytes(const FrameLayout &L) { return ((L.ndouble * 8 + L.nint * 4) + 15) & ~15; }  // one env's frame, rounded to 16 bytes
+
+#ifndef __HIPCC_RTC__
+#include <cstdlib>
+// knobs read from the environment (host code).  A knob read once per process is a `static const` at its point of use, initialised by one of these.
+inline int mjb_env_int(const char *name, int dflt) { const char *v = getenv(name); return v ? atoi(v) : dflt; }
+inline bool mjb_env_flag(const char *name) { const char *v = getenv(name); return v && *v && *v != '0'; }
+#endif
+
 enum { MJB_MODE_STEP = 0, MJB_MODE_FORWARD = 1, MJB_MODE_STEP1 = 2, MJB_MODE_STEP2 = 3, MJB_MODE_STEP21 = 4 /* STEP2 of one step, then STEP1 of the next */,
        // STEP2 of an RK4 step cut at the callback points of its evaluations (mjb_step2_rk_prefix; the evaluation index travels in the
        // kernel's `nsteps` argument): RKMID = second half of evaluation rk, rk4_stage(rk), first half of evaluation rk + 1;
@@ -289,12 +329,22 @@ enum { MJB_MODE_STEP = 0, MJB_MODE_FORWARD = 1, MJB_MODE_STEP1 = 2, MJB_MODE_STE
        MJB_MODE_RKMID = 5, MJB_MODE_RKLAST = 6 };
 
 // launches (implemented in mjb_step.hip); returns hipError_t as int
-// (steps envs [env_lo, nenv): the whole batch, or a prefix / the rest for the split steps of the host runtime)
+// (a step launch covers the whole batch, or a prefix / the rest for the split steps of the host runtime)
 int mjb_launch_noise(const KernelParams *Pdev, double *zbuf, unsigned int *zinfo, int nenv, int nu, int nsteps, unsigned int step0, void *stream);
-int mjb_launch_step(const KernelParams *Pdev, const FrameLayout &L, int env_lo, int nenv, int mode, int nsteps, unsigned int step0,
-                    int lanes_per_env, int envs_per_block, int constrained, int dense, void *stream);
+struct StepLaunch {
+	const KernelParams *params;  // device copy
+	const FrameLayout *L;        // the layout the kernel runs on (host copy)
+	int env_lo, env_hi;          // steps envs [env_lo, env_hi)
+	int mode, nsteps;            // MJB_MODE_*; steps of a fused launch (cut-RK4 modes: the evaluation index)
+	unsigned int step0;          // the step counter the launch starts at
+	int lanes, epb;              // lanes per env, envs per block
+	int variant;                 // MJB_KV_*
+	int chunk;                   // steps per work item of a chunked launch, 0 = one item per env
+	int dense;                   // unconstrained 16-lane kernels: 8 / 12 / 16 = the dense-M build for nv up to that, 0 = the generic one
+	void *stream;
+};
+int mjb_launch_step(const StepLaunch &a);
 int mjb_launch_reset(const KernelParams *Pdev, int nenv, const unsigned char *mask_dev, void *stream);
-int mjb_max_lds_bytes();
 // lane = env form of the unconstrained fused step (mjb_lane_env.hip)
 int mjb_lane_env_match(const mjb_model_desc *h);
 size_t mjb_lane_env_tape_doubles(const mjb_model_desc *h);      // size of the constant tape

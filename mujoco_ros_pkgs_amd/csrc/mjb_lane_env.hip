@@ -523,14 +523,15 @@ int mjb_launch_lane_env(const KernelParams *Pdev, int topo, const mjb_model_desc
 	const int n = env_hi - env_lo;
 	if (n <= 0) return 0;
 	// (measurement knob: envs per wavefront < 64 -- the wavefront starts with its upper lanes off)
-	static const int wl = [] { const char *v = getenv("MJB_LANE_ENV_WAVE_LANES"); const int k = v ? atoi(v) : 64; return (k == 16 || k == 32) ? k : 64; }();
+	static const int wl_env = mjb_env_int("MJB_LANE_ENV_WAVE_LANES", 64);
+	const int wl = (wl_env == 16 || wl_env == 32) ? wl_env : 64;
 	const dim3 grid((unsigned int)((n + wl - 1) / wl)), block(wl);
 	// LDS budget per wavefront from the CUs the launch leaves idle: one wavefront per CU may take all of its LDS
 	// (per DEVICE: a process may drive several GPUs, one batch each -- ADVICE r05)
 	int cur_dev = 0;
 	(void)hipGetDevice(&cur_dev);
 	const int ncu = device_cus(cur_dev);
-	static const int forced = [] { const char *v = getenv("MJB_LANE_ENV_LDS_KB"); return v ? atoi(v) : 0; }();  // measurement knob: 40 / 80 / 160
+	static const int forced = mjb_env_int("MJB_LANE_ENV_LDS_KB", 0);  // measurement knob: 40 / 80 / 160
 	// (from the BATCH's size, not the launch's env range: the instantiations differ in where data waits, and the compiler contracts a
 	//  few multiply-adds differently around that -- results agree to rounding, not bit for bit -- so every launch of one batch, whole or
 	//  a prefix / the rest of a split step, runs the same one)
@@ -539,10 +540,10 @@ int mjb_launch_lane_env(const KernelParams *Pdev, int topo, const mjb_model_desc
 	if (forced == 40 || forced == 80 || forced == 160) lp = forced;
 	// DUO: two wavefronts per 64 envs (mjb_lane_env_kernel.h) while the batch leaves at least every second SIMD idle -- the step's
 	// position half and velocity half side by side.  MJB_LANE_ENV_DUO=0 / 1: never / whenever the LDS budget allows (measurement knob)
-	static const int duo_env = [] { const char *v = getenv("MJB_LANE_ENV_DUO"); return v ? atoi(v) : -1; }();
+	static const int duo_env = mjb_env_int("MJB_LANE_ENV_DUO", -1);
 	const int form_ov = le_form_override.load();
 	const int duo_mode = form_ov >= 0 ? form_ov : duo_env;
-	static const int duo_max_waves = [] { const char *v = getenv("MJB_LANE_ENV_DUO_MAX_WAVES"); return v ? atoi(v) : -1; }();
+	static const int duo_max_waves = mjb_env_int("MJB_LANE_ENV_DUO_MAX_WAVES", -1);
 	int duo = (wl == 64 && lp >= 80 && duo_mode != 0 && (duo_mode > 0 || waves <= (duo_max_waves >= 0 ? duo_max_waves : 2 * ncu))) ? 1 : 0;
 	// ... pipelined (nothing computed twice) when a workgroup has a CU's LDS to itself.  MJB_LANE_ENV_DUO=1: the two-halves form only
 	if (duo && lp == 160 && duo_mode != 1) duo = 2;
@@ -550,7 +551,8 @@ int mjb_launch_lane_env(const KernelParams *Pdev, int topo, const mjb_model_desc
 	if (duo == 2 && duo_mode != 2 && 3 * waves <= 4 * ncu) duo = 3;
 	// ... FOUR when the block still has a SIMD of its CU to itself per wavefront: the pose wavefront's chain cut in two (mjb_lane_env_kernel.h, roles 8 - 11).
 	// MJB_LANE_ENV_SWEEP_WAVES=3 / 4: the measurement knob (mjb_lane_env_set_sweep_waves goes first)
-	static const int sweep_env = [] { const char *v = getenv("MJB_LANE_ENV_SWEEP_WAVES"); const int k = v ? atoi(v) : 0; return (k == 3 || k == 4) ? k : 0; }();
+	static const int sweep_knob = mjb_env_int("MJB_LANE_ENV_SWEEP_WAVES", 0);
+	const int sweep_env = (sweep_knob == 3 || sweep_knob == 4) ? sweep_knob : 0;
 	const int sweep_set = le_sweep_override.load();
 	const int sweep_ov = sweep_set ? sweep_set : sweep_env;
 	int sweep = duo == 3 ? (sweep_ov ? sweep_ov : (waves <= ncu ? 4 : 3)) : 0;
@@ -610,7 +612,7 @@ int mjb_launch_lane_env(const KernelParams *Pdev, int topo, const mjb_model_desc
 		return (int)hipGetLastError();                                                                                                        \
 	}
 #define MJB_LE_GO_DUO2(T)                                                                                                                   \
-	if constexpr (duo2_bytes<T>() <= 160 * 1024) {                                                                                            \
+	if constexpr (duo2_bytes<T>() <= mjb_max_lds_bytes()) {                                                                                            \
 		auto kern = mjb_lane_env_duo2_kernel<T>;                                                                                              \
 		constexpr int bytes = duo2_bytes<T>();                                                                                                \
 		const hipError_t attr = lds_attr_once(reinterpret_cast<const void *>(kern), bytes, cur_dev);                                          \
@@ -620,7 +622,7 @@ int mjb_launch_lane_env(const KernelParams *Pdev, int topo, const mjb_model_desc
 		return (int)hipGetLastError();                                                                                                        \
 	}
 #define MJB_LE_GO_TRIO(T, NW)                                                                                                               \
-	if constexpr ((NW == 4 ? quartet_bytes<T>() : trio_bytes<T>()) <= 160 * 1024) {                                                           \
+	if constexpr ((NW == 4 ? quartet_bytes<T>() : trio_bytes<T>()) <= mjb_max_lds_bytes()) {                                                           \
 		auto kern = mjb_lane_env_trio_kernel<T, NW>;                                                                                          \
 		constexpr int bytes = NW == 4 ? quartet_bytes<T>() : trio_bytes<T>();                                                                 \
 		const hipError_t attr = lds_attr_once(reinterpret_cast<const void *>(kern), bytes, cur_dev);                                          \

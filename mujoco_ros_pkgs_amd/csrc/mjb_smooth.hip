@@ -102,7 +102,7 @@ int mjb_launch_smooth(const KernelParams *Pdev, int topo, int env_lo, int env_hi
 	if (topo == id) {                                                                                                                    \
 		auto kern = mjb_smooth_kernel<T>;                                                                                                \
 		constexpr int bytes = Sq<T>::bytes();                                                                                            \
-		static_assert(bytes <= 160 * 1024, "smooth kernel: cdof, forces and inertias of the topology need more than a CU's LDS");       \
+		static_assert(bytes <= mjb_max_lds_bytes(), "smooth kernel: cdof, forces and inertias of the topology need more than a CU's LDS");       \
 		const hipError_t attr = sm_lds_attr(reinterpret_cast<const void *>(kern), bytes, dev);                                           \
 		if (attr != hipSuccess) return (int)attr;                                                                                        \
 		hipLaunchKernelGGL(kern, grid, block, bytes, (hipStream_t)stream, (const KernelParams MJB_AS4 *)Pdev, step, flags, env_lo, env_hi); \

@@ -3077,7 +3077,7 @@ template <int G, int CON, int DENSE> DEVI void forward_first(const KernelParams 
 	if constexpr (DENSE)
 		VIEW(P, compact, factor_dense16<G, DENSE>(m, e, e.f + L.qM, e.f + L.qLD, e.f + L.qLDiagInv, e.f + L.MhB, e.f + L.qH,
 		                                   e.f + L.qHdi, m.eulerdamp != 0, e.dadr, e.f + L.crbbuf));
-	else if constexpr (CON != 0) {
+	else if constexpr (CON != MJB_KV_NONE) {
 		if (P->m.nv <= 16)
 			VIEW(P, compact, {
 				int dl[16];
@@ -3085,7 +3085,7 @@ template <int G, int CON, int DENSE> DEVI void forward_first(const KernelParams 
 				factor_dense16<G, 16>(m, e, e.f + L.qM, e.f + L.qLD, e.f + L.qLDiagInv, e.f + L.MhB, e.f + L.qH, e.f + L.qHdi,
 				                      m.eulerdamp != 0, dl, e.f + L.crbbuf);
 			});
-		else if ((CON >= 2 && CON <= 4) && P->m.nv <= 32)  // (the 512-register Newton kernels, like TRI32 below)
+		else if (mjb_kv_newton(CON) && P->m.nv <= 32)  // (the 512-register Newton kernels, like TRI32 below)
 			VIEW(P, compact, {
 				if (m.flv_n > 0) {
 					MJB_KEEP_BRANCH();
@@ -3103,7 +3103,7 @@ template <int G, int CON, int DENSE> DEVI void forward_first(const KernelParams 
 		                            m.eulerdamp != 0));
 	}
 	PROF(3);
-	if constexpr (CON) {
+	if constexpr (CON != MJB_KV_NONE) {
 		MJB_REP(16) VIEW(P, compact, collision<G>(m, L, s, e));
 		PROF(16);
 	}
@@ -3112,19 +3112,19 @@ template <int G, int CON, int DENSE> DEVI void forward_first(const KernelParams 
 	// efc_J can overlay what the position / velocity stages no longer need (mjb_api.hip, compute_layout); on the full frame
 	// (mjb_forward / mjb_step1, whose callers may look at efc_* / contacts between the halves) in MuJoCo's place.  ONE copy of
 	// the stages in the instruction stream: a two-trip loop picks the trip they run in.
-	const int con_trip = (CON != 0 && compact) ? 1 : 0;
+	const int con_trip = (CON != MJB_KV_NONE && compact) ? 1 : 0;
 #pragma nounroll
-	for (int trip = 0; trip < (CON != 0 ? 2 : 1); trip++) {
-		if constexpr (CON != 0) {
+	for (int trip = 0; trip < (CON != MJB_KV_NONE ? 2 : 1); trip++) {
+		if constexpr (CON != MJB_KV_NONE) {
 			if (trip == con_trip) {
 				PROF_BEGIN();
 				MJB_REP(17) {
 				VIEW(P, compact, make_constraint<G, CON>(m, L, s, e));
 				PROF(17);
-				if constexpr (CON == 1 || CON == 5 || CON == 9) {
+				if constexpr (mjb_kv_pgs(CON)) {
 					// (plain PGS, nv <= 16: the rows of B = J M^-1 are solved for inside the PGS stage, in registers)
 					if (P->m.nv > 16) VIEW(P, compact, project_constraint<G, CON>(m, L, e));
-					else if constexpr (CON == 5) VIEW(P, compact, project_constraint_dense16<G, CON>(m, L, e));
+					else if constexpr (CON == MJB_KV_PGS_ELL) VIEW(P, compact, project_constraint_dense16<G, CON>(m, L, e));
 				}
 				VIEW(P, compact, reference_constraint<G, CON>(m, L, s, e));
 				}
@@ -3154,9 +3154,9 @@ template <int G, int CON, int DENSE> DEVI void forward_rest(const KernelParams M
 	PROF_BEGIN();
 	MJB_REP(9) VIEW(P, compact, fwd_actuation<G, (DENSE != 0)>(m, L, e));
 	PROF(9);
-	MJB_REP(10) VIEW(P, compact, fwd_acceleration<G, (CON != 0 ? -1 : DENSE), (CON >= 2 && CON <= 4)>(m, L, e, s.use_xfrc != 0));  // (TRI32: the Newton kernels -- in the PGS ones its 124 registers bring back the spill-before-exec-restore pattern)
+	MJB_REP(10) VIEW(P, compact, fwd_acceleration<G, (CON != MJB_KV_NONE ? -1 : DENSE), mjb_kv_newton(CON)>(m, L, e, s.use_xfrc != 0));  // (TRI32: the Newton kernels -- in the PGS ones its 124 registers bring back the spill-before-exec-restore pattern)
 	PROF(10);
-	if constexpr (CON == 4 && G == 64) {
+	if constexpr (CON == MJB_KV_NEWTON4 && G == 64) {
 		// up to 256 rows.  The fused step's frame holds the first L.jrows (= 64) rows of efc_J: an env-step within that runs the
 		// one-row-per-lane solver on it, one beyond reads J from the env's block in HBM; the full frame (mjb_forward / mjb_step1 /
 		// mjb_step2) holds all of J
@@ -3181,15 +3181,15 @@ template <int G, int CON, int DENSE> DEVI void forward_rest(const KernelParams M
 				fwd_constraint_newton<G, 4, false, true>(m, L, e, s.efc_Jg + (size_t)e.env * s.efc_Jg_stride);
 			}
 		});
-	} else if constexpr (CON >= 10 && CON <= 13 && G == 64) {
+	} else if constexpr (mjb_kv_slot(CON) && G == 64) {
 		// up to 1024 rows: the row-slot solver (Newton: 10 / 12, CG: 11 / 13), all row data in the frame -- in LDS (10 / 11) or in HBM (12 / 13)
-		VIEW(P, compact, fwd_constraint_newton<G, 1, (CON & 1) != 0, false, true>(m, L, e));
-	} else if constexpr (CON >= 2 && CON <= 3 && G == 64) {
-		VIEW(P, compact, fwd_constraint_newton<G, (CON == 2 ? 1 : 2)>(m, L, e));
-	} else if constexpr (CON >= 6 && CON <= 8 && G == 64) {
-		VIEW(P, compact, fwd_constraint_newton<G, (CON == 6 ? 1 : (CON == 7 ? 2 : 4)), true>(m, L, e));
-	} else if constexpr ((CON == 1 || CON == 5 || CON == 9) && G == 64) {
-		if constexpr (CON == 5) {  // elliptic cone blocks: rows of B in LDS (the block code leaves no registers for them)
+		VIEW(P, compact, fwd_constraint_newton<G, 1, mjb_kv_slot_cg(CON), false, true>(m, L, e));
+	} else if constexpr (mjb_kv_newton(CON) && G == 64) {
+		VIEW(P, compact, fwd_constraint_newton<G, mjb_kv_rows_per_lane(CON)>(m, L, e));
+	} else if constexpr (mjb_kv_cg(CON) && G == 64) {
+		VIEW(P, compact, fwd_constraint_newton<G, mjb_kv_rows_per_lane(CON), true>(m, L, e));
+	} else if constexpr (mjb_kv_pgs(CON) && G == 64) {
+		if constexpr (CON == MJB_KV_PGS_ELL) {  // elliptic cone blocks: rows of B in LDS (the block code leaves no registers for them)
 			VIEW(P, compact, fwd_constraint_pgs<G, true, false, CON>(m, L, s, e));
 		} else {
 			if (P->m.nv <= 16) {
@@ -3224,7 +3224,7 @@ template <int G, int CON, int DENSE> DEVI void forward_rest(const KernelParams M
 		VIEW(P, compact, fwd_constraint<G>(m, L, e));
 	}
 	PROF(11);
-	if constexpr (CON != 0) {  // workload statistics (mjb_set_stats): what this evaluation asked of the solver -- fire-and-forget atomics
+	if constexpr (CON != MJB_KV_NONE) {  // workload statistics (mjb_set_stats): what this evaluation asked of the solver -- fire-and-forget atomics
 		if (P->s.stats != nullptr) {
 			MJB_KEEP_BRANCH();
 			VIEW(P, compact, {
@@ -3499,15 +3499,14 @@ template <int G> STAGE void ctrl_noise(CModel m, CLayout L, CNoise nz, const Env
 // ------------------------------------------------------------------------------------------------
 // the kernel
 // ------------------------------------------------------------------------------------------------
-// CON: 0 = model without constraint rows; 1 = PGS (5 = PGS with elliptic cone blocks), 2 / 3 / 4 = Newton with 1 / 2 / 4 rows per lane,
-// 6 / 7 / 8 = CG with 1 / 2 / 4 rows per lane (the Newton solver without its Hessian) (collision / rows / solver stages compiled in;
-// one env per wavefront) -- separate kernels keep each instruction stream and register budget small.
+// CON: the kernel variant, MJB_KV_* of mjb_dev.h (constrained variants: collision / rows / solver stages compiled in; one env per
+// wavefront) -- separate kernels keep each instruction stream and register budget small.
 // Constrained kernels get the full 512-register budget (one wave per SIMD; most frames limit the CU to 1 - 4 envs anyway):
-// few spills, and room for the register-resident AR rows / Hessian rows of the solvers.  CON == 9 is the plain PGS step again
+// few spills, and room for the register-resident AR rows / Hessian rows of the solvers.  MJB_KV_PGS256 (9) is the plain PGS step again
 // under a 256-register cap, picked when EIGHT lean frames fit one CU's LDS: two waves per SIMD hide each other's dependent
 // chains, which is worth more than the spills cost (config 3: +31 % measured).
 // ROCm 7.2's LLVM can place a spill ahead of an exec restore and lose lanes (tools/check_spill_exec.py, `make lint`
-// guards every build): an earlier revision had to cap these kernels at 256 VGPRs because of it, and the CG variants (CON >= 6,
+// guards every build): an earlier revision had to cap these kernels at 256 VGPRs because of it, and the CG variants (6 - 8,
 // not a BASELINE workload) still are -- at 512 the allocator produced exactly that pattern in the 2-rows-per-lane CG kernel.  The
 // row-slot Newton kernels (10, 12) take the 512-register budget of the other Newton kernels: capped at 256 they were allocated 196 VGPRs +
 // 128 AGPRs anyway (one wave per SIMD) with 142 / 119 VGPRs spilled; the row-slot CG kernels (11, 13) fit 256.
@@ -3515,7 +3514,7 @@ template <int G, int CON, int DENSE>
 #ifndef MJB_DEV_OCC
 #define MJB_DEV_OCC 1
 #endif
-__global__ void __launch_bounds__(256, ((CON >= 6 && CON != 10 && CON != 12) ? 2 : (CON ? MJB_DEV_OCC : (G == 64 ? 4 : (G == 32 ? 2 : 1)))))
+__global__ void __launch_bounds__(256, mjb_kv_min_waves(CON, G, MJB_DEV_OCC))
     mjb_step_kernel(const KernelParams MJB_AS4 *__restrict__ P, const int mode_arg, const int nsteps,
                     const unsigned int step0, const int epb, const int frame_bytes, const int chunk, const int env_lo, const int env_hi)
 {
@@ -3666,7 +3665,7 @@ __global__ void __launch_bounds__(256, ((CON >= 6 && CON != 10 && CON != 12) ? 2
 		}
 	}
 	// (variants 12 / 13: the frame is the env's slot of DevState::frame_ws, set per env below; no dynamic LDS)
-	constexpr bool HBMF = CON == 12 || CON == 13;
+	constexpr bool HBMF = mjb_kv_hbm_frame(CON);
 	if constexpr (!HBMF) {
 		e.f = reinterpret_cast<double *>(smem + (size_t)slot * frame_bytes);
 		e.fi = reinterpret_cast<int *>(e.f + L.ndouble);
@@ -3677,7 +3676,7 @@ __global__ void __launch_bounds__(256, ((CON >= 6 && CON != 10 && CON != 12) ? 2
 	// earlier by a block that is running or done, so the wait cannot deadlock) and the state crosses HBM between chunks exactly
 	// as it does between launches.  An env's cost varies 2x around the mean and a CU holds few envs: with two envs per slot the
 	// slowest pair sets the launch time, with 2 * nchunk items per slot the slots even out (config 3: +7 %).
-	const bool dyn = CON != 0 && G == 64 && chunk > 0 && mode == MJB_MODE_STEP && s.sched != nullptr;  // (whole-batch launches only)
+	const bool dyn = CON != MJB_KV_NONE && G == 64 && chunk > 0 && mode == MJB_MODE_STEP && s.sched != nullptr;  // (whole-batch launches only)
 	const int nchunk = dyn ? (nsteps + chunk - 1) / chunk : 1;
 	// (otherwise) grid-stride over env groups so any batch size runs with a bounded grid
 	for (int base = env_lo + blockIdx.x * epb;; base += gridDim.x * epb) {
@@ -3711,7 +3710,7 @@ __global__ void __launch_bounds__(256, ((CON >= 6 && CON != 10 && CON != 12) ? 2
 
 		if (HBMF && (mode == MJB_MODE_STEP2 || mode == MJB_MODE_STEP21 || mode == MJB_MODE_RKMID || mode == MJB_MODE_RKLAST)) {
 			// resume: the full frame IS the workspace; the (possibly host-modified) state goes on top below
-		} else if (mode == MJB_MODE_STEP2 || (DENSE == 0 && CON != 9 && (mode == MJB_MODE_STEP21 || mode == MJB_MODE_RKMID || mode == MJB_MODE_RKLAST))) {
+		} else if (mode == MJB_MODE_STEP2 || (mjb_kv_chained(CON, DENSE) && (mode == MJB_MODE_STEP21 || mode == MJB_MODE_RKMID || mode == MJB_MODE_RKLAST))) {
 			// resume: full frame from the workspace, then the (possibly host-modified) state on top
 			// (eight loads in flight per lane: the copy is a chain of HBM round trips otherwise -- a split step of ONE callback env
 			//  is pure latency, profiles/r03_callback_path.txt)
@@ -3728,7 +3727,7 @@ __global__ void __launch_bounds__(256, ((CON >= 6 && CON != 10 && CON != 12) ? 2
 			for (int k = e.lane; k < L.nint; k += G) e.fi[k] = 0;
 			gsync<G>();
 		}
-		if constexpr (CON != 0) {
+		if constexpr (CON != MJB_KV_NONE) {
 			if (m.nv <= 16 && e.lane < 16) {
 				for (int q = 0; q < 4; q++) {
 					unsigned int w = 0;
@@ -3750,7 +3749,7 @@ __global__ void __launch_bounds__(256, ((CON >= 6 && CON != 10 && CON != 12) ? 2
 		// (not in the dense kernels nor in the 256-register PGS variant, which only ever runs fused launches: both lose 1 - 2.5 % to the
 		//  extra mode; the host picks the generic / 512-register kernels for this launch)
 		const int st0 = item_chunk * chunk;  // first step of this work item (0 unless the launch is chunked)
-		const int nst = mode == MJB_MODE_STEP ? (dyn ? (nsteps - st0 < chunk ? nsteps - st0 : chunk) : nsteps) : ((DENSE == 0 && CON != 9 && mode == MJB_MODE_STEP21) ? 2 : 1);
+		const int nst = mode == MJB_MODE_STEP ? (dyn ? (nsteps - st0 < chunk ? nsteps - st0 : chunk) : nsteps) : ((mjb_kv_chained(CON, DENSE) && mode == MJB_MODE_STEP21) ? 2 : 1);
 		// (an RK4 step cut at its callback points: this launch starts at evaluation rk0 -- whose first half the previous launch ran --
 		//  and stops after ONE rk4_stage, with the next evaluation's first half done)
 		// ctrl noise from the launch's pre-generated buffer (one value per lane: nu <= G), first value fetched here
@@ -3763,7 +3762,7 @@ __global__ void __launch_bounds__(256, ((CON >= 6 && CON != 10 && CON != 12) ? 2
 		const double *const zb = s.zbuf + (zhalf_i > 0 ? s.zhalf : 0ull);
 		double znext = 0;
 		if (zpre && e.lane < m.nu) znext = zb[((size_t)st0 * s.nenv + e.env) * m.nu + e.lane];
-		const bool rksplit = DENSE == 0 && CON != 9 && (mode == MJB_MODE_RKMID || mode == MJB_MODE_RKLAST);
+		const bool rksplit = mjb_kv_chained(CON, DENSE) && (mode == MJB_MODE_RKMID || mode == MJB_MODE_RKLAST);
 		const int rk0 = rksplit ? nsteps : 0;
 #pragma nounroll
 		for (int st = 0; st < nst; st++) {
@@ -3771,7 +3770,7 @@ __global__ void __launch_bounds__(256, ((CON >= 6 && CON != 10 && CON != 12) ? 2
 			//  otherwise, hoisted to the top of the kernel and kept in spilled SGPRs)
 			int mode = mode_arg;
 			asm volatile("" : "+s"(mode));
-			const bool combo = DENSE == 0 && CON != 9 && mode == MJB_MODE_STEP21;
+			const bool combo = mjb_kv_chained(CON, DENSE) && mode == MJB_MODE_STEP21;
 			const bool checks = mode != MJB_MODE_FORWARD;
 			const bool rkmode = mode == MJB_MODE_RKMID || mode == MJB_MODE_RKLAST;
 			const bool do_first = combo ? st == 1 : (mode != MJB_MODE_STEP2 && !rkmode), do_rest = combo ? st == 0 : mode != MJB_MODE_STEP1;
@@ -3848,7 +3847,7 @@ __global__ void __launch_bounds__(256, ((CON >= 6 && CON != 10 && CON != 12) ? 2
 			}
 			}
 			PROF(14);  // whole forward (incl. checks)
-			if (do_euler && !rk4) VIEW(P, compact, euler<G, (CON != 0), (CON >= 2 && CON <= 4), (DENSE != 0), (MJB_PGS_PRESOLVE && (CON == 1 || CON == 9))>(m, L, e));
+			if (do_euler && !rk4) VIEW(P, compact, euler<G, (CON != MJB_KV_NONE), mjb_kv_newton(CON), (DENSE != 0), (MJB_PGS_PRESOLVE && (CON == MJB_KV_PGS || CON == MJB_KV_PGS256))>(m, L, e));
 			PROF(15);
 		}
 
@@ -3909,13 +3908,11 @@ __global__ void mjb_reset_kernel(const KernelParams MJB_AS4 *__restrict__ P, con
 	s.energy[2 * e] = s.energy[2 * e + 1] = 0;
 }
 
-template <int G, int CON, int DENSE = 0>
-int launch_g(const KernelParams *Pdev, const FrameLayout &L, int env_lo, int env_hi, int mode, int nsteps, unsigned int step0,
-             int epb, void *stream, int chunk = 0)
+template <int G, int CON, int DENSE = 0> int launch_g(const StepLaunch &a)
 {
-	const int nenv = env_hi - env_lo;
-	constexpr bool HBMF = CON == 12 || CON == 13;  // (the frame lives in DevState::frame_ws)
-	const int frame_bytes = HBMF ? 0 : ((L.ndouble * 8 + L.nint * 4) + 15) & ~15;
+	const int nenv = a.env_hi - a.env_lo;
+	int epb = a.epb;
+	const int frame_bytes = mjb_kv_hbm_frame(CON) ? 0 : mjb_layout_bytes(*a.L);  // (in HBM: the frame lives in DevState::frame_ws)
 	const int maxlds = mjb_max_lds_bytes();
 	int threads = epb * G;
 	if (threads > 256) {
@@ -3929,7 +3926,7 @@ int launch_g(const KernelParams *Pdev, const FrameLayout &L, int env_lo, int env
 	size_t lds = (size_t)epb * frame_bytes;
 	if ((int)lds > maxlds) return (int)hipErrorInvalidValue;
 	{  // measurement knob: MJB_DEBUG_LDS_BYTES=<n> requests at least n bytes per block, i.e. caps the resident blocks per CU
-		static const int floor_bytes = [] { const char *v = getenv("MJB_DEBUG_LDS_BYTES"); return v ? atoi(v) : 0; }();
+		static const int floor_bytes = mjb_env_int("MJB_DEBUG_LDS_BYTES", 0);
 		if (floor_bytes > (int)lds && floor_bytes <= maxlds) lds = floor_bytes;
 	}
 	auto kern = mjb_step_kernel<G, CON, DENSE>;
@@ -3939,81 +3936,57 @@ int launch_g(const KernelParams *Pdev, const FrameLayout &L, int env_lo, int env
 	int blocks = (nenv + epb - 1) / epb;
 	const int maxblocks = 256 * 16;
 	if (blocks > maxblocks) blocks = maxblocks;
-	hipLaunchKernelGGL(kern, dim3(blocks), dim3(threads), lds, (hipStream_t)stream,
-	                   (const KernelParams MJB_AS4 *)Pdev, mode, nsteps, step0, epb, frame_bytes, CON != 0 ? chunk : 0, env_lo, env_hi);
+	hipLaunchKernelGGL(kern, dim3(blocks), dim3(threads), lds, (hipStream_t)a.stream, (const KernelParams MJB_AS4 *)a.params, a.mode, a.nsteps, a.step0, epb,
+	                   frame_bytes, CON != MJB_KV_NONE ? a.chunk : 0, a.env_lo, a.env_hi);
 	return (int)hipGetLastError();
+}
+
+// one build slice's variants: launches the one a.variant names
+template <int SLICE, int... CONS> int launch_variants(const StepLaunch &a)
+{
+	static_assert(((mjb_kv_slice(CONS) == SLICE) && ...), "variant listed in a slice other than its own (mjb_dev.h: mjb_kv_slice)");
+	int rc = (int)hipErrorInvalidValue;
+	(void)((a.variant == CONS && ((rc = launch_g<64, CONS>(a)), true)) || ...);
+	return rc;
 }
 
 }  // namespace
 
-// The kernel variants are compiled in slices, one translation unit per slice (-DMJB_GROUP=0..4: minutes of device code
-// generation run in parallel); without MJB_GROUP the whole file is one unit (profiling and development builds).
-//   0: models without constraint rows + the dispatcher   1: PGS (1, 5)   2: Newton 1 / 2 rows per lane   3: Newton 4 rows   4: CG
-//   7 / 8: the row-slot Newton / CG kernels (10, 11 with the frame in LDS; 12, 13 with it in HBM)
-//   5: the 256-register PGS variant (9) on its own: out-of-line helpers shared with the 512-register kernels would be compiled
-//      for their budget and cost it its second wave per SIMD, or spills (760 instead of 576 in the same unit as variants 1 / 5)
+// The kernel variants are compiled in slices, one translation unit per slice (-DMJB_GROUP=0..8: minutes of device code
+// generation run in parallel); without MJB_GROUP the whole file is one unit (profiling and development builds).  Which slice a
+// variant lives in: mjb_kv_slice (mjb_dev.h).  Slice 0 holds the models without constraint rows + the dispatcher, slice 6 the split
+// step's constraint kernel; 5 is the 256-register PGS variant on its own: out-of-line helpers shared with the 512-register kernels
+// would be compiled for their budget and cost it its second wave per SIMD, or spills (760 instead of 576 in the same unit as
+// variants 1 / 5); the row-slot kernels on a frame in HBM (8) are a slice of their own only to build in parallel.
 #ifndef MJB_GROUP
 #define MJB_GROUP -1
 #endif
 #define MJB_HAS_GROUP(g) (MJB_GROUP < 0 || MJB_GROUP == (g))
-int mjb_launch_group1(const KernelParams *Pdev, const FrameLayout &L, int env_lo, int nenv, int mode, int nsteps, unsigned int step0, int epb, int constrained, void *stream, int chunk);
-int mjb_launch_group2(const KernelParams *Pdev, const FrameLayout &L, int env_lo, int nenv, int mode, int nsteps, unsigned int step0, int epb, int constrained, void *stream, int chunk);
-int mjb_launch_group3(const KernelParams *Pdev, const FrameLayout &L, int env_lo, int nenv, int mode, int nsteps, unsigned int step0, int epb, int constrained, void *stream, int chunk);
-int mjb_launch_group4(const KernelParams *Pdev, const FrameLayout &L, int env_lo, int nenv, int mode, int nsteps, unsigned int step0, int epb, int constrained, void *stream, int chunk);
-int mjb_launch_group5(const KernelParams *Pdev, const FrameLayout &L, int env_lo, int nenv, int mode, int nsteps, unsigned int step0, int epb, int constrained, void *stream, int chunk);
-int mjb_launch_group7(const KernelParams *Pdev, const FrameLayout &L, int env_lo, int nenv, int mode, int nsteps, unsigned int step0, int epb, int constrained, void *stream, int chunk);
-int mjb_launch_group8(const KernelParams *Pdev, const FrameLayout &L, int env_lo, int nenv, int mode, int nsteps, unsigned int step0, int epb, int constrained, void *stream, int chunk);
+#define MJB_SLICE_FN(g) int mjb_launch_group##g(const StepLaunch &a)
+MJB_SLICE_FN(1); MJB_SLICE_FN(2); MJB_SLICE_FN(3); MJB_SLICE_FN(4); MJB_SLICE_FN(5); MJB_SLICE_FN(7); MJB_SLICE_FN(8);
 
+// (the order inside a list decides the order of the kernels in the slice's code object: the last one comes first)
 #if !defined(MJB_DEV_ONLY_CON)
 #if MJB_HAS_GROUP(1)
-int mjb_launch_group1(const KernelParams *Pdev, const FrameLayout &L, int env_lo, int nenv, int mode, int nsteps, unsigned int step0, int epb, int constrained, void *stream, int chunk)
-{
-	if (constrained == 5) return launch_g<64, 5>(Pdev, L, env_lo, nenv, mode, nsteps, step0, epb, stream, chunk);
-	return launch_g<64, 1>(Pdev, L, env_lo, nenv, mode, nsteps, step0, epb, stream, chunk);
-}
+MJB_SLICE_FN(1) { return launch_variants<1, MJB_KV_PGS, MJB_KV_PGS_ELL>(a); }
 #endif
 #if MJB_HAS_GROUP(5)
-int mjb_launch_group5(const KernelParams *Pdev, const FrameLayout &L, int env_lo, int nenv, int mode, int nsteps, unsigned int step0, int epb, int constrained, void *stream, int chunk)
-{
-	return launch_g<64, 9>(Pdev, L, env_lo, nenv, mode, nsteps, step0, epb, stream, chunk);
-}
+MJB_SLICE_FN(5) { return launch_variants<5, MJB_KV_PGS256>(a); }
 #endif
 #if MJB_HAS_GROUP(2)
-int mjb_launch_group2(const KernelParams *Pdev, const FrameLayout &L, int env_lo, int nenv, int mode, int nsteps, unsigned int step0, int epb, int constrained, void *stream, int chunk)
-{
-	if (constrained == 3) return launch_g<64, 3>(Pdev, L, env_lo, nenv, mode, nsteps, step0, epb, stream, chunk);
-	return launch_g<64, 2>(Pdev, L, env_lo, nenv, mode, nsteps, step0, epb, stream, chunk);
-}
+MJB_SLICE_FN(2) { return launch_variants<2, MJB_KV_NEWTON1, MJB_KV_NEWTON2>(a); }
 #endif
 #if MJB_HAS_GROUP(3)
-int mjb_launch_group3(const KernelParams *Pdev, const FrameLayout &L, int env_lo, int nenv, int mode, int nsteps, unsigned int step0, int epb, int constrained, void *stream, int chunk)
-{
-	return launch_g<64, 4>(Pdev, L, env_lo, nenv, mode, nsteps, step0, epb, stream, chunk);
-}
+MJB_SLICE_FN(3) { return launch_variants<3, MJB_KV_NEWTON4>(a); }
 #endif
 #if MJB_HAS_GROUP(4)
-int mjb_launch_group4(const KernelParams *Pdev, const FrameLayout &L, int env_lo, int nenv, int mode, int nsteps, unsigned int step0, int epb, int constrained, void *stream, int chunk)
-{
-	if (constrained == 7) return launch_g<64, 7>(Pdev, L, env_lo, nenv, mode, nsteps, step0, epb, stream, chunk);
-	if (constrained == 8) return launch_g<64, 8>(Pdev, L, env_lo, nenv, mode, nsteps, step0, epb, stream, chunk);
-	return launch_g<64, 6>(Pdev, L, env_lo, nenv, mode, nsteps, step0, epb, stream, chunk);
-}
+MJB_SLICE_FN(4) { return launch_variants<4, MJB_KV_CG1, MJB_KV_CG4, MJB_KV_CG2>(a); }
 #endif
 #if MJB_HAS_GROUP(7)
-// the row-slot solver (up to 1024 rows) on a frame in LDS: Newton (10), CG (11)
-int mjb_launch_group7(const KernelParams *Pdev, const FrameLayout &L, int env_lo, int nenv, int mode, int nsteps, unsigned int step0, int epb, int constrained, void *stream, int chunk)
-{
-	if (constrained == 11) return launch_g<64, 11>(Pdev, L, env_lo, nenv, mode, nsteps, step0, epb, stream, chunk);
-	return launch_g<64, 10>(Pdev, L, env_lo, nenv, mode, nsteps, step0, epb, stream, chunk);
-}
+MJB_SLICE_FN(7) { return launch_variants<7, MJB_KV_SLOT_NEWTON, MJB_KV_SLOT_CG>(a); }
 #endif
 #if MJB_HAS_GROUP(8)
-// ... on a frame in HBM (the layout exceeds one CU's LDS): Newton (12), CG (13) -- a slice of its own only to build in parallel
-int mjb_launch_group8(const KernelParams *Pdev, const FrameLayout &L, int env_lo, int nenv, int mode, int nsteps, unsigned int step0, int epb, int constrained, void *stream, int chunk)
-{
-	if (constrained == 13) return launch_g<64, 13>(Pdev, L, env_lo, nenv, mode, nsteps, step0, epb, stream, chunk);
-	return launch_g<64, 12>(Pdev, L, env_lo, nenv, mode, nsteps, step0, epb, stream, chunk);
-}
+MJB_SLICE_FN(8) { return launch_variants<8, MJB_KV_SLOT_NEWTON_HBM, MJB_KV_SLOT_CG_HBM>(a); }
 #endif
 #endif
 
@@ -4159,12 +4132,12 @@ int mjb_launch_cstep(const KernelParams *Pdev, const FrameLayout &L, int env_lo,
 {
 	const int nenv = env_hi - env_lo;
 	if (nenv <= 0) return 0;
-	const int frame_bytes = ((L.ndouble * 8 + L.nint * 4) + 15) & ~15;
+	const int frame_bytes = mjb_layout_bytes(L);
 	if (epb > 4) epb = 4;
 	if (epb < 1) epb = 1;
 	const size_t lds = (size_t)epb * frame_bytes;
-	if ((int)lds > 160 * 1024) return (int)hipErrorInvalidValue;
-	auto kern = mjb_cstep_kernel<9>;
+	if ((int)lds > mjb_max_lds_bytes()) return (int)hipErrorInvalidValue;
+	auto kern = mjb_cstep_kernel<MJB_KV_PGS256>;
 	if (lds > 65536) {  // (four frames of config 3: 80 KB.  Per device and size, not per launch: one launch = one step here)
 		static std::mutex mu;
 		static std::map<std::pair<int, int>, hipError_t> done;
@@ -4174,7 +4147,7 @@ int mjb_launch_cstep(const KernelParams *Pdev, const FrameLayout &L, int env_lo,
 		auto it = done.find({ dev, (int)lds });
 		hipError_t err;
 		if (it == done.end()) {
-			err = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+			err = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, mjb_max_lds_bytes());
 			done[{ dev, (int)lds }] = err;
 		} else
 			err = it->second;
@@ -4188,39 +4161,30 @@ int mjb_launch_cstep(const KernelParams *Pdev, const FrameLayout &L, int env_lo,
 #endif  // MJB_HAS_GROUP(6)
 
 #if MJB_HAS_GROUP(0)
-int mjb_max_lds_bytes() { return 160 * 1024; }
-
-int mjb_launch_step(const KernelParams *Pdev, const FrameLayout &L, int env_lo, int nenv, int mode, int nsteps, unsigned int step0,
-                    int lanes_per_env, int envs_per_block, int constrained, int dense, void *stream)
+int mjb_launch_step(const StepLaunch &a)
 {
-	// (the headline kernels are instantiated first so that they sit at the start of the code object whatever happens to the
-	//  size of the constrained ones: their absolute placement is worth ~2 % on config 2)
-	const int chunk = constrained >> 8;  // (steps per work item of a chunked launch, 0 = one item per env; mjb_api.hip: launch)
-	constrained &= 255;
 #ifdef MJB_DEV_ONLY_CON  // development switch: compile ONE constrained kernel variant (seconds instead of minutes)
-	return launch_g<64, MJB_DEV_ONLY_CON>(Pdev, L, env_lo, nenv, mode, nsteps, step0, envs_per_block, stream, chunk);
+	return launch_g<64, MJB_DEV_ONLY_CON>(a);
 #else
-	if (!constrained) {
-		switch (lanes_per_env) {
+	if (a.variant == MJB_KV_NONE) {
+		// (the headline kernels are instantiated first so that they sit at the start of the code object whatever happens to the
+		//  size of the constrained ones: their absolute placement is worth ~2 % on config 2)
+		switch (a.lanes) {
 		case 16:
-			if (dense == 12) return launch_g<16, 0, 12>(Pdev, L, env_lo, nenv, mode, nsteps, step0, envs_per_block, stream);
-			if (dense == 8) return launch_g<16, 0, 8>(Pdev, L, env_lo, nenv, mode, nsteps, step0, envs_per_block, stream);
-			if (dense) return launch_g<16, 0, 16>(Pdev, L, env_lo, nenv, mode, nsteps, step0, envs_per_block, stream);
-			return launch_g<16, 0>(Pdev, L, env_lo, nenv, mode, nsteps, step0, envs_per_block, stream);
-		case 8: return launch_g<8, 0>(Pdev, L, env_lo, nenv, mode, nsteps, step0, envs_per_block, stream);
-		case 32: return launch_g<32, 0>(Pdev, L, env_lo, nenv, mode, nsteps, step0, envs_per_block, stream);
-		case 64: return launch_g<64, 0>(Pdev, L, env_lo, nenv, mode, nsteps, step0, envs_per_block, stream);
+			if (a.dense == 12) return launch_g<16, MJB_KV_NONE, 12>(a);
+			if (a.dense == 8) return launch_g<16, MJB_KV_NONE, 8>(a);
+			if (a.dense) return launch_g<16, MJB_KV_NONE, 16>(a);
+			return launch_g<16, MJB_KV_NONE>(a);
+		case 8: return launch_g<8, MJB_KV_NONE>(a);
+		case 32: return launch_g<32, MJB_KV_NONE>(a);
+		case 64: return launch_g<64, MJB_KV_NONE>(a);
 		default: return (int)hipErrorInvalidValue;
 		}
 	}
-	if (lanes_per_env != 64) return (int)hipErrorInvalidValue;
-	if (constrained == 2 || constrained == 3) return mjb_launch_group2(Pdev, L, env_lo, nenv, mode, nsteps, step0, envs_per_block, constrained, stream, chunk);
-	if (constrained == 4) return mjb_launch_group3(Pdev, L, env_lo, nenv, mode, nsteps, step0, envs_per_block, constrained, stream, chunk);
-	if (constrained >= 6 && constrained <= 8) return mjb_launch_group4(Pdev, L, env_lo, nenv, mode, nsteps, step0, envs_per_block, constrained, stream, chunk);
-	if (constrained == 9) return mjb_launch_group5(Pdev, L, env_lo, nenv, mode, nsteps, step0, envs_per_block, constrained, stream, chunk);
-	if (constrained == 10 || constrained == 11) return mjb_launch_group7(Pdev, L, env_lo, nenv, mode, nsteps, step0, envs_per_block, constrained, stream, chunk);
-	if (constrained == 12 || constrained == 13) return mjb_launch_group8(Pdev, L, env_lo, nenv, mode, nsteps, step0, envs_per_block, constrained, stream, chunk);
-	return mjb_launch_group1(Pdev, L, env_lo, nenv, mode, nsteps, step0, envs_per_block, constrained, stream, chunk);
+	if (a.lanes != 64) return (int)hipErrorInvalidValue;
+	static int (*const slice[])(const StepLaunch &) = { nullptr, mjb_launch_group1, mjb_launch_group2, mjb_launch_group3, mjb_launch_group4,
+		                                                 mjb_launch_group5, nullptr, mjb_launch_group7, mjb_launch_group8 };
+	return slice[mjb_kv_slice(a.variant)](a);
 #endif
 }
 
