@@ -178,6 +178,12 @@ def load_library(path=None):
         "mjb_set_packed": (ci, [vp, ci, C.POINTER(ci), ci, ci, C.POINTER(cd)]),
         "mjb_derive_mass_params": (ci, [vp, C.POINTER(cd), C.POINTER(cd), C.POINTER(cd)]),
         "mjb_set_env_body_mass": (ci, [vp, ci, ci, C.POINTER(cd), C.POINTER(cd)]),
+        "mjb_derive_mass_params_armature": (ci, [vp, C.POINTER(cd), C.POINTER(cd), C.POINTER(cd), C.POINTER(cd)]),
+        "mjb_env_joint_stride": (ci, [vp]),
+        "mjb_set_env_joint_params": (ci, [vp, ci, ci, C.POINTER(cd)]),
+        "mjb_set_env_dof_params": (ci, [vp, ci, ci, C.POINTER(cd), C.POINTER(cd), C.POINTER(cd)]),
+        "mjb_set_env_joint_stiffness": (ci, [vp, ci, ci, C.POINTER(cd)]),
+        "mjb_set_env_actuator_params": (ci, [vp, ci, ci, C.POINTER(cd), C.POINTER(cd)]),
         "mjb_hwsim_configure": (ci, [vp, ci, C.POINTER(HwsimJoint)]),
         "mjb_hwsim_set_command": (ci, [vp, ci, ci, ci, C.POINTER(cd)]),
         "mjb_hwsim_command_ptr": (vp, [vp, ci]),

@@ -170,6 +170,7 @@ struct mjb_batch {
 	double *env_geom_size = nullptr;
 	int *env_geom_type = nullptr;
 	double *env_gravity = nullptr, *env_geom_friction = nullptr, *env_equality = nullptr, *env_mass = nullptr;  // per-env model parameter overrides (mjb_set_env_*)
+	std::vector<double> env_block;  // host mirror of env_mass, [nenv][mjb_env_block_doubles]: what an armature or mass change re-derives the env's mj_setConst constants from
 	// device-side DefaultRobotHWSim (mjb_hwsim_*)
 	HwSim hw{};
 	int *hw_ints = nullptr;        // joint | method | kind | antiwindup, [4][n]
@@ -3093,13 +3094,45 @@ int mjb_env_mass_stride(const mjb_model *m)
 	return 7 * m->h.nbody + m->h.nv + m->h.ntendon + 1;
 }
 
-int mjb_set_env_mass_params(mjb_batch *b, int env_lo, int env_hi, const double *params)
+// The env's block of inertial, joint and actuator constants (DevState::env_mass, mjb_dev.h): one allocation, mirrored on the host.  The
+// first override of either family fills every env's block with the model's values; a setter then edits its rows in the mirror and
+// uploads them.  EnvBlock: where the arrays of the joint section sit, behind the public mass block (jnt0 = mjb_env_mass_stride).
+namespace {
+struct EnvBlock {
+	int nb, nv, nt, nj, nu, jnt0, stride;
+	explicit EnvBlock(const mjb_model_desc &h) : nb(h.nbody), nv(h.nv), nt(h.ntendon), nj(h.njnt), nu(h.nu), jnt0(7 * h.nbody + h.nv + h.ntendon + 1),
+	                                             stride(mjb_env_block_doubles(h.nbody, h.nv, h.ntendon, h.njnt, h.nu)) {}
+	int damping() const { return jnt0; }
+	int armature() const { return jnt0 + nv; }
+	int frictionloss() const { return jnt0 + 2 * nv; }
+	int damping_int() const { return jnt0 + 3 * nv; }
+	int stiffness() const { return jnt0 + 4 * nv; }
+	int gainprm() const { return jnt0 + 4 * nv + nj; }
+	int biasprm() const { return jnt0 + 4 * nv + nj + 3 * nu; }
+};
+}  // namespace
+
+// what the integrator adds to M's diagonal per unit of h, from an env's damping and bias parameters: mjb_compile's rule (damp_int)
+static void env_damping_int(const mjb_model_desc &h, const double *damping, const double *biasprm, double *out)
 {
-	if (!b) return fail(MJB_EINVAL, "null batch");
+	for (int i = 0; i < h.nv; i++) out[i] = damping[i];
+	if (h.integrator != MJB_INT_IMPLICITFAST) return;
+	for (int i = 0; i < h.nv; i++) out[i] = (h.disableflags & MJB_DSBL_PASSIVE) ? 0.0 : damping[i];
+	if (h.disableflags & MJB_DSBL_ACTUATION) return;
+	for (int i = 0; i < h.nu; i++) {
+		if (h.actuator_trntype[i] != MJB_TRN_JOINT) continue;  // (site / tendon actuators: a velocity term is refused)
+		const double bv = h.actuator_biastype[i] == MJB_BIAS_AFFINE ? biasprm[3 * i + 2] : 0.0, g = h.actuator_gear[6 * i];
+		out[h.jnt_dofadr[h.actuator_trnid[2 * i]]] -= g * g * bv;
+	}
+}
+
+static int env_block_ensure(mjb_batch *b, const char *what)
+{
+	if (b->env_mass) return MJB_OK;
 	const mjb_model_desc &h = b->model->h;
-	const int n = 7 * h.nbody + h.nv + h.ntendon + 1;
-	std::vector<double> packed((size_t)n);
-	double *o = packed.data();
+	const EnvBlock B(h);
+	std::vector<double> row((size_t)B.stride);
+	double *o = row.data();
 	for (int i = 0; i < h.nbody; i++) o[i] = h.body_mass[i];
 	for (int i = 0; i < h.nbody; i++) o[h.nbody + i] = h.body_subtreemass[i];
 	for (int i = 0; i < 3 * h.nbody; i++) o[2 * h.nbody + i] = h.body_inertia[i];
@@ -3107,7 +3140,67 @@ int mjb_set_env_mass_params(mjb_batch *b, int env_lo, int env_hi, const double *
 	for (int i = 0; i < 2 * h.nbody; i++) o[5 * h.nbody + h.nv + i] = h.body_invweight0[i];
 	for (int i = 0; i < h.ntendon; i++) o[7 * h.nbody + h.nv + i] = h.tendon_invweight0[i];
 	o[7 * h.nbody + h.nv + h.ntendon] = h.meaninertia[0];
-	return env_param(b, &b->env_mass, &b->st.env_mass, n, packed.data(), env_lo, env_hi, params, "mjb_set_env_mass_params");
+	for (int i = 0; i < h.nv; i++) {
+		o[B.damping() + i] = h.dof_damping[i];
+		o[B.armature() + i] = h.dof_armature[i];
+		o[B.frictionloss() + i] = h.dof_frictionloss[i];
+		o[B.damping_int() + i] = b->model->damp_int[i];
+	}
+	for (int j = 0; j < h.njnt; j++) o[B.stiffness() + j] = h.jnt_stiffness[j];
+	for (int k = 0; k < 3 * h.nu; k++) { o[B.gainprm() + k] = h.actuator_gainprm[k]; o[B.biasprm() + k] = h.actuator_biasprm[k]; }
+	double *dev = dev_alloc<double>((size_t)b->nenv * B.stride);
+	if (!dev) return fail(MJB_ENOMEM, "%s: allocation failed", what);
+	std::vector<double> init((size_t)b->nenv * B.stride);
+	for (int e = 0; e < b->nenv; e++) memcpy(init.data() + (size_t)e * B.stride, o, (size_t)B.stride * sizeof(double));
+	if (hipMemcpy(dev, init.data(), init.size() * sizeof(double), hipMemcpyHostToDevice) != hipSuccess) {
+		hipFree(dev);
+		return fail(MJB_ENODEVICE, "%s: upload failed", what);
+	}
+	b->env_mass = dev;
+	b->st.env_mass = dev;
+	b->params_dirty = true;
+	return MJB_OK;
+}
+
+// The host mirror exists from the first joint-parameter call on (a batch that only ever sets masses keeps none): read back once.
+static int env_block_mirror(mjb_batch *b)
+{
+	if (!b->env_block.empty()) return MJB_OK;
+	const size_t n = (size_t)b->nenv * EnvBlock(b->model->h).stride;
+	b->env_block.resize(n);
+	if (hipMemcpy(b->env_block.data(), b->env_mass, n * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess) {
+		b->env_block.clear();
+		return fail(MJB_ENODEVICE, "reading the per-env constants back failed");
+	}
+	return MJB_OK;
+}
+
+static int env_block_upload(mjb_batch *b, int env_lo, int env_hi)
+{
+	const size_t stride = (size_t)EnvBlock(b->model->h).stride;
+	HIP_TRY(hipMemcpy(b->env_mass + (size_t)env_lo * stride, b->env_block.data() + (size_t)env_lo * stride, (size_t)(env_hi - env_lo) * stride * sizeof(double),
+	                  hipMemcpyHostToDevice));
+	return MJB_OK;
+}
+
+int mjb_set_env_mass_params(mjb_batch *b, int env_lo, int env_hi, const double *params)
+{
+	const char *what = "mjb_set_env_mass_params";
+	if (!b) return fail(MJB_EINVAL, "null batch");
+	if (!params) return fail(MJB_EINVAL, "%s: bad argument", what);
+	if (env_lo < 0 || env_hi > b->nenv || env_lo > env_hi) return fail(MJB_EINVAL, "%s: bad env range", what);
+	const EnvBlock B(b->model->h);
+	HIP_TRY(hipSetDevice(b->device));
+	HIP_TRY(hipStreamSynchronize(b->stream));
+	const int rc = env_block_ensure(b, what);
+	if (rc != MJB_OK) return rc;
+	if (!b->env_block.empty())
+		for (int e = env_lo; e < env_hi; e++)
+			memcpy(b->env_block.data() + (size_t)e * B.stride, params + (size_t)(e - env_lo) * B.jnt0, (size_t)B.jnt0 * sizeof(double));
+	if (env_hi > env_lo)  // the mass section of each env's row: rows of jnt0 doubles into rows of stride doubles
+		HIP_TRY(hipMemcpy2D(b->env_mass + (size_t)env_lo * B.stride, (size_t)B.stride * sizeof(double), params, (size_t)B.jnt0 * sizeof(double),
+		                    (size_t)B.jnt0 * sizeof(double), (size_t)(env_hi - env_lo), hipMemcpyHostToDevice));
+	return MJB_OK;
 }
 
 // ---- mj_setConst for new body masses (callbacks.cpp:251-256, :582), host side, plain C++ ----
@@ -3147,7 +3240,14 @@ struct SC {  // tiny dense helpers (row-major)
 int mjb_derive_mass_params(const mjb_model *model, const double *body_mass, const double *body_inertia, double *out)
 {
 	if (!model || !body_mass || !out) return fail(MJB_EINVAL, "mjb_derive_mass_params: bad argument");
+	return mjb_derive_mass_params_armature(model, body_mass, body_inertia, nullptr, out);
+}
+
+int mjb_derive_mass_params_armature(const mjb_model *model, const double *body_mass, const double *body_inertia, const double *dof_armature, double *out)
+{
+	if (!model || !body_mass || !out) return fail(MJB_EINVAL, "mjb_derive_mass_params_armature: bad argument");
 	const mjb_model_desc &h = model->h;
+	const double *armature = dof_armature ? dof_armature : h.dof_armature;
 	const int nb = h.nbody, nv = h.nv, nj = h.njnt, nt = h.ntendon;
 	const double *inertia = body_inertia ? body_inertia : h.body_inertia;
 	double *o_mass = out, *o_sub = out + nb, *o_inert = out + 2 * nb, *o_dof = out + 5 * nb, *o_body = out + 5 * nb + nv,
@@ -3246,7 +3346,7 @@ int mjb_derive_mass_params(const mjb_model *model, const double *body_mass, cons
 			}
 	};
 	std::vector<double> M((size_t)nv * nv, 0.0), jp((size_t)3 * nv), jr((size_t)3 * nv);
-	for (int i = 0; i < nv; i++) M[(size_t)i * nv + i] = h.dof_armature[i];
+	for (int i = 0; i < nv; i++) M[(size_t)i * nv + i] = armature[i];
 	for (int b = 1; b < nb; b++) {
 		const double mb = body_mass[b], *I = inertia + 3 * b;
 		if (mb == 0 && I[0] == 0 && I[1] == 0 && I[2] == 0) continue;
@@ -3334,23 +3434,174 @@ int mjb_set_env_body_mass(mjb_batch *b, int env_lo, int env_hi, const double *bo
 	if (!b || !body_mass) return fail(MJB_EINVAL, "mjb_set_env_body_mass: bad argument");
 	if (env_lo < 0 || env_hi > b->nenv || env_lo > env_hi) return fail(MJB_EINVAL, "mjb_set_env_body_mass: bad env range");
 	const mjb_model_desc &h = b->model->h;
-	const int stride = mjb_env_mass_stride(b->model), n = env_hi - env_lo;
+	const EnvBlock B(h);
+	const int stride = B.jnt0, n = env_hi - env_lo;
 	std::vector<double> packed((size_t)std::max(1, n) * stride);
 	// (the derivation is mj_setConst -- Jacobians of every body, an O(nbody nv^2) mass matrix and its inverse -- and a service call that
 	//  sets one mass on the whole batch, setBodyStateCB with the default env range, hands over nenv identical rows under the physics
 	//  mutex: derived once per DISTINCT row, the block of a row equal to its predecessor is copied)
+	// (an env that carries its own armature, mjb_set_env_dof_params, is derived with it: the mirror of its block has it)
+	auto arm = [&](int e) { return b->env_block.empty() ? h.dof_armature : b->env_block.data() + (size_t)(env_lo + e) * B.stride + B.armature(); };
 	for (int e = 0; e < n; e++) {
 		const double *bm = body_mass + (size_t)e * h.nbody, *bi = body_inertia ? body_inertia + (size_t)e * 3 * h.nbody : nullptr;
 		double *dst = packed.data() + (size_t)e * stride;
 		if (e > 0 && std::memcmp(bm, bm - h.nbody, sizeof(double) * h.nbody) == 0 &&
-		    (!bi || std::memcmp(bi, bi - 3 * h.nbody, sizeof(double) * 3 * h.nbody) == 0)) {
+		    (!bi || std::memcmp(bi, bi - 3 * h.nbody, sizeof(double) * 3 * h.nbody) == 0) &&
+		    (arm(e) == arm(e - 1) || std::memcmp(arm(e), arm(e - 1), sizeof(double) * h.nv) == 0)) {
 			std::memcpy(dst, dst - stride, sizeof(double) * stride);
 			continue;
 		}
-		const int rc = mjb_derive_mass_params(b->model, bm, bi, dst);
+		const int rc = mjb_derive_mass_params_armature(b->model, bm, bi, arm(e), dst);
 		if (rc != MJB_OK) return rc;
 	}
 	return mjb_set_env_mass_params(b, env_lo, env_hi, packed.data());
+}
+
+// ---- per-env joint and actuator parameters ----
+int mjb_env_joint_stride(const mjb_model *m)
+{
+	if (!m) return fail(MJB_EINVAL, "null model");
+	return 3 * m->h.nv + m->h.njnt + 6 * m->h.nu;
+}
+
+// One implementation behind the four setters: every array is optional and comes with its own per-env stride (the packed form hands
+// over six views of one block).  Everything is checked before anything is written: a refused call leaves the batch as it was.
+static int env_joint_set(mjb_batch *b, int env_lo, int env_hi, const double *damping, const double *armature, const double *frictionloss,
+                         const double *stiffness, const double *gainprm, const double *biasprm, int src_stride, const char *what)
+{
+	if (!b) return fail(MJB_EINVAL, "null batch");
+	if (!damping && !armature && !frictionloss && !stiffness && !gainprm && !biasprm) return fail(MJB_EINVAL, "%s: bad argument", what);
+	if (env_lo < 0 || env_hi > b->nenv || env_lo > env_hi) return fail(MJB_EINVAL, "%s: bad env range", what);
+	const mjb_model *M = b->model;
+	const mjb_model_desc &h = M->h;
+	const EnvBlock B(h);
+	if (B.stride == B.jnt0) return fail(MJB_EINVAL, "%s: the model has nothing to override", what);
+	const int n = env_hi - env_lo;
+	// a packed block (src_stride > 0) or a dense [env][len] array per argument
+	auto at = [&](const double *p, int e, int len) { return p + (size_t)e * (src_stride > 0 ? src_stride : len); };
+	auto nonneg = [&](const double *p, int len, const char *name, const char *unit) -> int {
+		if (!p) return MJB_OK;
+		for (int e = 0; e < n; e++)
+			for (int i = 0; i < len; i++) {
+				const double v = at(p, e, len)[i];
+				if (!std::isfinite(v) || v < 0)
+					return fail(MJB_EINVAL, "%s: %s of env %d, %s %d is %g: it must be finite and non-negative", what, name, env_lo + e, unit, i, v);
+			}
+		return MJB_OK;
+	};
+	int rc;
+	if ((rc = nonneg(damping, h.nv, "damping", "dof")) != MJB_OK) return rc;
+	if ((rc = nonneg(armature, h.nv, "armature", "dof")) != MJB_OK) return rc;
+	if ((rc = nonneg(frictionloss, h.nv, "frictionloss", "dof")) != MJB_OK) return rc;
+	if ((rc = nonneg(stiffness, h.njnt, "stiffness", "joint")) != MJB_OK) return rc;
+	for (const double *p : { gainprm, biasprm })
+		if (p)
+			for (int e = 0; e < n; e++)
+				for (int k = 0; k < 3 * h.nu; k++)
+					if (!std::isfinite(at(p, e, 3 * h.nu)[k]))
+						return fail(MJB_EINVAL, "%s: %s of env %d, actuator %d is not finite", what, p == gainprm ? "gainprm" : "biasprm", env_lo + e, k / 3);
+	// (FRICTIONLOSS disabled: no friction rows by the model's own choice, any value is inert)
+	if (frictionloss && M->nfriction == 0 && !(h.disableflags & MJB_DSBL_FRICTIONLOSS))
+		for (int e = 0; e < n; e++)
+			for (int i = 0; i < h.nv; i++)
+				if (at(frictionloss, e, h.nv)[i] > 0)
+					return fail(MJB_EUNSUPPORTED, "%s: positive frictionloss (env %d, dof %d) on a model compiled without dry-friction rows: give one joint of the "
+					                              "model a positive frictionloss so that its frames hold them", what, env_lo + e, i);
+	if (h.integrator == MJB_INT_IMPLICITFAST) {
+		if (gainprm)
+			for (int e = 0; e < n; e++)
+				for (int i = 0; i < h.nu; i++)
+					if (h.actuator_gaintype[i] == MJB_GAIN_AFFINE && at(gainprm, e, 3 * h.nu)[3 * i + 2] != 0)
+						return fail(MJB_EUNSUPPORTED, "%s: integrator implicitfast with a velocity term in an affine actuator gain is not supported (env %d, actuator %d)",
+						            what, env_lo + e, i);
+		if (biasprm)
+			for (int e = 0; e < n; e++)
+				for (int i = 0; i < h.nu; i++) {
+					const int trn = h.actuator_trntype[i];
+					if ((trn == MJB_TRN_SITE || trn == MJB_TRN_TENDON) && h.actuator_biastype[i] == MJB_BIAS_AFFINE && at(biasprm, e, 3 * h.nu)[3 * i + 2] != 0)
+						return fail(MJB_EUNSUPPORTED, "%s: integrator implicitfast with a velocity-dependent actuator on a %s is not supported (env %d, actuator %d)",
+						            what, trn == MJB_TRN_SITE ? "site" : "tendon", env_lo + e, i);
+				}
+	}
+	HIP_TRY(hipSetDevice(b->device));
+	if (b->env_mass) {
+		HIP_TRY(hipStreamSynchronize(b->stream));
+		if ((rc = env_block_mirror(b)) != MJB_OK) return rc;
+	}
+	// the model's frames hold M + h B and its factor only when mjb_compile found something to put there (DevModel::eulerdamp)
+	const bool euler_implicit = h.integrator == MJB_INT_EULER && !(h.disableflags & MJB_DSBL_EULERDAMP);
+	if (M->eulerdamp == 0 && (euler_implicit || h.integrator == MJB_INT_IMPLICITFAST) && (damping || biasprm)) {
+		std::vector<double> di((size_t)std::max(1, h.nv));
+		for (int e = 0; e < n; e++) {
+			const double *cur = b->env_block.empty() ? nullptr : b->env_block.data() + (size_t)(env_lo + e) * B.stride;
+			const double *d = damping ? at(damping, e, h.nv) : (cur ? cur + B.damping() : h.dof_damping);
+			const double *bp = biasprm ? at(biasprm, e, 3 * h.nu) : (cur ? cur + B.biasprm() : h.actuator_biasprm);
+			env_damping_int(h, d, bp, di.data());
+			for (int i = 0; i < h.nv; i++)
+				if (di[i] != 0)
+					return fail(MJB_EUNSUPPORTED, "%s: %s (env %d, dof %d) on a model compiled without the implicit-damping factor (no damped dof: its frames hold no "
+					                              "M + h B): give one joint of the model a positive damping", what,
+					            euler_implicit ? "positive damping under the Euler integrator" : "a velocity-dependent force under implicitfast", env_lo + e, i);
+		}
+	}
+	HIP_TRY(hipSetDevice(b->device));
+	HIP_TRY(hipStreamSynchronize(b->stream));
+	if ((rc = env_block_ensure(b, what)) != MJB_OK) return rc;
+	if ((rc = env_block_mirror(b)) != MJB_OK) return rc;
+	std::vector<double> saved;  // (a failed derivation -- a singular inertia -- restores the rows)
+	if (armature) saved.assign(b->env_block.begin() + (size_t)env_lo * B.stride, b->env_block.begin() + (size_t)env_hi * B.stride);
+	for (int e = 0; e < n; e++) {
+		double *row = b->env_block.data() + (size_t)(env_lo + e) * B.stride;
+		if (damping) memcpy(row + B.damping(), at(damping, e, h.nv), sizeof(double) * h.nv);
+		if (armature) memcpy(row + B.armature(), at(armature, e, h.nv), sizeof(double) * h.nv);
+		if (frictionloss) memcpy(row + B.frictionloss(), at(frictionloss, e, h.nv), sizeof(double) * h.nv);
+		if (stiffness) memcpy(row + B.stiffness(), at(stiffness, e, h.njnt), sizeof(double) * h.njnt);
+		if (gainprm) memcpy(row + B.gainprm(), at(gainprm, e, 3 * h.nu), sizeof(double) * 3 * h.nu);
+		if (biasprm) memcpy(row + B.biasprm(), at(biasprm, e, 3 * h.nu), sizeof(double) * 3 * h.nu);
+		if (damping || biasprm) env_damping_int(h, row + B.damping(), row + B.biasprm(), row + B.damping_int());
+		if (armature) {
+			// mj_setConst with the env's own masses, inertias and armature (derived once per distinct row, as mjb_set_env_body_mass does)
+			const double *prev = e > 0 ? row - B.stride : nullptr;
+			if (prev && std::memcmp(row, prev, sizeof(double) * h.nbody) == 0 && std::memcmp(row + 2 * h.nbody, prev + 2 * h.nbody, sizeof(double) * 3 * h.nbody) == 0 &&
+			    std::memcmp(row + B.armature(), prev + B.armature(), sizeof(double) * h.nv) == 0) {
+				memcpy(row, prev, sizeof(double) * B.jnt0);
+				continue;
+			}
+			std::vector<double> mass(row, row + h.nbody), inertia(row + 2 * h.nbody, row + 5 * h.nbody);
+			rc = mjb_derive_mass_params_armature(M, mass.data(), inertia.data(), row + B.armature(), row);
+			if (rc != MJB_OK) {
+				std::copy(saved.begin(), saved.end(), b->env_block.begin() + (size_t)env_lo * B.stride);
+				return rc;
+			}
+		}
+	}
+	return env_block_upload(b, env_lo, env_hi);
+}
+
+int mjb_set_env_dof_params(mjb_batch *b, int env_lo, int env_hi, const double *damping, const double *armature, const double *frictionloss)
+{
+	return env_joint_set(b, env_lo, env_hi, damping, armature, frictionloss, nullptr, nullptr, nullptr, 0, "mjb_set_env_dof_params");
+}
+
+int mjb_set_env_joint_stiffness(mjb_batch *b, int env_lo, int env_hi, const double *stiffness)
+{
+	return env_joint_set(b, env_lo, env_hi, nullptr, nullptr, nullptr, stiffness, nullptr, nullptr, 0, "mjb_set_env_joint_stiffness");
+}
+
+int mjb_set_env_actuator_params(mjb_batch *b, int env_lo, int env_hi, const double *gainprm, const double *biasprm)
+{
+	return env_joint_set(b, env_lo, env_hi, nullptr, nullptr, nullptr, nullptr, gainprm, biasprm, 0, "mjb_set_env_actuator_params");
+}
+
+int mjb_set_env_joint_params(mjb_batch *b, int env_lo, int env_hi, const double *params)
+{
+	if (!b || !params) return fail(MJB_EINVAL, "mjb_set_env_joint_params: bad argument");
+	const mjb_model_desc &h = b->model->h;
+	const double *p = params;
+	const double *damping = p, *armature = p + h.nv, *frictionloss = p + 2 * h.nv, *stiffness = p + 3 * h.nv, *gainprm = p + 3 * h.nv + h.njnt,
+	             *biasprm = p + 3 * h.nv + h.njnt + 3 * h.nu;
+	return env_joint_set(b, env_lo, env_hi, h.nv ? damping : nullptr, h.nv ? armature : nullptr, h.nv ? frictionloss : nullptr, h.njnt ? stiffness : nullptr,
+	                     h.nu ? gainprm : nullptr, h.nu ? biasprm : nullptr, mjb_env_joint_stride(b->model), "mjb_set_env_joint_params");
 }
 
 // ---- device-side DefaultRobotHWSim::writeSim (stage hwsim_write in mjb_step.hip) ----

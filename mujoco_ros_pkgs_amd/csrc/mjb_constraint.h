@@ -1151,7 +1151,7 @@ template <int G, int TAG> STAGE void make_constraint(CModel m, CLayout L, CState
 			if (it < neq) {
 				if (f[L.eqparam + 19 * it] != 0) n = m.eq_type[it] == MJB_EQ_CONNECT ? 3 : (m.eq_type[it] == MJB_EQ_WELD ? 6 : 1);  // joint, tendon: 1
 			} else if (it < neq + nfr) {
-				n = (it < neq + nfd ? m.dof_frictionloss[it - neq] : m.tendon_frictionloss[it - neq - nfd]) > 0 ? 1 : 0;
+				n = (it < neq + nfd ? MP_DOF_FRICTIONLOSS(m, e, it - neq) : m.tendon_frictionloss[it - neq - nfd]) > 0 ? 1 : 0;
 			} else if (it < neq + nfr + m.njnt + nten) {
 				if (do_lim && lim_on == 2) {  // (a limited ball joint: one row when the rotation angle comes within the margin of max(range))
 					MJB_KEEP_BRANCH();
@@ -1347,7 +1347,7 @@ template <int G, int TAG> STAGE void make_constraint(CModel m, CLayout L, CState
 		} else if (it < neq + nfr) {
 			const bool isdof = it < neq + nfd;
 			rstore(off, 0.0, 0.0, g0, row_R(g0, diag[0]));
-			rfl(off, isdof ? m.dof_frictionloss[idv] : m.tendon_frictionloss[idv]);
+			rfl(off, isdof ? MP_DOF_FRICTIONLOSS(m, e, idv) : m.tendon_frictionloss[idv]);
 			rtag(off, isdof ? MJB_CNSTR_FRICTION_DOF : MJB_CNSTR_FRICTION_TENDON, idv);
 		} else if (it < neq + nfr + m.njnt + nten) {
 			const int type = it < neq + nfr + m.njnt ? MJB_CNSTR_LIMIT_JOINT : MJB_CNSTR_LIMIT_TENDON;

@@ -165,8 +165,9 @@ struct DevState {
 	const double *env_geom_size;     // [nenv][ngeom][3] per-env geom sizes (NULL: the model's)
 	const int *env_geom_type;        // [nenv][ngeom] per-env geom types (NULL: the model's)
 	const double *env_equality;      // [nenv][neq][19] per-env equality parameters (NULL: the model's)
-	const double *env_mass;          // [nenv][7 nbody + nv + ntendon + 1] per-env inertial constants (NULL: the model's):
-	                                 // body_mass | body_subtreemass | body_inertia[3] | dof_invweight0 | body_invweight0[2] | tendon_invweight0 | meaninertia
+	const double *env_mass;          // [nenv][mjb_env_block_doubles] per-env inertial, joint and actuator constants (NULL: the model's):
+	                                 // body_mass | body_subtreemass | body_inertia[3] | dof_invweight0 | body_invweight0[2] | tendon_invweight0 | meaninertia  (the public mass block,
+	                                 // mjb_env_mass_stride) | dof_damping | dof_armature | dof_frictionloss | dof_damping_int | jnt_stiffness | actuator_gainprm[3] | actuator_biasprm[3]
 	int *sched;                      // [1 + nenv] work counter | chunks done per env, of a chunked fused launch (constrained kernels); NULL otherwise
 	double *efc_Jg;                  // [nenv][mjb_rowblock_doubles] row data of the env-steps whose rows outnumber the fused frame's share (kernel variant 4, RowBlock); NULL otherwise
 	unsigned long long efc_Jg_stride;  // doubles per env of efc_Jg: sized for the largest cone-block stride of the model's three frame layouts (the kernels lay a block out with the stride of the frame they run on)
@@ -199,6 +200,11 @@ struct DevState {
 MJB_HD inline size_t mjb_rowblock_doubles(int nefcmax, int nv, int nconmax, int hcs)
 {
 	return (size_t)nefcmax * nv + (size_t)8 * nefcmax + (size_t)hcs * nconmax + (size_t)2 * nefcmax;
+}
+// doubles per env of DevState::env_mass: the mass section (7 nbody + nv + ntendon + 1), then the joint section (4 nv + njnt + 6 nu)
+MJB_HD inline int mjb_env_block_doubles(int nbody, int nv, int ntendon, int njnt, int nu)
+{
+	return 7 * nbody + nv + ntendon + 1 + 4 * nv + njnt + 6 * nu;
 }
 struct RowBlock {
 	double *J, *D, *aref, *b, *force, *fl, *nwt_row, *hc;

@@ -278,6 +278,17 @@ DEVI EnvLite lite(const Env &e) { return EnvLite{ e.f, e.fi, e.lane, e.env, e.mp
 #define MP_BODY_INVW(m, e, i) ((e).mp ? (e).mp[5 * (m).nbody + (m).nv + (i)] : (m).body_invweight0[(i)])
 #define MP_TEN_INVW(m, e, i) ((e).mp ? (e).mp[7 * (m).nbody + (m).nv + (i)] : (m).tendon_invweight0[(i)])
 #define MP_MEANINERTIA(m, e) ((e).mp ? (e).mp[7 * (m).nbody + (m).nv + (m).ntendon] : (m).meaninertia[0])
+// ... and, behind the inertial section of the same block, the env's joint and actuator constants (mjb_set_env_dof_params /
+// mjb_set_env_joint_stiffness / mjb_set_env_actuator_params): dof_damping[nv] | dof_armature[nv] | dof_frictionloss[nv] |
+// dof_damping_int[nv] | jnt_stiffness[njnt] | actuator_gainprm[nu][3] | actuator_biasprm[nu][3]  (mjb_env_block_doubles, mjb_dev.h)
+#define MP_JNT0(m) (7 * (m).nbody + (m).nv + (m).ntendon + 1)
+#define MP_DOF_DAMPING(m, e, i) ((e).mp ? (e).mp[MP_JNT0(m) + (i)] : (m).dof_damping[(i)])
+#define MP_DOF_ARMATURE(m, e, i) ((e).mp ? (e).mp[MP_JNT0(m) + (m).nv + (i)] : (m).dof_armature[(i)])
+#define MP_DOF_FRICTIONLOSS(m, e, i) ((e).mp ? (e).mp[MP_JNT0(m) + 2 * (m).nv + (i)] : (m).dof_frictionloss[(i)])
+#define MP_DOF_DAMPING_INT(m, e, i) ((e).mp ? (e).mp[MP_JNT0(m) + 3 * (m).nv + (i)] : (m).dof_damping_int[(i)])
+#define MP_JNT_STIFFNESS(m, e, j) ((e).mp ? (e).mp[MP_JNT0(m) + 4 * (m).nv + (j)] : (m).jnt_stiffness[(j)])
+#define MP_ACT_GAINPRM(m, mp, k) ((mp) ? (mp)[MP_JNT0(m) + 4 * (m).nv + (m).njnt + (k)] : (m).actuator_gainprm[(k)])
+#define MP_ACT_BIASPRM(m, mp, k) ((mp) ? (mp)[MP_JNT0(m) + 4 * (m).nv + (m).njnt + 3 * (m).nu + (k)] : (m).actuator_biasprm[(k)])
 
 // ------------------------------------------------------------------------------------------------
 // A1  kinematics: body frames, joint anchors/axes, inertial / geom / site frames
@@ -925,10 +936,10 @@ template <int G, bool OBL> STAGE void crb(CModel m, CLayout L, const Env &e)
 		double a[6], b[6];
 		ld6(a, f + L.cdof + 6 * j);
 		ld6(b, buf + 6 * i);
-		double v = (i == j) ? m.dof_armature[i] : 0.0;
+		double v = (i == j) ? MP_DOF_ARMATURE(m, e, i) : 0.0;
 		v += dot6r(a, b);
 		f[L.qM + en] = v;
-		if (m.eulerdamp) f[L.MhB + en] = (i == j) ? v + m.timestep[0] * m.dof_damping_int[i] : v;
+		if (m.eulerdamp) f[L.MhB + en] = (i == j) ? v + m.timestep[0] * MP_DOF_DAMPING_INT(m, e, i) : v;
 	}
 	gsync<G>();
 	SPROF(24);
@@ -1894,7 +1905,7 @@ template <int G, bool CACHE = false> STAGE void passive(CModel m, CLayout L, con
 		int pa = m.jnt_qposadr[j], da = m.jnt_dofadr[j];
 		const int nd = jt == MJB_JNT_FREE ? 6 : (jt == MJB_JNT_BALL ? 3 : 1);
 		double frc[6] = { 0, 0, 0, 0, 0, 0 };
-		const double k = m.jnt_stiffness[j];
+		const double k = MP_JNT_STIFFNESS(m, e, j);
 		if (k != 0 && !off) {
 			int o = 0;
 			if (jt == MJB_JNT_FREE) {
@@ -1915,7 +1926,7 @@ template <int G, bool CACHE = false> STAGE void passive(CModel m, CLayout L, con
 		}
 		for (int c = 0; c < nd; c++) {
 			double v = frc[c];
-			if (!off) v -= m.dof_damping[da + c] * f[L.qvel + da + c];
+			if (!off) v -= MP_DOF_DAMPING(m, e, da + c) * f[L.qvel + da + c];
 			qp[da + c] = v;
 		}
 	}
@@ -2611,7 +2622,7 @@ template <int G, bool CACHE = false> STAGE void sensors(CModel m, CLayout L, CSt
 // A12 actuation and smooth acceleration
 // ------------------------------------------------------------------------------------------------
 // force of actuator i (mj_fwdActuation): gain * (clamped ctrl, or the activation of a stateful actuator) + bias, clamped to forcerange
-DEVI double actuator_force(CModel m, CLayout L, const double *f, int i)
+DEVI double actuator_force(CModel m, CLayout L, const double *f, const double *mp, int i)
 {
 	double ctrl = f[L.ctrl + i];
 	if (m.actuator_ctrllimited[i] && !(m.disableflags & MJB_DSBL_CLAMPCTRL)) {
@@ -2619,11 +2630,11 @@ DEVI double actuator_force(CModel m, CLayout L, const double *f, int i)
 		ctrl = ctrl < lo ? lo : (ctrl > hi ? hi : ctrl);
 	}
 	const double len = f[L.actuator_length + i], vel = f[L.actuator_velocity + i];
-	double gain = m.actuator_gainprm[3 * i], bias = 0;
+	double gain = MP_ACT_GAINPRM(m, mp, 3 * i), bias = 0;
 	if (m.actuator_gaintype[i] == MJB_GAIN_AFFINE)
-		gain = m.actuator_gainprm[3 * i] + m.actuator_gainprm[3 * i + 1] * len + m.actuator_gainprm[3 * i + 2] * vel;
+		gain = MP_ACT_GAINPRM(m, mp, 3 * i) + MP_ACT_GAINPRM(m, mp, 3 * i + 1) * len + MP_ACT_GAINPRM(m, mp, 3 * i + 2) * vel;
 	if (m.actuator_biastype[i] == MJB_BIAS_AFFINE)
-		bias = m.actuator_biasprm[3 * i] + m.actuator_biasprm[3 * i + 1] * len + m.actuator_biasprm[3 * i + 2] * vel;
+		bias = MP_ACT_BIASPRM(m, mp, 3 * i) + MP_ACT_BIASPRM(m, mp, 3 * i + 1) * len + MP_ACT_BIASPRM(m, mp, 3 * i + 2) * vel;
 	double input = ctrl;
 	if (m.na > 0) {  // a stateful actuator's gain multiplies its activation (mj_fwdActuation)
 		const int ja = m.actuator_actadr[i];
@@ -2643,7 +2654,7 @@ template <int G> __device__ __attribute__((noinline)) void site_actuation(CModel
 	double *f = e.f;
 	for (int r = e.lane; r < m.nsite_act; r += G) {
 		const int i = m.site_act[r];
-		f[L.actuator_force + i] = off ? 0.0 : actuator_force(m, L, f, i);
+		f[L.actuator_force + i] = off ? 0.0 : actuator_force(m, L, f, e.mp, i);
 	}
 	gsync<G>();
 	if (off) return;
@@ -2688,7 +2699,7 @@ template <int G, bool CACHE = false> STAGE void fwd_actuation(CModel m, CLayout 
 			const int i = m.dof_act_id[t];
 			double force = 0;
 			if (!off) {
-				force = actuator_force(m, L, f, i);
+				force = actuator_force(m, L, f, e.mp, i);
 				acc += m.dof_act_mom[t] * force;
 			}
 			f[L.actuator_force + i] = force;
@@ -3321,7 +3332,7 @@ template <int G> __device__ __attribute__((noinline)) void energy(CModel m, CLay
 				                               f[L.gravity + 2] * f[L.xipos + 3 * b + 2]);
 		if (!(m.disableflags & MJB_DSBL_PASSIVE)) {
 			for (int j = 0; j < m.njnt; j++) {
-				const double k = m.jnt_stiffness[j];
+				const double k = MP_JNT_STIFFNESS(m, e, j);
 				if (k == 0) continue;
 				int pa = m.jnt_qposadr[j];
 				const int jt = m.jnt_type[j];
@@ -3700,8 +3711,8 @@ __global__ void __launch_bounds__(256, mjb_kv_min_waves(CON, G, MJB_DEV_OCC))
 		}
 		if constexpr (G == 64) e.env = __builtin_amdgcn_readfirstlane(e.env);  // (one env per wavefront: keep the index and everything derived from it scalar)
 		if (e.env >= env_hi) continue;  // whole group idles together (group == slot)
-		if constexpr (DENSE == 0) e.mp = s.env_mass ? s.env_mass + (size_t)e.env * (7 * m.nbody + m.nv + m.ntendon + 1) : nullptr;
-		else e.mp = nullptr;  // (batches with per-env masses never run the dense kernels)
+		if constexpr (DENSE == 0) e.mp = s.env_mass ? s.env_mass + (size_t)e.env * mjb_env_block_doubles(m.nbody, m.nv, m.ntendon, m.njnt, m.nu) : nullptr;
+		else e.mp = nullptr;  // (batches with per-env masses / joint parameters never run the dense kernels)
 		double *ws = s.frame_ws ? s.frame_ws + (size_t)e.env * s.frame_stride : nullptr;
 		if constexpr (HBMF) {
 			e.f = ws;

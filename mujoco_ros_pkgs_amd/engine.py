@@ -56,6 +56,20 @@ class CompiledModel:
                                                out.ctypes.data_as(pd)), "mjb_derive_mass_params")
         return out
 
+    def derive_mass_params_armature(self, body_mass=None, body_inertia=None, armature=None):
+        """The same with a dof armature [nv] in place of the model's (mjb_derive_mass_params_armature; None: the model's values)."""
+        m = self.model
+        nb, nv = int(m["nbody"]), int(m["nv"])
+        pd = C.POINTER(C.c_double)
+        bm = np.ascontiguousarray(np.asarray(m["body_mass"] if body_mass is None else body_mass, dtype=np.float64).reshape(nb))
+        bi = None if body_inertia is None else np.ascontiguousarray(np.asarray(body_inertia, dtype=np.float64).reshape(nb, 3))
+        ar = None if armature is None else np.ascontiguousarray(np.asarray(armature, dtype=np.float64).reshape(nv))
+        out = np.zeros(self.lib.mjb_env_mass_stride(self.ptr))
+        _check(self.lib.mjb_derive_mass_params_armature(self.ptr, bm.ctypes.data_as(pd), None if bi is None else bi.ctypes.data_as(pd),
+                                                        None if ar is None else ar.ctypes.data_as(pd), out.ctypes.data_as(pd)),
+               "mjb_derive_mass_params_armature")
+        return out
+
     @property
     def frame_doubles(self):
         return self.lib.mjb_frame_doubles(self.ptr)
@@ -193,6 +207,43 @@ class Batch:
         pd = C.POINTER(C.c_double)
         _check(self.lib.mjb_set_env_body_mass(self.ptr, lo, hi, bm.ctypes.data_as(pd), None if bi is None else bi.ctypes.data_as(pd)),
                "mjb_set_env_body_mass")
+
+    def _env_array(self, a, n, *shape):
+        if a is None:
+            return None, None
+        a = np.ascontiguousarray(np.asarray(a, dtype=np.float64).reshape((n,) + shape))
+        return a, a.ctypes.data_as(C.POINTER(C.c_double))
+
+    def set_env_dof_params(self, damping=None, armature=None, frictionloss=None, lo=0, hi=None):
+        """Per-env dof_damping / dof_armature / dof_frictionloss, each [hi-lo, nv] or None to leave that array as it is
+        (mjb_set_env_dof_params: the engine re-derives what mj_setConst derives from the armature, and the integrator's damping)."""
+        hi = self.nenv if hi is None else hi
+        nv = int(self.cm.model["nv"])
+        d, dp = self._env_array(damping, hi - lo, nv)
+        a, ap = self._env_array(armature, hi - lo, nv)
+        f, fp = self._env_array(frictionloss, hi - lo, nv)
+        _check(self.lib.mjb_set_env_dof_params(self.ptr, lo, hi, dp, ap, fp), "mjb_set_env_dof_params")
+
+    def set_env_joint_stiffness(self, stiffness, lo=0, hi=None):
+        """Per-env jnt_stiffness [hi-lo, njnt] (mjb_set_env_joint_stiffness)."""
+        hi = self.nenv if hi is None else hi
+        s, sp = self._env_array(stiffness, hi - lo, int(self.cm.model["njnt"]))
+        _check(self.lib.mjb_set_env_joint_stiffness(self.ptr, lo, hi, sp), "mjb_set_env_joint_stiffness")
+
+    def set_env_actuator_params(self, gainprm=None, biasprm=None, lo=0, hi=None):
+        """Per-env actuator_gainprm / actuator_biasprm, each [hi-lo, nu, 3] or None (mjb_set_env_actuator_params): kp / kv of
+        <position> / <velocity> / <general> actuators."""
+        hi = self.nenv if hi is None else hi
+        nu = int(self.cm.model["nu"])
+        g, gp = self._env_array(gainprm, hi - lo, nu, 3)
+        b, bp = self._env_array(biasprm, hi - lo, nu, 3)
+        _check(self.lib.mjb_set_env_actuator_params(self.ptr, lo, hi, gp, bp), "mjb_set_env_actuator_params")
+
+    def set_env_joint_params(self, params, lo=0, hi=None):
+        """The same as one packed block per env, [hi-lo, mjb_env_joint_stride] (mjcf.joint_params lays one out)."""
+        hi = self.nenv if hi is None else hi
+        p, pp = self._env_array(params, hi - lo, int(self.lib.mjb_env_joint_stride(self.cm.ptr)))
+        _check(self.lib.mjb_set_env_joint_params(self.ptr, lo, hi, pp), "mjb_set_env_joint_params")
 
     # ---- device-side DefaultRobotHWSim (mjb_hwsim_*) ----
     def hwsim_configure(self, joints):

@@ -1371,9 +1371,8 @@ def with_body_mass(model, body_mass, body_inertia=None):
     """A copy of a compiled model with new body masses (and optionally principal inertias) and everything mj_setConst
     derives from them: body_subtreemass, dof_invweight0, body_invweight0, tendon_invweight0, meaninertia
     (the reference: setBodyState sets body_mass then calls mj_setConst, mujoco_ros/src/callbacks.cpp:251-256)."""
-    from . import refdyn
     m = Model(dict(model))
-    nbody, nv = int(m["nbody"]), int(m["nv"])
+    nbody = int(m["nbody"])
     mass = np.asarray(body_mass, dtype=np.float64).reshape(nbody).copy()
     m["body_mass"] = mass
     if body_inertia is not None:
@@ -1383,6 +1382,15 @@ def with_body_mass(model, body_mass, body_inertia=None):
     for b in range(nbody - 1, 0, -1):
         sub[parent[b]] += sub[b]
     m["body_subtreemass"] = sub
+    _rederive_invweight0(m)
+    return m
+
+
+def _rederive_invweight0(m):
+    """mj_setConst's set0 stage on a compiled model, in place: dof_invweight0, body_invweight0, tendon_invweight0, meaninertia from the
+    model's current masses, inertias and armature (refdyn.invweight0, the derivation the compiler itself uses)."""
+    from . import refdyn
+    nv = int(m["nv"])
     dof_inv, body_inv, mean = refdyn.invweight0(m)
     m["dof_invweight0"], m["body_invweight0"], m["meaninertia"] = dof_inv, body_inv, np.array([mean])
     nt = int(m["ntendon"])
@@ -1393,7 +1401,34 @@ def with_body_mass(model, body_mass, body_inertia=None):
                 J[t, m["jnt_dofadr"][m["wrap_objid"][w]]] += m["wrap_prm"][w]
         Minv = np.linalg.inv(refdyn.mass_matrix(m, np.asarray(m["qpos0"], dtype=np.float64)))
         m["tendon_invweight0"] = np.einsum("ti,ij,tj->t", J, Minv, J)
+
+
+def with_joint_params(model, damping=None, armature=None, frictionloss=None, stiffness=None, gainprm=None, biasprm=None):
+    """A copy of a compiled model with new joint / actuator parameters: dof_damping [nv], dof_armature [nv], dof_frictionloss [nv],
+    jnt_stiffness [njnt], actuator_gainprm / actuator_biasprm [nu, 3] (None: the model's own), and what mj_setConst derives from the
+    armature (dof_invweight0, body_invweight0, tendon_invweight0, meaninertia).  The structure stays the model's: frame capacities
+    (nefcmax counts the model's dry-friction rows), item lists and kernel choice are not recomputed -- what a batch env carrying
+    these values through Batch.set_env_dof_params / set_env_joint_stiffness / set_env_actuator_params computes."""
+    m = Model(dict(model))
+    nv, njnt, nu = int(m["nv"]), int(m["njnt"]), int(m["nu"])
+    for key, val, shape in (("dof_damping", damping, (nv,)), ("dof_armature", armature, (nv,)), ("dof_frictionloss", frictionloss, (nv,)),
+                            ("jnt_stiffness", stiffness, (njnt,)), ("actuator_gainprm", gainprm, (nu, 3)), ("actuator_biasprm", biasprm, (nu, 3))):
+        if val is None:
+            continue
+        a = np.asarray(val, dtype=np.float64).reshape(shape).copy()
+        if key in ("dof_damping", "dof_armature", "dof_frictionloss", "jnt_stiffness") and not (np.all(np.isfinite(a)) and np.all(a >= 0)):
+            raise MjcfError(f"with_joint_params: {key} must be finite and non-negative")
+        m[key] = a
+    if armature is not None:
+        _rederive_invweight0(m)
     return m
+
+
+def joint_params(model):
+    """The packed per-env block of mjb_set_env_joint_params for a compiled model: dof_damping | dof_armature | dof_frictionloss |
+    jnt_stiffness | actuator_gainprm | actuator_biasprm."""
+    return np.concatenate([np.asarray(model[k], dtype=np.float64).reshape(-1) for k in (
+        "dof_damping", "dof_armature", "dof_frictionloss", "jnt_stiffness", "actuator_gainprm", "actuator_biasprm")])
 
 
 def mass_params(model):
