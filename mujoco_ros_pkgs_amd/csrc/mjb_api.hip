@@ -929,6 +929,15 @@ mjb_model *mjb_compile(const mjb_model_desc *desc)
 			delete M;
 			return nullptr;
 		}
+		// the kinematics (every kernel's, and mj_setConst's mirror below) takes `jntnum == 1 && FREE` as the only free-joint case
+		for (int b = 0; b < h.nbody; b++)
+			for (int j = h.body_jntadr[b]; j < h.body_jntadr[b] + h.body_jntnum[b]; j++)
+				if (h.jnt_type[j] == MJB_JNT_FREE && (h.body_jntnum[b] != 1 || h.body_parentid[b] != 0)) {
+					fail(MJB_EINVAL, "mjb_compile: the free joint %d must be the only joint of a top-level body (body %d has %d joints, parent %d)", j, b,
+					     h.body_jntnum[b], h.body_parentid[b]);
+					delete M;
+					return nullptr;
+				}
 	}
 	// ---- validation of the tree tables the kernels index with
 	for (int b = 1; b < h.nbody; b++)

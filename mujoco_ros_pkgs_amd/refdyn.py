@@ -6,9 +6,13 @@ Two uses, neither on the product's step path:
    by the reference at /root/reference mujoco_ros/src/callbacks.cpp:254,582 and implicitly by
    ``mj_loadXML``) that fills ``dof_invweight0`` / ``body_invweight0`` -- model-compile-time
    constants the constraint stage reads.
-2. The tests use ``mass_matrix`` / ``bias_lagrange`` as a *differently derived* check of the C
-   oracle's CRB and RNE (SURVEY.md §8c substitute oracle (ii)): M from body Jacobians, bias from
-   finite-differenced Lagrangian terms.  Nothing here shares code or algorithm with oracle/ or csrc/.
+2. The tests use ``mass_matrix`` / ``bias_lagrange`` / ``bias_newton_euler`` / ``step_euler`` as a
+   *differently derived* check of the C oracle's and the HIP kernels' CRB, RNE and Euler step
+   (SURVEY.md §8c substitute oracle (ii)): M from body Jacobians, bias from finite-differenced
+   Lagrangian terms (hinge / slide models) and from Newton's and Euler's equations projected through
+   finite-differenced Jacobians (hinge, slide, ball and free joints, any number of joints per body,
+   a ball being the last rotational joint of its body).  On hinge / slide models the two biases are
+   independent derivations of one quantity.  Nothing here shares code or algorithm with oracle/ or csrc/.
 """
 from __future__ import annotations
 
@@ -148,6 +152,94 @@ def bias_lagrange(m, qpos, qvel, eps=1e-6):
     Mdot = np.tensordot(qvel, dM, axes=(0, 0))
     c = Mdot @ qvel - 0.5 * np.array([qvel @ dM[k] @ qvel for k in range(n)]) + dV
     return c
+
+
+def _quat_exp(w, t):
+    """Unit quaternion of the rotation by angle t |w| about w."""
+    w = np.asarray(w, dtype=np.float64)
+    n = np.linalg.norm(w)
+    if n == 0:
+        return np.array([1.0, 0, 0, 0])
+    return np.concatenate([[np.cos(0.5 * t * n)], w / n * np.sin(0.5 * t * n)])
+
+
+def integrate_pos(m, qpos, qvel, t):
+    """qpos moved for time t along constant qvel, on the configuration manifold: hinge / slide add, a ball joint's
+    quaternion is right-multiplied by exp(t w) (w in the body's frame), a free joint moves pos by t v and its quaternion
+    as a ball's."""
+    q = np.array(qpos, dtype=np.float64)
+    v = np.asarray(qvel, dtype=np.float64)
+    for j in range(m["njnt"]):
+        ty, qa, da = m["jnt_type"][j], m["jnt_qposadr"][j], m["jnt_dofadr"][j]
+        if ty == JNT_FREE:
+            q[qa:qa + 3] += t * v[da:da + 3]
+            q[qa + 3:qa + 7] = _quat_mul(q[qa + 3:qa + 7], _quat_exp(v[da + 3:da + 6], t))
+        elif ty == JNT_BALL:
+            q[qa:qa + 4] = _quat_mul(q[qa:qa + 4], _quat_exp(v[da:da + 3], t))
+        else:
+            q[qa] += t * v[da]
+    return q
+
+
+def _check_ball_last(m):
+    for b in range(1, m["nbody"]):
+        ja, jn = m["body_jntadr"][b], m["body_jntnum"][b]
+        for j in range(ja, ja + jn):
+            if m["jnt_type"][j] == JNT_BALL and any(m["jnt_type"][k] != JNT_SLIDE for k in range(j + 1, ja + jn)):
+                raise ValueError("bias_newton_euler needs a ball joint to be the last rotational joint of its body")
+
+
+def bias_newton_euler(m, qpos, qvel, eps=1e-6):
+    """Coriolis + centrifugal + gravity generalized force c(q,v) such that  M a + c = tau, as the body-by-body projection of
+    Newton's and Euler's equations at zero joint acceleration:
+
+        c = sum_b  Jp_b' m_b (dJp_b/dt v - g)  +  Jr_b' (I_b dJr_b/dt v + w_b x I_b w_b),      w_b = Jr_b v,
+
+    with Jp_b at the body's centre of mass, I_b its inertia in world axes, and dJ/dt a central difference of ``jac_point``
+    along ``integrate_pos`` (the exact flow of constant qvel).  Hinge, slide, ball and free joints, any number of joints
+    per body.
+
+    The ball-last condition: ``jac_point`` (as MuJoCo's cdof) gives a ball joint's three columns in the body's FINAL
+    frame.  That is d/dt of the kinematics along ``integrate_pos`` only if no rotation follows the ball on the same body,
+    so a ball joint must be the last rotational joint of its body (slides may follow).  ValueError otherwise."""
+    _check_ball_last(m)
+    qpos = np.asarray(qpos, dtype=np.float64)
+    v = np.asarray(qvel, dtype=np.float64)
+
+    def jacs(q):
+        kin = kinematics(m, q)
+        return kin, [jac_point(m, kin, b, kin["xipos"][b]) for b in range(m["nbody"])]
+
+    kin, J = jacs(qpos)
+    _, Jf = jacs(integrate_pos(m, qpos, v, eps))
+    _, Jb = jacs(integrate_pos(m, qpos, v, -eps))
+    g = np.asarray(m["gravity"], dtype=np.float64)
+    c = np.zeros(m["nv"])
+    for b in range(1, m["nbody"]):
+        jp, jr = J[b]
+        djp = (Jf[b][0] - Jb[b][0]) / (2 * eps)
+        djr = (Jf[b][1] - Jb[b][1]) / (2 * eps)
+        Iw = kin["ximat"][b] @ np.diag(m["body_inertia"][b]) @ kin["ximat"][b].T
+        w = jr @ v
+        c += m["body_mass"][b] * jp.T @ (djp @ v - g) + jr.T @ (Iw @ (djr @ v) + np.cross(w, Iw @ w))
+    return c
+
+
+def step_euler(m, qpos, qvel, qfrc):
+    """One semi-implicit Euler step with implicit joint damping of a model WITHOUT constraints:
+
+        v' = v + h (M + h B)^-1 (qfrc - c - B v),     q' = integrate_pos(q, v', h),      B = diag(dof_damping),
+
+    where qfrc is every generalized force other than bias and joint damping (springs, actuators, applied).
+    Returns (q', v', qacc_smooth) with  M qacc_smooth = qfrc - c - B v."""
+    qpos = np.asarray(qpos, dtype=np.float64)
+    v = np.asarray(qvel, dtype=np.float64)
+    h = float(np.asarray(m["timestep"]).ravel()[0])
+    M = mass_matrix(m, qpos)
+    B = np.diag(np.asarray(m["dof_damping"], dtype=np.float64))
+    f = np.asarray(qfrc, dtype=np.float64) - bias_newton_euler(m, qpos, v) - B @ v
+    vn = v + h * np.linalg.solve(M + h * B, f)
+    return integrate_pos(m, qpos, vn, h), vn, np.linalg.solve(M, f)
 
 
 def invweight0(m):
