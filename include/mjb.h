@@ -266,7 +266,13 @@ int mjb_fused_frame(const mjb_batch *b);
  * should pin one form); measured on MI355X it is ahead of the 16-lanes-per-env kernel from 4096 envs (276 vs 227 M env-steps/s) and 12x
  * ahead at 65 536.  mode: -1 = automatic (fused launches over >= MJB_LANE_ENV_MIN_ENVS envs, default 4096 -- the whole batch, or the non-callback envs of a
  * split step, mjb_step_rest -- of a model whose
- * topology is compiled in, with no per-env model overrides / hwsim stage / xfrc_applied), 0 = never, 1 = whenever eligible.
+ * topology is compiled in, with no per-env model overrides / hwsim stage / xfrc_applied), 0 = never, 1 = whenever eligible,
+ * 2 = whenever eligible, ALSO with per-env gravity and parameter blocks (mjb_set_env_gravity, mjb_set_env_body_mass / _mass_params, mjb_set_env_dof_params /
+ * _joint_stiffness / _actuator_params / _joint_params): such a batch stands the kernel down in every other mode; in mode 2 its launches run the kernel's
+ * one-wavefront form (mjb_lane_env_last_form() == 0) in a build that reads each env's gravity, joint stiffness / damping / armature, masses, inertias and
+ * actuator gain / bias parameters from a per-env table laid out [value][env] (built at the first such launch, its columns re-derived after every later
+ * mjb_set_env_* call on these values; sized mjb_model_lane_env_overlay() doubles per env).  Every other condition stays (hwsim stage, xfrc_applied, frame
+ * dumps, statistics); a mode-2 batch WITHOUT overrides runs exactly what mode 1 runs.
  * The environment variable MJB_LANE_ENV (same values) sets the default of new batches (read by mjb_make_batch).  While mjb_set_stats is
  * counting, fused launches run the generic kernels whatever the mode (the counters live in those).  No reference counterpart. */
 int mjb_set_lane_env(mjb_batch *b, int mode);
@@ -305,6 +311,17 @@ int mjb_lane_env_info(const mjb_batch *b, int *used_last);
 void mjb_lane_env_jit_counts(int *compiled, int *disk_hits);
 /* The same classification for a compiled model, without a batch or a device (>= 0 / -2 / -1 as above). */
 int mjb_model_lane_env(const mjb_model *m);
+/* INTROSPECTION (debug / test aid; no caller needs them to run a batch): the constants of a lane = env eligible model (mjb_model_lane_env != -1) as
+ * the kernel reads them, without a batch or a device.  Both return the
+ * number of doubles and fill `out` when it is not NULL and `cap` is large enough; -1: the model is not eligible.
+ * mjb_model_lane_env_tape: the constant tape -- dt gravity[3] pad[4] | per body, 32 doubles: pos[3] quat[4] jaxis[3] jpos[3] qpos0 stiffness spring
+ * ipos[3] ibody[6] mass damping armature hdamping pad[3] | per actuator, 16: gear ctrlrange[2] gain[3] bias[3] forcerange[2] pad[5]; ibody =
+ * R(iquat) diag(inertia) R(iquat)' as xx yy zz xy xz yz, hdamping = timestep * damping.
+ * mjb_model_lane_env_overlay: one env's column of the per-env table of mjb_set_lane_env's mode 2, here with the model's own values -- gravity[3] | per
+ * jointed body: stiffness damping armature hdamping | per moving body (a joint on its path to the world): mass ibody[6] | per actuator: gain[3] bias[3]
+ * | the mass of every other body but the world (mjENBL_ENERGY reads it). */
+int mjb_model_lane_env_tape(const mjb_model *m, double *out, int cap);
+int mjb_model_lane_env_overlay(const mjb_model *m, double *out, int cap);
 const char *mjb_lane_env_error(void);
 /* The lane = env kernel's FORM, process-wide: how many wavefronts share the 64 envs of a block.  0 = one (the whole step in one instruction stream);
  * 1 = two, the step's position half (poses, cinert, composite inertias, qM, factors, solves, Euler) and velocity half (velocities, forces,

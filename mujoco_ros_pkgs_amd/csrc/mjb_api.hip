@@ -182,7 +182,9 @@ struct mjb_batch {
 	size_t zcap = 0;               // its capacity in doubles PER HALF
 	bool zdouble = false;          // two halves allocated (side-stream speculation possible)
 	size_t zfail = (size_t)-1;     // smallest total allocation (doubles) that failed: not retried
-	int lane_env_mode = -1;        // mjb_set_lane_env: -1 automatic, 0 never, 1 whenever eligible
+	int lane_env_mode = -1;        // mjb_set_lane_env: -1 automatic, 0 never, 1 whenever eligible, 2 whenever eligible, also with per-env gravity / parameter blocks
+	double *le_overlay = nullptr;  // mode 2: the per-env overlay of the lane = env kernel, [mjb_lane_env_overlay_slots][nenv] (DevState::le_overlay), built at the first such launch
+	int le_ov_lo = 0, le_ov_hi = 0;  // envs [lo, hi) whose overlay columns a setter has outdated since (empty: lo >= hi)
 	// the split step (mjb_set_split_step): smooth half in lane = env form + constraint half per wavefront, alternating on a few streams of env slices
 	int split_mode = -1;           // -1 automatic (whole-batch fused launches of >= MJB_SPLIT_MIN_ENVS envs), 0 never, 1 whenever eligible
 	bool split_used = false;       // the last fused launch ran that way
@@ -1467,6 +1469,7 @@ void mjb_free_batch(mjb_batch *b)
 	if (b->env_geom_type) hipFree(b->env_geom_type);
 	if (b->env_equality) hipFree(b->env_equality);
 	if (b->env_mass) hipFree(b->env_mass);
+	if (b->le_overlay) hipFree(b->le_overlay);
 	if (b->hw_ints) hipFree(b->hw_ints);
 	if (b->hw_gains) hipFree(b->hw_gains);
 	if (b->hw_cmd) hipFree(b->hw_cmd);
@@ -1519,7 +1522,7 @@ mjb_batch *mjb_make_batch(const mjb_model *M, int nenv, int device)
 	b->L = M->L;
 	if (const char *v = getenv("MJB_LANE_ENV")) {  // default lane_env_mode of new batches (include/mjb.h, mjb_set_lane_env)
 		const int k = atoi(v);
-		if (k >= -1 && k <= 1) b->lane_env_mode = k;
+		if (k >= -1 && k <= 2) b->lane_env_mode = k;
 	}
 	const mjb_model_desc &h = M->h;
 	// ---- device model blob: [ints | doubles | derived int tables]
@@ -1674,6 +1677,7 @@ mjb_batch *mjb_make_batch(const mjb_model *M, int nenv, int device)
 	s.handoff = nullptr;
 	s.handoff_stride = 0;
 	s.reset_step = nullptr;
+	s.le_overlay = nullptr;
 	s.sens_every_step = 0;
 	for (int k = 0; k < 64; k++) s.colfunc[k] = MJB_COLFUNC_DEFAULT;
 	s.sched = nullptr;
@@ -2154,10 +2158,61 @@ static int speculate_ctrl_noise(mjb_batch *b, const LaunchReq &q, int zhalf_now)
 static bool want_lane_env(const mjb_batch *b, const LaunchReq &q, int variant)
 {
 	if (!(q.mode == MJB_MODE_STEP && q.compact && variant == MJB_KV_NONE && b->model->le_topo != MJB_LE_TOPO_NONE && !b->le_unavailable && b->lane_env_mode != 0 &&
-	      no_env_overrides(b) && !b->st.stats))
+	      (no_env_overrides(b) || (b->lane_env_mode == 2 && b->hw.n == 0)) && !b->st.stats))  // (mode 2: per-env gravity and parameter blocks ride along, le_overlay_sync)
 		return false;
 	static const int min_envs = mjb_env_int("MJB_LANE_ENV_MIN_ENVS", 4096);
-	return b->lane_env_mode == 1 || q.env_hi - q.env_lo >= min_envs;  // (also the fused launch of a split step's non-callback envs, mjb_step_rest)
+	return b->lane_env_mode >= 1 || q.env_hi - q.env_lo >= min_envs;  // (also the fused launch of a split step's non-callback envs, mjb_step_rest)
+}
+
+// Mode 2 of mjb_set_lane_env: the per-env overlay (DevState::le_overlay; PeSlots, mjb_lane_env_kernel.h) of a batch with per-env gravity or parameter
+// blocks.  Built for every env at the first such launch; afterwards the columns of the envs a mjb_set_env_* call has touched (le_overlay_touch) are
+// derived again ahead of the next launch.  Sources: env_gravity, the env's block of env_mass (its host mirror when there is one), else the model.
+static void le_overlay_touch(mjb_batch *b, int env_lo, int env_hi)
+{
+	if (!b->le_overlay || env_lo >= env_hi) return;
+	const bool none = b->le_ov_lo >= b->le_ov_hi;
+	b->le_ov_lo = none ? env_lo : std::min(b->le_ov_lo, env_lo);
+	b->le_ov_hi = none ? env_hi : std::max(b->le_ov_hi, env_hi);
+}
+static int le_overlay_sync(mjb_batch *b)
+{
+	const mjb_model_desc &h = b->model->h;
+	const int ns = mjb_lane_env_overlay_slots(&h), nenv = b->nenv;
+	if (!b->le_overlay) {
+		b->le_overlay = dev_alloc<double>((size_t)ns * nenv);
+		if (!b->le_overlay) return fail(MJB_ENOMEM, "lane = env kernel: allocation of the per-env overlay failed");
+		b->st.le_overlay = b->le_overlay;
+		b->params_dirty = true;
+		b->le_ov_lo = 0;
+		b->le_ov_hi = nenv;
+	}
+	const int lo = b->le_ov_lo, hi = b->le_ov_hi, n = hi - lo;
+	if (n <= 0) return MJB_OK;
+	HIP_TRY(hipStreamSynchronize(b->stream));  // (an earlier launch may still read the columns)
+	if (b->rest_pending && b->rest_stream) HIP_TRY(hipStreamSynchronize(b->rest_stream));
+	const size_t stride = (size_t)mjb_env_block_doubles(h.nbody, h.nv, h.ntendon, h.njnt, h.nu);
+	std::vector<double> grav, blk;
+	const double *rows = nullptr;
+	if (b->env_gravity) {
+		grav.resize((size_t)3 * n);
+		HIP_TRY(hipMemcpy(grav.data(), b->env_gravity + (size_t)3 * lo, grav.size() * sizeof(double), hipMemcpyDeviceToHost));
+	}
+	if (b->env_mass && !b->env_block.empty()) rows = b->env_block.data() + (size_t)lo * stride;
+	else if (b->env_mass) {
+		blk.resize(stride * n);
+		HIP_TRY(hipMemcpy(blk.data(), b->env_mass + (size_t)lo * stride, blk.size() * sizeof(double), hipMemcpyDeviceToHost));
+		rows = blk.data();
+	}
+	std::vector<double> col((size_t)ns), stage((size_t)ns * n);
+	for (int e = 0; e < n; e++) {
+		mjb_lane_env_overlay_row(&h, grav.empty() ? nullptr : grav.data() + (size_t)3 * e, rows ? rows + (size_t)e * stride : nullptr, col.data());
+		for (int k = 0; k < ns; k++) stage[(size_t)k * n + e] = col[k];
+	}
+	// slot k of envs [lo, hi): n consecutive doubles at le_overlay + k * nenv + lo
+	HIP_TRY(hipMemcpy2D(b->le_overlay + lo, (size_t)nenv * sizeof(double), stage.data(), (size_t)n * sizeof(double), (size_t)n * sizeof(double), (size_t)ns,
+	                    hipMemcpyHostToDevice));
+	b->le_ov_lo = b->le_ov_hi = 0;
+	return MJB_OK;
 }
 
 static int launch(mjb_batch *b, int mode, int nsteps, int env_lo = 0, int env_hi = -1, hipStream_t on = nullptr)
@@ -2178,6 +2233,8 @@ static int launch(mjb_batch *b, int mode, int nsteps, int env_lo = 0, int env_hi
 			b->params_dirty = true;
 		}
 	}
+	const bool le_per_env = b->lane_env_mode == 2 && (b->env_mass || b->env_gravity) && !use_split && want_lane_env(b, q, variant);
+	if (le_per_env && (rc = le_overlay_sync(b))) return rc;
 	if ((rc = sync_params(b))) return rc;
 	if (use_split) {
 		if (b->zvalid) {  // (the pre-generated ctrl-noise buffer names an older launch: this path draws its normals in the smooth kernel)
@@ -2197,7 +2254,7 @@ static int launch(mjb_batch *b, int mode, int nsteps, int env_lo = 0, int env_hi
 	bool use_le = want_lane_env(b, q, variant);
 	b->lane_env_used = use_le;
 	if (use_le) {
-		rc = mjb_launch_lane_env(b->params_dev, b->model->le_topo, &b->model->h, b->nenv, env_lo, env_hi, nsteps, b->step_counter, q.stream);
+		rc = mjb_launch_lane_env(b->params_dev, b->model->le_topo, &b->model->h, b->nenv, env_lo, env_hi, nsteps, b->step_counter, q.stream, le_per_env ? 1 : 0);
 		if (rc == MJB_LE_UNAVAILABLE) {  // (no hiprtc / no kernel header / compile error: remembered, the generic kernel runs -- mjb_lane_env_info says why)
 			b->le_unavailable = true;
 			b->lane_env_used = use_le = false;
@@ -2828,7 +2885,7 @@ int mjb_get_stats(mjb_batch *b, unsigned long long *out)
 int mjb_noise_mode(const mjb_batch *b) { return b ? b->noise_mode : 0; }
 int mjb_set_lane_env(mjb_batch *b, int mode)
 {
-	if (!b || mode < -1 || mode > 1) return fail(MJB_EINVAL, "mjb_set_lane_env: bad argument");
+	if (!b || mode < -1 || mode > 2) return fail(MJB_EINVAL, "mjb_set_lane_env: bad argument");
 	b->lane_env_mode = mode;
 	return MJB_OK;
 }
@@ -2863,6 +2920,20 @@ int mjb_model_frame_info(const mjb_model *m, int *full_hbm, int *fused_hbm)
 const char *mjb_lane_env_error(void) { return mjb_lane_env_jit_error(); }
 void mjb_lane_env_jit_counts(int *compiled, int *disk_hits) { mjb_lane_env_jit_stats(compiled, disk_hits); }
 int mjb_model_lane_env(const mjb_model *m) { return m ? m->le_topo : -1; }
+int mjb_model_lane_env_tape(const mjb_model *m, double *out, int cap)
+{
+	if (!m || m->le_topo == MJB_LE_TOPO_NONE) return -1;
+	const int n = (int)m->le_tape.size();
+	if (out && cap >= n) memcpy(out, m->le_tape.data(), (size_t)n * sizeof(double));
+	return n;
+}
+int mjb_model_lane_env_overlay(const mjb_model *m, double *out, int cap)
+{
+	if (!m || m->le_topo == MJB_LE_TOPO_NONE) return -1;
+	const int n = mjb_lane_env_overlay_slots(&m->h);
+	if (out && cap >= n) mjb_lane_env_overlay_row(&m->h, nullptr, nullptr, out);
+	return n;
+}
 int mjb_lane_env_info(const mjb_batch *b, int *used_last)
 {
 	if (used_last) *used_last = b && b->lane_env_used ? 1 : 0;
@@ -3038,7 +3109,9 @@ static int env_param(mjb_batch *b, double **arr, const double **slot, int per_en
 int mjb_set_env_gravity(mjb_batch *b, int env_lo, int env_hi, const double *gravity)
 {
 	if (!b) return fail(MJB_EINVAL, "null batch");
-	return env_param(b, &b->env_gravity, &b->st.env_gravity, 3, b->model->h.gravity, env_lo, env_hi, gravity, "mjb_set_env_gravity");
+	const int rc = env_param(b, &b->env_gravity, &b->st.env_gravity, 3, b->model->h.gravity, env_lo, env_hi, gravity, "mjb_set_env_gravity");
+	if (rc == MJB_OK) le_overlay_touch(b, env_lo, env_hi);
+	return rc;
 }
 
 int mjb_set_env_geom_friction(mjb_batch *b, int env_lo, int env_hi, const double *friction)
@@ -3189,6 +3262,7 @@ static int env_block_upload(mjb_batch *b, int env_lo, int env_hi)
 	const size_t stride = (size_t)EnvBlock(b->model->h).stride;
 	HIP_TRY(hipMemcpy(b->env_mass + (size_t)env_lo * stride, b->env_block.data() + (size_t)env_lo * stride, (size_t)(env_hi - env_lo) * stride * sizeof(double),
 	                  hipMemcpyHostToDevice));
+	le_overlay_touch(b, env_lo, env_hi);
 	return MJB_OK;
 }
 
@@ -3209,6 +3283,7 @@ int mjb_set_env_mass_params(mjb_batch *b, int env_lo, int env_hi, const double *
 	if (env_hi > env_lo)  // the mass section of each env's row: rows of jnt0 doubles into rows of stride doubles
 		HIP_TRY(hipMemcpy2D(b->env_mass + (size_t)env_lo * B.stride, (size_t)B.stride * sizeof(double), params, (size_t)B.jnt0 * sizeof(double),
 		                    (size_t)B.jnt0 * sizeof(double), (size_t)(env_hi - env_lo), hipMemcpyHostToDevice));
+	le_overlay_touch(b, env_lo, env_hi);
 	return MJB_OK;
 }
 

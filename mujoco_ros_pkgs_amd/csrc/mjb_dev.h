@@ -187,6 +187,8 @@ struct DevState {
 	                               // index 8 * type1 + type2: read instead of the pair record's copy when per-env geom TYPES are in play (a pair's current types)
 	const double *reset_step;      // [nq + nv + nv] qpos | qvel | qacc_warmstart one step after mj_resetData (mj_checkAcc's reset inside the split step), or NULL
 	int prof_base;                 // profiling build: first of the two probe ids this launch records (mjb_debug_profile_window)
+	const double *le_overlay;      // [slots][nenv] lane = env kernel, mjb_set_lane_env mode 2: each env's own gravity, joint constants, masses / inertias and
+	                               // actuator gains in the kernel's terms (PeSlots, mjb_lane_env_kernel.h); NULL until such a launch builds it
 };
 
 // The env's spill-over block in DevState::efc_Jg (kernel variant 4): efc_J [nefcmax][nv], then -- used only when the frame's row
@@ -360,8 +362,12 @@ enum { MJB_LE_TOPO_NONE = -1, MJB_LE_TOPO_JIT = -2, MJB_LE_UNAVAILABLE = -1000 }
 int mjb_lane_env_eligible(const mjb_model_desc *h);   // the model's structure fits the kernel (compiled in or not)
 const char *mjb_lane_env_jit_error(void);
 void mjb_lane_env_jit_stats(int *compiled, int *disk_hits);  // hiprtc builds of this process / builds taken from the disk cache instead              // why the last hiprtc build of a topology was not available ("" if none failed)
+// (per_env: the kernel that reads DevState::le_overlay -- solo form, whatever the batch size)
 int mjb_launch_lane_env(const KernelParams *Pdev, int topo, const mjb_model_desc *h, int nenv_batch, int env_lo, int env_hi, int nsteps, unsigned int step0,
-                        void *stream);
+                        void *stream, int per_env);
+// the per-env overlay of that kernel: its slot count, and one env's column from the env's gravity and its block of DevState::env_mass (NULL: the model's values)
+int mjb_lane_env_overlay_slots(const mjb_model_desc *h);
+void mjb_lane_env_overlay_row(const mjb_model_desc *h, const double *gravity, const double *env_block, double *out);
 // the split step (mjb_smooth_kernel.h + mjb_cstep_kernel): one step of envs [env_lo, env_hi) -- smooth half in lane = env form, then the constraint half
 int mjb_smooth_match(const mjb_model_desc *h);  // index of the compiled-in SmTopo the model has, or -1
 const char *mjb_smooth_name(int topo);

@@ -41,12 +41,12 @@ namespace {
 
 using namespace mjb_le;
 
-template <class T, int LP>
+template <class T, int LP, bool PE = false>  // (PE: per-env overrides from DevState::le_overlay, mjb_set_lane_env mode 2)
 __global__ void __launch_bounds__(64) mjb_lane_env_kernel(const KernelParams MJB_AS4 *__restrict__ P, const int nsteps, const unsigned int step0,
                                                           const int env_lo, const int env_hi)
 {
 	extern __shared__ __attribute__((aligned(16))) unsigned char smem_le[];
-	lane_env_body<T, LP>(P, nsteps, step0, env_lo, env_hi, smem_le);
+	lane_env_body<T, LP, 0, PE>(P, nsteps, step0, env_lo, env_hi, smem_le);
 }
 
 template <class T, int LP>
@@ -302,12 +302,12 @@ bool source_fingerprint(const std::string &dir, unsigned long long &hsh)
 	return true;
 }
 
-const JitKernel &jit_get(const mjb_model_desc &h, int lp, int duo)  // duo: 0 solo, 1 two halves, 2 pipelined, 3 three wavefronts, 4 four (form 3 with the pose sweep on two)
+const JitKernel &jit_get(const mjb_model_desc &h, int lp, int duo, bool pe)  // duo: 0 solo, 1 two halves, 2 pipelined, 3 three wavefronts, 4 four (form 3 with the pose sweep on two); pe: the solo form with per-env overrides
 {
 	int dev = 0;
 	(void)hipGetDevice(&dev);
 	const std::string topo = topo_source(h);
-	const std::string key = std::to_string(dev) + "|" + std::to_string(lp) + (duo == 4 ? "q|" : duo == 3 ? "t|" : (duo == 2 ? "p|" : (duo ? "d|" : "|"))) + topo;
+	const std::string key = std::to_string(dev) + "|" + std::to_string(lp) + (pe ? "e|" : duo == 4 ? "q|" : duo == 3 ? "t|" : (duo == 2 ? "p|" : (duo ? "d|" : "|"))) + topo;
 	std::lock_guard<std::mutex> lock(jit_mutex);
 	auto it = jit_cache.find(key);
 	if (it != jit_cache.end()) return it->second;
@@ -319,7 +319,10 @@ const JitKernel &jit_get(const mjb_model_desc &h, int lp, int duo)  // duo: 0 so
 	const std::string dir = source_dir();
 	const std::string slp = std::to_string(lp);
 	const std::string src = "#include \"mjb_lane_env_kernel.h\"\n" + topo +
-	                        (duo == 4 ? "extern \"C\" __global__ void __launch_bounds__(256) le_rt(const KernelParams MJB_AS4 *P, int nsteps, unsigned int step0, int lo, int hi)\n{\n"
+	                        (pe ? "extern \"C\" __global__ void __launch_bounds__(64) le_rt(const KernelParams MJB_AS4 *P, int nsteps, unsigned int step0, int lo, int hi)\n{\n"
+	                              "\t__shared__ __attribute__((aligned(16))) unsigned char smem[mjb_le::Lds<LeTopo_rt, " + slp + ">::bytes()];\n"
+	                              "\tmjb_le::lane_env_body<LeTopo_rt, " + slp + ", 0, true>(P, nsteps, step0, lo, hi, smem);\n}\n"
+	                         : duo == 4 ? "extern \"C\" __global__ void __launch_bounds__(256) le_rt(const KernelParams MJB_AS4 *P, int nsteps, unsigned int step0, int lo, int hi)\n{\n"
 	                                    "\t__shared__ __attribute__((aligned(16))) unsigned char smem[mjb_le::quartet_bytes<LeTopo_rt>()];\n"
 	                                    "\tmjb_le::lane_env_quartet<LeTopo_rt, 160>(P, nsteps, step0, lo, hi, smem);\n}\n"
 	                         : duo == 3 ? "extern \"C\" __global__ void __launch_bounds__(192) le_rt(const KernelParams MJB_AS4 *P, int nsteps, unsigned int step0, int lo, int hi)\n{\n"
@@ -461,6 +464,66 @@ size_t mjb_lane_env_tape_doubles(const mjb_model_desc *h)
 	return (sizeof(LeTapeHdr) + (size_t)h->nbody * sizeof(LeTapeBody) + (size_t)h->nu * sizeof(LeTapeAct)) / sizeof(double);
 }
 
+// Ib = R(iquat) diag(inertia) R(iquat)': xx yy zz xy xz yz
+static void le_ibody(const double *q, const double *in, double *ibody)
+{
+	double R[9];
+	const double q00 = q[0] * q[0], q01 = q[0] * q[1], q02 = q[0] * q[2], q03 = q[0] * q[3], q11 = q[1] * q[1], q12 = q[1] * q[2], q13 = q[1] * q[3],
+	             q22 = q[2] * q[2], q23 = q[2] * q[3], q33 = q[3] * q[3];
+	R[0] = q00 + q11 - q22 - q33; R[4] = q00 - q11 + q22 - q33; R[8] = q00 - q11 - q22 + q33;
+	R[1] = 2 * (q12 - q03); R[2] = 2 * (q13 + q02); R[3] = 2 * (q12 + q03); R[5] = 2 * (q23 - q01); R[6] = 2 * (q13 - q02); R[7] = 2 * (q23 + q01);
+	auto e = [&](int r, int c) { return R[3 * r] * in[0] * R[3 * c] + R[3 * r + 1] * in[1] * R[3 * c + 1] + R[3 * r + 2] * in[2] * R[3 * c + 2]; };
+	ibody[0] = e(0, 0); ibody[1] = e(1, 1); ibody[2] = e(2, 2); ibody[3] = e(0, 1); ibody[4] = e(0, 2); ibody[5] = e(1, 2);
+}
+
+// ---- the per-env overlay of the PE kernels (PeSlots, mjb_lane_env_kernel.h): one env's column, in slot order ----
+static bool le_moving(const mjb_model_desc *h, int b)  // a joint on the body's path to the world
+{
+	for (int a = b; a > 0; a = h->body_parentid[a])
+		if (h->body_jntnum[a] > 0) return true;
+	return false;
+}
+int mjb_lane_env_overlay_slots(const mjb_model_desc *h)
+{
+	int nj = 0, nm = 0;
+	for (int b = 1; b < h->nbody; b++) {
+		nj += h->body_jntnum[b] == 1;
+		nm += le_moving(h, b);
+	}
+	return 3 + 4 * nj + 7 * nm + 6 * h->nu + (h->nbody - 1 - nm);
+}
+// gravity: the env's (NULL: the model's); env_block: the env's block of DevState::env_mass, mass and joint section (NULL: the model's values)
+void mjb_lane_env_overlay_row(const mjb_model_desc *h, const double *gravity, const double *env_block, double *out)
+{
+	const int nb = h->nbody, nv = h->nv, jnt0 = 7 * nb + nv + h->ntendon + 1;
+	const double *mass = env_block ? env_block : h->body_mass, *inertia = env_block ? env_block + 2 * nb : h->body_inertia;
+	const double *damping = env_block ? env_block + jnt0 : h->dof_damping, *armature = env_block ? env_block + jnt0 + nv : h->dof_armature;
+	const double *stiffness = env_block ? env_block + jnt0 + 4 * nv : h->jnt_stiffness;
+	const double *gain = env_block ? env_block + jnt0 + 4 * nv + h->njnt : h->actuator_gainprm, *bias = env_block ? gain + 3 * h->nu : h->actuator_biasprm;
+	double *o = out;
+	for (int k = 0; k < 3; k++) *o++ = gravity ? gravity[k] : h->gravity[k];
+	for (int b = 1; b < nb; b++)
+		if (h->body_jntnum[b] == 1) {
+			const int j = h->body_jntadr[b], da = h->jnt_dofadr[j];
+			*o++ = stiffness[j];
+			*o++ = damping[da];
+			*o++ = armature[da];
+			*o++ = h->timestep[0] * damping[da];
+		}
+	for (int b = 1; b < nb; b++)
+		if (le_moving(h, b)) {
+			*o++ = mass[b];
+			le_ibody(h->body_iquat + 4 * b, inertia + 3 * b, o);
+			o += 6;
+		}
+	for (int i = 0; i < h->nu; i++) {
+		for (int k = 0; k < 3; k++) *o++ = gain[3 * i + k];
+		for (int k = 0; k < 3; k++) *o++ = bias[3 * i + k];
+	}
+	for (int b = 1; b < nb; b++)
+		if (!le_moving(h, b)) *o++ = mass[b];
+}
+
 void mjb_lane_env_tape(const mjb_model_desc *h, double *tape)
 {
 	LeTapeHdr *th = reinterpret_cast<LeTapeHdr *>(tape);
@@ -472,16 +535,7 @@ void mjb_lane_env_tape(const mjb_model_desc *h, double *tape)
 		LeTapeBody &t = tb[b];
 		for (int k = 0; k < 3; k++) { t.pos[k] = h->body_pos[3 * b + k]; t.ipos[k] = h->body_ipos[3 * b + k]; }
 		for (int k = 0; k < 4; k++) t.quat[k] = h->body_quat[4 * b + k];
-		{  // Ib = R(iquat) diag(inertia) R(iquat)': xx yy zz xy xz yz
-			const double *q = h->body_iquat + 4 * b, *in = h->body_inertia + 3 * b;
-			double R[9];
-			const double q00 = q[0] * q[0], q01 = q[0] * q[1], q02 = q[0] * q[2], q03 = q[0] * q[3], q11 = q[1] * q[1], q12 = q[1] * q[2], q13 = q[1] * q[3],
-			             q22 = q[2] * q[2], q23 = q[2] * q[3], q33 = q[3] * q[3];
-			R[0] = q00 + q11 - q22 - q33; R[4] = q00 - q11 + q22 - q33; R[8] = q00 - q11 - q22 + q33;
-			R[1] = 2 * (q12 - q03); R[2] = 2 * (q13 + q02); R[3] = 2 * (q12 + q03); R[5] = 2 * (q23 - q01); R[6] = 2 * (q13 - q02); R[7] = 2 * (q23 + q01);
-			auto e = [&](int r, int c) { return R[3 * r] * in[0] * R[3 * c] + R[3 * r + 1] * in[1] * R[3 * c + 1] + R[3 * r + 2] * in[2] * R[3 * c + 2]; };
-			t.ibody[0] = e(0, 0); t.ibody[1] = e(1, 1); t.ibody[2] = e(2, 2); t.ibody[3] = e(0, 1); t.ibody[4] = e(0, 2); t.ibody[5] = e(1, 2);
-		}
+		le_ibody(h->body_iquat + 4 * b, h->body_inertia + 3 * b, t.ibody);
 		t.mass = h->body_mass[b];
 		if (h->body_jntnum[b] == 1) {
 			const int j = h->body_jntadr[b];
@@ -518,13 +572,13 @@ const char *mjb_lane_env_name(int topo)
 // topo >= 0: a compiled-in topology; MJB_LE_TOPO_JIT: the model's own, compiled by hiprtc on first use (h = the model; returns
 // MJB_LE_UNAVAILABLE when that is not possible: the caller launches the generic kernel)
 int mjb_launch_lane_env(const KernelParams *Pdev, int topo, const mjb_model_desc *h, int nenv_batch, int env_lo, int env_hi, int nsteps, unsigned int step0,
-                        void *stream)
+                        void *stream, int per_env)
 {
 	const int n = env_hi - env_lo;
 	if (n <= 0) return 0;
 	// (measurement knob: envs per wavefront < 64 -- the wavefront starts with its upper lanes off)
 	static const int wl_env = mjb_env_int("MJB_LANE_ENV_WAVE_LANES", 64);
-	const int wl = (wl_env == 16 || wl_env == 32) ? wl_env : 64;
+	const int wl = (!per_env && (wl_env == 16 || wl_env == 32)) ? wl_env : 64;  // (the per-env build always runs full wavefronts)
 	const dim3 grid((unsigned int)((n + wl - 1) / wl)), block(wl);
 	// LDS budget per wavefront from the CUs the launch leaves idle: one wavefront per CU may take all of its LDS
 	// (per DEVICE: a process may drive several GPUs, one batch each -- ADVICE r05)
@@ -536,8 +590,8 @@ int mjb_launch_lane_env(const KernelParams *Pdev, int topo, const mjb_model_desc
 	//  few multiply-adds differently around that -- results agree to rounding, not bit for bit -- so every launch of one batch, whole or
 	//  a prefix / the rest of a split step, runs the same one)
 	const int waves = (nenv_batch + 63) / 64;
-	int lp = (ncu > 0 && waves <= ncu) ? 160 : ((ncu > 0 && waves <= 2 * ncu) ? 80 : 40);
-	if (forced == 40 || forced == 80 || forced == 160) lp = forced;
+	const int lp_batch = (forced == 40 || forced == 80 || forced == 160) ? forced : ((ncu > 0 && waves <= ncu) ? 160 : ((ncu > 0 && waves <= 2 * ncu) ? 80 : 40));
+	int lp = lp_batch;
 	// DUO: two wavefronts per 64 envs (mjb_lane_env_kernel.h) while the batch leaves at least every second SIMD idle -- the step's
 	// position half and velocity half side by side.  MJB_LANE_ENV_DUO=0 / 1: never / whenever the LDS budget allows (measurement knob)
 	static const int duo_env = mjb_env_int("MJB_LANE_ENV_DUO", -1);
@@ -557,6 +611,10 @@ int mjb_launch_lane_env(const KernelParams *Pdev, int topo, const mjb_model_desc
 	const int sweep_ov = sweep_set ? sweep_set : sweep_env;
 	int sweep = duo == 3 ? (sweep_ov ? sweep_ov : (waves <= ncu ? 4 : 3)) : 0;
 	if (duo_mode > 0 && lp < 80) lp = 80, duo = 1;  // (a forced two-wavefront form on a batch that would run four wavefronts per CU: two per CU)
+	if (per_env) {  // per-env overrides: the solo form at the budget the batch's size (or the knob) gives, whatever form is asked for
+		lp = lp_batch;
+		duo = 0, sweep = 0;
+	}
 	if (topo == MJB_LE_TOPO_JIT) {
 		if (!h) return (int)hipErrorInvalidValue;
 		{  // a larger model than the compiled-in ones: the smallest LDS budget its (qpos, qvel) pairs and body forces fit (fewer wavefronts per CU then)
@@ -578,7 +636,7 @@ int mjb_launch_lane_env(const KernelParams *Pdev, int topo, const mjb_model_desc
 			if (duo == 2 && need + 5 * ((need - h->nv) / 3) + 12 + (h->nv + 1) / 2 + 1 > 160) duo = 1;
 			if (duo == 1 && need + (h->nv + 1) / 2 + 1 > lp) duo = 0;
 		}
-		const JitKernel &k = jit_get(*h, lp, sweep == 4 ? 4 : duo);
+		const JitKernel &k = jit_get(*h, lp, sweep == 4 ? 4 : duo, per_env != 0);
 		if (!k.fn) {
 			set_jit_error(k.error);
 			return MJB_LE_UNAVAILABLE;
@@ -595,6 +653,17 @@ int mjb_launch_lane_env(const KernelParams *Pdev, int topo, const mjb_model_desc
 	{                                                                                                                                         \
 		auto kern = mjb_lane_env_kernel<T, LPV>;                                                                                              \
 		constexpr int bytes = Lds<T, LPV>::bytes();                                                                                           \
+		const hipError_t attr = lds_attr_once(reinterpret_cast<const void *>(kern), bytes, cur_dev);                                          \
+		if (attr != hipSuccess) return (int)attr;                                                                                             \
+		le_form_last = 0, le_sweep_last = 0;                                                                                                  \
+		hipLaunchKernelGGL(kern, grid, block, bytes, (hipStream_t)stream, (const KernelParams MJB_AS4 *)Pdev, nsteps, step0, env_lo, env_hi); \
+		return (int)hipGetLastError();                                                                                                        \
+	}
+#define MJB_LE_GO_PE(T, LPV)                                                                                                                 \
+	{                                                                                                                                         \
+		auto kern = mjb_lane_env_kernel<T, LPV, true>;                                                                                        \
+		constexpr int bytes = Lds<T, LPV>::bytes();                                                                                           \
+		if (!h || PeSlots<T>::n != mjb_lane_env_overlay_slots(h)) return (int)hipErrorInvalidValue;                                           \
 		const hipError_t attr = lds_attr_once(reinterpret_cast<const void *>(kern), bytes, cur_dev);                                          \
 		if (attr != hipSuccess) return (int)attr;                                                                                             \
 		le_form_last = 0, le_sweep_last = 0;                                                                                                  \
@@ -633,6 +702,9 @@ int mjb_launch_lane_env(const KernelParams *Pdev, int topo, const mjb_model_desc
 	}
 #define MJB_LE_X(id, T)                      \
 	if (topo == id) {                        \
+		if (per_env && lp == 160) MJB_LE_GO_PE(T, 160) \
+		if (per_env && lp == 80) MJB_LE_GO_PE(T, 80)   \
+		if (per_env) MJB_LE_GO_PE(T, 40)         \
 		if (duo == 3 && sweep == 4) MJB_LE_GO_TRIO(T, 4) \
 		if (duo == 3) MJB_LE_GO_TRIO(T, 3)   \
 		if (duo >= 2) MJB_LE_GO_DUO2(T)      \
@@ -645,6 +717,7 @@ int mjb_launch_lane_env(const KernelParams *Pdev, int topo, const mjb_model_desc
 	MJB_LE_TOPOS(MJB_LE_X)
 #undef MJB_LE_X
 #undef MJB_LE_GO
+#undef MJB_LE_GO_PE
 #undef MJB_LE_GO_DUO
 #undef MJB_LE_GO_DUO2
 #undef MJB_LE_GO_TRIO

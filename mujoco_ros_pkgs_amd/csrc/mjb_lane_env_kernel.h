@@ -189,6 +189,23 @@ template <class T, int LP> struct Lds {
 
 struct alignas(16) Pair { double a, b; };
 
+// The per-env overlay (DevState::le_overlay, PE kernels): the tape's numbers an env may carry its own value of (mjb_set_env_*), as rows
+// [slot][env] -- a wavefront's 64 lanes read 64 consecutive doubles.  Slots: gravity[3]; per JOINTED body, in body order, stiffness |
+// damping | armature | hdamping; per MOVING body (a joint on its path to the world) mass | ibody[6]; per actuator gain[3] | bias[3];
+// then the mass of every body at rest but the world (mj_energyPos alone reads it).  mjb_lane_env_overlay_row (mjb_lane_env.hip) fills
+// a column in this order.
+template <class T> struct PeSlots {
+	static constexpr bool moving(int b) { return Lds<T, (1 << 20)>::needed(b); }
+	static constexpr int njb(int b) { int n = 0; for (int a = 1; a < b; a++) if (T::body_jnt[a] >= 0) n++; return n; }  // jointed bodies ahead of b
+	static constexpr int nmb(int b) { int n = 0; for (int a = 1; a < b; a++) if (moving(a)) n++; return n; }             // moving bodies ahead of b
+	static constexpr int gravity(int k) { return k; }
+	static constexpr int joint(int b, int f) { return 3 + 4 * njb(b) + f; }  // f: 0 stiffness, 1 damping, 2 armature, 3 hdamping
+	static constexpr int inert(int b, int f) { return 3 + 4 * njb(T::NBODY) + 7 * nmb(b) + f; }  // f: 0 mass, 1 .. 6 ibody
+	static constexpr int act(int i, int f) { return 3 + 4 * njb(T::NBODY) + 7 * nmb(T::NBODY) + 6 * i + f; }  // f: 0 .. 2 gain, 3 .. 5 bias
+	static constexpr int rest(int b) { return act(T::NU, 0) + (b - 1 - nmb(b)); }
+	static constexpr int n = act(T::NU, 0) + (T::NBODY - 1 - nmb(T::NBODY));
+};
+
 // ROLE: 0 = one wavefront runs the whole step of its 64 envs.  1 / 2 = the DUO form, two wavefronts of one workgroup (on two SIMDs of a CU) share
 // the 64 envs of the block: the step's two independent halves -- what depends on qpos alone (poses, cinert, composite inertias, qM, both factors:
 // role 1, "P") and what depends on qvel too (velocities, the bodies' forces, the force block, qfrc_smooth: role 2, "V") -- run side by side, V hands
@@ -199,7 +216,9 @@ struct alignas(16) Pair { double a, b; };
 // loads -- V's ctrl-noise normals and qfrc_applied are fetched a sweep ahead of their use precisely so that nobody waits for HBM)
 DEVI void le_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 template <int NV> struct DuoSlots { static constexpr int n = (NV + 1) / 2 + 1; };  // qfrc_smooth pairs + the mail slot
-template <class T, int LP, int ROLE = 0>
+// PE: the batch carries per-env overrides (mjb_set_lane_env mode 2): gravity, the joint constants, masses / inertias and the actuator gains come
+// per lane from DevState::le_overlay instead of the tape (solo form only).
+template <class T, int LP, int ROLE = 0, bool PE = false>
 DEVI void lane_env_body(const KernelParams MJB_AS4 *__restrict__ P, const int nsteps, const unsigned int step0, const int env_lo, const int env_hi,
                         unsigned char *const smem_le)
 {
@@ -224,6 +243,8 @@ DEVI void lane_env_body(const KernelParams MJB_AS4 *__restrict__ P, const int ns
 	constexpr bool EPOS = ROLE == 0 || ROLE == 1 || ROLE == 3 || ROLE == 5 || ROLE == 9;                     // gathers mj_energyPos along its pose sweep
 	constexpr bool SENSF = ROLE == 0 || ROLE == 2 || ROLE == 3 || ROLE == 5 || ROLE == 9;  // frame sensors: who holds the poses (and, of two, who has the time)
 	using Q = Tq<T>;
+	static_assert(!PE || ROLE == 0, "lane = env kernel: per-env overrides run the solo form");
+	using OV = PeSlots<T>;
 	constexpr int LPE = PIPE ? (1 << 20) : (DUO ? LP - DuoSlots<NV>::n : LP);
 	using LD = Lds<T, LPE>;
 	static_assert(LD::slot(T::NBODY) <= LPE, "lane = env kernel: state and forces of the topology need more LDS than this instantiation's budget");
@@ -366,6 +387,20 @@ DEVI void lane_env_body(const KernelParams MJB_AS4 *__restrict__ P, const int ns
 				tb = reinterpret_cast<const LeTapeBody MJB_AS4 *>(th + 1);
 			}
 			const LeTapeAct MJB_AS4 *const ta = reinterpret_cast<const LeTapeAct MJB_AS4 *>(tb + NB);
+			// (PE) the env's own value of overlay slot sl: base + sl * nenv + env, the address re-derived on every trip like the tape's (a tail lane reads
+			//  the last env's column, as `ev` does everywhere else)
+			[[maybe_unused]] const char *ovb = nullptr;
+			[[maybe_unused]] size_t ovs = 0;
+			if constexpr (PE) {
+				const double *o = s.le_overlay;
+				asm volatile("" : "+s"(o));
+				ovb = reinterpret_cast<const char *>(o);
+				ovs = (size_t)s.nenv * sizeof(double);
+			}
+			[[maybe_unused]] const unsigned int ovl = (unsigned int)env * (unsigned int)sizeof(double);
+			[[maybe_unused]] auto pe_ld = [&](int sl) -> double {
+				return *(const double __attribute__((address_space(1))) *)(ovb + (size_t)sl * ovs + ovl);
+			};
 			const bool e_on = DP && last && (m.enableflags & MJB_ENBL_ENERGY);
 			bool ep_on = e_on;
 			if constexpr (EPOS != DP) ep_on = EPOS && last && (m.enableflags & MJB_ENBL_ENERGY);
@@ -390,6 +425,9 @@ DEVI void lane_env_body(const KernelParams MJB_AS4 *__restrict__ P, const int ns
 			double grav[3];
 			{
 				const bool g_on = !(m.disableflags & MJB_DSBL_GRAVITY);
+				if constexpr (PE) {
+					for (int k = 0; k < 3; k++) { const double g = pinv(pe_ld(OV::gravity(k))); grav[k] = g_on ? g : 0.0; }
+				} else
 				for (int k = 0; k < 3; k++) grav[k] = g_on ? th->gravity[k] : 0.0;
 			}
 			const bool pas_on = !(m.disableflags & MJB_DSBL_PASSIVE);
@@ -397,6 +435,7 @@ DEVI void lane_env_body(const KernelParams MJB_AS4 *__restrict__ P, const int ns
 			// (two scheduling regions per body, each fetching the NEXT region's half record at its top: the scalar loads of a region
 			//  cannot be hoisted beyond it -- left alone, the compiler issues them bodies ahead and parks ~540 SGPRs in VGPR lanes)
 			double hA[NB + 1][16], hB[NB][16];
+			[[maybe_unused]] double vB[PE ? NB : 1][7];  // (PE) the env's mass | ibody[6] of a body, fetched with the body's inertial half record
 			for (int k = 0; k < 14; k++) hA[1][k] = reinterpret_cast<const double MJB_AS4 *>(tb + 1)[k];
 			// ... and the (qpos, qvel) pair of the next jointed body: LDS reads and scalar loads share one counter, so a read issued where
 			// it is needed would wait for the record fetched beside it
@@ -624,6 +663,10 @@ DEVI void lane_env_body(const KernelParams MJB_AS4 *__restrict__ P, const int ns
 				touch_s(hA[b][0]);
 				if constexpr (j >= 0) touch_v(pq[b].a);
 				for (int k = 0; k < 10; k++) hB[b][k] = reinterpret_cast<const double MJB_AS4 *>(tb + b)[16 + k];
+				if constexpr (PE) {
+					if constexpr (OV::moving(b)) for (int k = 0; k < 7; k++) vB[b][k] = pe_ld(OV::inert(b, k));
+					else vB[b][0] = pe_ld(OV::rest(b));
+				}
 				const double *const A = hA[b];  // pos[3] quat[4] jaxis[3] jpos[3] qpos0 stiffness spring
 				if constexpr (ROLE == 5 && b == 1 && b + 1 < NB) {
 					if constexpr (T::body_jnt[b + 1] >= 0) {
@@ -666,6 +709,8 @@ DEVI void lane_env_body(const KernelParams MJB_AS4 *__restrict__ P, const int ns
 					}
 					if (ep_on && pas_on) {  // mj_energyPos: the joint spring
 						const double dqs = qp - tb[b].spring;  // (last step only)
+						if constexpr (PE) pe += 0.5 * pe_ld(OV::joint(b, 0)) * dqs * dqs;
+						else
 						pe += 0.5 * tb[b].stiffness * dqs * dqs;
 					}
 				}
@@ -706,7 +751,7 @@ DEVI void lane_env_body(const KernelParams MJB_AS4 *__restrict__ P, const int ns
 					matvec3(v, xmat[b], ip);
 					for (int k = 0; k < 3; k++) xipos[k] = v[k] + xpos[b][k];
 				}
-				const double mass = Bh[9];
+				const double mass = [&] { if constexpr (PE) return vB[b][0]; else return Bh[9]; }();
 				if (eg_on) pe -= mass * (grav[0] * xipos[0] + grav[1] * xipos[1] + grav[2] * xipos[2]);
 				frame_sensors(B, xipos);
 				if constexpr (LD::needed(b)) {
@@ -719,7 +764,8 @@ DEVI void lane_env_body(const KernelParams MJB_AS4 *__restrict__ P, const int ns
 						// world inertia X Ib X' with the body-frame inertia matrix Ib = R(iquat) diag(inertia) R(iquat)' from the tape
 						// (mju_inertCom builds the same matrix as ximat diag ximat', ximat = X R(iquat))
 						const double *X = xmat[b];
-						const double ixx = Bh[3], iyy = Bh[4], izz = Bh[5], ixy = Bh[6], ixz = Bh[7], iyz = Bh[8];
+						const double *const Ib = [&] { if constexpr (PE) return vB[b] + 1; else return Bh + 3; }();
+						const double ixx = Ib[0], iyy = Ib[1], izz = Ib[2], ixy = Ib[3], ixz = Ib[4], iyz = Ib[5];
 						double Tm[9];
 						for (int rr = 0; rr < 3; rr++) {
 							Tm[3 * rr + 0] = X[3 * rr] * ixx + X[3 * rr + 1] * ixy + X[3 * rr + 2] * ixz;
@@ -1050,6 +1096,12 @@ DEVI void lane_env_body(const KernelParams MJB_AS4 *__restrict__ P, const int ns
 					sq[j] = lp[64 * j];
 					const LeTapeBody MJB_AS4 &tj = tb[T::jnt_bodyid[j]];
 					double pas = 0;
+					if constexpr (PE) {
+						if (pas_on) {
+							pas = -pe_ld(OV::joint(T::jnt_bodyid[j], 0)) * (sq[j].a - tj.spring);
+							pas -= pe_ld(OV::joint(T::jnt_bodyid[j], 1)) * sq[j].b;
+						}
+					} else
 					if (pas_on) {
 						pas = -tj.stiffness * (sq[j].a - tj.spring);
 						pas -= tj.damping * sq[j].b;
@@ -1069,9 +1121,16 @@ DEVI void lane_env_body(const KernelParams MJB_AS4 *__restrict__ P, const int ns
 							if (clamp_on) c = clampd(c, A.ctrllo, A.ctrlhi);
 						}
 						const double len = sq[j].a * gear, vel = sq[j].b * gear;
-						double gain = A.gain[0], bs = 0;
+						double gain = 0, bs = 0;
+						if constexpr (PE) {
+							gain = pe_ld(OV::act(i, 0));
+							if constexpr (T::act_gaintype[i] == MJB_GAIN_AFFINE) gain = gain + pe_ld(OV::act(i, 1)) * len + pe_ld(OV::act(i, 2)) * vel;
+							if constexpr (T::act_biastype[i] == MJB_BIAS_AFFINE) bs = pe_ld(OV::act(i, 3)) + pe_ld(OV::act(i, 4)) * len + pe_ld(OV::act(i, 5)) * vel;
+						} else {
+						gain = A.gain[0];
 						if constexpr (T::act_gaintype[i] == MJB_GAIN_AFFINE) gain = gain + A.gain[1] * len + A.gain[2] * vel;
 						if constexpr (T::act_biastype[i] == MJB_BIAS_AFFINE) bs = A.bias[0] + A.bias[1] * len + A.bias[2] * vel;
+						}
 						force = gain * c + bs;
 						if constexpr (T::act_forcelimited[i]) force = clampd(force, A.forcelo, A.forcehi);
 						f[j] += gear * force;
@@ -1110,6 +1169,8 @@ DEVI void lane_env_body(const KernelParams MJB_AS4 *__restrict__ P, const int ns
 			auto fetch_body = [&](auto Bn) {
 				constexpr int nb = Bn;
 				constexpr int q0 = LD::slot(nb);
+				if constexpr (PE && T::body_jnt[nb] >= 0) parm[nb] = pe_ld(OV::joint(nb, 2));
+				else
 				if constexpr (DP && T::body_jnt[nb] >= 0) parm[nb] = tb[nb].armature;
 				if constexpr (DV) {
 					const Pair c0 = lp[64 * q0], c1 = lp[64 * (q0 + 1)], c2 = lp[64 * (q0 + 2)];
@@ -1134,6 +1195,8 @@ DEVI void lane_env_body(const KernelParams MJB_AS4 *__restrict__ P, const int ns
 				if constexpr (LD::needed(b)) {
 					if constexpr (DV) touch_v(pcf[b][0]);
 					else if constexpr (DP && LD::cin_slot(b) >= 0) touch_v(pcb[b][0]);
+					if constexpr (PE && j >= 0) touch_v(parm[b]);
+					else
 					if constexpr (DP && j >= 0) touch_s(parm[b]);
 					{
 						constexpr int nb = [] { for (int c = b - 1; c >= 1; c--) if (LD::needed(c)) return c; return 0; }();
@@ -1225,6 +1288,10 @@ DEVI void lane_env_body(const KernelParams MJB_AS4 *__restrict__ P, const int ns
 				sfor<NV>([&](auto I) {
 					sfor<NV>([&](auto A) {
 						constexpr int i = I, a = A;
+						if constexpr (PE) {
+							if constexpr (Q::anc(a, i) && a == i) qH[i][a] = qM[i][a] + pe_ld(OV::joint(T::jnt_bodyid[i], 3));
+							else if constexpr (Q::anc(a, i)) qH[i][a] = qM[i][a];
+						} else
 						if constexpr (Q::anc(a, i)) qH[i][a] = qM[i][a] + (a == i ? tb[T::jnt_bodyid[i]].hdamping : 0.0);
 					});
 				});

@@ -74,6 +74,22 @@ class CompiledModel:
     def frame_doubles(self):
         return self.lib.mjb_frame_doubles(self.ptr)
 
+    def lane_env_tape(self):
+        """The lane = env kernel's constant tape of the model (mjb_model_lane_env_tape), or None when the model is not eligible."""
+        return self._lane_env_doubles(self.lib.mjb_model_lane_env_tape)
+
+    def lane_env_overlay(self):
+        """One env's column of the per-env table of Batch.set_lane_env(2), with the model's own values (mjb_model_lane_env_overlay); None: not eligible."""
+        return self._lane_env_doubles(self.lib.mjb_model_lane_env_overlay)
+
+    def _lane_env_doubles(self, fn):
+        n = fn(self.ptr, None, 0)
+        if n < 0:
+            return None
+        out = np.zeros(n)
+        fn(self.ptr, out.ctypes.data_as(C.POINTER(C.c_double)), n)
+        return out
+
     def frame_info(self):
         """(the row-slot Newton / CG solver runs, the full frame lives in HBM, the fused frame lives in HBM) -- mjb_model_frame_info."""
         full, fused = C.c_int(0), C.c_int(0)
@@ -341,7 +357,9 @@ class Batch:
         return ("in-kernel", "same-stream", "side-stream")[int(self.lib.mjb_noise_mode(self.ptr))]
 
     def set_lane_env(self, mode):
-        """-1 automatic, 0 never, 1 whenever eligible: the lane = env form of the unconstrained fused step (mjb_set_lane_env)."""
+        """-1 automatic, 0 never, 1 whenever eligible, 2 whenever eligible -- also when the batch carries per-env gravity or parameter blocks
+        (set_env_gravity, set_env_body_mass, set_env_dof_params, set_env_joint_stiffness, set_env_actuator_params, ...), which the kernel then reads
+        per env; such a batch runs the generic kernels in every other mode: the lane = env form of the unconstrained fused step (mjb_set_lane_env)."""
         _check(self.lib.mjb_set_lane_env(self.ptr, int(mode)), "mjb_set_lane_env")
 
     def lane_env_info(self):
