@@ -276,6 +276,19 @@ int mjb_fused_frame(const mjb_batch *b);
  * The environment variable MJB_LANE_ENV (same values) sets the default of new batches (read by mjb_make_batch).  While mjb_set_stats is
  * counting, fused launches run the generic kernels whatever the mode (the counters live in those).  No reference counterpart. */
 int mjb_set_lane_env(mjb_batch *b, int mode);
+/* Opt-in (default off): with on = 1 the device hwsim stage (mjb_hwsim_configure, below) no longer stands the lane = env kernel down.  The batch's
+ * eligible launches then run the kernel's one-wavefront form (mjb_lane_env_last_form() == 0, at the LDS budget the batch size gives, whatever form is
+ * asked for) in a build that carries the stage: DefaultRobotHWSim::writeSim for one env per lane, at the control-callback point of every step (after
+ * the position and velocity stages, before actuation; a second time in the retry after a mj_checkAcc reset), with the controller cadence of
+ * mjb_hwsim_set_period, the e-stop rules, and the commands / PID state / cadence stamps read and written where mjb_hwsim_* keeps them -- the generic
+ * kernels continue the same batch, results equal to theirs to rounding.  Every other condition of mjb_set_lane_env stays (mode 0 never, the 4096-env
+ * threshold of mode -1, a compiled-in or hiprtc-built topology, whole fused launches, no xfrc_applied / frame dump / statistics, Euler).  A batch
+ * that has BOTH a hwsim stage and per-env gravity or parameter blocks keeps the generic kernels in every mode (there is no build with both), and so
+ * does a configuration in which two entries control one joint.  With the switch off, or without a hwsim stage, every launch runs what it ran without
+ * this call.  Measured on config 2's model with a seven-controller set (tools/lane_env_hwsim_rate.py, profiles/lane_env_hwsim.txt): 9.65 x the generic
+ * kernel's rate at 65 536 envs (1757 against 182 M env-steps/s), level with it at 4096 envs (189 against 182), and half the rate of the same kernel
+ * without a stage.  No reference counterpart. */
+int mjb_lane_env_set_hwsim(mjb_batch *b, int on);
 /* The lane = env kernel evaluates the sensor stages (A15) at the LAST step of a fused launch: sensordata is an output of the launch and nothing inside
  * it reads the values (the generic kernels evaluate them at every step into the LDS frame).  on = 1 makes it evaluate -- and store -- them at every
  * step: same results after the launch, and the per-step cost of A15 on that kernel becomes measurable (bench.py: other_configs.2_sensors_every_step). */

@@ -182,6 +182,8 @@ struct mjb_batch {
 	size_t zcap = 0;               // its capacity in doubles PER HALF
 	bool zdouble = false;          // two halves allocated (side-stream speculation possible)
 	size_t zfail = (size_t)-1;     // smallest total allocation (doubles) that failed: not retried
+	bool lane_env_hwsim = false;   // mjb_lane_env_set_hwsim: a batch with the device hwsim stage may run the lane = env kernel's HW build
+	bool hw_le_ok = false;         // the hwsim configuration has a per-dof table (HwSim::le_tab): no dof controlled by two entries
 	int lane_env_mode = -1;        // mjb_set_lane_env: -1 automatic, 0 never, 1 whenever eligible, 2 whenever eligible, also with per-env gravity / parameter blocks
 	double *le_overlay = nullptr;  // mode 2: the per-env overlay of the lane = env kernel, [mjb_lane_env_overlay_slots][nenv] (DevState::le_overlay), built at the first such launch
 	int le_ov_lo = 0, le_ov_hi = 0;  // envs [lo, hi) whose overlay columns a setter has outdated since (empty: lo >= hi)
@@ -2154,11 +2156,13 @@ static int speculate_ctrl_noise(mjb_batch *b, const LaunchReq &q, int zhalf_now)
 }
 
 // The lane = env kernel (mjb_lane_env.hip) for fused launches of a model whose topology is compiled in: one env per lane, no frame.
-// Per-env model overrides, the device hwsim stage, xfrc_applied and frame dumps keep the generic kernels.
+// Per-env model overrides (but mode 2), the device hwsim stage (but mjb_lane_env_set_hwsim), xfrc_applied and frame dumps keep the generic kernels.
+// (mjb_lane_env_set_hwsim: the hwsim stage rides along in the kernel's HW build -- unless the batch has per-env gravity or parameter blocks too)
+static bool le_hwsim(const mjb_batch *b) { return b->hw.n > 0 && b->lane_env_hwsim && b->hw_le_ok && !b->env_mass && !b->env_gravity; }
 static bool want_lane_env(const mjb_batch *b, const LaunchReq &q, int variant)
 {
 	if (!(q.mode == MJB_MODE_STEP && q.compact && variant == MJB_KV_NONE && b->model->le_topo != MJB_LE_TOPO_NONE && !b->le_unavailable && b->lane_env_mode != 0 &&
-	      (no_env_overrides(b) || (b->lane_env_mode == 2 && b->hw.n == 0)) && !b->st.stats))  // (mode 2: per-env gravity and parameter blocks ride along, le_overlay_sync)
+	      (no_env_overrides(b) || (b->lane_env_mode == 2 && b->hw.n == 0) || le_hwsim(b)) && !b->st.stats))  // (mode 2: per-env gravity and parameter blocks ride along, le_overlay_sync)
 		return false;
 	static const int min_envs = mjb_env_int("MJB_LANE_ENV_MIN_ENVS", 4096);
 	return b->lane_env_mode >= 1 || q.env_hi - q.env_lo >= min_envs;  // (also the fused launch of a split step's non-callback envs, mjb_step_rest)
@@ -2254,7 +2258,7 @@ static int launch(mjb_batch *b, int mode, int nsteps, int env_lo = 0, int env_hi
 	bool use_le = want_lane_env(b, q, variant);
 	b->lane_env_used = use_le;
 	if (use_le) {
-		rc = mjb_launch_lane_env(b->params_dev, b->model->le_topo, &b->model->h, b->nenv, env_lo, env_hi, nsteps, b->step_counter, q.stream, le_per_env ? 1 : 0);
+		rc = mjb_launch_lane_env(b->params_dev, b->model->le_topo, &b->model->h, b->nenv, env_lo, env_hi, nsteps, b->step_counter, q.stream, le_per_env ? MJB_LE_OVERLAY : (b->hw.n > 0 ? MJB_LE_HWSIM : MJB_LE_PLAIN));
 		if (rc == MJB_LE_UNAVAILABLE) {  // (no hiprtc / no kernel header / compile error: remembered, the generic kernel runs -- mjb_lane_env_info says why)
 			b->le_unavailable = true;
 			b->lane_env_used = use_le = false;
@@ -2887,6 +2891,12 @@ int mjb_set_lane_env(mjb_batch *b, int mode)
 {
 	if (!b || mode < -1 || mode > 2) return fail(MJB_EINVAL, "mjb_set_lane_env: bad argument");
 	b->lane_env_mode = mode;
+	return MJB_OK;
+}
+int mjb_lane_env_set_hwsim(mjb_batch *b, int on)
+{
+	if (!b) return fail(MJB_EINVAL, "null batch");
+	b->lane_env_hwsim = on != 0;
 	return MJB_OK;
 }
 int mjb_set_sensors_every_step(mjb_batch *b, int on)
@@ -3709,15 +3719,24 @@ int mjb_hwsim_configure(mjb_batch *b, int n, const mjb_hwsim_joint *joints)
 	if (b->hw_cad) hipFree(b->hw_cad);
 	b->hw_ints = nullptr; b->hw_gains = nullptr; b->hw_cmd = nullptr; b->hw_pid = nullptr; b->hw_cad = nullptr;
 	b->hw = HwSim{};
+	b->hw_le_ok = false;
 	b->params_dirty = true;
 	if (n == 0) return MJB_OK;
-	std::vector<int> ints((size_t)4 * n);
-	std::vector<double> gains((size_t)8 * n);
+	// (behind the [n] arrays: the same entries by dof for the lane = env kernel, HwSim::le_tab / le_gains; a dof two entries claim has no such table)
+	const int nv = h.nv;
+	std::vector<int> ints((size_t)4 * n + (size_t)4 * nv, 0);
+	std::vector<double> gains((size_t)8 * n + (size_t)8 * nv, 0.0);
+	for (int d = 0; d < nv; d++) ints[(size_t)4 * n + 4 * d] = -1;
+	b->hw_le_ok = true;
 	for (int k = 0; k < n; k++) {
 		const mjb_hwsim_joint &j = joints[k];
 		ints[k] = j.joint; ints[n + k] = j.method; ints[2 * n + k] = j.kind; ints[3 * n + k] = j.antiwindup ? 1 : 0;
 		const double g[8] = { j.p, j.i, j.d, j.i_max, j.i_min, j.effort_limit, j.lower, j.upper };
 		for (int q = 0; q < 8; q++) gains[(size_t)8 * k + q] = g[q];
+		int *t = ints.data() + (size_t)4 * n + 4 * h.jnt_dofadr[j.joint];
+		if (t[0] >= 0) b->hw_le_ok = false;
+		t[0] = k; t[1] = j.method; t[2] = j.kind; t[3] = j.antiwindup ? 1 : 0;
+		for (int q = 0; q < 8; q++) gains[(size_t)8 * n + (size_t)8 * h.jnt_dofadr[j.joint] + q] = g[q];
 	}
 	const size_t per = (size_t)b->nenv * n;
 	b->hw_ints = dev_alloc<int>(ints.size());
@@ -3733,6 +3752,8 @@ int mjb_hwsim_configure(mjb_batch *b, int n, const mjb_hwsim_joint *joints)
 	b->hw.estop = 0;
 	b->hw.joint = b->hw_ints; b->hw.method = b->hw_ints + n; b->hw.kind = b->hw_ints + 2 * n; b->hw.antiwindup = b->hw_ints + 3 * n;
 	b->hw.gains = b->hw_gains;
+	b->hw.le_tab = (mjb_ciptr)(b->hw_ints + 4 * n);
+	b->hw.le_gains = (mjb_cdptr)(b->hw_gains + (size_t)8 * n);
 	b->hw.cmd_pos = b->hw_cmd; b->hw.cmd_vel = b->hw_cmd + per; b->hw.cmd_eff = b->hw_cmd + 2 * per; b->hw.cmd_hold = b->hw_cmd + 3 * per;
 	b->hw.pid = b->hw_pid;
 	return MJB_OK;

@@ -275,6 +275,10 @@ struct HwSim {
 	// the step's own joint state with the model's timestep, the round-2 behaviour)
 	long long period_ns;                                     // control_period as ros::Duration counts it
 	double *cad;                                             // [nenv][2 + 2 n]: last update / last write [ns], joint_position_[n], joint_velocity_[n]
+	// the same configuration by DOF, for the lane = env kernel's HW build (mjb_lane_env_set_hwsim): a lane's forces are registers, so that kernel walks the
+	// dofs at compile time and reads what controls each one as scalars
+	mjb_ciptr le_tab;                                        // [nv][4]: entry k (-1: not controlled) | method | kind | antiwindup
+	mjb_cdptr le_gains;                                      // [nv][8]: the entry's gains
 };
 
 // Everything a launch needs, resident in device memory (uploaded when it changes); kernels get one
@@ -362,9 +366,11 @@ enum { MJB_LE_TOPO_NONE = -1, MJB_LE_TOPO_JIT = -2, MJB_LE_UNAVAILABLE = -1000 }
 int mjb_lane_env_eligible(const mjb_model_desc *h);   // the model's structure fits the kernel (compiled in or not)
 const char *mjb_lane_env_jit_error(void);
 void mjb_lane_env_jit_stats(int *compiled, int *disk_hits);  // hiprtc builds of this process / builds taken from the disk cache instead              // why the last hiprtc build of a topology was not available ("" if none failed)
-// (per_env: the kernel that reads DevState::le_overlay -- solo form, whatever the batch size)
+// which build of the kernel a launch runs: the plain one (any form), or one of the two that exist for the solo form only and run it whatever the batch size --
+// the one that reads DevState::le_overlay (template flag PE), the one with the device hwsim stage, KernelParams::hw (template flag HW)
+enum LeBuild { MJB_LE_PLAIN = 0, MJB_LE_OVERLAY = 1, MJB_LE_HWSIM = 2 };
 int mjb_launch_lane_env(const KernelParams *Pdev, int topo, const mjb_model_desc *h, int nenv_batch, int env_lo, int env_hi, int nsteps, unsigned int step0,
-                        void *stream, int per_env);
+                        void *stream, LeBuild build);
 // the per-env overlay of that kernel: its slot count, and one env's column from the env's gravity and its block of DevState::env_mass (NULL: the model's values)
 int mjb_lane_env_overlay_slots(const mjb_model_desc *h);
 void mjb_lane_env_overlay_row(const mjb_model_desc *h, const double *gravity, const double *env_block, double *out);

@@ -41,12 +41,12 @@ namespace {
 
 using namespace mjb_le;
 
-template <class T, int LP, bool PE = false>  // (PE: per-env overrides from DevState::le_overlay, mjb_set_lane_env mode 2)
+template <class T, int LP, bool PE = false, bool HW = false>  // (PE: per-env overrides from DevState::le_overlay, mjb_set_lane_env mode 2; HW: the device hwsim stage, mjb_lane_env_set_hwsim)
 __global__ void __launch_bounds__(64) mjb_lane_env_kernel(const KernelParams MJB_AS4 *__restrict__ P, const int nsteps, const unsigned int step0,
                                                           const int env_lo, const int env_hi)
 {
 	extern __shared__ __attribute__((aligned(16))) unsigned char smem_le[];
-	lane_env_body<T, LP, 0, PE>(P, nsteps, step0, env_lo, env_hi, smem_le);
+	lane_env_body<T, LP, 0, PE, HW>(P, nsteps, step0, env_lo, env_hi, smem_le);
 }
 
 template <class T, int LP>
@@ -302,12 +302,12 @@ bool source_fingerprint(const std::string &dir, unsigned long long &hsh)
 	return true;
 }
 
-const JitKernel &jit_get(const mjb_model_desc &h, int lp, int duo, bool pe)  // duo: 0 solo, 1 two halves, 2 pipelined, 3 three wavefronts, 4 four (form 3 with the pose sweep on two); pe: the solo form with per-env overrides
+const JitKernel &jit_get(const mjb_model_desc &h, int lp, int duo, LeBuild build)  // duo: 0 solo, 1 two halves, 2 pipelined, 3 three wavefronts, 4 four (form 3 with the pose sweep on two); build: the solo form's overlay / hwsim builds (mjb_dev.h)
 {
 	int dev = 0;
 	(void)hipGetDevice(&dev);
 	const std::string topo = topo_source(h);
-	const std::string key = std::to_string(dev) + "|" + std::to_string(lp) + (pe ? "e|" : duo == 4 ? "q|" : duo == 3 ? "t|" : (duo == 2 ? "p|" : (duo ? "d|" : "|"))) + topo;
+	const std::string key = std::to_string(dev) + "|" + std::to_string(lp) + (build == MJB_LE_HWSIM ? "h|" : build == MJB_LE_OVERLAY ? "e|" : duo == 4 ? "q|" : duo == 3 ? "t|" : (duo == 2 ? "p|" : (duo ? "d|" : "|"))) + topo;
 	std::lock_guard<std::mutex> lock(jit_mutex);
 	auto it = jit_cache.find(key);
 	if (it != jit_cache.end()) return it->second;
@@ -319,9 +319,9 @@ const JitKernel &jit_get(const mjb_model_desc &h, int lp, int duo, bool pe)  // 
 	const std::string dir = source_dir();
 	const std::string slp = std::to_string(lp);
 	const std::string src = "#include \"mjb_lane_env_kernel.h\"\n" + topo +
-	                        (pe ? "extern \"C\" __global__ void __launch_bounds__(64) le_rt(const KernelParams MJB_AS4 *P, int nsteps, unsigned int step0, int lo, int hi)\n{\n"
+	                        (build != MJB_LE_PLAIN ? "extern \"C\" __global__ void __launch_bounds__(64) le_rt(const KernelParams MJB_AS4 *P, int nsteps, unsigned int step0, int lo, int hi)\n{\n"
 	                              "\t__shared__ __attribute__((aligned(16))) unsigned char smem[mjb_le::Lds<LeTopo_rt, " + slp + ">::bytes()];\n"
-	                              "\tmjb_le::lane_env_body<LeTopo_rt, " + slp + ", 0, true>(P, nsteps, step0, lo, hi, smem);\n}\n"
+	                              "\tmjb_le::lane_env_body<LeTopo_rt, " + slp + (build == MJB_LE_HWSIM ? ", 0, false, true" : ", 0, true") + ">(P, nsteps, step0, lo, hi, smem);\n}\n"
 	                         : duo == 4 ? "extern \"C\" __global__ void __launch_bounds__(256) le_rt(const KernelParams MJB_AS4 *P, int nsteps, unsigned int step0, int lo, int hi)\n{\n"
 	                                    "\t__shared__ __attribute__((aligned(16))) unsigned char smem[mjb_le::quartet_bytes<LeTopo_rt>()];\n"
 	                                    "\tmjb_le::lane_env_quartet<LeTopo_rt, 160>(P, nsteps, step0, lo, hi, smem);\n}\n"
@@ -572,13 +572,13 @@ const char *mjb_lane_env_name(int topo)
 // topo >= 0: a compiled-in topology; MJB_LE_TOPO_JIT: the model's own, compiled by hiprtc on first use (h = the model; returns
 // MJB_LE_UNAVAILABLE when that is not possible: the caller launches the generic kernel)
 int mjb_launch_lane_env(const KernelParams *Pdev, int topo, const mjb_model_desc *h, int nenv_batch, int env_lo, int env_hi, int nsteps, unsigned int step0,
-                        void *stream, int per_env)
+                        void *stream, LeBuild build)
 {
 	const int n = env_hi - env_lo;
 	if (n <= 0) return 0;
 	// (measurement knob: envs per wavefront < 64 -- the wavefront starts with its upper lanes off)
 	static const int wl_env = mjb_env_int("MJB_LANE_ENV_WAVE_LANES", 64);
-	const int wl = (!per_env && (wl_env == 16 || wl_env == 32)) ? wl_env : 64;  // (the per-env build always runs full wavefronts)
+	const int wl = (build == MJB_LE_PLAIN && (wl_env == 16 || wl_env == 32)) ? wl_env : 64;  // (the overlay and hwsim builds always run full wavefronts)
 	const dim3 grid((unsigned int)((n + wl - 1) / wl)), block(wl);
 	// LDS budget per wavefront from the CUs the launch leaves idle: one wavefront per CU may take all of its LDS
 	// (per DEVICE: a process may drive several GPUs, one batch each -- ADVICE r05)
@@ -611,7 +611,7 @@ int mjb_launch_lane_env(const KernelParams *Pdev, int topo, const mjb_model_desc
 	const int sweep_ov = sweep_set ? sweep_set : sweep_env;
 	int sweep = duo == 3 ? (sweep_ov ? sweep_ov : (waves <= ncu ? 4 : 3)) : 0;
 	if (duo_mode > 0 && lp < 80) lp = 80, duo = 1;  // (a forced two-wavefront form on a batch that would run four wavefronts per CU: two per CU)
-	if (per_env) {  // per-env overrides: the solo form at the budget the batch's size (or the knob) gives, whatever form is asked for
+	if (build != MJB_LE_PLAIN) {  // per-env overrides / the hwsim stage: the solo form at the budget the batch's size (or the knob) gives, whatever form is asked for
 		lp = lp_batch;
 		duo = 0, sweep = 0;
 	}
@@ -636,7 +636,7 @@ int mjb_launch_lane_env(const KernelParams *Pdev, int topo, const mjb_model_desc
 			if (duo == 2 && need + 5 * ((need - h->nv) / 3) + 12 + (h->nv + 1) / 2 + 1 > 160) duo = 1;
 			if (duo == 1 && need + (h->nv + 1) / 2 + 1 > lp) duo = 0;
 		}
-		const JitKernel &k = jit_get(*h, lp, sweep == 4 ? 4 : duo, per_env != 0);
+		const JitKernel &k = jit_get(*h, lp, sweep == 4 ? 4 : duo, build);
 		if (!k.fn) {
 			set_jit_error(k.error);
 			return MJB_LE_UNAVAILABLE;
@@ -659,11 +659,11 @@ int mjb_launch_lane_env(const KernelParams *Pdev, int topo, const mjb_model_desc
 		hipLaunchKernelGGL(kern, grid, block, bytes, (hipStream_t)stream, (const KernelParams MJB_AS4 *)Pdev, nsteps, step0, env_lo, env_hi); \
 		return (int)hipGetLastError();                                                                                                        \
 	}
-#define MJB_LE_GO_PE(T, LPV)                                                                                                                 \
+#define MJB_LE_GO_SOLO(T, LPV, PEV, HWV)                                                                                                     \
 	{                                                                                                                                         \
-		auto kern = mjb_lane_env_kernel<T, LPV, true>;                                                                                        \
+		auto kern = mjb_lane_env_kernel<T, LPV, PEV, HWV>;                                                                                    \
 		constexpr int bytes = Lds<T, LPV>::bytes();                                                                                           \
-		if (!h || PeSlots<T>::n != mjb_lane_env_overlay_slots(h)) return (int)hipErrorInvalidValue;                                           \
+		if (PEV && (!h || PeSlots<T>::n != mjb_lane_env_overlay_slots(h))) return (int)hipErrorInvalidValue;                                  \
 		const hipError_t attr = lds_attr_once(reinterpret_cast<const void *>(kern), bytes, cur_dev);                                          \
 		if (attr != hipSuccess) return (int)attr;                                                                                             \
 		le_form_last = 0, le_sweep_last = 0;                                                                                                  \
@@ -702,9 +702,12 @@ int mjb_launch_lane_env(const KernelParams *Pdev, int topo, const mjb_model_desc
 	}
 #define MJB_LE_X(id, T)                      \
 	if (topo == id) {                        \
-		if (per_env && lp == 160) MJB_LE_GO_PE(T, 160) \
-		if (per_env && lp == 80) MJB_LE_GO_PE(T, 80)   \
-		if (per_env) MJB_LE_GO_PE(T, 40)         \
+		if (build == MJB_LE_HWSIM && lp == 160) MJB_LE_GO_SOLO(T, 160, false, true)  \
+		if (build == MJB_LE_HWSIM && lp == 80) MJB_LE_GO_SOLO(T, 80, false, true)    \
+		if (build == MJB_LE_HWSIM) MJB_LE_GO_SOLO(T, 40, false, true)                \
+		if (build == MJB_LE_OVERLAY && lp == 160) MJB_LE_GO_SOLO(T, 160, true, false) \
+		if (build == MJB_LE_OVERLAY && lp == 80) MJB_LE_GO_SOLO(T, 80, true, false)   \
+		if (build == MJB_LE_OVERLAY) MJB_LE_GO_SOLO(T, 40, true, false)               \
 		if (duo == 3 && sweep == 4) MJB_LE_GO_TRIO(T, 4) \
 		if (duo == 3) MJB_LE_GO_TRIO(T, 3)   \
 		if (duo >= 2) MJB_LE_GO_DUO2(T)      \
@@ -717,7 +720,7 @@ int mjb_launch_lane_env(const KernelParams *Pdev, int topo, const mjb_model_desc
 	MJB_LE_TOPOS(MJB_LE_X)
 #undef MJB_LE_X
 #undef MJB_LE_GO
-#undef MJB_LE_GO_PE
+#undef MJB_LE_GO_SOLO
 #undef MJB_LE_GO_DUO
 #undef MJB_LE_GO_DUO2
 #undef MJB_LE_GO_TRIO

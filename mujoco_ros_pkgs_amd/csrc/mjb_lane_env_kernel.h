@@ -144,6 +144,62 @@ DEVI void sincos_nb(double x, double *sn, double *cs)
 	*cs = ((q + 1) & 2) ? -c0 : c0;
 }
 
+// ---- the hwsim stage's helpers (HW builds; hwsim_write of mjb_step.hip for one env per lane), branch-free: lanes of one wavefront disagree on every
+// test in them.  Same operations on the same values as the generic kernel's ros_ns / angdist / angdist_with_limits, as selects.
+// fmod(x, y), y > 0, without libm's per-lane loop: the truncated quotient from one IEEE division (off by at most one while |x / y| < 2^53), put right by
+// the sign of a first remainder, then x - q y in one fma -- fmod's result is exactly representable, so that fma returns it exactly.  (|x / y| >= 2^53,
+// i.e. an angle beyond 5e16 rad, is not reduced exactly; mj_checkPos stops a joint at 1e10.)
+DEVI double seld(bool c, double a, double b) { return c ? a : b; }  // (both values evaluated by the caller: a select, whatever they cost)
+DEVI long long sell(bool c, long long a, long long b) { return c ? a : b; }
+DEVI double fmod_nb(double x, double y)
+{
+	const double ax = fabs(x);
+	const double q0 = trunc(ax / y);
+	const double r0 = fma(-q0, y, ax);
+	const double q = seld(r0 < 0, q0 - 1.0, seld(r0 >= y, q0 + 1.0, q0));
+	return copysign(fma(-q, y, ax), x);
+}
+DEVI long long ros_ns_nb(double t)  // ros::Time(double).toNSec(): sec = floor(t), nsec = round((t - sec) 1e9)
+{
+	const double sec = floor(t);
+	return (long long)sec * 1000000000LL + (long long)floor((t - sec) * 1e9 + 0.5);
+}
+DEVI double angdist_nb(double from, double to)  // angles::shortest_angular_distance
+{
+	const double two_pi = 6.283185307179586476925;
+	const double a = fmod_nb(fmod_nb(to - from, two_pi) + two_pi, two_pi);  // normalize_angle_positive
+	return seld(a > 0.5 * two_pi, a - two_pi, a);
+}
+DEVI double two_pi_complement_nb(double a0)
+{
+	const double two_pi = 6.283185307179586476925;
+	const double a = seld((a0 > two_pi) | (a0 < -two_pi), fmod_nb(a0, two_pi), a0);
+	return seld(a < 0, two_pi + a, seld(a > 0, -two_pi + a, two_pi));
+}
+DEVI bool find_min_max_delta_nb(double from, double left, double right, double &dmin, double &dmax)
+{
+	const double pi = 3.14159265358979323846;
+	const double d0 = angdist_nb(from, left), d1 = angdist_nb(from, right), d2 = two_pi_complement_nb(d0), d3 = two_pi_complement_nb(d1);
+	const bool c2 = d2 < d0, c3 = d3 > d1;
+	const double lo = seld(c2, d2, d0), lo2 = seld(c2, d0, d2), hi = seld(c3, d3, d1), hi2 = seld(c3, d1, d3);
+	const bool cross = (lo <= hi2) | (hi >= lo2), z0 = d0 == 0, z1 = d1 == 0;
+	dmin = seld(z0, d0, seld(z1, fmin(d0, d2), seld(cross, hi2, lo)));
+	dmax = seld(z0, fmax(d1, d3), seld(z1, d1, seld(cross, lo2, hi)));
+	return z0 | z1 | !cross | ((left == -pi) & (right == pi));
+}
+DEVI double angdist_with_limits_nb(double from, double to, double left, double right)  // angles::shortest_angular_distance_with_limits
+{
+	double dmin, dmax, tmin, tmax;
+	const bool inside = find_min_max_delta_nb(from, left, right, dmin, dmax);
+	const double delta = angdist_nb(from, to), comp = two_pi_complement_nb(delta);
+	find_min_max_delta_nb(to, left, right, tmin, tmax);
+	const double nearer = seld(fabs(delta) < fabs(comp), delta, comp), mx = fmax(delta, comp), mn = fmin(delta, comp);
+	const double byto = seld(fabs(tmin) < fabs(tmax), mx, seld(fabs(tmin) > fabs(tmax), mn, nearer));
+	const double in = seld((delta >= dmin) & (delta <= dmax), delta, seld((comp >= dmin) & (comp <= dmax), comp, byto));
+	const double out = seld(fabs(dmin) < fabs(dmax), mn, seld(fabs(dmin) > fabs(dmax), mx, nearer));
+	return seld(inside, in, out);
+}
+
 // LDS of a block (= one wavefront): pair slot q of lane l = the two doubles at (q * 64 + l) * 16 bytes -- one ds_read_b128 /
 // ds_write_b128 per pair, conflict-free.  Slots [0, NV): (qpos_i, qvel_i); then three slots per body whose force the backward
 // sweep reads (cfrc_body); then, while the budget LP lasts, five per body for its cinert (leaf-most bodies first): the wavefront's
@@ -218,7 +274,15 @@ DEVI void le_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "m
 template <int NV> struct DuoSlots { static constexpr int n = (NV + 1) / 2 + 1; };  // qfrc_smooth pairs + the mail slot
 // PE: the batch carries per-env overrides (mjb_set_lane_env mode 2): gravity, the joint constants, masses / inertias and the actuator gains come
 // per lane from DevState::le_overlay instead of the tape (solo form only).
-template <class T, int LP, int ROLE = 0, bool PE = false>
+// HW: the batch has a device hwsim stage (KernelParams::hw, mjb_lane_env_set_hwsim): DefaultRobotHWSim::writeSim runs per lane where the forces are
+// assembled -- behind the root -> leaf sweep, which is where the generic kernels run hwsim_write (between forward_first and forward_rest), inside the
+// attempt loop.  Which dof is controlled, and how, is wave-uniform run-time data (HwSim::le_tab / le_gains, by dof): scalar loads and wave-uniform
+// branches around per-lane selects.  Commands, PID state and cadence stamps are fetched per lane ([env][n] rows: strided) in the sweep's last region,
+// beside qfrc_applied, and PID state, stamps and the controlled dofs' qfrc_applied go back to HBM at every step -- qfrc_applied is STATE under the
+// stage (a step without a write keeps the last one's) and the generic kernels continue the same batch.  A POSITION / VELOCITY joint's new qpos / qvel
+// wait in registers for mj_Euler: everything between the stage and Euler (passive forces, actuator length / velocity, joint sensors, energy) was
+// computed by forward_first from the old state in the generic kernels.  Solo form only; no build with PE.
+template <class T, int LP, int ROLE = 0, bool PE = false, bool HW = false>
 DEVI void lane_env_body(const KernelParams MJB_AS4 *__restrict__ P, const int nsteps, const unsigned int step0, const int env_lo, const int env_hi,
                         unsigned char *const smem_le)
 {
@@ -244,6 +308,7 @@ DEVI void lane_env_body(const KernelParams MJB_AS4 *__restrict__ P, const int ns
 	constexpr bool SENSF = ROLE == 0 || ROLE == 2 || ROLE == 3 || ROLE == 5 || ROLE == 9;  // frame sensors: who holds the poses (and, of two, who has the time)
 	using Q = Tq<T>;
 	static_assert(!PE || ROLE == 0, "lane = env kernel: per-env overrides run the solo form");
+	static_assert(!HW || (ROLE == 0 && !PE), "lane = env kernel: the hwsim stage runs the solo form, without per-env overrides");
 	using OV = PeSlots<T>;
 	constexpr int LPE = PIPE ? (1 << 20) : (DUO ? LP - DuoSlots<NV>::n : LP);
 	using LD = Lds<T, LPE>;
@@ -261,8 +326,8 @@ DEVI void lane_env_body(const KernelParams MJB_AS4 *__restrict__ P, const int ns
 	constexpr int XS = PIPE ? RING + 6 * RINGN : LD::nslots(), MAIL = XS + (NV + 1) / 2, SC0 = MAIL + 1;  // (trio) SC0 + b: body b's half-angle (sin, cos), from C to P  // (DUO) pair slots of qfrc_smooth, and of P's verdicts for V
 	const int lane_le = DUO ? (int)(threadIdx.x & 63u) : (int)threadIdx.x;
 	Pair *const lp = reinterpret_cast<Pair *>(smem_le) + lane_le;  // pair slot q of this lane: lp[64 * q]
-	// (a tail lane without an env keeps running on the last env's data and stores nothing: no divergent exit, the wave-uniform
-	//  branches below stay uniform)
+	// (a tail lane without an env keeps running on the last env's data: no divergent exit, the wave-uniform branches below stay uniform. It stores
+	//  nothing of its own -- what it does store, at the launch's end and in the HW stage, is the last env's own value to the last env's address a second time)
 	const int env_raw = env_lo + (int)(blockIdx.x * (DUO ? 64u : blockDim.x)) + lane_le;  // (solo: blockDim.x = 64; fewer: a measurement knob, MJB_LANE_ENV_WAVE_LANES)
 	const bool live = env_raw < env_hi;
 	const int env = live ? env_raw : env_hi - 1;
@@ -375,6 +440,11 @@ DEVI void lane_env_body(const KernelParams MJB_AS4 *__restrict__ P, const int ns
 		}
 
 		double qacc[NV], qaccd[NV];  // M^-1 f, and the acceleration Euler advances with: (M + h B)^-1 f under implicit joint damping
+		// (HW) mj_checkAcc reset this lane: the retry runs the stage a second time for it and for no other lane | the stage wrote at this step |
+		// what it wrote to a POSITION / VELOCITY joint's qpos / qvel (applied in mj_Euler)
+		[[maybe_unused]] bool hw_bad = false, hw_wr = false;
+		[[maybe_unused]] double hov[NV > 0 ? NV : 1];
+		if constexpr (HW) sfor<NV>([&](auto I) { hov[I] = 0; });
 		double en_pe = 0, en_ke = 0;
 #pragma nounroll
 		for (int attempt = 0; attempt < 2; attempt++) {
@@ -625,6 +695,38 @@ DEVI void lane_env_body(const KernelParams MJB_AS4 *__restrict__ P, const int ns
 					lp[64 * (q0 + 2)] = Pair{ cf[4] + t1[4], cf[5] + t1[5] };
 				}
 			};
+			// (HW) the env's commands, PID state and cadence record: fetched in the sweep's last region, read by the force block behind it
+			[[maybe_unused]] double hcmd[NV > 0 ? NV : 1], hpi[NV > 0 ? NV : 1], hpl[NV > 0 ? NV : 1], hjp[NV > 0 ? NV : 1], hjv[NV > 0 ? NV : 1], hlu = 0, hlw = 0;
+			[[maybe_unused]] auto hw_fetch = [&]() __attribute__((always_inline)) {
+				// (every pointer taken from the parameter block where it is used: a local copy captured by the dof loop's closure keeps that closure in scratch)
+				if (Pq->hw.period_ns > 0) {
+					const double *const cad = Pq->hw.cad + ev * (size_t)(2 + 2 * Pq->hw.n);
+					hlu = cad[0];
+					hlw = cad[1];
+				}
+				sfor<NV>([&](auto I) __attribute__((always_inline)) {
+					hcmd[I] = hpi[I] = hpl[I] = hjp[I] = hjv[I] = 0;
+					const HwSim MJB_AS4 &hw = Pq->hw;
+					const int k = hw.le_tab[4 * I];
+					if (k >= 0) {
+						const int method = hw.le_tab[4 * I + 1], hn = hw.n;
+						const size_t at = ev * (size_t)hn + (size_t)k;
+						if (method == MJB_HW_EFFORT) hcmd[I] = hw.cmd_eff[at];
+						else if (method == MJB_HW_VELOCITY || method == MJB_HW_VELOCITY_PID) hcmd[I] = hw.cmd_vel[at];
+						else if (hw.estop != 0) hcmd[I] = hw.cmd_hold[at];
+						else hcmd[I] = hw.cmd_pos[at];
+						if (method == MJB_HW_POSITION_PID || method == MJB_HW_VELOCITY_PID) {
+							hpi[I] = hw.pid[2 * at];
+							hpl[I] = hw.pid[2 * at + 1];
+						}
+						if (hw.period_ns > 0) {
+							const double *const cad = hw.cad + ev * (size_t)(2 + 2 * hn);
+							hjp[I] = cad[2 + k];
+							hjv[I] = cad[2 + hn + k];
+						}
+					}
+				});
+			};
 			sfor<NB>([&](auto B) {
 				constexpr int b = B;
 				if constexpr (b > 0 && RINGC) {
@@ -860,6 +962,7 @@ DEVI void lane_env_body(const KernelParams MJB_AS4 *__restrict__ P, const int ns
 				}
 				if constexpr (b + 1 < NB) touch_rec<14>(hA[b + 1]);
 				if constexpr (DV && b == NB - 1) sfor<NV>([&](auto I) { qfa[I] = s.qfrc_applied[ev * NV + I]; });
+				if constexpr (HW && b == NB - 1) hw_fetch();
 				__builtin_amdgcn_sched_barrier(0);
 				}
 			});
@@ -1090,6 +1193,96 @@ DEVI void lane_env_body(const KernelParams MJB_AS4 *__restrict__ P, const int ns
 				} else {
 					sfor<NU>([&](auto I) { const double c = pinv(s.ctrl[ev * NU + I]); ctrl[I] = wasreset ? 0.0 : c; });  // (load first: a select around a load becomes a per-lane branch)
 				}
+				// ---- (HW) MujocoRosControlPlugin::controlCallback's cadence around writeSim (hwsim_write, mjb_step.hip): the decisions differ between
+				// the lanes, so they are selects; a lane the retry does not concern (h_run false) stores back what it loaded
+				[[maybe_unused]] bool h_upd = false, h_wr = false;
+				[[maybe_unused]] double h_dt = dt;
+				[[maybe_unused]] const bool h_run = attempt == 0 || hw_bad;
+				if constexpr (HW) {
+					const HwSim MJB_AS4 &hw = Pq->hw;
+					const long long per_ns = hw.period_ns;
+					h_wr = true;
+					if (per_ns > 0) {
+						const double lu0 = pinv(hlu), lw0 = pinv(hlw);
+						const long long t = ros_ns_nb(time);
+						long long lu = (long long)lu0, lw = (long long)lw0;
+						const bool back = t < lu;  // the time went backwards (reset): both stamps re-armed
+						lu = sell(back, t, lu);
+						lw = sell(back, t, lw);
+						const long long sim_period = t - lu;
+						h_upd = (sim_period >= per_ns) | ((lu == 0) & (sim_period != 0));  // (nothing happens at t = 0)
+						lu = sell(h_upd, t, lu);
+						h_wr = (lu != 0) & (t > lw);
+						h_dt = 1e-9 * (double)(t - lw);
+						double *const cad = hw.cad + ev * (size_t)(2 + 2 * hw.n);
+						const double lu1 = (double)lu, lw1 = (double)sell(h_wr, t, lw);
+						cad[0] = seld(h_run, lu1, lu0);
+						cad[1] = seld(h_run, lw1, lw0);
+					}
+					h_upd = h_upd & h_run;
+					hw_wr = (h_run & h_wr) | (!h_run & hw_wr);
+					h_wr = h_wr & h_run;
+				}
+				// (HW) dof j's qfrc_applied after the stage; sj: the dof's (qpos, qvel)
+				[[maybe_unused]] auto hw_dof = [&](auto I, const Pair sj) __attribute__((always_inline)) -> double {
+					constexpr int j = I;
+					const HwSim MJB_AS4 &hw = Pq->hw;
+					const double fa0 = pinv(qfa[j]);
+					const int k = hw.le_tab[4 * j];
+					if (k < 0) {  // not controlled: the user's value, zero after an in-launch reset -- and so it stands in HBM after the launch, as the generic kernels' frame copy does
+						const double v = seld(wasreset, 0.0, fa0);
+						if (last && __builtin_amdgcn_ballot_w64(wasreset)) s.qfrc_applied[ev * NV + j] = v;
+						return v;
+					}
+					const int method = hw.le_tab[4 * j + 1], kind = hw.le_tab[4 * j + 2], aw = hw.le_tab[4 * j + 3], hn = hw.n;
+					const double MJB_AS4 *const gn = hw.le_gains + 8 * j;
+					const bool estop = hw.estop != 0;
+					const size_t at = ev * (size_t)hn + (size_t)k;
+					double pos = sj.a, vel = sj.b;
+					if (hw.period_ns > 0) {  // readSim at an update: the joint state the PIDs see until the next one
+						const double jp0 = pinv(hjp[j]), jv0 = pinv(hjv[j]);
+						double jpn = sj.a;
+						if (kind != MJB_HW_PRISMATIC) jpn = jp0 + angdist_nb(jp0, sj.a);
+						pos = seld(h_upd, jpn, jp0);
+						vel = seld(h_upd, sj.b, jv0);
+						double *const cad = hw.cad + ev * (size_t)(2 + 2 * hn);
+						cad[2 + k] = pos;
+						cad[2 + hn + k] = vel;
+					}
+					const double cmd = pinv(hcmd[j]);
+					double out = 0, error = 0;
+					if (method == MJB_HW_EFFORT) out = estop ? 0.0 : cmd;
+					else if (method == MJB_HW_POSITION) hov[j] = cmd;
+					else if (method == MJB_HW_VELOCITY) hov[j] = estop ? 0.0 : cmd;
+					else if (method == MJB_HW_POSITION_PID) {
+						if (kind == MJB_HW_REVOLUTE) {
+							const double lower = gn[6], upper = gn[7];
+							if (upper > lower) error = angdist_with_limits_nb(pos, fmin(fmax(cmd, lower), upper), lower, upper);
+							else error = cmd - pos;
+						} else if (kind == MJB_HW_CONTINUOUS) error = angdist_nb(pos, cmd);
+						else error = cmd - pos;
+					} else error = estop ? -vel : cmd - vel;
+					if (method == MJB_HW_POSITION_PID || method == MJB_HW_VELOCITY_PID) {
+						const double ierr0 = pinv(hpi[j]), last0 = pinv(hpl[j]);
+						const double gi = gn[1];
+						const double derr = (error - last0) / h_dt;
+						double ierr = ierr0 + h_dt * error;
+						if (aw && gi != 0) ierr = fmin(fmax(ierr, gn[4] / fabs(gi)), gn[3] / fabs(gi));
+						double iterm = gi * ierr;
+						if (!aw) iterm = fmin(fmax(iterm, gn[4]), gn[3]);
+						out = gn[0] * error + iterm + gn[2] * derr;
+						const double el = gn[5];
+						if (el > 0) out = fmin(fmax(out, -el), el);
+						double *const pp = hw.pid + 2 * at;
+						pp[0] = seld(h_wr, ierr, ierr0);
+						pp[1] = seld(h_wr, error, last0);
+					}
+					// (the frame's qfrc_applied is zero after mj_resetData in this step; the stage then rewrites the dof if it writes. Only where the stage
+					//  runs on this trip: a lane that mj_checkPos / mj_checkVel reset and another lane's retry does not concern keeps what trip 0 stored)
+					const double fa = seld(h_wr, out, seld(h_run & (rs | hw_bad), 0.0, fa0));
+					s.qfrc_applied[ev * NV + j] = fa;
+					return fa;
+				};
 				Pair sq[NV > 0 ? NV : 1];
 				sfor<NV>([&](auto I) {
 					constexpr int j = I;
@@ -1106,6 +1299,8 @@ DEVI void lane_env_body(const KernelParams MJB_AS4 *__restrict__ P, const int ns
 						pas = -tj.stiffness * (sq[j].a - tj.spring);
 						pas -= tj.damping * sq[j].b;
 					}
+					if constexpr (HW) f[j] = pas + hw_dof(I, sq[j]);
+					else
 					f[j] = pas + (wasreset ? 0.0 : qfa[j]);
 				});
 				const bool act_on = !(m.disableflags & MJB_DSBL_ACTUATION);
@@ -1367,6 +1562,7 @@ DEVI void lane_env_body(const KernelParams MJB_AS4 *__restrict__ P, const int ns
 			sfor<NU>([&](auto I) { cn[I] = bada ? 0.0 : cn[I]; });
 			time = bada ? 0.0 : time;
 			wasreset = wasreset || bada;
+			if constexpr (HW) hw_bad = bada;
 			if constexpr (DUO && DP) {
 				lp[64 * MAIL] = Pair{ (double)(8 | (bada ? 4 : 0)), 0.0 };
 				le_barrier();  // (B, retry) V runs its half again on the reset state
@@ -1394,6 +1590,16 @@ DEVI void lane_env_body(const KernelParams MJB_AS4 *__restrict__ P, const int ns
 		badp_next = badv_next = false;
 		sfor<NV>([&](auto I) {
 			Pair s2 = lp[64 * I];
+			if constexpr (HW) {  // what the stage wrote to the state: Euler integrates from it
+				const HwSim MJB_AS4 &hw = Pq->hw;
+				if (hw.le_tab[4 * I] >= 0) {
+					const int method = hw.le_tab[4 * I + 1];
+					if (method == MJB_HW_POSITION) {
+						s2.a = seld(hw_wr, hov[I], s2.a);
+						s2.b = seld(hw_wr, 0.0, s2.b);
+					} else if (method == MJB_HW_VELOCITY) s2.b = seld(hw_wr, hov[I], s2.b);
+				}
+			}
 			s2.b += dt * qaccd[I];
 			s2.a += dt * s2.b;
 			lp[64 * I] = s2;

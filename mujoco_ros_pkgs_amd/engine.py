@@ -362,6 +362,11 @@ class Batch:
         per env; such a batch runs the generic kernels in every other mode: the lane = env form of the unconstrained fused step (mjb_set_lane_env)."""
         _check(self.lib.mjb_set_lane_env(self.ptr, int(mode)), "mjb_set_lane_env")
 
+    def set_lane_env_hwsim(self, on=True):
+        """Opt-in: a batch with the device hwsim stage (hwsim_configure) may run the lane = env kernel, in its one-wavefront build that carries the
+        stage; off (the default), such a batch runs the generic kernels (mjb_lane_env_set_hwsim)."""
+        _check(self.lib.mjb_lane_env_set_hwsim(self.ptr, 1 if on else 0), "mjb_lane_env_set_hwsim")
+
     def lane_env_info(self):
         """(compiled-in topology index or -1, the last fused launch ran the lane = env kernel)."""
         used = C.c_int(0)

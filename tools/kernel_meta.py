@@ -34,7 +34,7 @@ if os.path.exists(f):
         if mm.group(1) == "trio_":  # (form 3: the template's integer is the count of sweep wavefronts, not an LDS budget)
             mm = (None, mm.group(2), "form 3, " + ("four" if mm.group(3) == "4" else "three") + " wavefronts")
         else:
-            mm = (None, mm.group(2), (mm.group(3) or "-") + form + (", per-env overrides" if "Lb1E" in name.group(1) else ""))
+            mm = (None, mm.group(2), (mm.group(3) or "-") + form + (", per-env overrides" if "Lb1ELb0E" in name.group(1) else "") + (", hwsim stage" if "Lb0ELb1E" in name.group(1) else ""))
         mm = type("M", (), {"group": lambda self, i, _m=mm: _m[i]})()
         get = lambda k: int(re.search(r"\." + k + r":\s+(\d+)", blk).group(1))  # noqa: E731
         agpr = int(re.match(r":\s+(\d+)", blk).group(1))
