@@ -266,13 +266,14 @@ int mjb_fused_frame(const mjb_batch *b);
  * should pin one form); measured on MI355X it is ahead of the 16-lanes-per-env kernel from 4096 envs (276 vs 227 M env-steps/s) and 12x
  * ahead at 65 536.  mode: -1 = automatic (fused launches over >= MJB_LANE_ENV_MIN_ENVS envs, default 4096 -- the whole batch, or the non-callback envs of a
  * split step, mjb_step_rest -- of a model whose
- * topology is compiled in, with no per-env model overrides / hwsim stage / xfrc_applied), 0 = never, 1 = whenever eligible,
+ * topology is compiled in, with no per-env model overrides / hwsim stage / xfrc_applied -- the last two unless mjb_lane_env_set_hwsim /
+ * mjb_lane_env_set_xfrc, below, opt in), 0 = never, 1 = whenever eligible,
  * 2 = whenever eligible, ALSO with per-env gravity and parameter blocks (mjb_set_env_gravity, mjb_set_env_body_mass / _mass_params, mjb_set_env_dof_params /
  * _joint_stiffness / _actuator_params / _joint_params): such a batch stands the kernel down in every other mode; in mode 2 its launches run the kernel's
  * one-wavefront form (mjb_lane_env_last_form() == 0) in a build that reads each env's gravity, joint stiffness / damping / armature, masses, inertias and
  * actuator gain / bias parameters from a per-env table laid out [value][env] (built at the first such launch, its columns re-derived after every later
- * mjb_set_env_* call on these values; sized mjb_model_lane_env_overlay() doubles per env).  Every other condition stays (hwsim stage, xfrc_applied, frame
- * dumps, statistics); a mode-2 batch WITHOUT overrides runs exactly what mode 1 runs.
+ * mjb_set_env_* call on these values; sized mjb_model_lane_env_overlay() doubles per env).  Every other condition stays (hwsim stage, xfrc_applied -- which mjb_lane_env_set_xfrc
+ * lifts in this mode too --, frame dumps, statistics); a mode-2 batch WITHOUT overrides runs exactly what mode 1 runs.
  * The environment variable MJB_LANE_ENV (same values) sets the default of new batches (read by mjb_make_batch).  While mjb_set_stats is
  * counting, fused launches run the generic kernels whatever the mode (the counters live in those).  No reference counterpart. */
 int mjb_set_lane_env(mjb_batch *b, int mode);
@@ -282,13 +283,28 @@ int mjb_set_lane_env(mjb_batch *b, int mode);
  * the position and velocity stages, before actuation; a second time in the retry after a mj_checkAcc reset), with the controller cadence of
  * mjb_hwsim_set_period, the e-stop rules, and the commands / PID state / cadence stamps read and written where mjb_hwsim_* keeps them -- the generic
  * kernels continue the same batch, results equal to theirs to rounding.  Every other condition of mjb_set_lane_env stays (mode 0 never, the 4096-env
- * threshold of mode -1, a compiled-in or hiprtc-built topology, whole fused launches, no xfrc_applied / frame dump / statistics, Euler).  A batch
+ * threshold of mode -1, a compiled-in or hiprtc-built topology, whole fused launches, no xfrc_applied -- mjb_lane_env_set_xfrc does not lift this one for a batch
+ * with a stage -- / frame dump / statistics, Euler).  A batch
  * that has BOTH a hwsim stage and per-env gravity or parameter blocks keeps the generic kernels in every mode (there is no build with both), and so
  * does a configuration in which two entries control one joint.  With the switch off, or without a hwsim stage, every launch runs what it ran without
  * this call.  Measured on config 2's model with a seven-controller set (tools/lane_env_hwsim_rate.py, profiles/lane_env_hwsim.txt): 9.65 x the generic
  * kernel's rate at 65 536 envs (1757 against 182 M env-steps/s), level with it at 4096 envs (189 against 182), and half the rate of the same kernel
  * without a stage.  No reference counterpart. */
 int mjb_lane_env_set_hwsim(mjb_batch *b, int on);
+/* Opt-in (default off): with on = 1 a written xfrc_applied no longer stands the lane = env kernel down.  The batch's eligible launches then run the
+ * kernel's one-wavefront form (mjb_lane_env_last_form() == 0, at the LDS budget the batch size gives, whatever form is asked for) in a build that
+ * applies the Cartesian wrenches as mj_xfrcAccumulate does: each moving body's (force, torque) at its xipos, folded into the body's own force in the
+ * root -> leaf sweep.  The kernel reads the wrenches from a transposed copy of xfrc_applied, refilled on the launch's stream ahead of the first such
+ * launch after any write of the field (mjb_set, mjb_set_many, mjb_set_packed, mjb_reset); they are constant over the K steps of a launch.  An env that
+ * mj_check* resets inside a launch runs on without its wrench from there (the retry of that step included) and finds its rows of xfrc_applied zeroed
+ * after the launch, as mj_resetData leaves them.  Composes with mode 2 of mjb_set_lane_env (per-env gravity and parameter blocks); a batch that has
+ * BOTH a hwsim stage and a written xfrc_applied keeps the generic kernels (there is no build with both).  Every other condition of mjb_set_lane_env
+ * stays (mode 0 never, the 4096-env threshold of mode -1, a compiled-in or hiprtc-built topology, whole fused launches, no frame dump / statistics,
+ * Euler).  With the switch off, or while xfrc_applied has never been written, every launch runs what it ran without this call.  Measured on config 2's
+ * model with a wrench on every body of every env (tools/lane_env_xfrc_rate.py, profiles/lane_env_xfrc.txt): 3.12 x the generic kernel's rate at 4096 envs
+ * (276.5 against 88.8 M env-steps/s), 29.2 x at 65 536 (3482 against 119), and 0.92 / 0.93 of the same kernel's rate without a wrench.  No reference
+ * counterpart. */
+int mjb_lane_env_set_xfrc(mjb_batch *b, int on);
 /* The lane = env kernel evaluates the sensor stages (A15) at the LAST step of a fused launch: sensordata is an output of the launch and nothing inside
  * it reads the values (the generic kernels evaluate them at every step into the LDS frame).  on = 1 makes it evaluate -- and store -- them at every
  * step: same results after the launch, and the per-step cost of A15 on that kernel becomes measurable (bench.py: other_configs.2_sensors_every_step). */

@@ -212,6 +212,7 @@ def load_library(path=None):
         "mjb_fused_frame": (ci, [vp]),
         "mjb_set_lane_env": (ci, [vp, ci]),
         "mjb_lane_env_set_hwsim": (ci, [vp, ci]),
+        "mjb_lane_env_set_xfrc": (ci, [vp, ci]),
         "mjb_set_sensors_every_step": (ci, [vp, ci]),
         "mjb_lane_env_info": (ci, [vp, C.POINTER(ci)]),
         "mjb_lane_env_error": (C.c_char_p, []),

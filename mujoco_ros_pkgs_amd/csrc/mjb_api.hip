@@ -184,6 +184,9 @@ struct mjb_batch {
 	size_t zfail = (size_t)-1;     // smallest total allocation (doubles) that failed: not retried
 	bool lane_env_hwsim = false;   // mjb_lane_env_set_hwsim: a batch with the device hwsim stage may run the lane = env kernel's HW build
 	bool hw_le_ok = false;         // the hwsim configuration has a per-dof table (HwSim::le_tab): no dof controlled by two entries
+	bool lane_env_xfrc = false;    // mjb_lane_env_set_xfrc: a batch whose xfrc_applied has been written may run the lane = env kernel's XF builds
+	double *le_xfrc = nullptr;     // their wrench table, [6 * mjb_lane_env_xfrc_slots][nenv] (DevState::le_xfrc), built at the first such launch
+	bool le_xfrc_stale = true;     // xfrc_applied has been written (or reset) since the table was last filled
 	int lane_env_mode = -1;        // mjb_set_lane_env: -1 automatic, 0 never, 1 whenever eligible, 2 whenever eligible, also with per-env gravity / parameter blocks
 	double *le_overlay = nullptr;  // mode 2: the per-env overlay of the lane = env kernel, [mjb_lane_env_overlay_slots][nenv] (DevState::le_overlay), built at the first such launch
 	int le_ov_lo = 0, le_ov_hi = 0;  // envs [lo, hi) whose overlay columns a setter has outdated since (empty: lo >= hi)
@@ -1472,6 +1475,7 @@ void mjb_free_batch(mjb_batch *b)
 	if (b->env_equality) hipFree(b->env_equality);
 	if (b->env_mass) hipFree(b->env_mass);
 	if (b->le_overlay) hipFree(b->le_overlay);
+	if (b->le_xfrc) hipFree(b->le_xfrc);
 	if (b->hw_ints) hipFree(b->hw_ints);
 	if (b->hw_gains) hipFree(b->hw_gains);
 	if (b->hw_cmd) hipFree(b->hw_cmd);
@@ -1680,6 +1684,7 @@ mjb_batch *mjb_make_batch(const mjb_model *M, int nenv, int device)
 	s.handoff_stride = 0;
 	s.reset_step = nullptr;
 	s.le_overlay = nullptr;
+	s.le_xfrc = nullptr;
 	s.sens_every_step = 0;
 	for (int k = 0; k < 64; k++) s.colfunc[k] = MJB_COLFUNC_DEFAULT;
 	s.sched = nullptr;
@@ -2156,12 +2161,17 @@ static int speculate_ctrl_noise(mjb_batch *b, const LaunchReq &q, int zhalf_now)
 }
 
 // The lane = env kernel (mjb_lane_env.hip) for fused launches of a model whose topology is compiled in: one env per lane, no frame.
-// Per-env model overrides (but mode 2), the device hwsim stage (but mjb_lane_env_set_hwsim), xfrc_applied and frame dumps keep the generic kernels.
+// Per-env model overrides (but mode 2), the device hwsim stage (but mjb_lane_env_set_hwsim), xfrc_applied (but mjb_lane_env_set_xfrc) and frame dumps
+// keep the generic kernels.
 // (mjb_lane_env_set_hwsim: the hwsim stage rides along in the kernel's HW build -- unless the batch has per-env gravity or parameter blocks too)
 static bool le_hwsim(const mjb_batch *b) { return b->hw.n > 0 && b->lane_env_hwsim && b->hw_le_ok && !b->env_mass && !b->env_gravity; }
+// (mjb_lane_env_set_xfrc: a written xfrc_applied rides along in the kernel's XF builds -- unless the batch has a hwsim stage, there is no build with both.
+//  LaunchReq::compact stays what the generic path's frame choice reads; for this kernel, which has no frame, the xfrc term of it is lifted)
+static bool le_xfrc(const mjb_batch *b) { return b->st.use_xfrc && b->lane_env_xfrc && b->hw.n == 0; }
 static bool want_lane_env(const mjb_batch *b, const LaunchReq &q, int variant)
 {
-	if (!(q.mode == MJB_MODE_STEP && q.compact && variant == MJB_KV_NONE && b->model->le_topo != MJB_LE_TOPO_NONE && !b->le_unavailable && b->lane_env_mode != 0 &&
+	const bool frameless = q.compact || (le_xfrc(b) && !b->st.keep_frame);
+	if (!(q.mode == MJB_MODE_STEP && frameless && variant == MJB_KV_NONE && b->model->le_topo != MJB_LE_TOPO_NONE && !b->le_unavailable && b->lane_env_mode != 0 &&
 	      (no_env_overrides(b) || (b->lane_env_mode == 2 && b->hw.n == 0) || le_hwsim(b)) && !b->st.stats))  // (mode 2: per-env gravity and parameter blocks ride along, le_overlay_sync)
 		return false;
 	static const int min_envs = mjb_env_int("MJB_LANE_ENV_MIN_ENVS", 4096);
@@ -2219,6 +2229,33 @@ static int le_overlay_sync(mjb_batch *b)
 	return MJB_OK;
 }
 
+// mjb_lane_env_set_xfrc: the wrench table of the XF builds (DevState::le_xfrc; XfSlots, mjb_lane_env_kernel.h).  Allocated at the first such launch and
+// filled from xfrc_applied by a transpose kernel on the launch's stream, again whenever the field has been written or reset since the last fill (the
+// kernel itself keeps the two in step when it resets an env).
+static int le_xfrc_sync(mjb_batch *b, hipStream_t stream)
+{
+	const mjb_model_desc &h = b->model->h;
+	if (!b->le_xfrc) {
+		// (no dev_alloc: its memset runs on the null stream, which the batch's non-blocking stream does not wait for -- it could land behind the fill below,
+		//  which writes every entry anyway)
+		const size_t bytes = std::max<size_t>(1, (size_t)6 * mjb_lane_env_xfrc_slots(&h) * b->nenv) * sizeof(double);
+		if (hipMalloc((void **)&b->le_xfrc, bytes) != hipSuccess) {
+			(void)hipGetLastError();
+			b->le_xfrc = nullptr;
+			return fail(MJB_ENOMEM, "lane = env kernel: allocation of the xfrc_applied table failed");
+		}
+		b->st.le_xfrc = b->le_xfrc;
+		b->params_dirty = true;
+		b->le_xfrc_stale = true;
+	}
+	if (!b->le_xfrc_stale) return MJB_OK;
+	if (b->rest_pending && b->rest_stream && b->rest_stream != stream) HIP_TRY(hipStreamSynchronize(b->rest_stream));  // (an earlier launch may still read the table)
+	const int rc = mjb_lane_env_xfrc_fill(&h, b->st.xfrc_applied, b->le_xfrc, b->nenv, stream);
+	if (rc != 0) return fail(MJB_ENODEVICE, "lane = env kernel: xfrc_applied table fill failed: %s", hipGetErrorString((hipError_t)rc));
+	b->le_xfrc_stale = false;
+	return MJB_OK;
+}
+
 static int launch(mjb_batch *b, int mode, int nsteps, int env_lo = 0, int env_hi = -1, hipStream_t on = nullptr)
 {
 	if (env_hi < 0) env_hi = b->nenv;
@@ -2239,6 +2276,8 @@ static int launch(mjb_batch *b, int mode, int nsteps, int env_lo = 0, int env_hi
 	}
 	const bool le_per_env = b->lane_env_mode == 2 && (b->env_mass || b->env_gravity) && !use_split && want_lane_env(b, q, variant);
 	if (le_per_env && (rc = le_overlay_sync(b))) return rc;
+	const bool le_xf = le_xfrc(b) && !use_split && want_lane_env(b, q, variant);
+	if (le_xf && (rc = le_xfrc_sync(b, q.stream))) return rc;
 	if ((rc = sync_params(b))) return rc;
 	if (use_split) {
 		if (b->zvalid) {  // (the pre-generated ctrl-noise buffer names an older launch: this path draws its normals in the smooth kernel)
@@ -2258,7 +2297,8 @@ static int launch(mjb_batch *b, int mode, int nsteps, int env_lo = 0, int env_hi
 	bool use_le = want_lane_env(b, q, variant);
 	b->lane_env_used = use_le;
 	if (use_le) {
-		rc = mjb_launch_lane_env(b->params_dev, b->model->le_topo, &b->model->h, b->nenv, env_lo, env_hi, nsteps, b->step_counter, q.stream, le_per_env ? MJB_LE_OVERLAY : (b->hw.n > 0 ? MJB_LE_HWSIM : MJB_LE_PLAIN));
+		rc = mjb_launch_lane_env(b->params_dev, b->model->le_topo, &b->model->h, b->nenv, env_lo, env_hi, nsteps, b->step_counter, q.stream,
+		                         le_xf ? (le_per_env ? MJB_LE_OVERLAY_XFRC : MJB_LE_XFRC) : le_per_env ? MJB_LE_OVERLAY : (b->hw.n > 0 ? MJB_LE_HWSIM : MJB_LE_PLAIN));
 		if (rc == MJB_LE_UNAVAILABLE) {  // (no hiprtc / no kernel header / compile error: remembered, the generic kernel runs -- mjb_lane_env_info says why)
 			b->le_unavailable = true;
 			b->lane_env_used = use_le = false;
@@ -2501,6 +2541,7 @@ int mjb_reset(mjb_batch *b, const uint8_t *mask)
 	if (rc != 0) return fail(MJB_ENODEVICE, "reset launch failed: %s", hipGetErrorString((hipError_t)rc));
 	if (mask) HIP_TRY(hipStreamSynchronize(b->stream));
 	b->frame_valid = false;
+	b->le_xfrc_stale = true;  // (mj_resetData zeroes xfrc_applied)
 	if (!mask) b->rowstat_ever = false;  // (a new workload: the next long launch probes its rows first)
 	return MJB_OK;
 }
@@ -2590,6 +2631,7 @@ int mjb_set(mjb_batch *b, int field, int env_lo, int env_hi, const double *host)
 		double *p = state_ptr(b, field);
 		HIP_TRY(hipMemcpy(p + (size_t)env_lo * n, host, (size_t)(env_hi - env_lo) * n * sizeof(double),
 		                  hipMemcpyHostToDevice));
+		if (field == MJB_F_xfrc_applied) b->le_xfrc_stale = true;
 		if (field == MJB_F_xfrc_applied && !b->st.use_xfrc) {
 			b->st.use_xfrc = 1;
 			b->params_dirty = true;
@@ -2690,6 +2732,7 @@ int mjb_set_many(mjb_batch *b, int n, const int *fields, int env_lo, int env_hi,
 		if (kFields[field].kind == 0) {
 			err = hipMemcpyAsync(state_ptr(b, field) + (size_t)env_lo * sz, host[k], (size_t)(env_hi - env_lo) * sz * sizeof(double),
 			                     hipMemcpyHostToDevice, b->stream);
+			if (field == MJB_F_xfrc_applied) b->le_xfrc_stale = true;
 			if (field == MJB_F_xfrc_applied && !b->st.use_xfrc) {
 				b->st.use_xfrc = 1;
 				b->params_dirty = true;
@@ -2768,6 +2811,7 @@ static int packed_transfer(mjb_batch *b, int n, const int *fields, int env_lo, i
 		total += (long long)(env_hi - env_lo) * sz;
 		if (sz > 0) a.n++;
 		if (sz > maxdim) maxdim = sz;
+		if (!to_host && field == MJB_F_xfrc_applied) b->le_xfrc_stale = true;
 		if (!to_host && field == MJB_F_xfrc_applied && !b->st.use_xfrc) {
 			b->st.use_xfrc = 1;
 			b->params_dirty = true;
@@ -2897,6 +2941,12 @@ int mjb_lane_env_set_hwsim(mjb_batch *b, int on)
 {
 	if (!b) return fail(MJB_EINVAL, "null batch");
 	b->lane_env_hwsim = on != 0;
+	return MJB_OK;
+}
+int mjb_lane_env_set_xfrc(mjb_batch *b, int on)
+{
+	if (!b) return fail(MJB_EINVAL, "null batch");
+	b->lane_env_xfrc = on != 0;
 	return MJB_OK;
 }
 int mjb_set_sensors_every_step(mjb_batch *b, int on)

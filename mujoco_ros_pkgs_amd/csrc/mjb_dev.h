@@ -189,6 +189,8 @@ struct DevState {
 	int prof_base;                 // profiling build: first of the two probe ids this launch records (mjb_debug_profile_window)
 	const double *le_overlay;      // [slots][nenv] lane = env kernel, mjb_set_lane_env mode 2: each env's own gravity, joint constants, masses / inertias and
 	                               // actuator gains in the kernel's terms (PeSlots, mjb_lane_env_kernel.h); NULL until such a launch builds it
+	double *le_xfrc;               // [6 * slots][nenv] lane = env kernel, mjb_lane_env_set_xfrc: xfrc_applied of the moving bodies, transposed (XfSlots,
+	                               // mjb_lane_env_kernel.h); NULL until such a launch builds it.  The kernel zeroes the column of an env it resets
 };
 
 // The env's spill-over block in DevState::efc_Jg (kernel variant 4): efc_J [nefcmax][nv], then -- used only when the frame's row
@@ -367,12 +369,17 @@ int mjb_lane_env_eligible(const mjb_model_desc *h);   // the model's structure f
 const char *mjb_lane_env_jit_error(void);
 void mjb_lane_env_jit_stats(int *compiled, int *disk_hits);  // hiprtc builds of this process / builds taken from the disk cache instead              // why the last hiprtc build of a topology was not available ("" if none failed)
 // which build of the kernel a launch runs: the plain one (any form), or one of the two that exist for the solo form only and run it whatever the batch size --
-// the one that reads DevState::le_overlay (template flag PE), the one with the device hwsim stage, KernelParams::hw (template flag HW)
-enum LeBuild { MJB_LE_PLAIN = 0, MJB_LE_OVERLAY = 1, MJB_LE_HWSIM = 2 };
+// the one that reads DevState::le_overlay (template flag PE), the one with the device hwsim stage, KernelParams::hw (template flag HW), and the two
+// that apply xfrc_applied from DevState::le_xfrc (template flag XF), without and with the overlay
+enum LeBuild { MJB_LE_PLAIN = 0, MJB_LE_OVERLAY = 1, MJB_LE_HWSIM = 2, MJB_LE_XFRC = 3, MJB_LE_OVERLAY_XFRC = 4 };
 int mjb_launch_lane_env(const KernelParams *Pdev, int topo, const mjb_model_desc *h, int nenv_batch, int env_lo, int env_hi, int nsteps, unsigned int step0,
                         void *stream, LeBuild build);
 // the per-env overlay of that kernel: its slot count, and one env's column from the env's gravity and its block of DevState::env_mass (NULL: the model's values)
 int mjb_lane_env_overlay_slots(const mjb_model_desc *h);
+// the wrench table of that kernel's XF builds: its slot count (the model's moving bodies), and the transpose of xfrc_applied [nenv][nbody][6] into
+// table [6 * slots][nenv] for every env, on `stream`
+int mjb_lane_env_xfrc_slots(const mjb_model_desc *h);
+int mjb_lane_env_xfrc_fill(const mjb_model_desc *h, const double *xfrc_applied, double *table, int nenv, void *stream);
 void mjb_lane_env_overlay_row(const mjb_model_desc *h, const double *gravity, const double *env_block, double *out);
 // the split step (mjb_smooth_kernel.h + mjb_cstep_kernel): one step of envs [env_lo, env_hi) -- smooth half in lane = env form, then the constraint half
 int mjb_smooth_match(const mjb_model_desc *h);  // index of the compiled-in SmTopo the model has, or -1

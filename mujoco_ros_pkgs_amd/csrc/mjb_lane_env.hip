@@ -41,12 +41,12 @@ namespace {
 
 using namespace mjb_le;
 
-template <class T, int LP, bool PE = false, bool HW = false>  // (PE: per-env overrides from DevState::le_overlay, mjb_set_lane_env mode 2; HW: the device hwsim stage, mjb_lane_env_set_hwsim)
+template <class T, int LP, bool PE = false, bool HW = false, bool XF = false>  // (PE: per-env overrides from DevState::le_overlay, mjb_set_lane_env mode 2; HW: the device hwsim stage, mjb_lane_env_set_hwsim; XF: xfrc_applied from DevState::le_xfrc, mjb_lane_env_set_xfrc)
 __global__ void __launch_bounds__(64) mjb_lane_env_kernel(const KernelParams MJB_AS4 *__restrict__ P, const int nsteps, const unsigned int step0,
                                                           const int env_lo, const int env_hi)
 {
 	extern __shared__ __attribute__((aligned(16))) unsigned char smem_le[];
-	lane_env_body<T, LP, 0, PE, HW>(P, nsteps, step0, env_lo, env_hi, smem_le);
+	lane_env_body<T, LP, 0, PE, HW, XF>(P, nsteps, step0, env_lo, env_hi, smem_le);
 }
 
 template <class T, int LP>
@@ -302,12 +302,12 @@ bool source_fingerprint(const std::string &dir, unsigned long long &hsh)
 	return true;
 }
 
-const JitKernel &jit_get(const mjb_model_desc &h, int lp, int duo, LeBuild build)  // duo: 0 solo, 1 two halves, 2 pipelined, 3 three wavefronts, 4 four (form 3 with the pose sweep on two); build: the solo form's overlay / hwsim builds (mjb_dev.h)
+const JitKernel &jit_get(const mjb_model_desc &h, int lp, int duo, LeBuild build)  // duo: 0 solo, 1 two halves, 2 pipelined, 3 three wavefronts, 4 four (form 3 with the pose sweep on two); build: the solo form's overlay / hwsim / xfrc builds (mjb_dev.h)
 {
 	int dev = 0;
 	(void)hipGetDevice(&dev);
 	const std::string topo = topo_source(h);
-	const std::string key = std::to_string(dev) + "|" + std::to_string(lp) + (build == MJB_LE_HWSIM ? "h|" : build == MJB_LE_OVERLAY ? "e|" : duo == 4 ? "q|" : duo == 3 ? "t|" : (duo == 2 ? "p|" : (duo ? "d|" : "|"))) + topo;
+	const std::string key = std::to_string(dev) + "|" + std::to_string(lp) + (build == MJB_LE_OVERLAY_XFRC ? "ex|" : build == MJB_LE_XFRC ? "x|" : build == MJB_LE_HWSIM ? "h|" : build == MJB_LE_OVERLAY ? "e|" : duo == 4 ? "q|" : duo == 3 ? "t|" : (duo == 2 ? "p|" : (duo ? "d|" : "|"))) + topo;
 	std::lock_guard<std::mutex> lock(jit_mutex);
 	auto it = jit_cache.find(key);
 	if (it != jit_cache.end()) return it->second;
@@ -321,7 +321,7 @@ const JitKernel &jit_get(const mjb_model_desc &h, int lp, int duo, LeBuild build
 	const std::string src = "#include \"mjb_lane_env_kernel.h\"\n" + topo +
 	                        (build != MJB_LE_PLAIN ? "extern \"C\" __global__ void __launch_bounds__(64) le_rt(const KernelParams MJB_AS4 *P, int nsteps, unsigned int step0, int lo, int hi)\n{\n"
 	                              "\t__shared__ __attribute__((aligned(16))) unsigned char smem[mjb_le::Lds<LeTopo_rt, " + slp + ">::bytes()];\n"
-	                              "\tmjb_le::lane_env_body<LeTopo_rt, " + slp + (build == MJB_LE_HWSIM ? ", 0, false, true" : ", 0, true") + ">(P, nsteps, step0, lo, hi, smem);\n}\n"
+	                              "\tmjb_le::lane_env_body<LeTopo_rt, " + slp + (build == MJB_LE_OVERLAY_XFRC ? ", 0, true, false, true" : build == MJB_LE_XFRC ? ", 0, false, false, true" : build == MJB_LE_HWSIM ? ", 0, false, true" : ", 0, true") + ">(P, nsteps, step0, lo, hi, smem);\n}\n"
 	                         : duo == 4 ? "extern \"C\" __global__ void __launch_bounds__(256) le_rt(const KernelParams MJB_AS4 *P, int nsteps, unsigned int step0, int lo, int hi)\n{\n"
 	                                    "\t__shared__ __attribute__((aligned(16))) unsigned char smem[mjb_le::quartet_bytes<LeTopo_rt>()];\n"
 	                                    "\tmjb_le::lane_env_quartet<LeTopo_rt, 160>(P, nsteps, step0, lo, hi, smem);\n}\n"
@@ -492,6 +492,34 @@ int mjb_lane_env_overlay_slots(const mjb_model_desc *h)
 	}
 	return 3 + 4 * nj + 7 * nm + 6 * h->nu + (h->nbody - 1 - nm);
 }
+// ---- the wrench table of the XF kernels (XfSlots, mjb_lane_env_kernel.h): a slot per moving body, in body order ----
+int mjb_lane_env_xfrc_slots(const mjb_model_desc *h)
+{
+	int nm = 0;
+	for (int b = 1; b < h->nbody; b++) nm += le_moving(h, b);
+	return nm;
+}
+namespace {
+struct XfMap { int body[24], n; };  // (mjb_lane_env_eligible: at most 24 bodies)
+// one thread per (env, slot): the six doubles of a wrench to six rows; consecutive threads = consecutive envs, the stores coalesce
+__global__ void mjb_le_xfrc_fill_kernel(const double *__restrict__ xfrc, double *__restrict__ table, const XfMap map, const int nbody, const int nenv)
+{
+	const int env = (int)(blockIdx.x * blockDim.x + threadIdx.x), sl = (int)blockIdx.y;
+	if (env >= nenv || sl >= map.n) return;
+	const double *src = xfrc + ((size_t)env * nbody + map.body[sl]) * 6;
+	for (int k = 0; k < 6; k++) table[(size_t)(6 * sl + k) * nenv + env] = src[k];
+}
+}  // namespace
+int mjb_lane_env_xfrc_fill(const mjb_model_desc *h, const double *xfrc_applied, double *table, int nenv, void *stream)
+{
+	XfMap map{};
+	for (int b = 1; b < h->nbody && map.n < 24; b++)
+		if (le_moving(h, b)) map.body[map.n++] = b;
+	if (map.n == 0 || nenv <= 0) return 0;
+	hipLaunchKernelGGL(mjb_le_xfrc_fill_kernel, dim3((unsigned int)((nenv + 255) / 256), (unsigned int)map.n), dim3(256), 0, (hipStream_t)stream, xfrc_applied, table,
+	                   map, h->nbody, nenv);
+	return (int)hipGetLastError();
+}
 // gravity: the env's (NULL: the model's); env_block: the env's block of DevState::env_mass, mass and joint section (NULL: the model's values)
 void mjb_lane_env_overlay_row(const mjb_model_desc *h, const double *gravity, const double *env_block, double *out)
 {
@@ -578,7 +606,7 @@ int mjb_launch_lane_env(const KernelParams *Pdev, int topo, const mjb_model_desc
 	if (n <= 0) return 0;
 	// (measurement knob: envs per wavefront < 64 -- the wavefront starts with its upper lanes off)
 	static const int wl_env = mjb_env_int("MJB_LANE_ENV_WAVE_LANES", 64);
-	const int wl = (build == MJB_LE_PLAIN && (wl_env == 16 || wl_env == 32)) ? wl_env : 64;  // (the overlay and hwsim builds always run full wavefronts)
+	const int wl = (build == MJB_LE_PLAIN && (wl_env == 16 || wl_env == 32)) ? wl_env : 64;  // (the overlay, hwsim and xfrc builds always run full wavefronts)
 	const dim3 grid((unsigned int)((n + wl - 1) / wl)), block(wl);
 	// LDS budget per wavefront from the CUs the launch leaves idle: one wavefront per CU may take all of its LDS
 	// (per DEVICE: a process may drive several GPUs, one batch each -- ADVICE r05)
@@ -611,7 +639,7 @@ int mjb_launch_lane_env(const KernelParams *Pdev, int topo, const mjb_model_desc
 	const int sweep_ov = sweep_set ? sweep_set : sweep_env;
 	int sweep = duo == 3 ? (sweep_ov ? sweep_ov : (waves <= ncu ? 4 : 3)) : 0;
 	if (duo_mode > 0 && lp < 80) lp = 80, duo = 1;  // (a forced two-wavefront form on a batch that would run four wavefronts per CU: two per CU)
-	if (build != MJB_LE_PLAIN) {  // per-env overrides / the hwsim stage: the solo form at the budget the batch's size (or the knob) gives, whatever form is asked for
+	if (build != MJB_LE_PLAIN) {  // per-env overrides / the hwsim stage / xfrc_applied: the solo form at the budget the batch's size (or the knob) gives, whatever form is asked for
 		lp = lp_batch;
 		duo = 0, sweep = 0;
 	}
@@ -659,11 +687,12 @@ int mjb_launch_lane_env(const KernelParams *Pdev, int topo, const mjb_model_desc
 		hipLaunchKernelGGL(kern, grid, block, bytes, (hipStream_t)stream, (const KernelParams MJB_AS4 *)Pdev, nsteps, step0, env_lo, env_hi); \
 		return (int)hipGetLastError();                                                                                                        \
 	}
-#define MJB_LE_GO_SOLO(T, LPV, PEV, HWV)                                                                                                     \
+#define MJB_LE_GO_SOLO(T, LPV, PEV, HWV, XFV)                                                                                                \
 	{                                                                                                                                         \
-		auto kern = mjb_lane_env_kernel<T, LPV, PEV, HWV>;                                                                                    \
+		auto kern = mjb_lane_env_kernel<T, LPV, PEV, HWV, XFV>;                                                                               \
 		constexpr int bytes = Lds<T, LPV>::bytes();                                                                                           \
 		if (PEV && (!h || PeSlots<T>::n != mjb_lane_env_overlay_slots(h))) return (int)hipErrorInvalidValue;                                  \
+		if (XFV && (!h || XfSlots<T>::n != mjb_lane_env_xfrc_slots(h))) return (int)hipErrorInvalidValue;                                     \
 		const hipError_t attr = lds_attr_once(reinterpret_cast<const void *>(kern), bytes, cur_dev);                                          \
 		if (attr != hipSuccess) return (int)attr;                                                                                             \
 		le_form_last = 0, le_sweep_last = 0;                                                                                                  \
@@ -702,12 +731,18 @@ int mjb_launch_lane_env(const KernelParams *Pdev, int topo, const mjb_model_desc
 	}
 #define MJB_LE_X(id, T)                      \
 	if (topo == id) {                        \
-		if (build == MJB_LE_HWSIM && lp == 160) MJB_LE_GO_SOLO(T, 160, false, true)  \
-		if (build == MJB_LE_HWSIM && lp == 80) MJB_LE_GO_SOLO(T, 80, false, true)    \
-		if (build == MJB_LE_HWSIM) MJB_LE_GO_SOLO(T, 40, false, true)                \
-		if (build == MJB_LE_OVERLAY && lp == 160) MJB_LE_GO_SOLO(T, 160, true, false) \
-		if (build == MJB_LE_OVERLAY && lp == 80) MJB_LE_GO_SOLO(T, 80, true, false)   \
-		if (build == MJB_LE_OVERLAY) MJB_LE_GO_SOLO(T, 40, true, false)               \
+		if (build == MJB_LE_HWSIM && lp == 160) MJB_LE_GO_SOLO(T, 160, false, true, false)  \
+		if (build == MJB_LE_HWSIM && lp == 80) MJB_LE_GO_SOLO(T, 80, false, true, false)    \
+		if (build == MJB_LE_HWSIM) MJB_LE_GO_SOLO(T, 40, false, true, false)                \
+		if (build == MJB_LE_OVERLAY && lp == 160) MJB_LE_GO_SOLO(T, 160, true, false, false) \
+		if (build == MJB_LE_OVERLAY && lp == 80) MJB_LE_GO_SOLO(T, 80, true, false, false)   \
+		if (build == MJB_LE_OVERLAY) MJB_LE_GO_SOLO(T, 40, true, false, false)               \
+		if (build == MJB_LE_XFRC && lp == 160) MJB_LE_GO_SOLO(T, 160, false, false, true)   \
+		if (build == MJB_LE_XFRC && lp == 80) MJB_LE_GO_SOLO(T, 80, false, false, true)     \
+		if (build == MJB_LE_XFRC) MJB_LE_GO_SOLO(T, 40, false, false, true)                 \
+		if (build == MJB_LE_OVERLAY_XFRC && lp == 160) MJB_LE_GO_SOLO(T, 160, true, false, true) \
+		if (build == MJB_LE_OVERLAY_XFRC && lp == 80) MJB_LE_GO_SOLO(T, 80, true, false, true)   \
+		if (build == MJB_LE_OVERLAY_XFRC) MJB_LE_GO_SOLO(T, 40, true, false, true)               \
 		if (duo == 3 && sweep == 4) MJB_LE_GO_TRIO(T, 4) \
 		if (duo == 3) MJB_LE_GO_TRIO(T, 3)   \
 		if (duo >= 2) MJB_LE_GO_DUO2(T)      \

@@ -262,6 +262,14 @@ template <class T> struct PeSlots {
 	static constexpr int n = act(T::NU, 0) + (T::NBODY - 1 - nmb(T::NBODY));
 };
 
+// The wrench table (DevState::le_xfrc, XF kernels): xfrc_applied of the MOVING bodies as rows [6 * slot + k][env], k = force[3] | torque[3] as in
+// mjData.xfrc_applied -- a wavefront's 64 lanes read 64 consecutive doubles.  A body at rest (the world, a jointless chain down from it) has no
+// slot: its wrench moves nothing.  mjb_lane_env_xfrc_fill (mjb_lane_env.hip) transposes the canonical [env][nbody][6] array into it.
+template <class T> struct XfSlots {
+	static constexpr int slot(int b) { return PeSlots<T>::nmb(b); }
+	static constexpr int n = PeSlots<T>::nmb(T::NBODY);
+};
+
 // ROLE: 0 = one wavefront runs the whole step of its 64 envs.  1 / 2 = the DUO form, two wavefronts of one workgroup (on two SIMDs of a CU) share
 // the 64 envs of the block: the step's two independent halves -- what depends on qpos alone (poses, cinert, composite inertias, qM, both factors:
 // role 1, "P") and what depends on qvel too (velocities, the bodies' forces, the force block, qfrc_smooth: role 2, "V") -- run side by side, V hands
@@ -282,7 +290,14 @@ template <int NV> struct DuoSlots { static constexpr int n = (NV + 1) / 2 + 1; }
 // stage (a step without a write keeps the last one's) and the generic kernels continue the same batch.  A POSITION / VELOCITY joint's new qpos / qvel
 // wait in registers for mj_Euler: everything between the stage and Euler (passive forces, actuator length / velocity, joint sensors, energy) was
 // computed by forward_first from the old state in the generic kernels.  Solo form only; no build with PE.
-template <class T, int LP, int ROLE = 0, bool PE = false, bool HW = false>
+// XF: the batch carries xfrc_applied (mjb_lane_env_set_xfrc): mj_xfrcAccumulate rides in the root -> leaf sweep.  A moving body's wrench (f, t) acts at
+// its xipos; as a spatial force about the tree root's origin, (t + (xipos - origin) x f ; f), it is taken off the body's cfrc_body where that is
+// formed, so the leaf -> root sweep's projection on cdof yields qfrc_bias - J' xfrc and qfrc_smooth gains + J' xfrc: no pass of its own.  The wrench
+// is constant over the launch but there is no register or LDS to keep 6 doubles per body in: every step re-reads it from DevState::le_xfrc
+// (XfSlots), coalesced, one region ahead of its use.  mj_resetData zeroes xfrc_applied: a lane reset inside the launch reads zero from then on
+// (the retry after a mj_checkAcc reset included), and at the launch's end its rows of xfrc_applied and its column of the table are zeroed in HBM.
+// Solo form only; composes with PE, not with HW.
+template <class T, int LP, int ROLE = 0, bool PE = false, bool HW = false, bool XF = false>
 DEVI void lane_env_body(const KernelParams MJB_AS4 *__restrict__ P, const int nsteps, const unsigned int step0, const int env_lo, const int env_hi,
                         unsigned char *const smem_le)
 {
@@ -309,7 +324,9 @@ DEVI void lane_env_body(const KernelParams MJB_AS4 *__restrict__ P, const int ns
 	using Q = Tq<T>;
 	static_assert(!PE || ROLE == 0, "lane = env kernel: per-env overrides run the solo form");
 	static_assert(!HW || (ROLE == 0 && !PE), "lane = env kernel: the hwsim stage runs the solo form, without per-env overrides");
+	static_assert(!XF || (ROLE == 0 && !HW), "lane = env kernel: xfrc_applied runs the solo form, without the hwsim stage");
 	using OV = PeSlots<T>;
+	using XS6 = XfSlots<T>;
 	constexpr int LPE = PIPE ? (1 << 20) : (DUO ? LP - DuoSlots<NV>::n : LP);
 	using LD = Lds<T, LPE>;
 	static_assert(LD::slot(T::NBODY) <= LPE, "lane = env kernel: state and forces of the topology need more LDS than this instantiation's budget");
@@ -468,6 +485,18 @@ DEVI void lane_env_body(const KernelParams MJB_AS4 *__restrict__ P, const int ns
 				ovs = (size_t)s.nenv * sizeof(double);
 			}
 			[[maybe_unused]] const unsigned int ovl = (unsigned int)env * (unsigned int)sizeof(double);
+			// (XF) row r of the wrench table, this lane's env: base + r * nenv + env, re-derived on every trip like the overlay's
+			[[maybe_unused]] const char *xfb = nullptr;
+			[[maybe_unused]] size_t xfs = 0;
+			if constexpr (XF) {
+				const double *o = s.le_xfrc;
+				asm volatile("" : "+s"(o));
+				xfb = reinterpret_cast<const char *>(o);
+				xfs = (size_t)s.nenv * sizeof(double);
+			}
+			[[maybe_unused]] auto xf_ld = [&](int row) -> double {
+				return *(const double __attribute__((address_space(1))) *)(xfb + (size_t)row * xfs + ovl);
+			};
 			[[maybe_unused]] auto pe_ld = [&](int sl) -> double {
 				return *(const double __attribute__((address_space(1))) *)(ovb + (size_t)sl * ovs + ovl);
 			};
@@ -506,6 +535,7 @@ DEVI void lane_env_body(const KernelParams MJB_AS4 *__restrict__ P, const int ns
 			//  cannot be hoisted beyond it -- left alone, the compiler issues them bodies ahead and parks ~540 SGPRs in VGPR lanes)
 			double hA[NB + 1][16], hB[NB][16];
 			[[maybe_unused]] double vB[PE ? NB : 1][7];  // (PE) the env's mass | ibody[6] of a body, fetched with the body's inertial half record
+			[[maybe_unused]] double xw[XF ? NB : 1][6];  // (XF) the env's wrench on a moving body, fetched with the body's inertial half record
 			for (int k = 0; k < 14; k++) hA[1][k] = reinterpret_cast<const double MJB_AS4 *>(tb + 1)[k];
 			// ... and the (qpos, qvel) pair of the next jointed body: LDS reads and scalar loads share one counter, so a read issued where
 			// it is needed would wait for the record fetched beside it
@@ -769,6 +799,7 @@ DEVI void lane_env_body(const KernelParams MJB_AS4 *__restrict__ P, const int ns
 					if constexpr (OV::moving(b)) for (int k = 0; k < 7; k++) vB[b][k] = pe_ld(OV::inert(b, k));
 					else vB[b][0] = pe_ld(OV::rest(b));
 				}
+				if constexpr (XF && LD::needed(b)) for (int k = 0; k < 6; k++) xw[b][k] = xf_ld(6 * XS6::slot(b) + k);
 				const double *const A = hA[b];  // pos[3] quat[4] jaxis[3] jpos[3] qpos0 stiffness spring
 				if constexpr (ROLE == 5 && b == 1 && b + 1 < NB) {
 					if constexpr (T::body_jnt[b + 1] >= 0) {
@@ -939,6 +970,15 @@ DEVI void lane_env_body(const KernelParams MJB_AS4 *__restrict__ P, const int ns
 						mul_inert_vec(cf, ci, cacc[b]);
 						mul_inert_vec(t0, ci, cvel[b]);
 						cross_force(t1, cvel[b], t0);
+						if constexpr (XF) {
+							// mj_xfrcAccumulate: the body's wrench at xipos as a spatial force about the tree root's origin, off the body's own force
+							double xd[3], w[6], tq[3];
+							if constexpr (r == b) for (int k = 0; k < 3; k++) xd[k] = xipos[k] - pos[k];
+							else for (int k = 0; k < 3; k++) xd[k] = xipos[k] - xpos[r][k];
+							for (int k = 0; k < 6; k++) { const double v = pinv(xw[b][k]); w[k] = seld(wasreset, 0.0, v); }  // (zero after mj_resetData; load first, then select)
+							cross3(tq, xd, w);
+							for (int k = 0; k < 3; k++) { cf[k] -= w[3 + k] + tq[k]; cf[3 + k] -= w[k]; }
+						}
 						constexpr int q0 = LD::slot(b);
 						lp[64 * q0] = Pair{ cf[0] + t1[0], cf[1] + t1[1] };
 						lp[64 * (q0 + 1)] = Pair{ cf[2] + t1[2], cf[3] + t1[3] };
@@ -1633,6 +1673,17 @@ DEVI void lane_env_body(const KernelParams MJB_AS4 *__restrict__ P, const int ns
 			sfor<NU>([&](auto I) { s.ctrlnoise[ev * NU + I] = cn[I]; });
 			if (nz_on) sfor<NU>([&](auto I) { s.ctrl[ev * NU + I] = cn[I]; });
 			else if (__builtin_amdgcn_ballot_w64(wasreset)) sfor<NU>([&](auto I) { const double c = pinv(s.ctrl[ev * NU + I]); s.ctrl[ev * NU + I] = wasreset ? 0.0 : c; });
+		}
+		if constexpr (XF) {
+			// mj_resetData zeroed the env's xfrc_applied: the canonical rows (every body's) and the table's column, under the wave-uniform test -- every
+			// lane of such a wavefront stores, a lane that was not reset what it loaded
+			if (__builtin_amdgcn_ballot_w64(wasreset)) {
+				double *const xa = s.xfrc_applied + ev * (size_t)(6 * NB);
+				sfor<6 * NB>([&](auto I) { const double c = pinv(xa[I]); xa[I] = seld(wasreset, 0.0, c); });
+				double *const xt = s.le_xfrc + ev;
+				const size_t ne = (size_t)s.nenv;
+				sfor<6 * XS6::n>([&](auto I) { const double c = pinv(xt[(size_t)I * ne]); xt[(size_t)I * ne] = seld(wasreset, 0.0, c); });
+			}
 		}
 	}
 }

@@ -367,6 +367,11 @@ class Batch:
         stage; off (the default), such a batch runs the generic kernels (mjb_lane_env_set_hwsim)."""
         _check(self.lib.mjb_lane_env_set_hwsim(self.ptr, 1 if on else 0), "mjb_lane_env_set_hwsim")
 
+    def set_lane_env_xfrc(self, on=True):
+        """Opt-in: a batch whose xfrc_applied has been written may run the lane = env kernel, in its one-wavefront build that applies the wrenches
+        (with mode 2: together with the per-env overlay); off (the default), such a batch runs the generic kernels (mjb_lane_env_set_xfrc)."""
+        _check(self.lib.mjb_lane_env_set_xfrc(self.ptr, 1 if on else 0), "mjb_lane_env_set_xfrc")
+
     def lane_env_info(self):
         """(compiled-in topology index or -1, the last fused launch ran the lane = env kernel)."""
         used = C.c_int(0)

@@ -34,7 +34,9 @@ if os.path.exists(f):
         if mm.group(1) == "trio_":  # (form 3: the template's integer is the count of sweep wavefronts, not an LDS budget)
             mm = (None, mm.group(2), "form 3, " + ("four" if mm.group(3) == "4" else "three") + " wavefronts")
         else:
-            mm = (None, mm.group(2), (mm.group(3) or "-") + form + (", per-env overrides" if "Lb1ELb0E" in name.group(1) else "") + (", hwsim stage" if "Lb0ELb1E" in name.group(1) else ""))
+            fl = re.search(r"Lb([01])ELb([01])ELb([01])E", name.group(1))  # (the solo kernel's template flags PE, HW, XF)
+            fl = [x == "1" for x in fl.groups()] if fl else [False] * 3
+            mm = (None, mm.group(2), (mm.group(3) or "-") + form + (", per-env overrides" if fl[0] else "") + (", hwsim stage" if fl[1] else "") + (", xfrc_applied" if fl[2] else ""))
         mm = type("M", (), {"group": lambda self, i, _m=mm: _m[i]})()
         get = lambda k: int(re.search(r"\." + k + r":\s+(\d+)", blk).group(1))  # noqa: E731
         agpr = int(re.match(r":\s+(\d+)", blk).group(1))
