@@ -658,7 +658,7 @@ int mjb_launch_lane_env(const KernelParams *Pdev, int topo, const mjb_model_desc
 				return MJB_LE_UNAVAILABLE;
 			}
 			if (fit > lp) lp = fit;
-			if (sweep == 4 && need + 5 * ((need - h->nv) / 3) + 18 + (h->nv + 1) / 2 + 1 + h->nbody + 14 > 160) sweep = 3;  // (the quartet's two rings behind the trio's layout)
+			if (sweep == 4 && need + 5 * ((need - h->nv) / 3) + 18 + (h->nv + 1) / 2 + 1 + h->nbody + mjb_le::QUARTET_EXTRA > 160) sweep = 3;  // (the quartet's two rings and X's mail slot behind the trio's layout: quartet_bytes<T>())
 			if (duo == 3 && need + 5 * ((need - h->nv) / 3) + 18 + (h->nv + 1) / 2 + 1 + h->nbody > 160) duo = 2;
 			if (duo != 3) sweep = 0;
 			if (duo == 2 && need + 5 * ((need - h->nv) / 3) + 12 + (h->nv + 1) / 2 + 1 > 160) duo = 1;

@@ -280,6 +280,9 @@ template <class T> struct XfSlots {
 // loads -- V's ctrl-noise normals and qfrc_applied are fetched a sweep ahead of their use precisely so that nobody waits for HBM)
 DEVI void le_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 template <int NV> struct DuoSlots { static constexpr int n = (NV + 1) / 2 + 1; };  // qfrc_smooth pairs + the mail slot
+// pair slots of a quartet block behind the trio's layout: O's quaternion ring (2 x 4), C's cdof ring (2 x 3), X's mail slot.  quartet_bytes<T>() below and the
+// launcher's fit test for hiprtc-built models (mjb_lane_env.hip) both count with it
+constexpr int QUARTET_EXTRA = 15;
 // PE: the batch carries per-env overrides (mjb_set_lane_env mode 2): gravity, the joint constants, masses / inertias and the actuator gains come
 // per lane from DevState::le_overlay instead of the tape (solo form only).
 // HW: the batch has a device hwsim stage (KernelParams::hw, mjb_lane_env_set_hwsim): DefaultRobotHWSim::writeSim runs per lane where the forces are
@@ -321,6 +324,13 @@ DEVI void lane_env_body(const KernelParams MJB_AS4 *__restrict__ P, const int ns
 	constexpr bool VLDS = ROLE == 7 || ROLE == 11;  // V of three / four wavefronts: cinert from C through LDS
 	constexpr bool EPOS = ROLE == 0 || ROLE == 1 || ROLE == 3 || ROLE == 5 || ROLE == 9;                     // gathers mj_energyPos along its pose sweep
 	constexpr bool SENSF = ROLE == 0 || ROLE == 2 || ROLE == 3 || ROLE == 5 || ROLE == 9;  // frame sensors: who holds the poses (and, of two, who has the time)
+	// (the quartet's tail is split by MATRIX: X keeps its own cdof, reads C's cinert from LDS behind the sweep's last barrier, builds qM a second time beside C,
+	//  factors M, solves qacc = M^-1 f and takes mj_checkAcc's decision; C factors M + h B alone, solves the acceleration Euler advances with and integrates
+	//  SPECULATIVELY -- X's verdict, read by all four behind rendezvous B, either lets the step stand or has C put the old state back.  Nothing but V's
+	//  qfrc_smooth and the two mail slots crosses LDS, and the step has no barrier the trio's tail does not have.)
+	[[maybe_unused]] constexpr bool XW = ROLE == 9;               // X of four wavefronts: the walk's position half, the M factor, the qacc solve, mj_checkAcc
+	[[maybe_unused]] constexpr bool DPW = DP || XW;               // runs the position half of the leaf -> root walk
+	[[maybe_unused]] constexpr bool FM = ROLE != 10, FH = !XW;    // factors and solves with M / with M + h B
 	using Q = Tq<T>;
 	static_assert(!PE || ROLE == 0, "lane = env kernel: per-env overrides run the solo form");
 	static_assert(!HW || (ROLE == 0 && !PE), "lane = env kernel: the hwsim stage runs the solo form, without per-env overrides");
@@ -340,6 +350,8 @@ DEVI void lane_env_body(const KernelParams MJB_AS4 *__restrict__ P, const int ns
 	constexpr int LASTB = [] { for (int c = NB - 1; c >= 1; c--) if (LD::needed(c)) return c; return 0; }();  // the leaf the composite-inertia sweep starts at
 	constexpr int RING = LD::nslots();                                              // (PIPE) 2 x 6 pair slots of the pose ring behind the solo layout
 	constexpr int QR0 = RING + 18 + DuoSlots<NV>::n + NB, CD0 = QR0 + 8;  // (quartet, behind the trio's layout) O's quaternion ring: 2 x (xquat, the frame before the joint); C's cdof ring: 2 x 3
+	[[maybe_unused]] constexpr int XMAIL = CD0 + 6;  // (quartet) X's verdict on the step (mj_checkAcc), a slot nobody else writes: the last of QUARTET_EXTRA
+	static_assert(XMAIL + 1 == QR0 + QUARTET_EXTRA, "lane = env kernel: the quartet's slots and quartet_bytes<T>() (and the host's fit test for hiprtc-built models) go together");
 	constexpr int XS = PIPE ? RING + 6 * RINGN : LD::nslots(), MAIL = XS + (NV + 1) / 2, SC0 = MAIL + 1;  // (trio) SC0 + b: body b's half-angle (sin, cos), from C to P  // (DUO) pair slots of qfrc_smooth, and of P's verdicts for V
 	const int lane_le = DUO ? (int)(threadIdx.x & 63u) : (int)threadIdx.x;
 	Pair *const lp = reinterpret_cast<Pair *>(smem_le) + lane_le;  // pair slot q of this lane: lp[64 * q]
@@ -1151,6 +1163,27 @@ DEVI void lane_env_body(const KernelParams MJB_AS4 *__restrict__ P, const int ns
 						lp[64 * (rg + 3)] = Pair{ xm[3], xm[4] };
 						lp[64 * (rg + 4)] = Pair{ xm[5], xm[6] };
 						lp[64 * (rg + 5)] = Pair{ xm[7], xm[8] };
+						if constexpr (j >= 0) {  // cdof for X's own leaf -> root walk: C's expressions (consume) on the same pose, kept in registers to the tail
+							double *cd = cdof[j];
+							const double ax[3] = { A[7], A[8], A[9] };
+							double xaxis[3];
+							matvec3(xaxis, xm, ax);
+							if constexpr (T::jnt_type[j] == MJB_JNT_SLIDE) {
+								cd[0] = cd[1] = cd[2] = 0;
+								for (int k = 0; k < 3; k++) cd[3 + k] = xaxis[k];
+							} else {
+								const double jp[3] = { A[10], A[11], A[12] };
+								double xa[3] = { xp[0], xp[1], xp[2] }, off[3];
+								if (jp[0] != 0 || jp[1] != 0 || jp[2] != 0) {
+									double v[3];
+									matvec3(v, xm, jp);
+									for (int k = 0; k < 3; k++) xa[k] += v[k];
+								}
+								for (int k = 0; k < 3; k++) off[k] = -xa[k];  // (root origin - anchor)
+								for (int k = 0; k < 3; k++) cd[k] = xaxis[k];
+								cross3(cd + 3, xaxis, off);
+							}
+						}
 					}
 				};
 				auto x_phase = [&](auto Bq) {
@@ -1406,12 +1439,12 @@ DEVI void lane_env_body(const KernelParams MJB_AS4 *__restrict__ P, const int ns
 				constexpr int q0 = LD::slot(nb);
 				if constexpr (PE && T::body_jnt[nb] >= 0) parm[nb] = pe_ld(OV::joint(nb, 2));
 				else
-				if constexpr (DP && T::body_jnt[nb] >= 0) parm[nb] = tb[nb].armature;
+				if constexpr (DPW && T::body_jnt[nb] >= 0) parm[nb] = tb[nb].armature;
 				if constexpr (DV) {
 					const Pair c0 = lp[64 * q0], c1 = lp[64 * (q0 + 1)], c2 = lp[64 * (q0 + 2)];
 					pcf[nb][0] = c0.a; pcf[nb][1] = c0.b; pcf[nb][2] = c1.a; pcf[nb][3] = c1.b; pcf[nb][4] = c2.a; pcf[nb][5] = c2.b;
 				}
-				if constexpr (DP && LD::cin_slot(nb) >= 0) {
+				if constexpr (DPW && LD::cin_slot(nb) >= 0) {
 					constexpr int cs = LD::cin_slot(nb);
 					for (int k = 0; k < 5; k++) {
 						const Pair c = lp[64 * (cs + k)];
@@ -1429,10 +1462,10 @@ DEVI void lane_env_body(const KernelParams MJB_AS4 *__restrict__ P, const int ns
 				constexpr int p = T::body_parentid[b], j = T::body_jnt[b];
 				if constexpr (LD::needed(b)) {
 					if constexpr (DV) touch_v(pcf[b][0]);
-					else if constexpr (DP && LD::cin_slot(b) >= 0) touch_v(pcb[b][0]);
+					else if constexpr (DPW && LD::cin_slot(b) >= 0) touch_v(pcb[b][0]);
 					if constexpr (PE && j >= 0) touch_v(parm[b]);
 					else
-					if constexpr (DP && j >= 0) touch_s(parm[b]);
+					if constexpr (DPW && j >= 0) touch_s(parm[b]);
 					{
 						constexpr int nb = [] { for (int c = b - 1; c >= 1; c--) if (LD::needed(c)) return c; return 0; }();
 						if constexpr (nb > 0) fetch_body(IC<nb>{});
@@ -1443,7 +1476,7 @@ DEVI void lane_env_body(const KernelParams MJB_AS4 *__restrict__ P, const int ns
 					constexpr bool has_child = [] { for (int c = b + 1; c < NB; c++) if (T::body_parentid[c] == b && LD::needed(c)) return true; return false; }();
 					if constexpr (DV && has_child) for (int k = 0; k < 6; k++) cf[k] += csum[b][k];
 					[[maybe_unused]] double cb[10];  // composite inertia of the body (mj_crb)
-					if constexpr (DP) {
+					if constexpr (DPW) {
 						if constexpr (LD::cin_slot(b) >= 0) {
 							for (int k = 0; k < 10; k++) cb[k] = pcb[b][k];
 						} else {
@@ -1453,7 +1486,7 @@ DEVI void lane_env_body(const KernelParams MJB_AS4 *__restrict__ P, const int ns
 					}
 					if constexpr (j >= 0) {
 						if constexpr (DV) f[j] -= dot6r(cdof[j], cf);
-						if constexpr (DP) {
+						if constexpr (DPW) {
 							double buf[6];
 							mul_inert_vec(buf, cb, cdof[j]);
 							sfor<NV>([&](auto A) {
@@ -1468,7 +1501,7 @@ DEVI void lane_env_body(const KernelParams MJB_AS4 *__restrict__ P, const int ns
 							if constexpr (first) for (int k = 0; k < 6; k++) csum[p][k] = cf[k];
 							else for (int k = 0; k < 6; k++) csum[p][k] += cf[k];
 						}
-						if constexpr (DP) {
+						if constexpr (DPW) {
 							if constexpr (first) for (int k = 0; k < 10; k++) crbs[p][k] = cb[k];
 							else for (int k = 0; k < 10; k++) crbs[p][k] += cb[k];
 						}
@@ -1478,7 +1511,7 @@ DEVI void lane_env_body(const KernelParams MJB_AS4 *__restrict__ P, const int ns
 			});
 			LE_PK(3);
 			if constexpr (ROLE == 5 || ROLE == 9) en_pe = pe;
-			if constexpr (DUO && !DP) {
+			if constexpr (DUO && !DP && !XW) {
 				// ---- V's half ends here: qfrc_smooth to P, then P's verdict on the step (the trio's P: the two rendezvous and the verdict)
 				if constexpr (DV) sfor<(NV + 1) / 2>([&](auto K) {
 					constexpr int k = K;
@@ -1488,7 +1521,8 @@ DEVI void lane_env_body(const KernelParams MJB_AS4 *__restrict__ P, const int ns
 				le_barrier();  // (A) qfrc_smooth is in LDS; P's factors are ready
 				LE_PK(5);
 				le_barrier();  // (B) P has solved and either integrated or -- bad qacc -- reset its lanes
-				const int code = (int)lp[64 * MAIL].a;
+				int code = (int)lp[64 * MAIL].a;
+				if constexpr (QUAD) code |= (int)lp[64 * XMAIL].a;  // (four wavefronts: bits 0 / 1 are C's, on the state it committed; bits 2 / 3 X's, mj_checkAcc)
 				LE_PK(6);
 				if (!(__builtin_amdgcn_readfirstlane(code) & 8)) {  // (bit 3: P's ballot, the same in every lane)
 					badp_next = (code & 2) != 0;
@@ -1499,6 +1533,7 @@ DEVI void lane_env_body(const KernelParams MJB_AS4 *__restrict__ P, const int ns
 				sfor<NU>([&](auto I) { cn[I] = bada ? 0.0 : cn[I]; });
 				time = bada ? 0.0 : time;
 				wasreset = wasreset || bada;
+				if constexpr (QUAD) le_barrier();  // (R) C has put the old state back, the reset lanes' qpos0: the second trip reads it
 				continue;
 			}
 			if (e_on) {  // mj_energyVel: 0.5 qvel' M qvel (mj_energyPos was gathered along the sweep)
@@ -1517,7 +1552,7 @@ DEVI void lane_env_body(const KernelParams MJB_AS4 *__restrict__ P, const int ns
 			// ================= A3 mj_factorM + A12 mj_fwdAcceleration; A16's (M + h B) factor and solve beside them =================
 			// L'DL in place, pivots from the last dof up: row k scaled by 1 / D_k, then row i -= L_ki * (row k restricted to i's ancestors)
 			const bool damp_on = m.eulerdamp != 0;
-			constexpr bool FH = true;
+			// (four wavefronts: X has the M of every line below and no other, C the M + h B -- with mjDSBL_EULERDAMP C's h B is zero and its arithmetic X's)
 			double qH[NV > 0 ? NV : 1][NV > 0 ? NV : 1], dinv[NV > 0 ? NV : 1], hinv[NV > 0 ? NV : 1];
 			if constexpr (FH) {
 				sfor<NV>([&](auto I) {
@@ -1527,40 +1562,45 @@ DEVI void lane_env_body(const KernelParams MJB_AS4 *__restrict__ P, const int ns
 							if constexpr (Q::anc(a, i) && a == i) qH[i][a] = qM[i][a] + pe_ld(OV::joint(T::jnt_bodyid[i], 3));
 							else if constexpr (Q::anc(a, i)) qH[i][a] = qM[i][a];
 						} else
+						if constexpr (Q::anc(a, i) && a == i && !FM) {
+							const double hd = pins(tb[T::jnt_bodyid[i]].hdamping);  // (loaded, then selected)
+							qH[i][a] = qM[i][a] + (damp_on ? hd : 0.0);
+						} else
 						if constexpr (Q::anc(a, i)) qH[i][a] = qM[i][a] + (a == i ? tb[T::jnt_bodyid[i]].hdamping : 0.0);
 					});
 				});
 			}
 			sfor<NV>([&](auto Ki) {
 				constexpr int k = NV - 1 - Ki;
-				dinv[k] = frcp(qM[k][k]);
+				if constexpr (FM) dinv[k] = frcp(qM[k][k]);
 				if constexpr (FH) hinv[k] = frcp(qH[k][k]);
 				sfor<NV>([&](auto Ii) {
 					constexpr int i = NV - 1 - Ii;  // ancestors of k, nearest first
 					if constexpr (i < k && Q::anc(i, k)) {
-						const double tm = qM[k][i] * dinv[k];
+						[[maybe_unused]] double tm = 0;
+						if constexpr (FM) tm = qM[k][i] * dinv[k];
 						[[maybe_unused]] double th = 0;
 						if constexpr (FH) th = qH[k][i] * hinv[k];
 						sfor<NV>([&](auto A) {
 							constexpr int a = A;
 							if constexpr (Q::anc(a, i)) {
-								qM[i][a] -= tm * qM[k][a];
+								if constexpr (FM) qM[i][a] -= tm * qM[k][a];
 								if constexpr (FH) qH[i][a] -= th * qH[k][a];
 							}
 						});
-						qM[k][i] = tm;
+						if constexpr (FM) qM[k][i] = tm;
 						if constexpr (FH) qH[k][i] = th;
 					}
 				});
 			});
 			// x = M^-1 f and y = (M + h B)^-1 f: L' sweep, D, L sweep
 			double x[NV > 0 ? NV : 1], y[NV > 0 ? NV : 1];
-			if constexpr (DUO && DP && NV > 0) {  // (the factors BEFORE the rendezvous: left alone the compiler sinks them behind it, next to the solves)
-				touch_v(dinv[0]);
+			if constexpr (DUO && DPW && NV > 0) {  // (the factors BEFORE the rendezvous: left alone the compiler sinks them behind it, next to the solves)
+				if constexpr (FM) touch_v(dinv[0]);
 				if constexpr (FH) touch_v(hinv[0]);
 			}
 			LE_PK(4);
-			if constexpr (DUO && DP) {
+			if constexpr (DUO && DPW) {
 				le_barrier();  // (A) V's qfrc_smooth
 				LE_PK(5);
 				sfor<(NV + 1) / 2>([&](auto K) {
@@ -1575,19 +1615,81 @@ DEVI void lane_env_body(const KernelParams MJB_AS4 *__restrict__ P, const int ns
 				constexpr int i = NV - 1 - Ii;
 				sfor<NV>([&](auto A) {
 					constexpr int a = A;
-					if constexpr (a < i && Q::anc(a, i)) { x[a] -= qM[i][a] * x[i]; if constexpr (FH) y[a] -= qH[i][a] * y[i]; }
+					if constexpr (a < i && Q::anc(a, i)) { if constexpr (FM) x[a] -= qM[i][a] * x[i]; if constexpr (FH) y[a] -= qH[i][a] * y[i]; }
 				});
 			});
-			sfor<NV>([&](auto I) { x[I] *= dinv[I]; if constexpr (FH) y[I] *= hinv[I]; });
+			sfor<NV>([&](auto I) { if constexpr (FM) x[I] *= dinv[I]; if constexpr (FH) y[I] *= hinv[I]; });
 			sfor<NV>([&](auto I) {
 				constexpr int i = I;
 				sfor<NV>([&](auto Ai) {
 					constexpr int a = NV - 1 - Ai;  // nearest ancestor first, as mj_solveLD walks them
-					if constexpr (a < i && Q::anc(a, i)) { x[i] -= qM[i][a] * x[a]; if constexpr (FH) y[i] -= qH[i][a] * y[a]; }
+					if constexpr (a < i && Q::anc(a, i)) { if constexpr (FM) x[i] -= qM[i][a] * x[a]; if constexpr (FH) y[i] -= qH[i][a] * y[a]; }
 				});
 			});
+			if constexpr (XW) sfor<NV>([&](auto I) { qacc[I] = x[I]; });
+			else if constexpr (!FM) sfor<NV>([&](auto I) { qaccd[I] = y[I]; });
+			else
 			sfor<NV>([&](auto I) { qacc[I] = x[I]; qaccd[I] = damp_on ? y[I] : x[I]; });
 
+			if constexpr (XW) {
+				// ---- (four wavefronts) mj_checkAcc on X: the verdict goes to the other three by mail -- bit 3 = some lane of the wavefront is bad, bit 2 = this
+				// lane is -- while C integrates on the assumption that nobody is.  The second trip checks nothing and mails 0.
+				bool bada = false;
+				sfor<NV>([&](auto I) { bada |= bad_val(qacc[I]); });
+				const bool retry = attempt == 0 && __builtin_amdgcn_ballot_w64(bada) != 0;  // (wave-uniform)
+				if (retry) atomicAdd(s.nwarn + MJB_WARN_BADQACC, (bada && live) ? 1ull : 0ull);
+				const double verdict = bada ? 12.0 : 8.0;
+				lp[64 * XMAIL] = Pair{ retry ? verdict : 0.0, 0.0 };
+				LE_PK(6);
+				le_barrier();  // (B) C's new state and its verdicts on it
+				LE_PK(7);
+				if (!retry) {
+					const int code = (int)lp[64 * MAIL].a;
+					badp_next = (code & 2) != 0;
+					badv_next = (code & 1) != 0;
+					break;
+				}
+				sfor<NU>([&](auto I) { cn[I] = bada ? 0.0 : cn[I]; });
+				time = bada ? 0.0 : time;
+				wasreset = wasreset || bada;
+				le_barrier();  // (R) C has put the old state back
+				continue;
+			}
+			if constexpr (ROLE == 10) {
+				// ---- (four wavefronts) C: mj_Euler at once, on the assumption that X finds qacc good; the nine (qpos, qvel) pairs it read stay in registers
+				// until X's verdict is in, and `time` waits for it too
+				Pair sv[NV > 0 ? NV : 1];
+				bool bp = false, bv = false;
+				sfor<NV>([&](auto I) {
+					Pair s2 = lp[64 * I];
+					sv[I] = s2;
+					s2.b += dt * qaccd[I];
+					s2.a += dt * s2.b;
+					lp[64 * I] = s2;
+					bp |= bad_val(s2.a);  // the next step's mj_checkPos / mj_checkVel
+					bv |= bad_val(s2.b);
+				});
+				badp_next = bp;
+				badv_next = bv;
+				lp[64 * MAIL] = Pair{ (double)((bp ? 2 : 0) | (bv ? 1 : 0)), 0.0 };
+				LE_PK(6);
+				le_barrier();  // (B) the new state and its verdicts; X's verdict on qacc
+				LE_PK(7);
+				const int xc = (int)lp[64 * XMAIL].a;
+				if (!(__builtin_amdgcn_readfirstlane(xc) & 8)) break;  // (bit 3: X's ballot, the same in every lane and for all four wavefronts)
+				// the rare path: some lane's qacc was bad.  The step is undone -- a bad lane gets mj_resetData's state, every other lane the pair it had -- and the
+				// forward pass runs once more for the whole wavefront
+				const bool bada = (xc & 4) != 0;
+				sfor<NV>([&](auto I) {
+					const double q0 = pins(tb[T::jnt_bodyid[I]].qpos0);
+					lp[64 * I] = Pair{ bada ? q0 : sv[I].a, bada ? 0.0 : sv[I].b };
+				});
+				sfor<NU>([&](auto I) { cn[I] = bada ? 0.0 : cn[I]; });
+				time = bada ? 0.0 : time;
+				wasreset = wasreset || bada;
+				le_barrier();  // (R) the old state is back: the second trip reads it
+				continue;
+			}
 			// ---- mj_checkAcc: a bad qacc resets the env and the forward pass runs once more (mj_step)
 			if (attempt) break;
 			bool bada = false;
@@ -1611,12 +1713,21 @@ DEVI void lane_env_body(const KernelParams MJB_AS4 *__restrict__ P, const int ns
 		if constexpr (ROLE == 5 || ROLE == 9) {
 			if (last && (m.enableflags & MJB_ENBL_ENERGY)) s.energy[2 * ev] = en_pe;  // (C stores the kinetic half)
 		}
+		if constexpr (XW) {
+			if (last) {  // (four wavefronts: qacc is X's)
+				sfor<NV>([&](auto I) {
+					s.qacc[ev * NV + I] = qacc[I];
+					s.qacc_warmstart[ev * NV + I] = qacc[I];
+				});
+			}
+		}
 		if constexpr (DUO && !DP) {
 			time += dt;
 			continue;
 		}
 
 		if (last) {  // mj_advance's qacc_warmstart = qacc; mjData.energy of the launch's last step
+			if constexpr (ROLE != 10)
 			sfor<NV>([&](auto I) {
 				s.qacc[ev * NV + I] = qacc[I];
 				s.qacc_warmstart[ev * NV + I] = qacc[I];
@@ -1625,6 +1736,10 @@ DEVI void lane_env_body(const KernelParams MJB_AS4 *__restrict__ P, const int ns
 				if constexpr (EPOS) s.energy[2 * ev] = en_pe;
 				s.energy[2 * ev + 1] = en_ke;
 			}
+		}
+		if constexpr (ROLE == 10) {  // (four wavefronts: C has integrated inside the loop, ahead of X's verdict)
+			time += dt;
+			continue;
 		}
 		// ================= A16 mj_Euler =================
 		badp_next = badv_next = false;
@@ -1693,8 +1808,8 @@ template <class T, int LP> constexpr int duo_bytes() { return (Lds<T, LP - DuoSl
 
 // ... and of a pipelined DUO block (roles 3 / 4): every needed body's cinert, every dof's cdof, the pose ring, the exchange slots
 template <class T> constexpr int trio_bytes() { return (Lds<T, (1 << 20)>::nslots() + 18 + DuoSlots<T::NV>::n + T::NBODY) * 64 * 16; }
-// ... and of a quartet block: the trio's layout, then O's quaternion ring (2 x 4 pair slots) and C's cdof ring (2 x 3)
-template <class T> constexpr int quartet_bytes() { return trio_bytes<T>() + 14 * 64 * 16; }
+// ... and of a quartet block: the trio's layout, then O's quaternion ring (2 x 4 pair slots), C's cdof ring (2 x 3) and X's mail slot
+template <class T> constexpr int quartet_bytes() { return trio_bytes<T>() + QUARTET_EXTRA * 64 * 16; }
 template <class T> constexpr int duo2_bytes() { return (Lds<T, (1 << 20)>::nslots() + 12 + DuoSlots<T::NV>::n) * 64 * 16; }
 template <class T, int LP>
 DEVI void lane_env_duo2(const KernelParams MJB_AS4 *__restrict__ P, const int nsteps, const unsigned int step0, const int env_lo, const int env_hi,
