@@ -351,6 +351,15 @@ int mjb_model_lane_env(const mjb_model *m);
  * | the mass of every other body but the world (mjENBL_ENERGY reads it). */
 int mjb_model_lane_env_tape(const mjb_model *m, double *out, int cap);
 int mjb_model_lane_env_overlay(const mjb_model *m, double *out, int cap);
+/* mjb_lane_env_plan: the variant of the kernel the launcher picks ("The lane = env launcher"), as a pure function of its arguments -- the
+ * process's environment variables and the settings of mjb_lane_env_set_form / mjb_lane_env_set_sweep_waves are NOT looked at, no device is touched.
+ * m: the model (its layouts are counted when hiprtc builds its kernel), or NULL for "a compiled-in topology": no fit limit.  ncu: CUs of the device;
+ * nenv: envs of the batch; build: 0 plain, 1 per-env overlay (mjb_set_lane_env mode 2), 2 hwsim stage, 3 xfrc_applied, 4 overlay + xfrc_applied;
+ * form: -1 the rule, 0 .. 3 as mjb_lane_env_set_form; sweep_waves: 0 the rule, 3 / 4 as mjb_lane_env_set_sweep_waves; lds_kb: 0 by batch size,
+ * 40 / 80 / 160 as MJB_LANE_ENV_LDS_KB.  Fills (each may be NULL) the form, form 3's sweep wavefronts (0 otherwise) and the LDS budget in KB, the
+ * values mjb_lane_env_last_form / mjb_lane_env_last_sweep_waves report after such a launch.  Returns 0; -1: the model is not eligible or needs more
+ * LDS than a CU has, or an argument is out of range. */
+int mjb_lane_env_plan(const mjb_model *m, int ncu, int nenv, int build, int form, int sweep_waves, int lds_kb, int *out_form, int *out_sweep_waves, int *out_lds_kb);
 const char *mjb_lane_env_error(void);
 /* The lane = env kernel's FORM, process-wide: how many wavefronts share the 64 envs of a block.  0 = one (the whole step in one instruction stream);
  * 1 = two, the step's position half (poses, cinert, composite inertias, qM, factors, solves, Euler) and velocity half (velocities, forces,

@@ -2994,6 +2994,11 @@ int mjb_model_lane_env_overlay(const mjb_model *m, double *out, int cap)
 	if (out && cap >= n) mjb_lane_env_overlay_row(&m->h, nullptr, nullptr, out);
 	return n;
 }
+int mjb_lane_env_plan(const mjb_model *m, int ncu, int nenv, int build, int form, int sweep_waves, int lds_kb, int *out_form, int *out_sweep_waves, int *out_lds_kb)
+{
+	if (m && m->le_topo == MJB_LE_TOPO_NONE) return -1;
+	return mjb_lane_env_plan_for(m && m->le_topo == MJB_LE_TOPO_JIT ? &m->h : nullptr, ncu, nenv, build, form, sweep_waves, lds_kb, out_form, out_sweep_waves, out_lds_kb);
+}
 int mjb_lane_env_info(const mjb_batch *b, int *used_last)
 {
 	if (used_last) *used_last = b && b->lane_env_used ? 1 : 0;

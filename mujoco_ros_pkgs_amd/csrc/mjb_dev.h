@@ -366,14 +366,18 @@ void mjb_lane_env_tape(const mjb_model_desc *h, double *tape);  // fills it
 const char *mjb_lane_env_name(int topo);
 enum { MJB_LE_TOPO_NONE = -1, MJB_LE_TOPO_JIT = -2, MJB_LE_UNAVAILABLE = -1000 };
 int mjb_lane_env_eligible(const mjb_model_desc *h);   // the model's structure fits the kernel (compiled in or not)
-const char *mjb_lane_env_jit_error(void);
-void mjb_lane_env_jit_stats(int *compiled, int *disk_hits);  // hiprtc builds of this process / builds taken from the disk cache instead              // why the last hiprtc build of a topology was not available ("" if none failed)
+const char *mjb_lane_env_jit_error(void);                    // why the last hiprtc build of a topology was not available ("" if none failed)
+void mjb_lane_env_jit_stats(int *compiled, int *disk_hits);  // hiprtc builds of this process / builds taken from the disk cache instead
 // which build of the kernel a launch runs: the plain one (any form), or one of the two that exist for the solo form only and run it whatever the batch size --
 // the one that reads DevState::le_overlay (template flag PE), the one with the device hwsim stage, KernelParams::hw (template flag HW), and the two
 // that apply xfrc_applied from DevState::le_xfrc (template flag XF), without and with the overlay
 enum LeBuild { MJB_LE_PLAIN = 0, MJB_LE_OVERLAY = 1, MJB_LE_HWSIM = 2, MJB_LE_XFRC = 3, MJB_LE_OVERLAY_XFRC = 4 };
 int mjb_launch_lane_env(const KernelParams *Pdev, int topo, const mjb_model_desc *h, int nenv_batch, int env_lo, int env_hi, int nsteps, unsigned int step0,
                         void *stream, LeBuild build);
+// the launcher's plan with the environment's knobs at their defaults (mjb_lane_env_plan of include/mjb.h; fit_model: the model when hiprtc builds its
+// kernel, NULL for a compiled-in topology); 0, or -1: no variant
+int mjb_lane_env_plan_for(const mjb_model_desc *fit_model, int ncu, int nenv_batch, int build, int form, int sweep_waves, int lds_kb, int *out_form, int *out_sweep,
+                          int *out_lds_kb);
 // the per-env overlay of that kernel: its slot count, and one env's column from the env's gravity and its block of DevState::env_mass (NULL: the model's values)
 int mjb_lane_env_overlay_slots(const mjb_model_desc *h);
 // the wrench table of that kernel's XF builds: its slot count (the model's moving bodies), and the transpose of xfrc_applied [nenv][nbody][6] into

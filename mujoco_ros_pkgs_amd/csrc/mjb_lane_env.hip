@@ -19,6 +19,11 @@
 // gen_lane_env_topo.py, ctrl noise (mujoco_env.cpp:469-481), mj_check* resets, mjENBL_ENERGY.  Arithmetic follows MuJoCo's
 // com-based formulation stage by stage (oracle/mjo_smooth.c); sums over bodies run in ascending instead of leaf-to-root order and
 // reciprocals are Newton-refined hardware seeds, so results agree with the oracle to rounding, not bit for bit (tests/test_gpu_lane_env.py).
+//
+// The host side in this file, in order: which models the kernel takes (mjb_lane_env_match / _eligible); LeVariant and the table of the variants that
+// exist (le_rows); the hiprtc build of a variant for a model without a compiled-in topology (jit_get); the tape, overlay and wrench tables; the PLAN
+// (le_plan: CU count, batch size, build, the knobs' values and, for a hiprtc model, its slot counts -> a LeVariant; pure, DESIGN.md "The lane = env
+// launcher" has the rule and what it reaches by default); and mjb_launch_lane_env, which gathers the plan's inputs, asks it, records and launches.
 #include <hip/hip_runtime.h>
 
 #include <dlfcn.h>
@@ -46,7 +51,7 @@ __global__ void __launch_bounds__(64) mjb_lane_env_kernel(const KernelParams MJB
                                                           const int env_lo, const int env_hi)
 {
 	extern __shared__ __attribute__((aligned(16))) unsigned char smem_le[];
-	lane_env_body<T, LP, 0, PE, HW, XF>(P, nsteps, step0, env_lo, env_hi, smem_le);
+	lane_env_body<T, LP, LE_SOLO, PE, HW, XF>(P, nsteps, step0, env_lo, env_hi, smem_le);
 }
 
 template <class T, int LP>
@@ -106,18 +111,66 @@ template <class T> bool topo_matches(const mjb_model_desc &h)
 
 }  // namespace
 
+// what both classifications below ask first: an unconstrained Euler model of one-dof joints, without mocap bodies, tendons, equalities or activations
+static bool le_plain_tree(const mjb_model_desc *h)
+{
+	return h && h->nefcmax <= 0 && h->nconmax <= 0 && h->integrator == MJB_INT_EULER && h->nmocap <= 0 && h->ntendon <= 0 && h->neq <= 0 && h->na <= 0 &&
+	       h->nq == h->nv && h->njnt == h->nv;
+}
+
 // Index of the compiled-in topology the model has, or -1 (mjb_compile; the generic kernels run every model).
 int mjb_lane_env_match(const mjb_model_desc *h)
 {
-	if (!h || h->nefcmax > 0 || h->nconmax > 0 || h->integrator != MJB_INT_EULER || h->nmocap > 0 || h->ntendon > 0 || h->neq > 0 || h->na > 0 ||
-	    h->nq != h->nv || h->njnt != h->nv)
-		return -1;
+	if (!le_plain_tree(h)) return -1;
 #define MJB_LE_X(id, T) \
 	if (topo_matches<T>(*h)) return id;
 	MJB_LE_TOPOS(MJB_LE_X)
 #undef MJB_LE_X
 	return -1;
 }
+
+// ---- ONE description of a kernel variant: what the plan (le_plan, below) returns; the compiled-in dispatch, the hiprtc source, the in-process cache
+// key, the block size and the LDS bytes all come from it ----
+namespace {
+struct LeVariant {
+	int form;                 // 0 one wavefront per 64 envs, 1 two halves, 2 pipelined, 3 the sweep on three or four wavefronts (include/mjb.h)
+	int sweep;                // form 3: the wavefronts of its root -> leaf sweep, 3 / 4; 0 in every other form
+	int lds_kb;               // the instantiation's LDS budget LP, in pair slots = KB: 40 / 80 / 160 (form 1: 80 / 160; forms 2 and 3: 160)
+	LeBuild build;            // a build other than the plain one exists in form 0 alone
+	int wave_lanes;           // envs per wavefront: 64 (16 / 32: the measurement knob, plain build)
+	const char *unavailable;  // non-null: there is no variant for the request, and why
+};
+// the variants that exist, and what tells them apart everywhere: the template flags of the compiled-in kernel, the tag of the cache key, and the two
+// expressions of the hiprtc source ($ = the budget)
+struct LeRow {
+	int form, sweep;
+	LeBuild build;
+	bool pe, hw, xf;
+	const char *tag, *bytes, *body;
+};
+constexpr LeRow le_rows[] = {
+	{ 0, 0, MJB_LE_PLAIN, false, false, false, "|", "Lds<LeTopo_rt, $>::bytes()", "lane_env_body<LeTopo_rt, $>" },
+	{ 0, 0, MJB_LE_OVERLAY, true, false, false, "e|", "Lds<LeTopo_rt, $>::bytes()", "lane_env_body<LeTopo_rt, $, 0, true>" },
+	{ 0, 0, MJB_LE_HWSIM, false, true, false, "h|", "Lds<LeTopo_rt, $>::bytes()", "lane_env_body<LeTopo_rt, $, 0, false, true>" },
+	{ 0, 0, MJB_LE_XFRC, false, false, true, "x|", "Lds<LeTopo_rt, $>::bytes()", "lane_env_body<LeTopo_rt, $, 0, false, false, true>" },
+	{ 0, 0, MJB_LE_OVERLAY_XFRC, true, false, true, "ex|", "Lds<LeTopo_rt, $>::bytes()", "lane_env_body<LeTopo_rt, $, 0, true, false, true>" },
+	{ 1, 0, MJB_LE_PLAIN, false, false, false, "d|", "duo_bytes<LeTopo_rt, $>()", "lane_env_duo<LeTopo_rt, $>" },
+	{ 2, 0, MJB_LE_PLAIN, false, false, false, "p|", "duo2_bytes<LeTopo_rt>()", "lane_env_duo2<LeTopo_rt, 160>" },
+	{ 3, 3, MJB_LE_PLAIN, false, false, false, "t|", "trio_bytes<LeTopo_rt>()", "lane_env_trio<LeTopo_rt, 160>" },
+	{ 3, 4, MJB_LE_PLAIN, false, false, false, "q|", "quartet_bytes<LeTopo_rt>()", "lane_env_quartet<LeTopo_rt, 160>" },
+};
+constexpr const LeRow *le_row(int form, int sweep, LeBuild build)
+{
+	for (const LeRow &r : le_rows)
+		if (r.form == form && r.sweep == sweep && r.build == build) return &r;
+	return nullptr;
+}
+constexpr int le_block(const LeVariant &v) { return v.form == 3 ? 64 * v.sweep : (v.form ? 128 : v.wave_lanes); }  // threads of a block: 64 envs (form 0: wave_lanes)
+template <class T, int LP> constexpr int le_lds_bytes(int form, int sweep)  // dynamic LDS of the compiled-in kernel
+{
+	return form == 3 ? (sweep == 4 ? quartet_bytes<T>() : trio_bytes<T>()) : (form == 2 ? duo2_bytes<T>() : (form == 1 ? duo_bytes<T, LP>() : Lds<T, LP>::bytes()));
+}
+}  // namespace
 
 // ---- any other eligible model: the same template, compiled for the model's structure by hiprtc at its first fused launch ----
 // (hiprtc is dlopen'ed: libmjb.so does not depend on it.  Whatever goes wrong -- no libhiprtc, the kernel header not next to the
@@ -126,9 +179,7 @@ int mjb_lane_env_match(const mjb_model_desc *h)
 // 1 when the model's structure fits the kernel (what tools/gen_lane_env_topo.py's eligible() accepts), whether or not a topology is compiled in
 int mjb_lane_env_eligible(const mjb_model_desc *h)
 {
-	if (!h || h->nefcmax > 0 || h->nconmax > 0 || h->integrator != MJB_INT_EULER || h->nmocap > 0 || h->ntendon > 0 || h->neq > 0 || h->na > 0 ||
-	    h->nq != h->nv || h->njnt != h->nv || h->nv < 1 || h->nbody > 24 || h->nv > 20)  // (size: ~22 doubles of state per body must fit the register file)
-		return 0;
+	if (!le_plain_tree(h) || h->nv < 1 || h->nbody > 24 || h->nv > 20) return 0;  // (size: ~22 doubles of state per body must fit the register file)
 	for (int j = 0; j < h->njnt; j++)
 		if ((h->jnt_type[j] != MJB_JNT_SLIDE && h->jnt_type[j] != MJB_JNT_HINGE) || h->jnt_qposadr[j] != j || h->jnt_dofadr[j] != j || h->dof_jntid[j] != j) return 0;
 	for (int b = 0; b < h->nbody; b++)
@@ -222,7 +273,7 @@ struct JitKernel {
 	std::string error;  // non-empty: not available, why
 };
 std::mutex jit_mutex;
-std::map<std::string, JitKernel> jit_cache;  // key: device | LDS budget | topology text
+std::map<std::string, JitKernel> jit_cache;  // key: device | LDS budget, the variant's tag (le_rows) | topology text
 std::string jit_last_error;  // guarded by jit_err_mutex; mjb_lane_env_jit_error() hands out a thread-local copy
 std::mutex jit_err_mutex;
 void set_jit_error(const std::string &e)
@@ -302,41 +353,38 @@ bool source_fingerprint(const std::string &dir, unsigned long long &hsh)
 	return true;
 }
 
-const JitKernel &jit_get(const mjb_model_desc &h, int lp, int duo, LeBuild build)  // duo: 0 solo, 1 two halves, 2 pipelined, 3 three wavefronts, 4 four (form 3 with the pose sweep on two); build: the solo form's overlay / hwsim / xfrc builds (mjb_dev.h)
+// the source hiprtc compiles for a variant: the kernel header, the topology, one kernel `le_rt` with the variant's launch bounds, LDS and body
+std::string jit_source(const LeRow &r, const LeVariant &v, const std::string &topo)
 {
+	auto with_budget = [&](std::string t) {
+		const size_t at = t.find('$');
+		return at == std::string::npos ? t : t.replace(at, 1, std::to_string(v.lds_kb));
+	};
+	return "#include \"mjb_lane_env_kernel.h\"\n" + topo + "extern \"C\" __global__ void __launch_bounds__(" + std::to_string(v.form ? le_block(v) : 64) +
+	       ") le_rt(const KernelParams MJB_AS4 *P, int nsteps, unsigned int step0, int lo, int hi)\n{\n"
+	       "\t__shared__ __attribute__((aligned(16))) unsigned char smem[mjb_le::" + with_budget(r.bytes) + "];\n"
+	       "\tmjb_le::" + with_budget(r.body) + "(P, nsteps, step0, lo, hi, smem);\n}\n";
+}
+
+const JitKernel &jit_get(const mjb_model_desc &h, const LeVariant &v)
+{
+	static const JitKernel no_such_variant{ nullptr, nullptr, "no such variant of the kernel" };
+	const LeRow *const row = le_row(v.form, v.sweep, v.build);
+	if (!row) return no_such_variant;  // (never from le_plan)
 	int dev = 0;
 	(void)hipGetDevice(&dev);
 	const std::string topo = topo_source(h);
-	const std::string key = std::to_string(dev) + "|" + std::to_string(lp) + (build == MJB_LE_OVERLAY_XFRC ? "ex|" : build == MJB_LE_XFRC ? "x|" : build == MJB_LE_HWSIM ? "h|" : build == MJB_LE_OVERLAY ? "e|" : duo == 4 ? "q|" : duo == 3 ? "t|" : (duo == 2 ? "p|" : (duo ? "d|" : "|"))) + topo;
+	const std::string key = std::to_string(dev) + "|" + std::to_string(v.lds_kb) + row->tag + topo;
 	std::lock_guard<std::mutex> lock(jit_mutex);
 	auto it = jit_cache.find(key);
 	if (it != jit_cache.end()) return it->second;
 	JitKernel &k = jit_cache[key];
-	static const bool off = [] { const char *v = getenv("MJB_LANE_ENV_JIT"); return v && *v == '0'; }();
+	static const bool off = [] { const char *e = getenv("MJB_LANE_ENV_JIT"); return e && *e == '0'; }();
 	if (off) { k.error = "disabled (MJB_LANE_ENV_JIT=0)"; return k; }
 	RtcApi &r = rtc();
 	if (!r.ok) { k.error = "libhiprtc.so not found"; return k; }
 	const std::string dir = source_dir();
-	const std::string slp = std::to_string(lp);
-	const std::string src = "#include \"mjb_lane_env_kernel.h\"\n" + topo +
-	                        (build != MJB_LE_PLAIN ? "extern \"C\" __global__ void __launch_bounds__(64) le_rt(const KernelParams MJB_AS4 *P, int nsteps, unsigned int step0, int lo, int hi)\n{\n"
-	                              "\t__shared__ __attribute__((aligned(16))) unsigned char smem[mjb_le::Lds<LeTopo_rt, " + slp + ">::bytes()];\n"
-	                              "\tmjb_le::lane_env_body<LeTopo_rt, " + slp + (build == MJB_LE_OVERLAY_XFRC ? ", 0, true, false, true" : build == MJB_LE_XFRC ? ", 0, false, false, true" : build == MJB_LE_HWSIM ? ", 0, false, true" : ", 0, true") + ">(P, nsteps, step0, lo, hi, smem);\n}\n"
-	                         : duo == 4 ? "extern \"C\" __global__ void __launch_bounds__(256) le_rt(const KernelParams MJB_AS4 *P, int nsteps, unsigned int step0, int lo, int hi)\n{\n"
-	                                    "\t__shared__ __attribute__((aligned(16))) unsigned char smem[mjb_le::quartet_bytes<LeTopo_rt>()];\n"
-	                                    "\tmjb_le::lane_env_quartet<LeTopo_rt, 160>(P, nsteps, step0, lo, hi, smem);\n}\n"
-	                         : duo == 3 ? "extern \"C\" __global__ void __launch_bounds__(192) le_rt(const KernelParams MJB_AS4 *P, int nsteps, unsigned int step0, int lo, int hi)\n{\n"
-	                                    "\t__shared__ __attribute__((aligned(16))) unsigned char smem[mjb_le::trio_bytes<LeTopo_rt>()];\n"
-	                                    "\tmjb_le::lane_env_trio<LeTopo_rt, 160>(P, nsteps, step0, lo, hi, smem);\n}\n"
-	                         : duo == 2 ? "extern \"C\" __global__ void __launch_bounds__(128) le_rt(const KernelParams MJB_AS4 *P, int nsteps, unsigned int step0, int lo, int hi)\n{\n"
-	                                    "\t__shared__ __attribute__((aligned(16))) unsigned char smem[mjb_le::duo2_bytes<LeTopo_rt>()];\n"
-	                                    "\tmjb_le::lane_env_duo2<LeTopo_rt, 160>(P, nsteps, step0, lo, hi, smem);\n}\n"
-	                         : duo ? "extern \"C\" __global__ void __launch_bounds__(128) le_rt(const KernelParams MJB_AS4 *P, int nsteps, unsigned int step0, int lo, int hi)\n{\n"
-	                               "\t__shared__ __attribute__((aligned(16))) unsigned char smem[mjb_le::duo_bytes<LeTopo_rt, " + slp + ">()];\n"
-	                               "\tmjb_le::lane_env_duo<LeTopo_rt, " + slp + ">(P, nsteps, step0, lo, hi, smem);\n}\n"
-	                             : "extern \"C\" __global__ void __launch_bounds__(64) le_rt(const KernelParams MJB_AS4 *P, int nsteps, unsigned int step0, int lo, int hi)\n{\n"
-	                               "\t__shared__ __attribute__((aligned(16))) unsigned char smem[mjb_le::Lds<LeTopo_rt, " + slp + ">::bytes()];\n"
-	                               "\tmjb_le::lane_env_body<LeTopo_rt, " + slp + ">(P, nsteps, step0, lo, hi, smem);\n}\n");
+	const std::string src = jit_source(*row, v, topo);
 	// the disk cache first
 	std::string cpath;
 	{
@@ -597,167 +645,175 @@ const char *mjb_lane_env_name(int topo)
 	return "";
 }
 
+// ---- THE PLAN: which variant a launch runs, as a pure function of what it is given -- no environment variable, no atomic, no device is read here
+// (mjb_launch_lane_env gathers them; mjb_lane_env_plan, the introspection entry, and tests/test_lane_env_plan.py call it with values of their own) ----
+namespace {
+struct LePlanIn {
+	int ncu;            // CUs of the device (0: not known -- the leanest budget, one wavefront)
+	int nenv_batch;     // envs of the BATCH, not of the launch's range: the instantiations agree to rounding, not bit for bit (the compiler contracts a few
+	                    // multiply-adds differently around where data waits), so every launch of a batch -- whole, a prefix, the rest of a split step -- runs one
+	LeBuild build;
+	int form;           // -1: by batch size; 0: one wavefront always; 1 / 2 / 3: that form whenever the LDS allows (mjb_lane_env_set_form, else MJB_LANE_ENV_DUO)
+	int duo_max_waves;  // the automatic rule runs more than one wavefront per 64 envs up to this many wavefronts of envs; -1: 2 x CUs (MJB_LANE_ENV_DUO_MAX_WAVES)
+	int sweep;          // form 3's sweep wavefronts, 3 / 4; 0: by batch size (mjb_lane_env_set_sweep_waves, else MJB_LANE_ENV_SWEEP_WAVES)
+	int lds_kb;         // 40 / 80 / 160; anything else: by batch size (MJB_LANE_ENV_LDS_KB)
+	int wave_lanes;     // 16 / 32: envs per wavefront of the plain one-wavefront form; anything else: 64 (MJB_LANE_ENV_WAVE_LANES)
+	bool fit;           // a hiprtc-built model: the layouts are counted for it, and what does not fit a CU's LDS steps down
+	int nv, nmov, nbody;  // ... from these: dofs, moving bodies (mjb_lane_env_xfrc_slots), bodies
+};
+
+LeVariant le_plan(const LePlanIn &in)
+{
+	LeVariant v{ 0, 0, 0, in.build, 64, nullptr };
+	const bool plain = in.build == MJB_LE_PLAIN;
+	if (plain && (in.wave_lanes == 16 || in.wave_lanes == 32)) v.wave_lanes = in.wave_lanes;  // (the overlay, hwsim and xfrc builds always run full wavefronts)
+	// the LDS budget per wavefront from the CUs the batch leaves idle: one wavefront per CU may take all of its LDS, two half of it each
+	const int ncu = in.ncu, waves = (in.nenv_batch + 63) / 64;
+	v.lds_kb = (in.lds_kb == 40 || in.lds_kb == 80 || in.lds_kb == 160) ? in.lds_kb : ((ncu > 0 && waves <= ncu) ? 160 : ((ncu > 0 && waves <= 2 * ncu) ? 80 : 40));
+	// the form: more than one wavefront per 64 envs in the plain build alone
+	if (plain && in.form > 0 && v.lds_kb < 80) {
+		// a forced multi-wavefront form on a batch that would run four wavefronts per CU: the two halves at two per CU
+		v.form = 1;
+		v.lds_kb = 80;
+	} else if (plain && v.wave_lanes == 64 && v.lds_kb >= 80 && in.form != 0 && (in.form > 0 || waves <= (in.duo_max_waves >= 0 ? in.duo_max_waves : 2 * ncu))) {
+		// two wavefronts per 64 envs while the batch leaves at least every second SIMD idle: the step's position half and velocity half side by side ...
+		v.form = 1;
+		// ... pipelined (nothing computed twice) when a workgroup has a CU's LDS to itself; form 1 asked for: the two halves only
+		if (v.lds_kb == 160 && in.form != 1) v.form = 2;
+		// ... and three wavefronts (the pose chain alone on the first) while three SIMDs per block are there: the same LDS layout, so the same bound
+		if (v.form == 2 && in.form != 2 && 3 * waves <= 4 * ncu) v.form = 3;
+		// ... its sweep on four when the block still has a SIMD of its CU to itself per wavefront: the pose wavefront's chain cut in two
+		if (v.form == 3) v.sweep = (in.sweep == 3 || in.sweep == 4) ? in.sweep : (waves <= ncu ? 4 : 3);
+	}  // (otherwise -- the overlay / hwsim / xfrc builds whatever is asked for -- the solo form at that budget)
+	if (!in.fit) return v;
+	// a hiprtc-built model may be larger than the compiled-in ones: the smallest budget its (qpos, qvel) pairs and body forces fit (fewer wavefronts per
+	// CU then), and of the forms the first one down whose layout fits
+	const int state = le_state_slots(in.nv, in.nmov);
+	if (state > LE_MAX_SLOTS) {
+		v.unavailable = "the model needs more than 160 KB of LDS per wavefront";
+		return v;
+	}
+	const int least = state <= 40 ? 40 : (state <= 80 ? 80 : 160);
+	if (least > v.lds_kb) v.lds_kb = least;
+	if (v.sweep == 4 && le_quartet_slots(in.nv, in.nmov, in.nbody) > LE_MAX_SLOTS) v.sweep = 3;
+	if (v.form == 3 && le_trio_slots(in.nv, in.nmov, in.nbody) > LE_MAX_SLOTS) v.form = 2, v.sweep = 0;
+	if (v.form == 2 && le_duo2_slots(in.nv, in.nmov) > LE_MAX_SLOTS) v.form = 1;
+	if (v.form == 1 && state + le_exchange_slots(in.nv) > v.lds_kb) v.form = 0;
+	return v;
+}
+// ---- end of the plan ----
+
+// ---- launching a compiled-in variant: one helper does the launch, a compile-time walk over (topology, build, form, budget) finds the kernel ----
+struct LeLaunch {
+	const KernelParams *Pdev;
+	const mjb_model_desc *h;  // (may be NULL: the overlay / xfrc builds check their slot counts against it)
+	int env_lo, env_hi, nsteps;
+	unsigned int step0;
+	hipStream_t stream;
+	int dev;
+};
+unsigned int le_grid(const LeVariant &v, const LeLaunch &a) { return (unsigned int)((a.env_hi - a.env_lo + v.wave_lanes - 1) / v.wave_lanes); }
+// `ran`: the variant the kernel is, for the record -- the one asked for, or the next one down that the topology's layout fits
+template <class K> int le_go(K kern, int bytes, const LeVariant &ran, const LeLaunch &a)
+{
+	const hipError_t attr = lds_attr_once(reinterpret_cast<const void *>(kern), bytes, a.dev);
+	if (attr != hipSuccess) return (int)attr;
+	le_form_last = ran.form, le_sweep_last = ran.sweep;
+	hipLaunchKernelGGL(kern, dim3(le_grid(ran, a)), dim3((unsigned int)le_block(ran)), bytes, a.stream, (const KernelParams MJB_AS4 *)a.Pdev, a.nsteps, a.step0, a.env_lo,
+	                   a.env_hi);
+	return (int)hipGetLastError();
+}
+template <class T, int LP, LeBuild B> int le_go_solo(const LeVariant &v, const LeLaunch &a)
+{
+	constexpr LeRow r = *le_row(0, 0, B);
+	if (r.pe && (!a.h || PeSlots<T>::n != mjb_lane_env_overlay_slots(a.h))) return (int)hipErrorInvalidValue;
+	if (r.xf && (!a.h || XfSlots<T>::n != mjb_lane_env_xfrc_slots(a.h))) return (int)hipErrorInvalidValue;
+	return le_go(mjb_lane_env_kernel<T, LP, r.pe, r.hw, r.xf>, le_lds_bytes<T, LP>(0, 0), v, a);
+}
+template <class T, LeBuild B> int le_go_build(const LeVariant &v, const LeLaunch &a)  // a build of the solo form, at the budget
+{
+	return v.lds_kb == 160 ? le_go_solo<T, 160, B>(v, a) : (v.lds_kb == 80 ? le_go_solo<T, 80, B>(v, a) : le_go_solo<T, 40, B>(v, a));
+}
+template <class T> int le_go_topo(const LeVariant &v, const LeLaunch &a)
+{
+	switch (v.build) {  // the opt-in builds: the solo form alone
+	case MJB_LE_HWSIM: return le_go_build<T, MJB_LE_HWSIM>(v, a);
+	case MJB_LE_OVERLAY: return le_go_build<T, MJB_LE_OVERLAY>(v, a);
+	case MJB_LE_XFRC: return le_go_build<T, MJB_LE_XFRC>(v, a);
+	case MJB_LE_OVERLAY_XFRC: return le_go_build<T, MJB_LE_OVERLAY_XFRC>(v, a);
+	case MJB_LE_PLAIN: break;
+	}
+	// the plain build: forms 3 and 2 exist at 160 KB alone, form 1 at 160 and 80.  A form whose layout is beyond a CU's LDS for this topology steps
+	// down to the next one, as the plan does for a hiprtc-built model
+	auto as = [&](int form, int sweep) { LeVariant ran = v; ran.form = form, ran.sweep = sweep; return ran; };
+	if constexpr (le_lds_bytes<T, 160>(3, 4) <= mjb_max_lds_bytes())
+		if (v.form == 3 && v.sweep == 4) return le_go(mjb_lane_env_trio_kernel<T, 4>, le_lds_bytes<T, 160>(3, 4), as(3, 4), a);
+	if constexpr (le_lds_bytes<T, 160>(3, 3) <= mjb_max_lds_bytes())
+		if (v.form == 3) return le_go(mjb_lane_env_trio_kernel<T, 3>, le_lds_bytes<T, 160>(3, 3), as(3, 3), a);
+	if constexpr (le_lds_bytes<T, 160>(2, 0) <= mjb_max_lds_bytes())
+		if (v.form >= 2) return le_go(mjb_lane_env_duo2_kernel<T>, le_lds_bytes<T, 160>(2, 0), as(2, 0), a);
+	if (v.form >= 1 && v.lds_kb == 160) return le_go(mjb_lane_env_duo_kernel<T, 160>, le_lds_bytes<T, 160>(1, 0), as(1, 0), a);
+	if (v.form >= 1 && v.lds_kb == 80) return le_go(mjb_lane_env_duo_kernel<T, 80>, le_lds_bytes<T, 80>(1, 0), as(1, 0), a);
+	return le_go_build<T, MJB_LE_PLAIN>(v, a);
+}
+LePlanIn le_plan_in(const mjb_model_desc *fit_model, int ncu, int nenv_batch, LeBuild build, int form, int duo_max_waves, int sweep, int lds_kb, int wave_lanes)
+{
+	LePlanIn in{ ncu, nenv_batch, build, form, duo_max_waves, sweep, lds_kb, wave_lanes, fit_model != nullptr, 0, 0, 0 };
+	if (fit_model) in.nv = fit_model->nv, in.nmov = mjb_lane_env_xfrc_slots(fit_model), in.nbody = fit_model->nbody;
+	return in;
+}
+}  // namespace
+
+// the plan for (device size, batch size, build, requests) with every knob of the environment at its default (include/mjb.h: mjb_lane_env_plan);
+// fit_model: the model when hiprtc builds its kernel, NULL for a compiled-in topology
+int mjb_lane_env_plan_for(const mjb_model_desc *fit_model, int ncu, int nenv_batch, int build, int form, int sweep_waves, int lds_kb, int *out_form, int *out_sweep,
+                          int *out_lds_kb)
+{
+	if (build < MJB_LE_PLAIN || build > MJB_LE_OVERLAY_XFRC || nenv_batch <= 0) return -1;
+	const LeVariant v = le_plan(le_plan_in(fit_model, ncu, nenv_batch, (LeBuild)build, (form >= 0 && form <= 3) ? form : -1, -1, sweep_waves, lds_kb, 64));
+	if (v.unavailable) return -1;
+	if (out_form) *out_form = v.form;
+	if (out_sweep) *out_sweep = v.sweep;
+	if (out_lds_kb) *out_lds_kb = v.lds_kb;
+	return 0;
+}
+
 // topo >= 0: a compiled-in topology; MJB_LE_TOPO_JIT: the model's own, compiled by hiprtc on first use (h = the model; returns
-// MJB_LE_UNAVAILABLE when that is not possible: the caller launches the generic kernel)
+// MJB_LE_UNAVAILABLE when that is not possible: the caller launches the generic kernel).  Gathers the plan's inputs, asks it, launches.
 int mjb_launch_lane_env(const KernelParams *Pdev, int topo, const mjb_model_desc *h, int nenv_batch, int env_lo, int env_hi, int nsteps, unsigned int step0,
                         void *stream, LeBuild build)
 {
-	const int n = env_hi - env_lo;
-	if (n <= 0) return 0;
-	// (measurement knob: envs per wavefront < 64 -- the wavefront starts with its upper lanes off)
+	if (env_hi - env_lo <= 0) return 0;
+	if (topo == MJB_LE_TOPO_JIT && !h) return (int)hipErrorInvalidValue;
+	// the measurement knobs of the environment, read once; the two process-wide requests go first
 	static const int wl_env = mjb_env_int("MJB_LANE_ENV_WAVE_LANES", 64);
-	const int wl = (build == MJB_LE_PLAIN && (wl_env == 16 || wl_env == 32)) ? wl_env : 64;  // (the overlay, hwsim and xfrc builds always run full wavefronts)
-	const dim3 grid((unsigned int)((n + wl - 1) / wl)), block(wl);
-	// LDS budget per wavefront from the CUs the launch leaves idle: one wavefront per CU may take all of its LDS
-	// (per DEVICE: a process may drive several GPUs, one batch each -- ADVICE r05)
-	int cur_dev = 0;
-	(void)hipGetDevice(&cur_dev);
-	const int ncu = device_cus(cur_dev);
-	static const int forced = mjb_env_int("MJB_LANE_ENV_LDS_KB", 0);  // measurement knob: 40 / 80 / 160
-	// (from the BATCH's size, not the launch's env range: the instantiations differ in where data waits, and the compiler contracts a
-	//  few multiply-adds differently around that -- results agree to rounding, not bit for bit -- so every launch of one batch, whole or
-	//  a prefix / the rest of a split step, runs the same one)
-	const int waves = (nenv_batch + 63) / 64;
-	const int lp_batch = (forced == 40 || forced == 80 || forced == 160) ? forced : ((ncu > 0 && waves <= ncu) ? 160 : ((ncu > 0 && waves <= 2 * ncu) ? 80 : 40));
-	int lp = lp_batch;
-	// DUO: two wavefronts per 64 envs (mjb_lane_env_kernel.h) while the batch leaves at least every second SIMD idle -- the step's
-	// position half and velocity half side by side.  MJB_LANE_ENV_DUO=0 / 1: never / whenever the LDS budget allows (measurement knob)
+	static const int lds_env = mjb_env_int("MJB_LANE_ENV_LDS_KB", 0);
 	static const int duo_env = mjb_env_int("MJB_LANE_ENV_DUO", -1);
-	const int form_ov = le_form_override.load();
-	const int duo_mode = form_ov >= 0 ? form_ov : duo_env;
 	static const int duo_max_waves = mjb_env_int("MJB_LANE_ENV_DUO_MAX_WAVES", -1);
-	int duo = (wl == 64 && lp >= 80 && duo_mode != 0 && (duo_mode > 0 || waves <= (duo_max_waves >= 0 ? duo_max_waves : 2 * ncu))) ? 1 : 0;
-	// ... pipelined (nothing computed twice) when a workgroup has a CU's LDS to itself.  MJB_LANE_ENV_DUO=1: the two-halves form only
-	if (duo && lp == 160 && duo_mode != 1) duo = 2;
-	// ... and THREE wavefronts (the pose chain alone on the first) while three SIMDs per block are there: the same LDS layout, so the same bound
-	if (duo == 2 && duo_mode != 2 && 3 * waves <= 4 * ncu) duo = 3;
-	// ... FOUR when the block still has a SIMD of its CU to itself per wavefront: the pose wavefront's chain cut in two (mjb_lane_env_kernel.h, roles 8 - 11).
-	// MJB_LANE_ENV_SWEEP_WAVES=3 / 4: the measurement knob (mjb_lane_env_set_sweep_waves goes first)
-	static const int sweep_knob = mjb_env_int("MJB_LANE_ENV_SWEEP_WAVES", 0);
-	const int sweep_env = (sweep_knob == 3 || sweep_knob == 4) ? sweep_knob : 0;
-	const int sweep_set = le_sweep_override.load();
-	const int sweep_ov = sweep_set ? sweep_set : sweep_env;
-	int sweep = duo == 3 ? (sweep_ov ? sweep_ov : (waves <= ncu ? 4 : 3)) : 0;
-	if (duo_mode > 0 && lp < 80) lp = 80, duo = 1;  // (a forced two-wavefront form on a batch that would run four wavefronts per CU: two per CU)
-	if (build != MJB_LE_PLAIN) {  // per-env overrides / the hwsim stage / xfrc_applied: the solo form at the budget the batch's size (or the knob) gives, whatever form is asked for
-		lp = lp_batch;
-		duo = 0, sweep = 0;
+	static const int sweep_env = mjb_env_int("MJB_LANE_ENV_SWEEP_WAVES", 0);
+	const int form_ov = le_form_override.load(), sweep_ov = le_sweep_override.load();
+	LeLaunch a{ Pdev, h, env_lo, env_hi, nsteps, step0, (hipStream_t)stream, 0 };
+	(void)hipGetDevice(&a.dev);  // (the CU count per DEVICE: a process may drive several GPUs, one batch each -- ADVICE r05)
+	const LeVariant v = le_plan(le_plan_in(topo == MJB_LE_TOPO_JIT ? h : nullptr, device_cus(a.dev), nenv_batch, build, form_ov >= 0 ? form_ov : duo_env, duo_max_waves,
+	                                       sweep_ov ? sweep_ov : sweep_env, lds_env, wl_env));
+	if (v.unavailable) {
+		set_jit_error(v.unavailable);
+		return MJB_LE_UNAVAILABLE;
 	}
 	if (topo == MJB_LE_TOPO_JIT) {
-		if (!h) return (int)hipErrorInvalidValue;
-		{  // a larger model than the compiled-in ones: the smallest LDS budget its (qpos, qvel) pairs and body forces fit (fewer wavefronts per CU then)
-			int need = h->nv;
-			for (int b = 1; b < h->nbody; b++) {
-				bool moves = false;
-				for (int a = b; a > 0; a = h->body_parentid[a]) moves = moves || h->body_jntnum[a] > 0;
-				if (moves) need += 3;
-			}
-			const int fit = need <= 40 ? 40 : (need <= 80 ? 80 : 160);
-			if (need > 160) {
-				set_jit_error("the model needs more than 160 KB of LDS per wavefront");
-				return MJB_LE_UNAVAILABLE;
-			}
-			if (fit > lp) lp = fit;
-			if (sweep == 4 && need + 5 * ((need - h->nv) / 3) + 18 + (h->nv + 1) / 2 + 1 + h->nbody + mjb_le::QUARTET_EXTRA > 160) sweep = 3;  // (the quartet's two rings and X's mail slot behind the trio's layout: quartet_bytes<T>())
-			if (duo == 3 && need + 5 * ((need - h->nv) / 3) + 18 + (h->nv + 1) / 2 + 1 + h->nbody > 160) duo = 2;
-			if (duo != 3) sweep = 0;
-			if (duo == 2 && need + 5 * ((need - h->nv) / 3) + 12 + (h->nv + 1) / 2 + 1 > 160) duo = 1;
-			if (duo == 1 && need + (h->nv + 1) / 2 + 1 > lp) duo = 0;
-		}
-		const JitKernel &k = jit_get(*h, lp, sweep == 4 ? 4 : duo, build);
+		const JitKernel &k = jit_get(*h, v);
 		if (!k.fn) {
 			set_jit_error(k.error);
 			return MJB_LE_UNAVAILABLE;
 		}
 		const KernelParams MJB_AS4 *Pd = (const KernelParams MJB_AS4 *)Pdev;
-		int a_nsteps = nsteps, a_lo = env_lo, a_hi = env_hi;
-		unsigned int a_step0 = step0;
-		void *args[] = { (void *)&Pd, (void *)&a_nsteps, (void *)&a_step0, (void *)&a_lo, (void *)&a_hi };
-		le_form_last = duo;
-		le_sweep_last = sweep;
-		return (int)hipModuleLaunchKernel(k.fn, grid.x, 1, 1, duo == 3 ? 64 * sweep : (duo ? 128 : block.x), 1, 1, 0, (hipStream_t)stream, args, nullptr);
+		void *args[] = { (void *)&Pd, (void *)&a.nsteps, (void *)&a.step0, (void *)&a.env_lo, (void *)&a.env_hi };
+		le_form_last = v.form, le_sweep_last = v.sweep;
+		return (int)hipModuleLaunchKernel(k.fn, le_grid(v, a), 1, 1, (unsigned int)le_block(v), 1, 1, 0, a.stream, args, nullptr);  // (the kernel's LDS is static)
 	}
-#define MJB_LE_GO(T, LPV)                                                                                                                    \
-	{                                                                                                                                         \
-		auto kern = mjb_lane_env_kernel<T, LPV>;                                                                                              \
-		constexpr int bytes = Lds<T, LPV>::bytes();                                                                                           \
-		const hipError_t attr = lds_attr_once(reinterpret_cast<const void *>(kern), bytes, cur_dev);                                          \
-		if (attr != hipSuccess) return (int)attr;                                                                                             \
-		le_form_last = 0, le_sweep_last = 0;                                                                                                  \
-		hipLaunchKernelGGL(kern, grid, block, bytes, (hipStream_t)stream, (const KernelParams MJB_AS4 *)Pdev, nsteps, step0, env_lo, env_hi); \
-		return (int)hipGetLastError();                                                                                                        \
-	}
-#define MJB_LE_GO_SOLO(T, LPV, PEV, HWV, XFV)                                                                                                \
-	{                                                                                                                                         \
-		auto kern = mjb_lane_env_kernel<T, LPV, PEV, HWV, XFV>;                                                                               \
-		constexpr int bytes = Lds<T, LPV>::bytes();                                                                                           \
-		if (PEV && (!h || PeSlots<T>::n != mjb_lane_env_overlay_slots(h))) return (int)hipErrorInvalidValue;                                  \
-		if (XFV && (!h || XfSlots<T>::n != mjb_lane_env_xfrc_slots(h))) return (int)hipErrorInvalidValue;                                     \
-		const hipError_t attr = lds_attr_once(reinterpret_cast<const void *>(kern), bytes, cur_dev);                                          \
-		if (attr != hipSuccess) return (int)attr;                                                                                             \
-		le_form_last = 0, le_sweep_last = 0;                                                                                                  \
-		hipLaunchKernelGGL(kern, grid, block, bytes, (hipStream_t)stream, (const KernelParams MJB_AS4 *)Pdev, nsteps, step0, env_lo, env_hi); \
-		return (int)hipGetLastError();                                                                                                        \
-	}
-#define MJB_LE_GO_DUO(T, LPV)                                                                                                                \
-	{                                                                                                                                         \
-		auto kern = mjb_lane_env_duo_kernel<T, LPV>;                                                                                          \
-		constexpr int bytes = duo_bytes<T, LPV>();                                                                                            \
-		const hipError_t attr = lds_attr_once(reinterpret_cast<const void *>(kern), bytes, cur_dev);                                          \
-		if (attr != hipSuccess) return (int)attr;                                                                                             \
-		le_form_last = 1, le_sweep_last = 0;                                                                                                  \
-		hipLaunchKernelGGL(kern, grid, dim3(128), bytes, (hipStream_t)stream, (const KernelParams MJB_AS4 *)Pdev, nsteps, step0, env_lo, env_hi); \
-		return (int)hipGetLastError();                                                                                                        \
-	}
-#define MJB_LE_GO_DUO2(T)                                                                                                                   \
-	if constexpr (duo2_bytes<T>() <= mjb_max_lds_bytes()) {                                                                                            \
-		auto kern = mjb_lane_env_duo2_kernel<T>;                                                                                              \
-		constexpr int bytes = duo2_bytes<T>();                                                                                                \
-		const hipError_t attr = lds_attr_once(reinterpret_cast<const void *>(kern), bytes, cur_dev);                                          \
-		if (attr != hipSuccess) return (int)attr;                                                                                             \
-		le_form_last = 2, le_sweep_last = 0;                                                                                                  \
-		hipLaunchKernelGGL(kern, grid, dim3(128), bytes, (hipStream_t)stream, (const KernelParams MJB_AS4 *)Pdev, nsteps, step0, env_lo, env_hi); \
-		return (int)hipGetLastError();                                                                                                        \
-	}
-#define MJB_LE_GO_TRIO(T, NW)                                                                                                               \
-	if constexpr ((NW == 4 ? quartet_bytes<T>() : trio_bytes<T>()) <= mjb_max_lds_bytes()) {                                                           \
-		auto kern = mjb_lane_env_trio_kernel<T, NW>;                                                                                          \
-		constexpr int bytes = NW == 4 ? quartet_bytes<T>() : trio_bytes<T>();                                                                 \
-		const hipError_t attr = lds_attr_once(reinterpret_cast<const void *>(kern), bytes, cur_dev);                                          \
-		if (attr != hipSuccess) return (int)attr;                                                                                             \
-		le_form_last = 3, le_sweep_last = NW;                                                                                                 \
-		hipLaunchKernelGGL(kern, grid, dim3(64 * NW), bytes, (hipStream_t)stream, (const KernelParams MJB_AS4 *)Pdev, nsteps, step0, env_lo, env_hi); \
-		return (int)hipGetLastError();                                                                                                        \
-	}
-#define MJB_LE_X(id, T)                      \
-	if (topo == id) {                        \
-		if (build == MJB_LE_HWSIM && lp == 160) MJB_LE_GO_SOLO(T, 160, false, true, false)  \
-		if (build == MJB_LE_HWSIM && lp == 80) MJB_LE_GO_SOLO(T, 80, false, true, false)    \
-		if (build == MJB_LE_HWSIM) MJB_LE_GO_SOLO(T, 40, false, true, false)                \
-		if (build == MJB_LE_OVERLAY && lp == 160) MJB_LE_GO_SOLO(T, 160, true, false, false) \
-		if (build == MJB_LE_OVERLAY && lp == 80) MJB_LE_GO_SOLO(T, 80, true, false, false)   \
-		if (build == MJB_LE_OVERLAY) MJB_LE_GO_SOLO(T, 40, true, false, false)               \
-		if (build == MJB_LE_XFRC && lp == 160) MJB_LE_GO_SOLO(T, 160, false, false, true)   \
-		if (build == MJB_LE_XFRC && lp == 80) MJB_LE_GO_SOLO(T, 80, false, false, true)     \
-		if (build == MJB_LE_XFRC) MJB_LE_GO_SOLO(T, 40, false, false, true)                 \
-		if (build == MJB_LE_OVERLAY_XFRC && lp == 160) MJB_LE_GO_SOLO(T, 160, true, false, true) \
-		if (build == MJB_LE_OVERLAY_XFRC && lp == 80) MJB_LE_GO_SOLO(T, 80, true, false, true)   \
-		if (build == MJB_LE_OVERLAY_XFRC) MJB_LE_GO_SOLO(T, 40, true, false, true)               \
-		if (duo == 3 && sweep == 4) MJB_LE_GO_TRIO(T, 4) \
-		if (duo == 3) MJB_LE_GO_TRIO(T, 3)   \
-		if (duo >= 2) MJB_LE_GO_DUO2(T)      \
-		if (duo && lp == 160) MJB_LE_GO_DUO(T, 160) \
-		if (duo && lp == 80) MJB_LE_GO_DUO(T, 80)   \
-		if (lp == 160) MJB_LE_GO(T, 160)     \
-		if (lp == 80) MJB_LE_GO(T, 80)       \
-		MJB_LE_GO(T, 40)                     \
-	}
+#define MJB_LE_X(id, T) \
+	if (topo == id) return le_go_topo<T>(v, a);
 	MJB_LE_TOPOS(MJB_LE_X)
 #undef MJB_LE_X
-#undef MJB_LE_GO
-#undef MJB_LE_GO_SOLO
-#undef MJB_LE_GO_DUO
-#undef MJB_LE_GO_DUO2
-#undef MJB_LE_GO_TRIO
 	return (int)hipErrorInvalidValue;
 }

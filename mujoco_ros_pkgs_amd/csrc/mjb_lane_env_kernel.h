@@ -206,6 +206,30 @@ DEVI double angdist_with_limits_nb(double from, double to, double left, double r
 // overflow space next to its registers.  LP = 40 pair slots (40 KB) when four wavefronts share a CU, 80 / 160 when the batch leaves
 // a CU to two / one (the launcher picks): what does not fit stays in registers, i.e. mostly in their AGPR half, at four moves per
 // double and round trip against one LDS instruction per PAIR and direction.
+// ---- the LDS layouts of every form, counted ONCE, in pair slots, from plain integers: nv, nmov = the bodies whose force the backward sweep reads
+// (Lds<>::needed), nbody, and a budget.  The kernel's offsets and the *_bytes<T>() of the compiled-in topologies below are written with these; the
+// launcher's fit test for hiprtc-built models (le_plan, mjb_lane_env.hip) calls them with the model's counts.  A slot is one KB: budgets are in both.
+constexpr int LE_SLOT_BYTES = 64 * 16;
+constexpr int LE_MAX_SLOTS = mjb_max_lds_bytes() / LE_SLOT_BYTES;  // a CU's LDS
+constexpr int RING_DUO2 = 2, RING_TRIO = 3;  // depth of the pose ring: the pipelined duo's V reads one body behind P, the trio's (and quartet's) two
+constexpr int le_ring_slots(int depth) { return 6 * depth; }  // (xpos, xmat) of a body: 12 doubles
+// pair slots of a quartet block behind the trio's layout: O's quaternion ring (2 x 4), C's cdof ring (2 x 3), X's mail slot
+constexpr int QUARTET_EXTRA = 15;
+constexpr int le_state_slots(int nv, int nmov) { return nv + 3 * nmov; }  // (qpos, qvel) pairs + cfrc_body: what every form must hold
+constexpr int le_solo_slots(int nv, int nmov, int budget)                 // ... + five of cinert per body while the budget lasts
+{
+	int at = le_state_slots(nv, nmov);
+	for (int k = 0; k < nmov; k++)
+		if (at + 5 <= budget) at += 5;
+	return at;
+}
+constexpr int le_full_slots(int nv, int nmov) { return le_state_slots(nv, nmov) + 5 * nmov; }  // ... of every body (the pipelined forms)
+constexpr int le_exchange_slots(int nv) { return (nv + 1) / 2 + 1; }                           // qfrc_smooth pairs + the mail slot
+constexpr int le_duo_slots(int nv, int nmov, int budget) { return le_solo_slots(nv, nmov, budget - le_exchange_slots(nv)) + le_exchange_slots(nv); }
+constexpr int le_duo2_slots(int nv, int nmov) { return le_full_slots(nv, nmov) + le_ring_slots(RING_DUO2) + le_exchange_slots(nv); }
+constexpr int le_trio_slots(int nv, int nmov, int nbody) { return le_full_slots(nv, nmov) + le_ring_slots(RING_TRIO) + le_exchange_slots(nv) + nbody; }  // (+ a (sin, cos) slot per body)
+constexpr int le_quartet_slots(int nv, int nmov, int nbody) { return le_trio_slots(nv, nmov, nbody) + QUARTET_EXTRA; }
+
 template <class T, int LP> struct Lds {
 	using Q = Tq<T>;
 	// the body's cfrc is consumed by the backward sweep (it, or an ancestor, carries a joint)
@@ -233,14 +257,9 @@ template <class T, int LP> struct Lds {
 		}
 		return -1;
 	}
-	static constexpr int nslots()
-	{
-		int at = slot(T::NBODY);
-		for (int a = T::NBODY - 1; a >= 1; a--)
-			if (needed(a) && at + 5 <= LP) at += 5;
-		return at;
-	}
-	static constexpr int bytes() { return nslots() * 64 * 16; }
+	static constexpr int nmov() { return (slot(T::NBODY) - T::NV) / 3; }  // the needed bodies
+	static constexpr int nslots() { return le_solo_slots(T::NV, nmov(), LP); }
+	static constexpr int bytes() { return nslots() * LE_SLOT_BYTES; }
 };
 
 struct alignas(16) Pair { double a, b; };
@@ -270,19 +289,52 @@ template <class T> struct XfSlots {
 	static constexpr int n = PeSlots<T>::nmb(T::NBODY);
 };
 
-// ROLE: 0 = one wavefront runs the whole step of its 64 envs.  1 / 2 = the DUO form, two wavefronts of one workgroup (on two SIMDs of a CU) share
-// the 64 envs of the block: the step's two independent halves -- what depends on qpos alone (poses, cinert, composite inertias, qM, both factors:
-// role 1, "P") and what depends on qvel too (velocities, the bodies' forces, the force block, qfrc_smooth: role 2, "V") -- run side by side, V hands
-// qfrc_smooth over through LDS, P solves and integrates, and hands the new state (which lives in LDS anyway) and the mj_check* verdicts back.  Both
-// compute the poses, cdof and cinert (the shared prefix).  A lone wavefront issues one instruction every ~4 cycles whatever it is, so the step's
-// length is its instruction count: ~6.2 k in one piece, ~max(P, V) + solve + Euler in two.  Pays while the batch leaves SIMDs idle (the launcher).
+// ROLE of a wavefront (lane_env_body's template argument, an int with these values): which part of the step of its block's 64 envs it runs.
+enum LeRole : int {
+	// one wavefront runs the whole step of its 64 envs
+	LE_SOLO = 0,
+	// the DUO form, two wavefronts of one workgroup (on two SIMDs of a CU) share the 64 envs of the block: the step's two independent halves -- what
+	// depends on qpos alone (poses, cinert, composite inertias, qM, both factors: "P") and what depends on qvel too (velocities, the bodies' forces, the
+	// force block, qfrc_smooth: "V") -- run side by side, V hands qfrc_smooth over through LDS, P solves and integrates, and hands the new state (which
+	// lives in LDS anyway) and the mj_check* verdicts back.  Both compute the poses, cdof and cinert (the shared prefix).  A lone wavefront issues one
+	// instruction every ~4 cycles whatever it is, so the step's length is its instruction count: ~6.2 k in one piece, ~max(P, V) + solve + Euler in
+	// two.  Pays while the batch leaves SIMDs idle (the launcher).
+	LE_DUO_P = 1,
+	LE_DUO_V = 2,
+	// the PIPELINED duo: P computes every pose and cinert ONCE and passes them on body by body -- a workgroup barrier per body, a two-deep ring of
+	// (xpos, xmat) in LDS -- V follows one body behind with cdof, velocities and forces and passes cdof back for P's composite-inertia sweep.  Nothing
+	// is computed twice; needs every needed body's cinert and cdof in LDS: duo2_bytes<T>().
+	LE_PIPE_P = 3,
+	LE_PIPE_V = 4,
+	// the TRIO, three wavefronts per 64 envs: P runs the pose chain and nothing else; C follows it through the ring with cinert and cdof, then takes
+	// the composite-inertia sweep, qM, both factors, the solves and Euler; V as the pipelined V, with its own cinert of every body.  P's sweep is the
+	// step's critical chain: everything that is not a pose is off it.
+	LE_TRIO_P = 5,
+	LE_TRIO_C = 6,
+	LE_TRIO_V = 7,
+	// the QUARTET, the trio with its pose wavefront cut in two, on the CU's fourth SIMD: O runs the ORIENTATION chain and nothing else -- xquat[b] =
+	// normalize(xquat[p] body_quat hinge_quat), the one part of a pose the next body's waits for -- with every hinge's half-angle sine and cosine one
+	// body ahead, and passes the unit quaternion on through a two-deep ring; X follows one body behind: rotation matrix, the position chain, inertial
+	// frame, mj_energyPos, frame sensors, the pose ring; C as the trio's C one body behind X, without the sines, and it publishes cdof; V as the trio's V
+	// one body behind C, with C's cdof instead of its own.  One barrier per MOVING body plus two to drain: sweep phase k has O on the k-th moving body,
+	// X on the one before, C two and V three before; the bodies at rest are O's and X's own business ahead of the phases.
+	// The quartet's tail is split by MATRIX: X keeps its own cdof, reads C's cinert from LDS behind the sweep's last barrier, builds qM a second time
+	// beside C, factors M, solves qacc = M^-1 f and takes mj_checkAcc's decision; C factors M + h B alone, solves the acceleration Euler advances with
+	// and integrates SPECULATIVELY -- X's verdict, read by all four behind rendezvous B, either lets the step stand or has C put the old state back.
+	// Nothing but V's qfrc_smooth and the two mail slots crosses LDS, and the step has no barrier the trio's tail does not have.
+	LE_QUAD_O = 8,
+	LE_QUAD_X = 9,
+	LE_QUAD_C = 10,
+	LE_QUAD_V = 11,
+};
+constexpr bool le_two_halves(int role) { return role == LE_DUO_P || role == LE_DUO_V; }
+constexpr bool le_pipelined_duo(int role) { return role == LE_PIPE_P || role == LE_PIPE_V; }
+constexpr bool le_trio(int role) { return role == LE_TRIO_P || role == LE_TRIO_C || role == LE_TRIO_V; }
+constexpr bool le_quartet(int role) { return role == LE_QUAD_O || role == LE_QUAD_X || role == LE_QUAD_C || role == LE_QUAD_V; }
 // rendezvous of a DUO block's two wavefronts: LDS traffic done, then the barrier.  (__syncthreads() also waits for the wavefront's outstanding GLOBAL
 // loads -- V's ctrl-noise normals and qfrc_applied are fetched a sweep ahead of their use precisely so that nobody waits for HBM)
 DEVI void le_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-template <int NV> struct DuoSlots { static constexpr int n = (NV + 1) / 2 + 1; };  // qfrc_smooth pairs + the mail slot
-// pair slots of a quartet block behind the trio's layout: O's quaternion ring (2 x 4), C's cdof ring (2 x 3), X's mail slot.  quartet_bytes<T>() below and the
-// launcher's fit test for hiprtc-built models (mjb_lane_env.hip) both count with it
-constexpr int QUARTET_EXTRA = 15;
+template <int NV> struct DuoSlots { static constexpr int n = le_exchange_slots(NV); };  // qfrc_smooth pairs + the mail slot
 // PE: the batch carries per-env overrides (mjb_set_lane_env mode 2): gravity, the joint constants, masses / inertias and the actuator gains come
 // per lane from DevState::le_overlay instead of the tape (solo form only).
 // HW: the batch has a device hwsim stage (KernelParams::hw, mjb_lane_env_set_hwsim): DefaultRobotHWSim::writeSim runs per lane where the forces are
@@ -300,41 +352,29 @@ constexpr int QUARTET_EXTRA = 15;
 // (XfSlots), coalesced, one region ahead of its use.  mj_resetData zeroes xfrc_applied: a lane reset inside the launch reads zero from then on
 // (the retry after a mj_checkAcc reset included), and at the launch's end its rows of xfrc_applied and its column of the table are zeroed in HBM.
 // Solo form only; composes with PE, not with HW.
-template <class T, int LP, int ROLE = 0, bool PE = false, bool HW = false, bool XF = false>
+template <class T, int LP, int ROLE = LE_SOLO, bool PE = false, bool HW = false, bool XF = false>
 DEVI void lane_env_body(const KernelParams MJB_AS4 *__restrict__ P, const int nsteps, const unsigned int step0, const int env_lo, const int env_hi,
                         unsigned char *const smem_le)
 {
 	constexpr int NB = T::NBODY, NV = T::NV, NU = T::NU;
-	// (roles 3 / 4 = the PIPELINED duo: P computes every pose and cinert ONCE and passes them on body by body -- a workgroup barrier per body, a
-	//  two-deep ring of (xpos, xmat) in LDS -- V follows one body behind with cdof, velocities and forces and passes cdof back for P's composite-inertia
-	//  sweep.  Nothing is computed twice; needs every needed body's cinert and cdof in LDS: Duo2<T>.)
-	// (roles 5 / 6 / 7 = the TRIO, three wavefronts per 64 envs: 5 = P runs the pose chain and nothing else; 6 = C follows it through the ring with cinert
-	//  and cdof, then takes the composite-inertia sweep, qM, both factors, the solves and Euler; 7 = V as role 4, with its own cinert of every body.
-	//  P's sweep is the step's critical chain: everything that is not a pose is off it.)
-	// (roles 8 / 9 / 10 / 11 = the QUARTET, the trio with its pose wavefront cut in two, on the CU's fourth SIMD: 8 = O runs the ORIENTATION chain and nothing
-	//  else -- xquat[b] = normalize(xquat[p] body_quat hinge_quat), the one part of a pose the next body's waits for -- with every hinge's half-angle sine and
-	//  cosine one body ahead, and passes the unit quaternion on through a two-deep ring; 9 = X follows one body behind: rotation matrix, the position chain,
-	//  inertial frame, mj_energyPos, frame sensors, the pose ring; 10 = C as role 6 one body behind X, without the sines, and it publishes cdof; 11 = V as
-	//  role 7 one body behind C, with C's cdof instead of its own.  One barrier per MOVING body plus two to drain: sweep phase k has O on the k-th moving
-	//  body, X on the one before, C two and V three before; the bodies at rest are O's and X's own business ahead of the phases.)
-	constexpr bool QUAD = ROLE >= 8;
-	constexpr bool DP = ROLE == 0 || ROLE == 1 || ROLE == 3 || ROLE == 6 || ROLE == 10, DV = ROLE == 0 || ROLE == 2 || ROLE == 4 || ROLE == 7 || ROLE == 11, DUO = ROLE != 0;  // this wavefront does the position half (inertias, factors, solves, Euler) / the velocity half
-	constexpr bool PIPE = ROLE >= 3;
-	constexpr bool POSE = ROLE <= 3 || ROLE == 5, RINGC = ROLE == 4 || ROLE == 6 || ROLE == 7;  // computes the poses / takes them from the ring (the quartet's roles have a sweep of their own below)
-	constexpr bool VLDS = ROLE == 7 || ROLE == 11;  // V of three / four wavefronts: cinert from C through LDS
-	constexpr bool EPOS = ROLE == 0 || ROLE == 1 || ROLE == 3 || ROLE == 5 || ROLE == 9;                     // gathers mj_energyPos along its pose sweep
-	constexpr bool SENSF = ROLE == 0 || ROLE == 2 || ROLE == 3 || ROLE == 5 || ROLE == 9;  // frame sensors: who holds the poses (and, of two, who has the time)
-	// (the quartet's tail is split by MATRIX: X keeps its own cdof, reads C's cinert from LDS behind the sweep's last barrier, builds qM a second time beside C,
-	//  factors M, solves qacc = M^-1 f and takes mj_checkAcc's decision; C factors M + h B alone, solves the acceleration Euler advances with and integrates
-	//  SPECULATIVELY -- X's verdict, read by all four behind rendezvous B, either lets the step stand or has C put the old state back.  Nothing but V's
-	//  qfrc_smooth and the two mail slots crosses LDS, and the step has no barrier the trio's tail does not have.)
-	[[maybe_unused]] constexpr bool XW = ROLE == 9;               // X of four wavefronts: the walk's position half, the M factor, the qacc solve, mj_checkAcc
+	// ---- what this wavefront does, from its role: the one place a role is looked at by group
+	constexpr bool QUAD = le_quartet(ROLE), TRIQ = le_trio(ROLE) || QUAD;  // of four wavefronts / of three or four
+	constexpr bool HALVES = ROLE == LE_SOLO || le_two_halves(ROLE);         // computes every pose and cinert itself: solo, or either half of the two-halves duo
+	constexpr bool DP = ROLE == LE_SOLO || ROLE == LE_DUO_P || ROLE == LE_PIPE_P || ROLE == LE_TRIO_C || ROLE == LE_QUAD_C, DV = ROLE == LE_SOLO || ROLE == LE_DUO_V || ROLE == LE_PIPE_V || ROLE == LE_TRIO_V || ROLE == LE_QUAD_V, DUO = ROLE != LE_SOLO;  // this wavefront does the position half (inertias, factors, solves, Euler) / the velocity half
+	constexpr bool PIPE = le_pipelined_duo(ROLE) || TRIQ;  // bodies pass between wavefronts through the pose ring
+	constexpr bool POSE = HALVES || ROLE == LE_PIPE_P || ROLE == LE_TRIO_P, RINGC = ROLE == LE_PIPE_V || ROLE == LE_TRIO_C || ROLE == LE_TRIO_V;  // computes the poses / takes them from the ring (the quartet's roles have a sweep of their own below)
+	constexpr bool VLDS = ROLE == LE_TRIO_V || ROLE == LE_QUAD_V;  // V of three / four wavefronts: cinert from C through LDS
+	constexpr bool EPOS = ROLE == LE_SOLO || ROLE == LE_DUO_P || ROLE == LE_PIPE_P || ROLE == LE_TRIO_P || ROLE == LE_QUAD_X;                     // gathers mj_energyPos along its pose sweep
+	constexpr bool SENSF = ROLE == LE_SOLO || ROLE == LE_DUO_V || ROLE == LE_PIPE_P || ROLE == LE_TRIO_P || ROLE == LE_QUAD_X;  // frame sensors: who holds the poses (and, of two, who has the time)
+	[[maybe_unused]] constexpr bool XW = ROLE == LE_QUAD_X;               // X of four wavefronts: the walk's position half, the M factor, the qacc solve, mj_checkAcc
 	[[maybe_unused]] constexpr bool DPW = DP || XW;               // runs the position half of the leaf -> root walk
-	[[maybe_unused]] constexpr bool FM = ROLE != 10, FH = !XW;    // factors and solves with M / with M + h B
+	[[maybe_unused]] constexpr bool FM = ROLE != LE_QUAD_C, FH = !XW;    // factors and solves with M (and so holds qacc) / with M + h B
+	[[maybe_unused]] constexpr bool POSEW = ROLE == LE_TRIO_P || ROLE == LE_QUAD_X;  // the pose wavefront of three / four: mj_energyPos is its only result past the sweep
+	[[maybe_unused]] constexpr bool OWNCIN = ROLE != LE_TRIO_V;                     // a ring consumer that computes the cinert of the body it takes (the trio's V takes C's, one phase later)
 	using Q = Tq<T>;
-	static_assert(!PE || ROLE == 0, "lane = env kernel: per-env overrides run the solo form");
-	static_assert(!HW || (ROLE == 0 && !PE), "lane = env kernel: the hwsim stage runs the solo form, without per-env overrides");
-	static_assert(!XF || (ROLE == 0 && !HW), "lane = env kernel: xfrc_applied runs the solo form, without the hwsim stage");
+	static_assert(!PE || ROLE == LE_SOLO, "lane = env kernel: per-env overrides run the solo form");
+	static_assert(!HW || (ROLE == LE_SOLO && !PE), "lane = env kernel: the hwsim stage runs the solo form, without per-env overrides");
+	static_assert(!XF || (ROLE == LE_SOLO && !HW), "lane = env kernel: xfrc_applied runs the solo form, without the hwsim stage");
 	using OV = PeSlots<T>;
 	using XS6 = XfSlots<T>;
 	constexpr int LPE = PIPE ? (1 << 20) : (DUO ? LP - DuoSlots<NV>::n : LP);
@@ -346,13 +386,13 @@ DEVI void lane_env_body(const KernelParams MJB_AS4 *__restrict__ P, const int ns
 		if (T::jnt_type[T::body_jnt[b]] != MJB_JNT_HINGE) return false;
 		return LD::needed(b) && LD::needed(b - 1) && LD::needed(b - 2);
 	};
-	constexpr int RINGN = ROLE >= 5 ? 3 : 2;  // depth of the pose ring (the trio's V reads two bodies behind P)
+	constexpr int RINGN = TRIQ ? RING_TRIO : RING_DUO2;  // depth of the pose ring (the trio's V reads two bodies behind P)
 	constexpr int LASTB = [] { for (int c = NB - 1; c >= 1; c--) if (LD::needed(c)) return c; return 0; }();  // the leaf the composite-inertia sweep starts at
-	constexpr int RING = LD::nslots();                                              // (PIPE) 2 x 6 pair slots of the pose ring behind the solo layout
-	constexpr int QR0 = RING + 18 + DuoSlots<NV>::n + NB, CD0 = QR0 + 8;  // (quartet, behind the trio's layout) O's quaternion ring: 2 x (xquat, the frame before the joint); C's cdof ring: 2 x 3
+	constexpr int RING = LD::nslots();  // (PIPE) the pose ring, RINGN x 6 pair slots, behind the solo layout
+	constexpr int QR0 = RING + le_ring_slots(RING_TRIO) + DuoSlots<NV>::n + NB, CD0 = QR0 + 8;  // (quartet, behind the trio's layout) O's quaternion ring: 2 x (xquat, the frame before the joint); C's cdof ring: 2 x 3
 	[[maybe_unused]] constexpr int XMAIL = CD0 + 6;  // (quartet) X's verdict on the step (mj_checkAcc), a slot nobody else writes: the last of QUARTET_EXTRA
-	static_assert(XMAIL + 1 == QR0 + QUARTET_EXTRA, "lane = env kernel: the quartet's slots and quartet_bytes<T>() (and the host's fit test for hiprtc-built models) go together");
-	constexpr int XS = PIPE ? RING + 6 * RINGN : LD::nslots(), MAIL = XS + (NV + 1) / 2, SC0 = MAIL + 1;  // (trio) SC0 + b: body b's half-angle (sin, cos), from C to P  // (DUO) pair slots of qfrc_smooth, and of P's verdicts for V
+	static_assert(XMAIL + 1 == QR0 + QUARTET_EXTRA, "lane = env kernel: the quartet's slots end where le_quartet_slots() says");
+	constexpr int XS = PIPE ? RING + le_ring_slots(RINGN) : LD::nslots(), MAIL = XS + (NV + 1) / 2, SC0 = MAIL + 1;  // (trio) SC0 + b: body b's half-angle (sin, cos), from C to P  // (DUO) pair slots of qfrc_smooth, and of P's verdicts for V
 	const int lane_le = DUO ? (int)(threadIdx.x & 63u) : (int)threadIdx.x;
 	Pair *const lp = reinterpret_cast<Pair *>(smem_le) + lane_le;  // pair slot q of this lane: lp[64 * q]
 	// (a tail lane without an env keeps running on the last env's data: no divergent exit, the wave-uniform branches below stay uniform. It stores
@@ -562,7 +602,7 @@ DEVI void lane_env_body(const KernelParams MJB_AS4 *__restrict__ P, const int ns
 			// critical chain; the body's (qpos, qvel) pair and qpos0 are fetched one more region ahead for that
 			[[maybe_unused]] double psn[NB + 2], pcs[NB + 2], q0n[NB + 2];
 			[[maybe_unused]] Pair pqn[NB + 2], scq[NB + 2];
-			if constexpr (ROLE == 5 && NB > 2) {
+			if constexpr (ROLE == LE_TRIO_P && NB > 2) {
 				if constexpr (T::body_jnt[2] >= 0) {
 					if constexpr (T::jnt_type[T::body_jnt[2]] == MJB_JNT_HINGE) {
 						pqn[2] = lp[64 * T::body_jnt[2]];
@@ -626,11 +666,11 @@ DEVI void lane_env_body(const KernelParams MJB_AS4 *__restrict__ P, const int ns
 				static_assert(c0 >= 0, "pipelined forms: every needed body's cinert lives in LDS");
 				[[maybe_unused]] double xp[3], xm[9];
 				double ci[10];
-				if constexpr (ROLE != 11) {
+				if constexpr (ROLE != LE_QUAD_V) {
 					const Pair a0 = lp[64 * rg], a1 = lp[64 * (rg + 1)], a2 = lp[64 * (rg + 2)], a3 = lp[64 * (rg + 3)], a4 = lp[64 * (rg + 4)], a5 = lp[64 * (rg + 5)];
 					xp[0] = a0.a; xp[1] = a0.b; xp[2] = a1.a; xm[0] = a1.b; xm[1] = a2.a; xm[2] = a2.b; xm[3] = a3.a; xm[4] = a3.b; xm[5] = a4.a; xm[6] = a4.b; xm[7] = a5.a; xm[8] = a5.b;
 				}
-				if constexpr ((ROLE == 4 && b == LASTB) || VLDS) {
+				if constexpr ((ROLE == LE_PIPE_V && b == LASTB) || VLDS) {
 					// the LAST needed body's cinert came with its pose: P computes that one itself and goes from its last pose straight into the
 					// composite-inertia sweep, which starts at this body -- it never waits for V's last phase
 					for (int k = 0; k < 5; k++) {
@@ -668,7 +708,7 @@ DEVI void lane_env_body(const KernelParams MJB_AS4 *__restrict__ P, const int ns
 					ci[7] = mass * dif[1];
 					ci[8] = mass * dif[2];
 					ci[9] = mass;
-					if constexpr (ROLE != 7) for (int k = 0; k < 5; k++) lp[64 * (c0 + k)] = Pair{ ci[2 * k], ci[2 * k + 1] };  // (for the composite-inertia sweep of P / of C itself)
+					if constexpr (OWNCIN) for (int k = 0; k < 5; k++) lp[64 * (c0 + k)] = Pair{ ci[2 * k], ci[2 * k + 1] };  // (for the composite-inertia sweep of P / of C itself)
 				}
 				[[maybe_unused]] double pv[6], pa[6];
 				if constexpr (!DV) {
@@ -684,7 +724,7 @@ DEVI void lane_env_body(const KernelParams MJB_AS4 *__restrict__ P, const int ns
 					if constexpr (DV) qv = lp[64 * j].b;
 					double *cd = cdof[j];
 					constexpr int cq = CD0 + 3 * (ord % 2);  // (quartet) the body's slots of the cdof ring
-					if constexpr (ROLE == 11) {  // (the quartet's V: C's cdof, one phase old)
+					if constexpr (ROLE == LE_QUAD_V) {  // (the quartet's V: C's cdof, one phase old)
 						const Pair d0 = lp[64 * cq], d1 = lp[64 * (cq + 1)], d2 = lp[64 * (cq + 2)];
 						cd[0] = d0.a; cd[1] = d0.b; cd[2] = d1.a; cd[3] = d1.b; cd[4] = d2.a; cd[5] = d2.b;
 						if constexpr (T::jnt_type[j] == MJB_JNT_SLIDE) cd[0] = cd[1] = cd[2] = 0;
@@ -709,7 +749,7 @@ DEVI void lane_env_body(const KernelParams MJB_AS4 *__restrict__ P, const int ns
 						for (int k = 0; k < 3; k++) cd[k] = xaxis[k];
 						cross3(cd + 3, xaxis, off);
 					}
-					if constexpr (ROLE == 10) {  // (the quartet's C: cdof to V)
+					if constexpr (ROLE == LE_QUAD_C) {  // (the quartet's C: cdof to V)
 						lp[64 * cq] = Pair{ cd[0], cd[1] };
 						lp[64 * (cq + 1)] = Pair{ cd[2], cd[3] };
 						lp[64 * (cq + 2)] = Pair{ cd[4], cd[5] };
@@ -775,7 +815,7 @@ DEVI void lane_env_body(const KernelParams MJB_AS4 *__restrict__ P, const int ns
 					// ---- the pipelined V (and the trio's C): body b's pose and cinert come through LDS, one barrier per needed body.  The trio's V runs TWO bodies
 					// behind P: it takes the cinert C computed one phase earlier instead of computing its own, and never paces the pose chain
 					if constexpr (LD::needed(b)) {
-						if constexpr (ROLE == 6) {
+						if constexpr (ROLE == LE_TRIO_C) {
 							// (the trio's C) a hinge's half-angle sine and cosine are a third of the pose chain's instructions and depend on qpos alone: C computes them
 							// two bodies ahead of P, in the time it would wait at this barrier, and P picks them up from LDS
 							constexpr int t2 = [] {
@@ -793,7 +833,7 @@ DEVI void lane_env_body(const KernelParams MJB_AS4 *__restrict__ P, const int ns
 						LE_PK(0);
 						le_barrier();
 						LE_PK(2);
-						if constexpr (ROLE != 7) consume(IC<b>{});
+						if constexpr (OWNCIN) consume(IC<b>{});
 						else {
 							constexpr int pb = [] { for (int c = b - 1; c >= 1; c--) if (LD::needed(c)) return c; return 0; }();
 							if constexpr (pb > 0) consume(IC<pb>{});
@@ -813,7 +853,7 @@ DEVI void lane_env_body(const KernelParams MJB_AS4 *__restrict__ P, const int ns
 				}
 				if constexpr (XF && LD::needed(b)) for (int k = 0; k < 6; k++) xw[b][k] = xf_ld(6 * XS6::slot(b) + k);
 				const double *const A = hA[b];  // pos[3] quat[4] jaxis[3] jpos[3] qpos0 stiffness spring
-				if constexpr (ROLE == 5 && b == 1 && b + 1 < NB) {
+				if constexpr (ROLE == LE_TRIO_P && b == 1 && b + 1 < NB) {
 					if constexpr (T::body_jnt[b + 1] >= 0) {
 						if constexpr (T::jnt_type[T::body_jnt[b + 1]] == MJB_JNT_HINGE) sincos_nb((pqn[b + 1].a - q0n[b + 1]) * 0.5, &psn[b + 1], &pcs[b + 1]);
 					}
@@ -845,8 +885,8 @@ DEVI void lane_env_body(const KernelParams MJB_AS4 *__restrict__ P, const int ns
 					}
 					if constexpr (T::jnt_type[j] == MJB_JNT_HINGE) {
 						double sn, cs, ql[4], q[4];
-						if constexpr (ROLE == 5 && SCUSE(b)) { sn = scq[b].a; cs = scq[b].b; }  // (C's, fetched in the previous body's second region)
-						else if constexpr (ROLE == 5 && b == 2) { sn = psn[b]; cs = pcs[b]; }  // (computed beside the first body's chain)
+						if constexpr (ROLE == LE_TRIO_P && SCUSE(b)) { sn = scq[b].a; cs = scq[b].b; }  // (C's, fetched in the previous body's second region)
+						else if constexpr (ROLE == LE_TRIO_P && b == 2) { sn = psn[b]; cs = pcs[b]; }  // (computed beside the first body's chain)
 						else sincos_nb((qp - A[13]) * 0.5, &sn, &cs);
 						ql[0] = cs; ql[1] = A[7] * sn; ql[2] = A[8] * sn; ql[3] = A[9] * sn;
 						qmul(q, quat, ql);
@@ -885,7 +925,7 @@ DEVI void lane_env_body(const KernelParams MJB_AS4 *__restrict__ P, const int ns
 					constexpr int nb = [] { for (int c = b + 1; c < NB; c++) if (T::body_jnt[c] >= 0) return c; return -1; }();
 					if constexpr (nb >= 0) pq[nb] = lp[64 * T::body_jnt[nb]];
 				}
-				if constexpr (ROLE == 5 && SCUSE(b + 1)) scq[b + 1] = lp[64 * (SC0 + b + 1)];
+				if constexpr (ROLE == LE_TRIO_P && SCUSE(b + 1)) scq[b + 1] = lp[64 * (SC0 + b + 1)];
 				const double *const Bh = hB[b];  // ipos[3] ibody[6] mass damping armature hdamping
 				// inertial frame
 				double xipos[3];
@@ -902,7 +942,7 @@ DEVI void lane_env_body(const KernelParams MJB_AS4 *__restrict__ P, const int ns
 				if constexpr (LD::needed(b)) {
 					// cinert about the tree root's origin (mju_inertCom with that offset)
 					[[maybe_unused]] double ci[10];
-					if constexpr (ROLE <= 2 || (ROLE == 3 && b == LASTB)) {
+					if constexpr (HALVES || (ROLE == LE_PIPE_P && b == LASTB)) {
 						double dif[3];
 						if constexpr (r == b) { dif[0] = xipos[0] - pos[0]; dif[1] = xipos[1] - pos[1]; dif[2] = xipos[2] - pos[2]; }
 						else for (int k = 0; k < 3; k++) dif[k] = xipos[k] - xpos[r][k];
@@ -943,7 +983,7 @@ DEVI void lane_env_body(const KernelParams MJB_AS4 *__restrict__ P, const int ns
 					} else {
 						for (int k = 0; k < 6; k++) { pv[k] = cvel[p][k]; pa[k] = cacc[p][k]; }
 					}
-					if constexpr (ROLE == 5) {  // (the trio's P: poses only)
+					if constexpr (ROLE == LE_TRIO_P) {  // (the trio's P: poses only)
 					} else if constexpr (j >= 0) {
 						double *cd = cdof[j];
 						if constexpr (T::jnt_type[j] == MJB_JNT_SLIDE) {
@@ -968,7 +1008,7 @@ DEVI void lane_env_body(const KernelParams MJB_AS4 *__restrict__ P, const int ns
 					} else if constexpr (DV) {
 						for (int k = 0; k < 6; k++) { cvel[b][k] = pv[k]; cacc[b][k] = pa[k]; }
 					}
-					if constexpr (DP && (ROLE != 3 || b == LASTB)) {  // the composite-inertia sweep reads it back (pipelined duo: the last body's, which V's force computation reads too)
+					if constexpr (DP && (ROLE != LE_PIPE_P || b == LASTB)) {  // the composite-inertia sweep reads it back (pipelined duo: the last body's, which V's force computation reads too)
 						if constexpr (LD::cin_slot(b) >= 0) {
 							constexpr int c0 = LD::cin_slot(b);
 							for (int k = 0; k < 5; k++) lp[64 * (c0 + k)] = Pair{ ci[2 * k], ci[2 * k + 1] };
@@ -996,7 +1036,7 @@ DEVI void lane_env_body(const KernelParams MJB_AS4 *__restrict__ P, const int ns
 						lp[64 * (q0 + 1)] = Pair{ cf[2] + t1[2], cf[3] + t1[3] };
 						lp[64 * (q0 + 2)] = Pair{ cf[4] + t1[4], cf[5] + t1[5] };
 					}
-					if constexpr (ROLE == 3 || ROLE == 5) {  // the pose to V (and, of three, to C)
+					if constexpr (ROLE == LE_PIPE_P || ROLE == LE_TRIO_P) {  // the pose to V (and, of three, to C)
 						constexpr int ord = (LD::slot(b) - NV) / 3, rg = RING + 6 * (ord % RINGN);
 						const double *xm = xmat[b];
 						double xp[3] = { 0, 0, 0 };  // relative to the tree root's origin: what cdof is taken about
@@ -1200,22 +1240,22 @@ DEVI void lane_env_body(const KernelParams MJB_AS4 *__restrict__ P, const int ns
 						touch_rec<10>(hB[nx]);
 					}
 				};
-				if constexpr (ROLE == 8 || ROLE == 9) {
+				if constexpr (ROLE == LE_QUAD_O || ROLE == LE_QUAD_X) {
 					// the bodies at rest, then the first needed body's record
 					sfor<NB>([&](auto Bq) {
 						constexpr int b = Bq;
 						if constexpr (b > 0 && !LD::needed(b)) {
 							for (int k = 0; k < 14; k++) hA[b][k] = reinterpret_cast<const double MJB_AS4 *>(tb + b)[k];
-							if constexpr (ROLE == 9) for (int k = 0; k < 10; k++) hB[b][k] = reinterpret_cast<const double MJB_AS4 *>(tb + b)[16 + k];
-							if constexpr (ROLE == 8) o_body(Bq);
+							if constexpr (ROLE == LE_QUAD_X) for (int k = 0; k < 10; k++) hB[b][k] = reinterpret_cast<const double MJB_AS4 *>(tb + b)[16 + k];
+							if constexpr (ROLE == LE_QUAD_O) o_body(Bq);
 							else x_body(Bq);
 						}
 					});
 					if constexpr (N1 < NB) {
 						for (int k = 0; k < 14; k++) hA[N1][k] = reinterpret_cast<const double MJB_AS4 *>(tb + N1)[k];
-						if constexpr (ROLE == 9) for (int k = 0; k < 10; k++) hB[N1][k] = reinterpret_cast<const double MJB_AS4 *>(tb + N1)[16 + k];
+						if constexpr (ROLE == LE_QUAD_X) for (int k = 0; k < 10; k++) hB[N1][k] = reinterpret_cast<const double MJB_AS4 *>(tb + N1)[16 + k];
 					}
-					if constexpr (ROLE == 8) {
+					if constexpr (ROLE == LE_QUAD_O) {
 						if constexpr (HINGE(N1)) {
 							opq[N1] = lp[64 * T::body_jnt[N1 < NB ? N1 : 0]];
 							oq0[N1] = tb[N1].qpos0;
@@ -1231,11 +1271,11 @@ DEVI void lane_env_body(const KernelParams MJB_AS4 *__restrict__ P, const int ns
 				// phase k: O on the k-th needed body, X on the one before, C two, V three before; every wavefront takes the KN + 2 barriers, V's last body comes behind the last one
 				sfor<KN + 3>([&](auto Ki) {
 					constexpr int k = Ki + 1;
-					constexpr int kk = k - (ROLE - 8);  // this role's body, counted among the needed ones
+					constexpr int kk = k - (ROLE - LE_QUAD_O);  // this role's body, counted among the needed ones
 					if constexpr (kk >= 1 && kk <= KN) {
 						constexpr int bb = NTH(kk);
-						if constexpr (ROLE == 8) o_phase(IC<bb>{});
-						else if constexpr (ROLE == 9) x_phase(IC<bb>{});
+						if constexpr (ROLE == LE_QUAD_O) o_phase(IC<bb>{});
+						else if constexpr (ROLE == LE_QUAD_X) x_phase(IC<bb>{});
 						else consume(IC<bb>{});
 					}
 					if constexpr (DV && k == 1) sfor<NV>([&](auto I) { qfa[I] = s.qfrc_applied[ev * NV + I]; });  // (read by the force block behind the sweep: a trip to HBM)
@@ -1249,9 +1289,9 @@ DEVI void lane_env_body(const KernelParams MJB_AS4 *__restrict__ P, const int ns
 			}
 
 			LE_PK(0);
-			if constexpr (ROLE >= 5 && !QUAD) {  // (the trio: C's cinert of the last body is in LDS; V takes that body now)
+			if constexpr (TRIQ && !QUAD) {  // (the trio: C's cinert of the last body is in LDS; V takes that body now)
 				le_barrier();
-				if constexpr (ROLE == 7) consume(IC<LASTB>{});
+				if constexpr (ROLE == LE_TRIO_V) consume(IC<LASTB>{});
 			}
 			LE_PK(1);
 			// ============ A8 mj_passive, the injector's OU update, A12 mj_fwdActuation (joint transmission), qfrc_applied ============
@@ -1510,7 +1550,7 @@ DEVI void lane_env_body(const KernelParams MJB_AS4 *__restrict__ P, const int ns
 				__builtin_amdgcn_sched_barrier(0);
 			});
 			LE_PK(3);
-			if constexpr (ROLE == 5 || ROLE == 9) en_pe = pe;
+			if constexpr (POSEW) en_pe = pe;
 			if constexpr (DUO && !DP && !XW) {
 				// ---- V's half ends here: qfrc_smooth to P, then P's verdict on the step (the trio's P: the two rendezvous and the verdict)
 				if constexpr (DV) sfor<(NV + 1) / 2>([&](auto K) {
@@ -1655,7 +1695,7 @@ DEVI void lane_env_body(const KernelParams MJB_AS4 *__restrict__ P, const int ns
 				le_barrier();  // (R) C has put the old state back
 				continue;
 			}
-			if constexpr (ROLE == 10) {
+			if constexpr (ROLE == LE_QUAD_C) {
 				// ---- (four wavefronts) C: mj_Euler at once, on the assumption that X finds qacc good; the nine (qpos, qvel) pairs it read stay in registers
 				// until X's verdict is in, and `time` waits for it too
 				Pair sv[NV > 0 ? NV : 1];
@@ -1710,7 +1750,7 @@ DEVI void lane_env_body(const KernelParams MJB_AS4 *__restrict__ P, const int ns
 				le_barrier();  // (B, retry) V runs its half again on the reset state
 			}
 		}
-		if constexpr (ROLE == 5 || ROLE == 9) {
+		if constexpr (POSEW) {
 			if (last && (m.enableflags & MJB_ENBL_ENERGY)) s.energy[2 * ev] = en_pe;  // (C stores the kinetic half)
 		}
 		if constexpr (XW) {
@@ -1727,7 +1767,7 @@ DEVI void lane_env_body(const KernelParams MJB_AS4 *__restrict__ P, const int ns
 		}
 
 		if (last) {  // mj_advance's qacc_warmstart = qacc; mjData.energy of the launch's last step
-			if constexpr (ROLE != 10)
+			if constexpr (FM)
 			sfor<NV>([&](auto I) {
 				s.qacc[ev * NV + I] = qacc[I];
 				s.qacc_warmstart[ev * NV + I] = qacc[I];
@@ -1737,7 +1777,7 @@ DEVI void lane_env_body(const KernelParams MJB_AS4 *__restrict__ P, const int ns
 				s.energy[2 * ev + 1] = en_ke;
 			}
 		}
-		if constexpr (ROLE == 10) {  // (four wavefronts: C has integrated inside the loop, ahead of X's verdict)
+		if constexpr (ROLE == LE_QUAD_C) {  // (four wavefronts: C has integrated inside the loop, ahead of X's verdict)
 			time += dt;
 			continue;
 		}
@@ -1770,7 +1810,7 @@ DEVI void lane_env_body(const KernelParams MJB_AS4 *__restrict__ P, const int ns
 		}
 	}
 #ifdef MJB_LE_PROBE
-	if (env_raw == env_lo) for (int k = 0; k < 8; k++) P->s.sensordata[(ROLE == 4 || ROLE == 2 || ROLE == 6 || ROLE == 10 ? 8 : (ROLE == 7 || ROLE == 11 ? 16 : (ROLE == 9 ? 24 : 0))) + k] = (double)pk_acc[k] / nsteps;
+	if (env_raw == env_lo) for (int k = 0; k < 8; k++) P->s.sensordata[(ROLE == LE_PIPE_V || ROLE == LE_DUO_V || ROLE == LE_TRIO_C || ROLE == LE_QUAD_C ? 8 : (ROLE == LE_TRIO_V || ROLE == LE_QUAD_V ? 16 : (ROLE == LE_QUAD_X ? 24 : 0))) + k] = (double)pk_acc[k] / nsteps;
 #endif
 
 	// ---- the launch's state back to HBM (store_state of the generic kernels; sensordata went out from the last step)
@@ -1804,19 +1844,20 @@ DEVI void lane_env_body(const KernelParams MJB_AS4 *__restrict__ P, const int ns
 }
 
 // LDS of a DUO block: the solo layout under a budget reduced by the exchange slots, then those
-template <class T, int LP> constexpr int duo_bytes() { return (Lds<T, LP - DuoSlots<T::NV>::n>::nslots() + DuoSlots<T::NV>::n) * 64 * 16; }
+template <class T, int LP> constexpr int duo_bytes() { return le_duo_slots(T::NV, Lds<T, LP>::nmov(), LP) * LE_SLOT_BYTES; }
 
-// ... and of a pipelined DUO block (roles 3 / 4): every needed body's cinert, every dof's cdof, the pose ring, the exchange slots
-template <class T> constexpr int trio_bytes() { return (Lds<T, (1 << 20)>::nslots() + 18 + DuoSlots<T::NV>::n + T::NBODY) * 64 * 16; }
+// ... of a pipelined DUO block: every needed body's cinert, the pose ring, the exchange slots
+template <class T> constexpr int duo2_bytes() { return le_duo2_slots(T::NV, Lds<T, 0>::nmov()) * LE_SLOT_BYTES; }
+// ... of a trio block: the same with the deeper ring and a (sin, cos) slot per body
+template <class T> constexpr int trio_bytes() { return le_trio_slots(T::NV, Lds<T, 0>::nmov(), T::NBODY) * LE_SLOT_BYTES; }
 // ... and of a quartet block: the trio's layout, then O's quaternion ring (2 x 4 pair slots), C's cdof ring (2 x 3) and X's mail slot
-template <class T> constexpr int quartet_bytes() { return trio_bytes<T>() + QUARTET_EXTRA * 64 * 16; }
-template <class T> constexpr int duo2_bytes() { return (Lds<T, (1 << 20)>::nslots() + 12 + DuoSlots<T::NV>::n) * 64 * 16; }
+template <class T> constexpr int quartet_bytes() { return le_quartet_slots(T::NV, Lds<T, 0>::nmov(), T::NBODY) * LE_SLOT_BYTES; }
 template <class T, int LP>
 DEVI void lane_env_duo2(const KernelParams MJB_AS4 *__restrict__ P, const int nsteps, const unsigned int step0, const int env_lo, const int env_hi,
                         unsigned char *const smem_le)
 {
-	if (__builtin_amdgcn_readfirstlane((int)threadIdx.x) < 64) lane_env_body<T, LP, 3>(P, nsteps, step0, env_lo, env_hi, smem_le);
-	else lane_env_body<T, LP, 4>(P, nsteps, step0, env_lo, env_hi, smem_le);
+	if (__builtin_amdgcn_readfirstlane((int)threadIdx.x) < 64) lane_env_body<T, LP, LE_PIPE_P>(P, nsteps, step0, env_lo, env_hi, smem_le);
+	else lane_env_body<T, LP, LE_PIPE_V>(P, nsteps, step0, env_lo, env_hi, smem_le);
 }
 
 // the TRIO: wavefront 0 = the pose chain, 1 = inertias / factors / solves / Euler, 2 = velocities and forces (blockDim.x = 192; the pipelined duo's LDS layout)
@@ -1825,9 +1866,9 @@ DEVI void lane_env_trio(const KernelParams MJB_AS4 *__restrict__ P, const int ns
                         unsigned char *const smem_le)
 {
 	const int w = __builtin_amdgcn_readfirstlane((int)threadIdx.x) >> 6;
-	if (w == 0) lane_env_body<T, LP, 5>(P, nsteps, step0, env_lo, env_hi, smem_le);
-	else if (w == 1) lane_env_body<T, LP, 6>(P, nsteps, step0, env_lo, env_hi, smem_le);
-	else lane_env_body<T, LP, 7>(P, nsteps, step0, env_lo, env_hi, smem_le);
+	if (w == 0) lane_env_body<T, LP, LE_TRIO_P>(P, nsteps, step0, env_lo, env_hi, smem_le);
+	else if (w == 1) lane_env_body<T, LP, LE_TRIO_C>(P, nsteps, step0, env_lo, env_hi, smem_le);
+	else lane_env_body<T, LP, LE_TRIO_V>(P, nsteps, step0, env_lo, env_hi, smem_le);
 }
 
 // the QUARTET: wavefront 0 = the orientation chain, 1 = frames and positions, 2 = inertias / factors / solves / Euler, 3 = velocities and forces (blockDim.x = 256)
@@ -1836,10 +1877,10 @@ DEVI void lane_env_quartet(const KernelParams MJB_AS4 *__restrict__ P, const int
                            unsigned char *const smem_le)
 {
 	const int w = __builtin_amdgcn_readfirstlane((int)threadIdx.x) >> 6;
-	if (w == 0) lane_env_body<T, LP, 8>(P, nsteps, step0, env_lo, env_hi, smem_le);
-	else if (w == 1) lane_env_body<T, LP, 9>(P, nsteps, step0, env_lo, env_hi, smem_le);
-	else if (w == 2) lane_env_body<T, LP, 10>(P, nsteps, step0, env_lo, env_hi, smem_le);
-	else lane_env_body<T, LP, 11>(P, nsteps, step0, env_lo, env_hi, smem_le);
+	if (w == 0) lane_env_body<T, LP, LE_QUAD_O>(P, nsteps, step0, env_lo, env_hi, smem_le);
+	else if (w == 1) lane_env_body<T, LP, LE_QUAD_X>(P, nsteps, step0, env_lo, env_hi, smem_le);
+	else if (w == 2) lane_env_body<T, LP, LE_QUAD_C>(P, nsteps, step0, env_lo, env_hi, smem_le);
+	else lane_env_body<T, LP, LE_QUAD_V>(P, nsteps, step0, env_lo, env_hi, smem_le);
 }
 
 // the DUO kernel's body: wavefront 0 of the block takes the position half, wavefront 1 the velocity half (blockDim.x = 128)
@@ -1847,8 +1888,8 @@ template <class T, int LP>
 DEVI void lane_env_duo(const KernelParams MJB_AS4 *__restrict__ P, const int nsteps, const unsigned int step0, const int env_lo, const int env_hi,
                        unsigned char *const smem_le)
 {
-	if (__builtin_amdgcn_readfirstlane((int)threadIdx.x) < 64) lane_env_body<T, LP, 1>(P, nsteps, step0, env_lo, env_hi, smem_le);
-	else lane_env_body<T, LP, 2>(P, nsteps, step0, env_lo, env_hi, smem_le);
+	if (__builtin_amdgcn_readfirstlane((int)threadIdx.x) < 64) lane_env_body<T, LP, LE_DUO_P>(P, nsteps, step0, env_lo, env_hi, smem_le);
+	else lane_env_body<T, LP, LE_DUO_V>(P, nsteps, step0, env_lo, env_hi, smem_le);
 }
 
 }  // namespace mjb_le
