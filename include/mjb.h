@@ -275,7 +275,15 @@ int mjb_fused_frame(const mjb_batch *b);
  * mjb_set_env_* call on these values; sized mjb_model_lane_env_overlay() doubles per env).  Every other condition stays (hwsim stage, xfrc_applied -- which mjb_lane_env_set_xfrc
  * lifts in this mode too --, frame dumps, statistics); a mode-2 batch WITHOUT overrides runs exactly what mode 1 runs.
  * The environment variable MJB_LANE_ENV (same values) sets the default of new batches (read by mjb_make_batch).  While mjb_set_stats is
- * counting, fused launches run the generic kernels whatever the mode (the counters live in those).  No reference counterpart. */
+ * counting, fused launches run the generic kernels whatever the mode (the counters live in those).
+ * Actuator activation states (mjData.act; dyntype integrator / filter on joint transmissions: <general dyntype>, <intvelocity>, <cylinder>): such a model
+ * is eligible like any other (mjb_model_lane_env() == -2, its kernel built by hiprtc).  act is read from the batch's `act` field at the start of a
+ * launch, lives in the lane's registers, advances once per step as the generic kernels advance it (act_dot from the clamped ctrl, the force from the
+ * current act, actrange where actlimited, zero after a mj_check* reset, frozen under mjDSBL_ACTUATION) and is written back at the launch's end: launch
+ * splits and hand-overs to and from the generic kernels carry it.  Its launches run the one-wavefront form (mjb_lane_env_last_form() == 0) whatever
+ * form is asked for, in the plain, mode-2 and xfrc builds; with a device hwsim stage such a batch keeps the generic kernels (there is no build with
+ * both).  Measured on config 2's arm with <intvelocity> on its seven joints and one filter actuator (tools/lane_env_act_rate.py,
+ * profiles/lane_env_act.txt): 278.9 against the generic kernel's 196.1 M env-steps/s at 4096 envs (1.42 x), 3121 against 197 at 65 536 (15.9 x), 0.92 / 0.84 of plain franka_like's rate in the same one-wavefront form; the lane = env kernel is ahead at 4096 envs, so mode -1 keeps its 4096-env threshold for these models.  No reference counterpart. */
 int mjb_set_lane_env(mjb_batch *b, int mode);
 /* Opt-in (default off): with on = 1 the device hwsim stage (mjb_hwsim_configure, below) no longer stands the lane = env kernel down.  The batch's
  * eligible launches then run the kernel's one-wavefront form (mjb_lane_env_last_form() == 0, at the LDS budget the batch size gives, whatever form is
@@ -344,8 +352,9 @@ int mjb_model_lane_env(const mjb_model *m);
  * the kernel reads them, without a batch or a device.  Both return the
  * number of doubles and fill `out` when it is not NULL and `cap` is large enough; -1: the model is not eligible.
  * mjb_model_lane_env_tape: the constant tape -- dt gravity[3] pad[4] | per body, 32 doubles: pos[3] quat[4] jaxis[3] jpos[3] qpos0 stiffness spring
- * ipos[3] ibody[6] mass damping armature hdamping pad[3] | per actuator, 16: gear ctrlrange[2] gain[3] bias[3] forcerange[2] pad[5]; ibody =
- * R(iquat) diag(inertia) R(iquat)' as xx yy zz xy xz yz, hdamping = timestep * damping.
+ * ipos[3] ibody[6] mass damping armature hdamping pad[3] | per actuator, 16: gear ctrlrange[2] gain[3] bias[3] forcerange[2] dyntau actrange[2] pad[2]; ibody =
+ * R(iquat) diag(inertia) R(iquat)' as xx yy zz xy xz yz, hdamping = timestep * damping, dyntau = max(mjMINVAL, dynprm[0]) of a filter actuator -- the
+ * time constant itself, which act_dot divides by, not its reciprocal -- and 0 for every other; dyntau and actrange are 0 for a stateless actuator.
  * mjb_model_lane_env_overlay: one env's column of the per-env table of mjb_set_lane_env's mode 2, here with the model's own values -- gravity[3] | per
  * jointed body: stiffness damping armature hdamping | per moving body (a joint on its path to the world): mass ibody[6] | per actuator: gain[3] bias[3]
  * | the mass of every other body but the world (mjENBL_ENERGY reads it). */
@@ -357,8 +366,9 @@ int mjb_model_lane_env_overlay(const mjb_model *m, double *out, int cap);
  * nenv: envs of the batch; build: 0 plain, 1 per-env overlay (mjb_set_lane_env mode 2), 2 hwsim stage, 3 xfrc_applied, 4 overlay + xfrc_applied;
  * form: -1 the rule, 0 .. 3 as mjb_lane_env_set_form; sweep_waves: 0 the rule, 3 / 4 as mjb_lane_env_set_sweep_waves; lds_kb: 0 by batch size,
  * 40 / 80 / 160 as MJB_LANE_ENV_LDS_KB.  Fills (each may be NULL) the form, form 3's sweep wavefronts (0 otherwise) and the LDS budget in KB, the
- * values mjb_lane_env_last_form / mjb_lane_env_last_sweep_waves report after such a launch.  Returns 0; -1: the model is not eligible or needs more
- * LDS than a CU has, or an argument is out of range. */
+ * values mjb_lane_env_last_form / mjb_lane_env_last_sweep_waves report after such a launch.  A model with activation states (na > 0): form 0 whatever
+ * is asked for, and no variant at all for build 2.  Returns 0; -1: the model is not eligible or needs more LDS than a CU has, there is no such variant,
+ * or an argument is out of range. */
 int mjb_lane_env_plan(const mjb_model *m, int ncu, int nenv, int build, int form, int sweep_waves, int lds_kb, int *out_form, int *out_sweep_waves, int *out_lds_kb);
 const char *mjb_lane_env_error(void);
 /* The lane = env kernel's FORM, process-wide: how many wavefronts share the 64 envs of a block.  0 = one (the whole step in one instruction stream);

@@ -95,7 +95,8 @@ struct LeTapeBody {
 	// inertial half
 	double ipos[3], ibody[6] /* R(iquat) diag(inertia) R(iquat)': xx yy zz xy xz yz */, mass, damping, armature, hdamping /* timestep * damping */, pad[3];
 };
-struct LeTapeAct { double gear, ctrllo, ctrlhi, gain[3], bias[3], forcelo, forcehi, pad[5]; };
+// (dyntau: a filter actuator's max(mjMINVAL, dynprm[0]) -- the divisor of act_dot, not its reciprocal; actlo / acthi: actrange.  Zero for a stateless actuator)
+struct LeTapeAct { double gear, ctrllo, ctrlhi, gain[3], bias[3], forcelo, forcehi, dyntau, actlo, acthi, pad[2]; };
 static_assert(sizeof(LeTapeHdr) == 64 && sizeof(LeTapeBody) == 256 && sizeof(LeTapeAct) == 128, "lane = env tape records");
 
 // Offsets (in doubles / ints) of every data field inside one per-env frame.

@@ -15,7 +15,8 @@
 //   * the state of 64 envs lives in the wavefront's registers for all K fused steps (512 per lane at one wavefront per SIMD);
 //     what does not fit spills to the AGPR half of the file and then to scratch -- `tools/kernel_meta.py` reports both.
 // Same step as the oracle's mjo_step / mj_step (mujoco_env.cpp:498,552,593) for models the topology tables cover: hinge / slide
-// trees without constraint rows, Euler with implicit joint damping, joint-transmission actuators, the sensors listed in
+// trees without constraint rows, Euler with implicit joint damping, joint-transmission actuators -- stateless, or with an integrator / filter
+// activation state (mjData.act: in registers for the launch, one-wavefront form, hiprtc-built models) --, the sensors listed in
 // gen_lane_env_topo.py, ctrl noise (mujoco_env.cpp:469-481), mj_check* resets, mjENBL_ENERGY.  Arithmetic follows MuJoCo's
 // com-based formulation stage by stage (oracle/mjo_smooth.c); sums over bodies run in ascending instead of leaf-to-root order and
 // reciprocals are Newton-refined hardware seeds, so results agree with the oracle to rounding, not bit for bit (tests/test_gpu_lane_env.py).
@@ -82,7 +83,7 @@ __global__ void __launch_bounds__(64 * NW) mjb_lane_env_trio_kernel(const Kernel
 
 template <class T> bool topo_matches(const mjb_model_desc &h)
 {
-	if (h.nbody != T::NBODY || h.nq != T::NQ || h.nv != T::NV || h.nu != T::NU || h.njnt != T::NJNT || h.nsite != T::NSITE ||
+	if (h.nbody != T::NBODY || h.nq != T::NQ || h.nv != T::NV || h.nu != T::NU || h.na != T::NA || h.njnt != T::NJNT || h.nsite != T::NSITE ||
 	    h.nsensor != T::NSENSOR || h.nsensordata != T::NSENSORDATA || h.nM != T::NM)
 		return false;
 	for (int b = 0; b < h.nbody; b++) {
@@ -96,9 +97,10 @@ template <class T> bool topo_matches(const mjb_model_desc &h)
 	for (int d = 0; d < h.nv; d++)
 		if (h.dof_parentid[d] != T::dof_parentid[d] || h.dof_Madr[d] != T::dof_Madr[d] || h.dof_jntid[d] != d) return false;
 	for (int i = 0; i < h.nu; i++)
-		if (h.actuator_trntype[i] != MJB_TRN_JOINT || h.actuator_dyntype[i] != MJB_DYN_NONE || h.actuator_trnid[2 * i] != T::act_jnt[i] ||
+		if (h.actuator_trntype[i] != MJB_TRN_JOINT || h.actuator_dyntype[i] != T::act_dyntype[i] || h.actuator_trnid[2 * i] != T::act_jnt[i] ||
 		    h.actuator_gaintype[i] != T::act_gaintype[i] || h.actuator_biastype[i] != T::act_biastype[i] ||
-		    (h.actuator_ctrllimited[i] != 0) != (T::act_ctrllimited[i] != 0) || (h.actuator_forcelimited[i] != 0) != (T::act_forcelimited[i] != 0))
+		    (h.actuator_ctrllimited[i] != 0) != (T::act_ctrllimited[i] != 0) || (h.actuator_forcelimited[i] != 0) != (T::act_forcelimited[i] != 0) ||
+		    (h.na > 0 && (h.actuator_actadr[i] != T::act_actadr[i] || (h.actuator_actlimited[i] != 0) != (T::act_actlimited[i] != 0))))
 			return false;
 	for (int i = 0; i < h.nsite; i++)
 		if (h.site_bodyid[i] != T::site_bodyid[i] || (h.site_sameframe[i] != 0) != (T::site_sameframe[i] != 0)) return false;
@@ -111,11 +113,18 @@ template <class T> bool topo_matches(const mjb_model_desc &h)
 
 }  // namespace
 
-// what both classifications below ask first: an unconstrained Euler model of one-dof joints, without mocap bodies, tendons, equalities or activations
+// what both classifications below ask first: an unconstrained Euler model of one-dof joints, without mocap bodies, tendons or equalities
 static bool le_plain_tree(const mjb_model_desc *h)
 {
-	return h && h->nefcmax <= 0 && h->nconmax <= 0 && h->integrator == MJB_INT_EULER && h->nmocap <= 0 && h->ntendon <= 0 && h->neq <= 0 && h->na <= 0 &&
+	return h && h->nefcmax <= 0 && h->nconmax <= 0 && h->integrator == MJB_INT_EULER && h->nmocap <= 0 && h->ntendon <= 0 && h->neq <= 0 &&
 	       h->nq == h->nv && h->njnt == h->nv;
+}
+// an actuator's dynamics the kernel runs: none, or an activation state of its own that integrates ctrl / filters it (muscle and user dynamics: the loader's refusal)
+static bool le_dyntype_ok(const mjb_model_desc *h, int i)
+{
+	const int d = h->actuator_dyntype[i];
+	if (d == MJB_DYN_NONE) return h->na <= 0 || h->actuator_actadr[i] < 0;
+	return (d == MJB_DYN_INTEGRATOR || d == MJB_DYN_FILTER) && h->actuator_actadr[i] >= 0 && h->actuator_actadr[i] < h->na;
 }
 
 // Index of the compiled-in topology the model has, or -1 (mjb_compile; the generic kernels run every model).
@@ -193,8 +202,10 @@ int mjb_lane_env_eligible(const mjb_model_desc *h)
 		if (frame && (h->sensor_refid[i] >= 0 || (ot != MJB_OBJ_BODY && ot != MJB_OBJ_XBODY && ot != MJB_OBJ_SITE))) return 0;
 	}
 	for (int i = 0; i < h->nu; i++)
-		if (h->actuator_trntype[i] != MJB_TRN_JOINT || h->actuator_dyntype[i] != MJB_DYN_NONE) return 0;
-	return 1;
+		if (h->actuator_trntype[i] != MJB_TRN_JOINT || !le_dyntype_ok(h, i)) return 0;
+	int owned = 0;  // (every slot of act has its one actuator: the kernel writes a slot where it runs its owner)
+	for (int i = 0; i < h->nu; i++) owned += h->actuator_dyntype[i] != MJB_DYN_NONE;
+	return owned == (h->na > 0 ? h->na : 0);
 }
 
 namespace {
@@ -209,7 +220,7 @@ std::string topo_source(const mjb_model_desc &h)
 		for (int i = 0; i < (count > 0 ? count : 1); i++) s += (i ? ", " : "") + std::to_string(count > 0 ? (int)get(i) : 0);
 		s += " };\n";
 	};
-	scalar("NBODY", h.nbody); scalar("NQ", h.nq); scalar("NV", h.nv); scalar("NU", h.nu); scalar("NJNT", h.njnt); scalar("NSITE", h.nsite);
+	scalar("NBODY", h.nbody); scalar("NQ", h.nq); scalar("NV", h.nv); scalar("NU", h.nu); scalar("NA", h.na); scalar("NJNT", h.njnt); scalar("NSITE", h.nsite);
 	scalar("NSENSOR", h.nsensor); scalar("NSENSORDATA", h.nsensordata); scalar("NM", h.nM);
 	arr("body_parentid", h.nbody, [&](int i) { return h.body_parentid[i]; });
 	arr("body_rootid", h.nbody, [&](int i) { return h.body_rootid[i]; });
@@ -224,6 +235,9 @@ std::string topo_source(const mjb_model_desc &h)
 	arr("act_biastype", h.nu, [&](int i) { return h.actuator_biastype[i]; });
 	arr("act_ctrllimited", h.nu, [&](int i) { return h.actuator_ctrllimited[i] != 0; });
 	arr("act_forcelimited", h.nu, [&](int i) { return h.actuator_forcelimited[i] != 0; });
+	arr("act_dyntype", h.nu, [&](int i) { return h.actuator_dyntype[i]; });
+	arr("act_actadr", h.nu, [&](int i) { return h.na > 0 ? h.actuator_actadr[i] : 0; });
+	arr("act_actlimited", h.nu, [&](int i) { return h.na > 0 && h.actuator_actlimited[i] != 0; });
 	arr("site_bodyid", h.nsite, [&](int i) { return h.site_bodyid[i]; });
 	arr("site_sameframe", h.nsite, [&](int i) { return h.site_sameframe[i] != 0; });
 	arr("sensor_type", h.nsensor, [&](int i) { return h.sensor_type[i]; });
@@ -633,6 +647,11 @@ void mjb_lane_env_tape(const mjb_model_desc *h, double *tape)
 		for (int k = 0; k < 3; k++) { a.gain[k] = h->actuator_gainprm[3 * i + k]; a.bias[k] = h->actuator_biasprm[3 * i + k]; }
 		a.forcelo = h->actuator_forcerange[2 * i];
 		a.forcehi = h->actuator_forcerange[2 * i + 1];
+		if (h->na > 0 && h->actuator_actadr[i] >= 0) {  // (an activation state: the filter's time constant as act_dot divides by it, and actrange)
+			if (h->actuator_dyntype[i] == MJB_DYN_FILTER) a.dyntau = h->actuator_dynprm[3 * i] > MJB_MINVAL ? h->actuator_dynprm[3 * i] : MJB_MINVAL;
+			a.actlo = h->actuator_actrange[2 * i];
+			a.acthi = h->actuator_actrange[2 * i + 1];
+		}
 	}
 }
 
@@ -660,6 +679,7 @@ struct LePlanIn {
 	int wave_lanes;     // 16 / 32: envs per wavefront of the plain one-wavefront form; anything else: 64 (MJB_LANE_ENV_WAVE_LANES)
 	bool fit;           // a hiprtc-built model: the layouts are counted for it, and what does not fit a CU's LDS steps down
 	int nv, nmov, nbody;  // ... from these: dofs, moving bodies (mjb_lane_env_xfrc_slots), bodies
+	int na;             // ... and its activation states: the one-wavefront form alone carries them, and no build with the hwsim stage
 };
 
 LeVariant le_plan(const LePlanIn &in)
@@ -686,6 +706,13 @@ LeVariant le_plan(const LePlanIn &in)
 		if (v.form == 3) v.sweep = (in.sweep == 3 || in.sweep == 4) ? in.sweep : (waves <= ncu ? 4 : 3);
 	}  // (otherwise -- the overlay / hwsim / xfrc builds whatever is asked for -- the solo form at that budget)
 	if (!in.fit) return v;
+	if (in.na > 0) {  // (act lives in the registers of the one wavefront that assembles the forces and integrates; a model with na > 0 is always hiprtc's)
+		if (in.build == MJB_LE_HWSIM) {
+			v.unavailable = "no build of the kernel has both the hwsim stage and activation states";
+			return v;
+		}
+		v.form = 0, v.sweep = 0;
+	}
 	// a hiprtc-built model may be larger than the compiled-in ones: the smallest budget its (qpos, qvel) pairs and body forces fit (fewer wavefronts per
 	// CU then), and of the forms the first one down whose layout fits
 	const int state = le_state_slots(in.nv, in.nmov);
@@ -758,8 +785,8 @@ template <class T> int le_go_topo(const LeVariant &v, const LeLaunch &a)
 }
 LePlanIn le_plan_in(const mjb_model_desc *fit_model, int ncu, int nenv_batch, LeBuild build, int form, int duo_max_waves, int sweep, int lds_kb, int wave_lanes)
 {
-	LePlanIn in{ ncu, nenv_batch, build, form, duo_max_waves, sweep, lds_kb, wave_lanes, fit_model != nullptr, 0, 0, 0 };
-	if (fit_model) in.nv = fit_model->nv, in.nmov = mjb_lane_env_xfrc_slots(fit_model), in.nbody = fit_model->nbody;
+	LePlanIn in{ ncu, nenv_batch, build, form, duo_max_waves, sweep, lds_kb, wave_lanes, fit_model != nullptr, 0, 0, 0, 0 };
+	if (fit_model) in.nv = fit_model->nv, in.nmov = mjb_lane_env_xfrc_slots(fit_model), in.nbody = fit_model->nbody, in.na = fit_model->na;
 	return in;
 }
 }  // namespace

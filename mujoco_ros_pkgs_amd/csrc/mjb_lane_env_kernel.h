@@ -356,7 +356,7 @@ template <class T, int LP, int ROLE = LE_SOLO, bool PE = false, bool HW = false,
 DEVI void lane_env_body(const KernelParams MJB_AS4 *__restrict__ P, const int nsteps, const unsigned int step0, const int env_lo, const int env_hi,
                         unsigned char *const smem_le)
 {
-	constexpr int NB = T::NBODY, NV = T::NV, NU = T::NU;
+	constexpr int NB = T::NBODY, NV = T::NV, NU = T::NU, NA = T::NA;
 	// ---- what this wavefront does, from its role: the one place a role is looked at by group
 	constexpr bool QUAD = le_quartet(ROLE), TRIQ = le_trio(ROLE) || QUAD;  // of four wavefronts / of three or four
 	constexpr bool HALVES = ROLE == LE_SOLO || le_two_halves(ROLE);         // computes every pose and cinert itself: solo, or either half of the two-halves duo
@@ -375,6 +375,7 @@ DEVI void lane_env_body(const KernelParams MJB_AS4 *__restrict__ P, const int ns
 	static_assert(!PE || ROLE == LE_SOLO, "lane = env kernel: per-env overrides run the solo form");
 	static_assert(!HW || (ROLE == LE_SOLO && !PE), "lane = env kernel: the hwsim stage runs the solo form, without per-env overrides");
 	static_assert(!XF || (ROLE == LE_SOLO && !HW), "lane = env kernel: xfrc_applied runs the solo form, without the hwsim stage");
+	static_assert(NA == 0 || (ROLE == LE_SOLO && !HW), "lane = env kernel: activation states run the solo form, without the hwsim stage");
 	using OV = PeSlots<T>;
 	using XS6 = XfSlots<T>;
 	constexpr int LPE = PIPE ? (1 << 20) : (DUO ? LP - DuoSlots<NV>::n : LP);
@@ -402,8 +403,9 @@ DEVI void lane_env_body(const KernelParams MJB_AS4 *__restrict__ P, const int ns
 	const int env = live ? env_raw : env_hi - 1;
 	const size_t ev = (size_t)env;
 
-	// ---- the env's state: (qpos, qvel) in LDS, the OU noise state in registers
+	// ---- the env's state: (qpos, qvel) in LDS, the OU noise state and the activation states (mjData.act, NA > 0) in registers
 	double cn[NU > 0 ? NU : 1];
+	[[maybe_unused]] double act[NA > 0 ? NA : 1];
 	double time;
 	bool badp_next = false, badv_next = false;  // mj_checkPos / mj_checkVel verdict on the state the next step starts from
 	bool wasreset = false;  // mj_resetData ran inside this launch: ctrl / qfrc_applied read as zero from then on (the frame copy of the generic kernels)
@@ -418,6 +420,7 @@ DEVI void lane_env_body(const KernelParams MJB_AS4 *__restrict__ P, const int ns
 			});
 		}
 		sfor<NU>([&](auto I) { cn[I] = DV ? s.ctrlnoise[ev * NU + I] : 0.0; });
+		if constexpr (NA > 0) sfor<NA>([&](auto I) { act[I] = s.act[ev * NA + I]; });
 		time = s.time[ev];
 		if constexpr (DUO) {  // the load is "Euler of step -1": P's verdicts on the loaded state go to V by mail
 			if constexpr (DP) lp[64 * MAIL] = Pair{ (double)((badp_next ? 2 : 0) | (badv_next ? 1 : 0)), 0.0 };
@@ -501,6 +504,7 @@ DEVI void lane_env_body(const KernelParams MJB_AS4 *__restrict__ P, const int ns
 						lp[64 * I] = Pair{ bad ? q0 : oa, bad ? 0.0 : ob };
 					});
 				}
+				if constexpr (NA > 0) sfor<NA>([&](auto I) { act[I] = bad ? 0.0 : act[I]; });
 				time = bad ? 0.0 : time;
 				wasreset = wasreset || bad;
 				rs = bad;
@@ -509,6 +513,9 @@ DEVI void lane_env_body(const KernelParams MJB_AS4 *__restrict__ P, const int ns
 		}
 
 		double qacc[NV], qaccd[NV];  // M^-1 f, and the acceleration Euler advances with: (M + h B)^-1 f under implicit joint damping
+		// (NA > 0) the activation states mj_Euler commits: act + h act_dot, clamped to actrange.  Formed where the forces are assembled, on either trip of the
+		// loop below from the trip's own act -- a lane mj_checkAcc reset forms it again from zero --, and committed once, behind the loop
+		[[maybe_unused]] double actn[NA > 0 ? NA : 1];
 		// (HW) mj_checkAcc reset this lane: the retry runs the stage a second time for it and for no other lane | the stage wrote at this step |
 		// what it wrote to a POSITION / VELOCITY joint's qpos / qvel (applied in mj_Euler)
 		[[maybe_unused]] bool hw_bad = false, hw_wr = false;
@@ -1423,10 +1430,21 @@ DEVI void lane_env_body(const KernelParams MJB_AS4 *__restrict__ P, const int ns
 					double force = 0;
 					const LeTapeAct MJB_AS4 &A = ta[i];
 					const double gear = A.gear;
+					// (NA > 0) an actuator with an activation state: its force is gain * act + bias on the CURRENT act, and the clamped ctrl drives act_dot
+					constexpr bool stateful = NA > 0 && T::act_dyntype[i] != MJB_DYN_NONE;
+					constexpr int ja = stateful ? T::act_actadr[i] : 0;
+					static_assert(!stateful || (ja >= 0 && ja < NA), "lane = env kernel: a stateful actuator's slot of act");
+					[[maybe_unused]] double dot = 0;  // act_dot (zero under mjDSBL_ACTUATION: act keeps its value, clamped)
 					if (act_on) {
 						double c = ctrl[i];
 						if constexpr (T::act_ctrllimited[i]) {
 							if (clamp_on) c = clampd(c, A.ctrllo, A.ctrlhi);
+						}
+						if constexpr (stateful) {
+							const double a0 = act[ja];
+							if constexpr (T::act_dyntype[i] == MJB_DYN_INTEGRATOR) dot = c;
+							else dot = (c - a0) / A.dyntau;  // (filter: the tape holds max(mjMINVAL, dynprm[0]))
+							c = a0;
 						}
 						const double len = sq[j].a * gear, vel = sq[j].b * gear;
 						double gain = 0, bs = 0;
@@ -1442,6 +1460,11 @@ DEVI void lane_env_body(const KernelParams MJB_AS4 *__restrict__ P, const int ns
 						force = gain * c + bs;
 						if constexpr (T::act_forcelimited[i]) force = clampd(force, A.forcelo, A.forcehi);
 						f[j] += gear * force;
+					}
+					if constexpr (stateful) {  // mj_advance's half of mj_Euler for this actuator (advance_act, mjb_step.hip)
+						double a = act[ja] + dt * dot;
+						if constexpr (T::act_actlimited[i]) a = clampd(a, A.actlo, A.acthi);
+						actn[ja] = a;
 					}
 					if (sens_on) {
 						sfor<T::NSENSOR>([&](auto S) {
@@ -1742,6 +1765,7 @@ DEVI void lane_env_body(const KernelParams MJB_AS4 *__restrict__ P, const int ns
 				lp[64 * I] = Pair{ bada ? q0 : oa, bada ? 0.0 : ob };
 			});
 			sfor<NU>([&](auto I) { cn[I] = bada ? 0.0 : cn[I]; });
+			if constexpr (NA > 0) sfor<NA>([&](auto I) { act[I] = bada ? 0.0 : act[I]; });
 			time = bada ? 0.0 : time;
 			wasreset = wasreset || bada;
 			if constexpr (HW) hw_bad = bada;
@@ -1801,6 +1825,7 @@ DEVI void lane_env_body(const KernelParams MJB_AS4 *__restrict__ P, const int ns
 			badp_next |= bad_val(s2.a);  // the next step's mj_checkPos / mj_checkVel
 			badv_next |= bad_val(s2.b);
 		});
+		if constexpr (NA > 0) sfor<NA>([&](auto I) { act[I] = actn[I]; });
 		time += dt;
 		if constexpr (DUO && DP) {
 			lp[64 * MAIL] = Pair{ (double)((badp_next ? 2 : 0) | (badv_next ? 1 : 0)), 0.0 };
@@ -1823,6 +1848,7 @@ DEVI void lane_env_body(const KernelParams MJB_AS4 *__restrict__ P, const int ns
 				s.qvel[ev * NV + I] = s2.b;
 			});
 			s.time[ev] = time;
+			if constexpr (NA > 0) sfor<NA>([&](auto I) { s.act[ev * NA + I] = act[I]; });
 		}
 		if constexpr (DV) {
 			sfor<NU>([&](auto I) { s.ctrlnoise[ev * NU + I] = cn[I]; });

@@ -359,7 +359,9 @@ class Batch:
     def set_lane_env(self, mode):
         """-1 automatic, 0 never, 1 whenever eligible, 2 whenever eligible -- also when the batch carries per-env gravity or parameter blocks
         (set_env_gravity, set_env_body_mass, set_env_dof_params, set_env_joint_stiffness, set_env_actuator_params, ...), which the kernel then reads
-        per env; such a batch runs the generic kernels in every other mode: the lane = env form of the unconstrained fused step (mjb_set_lane_env)."""
+        per env; such a batch runs the generic kernels in every other mode: the lane = env form of the unconstrained fused step (mjb_set_lane_env).
+        Models with actuator activation states (integrator / filter; <intvelocity>, <cylinder>) are eligible too: the kernel carries `act` between
+        get("act") / set("act") and the generic kernels, in its one-wavefront form; not together with a device hwsim stage."""
         _check(self.lib.mjb_set_lane_env(self.ptr, int(mode)), "mjb_set_lane_env")
 
     def set_lane_env_hwsim(self, on=True):

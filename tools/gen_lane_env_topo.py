@@ -33,8 +33,8 @@ def eligible(m):
         return "constraint rows"
     if m["integrator"] != 0:
         return "integrator"
-    if m["nmocap"] or m["ntendon"] or m["neq"] or m["na"]:
-        return "mocap / tendon / equality / activation"
+    if m["nmocap"] or m["ntendon"] or m["neq"]:
+        return "mocap / tendon / equality"
     if m["nq"] != m["nv"] or m["njnt"] != m["nv"]:
         return "a joint with more than one dof"
     for j in range(m["njnt"]):
@@ -49,8 +49,10 @@ def eligible(m):
         if int(m["sensor_type"][i]) in (23, 24) and (m["sensor_refid"][i] >= 0 or int(m["sensor_objtype"][i]) not in (1, 2, 6)):
             return "frame sensor with a reference frame / unsupported object"
     for i in range(m["nu"]):
-        if m["actuator_trntype"][i] != 0 or m["actuator_dyntype"][i] != 0:
+        if m["actuator_trntype"][i] != 0 or int(m["actuator_dyntype"][i]) not in (0, 1, 2):  # none, integrator, filter
             return "actuator transmission / dynamics"
+    if sum(int(d) != 0 for d in m["actuator_dyntype"]) != m["na"]:
+        return "activation states without an actuator of their own"
     return None
 
 
@@ -69,7 +71,7 @@ def emit(name, m):
     body_jnt = [int(m["body_jntadr"][b]) if m["body_jntnum"][b] == 1 else -1 for b in range(nb)]
     s = "struct LeTopo_%s {\n" % name
     s += '\tstatic constexpr const char *name = "%s";\n' % name
-    for k in ("nbody", "nq", "nv", "nu", "njnt", "nsite", "nsensor", "nsensordata", "nM"):
+    for k in ("nbody", "nq", "nv", "nu", "na", "njnt", "nsite", "nsensor", "nsensordata", "nM"):
         s += "\tstatic constexpr int %s = %d;\n" % (k.upper() if k != "nM" else "NM", m[k])
     s += arr("body_parentid", m["body_parentid"])
     s += arr("body_rootid", m["body_rootid"])
@@ -84,6 +86,11 @@ def emit(name, m):
     s += arr("act_biastype", m["actuator_biastype"])
     s += arr("act_ctrllimited", m["actuator_ctrllimited"])
     s += arr("act_forcelimited", m["actuator_forcelimited"])
+    # activation states (mjData.act): the kind of each actuator's dynamics, its slot of act (-1: stateless), whether actrange clamps it
+    stateful = m["na"] > 0
+    s += arr("act_dyntype", m["actuator_dyntype"])
+    s += arr("act_actadr", m["actuator_actadr"] if stateful else [0] * m["nu"])
+    s += arr("act_actlimited", m["actuator_actlimited"] if stateful else [0] * m["nu"])
     s += arr("site_bodyid", m["site_bodyid"])
     s += arr("site_sameframe", m["site_sameframe"])
     s += arr("sensor_type", m["sensor_type"])
