@@ -134,7 +134,15 @@ int mjb_device_count(void);
  * Caps of the one-env-per-wavefront kernels: nv <= 64; nefcmax <= 128 under PGS (64 with elliptic contacts) and a per-env frame within one
  * CU's LDS (160 KB); nefcmax <= 1024 under Newton / CG, with a frame of any size.  Newton / CG models with more than 256 rows of capacity, or
  * whose full frame exceeds the LDS budget, run the row-slot solver, and any of their frames that exceeds the budget lives in HBM
- * (mjb_model_frame_info).  Beyond a cap the call fails with MJB_EUNSUPPORTED. */
+ * (mjb_model_frame_info).  Beyond a cap the call fails with MJB_EUNSUPPORTED.
+ *
+ * body_gravcomp[nbody] (MuJoCo >= 2.3.1): mj_passive adds, for every body b >= 1 with body_gravcomp[b] != 0, the force
+ * -gravity * body_mass[b] * body_gravcomp[b] at xipos[b] to qfrc_passive through the point Jacobian (mj_applyFT without torque) -- unless
+ * mjDSBL_PASSIVE or mjDSBL_GRAVITY is set or gravity is zero.  Any finite value is taken (above 1 and below 0 too); a non-finite one fails
+ * with MJB_EINVAL.  The mass and gravity are the env's (mjb_set_env_mass_params / mjb_set_env_gravity).  A body without a dof above it (welded to
+ * the world, mocap) contributes nothing.  Energy, sensors and qfrc_bias do not see the term.  A model with a non-zero entry matches no compiled-in
+ * topology of the lane = env kernel: an eligible one is built by hiprtc (mjb_model_lane_env == -2) and runs the one-wavefront form whatever form
+ * is asked for; the split step stands down (mjb_model_split_step == -1). */
 mjb_model *mjb_compile(const mjb_model_desc *desc);
 void mjb_free_model(mjb_model *m); /* mj_deleteModel, mujoco_env.cpp:747 */
 

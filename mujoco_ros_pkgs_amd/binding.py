@@ -89,7 +89,9 @@ def make_desc(model):
             rows = int(model[a])
             cols = int(b)
             dt = np.int32 if kind == "ARR_I" else np.float64
-            arr = np.ascontiguousarray(np.asarray(model[name], dtype=dt).reshape(-1))
+            # (body_gravcomp: a model dict built by hand before the field existed has none -- no body is compensated)
+            src = np.zeros(rows * cols, dt) if name == "body_gravcomp" and name not in model else model[name]
+            arr = np.ascontiguousarray(np.asarray(src, dtype=dt).reshape(-1))
             if arr.size != rows * cols:
                 raise ValueError(f"model field {name}: expected {rows}x{cols}, got {arr.size}")
             if arr.size == 0:

@@ -102,6 +102,7 @@ struct mjb_model {
 	std::vector<double> dof_act_mom;  // moment arm of entry t of the per-dof actuator lists (dof_act_adr / dof_act_id)
 	int act_tendon = 0;               // some actuator drives a tendon
 	std::vector<int> site_act;        // actuators with a site transmission, in actuator order (DevModel::site_act)
+	std::vector<int> gravcomp_body;   // bodies with body_gravcomp != 0, ascending (DevModel::gravcomp_body; its size is mjModel.ngravcomp)
 	std::vector<double> damp_int;  // [nv] -diag(D) of the integrator's implicit matrix M + h diag(.): dof_damping (Euler) / implicitfast's constant velocity derivative
 	std::vector<int> lim_i;        // [njnt + ntendon][4]
 	int sens_ncopy[3] = { 0, 0, 0 }, sens_nslow[3] = { 0, 0, 0 }, sens_ncopy_max = 0;
@@ -998,6 +999,15 @@ mjb_model *mjb_compile(const mjb_model_desc *desc)
 		}
 		if (oks) M->site_act.push_back(i);
 	}
+	// gravity compensation: any finite coefficient (above 1 and below 0 too); the bodies that have one
+	for (int b = 0; b < h.nbody; b++) {
+		if (!std::isfinite(h.body_gravcomp[b])) {
+			fail(MJB_EINVAL, "mjb_compile: body_gravcomp[%d] is not finite", b);
+			delete M;
+			return nullptr;
+		}
+		if (b > 0 && h.body_gravcomp[b] != 0) M->gravcomp_body.push_back(b);
+	}
 	// velocity-group start of each dof (hinge/slide: itself; ball: first of 3; free: first of each triple)
 	M->dof_jstart.resize(h.nv);
 	for (int dd = 0; dd < h.nv; dd++) {
@@ -1206,12 +1216,13 @@ mjb_model *mjb_compile(const mjb_model_desc *desc)
 	for (int b = 1; b < h.nbody; b++)
 		for (int i = 0; i < h.nv; i++)
 			if ((M->body_dofmask[2 * b + (i >> 5)] >> (i & 31)) & 1) M->dof_bodymask[2 * i + (b >> 5)] |= (int)(1u << (b & 31));
+	const bool gravcomp = !M->gravcomp_body.empty();  // (such a model matches no compiled-in topology; the split step's smooth kernel has no such term and stands down)
 	M->le_topo = mjb_lane_env_match(&h);
 	if (M->le_topo < 0 && mjb_lane_env_eligible(&h)) M->le_topo = MJB_LE_TOPO_JIT;
 	// the split step (smooth half in lane = env form, constraint half one env per wavefront): the constraint half is kernel variant 9's -- plain PGS,
 	// pyramidal / frictionless contacts, nv <= 16, no stage that needs mj_rnePostConstraint
 	M->sm_topo = -1;
-	if (h.nefcmax > 0 && h.solver == MJB_SOL_PGS && !(h.cone == MJB_CONE_ELLIPTIC && h.nconmax > 0) && h.nv <= 16 && !M->need_rnepost && h.nefcmax <= 128)
+	if (!gravcomp && h.nefcmax > 0 && h.solver == MJB_SOL_PGS && !(h.cone == MJB_CONE_ELLIPTIC && h.nconmax > 0) && h.nv <= 16 && !M->need_rnepost && h.nefcmax <= 128)
 		M->sm_topo = mjb_smooth_match(&h);
 	if (M->le_topo != MJB_LE_TOPO_NONE || M->sm_topo >= 0) {
 		M->le_tape.assign(mjb_lane_env_tape_doubles(&h), 0.0);
@@ -1536,7 +1547,7 @@ mjb_batch *mjb_make_batch(const mjb_model *M, int nenv, int device)
 	size_t nt = M->M_rowdof.size() + M->M_coldof.size() + M->dof_depth.size() + M->dof_jstart.size() +
 	            M->body_rec.size() + M->body_rec2.size() + M->dof_rec.size() + M->fac_ops.size() + M->fac_beg.size() +
 	            M->body_dofmask.size() + M->body_submask.size() + M->M_dense.size() + M->M_sym.size() + M->body_anc.size() + M->dof_bodymask.size() + M->body_dofanc.size() + M->dof_rec2.size() + M->jnt_rec.size() + M->flv_hdr.size() + M->flv_rec.size() + M->flv_ent.size() + M->sens_copy.size() + M->sens_slow.size() + M->dof_act_adr.size() +
-	            M->dof_act_id.size() + M->pair_i.size() + M->lim_i.size() + M->site_act.size() + 108;
+	            M->dof_act_id.size() + M->pair_i.size() + M->lim_i.size() + M->site_act.size() + M->gravcomp_body.size() + 112;
 	size_t bytes_i = ((ni + nt) * sizeof(int) + 15) & ~size_t(15);
 	// (the lane = env tape starts on a 64-byte boundary of the blob: wide scalar loads)
 	const size_t o_damp = nd + M->pair_d.size() + M->lim_d.size() + M->sub_S.size();
@@ -1564,7 +1575,7 @@ mjb_batch *mjb_make_batch(const mjb_model *M, int nenv, int device)
 	size_t o_row = put(M->M_rowdof), o_col = put(M->M_coldof), o_dep = put(M->dof_depth), o_js = put(M->dof_jstart);
 	size_t o_br = put(M->body_rec), o_br2 = put(M->body_rec2), o_dr = put(M->dof_rec), o_fo = put(M->fac_ops),
 	       o_fb = put(M->fac_beg), o_dm = put(M->body_dofmask), o_sm = put(M->body_submask), o_md = put(M->M_dense), o_ms = put(M->M_sym), o_an = put(M->body_anc), o_db = put(M->dof_bodymask), o_sc = put(M->sens_copy), o_ss = put(M->sens_slow),
-	       o_aa = put(M->dof_act_adr), o_ai = put(M->dof_act_id), o_pi = put(M->pair_i), o_li = put(M->lim_i), o_da = put(M->body_dofanc), o_dr2 = put(M->dof_rec2), o_jr = put(M->jnt_rec), o_fh = put(M->flv_hdr), o_fr = put(M->flv_rec), o_fe = put(M->flv_ent), o_sa = put(M->site_act);
+	       o_aa = put(M->dof_act_adr), o_ai = put(M->dof_act_id), o_pi = put(M->pair_i), o_li = put(M->lim_i), o_da = put(M->body_dofanc), o_dr2 = put(M->dof_rec2), o_jr = put(M->jnt_rec), o_fh = put(M->flv_hdr), o_fr = put(M->flv_rec), o_fe = put(M->flv_ent), o_sa = put(M->site_act), o_gc = put(M->gravcomp_body);
 	if (nd) memcpy(hd, M->hdbl.data(), nd * sizeof(double));
 	memcpy(hd + nd, M->pair_d.data(), M->pair_d.size() * sizeof(double));
 	memcpy(hd + nd + M->pair_d.size(), M->lim_d.data(), M->lim_d.size() * sizeof(double));
@@ -1633,6 +1644,8 @@ mjb_batch *mjb_make_batch(const mjb_model *M, int nenv, int device)
 	dm.act_tendon = M->act_tendon;
 	dm.site_act = (mjb_ciptr)(di + o_sa);
 	dm.nsite_act = (int)M->site_act.size();
+	dm.gravcomp_body = (mjb_ciptr)(di + o_gc);
+	dm.ngravcomp = (int)M->gravcomp_body.size();
 	dm.sub_nt = M->sub_nt;
 	dm.le_tape = M->le_tape.empty() ? (mjb_cdptr) nullptr : (mjb_cdptr)(dd + o_tape);
 	dm.lim_i = (mjb_ciptr)(di + o_li);

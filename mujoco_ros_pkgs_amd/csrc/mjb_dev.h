@@ -85,6 +85,10 @@ struct DevModel {
 	// computes one row of nv per actuator into the frame (FrameLayout::act_mom) at every forward evaluation (mjb_step.hip, site_transmission)
 	mjb_ciptr site_act;      // [nsite_act] actuator ids
 	int nsite_act;
+	// gravity compensation (mjModel.body_gravcomp): the bodies b >= 1 with a non-zero coefficient, ascending; mjModel.ngravcomp of them.  The passive
+	// stage adds their forces to qfrc_passive from xipos, cdof and subtree_com of the position stage (mjb_step.hip, gravcomp): no frame storage
+	mjb_ciptr gravcomp_body;  // [ngravcomp]
+	int ngravcomp;
 };
 
 // (64-byte records: one s_load_dwordx16 per half)

@@ -131,6 +131,8 @@ static bool le_dyntype_ok(const mjb_model_desc *h, int i)
 int mjb_lane_env_match(const mjb_model_desc *h)
 {
 	if (!le_plain_tree(h)) return -1;
+	for (int b = 1; b < h->nbody; b++)
+		if (h->body_gravcomp[b] != 0) return -1;  // (gravity compensation is a compile-time flag per body, LeGc: no compiled-in topology has one set)
 #define MJB_LE_X(id, T) \
 	if (topo_matches<T>(*h)) return id;
 	MJB_LE_TOPOS(MJB_LE_X)
@@ -226,6 +228,7 @@ std::string topo_source(const mjb_model_desc &h)
 	arr("body_rootid", h.nbody, [&](int i) { return h.body_rootid[i]; });
 	arr("body_jnt", h.nbody, [&](int i) { return h.body_jntnum[i] == 1 ? h.body_jntadr[i] : -1; });
 	arr("body_sameframe", h.nbody, [&](int i) { return h.body_sameframe[i] != 0; });
+	arr("body_gc", h.nbody, [&](int i) { return i > 0 && h.body_gravcomp[i] != 0; });
 	arr("jnt_type", h.njnt, [&](int i) { return h.jnt_type[i]; });
 	arr("jnt_bodyid", h.njnt, [&](int i) { return h.jnt_bodyid[i]; });
 	arr("dof_parentid", h.nv, [&](int i) { return h.dof_parentid[i]; });
@@ -627,6 +630,7 @@ void mjb_lane_env_tape(const mjb_model_desc *h, double *tape)
 		for (int k = 0; k < 4; k++) t.quat[k] = h->body_quat[4 * b + k];
 		le_ibody(h->body_iquat + 4 * b, h->body_inertia + 3 * b, t.ibody);
 		t.mass = h->body_mass[b];
+		t.pad[0] = h->body_gravcomp[b];  // (gravity compensation: read where the topology flags the body, LeGc)
 		if (h->body_jntnum[b] == 1) {
 			const int j = h->body_jntadr[b];
 			for (int k = 0; k < 3; k++) { t.jaxis[k] = h->jnt_axis[3 * j + k]; t.jpos[k] = h->jnt_pos[3 * j + k]; }
@@ -680,6 +684,7 @@ struct LePlanIn {
 	bool fit;           // a hiprtc-built model: the layouts are counted for it, and what does not fit a CU's LDS steps down
 	int nv, nmov, nbody;  // ... from these: dofs, moving bodies (mjb_lane_env_xfrc_slots), bodies
 	int na;             // ... and its activation states: the one-wavefront form alone carries them, and no build with the hwsim stage
+	bool gc;            // ... and whether a body has gravity compensation: the one-wavefront form alone has the term, in every build
 };
 
 LeVariant le_plan(const LePlanIn &in)
@@ -690,28 +695,28 @@ LeVariant le_plan(const LePlanIn &in)
 	// the LDS budget per wavefront from the CUs the batch leaves idle: one wavefront per CU may take all of its LDS, two half of it each
 	const int ncu = in.ncu, waves = (in.nenv_batch + 63) / 64;
 	v.lds_kb = (in.lds_kb == 40 || in.lds_kb == 80 || in.lds_kb == 160) ? in.lds_kb : ((ncu > 0 && waves <= ncu) ? 160 : ((ncu > 0 && waves <= 2 * ncu) ? 80 : 40));
-	// the form: more than one wavefront per 64 envs in the plain build alone
-	if (plain && in.form > 0 && v.lds_kb < 80) {
+	// the form: more than one wavefront per 64 envs in the plain build alone.  A model with activation states (act lives in the registers of the one
+	// wavefront that assembles the forces and integrates) or gravity compensation (the one-wavefront form alone has the term) -- always hiprtc's --
+	// is planned as if form 0 had been asked for, whatever is: the same budget and lanes per wavefront as that request
+	const int form = (in.fit && (in.na > 0 || in.gc)) ? 0 : in.form;
+	if (plain && form > 0 && v.lds_kb < 80) {
 		// a forced multi-wavefront form on a batch that would run four wavefronts per CU: the two halves at two per CU
 		v.form = 1;
 		v.lds_kb = 80;
-	} else if (plain && v.wave_lanes == 64 && v.lds_kb >= 80 && in.form != 0 && (in.form > 0 || waves <= (in.duo_max_waves >= 0 ? in.duo_max_waves : 2 * ncu))) {
+	} else if (plain && v.wave_lanes == 64 && v.lds_kb >= 80 && form != 0 && (form > 0 || waves <= (in.duo_max_waves >= 0 ? in.duo_max_waves : 2 * ncu))) {
 		// two wavefronts per 64 envs while the batch leaves at least every second SIMD idle: the step's position half and velocity half side by side ...
 		v.form = 1;
 		// ... pipelined (nothing computed twice) when a workgroup has a CU's LDS to itself; form 1 asked for: the two halves only
-		if (v.lds_kb == 160 && in.form != 1) v.form = 2;
+		if (v.lds_kb == 160 && form != 1) v.form = 2;
 		// ... and three wavefronts (the pose chain alone on the first) while three SIMDs per block are there: the same LDS layout, so the same bound
-		if (v.form == 2 && in.form != 2 && 3 * waves <= 4 * ncu) v.form = 3;
+		if (v.form == 2 && form != 2 && 3 * waves <= 4 * ncu) v.form = 3;
 		// ... its sweep on four when the block still has a SIMD of its CU to itself per wavefront: the pose wavefront's chain cut in two
 		if (v.form == 3) v.sweep = (in.sweep == 3 || in.sweep == 4) ? in.sweep : (waves <= ncu ? 4 : 3);
 	}  // (otherwise -- the overlay / hwsim / xfrc builds whatever is asked for -- the solo form at that budget)
 	if (!in.fit) return v;
-	if (in.na > 0) {  // (act lives in the registers of the one wavefront that assembles the forces and integrates; a model with na > 0 is always hiprtc's)
-		if (in.build == MJB_LE_HWSIM) {
-			v.unavailable = "no build of the kernel has both the hwsim stage and activation states";
-			return v;
-		}
-		v.form = 0, v.sweep = 0;
+	if (in.na > 0 && in.build == MJB_LE_HWSIM) {
+		v.unavailable = "no build of the kernel has both the hwsim stage and activation states";
+		return v;
 	}
 	// a hiprtc-built model may be larger than the compiled-in ones: the smallest budget its (qpos, qvel) pairs and body forces fit (fewer wavefronts per
 	// CU then), and of the forms the first one down whose layout fits
@@ -785,8 +790,11 @@ template <class T> int le_go_topo(const LeVariant &v, const LeLaunch &a)
 }
 LePlanIn le_plan_in(const mjb_model_desc *fit_model, int ncu, int nenv_batch, LeBuild build, int form, int duo_max_waves, int sweep, int lds_kb, int wave_lanes)
 {
-	LePlanIn in{ ncu, nenv_batch, build, form, duo_max_waves, sweep, lds_kb, wave_lanes, fit_model != nullptr, 0, 0, 0, 0 };
-	if (fit_model) in.nv = fit_model->nv, in.nmov = mjb_lane_env_xfrc_slots(fit_model), in.nbody = fit_model->nbody, in.na = fit_model->na;
+	LePlanIn in{ ncu, nenv_batch, build, form, duo_max_waves, sweep, lds_kb, wave_lanes, fit_model != nullptr, 0, 0, 0, 0, false };
+	if (fit_model) {
+		in.nv = fit_model->nv, in.nmov = mjb_lane_env_xfrc_slots(fit_model), in.nbody = fit_model->nbody, in.na = fit_model->na;
+		for (int b = 1; b < fit_model->nbody; b++) in.gc = in.gc || fit_model->body_gravcomp[b] != 0;
+	}
 	return in;
 }
 }  // namespace

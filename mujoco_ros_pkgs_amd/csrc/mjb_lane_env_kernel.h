@@ -289,6 +289,12 @@ template <class T> struct XfSlots {
 	static constexpr int n = PeSlots<T>::nmb(T::NBODY);
 };
 
+// Gravity compensation (mjModel.body_gravcomp): a topology may flag its compensated bodies, body_gc[NBODY] (the hiprtc-built ones do; a topology
+// without the array has none).  The coefficient itself is run-time data, LeTapeBody::pad[0].
+template <class T, class = void> struct LeGc { static constexpr bool on(int) { return false; } };
+template <class T> struct LeGc<T, decltype((void)T::body_gc)> { static constexpr bool on(int b) { return T::body_gc[b] != 0; } };
+template <class T> constexpr bool le_any_gc() { for (int b = 1; b < T::NBODY; b++) if (LeGc<T>::on(b)) return true; return false; }
+
 // ROLE of a wavefront (lane_env_body's template argument, an int with these values): which part of the step of its block's 64 envs it runs.
 enum LeRole : int {
 	// one wavefront runs the whole step of its 64 envs
@@ -352,6 +358,10 @@ template <int NV> struct DuoSlots { static constexpr int n = le_exchange_slots(N
 // (XfSlots), coalesced, one region ahead of its use.  mj_resetData zeroes xfrc_applied: a lane reset inside the launch reads zero from then on
 // (the retry after a mj_checkAcc reset included), and at the launch's end its rows of xfrc_applied and its column of the table are zeroed in HBM.
 // Solo form only; composes with PE, not with HW.
+// Gravity compensation (LeGc<T>: a compile-time flag per body, no code for the others): mj_passive's force F = -gravity * mass * gravcomp at the
+// body's xipos is folded where XF folds a wrench -- (xd x F ; F) about the tree root's origin off the body's cfrc_body -- with the step's own
+// grav[] (zero under mjDSBL_GRAVITY, the env's under PE), the mass the inertial half already holds (the env's under PE) and pas_on.  The kernel keeps
+// no qfrc_passive: the term reaches qfrc_smooth through the leaf -> root projection.  Solo form only, every build of it.
 template <class T, int LP, int ROLE = LE_SOLO, bool PE = false, bool HW = false, bool XF = false>
 DEVI void lane_env_body(const KernelParams MJB_AS4 *__restrict__ P, const int nsteps, const unsigned int step0, const int env_lo, const int env_hi,
                         unsigned char *const smem_le)
@@ -376,6 +386,7 @@ DEVI void lane_env_body(const KernelParams MJB_AS4 *__restrict__ P, const int ns
 	static_assert(!HW || (ROLE == LE_SOLO && !PE), "lane = env kernel: the hwsim stage runs the solo form, without per-env overrides");
 	static_assert(!XF || (ROLE == LE_SOLO && !HW), "lane = env kernel: xfrc_applied runs the solo form, without the hwsim stage");
 	static_assert(NA == 0 || (ROLE == LE_SOLO && !HW), "lane = env kernel: activation states run the solo form, without the hwsim stage");
+	static_assert(!le_any_gc<T>() || ROLE == LE_SOLO, "lane = env kernel: gravity compensation runs the solo form");
 	using OV = PeSlots<T>;
 	using XS6 = XfSlots<T>;
 	constexpr int LPE = PIPE ? (1 << 20) : (DUO ? LP - DuoSlots<NV>::n : LP);
@@ -1037,6 +1048,16 @@ DEVI void lane_env_body(const KernelParams MJB_AS4 *__restrict__ P, const int ns
 							for (int k = 0; k < 6; k++) { const double v = pinv(xw[b][k]); w[k] = seld(wasreset, 0.0, v); }  // (zero after mj_resetData; load first, then select)
 							cross3(tq, xd, w);
 							for (int k = 0; k < 3; k++) { cf[k] -= w[3 + k] + tq[k]; cf[3 + k] -= w[k]; }
+						}
+						if constexpr (LeGc<T>::on(b)) {
+							// mj_passive, body_gravcomp: -gravity * mass * gravcomp at xipos, folded as the wrench above (no torque)
+							double xd[3], F[3], tq[3];
+							if constexpr (r == b) for (int k = 0; k < 3; k++) xd[k] = xipos[k] - pos[k];
+							else for (int k = 0; k < 3; k++) xd[k] = xipos[k] - xpos[r][k];
+							const double sc = pas_on ? -mass * tb[b].pad[0] : 0.0;
+							for (int k = 0; k < 3; k++) F[k] = sc * grav[k];
+							cross3(tq, xd, F);
+							for (int k = 0; k < 3; k++) { cf[k] -= tq[k]; cf[3 + k] -= F[k]; }
 						}
 						constexpr int q0 = LD::slot(b);
 						lp[64 * q0] = Pair{ cf[0] + t1[0], cf[1] + t1[1] };

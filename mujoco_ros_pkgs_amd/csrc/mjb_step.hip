@@ -1882,6 +1882,33 @@ template <int G, bool OBL> STAGE void com_vel(CModel m, CLayout L, const Env &e)
 }
 
 // ------------------------------------------------------------------------------------------------
+// gravity compensation (mj_passive, body_gravcomp): every compensated body b gets F_b = -gravity * mass_b * gravcomp_b at xipos_b,
+// qfrc_passive += J_p(b, xipos_b)' F_b (mj_applyFT without torque).  Lane = dof: the column of point_jac, summed over the compensated
+// bodies the dof moves, in body order.  Mass and gravity are the env's.  Off with mjDSBL_PASSIVE / mjDSBL_GRAVITY and under zero gravity.
+// Out of line, like site_transmission: models without gravcomp reach neither these registers nor these instruction-cache lines.
+// ------------------------------------------------------------------------------------------------
+template <int G> __device__ __attribute__((noinline)) void gravcomp(CModel m, CLayout L, const EnvLite e)
+{
+	double *f = e.f;
+	double g[3];
+	ld3(g, f + L.gravity);
+	const bool on = !(m.disableflags & (MJB_DSBL_PASSIVE | MJB_DSBL_GRAVITY)) && (g[0] != 0 || g[1] != 0 || g[2] != 0);
+	for (int d = e.lane; d < m.nv && on; d += G) {
+		double acc = 0;
+		for (int r = 0; r < m.ngravcomp; r++) {
+			const int b = m.gravcomp_body[r];
+			double p[3], jp[3], jr[3];
+			ld3(p, f + L.xipos + 3 * b);
+			point_jac(m, L, f, b, p, d, jp, jr);
+			const double s = -MP_BODY_MASS(m, e, b) * m.body_gravcomp[b];
+			acc += s * dot3(jp, g);
+		}
+		f[L.qfrc_passive + d] += acc;
+	}
+	gsync<G>();
+}
+
+// ------------------------------------------------------------------------------------------------
 // A8  passive forces: joint springs and dof dampers
 // ------------------------------------------------------------------------------------------------
 template <int G, bool CACHE = false> STAGE void passive(CModel m, CLayout L, const Env &e)
@@ -1951,6 +1978,7 @@ template <int G, bool CACHE = false> STAGE void passive(CModel m, CLayout L, con
 			}
 		gsync<G>();
 	}
+	if (m.ngravcomp > 0) gravcomp<G>(m, L, lite(e));
 }
 
 // ------------------------------------------------------------------------------------------------

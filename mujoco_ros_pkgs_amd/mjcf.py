@@ -405,8 +405,9 @@ class _Compiler:
             b = dict(name=a.get("name", f"body{bid}"), parent=parent,
                      pos=_floats(a.get("pos", "0 0 0"), 3, "body pos"),
                      quat=self._orientation(a, "body"), inertial=None, joints=[], geoms=[], sites=[])
-            if float(a.get("gravcomp", 0)) != 0:
-                raise MjcfError(f"body '{b['name']}': gravcomp is not supported")
+            b["gravcomp"] = float(a.get("gravcomp", 0))
+            if not np.isfinite(b["gravcomp"]):
+                raise MjcfError(f"body '{b['name']}': gravcomp must be finite")
             b["mocap"] = a.get("mocap", "false") == "true"
             if b["mocap"] and parent != 0:
                 raise MjcfError(f"mocap body '{b['name']}' must be a child of the world")
@@ -880,6 +881,7 @@ class _Compiler:
             elif b["geoms"] and bi > 0 and self.inertiafromgeom != "false":
                 body_mass[bi], body_ipos[bi], body_iquat[bi], body_inertia[bi] = _inertia_from_geoms(b["geoms"])
         m.update(body_mass=body_mass, body_inertia=body_inertia, body_ipos=body_ipos, body_iquat=body_iquat)
+        m["body_gravcomp"] = np.array([b.get("gravcomp", 0.0) for b in B], D)
         m["body_sameframe"] = np.array(
             [int(np.all(body_ipos[i] == 0) and np.all(body_iquat[i] == [1, 0, 0, 0])) for i in range(nbody)], I)
         sub = body_mass.copy()
@@ -1421,6 +1423,17 @@ def with_joint_params(model, damping=None, armature=None, frictionloss=None, sti
         m[key] = a
     if armature is not None:
         _rederive_invweight0(m)
+    return m
+
+
+def with_gravcomp(model, values):
+    """A copy of a compiled model with a new body_gravcomp [nbody] (the world's entry is ignored by mj_passive).  Nothing is derived from
+    it; what mjb_compile chooses by it -- the kernels a model with a non-zero entry runs -- follows when the copy is compiled."""
+    m = Model(dict(model))
+    a = np.asarray(values, dtype=np.float64).reshape(int(m["nbody"])).copy()
+    if not np.all(np.isfinite(a)):
+        raise MjcfError("with_gravcomp: body_gravcomp must be finite")
+    m["body_gravcomp"] = a
     return m
 
 

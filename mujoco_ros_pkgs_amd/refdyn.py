@@ -135,6 +135,24 @@ def potential(m, qpos):
     return -sum(m["body_mass"][b] * np.dot(g, kin["xipos"][b]) for b in range(1, m["nbody"]))
 
 
+def gravcomp_force(m, qpos):
+    """Generalized force of MuJoCo's body gravity compensation (mj_passive, body_gravcomp), from its definition:
+
+        sum_b  Jp_b' (-g m_b gc_b),      Jp_b the translational Jacobian of body b at its centre of mass,
+
+    zero when gravity is zero.  (The disable flags are the caller's business: this is the term itself.)"""
+    qpos = np.asarray(qpos, dtype=np.float64)
+    kin = kinematics(m, qpos)
+    g = np.asarray(m["gravity"], dtype=np.float64)
+    gc = np.asarray(m["body_gravcomp"], dtype=np.float64) if "body_gravcomp" in m else np.zeros(m["nbody"])
+    out = np.zeros(m["nv"])
+    for b in range(1, m["nbody"]):
+        if gc[b] != 0:
+            jp, _ = jac_point(m, kin, b, kin["xipos"][b])
+            out += jp.T @ (-g * m["body_mass"][b] * gc[b])
+    return out
+
+
 def bias_lagrange(m, qpos, qvel, eps=1e-6):
     """Coriolis + centrifugal + gravity generalized force c(q,v) such that  M a + c = tau,
     from the Lagrangian (central finite differences of M(q) and V(q)).  Hinge/slide joints only

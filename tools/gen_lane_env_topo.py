@@ -67,6 +67,8 @@ def emit(name, m):
     why = eligible(m)
     if why:
         raise SystemExit("%s does not fit the lane = env kernel: %s" % (name, why))
+    if "body_gravcomp" in m and any(m["body_gravcomp"][1:] != 0):  # (a hand-built dict from before the field has none)
+        raise SystemExit("%s has gravity compensation: mjb_lane_env_match takes no such model for a compiled-in topology" % name)
     nb = m["nbody"]
     body_jnt = [int(m["body_jntadr"][b]) if m["body_jntnum"][b] == 1 else -1 for b in range(nb)]
     s = "struct LeTopo_%s {\n" % name
@@ -77,6 +79,9 @@ def emit(name, m):
     s += arr("body_rootid", m["body_rootid"])
     s += arr("body_jnt", body_jnt)
     s += arr("body_sameframe", m["body_sameframe"])
+    # gravity compensation: a flag per body (the coefficient is run-time data).  Always zeros here -- a model with gravcomp was refused above and is
+    # hiprtc's, whose topology text (mjb_lane_env.hip, topo_source) sets the flags
+    s += arr("body_gc", [0] * nb)
     s += arr("jnt_type", m["jnt_type"])
     s += arr("jnt_bodyid", m["jnt_bodyid"])
     s += arr("dof_parentid", m["dof_parentid"])
