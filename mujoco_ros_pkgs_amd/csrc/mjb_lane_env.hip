@@ -81,6 +81,9 @@ __global__ void __launch_bounds__(64 * NW) mjb_lane_env_trio_kernel(const Kernel
 	else lane_env_trio<T, 160>(P, nsteps, step0, env_lo, env_hi, smem_le);
 }
 
+// the joint's anchor is off centre (jnt_pos != 0): structure of a topology, LeOffc
+static bool le_jnt_offc(const mjb_model_desc &h, int j) { return h.jnt_pos[3 * j] != 0 || h.jnt_pos[3 * j + 1] != 0 || h.jnt_pos[3 * j + 2] != 0; }
+
 template <class T> bool topo_matches(const mjb_model_desc &h)
 {
 	if (h.nbody != T::NBODY || h.nq != T::NQ || h.nv != T::NV || h.nu != T::NU || h.na != T::NA || h.njnt != T::NJNT || h.nsite != T::NSITE ||
@@ -94,6 +97,9 @@ template <class T> bool topo_matches(const mjb_model_desc &h)
 	}
 	for (int j = 0; j < h.njnt; j++)
 		if (h.jnt_type[j] != T::jnt_type[j] || h.jnt_bodyid[j] != T::jnt_bodyid[j] || h.jnt_qposadr[j] != j || h.jnt_dofadr[j] != j) return false;
+	if constexpr (LeOffc<T>::known)  // (an anchor off centre where the table has none, or the reverse: the compiled-in kernel has no code for this model)
+		for (int j = 0; j < h.njnt; j++)
+			if (le_jnt_offc(h, j) != LeOffc<T>::on(j)) return false;
 	for (int d = 0; d < h.nv; d++)
 		if (h.dof_parentid[d] != T::dof_parentid[d] || h.dof_Madr[d] != T::dof_Madr[d] || h.dof_jntid[d] != d) return false;
 	for (int i = 0; i < h.nu; i++)
@@ -231,6 +237,7 @@ std::string topo_source(const mjb_model_desc &h)
 	arr("body_gc", h.nbody, [&](int i) { return i > 0 && h.body_gravcomp[i] != 0; });
 	arr("jnt_type", h.njnt, [&](int i) { return h.jnt_type[i]; });
 	arr("jnt_bodyid", h.njnt, [&](int i) { return h.jnt_bodyid[i]; });
+	arr("jnt_offc", h.njnt, [&](int i) { return le_jnt_offc(h, i); });
 	arr("dof_parentid", h.nv, [&](int i) { return h.dof_parentid[i]; });
 	arr("dof_Madr", h.nv, [&](int i) { return h.dof_Madr[i]; });
 	arr("act_jnt", h.nu, [&](int i) { return h.actuator_trnid[2 * i]; });

@@ -295,6 +295,18 @@ template <class T, class = void> struct LeGc { static constexpr bool on(int) { r
 template <class T> struct LeGc<T, decltype((void)T::body_gc)> { static constexpr bool on(int b) { return T::body_gc[b] != 0; } };
 template <class T> constexpr bool le_any_gc() { for (int b = 1; b < T::NBODY; b++) if (LeGc<T>::on(b)) return true; return false; }
 
+// Off-centre anchors (mjModel.jnt_pos != 0): a topology may flag them per joint, jnt_offc[NJNT] (the generated and the hiprtc-built ones do, and
+// mjb_lane_env_match compares the flags).  Where the flags are known AND the caller asks for them (USE: the quartet's roles -- every other form keeps
+// its code as it is), "is this anchor off centre" is a constant and the untaken side compiles to nothing; otherwise it is the run-time test on the
+// tape's jpos, wave-uniform.
+template <class T, class = void> struct LeOffc { static constexpr bool known = false; static constexpr bool on(int) { return false; } };
+template <class T> struct LeOffc<T, decltype((void)T::jnt_offc)> { static constexpr bool known = true; static constexpr bool on(int j) { return T::jnt_offc[j] != 0; } };
+template <class T, bool USE, int J> DEVI bool le_offc(const double jx, const double jy, const double jz)
+{
+	if constexpr (USE && LeOffc<T>::known) return LeOffc<T>::on(J);
+	else return jx != 0 || jy != 0 || jz != 0;
+}
+
 // ROLE of a wavefront (lane_env_body's template argument, an int with these values): which part of the step of its block's 64 envs it runs.
 enum LeRole : int {
 	// one wavefront runs the whole step of its 64 envs
@@ -324,8 +336,9 @@ enum LeRole : int {
 	// frame, mj_energyPos, frame sensors, the pose ring; C as the trio's C one body behind X, without the sines, and it publishes cdof; V as the trio's V
 	// one body behind C, with C's cdof instead of its own.  One barrier per MOVING body plus two to drain: sweep phase k has O on the k-th moving body,
 	// X on the one before, C two and V three before; the bodies at rest are O's and X's own business ahead of the phases.
-	// The quartet's tail is split by MATRIX: X keeps its own cdof, reads C's cinert from LDS behind the sweep's last barrier, builds qM a second time
-	// beside C, factors M, solves qacc = M^-1 f and takes mj_checkAcc's decision; C factors M + h B alone, solves the acceleration Euler advances with
+	// The quartet's tail is split by MATRIX: X takes every joint's cdof from C's ring one phase after C wrote it (where V reads it, one phase before C
+	// writes the slot again -- X computes none: it is the wavefront the phases wait for), reads C's cinert from LDS behind the sweep's last barrier,
+	// builds qM a second time beside C from those very numbers, factors M, solves qacc = M^-1 f and takes mj_checkAcc's decision; C factors M + h B alone, solves the acceleration Euler advances with
 	// and integrates SPECULATIVELY -- X's verdict, read by all four behind rendezvous B, either lets the step stand or has C put the old state back.
 	// Nothing but V's qfrc_smooth and the two mail slots crosses LDS, and the step has no barrier the trio's tail does not have.
 	LE_QUAD_O = 8,
@@ -758,7 +771,7 @@ DEVI void lane_env_body(const KernelParams MJB_AS4 *__restrict__ P, const int ns
 						// (the anchor from the body's FINAL frame: xpos + xmat jnt_pos -- the point mj_kinematics' off-centre correction keeps fixed)
 						const double jp[3] = { tj.jpos[0], tj.jpos[1], tj.jpos[2] };
 						double xanch[3] = { xp[0], xp[1], xp[2] }, off[3];
-						if (jp[0] != 0 || jp[1] != 0 || jp[2] != 0) {
+						if (le_offc<T, QUAD, j>(jp[0], jp[1], jp[2])) {
 							double v[3];
 							matvec3(v, xm, jp);
 							for (int k = 0; k < 3; k++) xanch[k] += v[k];
@@ -1115,8 +1128,8 @@ DEVI void lane_env_body(const KernelParams MJB_AS4 *__restrict__ P, const int ns
 						for (int k = 0; k < 4; k++) quat[k] = q[k];
 					}
 					if constexpr (j >= 0) {
-						// (an off-centre anchor, wave-uniform: X needs the frame before the joint motion too)
-						if (A[10] != 0 || A[11] != 0 || A[12] != 0) {
+						// (an off-centre anchor -- the topology's flag, or wave-uniform: X needs the frame before the joint motion too)
+						if (le_offc<T, true, j>(A[10], A[11], A[12])) {
 							lp[64 * (qr + 2)] = Pair{ quat[0], quat[1] };
 							lp[64 * (qr + 3)] = Pair{ quat[2], quat[3] };
 						}
@@ -1177,7 +1190,7 @@ DEVI void lane_env_body(const KernelParams MJB_AS4 *__restrict__ P, const int ns
 					if constexpr (j >= 0) {
 						qp = sp.a;
 						const double jp[3] = { A[10], A[11], A[12] };
-						offc = jp[0] != 0 || jp[1] != 0 || jp[2] != 0;
+						offc = le_offc<T, true, j>(jp[0], jp[1], jp[2]);
 						for (int k = 0; k < 3; k++) xanch[k] = pos[k];
 						if (offc) {
 							const Pair h0 = lp[64 * (qr + 2)], h1 = lp[64 * (qr + 3)];
@@ -1231,27 +1244,18 @@ DEVI void lane_env_body(const KernelParams MJB_AS4 *__restrict__ P, const int ns
 						lp[64 * (rg + 3)] = Pair{ xm[3], xm[4] };
 						lp[64 * (rg + 4)] = Pair{ xm[5], xm[6] };
 						lp[64 * (rg + 5)] = Pair{ xm[7], xm[8] };
-						if constexpr (j >= 0) {  // cdof for X's own leaf -> root walk: C's expressions (consume) on the same pose, kept in registers to the tail
-							double *cd = cdof[j];
-							const double ax[3] = { A[7], A[8], A[9] };
-							double xaxis[3];
-							matvec3(xaxis, xm, ax);
-							if constexpr (T::jnt_type[j] == MJB_JNT_SLIDE) {
-								cd[0] = cd[1] = cd[2] = 0;
-								for (int k = 0; k < 3; k++) cd[3 + k] = xaxis[k];
-							} else {
-								const double jp[3] = { A[10], A[11], A[12] };
-								double xa[3] = { xp[0], xp[1], xp[2] }, off[3];
-								if (jp[0] != 0 || jp[1] != 0 || jp[2] != 0) {
-									double v[3];
-									matvec3(v, xm, jp);
-									for (int k = 0; k < 3; k++) xa[k] += v[k];
-								}
-								for (int k = 0; k < 3; k++) off[k] = -xa[k];  // (root origin - anchor)
-								for (int k = 0; k < 3; k++) cd[k] = xaxis[k];
-								cross3(cd + 3, xaxis, off);
-							}
-						}
+					}
+				};
+				// X, cdof for its own leaf -> root walk: the six doubles C publishes for V (consume), taken from the ring where V takes them -- the phase after
+				// C wrote the slot, one before C writes it again; the last needed body's behind the sweep's last barrier.  Kept in registers to the tail.
+				[[maybe_unused]] auto x_cdof = [&](auto Bq) {
+					constexpr int b = Bq, j = T::body_jnt[b];
+					if constexpr (j >= 0) {
+						constexpr int cq = CD0 + 3 * (((LD::slot(b) - NV) / 3) % 2);
+						const Pair d0 = lp[64 * cq], d1 = lp[64 * (cq + 1)], d2 = lp[64 * (cq + 2)];
+						double *cd = cdof[j];
+						cd[0] = d0.a; cd[1] = d0.b; cd[2] = d1.a; cd[3] = d1.b; cd[4] = d2.a; cd[5] = d2.b;
+						if constexpr (T::jnt_type[j] == MJB_JNT_SLIDE) cd[0] = cd[1] = cd[2] = 0;
 					}
 				};
 				auto x_phase = [&](auto Bq) {
@@ -1264,8 +1268,16 @@ DEVI void lane_env_body(const KernelParams MJB_AS4 *__restrict__ P, const int ns
 					}
 					x_body(Bq);
 					if constexpr (nx < NB) {
-						touch_rec<14>(hA[nx]);
-						touch_rec<10>(hB[nx]);
+						// (the entries X reads of a needed body's record, no others: its orientation is O's, its cdof C's -- the joint axis and qpos0 are a
+						//  slide's business here, jpos an off-centre anchor's, and the inertia matrix nobody's)
+						constexpr int jn = T::body_jnt[nx];
+						const double *const a = hA[nx], *const h = hB[nx];
+						asm volatile("" ::"s"(a[0]), "s"(a[1]), "s"(a[2]), "s"(h[9]));
+						if constexpr (!T::body_sameframe[nx]) asm volatile("" ::"s"(h[0]), "s"(h[1]), "s"(h[2]));
+						if constexpr (jn >= 0) {
+							if constexpr (T::jnt_type[jn < 0 ? 0 : jn] == MJB_JNT_SLIDE) asm volatile("" ::"s"(a[7]), "s"(a[8]), "s"(a[9]), "s"(a[13]));
+							if constexpr (!LeOffc<T>::known || LeOffc<T>::on(jn < 0 ? 0 : jn)) asm volatile("" ::"s"(a[10]), "s"(a[11]), "s"(a[12]));
+						}
 					}
 				};
 				if constexpr (ROLE == LE_QUAD_O || ROLE == LE_QUAD_X) {
@@ -1296,7 +1308,7 @@ DEVI void lane_env_body(const KernelParams MJB_AS4 *__restrict__ P, const int ns
 					}
 				}
 				__builtin_amdgcn_sched_barrier(0);
-				// phase k: O on the k-th needed body, X on the one before, C two, V three before; every wavefront takes the KN + 2 barriers, V's last body comes behind the last one
+				// phase k: O on the k-th needed body, X on the one before, C two, V three before (and X picks up the cdof of V's body); every wavefront takes the KN + 2 barriers, V's last body comes behind the last one
 				sfor<KN + 3>([&](auto Ki) {
 					constexpr int k = Ki + 1;
 					constexpr int kk = k - (ROLE - LE_QUAD_O);  // this role's body, counted among the needed ones
@@ -1306,6 +1318,8 @@ DEVI void lane_env_body(const KernelParams MJB_AS4 *__restrict__ P, const int ns
 						else if constexpr (ROLE == LE_QUAD_X) x_phase(IC<bb>{});
 						else consume(IC<bb>{});
 					}
+					// (X) cdof of the body C handled one phase ago, beside V's read of the same slot; in phase KN + 3, behind the last barrier, the last body's
+					if constexpr (ROLE == LE_QUAD_X && k - 3 >= 1 && k - 3 <= KN) x_cdof(IC<NTH(k - 3 >= 1 ? k - 3 : 1)>{});
 					if constexpr (DV && k == 1) sfor<NV>([&](auto I) { qfa[I] = s.qfrc_applied[ev * NV + I]; });  // (read by the force block behind the sweep: a trip to HBM)
 					if constexpr (k <= KN + 2) {
 						LE_PK(0);

@@ -84,6 +84,9 @@ def emit(name, m):
     s += arr("body_gc", [0] * nb)
     s += arr("jnt_type", m["jnt_type"])
     s += arr("jnt_bodyid", m["jnt_bodyid"])
+    # off-centre anchors: a flag per joint, 1 where jnt_pos != 0 (the offset itself is run-time data).  mjb_lane_env_match compares it: the kernel has
+    # the off-centre code of the flagged joints and of no other
+    s += arr("jnt_offc", [any(float(v) != 0 for v in m["jnt_pos"][j]) for j in range(m["njnt"])])
     s += arr("dof_parentid", m["dof_parentid"])
     s += arr("dof_Madr", m["dof_Madr"])
     s += arr("act_jnt", [m["actuator_trnid"][i][0] for i in range(m["nu"])])
