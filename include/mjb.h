@@ -142,7 +142,13 @@ int mjb_device_count(void);
  * with MJB_EINVAL.  The mass and gravity are the env's (mjb_set_env_mass_params / mjb_set_env_gravity).  A body without a dof above it (welded to
  * the world, mocap) contributes nothing.  Energy, sensors and qfrc_bias do not see the term.  A model with a non-zero entry matches no compiled-in
  * topology of the lane = env kernel: an eligible one is built by hiprtc (mjb_model_lane_env == -2) and runs the one-wavefront form whatever form
- * is asked for; the split step stands down (mjb_model_split_step == -1). */
+ * is asked for; the split step stands down (mjb_model_split_step == -1).
+ *
+ * Sensors: the generic kernels evaluate every type of the enum above.  The lane = env kernel takes jointpos, jointvel, actuatorpos / -vel / -frc, clock,
+ * framepos / framequat, and -- in its one-wavefront form, in a kernel built by hiprtc (mjb_model_lane_env == -2), never a compiled-in topology --
+ * framexaxis / -yaxis / -zaxis, framelinvel, frameangvel, framelinacc, frameangacc on a body / xbody / site without a reference frame, and velocimeter,
+ * gyro, accelerometer, force, torque on a site.  Any other sensor (a reference frame, touch, rangefinder, magnetometer, subtree and limit sensors)
+ * leaves the model to the generic kernels (mjb_model_lane_env == -1). */
 mjb_model *mjb_compile(const mjb_model_desc *desc);
 void mjb_free_model(mjb_model *m); /* mj_deleteModel, mujoco_env.cpp:747 */
 
@@ -291,7 +297,17 @@ int mjb_fused_frame(const mjb_batch *b);
  * splits and hand-overs to and from the generic kernels carry it.  Its launches run the one-wavefront form (mjb_lane_env_last_form() == 0) whatever
  * form is asked for, in the plain, mode-2 and xfrc builds; with a device hwsim stage such a batch keeps the generic kernels (there is no build with
  * both).  Measured on config 2's arm with <intvelocity> on its seven joints and one filter actuator (tools/lane_env_act_rate.py,
- * profiles/lane_env_act.txt): 278.9 against the generic kernel's 196.1 M env-steps/s at 4096 envs (1.42 x), 3121 against 197 at 65 536 (15.9 x), 0.92 / 0.84 of plain franka_like's rate in the same one-wavefront form; the lane = env kernel is ahead at 4096 envs, so mode -1 keeps its 4096-env threshold for these models.  No reference counterpart. */
+ * profiles/lane_env_act.txt): 278.9 against the generic kernel's 196.1 M env-steps/s at 4096 envs (1.42 x), 3121 against 197 at 65 536 (15.9 x), 0.92 / 0.84 of plain franka_like's rate in the same one-wavefront form; the lane = env kernel is ahead at 4096 envs, so mode -1 keeps its 4096-env threshold for these models.  No reference counterpart.
+ * Frame-axis, velocity- and acceleration-stage sensors (the list at mjb_compile): such a model is eligible like any other (mjb_model_lane_env() == -2) and
+ * its launches run the one-wavefront form whatever form is asked for, in the plain, mode-2, hwsim and xfrc builds, with activation states and gravity
+ * compensation.  Velocity sensors are evaluated in the root -> leaf sweep; accelerometer, force, torque, framelinacc and frameangacc in a pass behind the
+ * qacc solve and ahead of mj_checkAcc's verdict (mj_rnePostConstraint: cacc with qacc, cfrc_int with xfrc_applied as cfrc_ext in the xfrc builds), on the
+ * steps that evaluate sensors -- the launch's last one, or every one under mjb_set_sensors_every_step.  One combination keeps the generic kernels: a
+ * written xfrc_applied under mjb_lane_env_set_xfrc with a force / torque sensor on a body that has no joint on its path to the world (the kernel's wrench
+ * table has no slot for such a body; mjb_lane_env_plan answers -1 for the xfrc builds).  Measured on config 2's arm with a wrist IMU, a wrist force /
+ * torque pair, an end-effector framelinvel and a base force sensor (tools/lane_env_sensors_rate.py, profiles/lane_env_sensors.txt): 262 against the
+ * generic kernel's 69 M env-steps/s at 4096 envs (3.8 x), 2783 against 93 at 65 536 (30.1 x); 0.87 / 0.74 of the same arm's rate without those sensors,
+ * and 0.76 / 0.68 of its own rate when sensors are evaluated at every step.  No reference counterpart. */
 int mjb_set_lane_env(mjb_batch *b, int mode);
 /* Opt-in (default off): with on = 1 the device hwsim stage (mjb_hwsim_configure, below) no longer stands the lane = env kernel down.  The batch's
  * eligible launches then run the kernel's one-wavefront form (mjb_lane_env_last_form() == 0, at the LDS budget the batch size gives, whatever form is
@@ -349,7 +365,7 @@ int mjb_model_frame_info(const mjb_model *m, int *full_hbm, int *fused_hbm);
 /* >= 0: index of the compiled-in topology the batch's model matches; -2: none compiled in, but the model's structure fits the kernel -- its
  * first eligible launch builds the kernel for it through hiprtc (libhiprtc.so and csrc/mjb_lane_env_kernel.h next to libmjb.so; a few
  * seconds, cached per process); -3: that build was not possible (mjb_lane_env_error says why) and the generic kernels run; -1: the model does not
- * fit (constraint rows, free / ball joints, RK4, ...).  *used_last (may be NULL) = 1 when the last fused launch ran the lane = env kernel. */
+ * fit (constraint rows, free / ball joints, RK4, a sensor outside the list at mjb_compile, ...).  *used_last (may be NULL) = 1 when the last fused launch ran the lane = env kernel. */
 int mjb_lane_env_info(const mjb_batch *b, int *used_last);
 /* hiprtc builds of the lane = env kernel are kept on disk: $MJB_JIT_CACHE (default $XDG_CACHE_HOME/mjb_jit or ~/.cache/mjb_jit; "0" = off), one code
  * object per (gfx arch, kernel-header fingerprint, LDS budget, form, topology).  Counts of this process: kernels compiled / taken from the cache. */
@@ -375,7 +391,8 @@ int mjb_model_lane_env_overlay(const mjb_model *m, double *out, int cap);
  * form: -1 the rule, 0 .. 3 as mjb_lane_env_set_form; sweep_waves: 0 the rule, 3 / 4 as mjb_lane_env_set_sweep_waves; lds_kb: 0 by batch size,
  * 40 / 80 / 160 as MJB_LANE_ENV_LDS_KB.  Fills (each may be NULL) the form, form 3's sweep wavefronts (0 otherwise) and the LDS budget in KB, the
  * values mjb_lane_env_last_form / mjb_lane_env_last_sweep_waves report after such a launch.  A model with activation states (na > 0): form 0 whatever
- * is asked for, and no variant at all for build 2.  Returns 0; -1: the model is not eligible or needs more LDS than a CU has, there is no such variant,
+ * is asked for, and no variant at all for build 2.  A model with a frame-axis, velocity- or acceleration-stage sensor: form 0 whatever is asked for,
+ * and no variant for builds 3 and 4 when a force / torque sensor sits on a body without a joint on its path to the world.  Returns 0; -1: the model is not eligible or needs more LDS than a CU has, there is no such variant,
  * or an argument is out of range. */
 int mjb_lane_env_plan(const mjb_model *m, int ncu, int nenv, int build, int form, int sweep_waves, int lds_kb, int *out_form, int *out_sweep_waves, int *out_lds_kb);
 const char *mjb_lane_env_error(void);

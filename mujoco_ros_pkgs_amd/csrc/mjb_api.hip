@@ -2181,7 +2181,8 @@ static int speculate_ctrl_noise(mjb_batch *b, const LaunchReq &q, int zhalf_now)
 static bool le_hwsim(const mjb_batch *b) { return b->hw.n > 0 && b->lane_env_hwsim && b->hw_le_ok && !b->env_mass && !b->env_gravity && b->model->h.na <= 0; }
 // (mjb_lane_env_set_xfrc: a written xfrc_applied rides along in the kernel's XF builds -- unless the batch has a hwsim stage, there is no build with both.
 //  LaunchReq::compact stays what the generic path's frame choice reads; for this kernel, which has no frame, the xfrc term of it is lifted)
-static bool le_xfrc(const mjb_batch *b) { return b->st.use_xfrc && b->lane_env_xfrc && b->hw.n == 0; }
+// (... or the model has a force / torque sensor on a body at rest: the wrench table has no slot for that body's xfrc_applied, mjb_lane_env_plan answers -1)
+static bool le_xfrc(const mjb_batch *b) { return b->st.use_xfrc && b->lane_env_xfrc && b->hw.n == 0 && !mjb_lane_env_wrench_at_rest(&b->model->h); }
 static bool want_lane_env(const mjb_batch *b, const LaunchReq &q, int variant)
 {
 	const bool frameless = q.compact || (le_xfrc(b) && !b->st.keep_frame);

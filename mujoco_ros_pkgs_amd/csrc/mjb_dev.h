@@ -388,6 +388,7 @@ int mjb_lane_env_overlay_slots(const mjb_model_desc *h);
 // the wrench table of that kernel's XF builds: its slot count (the model's moving bodies), and the transpose of xfrc_applied [nenv][nbody][6] into
 // table [6 * slots][nenv] for every env, on `stream`
 int mjb_lane_env_xfrc_slots(const mjb_model_desc *h);
+int mjb_lane_env_wrench_at_rest(const mjb_model_desc *h);  // 1: a force / torque sensor sits on a body at rest, whose xfrc_applied has no slot in that table -- no XF build for the model
 int mjb_lane_env_xfrc_fill(const mjb_model_desc *h, const double *xfrc_applied, double *table, int nenv, void *stream);
 void mjb_lane_env_overlay_row(const mjb_model_desc *h, const double *gravity, const double *env_block, double *out);
 // the split step (mjb_smooth_kernel.h + mjb_cstep_kernel): one step of envs [env_lo, env_hi) -- smooth half in lane = env form, then the constraint half

@@ -133,12 +133,23 @@ static bool le_dyntype_ok(const mjb_model_desc *h, int i)
 	return (d == MJB_DYN_INTEGRATOR || d == MJB_DYN_FILTER) && h->actuator_actadr[i] >= 0 && h->actuator_actadr[i] < h->na;
 }
 
+// a sensor of the types the one-wavefront form alone evaluates (LeSens, mjb_lane_env_kernel.h): frame axes, the velocity and the acceleration stage
+static bool le_extra_sensors(const mjb_model_desc *h)
+{
+	for (int i = 0; i < h->nsensor; i++)
+		if (mjb_le::le_axis_type(h->sensor_type[i]) || mjb_le::le_vel_type(h->sensor_type[i]) || mjb_le::le_acc_type(h->sensor_type[i])) return true;
+	return false;
+}
+// ... and a force / torque sensor whose site sits on a body at rest: the wrench table of the xfrc builds has no slot for such a body's xfrc_applied
+static bool le_wrench_at_rest(const mjb_model_desc *h);
+
 // Index of the compiled-in topology the model has, or -1 (mjb_compile; the generic kernels run every model).
 int mjb_lane_env_match(const mjb_model_desc *h)
 {
 	if (!le_plain_tree(h)) return -1;
 	for (int b = 1; b < h->nbody; b++)
 		if (h->body_gravcomp[b] != 0) return -1;  // (gravity compensation is a compile-time flag per body, LeGc: no compiled-in topology has one set)
+	if (le_extra_sensors(h)) return -1;  // (... and none carries a frame-axis, velocity- or acceleration-stage sensor, LeSens: such a model is hiprtc's)
 #define MJB_LE_X(id, T) \
 	if (topo_matches<T>(*h)) return id;
 	MJB_LE_TOPOS(MJB_LE_X)
@@ -203,11 +214,15 @@ int mjb_lane_env_eligible(const mjb_model_desc *h)
 		if (h->body_jntnum[b] > 1) return 0;
 	for (int i = 0; i < h->nsensor; i++) {
 		const int t = h->sensor_type[i], ot = h->sensor_objtype[i];
-		const bool frame = t == MJB_SENS_FRAMEPOS || t == MJB_SENS_FRAMEQUAT;
-		if (!(frame || t == MJB_SENS_JOINTPOS || t == MJB_SENS_JOINTVEL || t == MJB_SENS_ACTUATORFRC || t == MJB_SENS_ACTUATORPOS || t == MJB_SENS_ACTUATORVEL ||
+		// on a frame (body / xbody / site), without a reference frame; on a site (velocimeter, gyro, accelerometer, force, torque)
+		const bool frame = t == MJB_SENS_FRAMEPOS || t == MJB_SENS_FRAMEQUAT || mjb_le::le_axis_type(t) || t == MJB_SENS_FRAMELINVEL || t == MJB_SENS_FRAMEANGVEL ||
+		                   t == MJB_SENS_FRAMELINACC || t == MJB_SENS_FRAMEANGACC;
+		const bool site = t == MJB_SENS_VELOCIMETER || t == MJB_SENS_GYRO || t == MJB_SENS_ACCELEROMETER || mjb_le::le_wrench_type(t);
+		if (!(frame || site || t == MJB_SENS_JOINTPOS || t == MJB_SENS_JOINTVEL || t == MJB_SENS_ACTUATORFRC || t == MJB_SENS_ACTUATORPOS || t == MJB_SENS_ACTUATORVEL ||
 		      t == MJB_SENS_CLOCK))
 			return 0;
 		if (frame && (h->sensor_refid[i] >= 0 || (ot != MJB_OBJ_BODY && ot != MJB_OBJ_XBODY && ot != MJB_OBJ_SITE))) return 0;
+		if (site && ot != MJB_OBJ_SITE) return 0;
 	}
 	for (int i = 0; i < h->nu; i++)
 		if (h->actuator_trntype[i] != MJB_TRN_JOINT || !le_dyntype_ok(h, i)) return 0;
@@ -555,6 +570,13 @@ static bool le_moving(const mjb_model_desc *h, int b)  // a joint on the body's 
 		if (h->body_jntnum[a] > 0) return true;
 	return false;
 }
+int mjb_lane_env_wrench_at_rest(const mjb_model_desc *h) { return h && le_wrench_at_rest(h) ? 1 : 0; }
+static bool le_wrench_at_rest(const mjb_model_desc *h)
+{
+	for (int i = 0; i < h->nsensor; i++)
+		if (mjb_le::le_wrench_type(h->sensor_type[i]) && h->sensor_objtype[i] == MJB_OBJ_SITE && !le_moving(h, h->site_bodyid[h->sensor_objid[i]])) return true;
+	return false;
+}
 int mjb_lane_env_overlay_slots(const mjb_model_desc *h)
 {
 	int nj = 0, nm = 0;
@@ -692,6 +714,8 @@ struct LePlanIn {
 	int nv, nmov, nbody;  // ... from these: dofs, moving bodies (mjb_lane_env_xfrc_slots), bodies
 	int na;             // ... and its activation states: the one-wavefront form alone carries them, and no build with the hwsim stage
 	bool gc;            // ... and whether a body has gravity compensation: the one-wavefront form alone has the term, in every build
+	bool sens;          // ... and whether it has a frame-axis, velocity- or acceleration-stage sensor (LeSens): the one-wavefront form alone evaluates them, in every build
+	bool wrench_rest;   // ... one of them a force / torque sensor on a body at rest: not in the xfrc builds, whose wrench table has no slot for such a body
 };
 
 LeVariant le_plan(const LePlanIn &in)
@@ -703,9 +727,10 @@ LeVariant le_plan(const LePlanIn &in)
 	const int ncu = in.ncu, waves = (in.nenv_batch + 63) / 64;
 	v.lds_kb = (in.lds_kb == 40 || in.lds_kb == 80 || in.lds_kb == 160) ? in.lds_kb : ((ncu > 0 && waves <= ncu) ? 160 : ((ncu > 0 && waves <= 2 * ncu) ? 80 : 40));
 	// the form: more than one wavefront per 64 envs in the plain build alone.  A model with activation states (act lives in the registers of the one
-	// wavefront that assembles the forces and integrates) or gravity compensation (the one-wavefront form alone has the term) -- always hiprtc's --
+	// wavefront that assembles the forces and integrates), gravity compensation (the one-wavefront form alone has the term) or a sensor beyond poses and
+	// joint / actuator scalars (the one-wavefront form alone has the velocity sensors in its sweep and the pass behind the qacc solve) -- always hiprtc's --
 	// is planned as if form 0 had been asked for, whatever is: the same budget and lanes per wavefront as that request
-	const int form = (in.fit && (in.na > 0 || in.gc)) ? 0 : in.form;
+	const int form = (in.fit && (in.na > 0 || in.gc || in.sens)) ? 0 : in.form;
 	if (plain && form > 0 && v.lds_kb < 80) {
 		// a forced multi-wavefront form on a batch that would run four wavefronts per CU: the two halves at two per CU
 		v.form = 1;
@@ -723,6 +748,10 @@ LeVariant le_plan(const LePlanIn &in)
 	if (!in.fit) return v;
 	if (in.na > 0 && in.build == MJB_LE_HWSIM) {
 		v.unavailable = "no build of the kernel has both the hwsim stage and activation states";
+		return v;
+	}
+	if (in.wrench_rest && (in.build == MJB_LE_XFRC || in.build == MJB_LE_OVERLAY_XFRC)) {
+		v.unavailable = "no xfrc build of the kernel has a force / torque sensor on a body at rest: the wrench table has no slot for that body";
 		return v;
 	}
 	// a hiprtc-built model may be larger than the compiled-in ones: the smallest budget its (qpos, qvel) pairs and body forces fit (fewer wavefronts per
@@ -797,8 +826,9 @@ template <class T> int le_go_topo(const LeVariant &v, const LeLaunch &a)
 }
 LePlanIn le_plan_in(const mjb_model_desc *fit_model, int ncu, int nenv_batch, LeBuild build, int form, int duo_max_waves, int sweep, int lds_kb, int wave_lanes)
 {
-	LePlanIn in{ ncu, nenv_batch, build, form, duo_max_waves, sweep, lds_kb, wave_lanes, fit_model != nullptr, 0, 0, 0, 0, false };
+	LePlanIn in{ ncu, nenv_batch, build, form, duo_max_waves, sweep, lds_kb, wave_lanes, fit_model != nullptr, 0, 0, 0, 0, false, false, false };
 	if (fit_model) {
+		in.sens = le_extra_sensors(fit_model), in.wrench_rest = le_wrench_at_rest(fit_model);
 		in.nv = fit_model->nv, in.nmov = mjb_lane_env_xfrc_slots(fit_model), in.nbody = fit_model->nbody, in.na = fit_model->na;
 		for (int b = 1; b < fit_model->nbody; b++) in.gc = in.gc || fit_model->body_gravcomp[b] != 0;
 	}

@@ -295,6 +295,28 @@ template <class T, class = void> struct LeGc { static constexpr bool on(int) { r
 template <class T> struct LeGc<T, decltype((void)T::body_gc)> { static constexpr bool on(int b) { return T::body_gc[b] != 0; } };
 template <class T> constexpr bool le_any_gc() { for (int b = 1; b < T::NBODY; b++) if (LeGc<T>::on(b)) return true; return false; }
 
+// Sensors beyond poses and joint / actuator scalars: the set is a compile-time fact of the topology (T::sensor_type[]), like LeGc.  Frame axes ride with
+// the pose sensors; velocity-stage sensors (velocimeter, gyro, framelinvel, frameangvel) are evaluated in the root -> leaf sweep where cvel is formed;
+// acceleration-stage sensors (accelerometer, force, torque, framelinacc, frameangacc) in a post pass behind the qacc solve -- mj_rnePostConstraint for the
+// lane.  A topology without them has none of that code.  One-wavefront form only, every build of it.
+constexpr bool le_axis_type(int t) { return t == MJB_SENS_FRAMEXAXIS || t == MJB_SENS_FRAMEYAXIS || t == MJB_SENS_FRAMEZAXIS; }
+constexpr bool le_vel_type(int t) { return t == MJB_SENS_VELOCIMETER || t == MJB_SENS_GYRO || t == MJB_SENS_FRAMELINVEL || t == MJB_SENS_FRAMEANGVEL; }
+constexpr bool le_wrench_type(int t) { return t == MJB_SENS_FORCE || t == MJB_SENS_TORQUE; }
+constexpr bool le_accel_type(int t) { return t == MJB_SENS_ACCELEROMETER || t == MJB_SENS_FRAMELINACC || t == MJB_SENS_FRAMEANGACC; }
+constexpr bool le_acc_type(int t) { return le_wrench_type(t) || le_accel_type(t); }
+template <class T> struct LeSens {
+	static constexpr bool any(bool (*is)(int)) { for (int i = 0; i < T::NSENSOR; i++) if (is(T::sensor_type[i])) return true; return false; }
+	static constexpr bool vel() { return any(le_vel_type); }  // has a velocity-stage sensor
+	static constexpr bool acc() { return any(le_acc_type); }  // has an acceleration-stage sensor
+	static constexpr bool extra() { return vel() || acc() || any(le_axis_type); }
+	static constexpr int body(int i) { return T::sensor_objtype[i] == MJB_OBJ_SITE ? T::site_bodyid[T::sensor_objid[i]] : T::sensor_objid[i]; }  // the body sensor i's object sits on
+	static constexpr bool on(int b, bool (*is)(int)) { for (int i = 0; i < T::NSENSOR; i++) if (is(T::sensor_type[i]) && body(i) == b) return true; return false; }
+	static constexpr bool under(int b, int a) { for (int c = b; c > 0; c = T::body_parentid[c]) if (c == a) return true; return false; }  // b is a or in a's subtree (a > 0)
+	// some body of b's subtree (b included) carries such a sensor / b is in the subtree of a body that does
+	static constexpr bool above(int b, bool (*is)(int)) { for (int c = b; c < T::NBODY; c++) if (under(c, b) && on(c, is)) return true; return false; }
+	static constexpr bool below(int b, bool (*is)(int)) { for (int a = b; a > 0; a = T::body_parentid[a]) if (on(a, is)) return true; return false; }
+};
+
 // Off-centre anchors (mjModel.jnt_pos != 0): a topology may flag them per joint, jnt_offc[NJNT] (the generated and the hiprtc-built ones do, and
 // mjb_lane_env_match compares the flags).  Where the flags are known AND the caller asks for them (USE: the quartet's roles -- every other form keeps
 // its code as it is), "is this anchor off centre" is a constant and the untaken side compiles to nothing; otherwise it is the run-time test on the
@@ -400,6 +422,8 @@ DEVI void lane_env_body(const KernelParams MJB_AS4 *__restrict__ P, const int ns
 	static_assert(!XF || (ROLE == LE_SOLO && !HW), "lane = env kernel: xfrc_applied runs the solo form, without the hwsim stage");
 	static_assert(NA == 0 || (ROLE == LE_SOLO && !HW), "lane = env kernel: activation states run the solo form, without the hwsim stage");
 	static_assert(!le_any_gc<T>() || ROLE == LE_SOLO, "lane = env kernel: gravity compensation runs the solo form");
+	using SN = LeSens<T>;
+	static_assert(!SN::extra() || ROLE == LE_SOLO, "lane = env kernel: frame-axis, velocity- and acceleration-stage sensors run the solo form");
 	using OV = PeSlots<T>;
 	using XS6 = XfSlots<T>;
 	constexpr int LPE = PIPE ? (1 << 20) : (DUO ? LP - DuoSlots<NV>::n : LP);
@@ -605,6 +629,7 @@ DEVI void lane_env_body(const KernelParams MJB_AS4 *__restrict__ P, const int ns
 			double cvel[NB][6], cacc[NB][6];
 			double f[NV > 0 ? NV : 1];  // qfrc_passive + qfrc_applied + qfrc_actuator, then (- qfrc_bias) qfrc_smooth
 			double grav[3];
+			[[maybe_unused]] double rw[SN::acc() ? NB : 1][4];  // (a force / torque sensor on a body at rest) mass * (xipos - the root's origin) | mass of the bodies at rest under it
 			{
 				const bool g_on = !(m.disableflags & MJB_DSBL_GRAVITY);
 				if constexpr (PE) {
@@ -641,12 +666,41 @@ DEVI void lane_env_body(const KernelParams MJB_AS4 *__restrict__ P, const int ns
 					}
 				}
 			}
+			// (frame-axis, velocity- and acceleration-stage sensors) the frame of the object sensor S sits on, from its body's pose: origin relative to the
+			// origin of the tree's root body -- the point this kernel takes spatial quantities about -- and rotation matrix (mj_local2Global: the quaternion product)
+			[[maybe_unused]] auto sens_frame = [&](auto S, double *dif, double *R) {
+				constexpr int i = S, ot = T::sensor_objtype[i], id = T::sensor_objid[i], b = SN::body(i), r = T::body_rootid[b];
+				constexpr bool same = ot == MJB_OBJ_XBODY || (ot == MJB_OBJ_SITE ? T::site_sameframe[id] != 0 : T::body_sameframe[b] != 0);
+				for (int k = 0; k < 3; k++) dif[k] = r == b ? 0.0 : xpos[b][k] - xpos[r][k];
+				if constexpr (!same) {
+					double lp3[3], v[3];
+					if constexpr (ot == MJB_OBJ_SITE) ldc3(lp3, m.site_pos + 3 * id);
+					else { lp3[0] = tb[b].ipos[0]; lp3[1] = tb[b].ipos[1]; lp3[2] = tb[b].ipos[2]; }
+					matvec3(v, xmat[b], lp3);
+					for (int k = 0; k < 3; k++) dif[k] += v[k];
+				}
+				if constexpr (ot == MJB_OBJ_XBODY) {
+					for (int k = 0; k < 9; k++) R[k] = xmat[b][k];
+				} else {
+					double lq[4], q[4];
+					if constexpr (ot == MJB_OBJ_SITE) ldc4(lq, m.site_quat + 4 * id);
+					else ldc4(lq, m.body_iquat + 4 * b);
+					qmul(q, xquat[b], lq);
+					quat2mat_nocheck(R, q);
+				}
+			};
 			// position-stage sensors on a body's frames (the last step's values are the launch's sensordata)
 			auto frame_sensors = [&](auto Bq, const double *xipos) {
 				constexpr int b = Bq;
 				if (sensf_on) {
 					sfor<T::NSENSOR>([&](auto S) {
 						constexpr int i = S, type = T::sensor_type[i], ot = T::sensor_objtype[i], id = T::sensor_objid[i], adr = T::sensor_adr[i];
+						if constexpr (le_axis_type(type) && SN::body(i) == b) {  // a column of the object's rotation matrix (mjDATATYPE_AXIS: no cutoff)
+							double dif[3], R[9];
+							sens_frame(S, dif, R);
+							constexpr int c = type - MJB_SENS_FRAMEXAXIS;
+							for (int k = 0; k < 3; k++) sd[adr + k] = R[3 * k + c];
+						}
 						if constexpr (type == MJB_SENS_FRAMEPOS || type == MJB_SENS_FRAMEQUAT) {
 							constexpr int sb = ot == MJB_OBJ_SITE ? T::site_bodyid[id] : id;
 							if constexpr (sb == b) {
@@ -685,6 +739,31 @@ DEVI void lane_env_body(const KernelParams MJB_AS4 *__restrict__ P, const int ns
 									for (int k = 0; k < 4; k++) sd[adr + k] = o4[k];
 								}
 							}
+						}
+					});
+				}
+			};
+			// velocity-stage sensors on a body (mj_objectVelocity): cvel, taken about the tree root's origin, moved to the object -- the lever arm is the object's
+			// position relative to that origin, the result does not depend on the point -- in the object's frame (velocimeter, gyro) or the world's (framelinvel,
+			// frameangvel without a reference frame).  A body at rest reads zero.
+			[[maybe_unused]] auto vel_sensors = [&](auto Bq) {
+				constexpr int b = Bq;
+				if (sensf_on) {
+					sfor<T::NSENSOR>([&](auto S) {
+						constexpr int i = S, type = T::sensor_type[i], adr = T::sensor_adr[i];
+						if constexpr (le_vel_type(type) && SN::body(i) == b) {
+							double out[3] = { 0, 0, 0 };
+							if constexpr (LD::needed(b)) {
+								double dif[3], R[9], cr[3], w[3];
+								sens_frame(S, dif, R);
+								cross3(cr, dif, cvel[b]);
+								constexpr bool ang = type == MJB_SENS_GYRO || type == MJB_SENS_FRAMEANGVEL;
+								for (int k = 0; k < 3; k++) w[k] = ang ? cvel[b][k] : cvel[b][3 + k] - cr[k];
+								if constexpr (type == MJB_SENS_GYRO || type == MJB_SENS_VELOCIMETER) matTvec3(out, R, w);
+								else for (int k = 0; k < 3; k++) out[k] = w[k];
+							}
+							const double cut = m.sensor_cutoff[i];
+							for (int k = 0; k < 3; k++) sd[adr + k] = cut > 0 ? clampd(out[k], -cut, cut) : out[k];
 						}
 					});
 				}
@@ -1039,6 +1118,7 @@ DEVI void lane_env_body(const KernelParams MJB_AS4 *__restrict__ P, const int ns
 					} else if constexpr (DV) {
 						for (int k = 0; k < 6; k++) { cvel[b][k] = pv[k]; cacc[b][k] = pa[k]; }
 					}
+					if constexpr (SN::vel()) vel_sensors(B);
 					if constexpr (DP && (ROLE != LE_PIPE_P || b == LASTB)) {  // the composite-inertia sweep reads it back (pipelined duo: the last body's, which V's force computation reads too)
 						if constexpr (LD::cin_slot(b) >= 0) {
 							constexpr int c0 = LD::cin_slot(b);
@@ -1091,6 +1171,12 @@ DEVI void lane_env_body(const KernelParams MJB_AS4 *__restrict__ P, const int ns
 						LE_PK(0);
 						le_barrier();
 						LE_PK(2);
+					}
+				} else {  // a body at rest: swept for its pose alone.  Its velocity sensors read zero; a force / torque sensor above it takes its weight
+					if constexpr (SN::vel()) vel_sensors(B);
+					if constexpr (SN::below(b, le_wrench_type)) {
+						for (int k = 0; k < 3; k++) rw[b][k] = mass * (xipos[k] - xpos[r][k]);  // (r is at rest too: b == r reads its own xpos)
+						rw[b][3] = mass;
 					}
 				}
 				if constexpr (b + 1 < NB) touch_rec<14>(hA[b + 1]);
@@ -1787,6 +1873,141 @@ DEVI void lane_env_body(const KernelParams MJB_AS4 *__restrict__ P, const int ns
 				wasreset = wasreset || bada;
 				le_barrier();  // (R) the old state is back: the second trip reads it
 				continue;
+			}
+			// ================= mj_rnePostConstraint for the lane: the acceleration-stage sensors =================
+			// Behind the qacc solve and ahead of mj_checkAcc's verdict, where the generic kernels run rne_post: a lane that verdict resets gets its sensordata
+			// from the retry.  On sensor steps only (wave-uniform), selects only.  What is still there from the sweep: cdof in registers, (qpos, qvel) and each
+			// body's bias force -- cinert cacc + cvel x* (cinert cvel), cacc without qacc, less the body's xfrc_applied wrench (XF) and its gravity compensation --
+			// in LDS, cinert in LDS or cin[], the poses.  The pass adds what qacc contributes: dq[b] = sum over the dofs on b's path of cdof qacc, one more
+			// root -> leaf accumulation, and cfrc_int[a] = sum over a's subtree of (bias force + cinert dq), with the gravity compensation put back (a passive
+			// force: not part of cfrc_int in MuJoCo).  cvel and the bias part of cacc are formed again from cdof and qvel for the bodies between the root and
+			// an accelerometer / framelinacc / frameangacc, and for no other.  A body at rest: cvel = 0, cacc = (0, -gravity), its own force its weight.
+			if constexpr (SN::acc()) {
+				constexpr bool wrench_at_rest = [] { for (int a = 1; a < NB; a++) if (!LD::needed(a) && SN::on(a, le_wrench_type)) return true; return false; }();
+				static_assert(!XF || !wrench_at_rest, "lane = env kernel: the wrench table has no slot for a body at rest -- no xfrc build with a force / torque sensor on one (le_plan)");
+				if (sens_on) {
+					double pv[NB][6], pb[NB][6], dq[NB][6], fs[NB][6];  // cvel | cacc's bias part | cacc's qacc part | cfrc_int of a body with a force / torque sensor
+					sfor<NB>([&](auto B) {
+						constexpr int b = B;
+						if constexpr (b > 0 && LD::needed(b)) {
+							constexpr int p = T::body_parentid[b], j = T::body_jnt[b];
+							constexpr bool prest = p == 0 || !LD::needed(p);
+							constexpr bool wr = SN::above(b, le_wrench_type) || SN::below(b, le_wrench_type);
+							constexpr bool kin = SN::above(b, le_accel_type) || (HW && wr);  // (HW: cvel of every body of the pass -- the stage's write to a joint's qvel, below)
+							if constexpr (kin || wr) {
+								for (int k = 0; k < 6; k++) dq[b][k] = prest ? 0.0 : dq[p][k];
+								if constexpr (j >= 0) for (int k = 0; k < 6; k++) dq[b][k] += cdof[j][k] * qacc[j];
+							}
+							if constexpr (kin) {
+								for (int k = 0; k < 6; k++) pv[b][k] = prest ? 0.0 : pv[p][k];
+								for (int k = 0; k < 3; k++) { pb[b][k] = prest ? 0.0 : pb[p][k]; pb[b][3 + k] = prest ? -grav[k] : pb[p][3 + k]; }
+								if constexpr (j >= 0) {
+									const double qv = lp[64 * j].b;
+									if constexpr (!prest) {  // (cdof_dot = cvel(parent) x cdof: zero under a parent at rest)
+										double cdd[6];
+										cross_motion(cdd, pv[p], cdof[j]);
+										for (int k = 0; k < 6; k++) pb[b][k] += cdd[k] * qv;
+										if constexpr (HW) {
+											// (the generic kernels' hwsim_write puts a POSITION / VELOCITY joint's new qvel into the frame ahead of rne_post, which forms cdof_dot qvel
+											//  with it -- cdof_dot and cvel still those of the old state.  Here that qvel waits for mj_Euler in hov[]: the difference goes into the qacc
+											//  part, and with it into the forces)
+											const HwSim MJB_AS4 &hw = Pq->hw;
+											if (hw.le_tab[4 * j] >= 0) {
+												const int method = hw.le_tab[4 * j + 1];
+												if (method == MJB_HW_POSITION || method == MJB_HW_VELOCITY) {
+													const double qn = seld(hw_wr, method == MJB_HW_POSITION ? 0.0 : hov[j], qv);
+													for (int k = 0; k < 6; k++) dq[b][k] += cdd[k] * (qn - qv);
+												}
+											}
+										}
+									}
+									for (int k = 0; k < 6; k++) pv[b][k] += cdof[j][k] * qv;
+								}
+							}
+						}
+					});
+					// cfrc_int of the bodies that carry a force / torque sensor: the weights of the bodies at rest in the subtree, then every moving body's own force
+					sfor<NB>([&](auto A) {
+						constexpr int a = A;
+						if constexpr (a > 0 && SN::on(a, le_wrench_type)) {
+							for (int k = 0; k < 6; k++) fs[a][k] = 0;
+							if constexpr (!LD::needed(a)) {
+								sfor<NB>([&](auto Cq) {
+									constexpr int c = Cq;
+									if constexpr (c >= a && !LD::needed(c) && SN::under(c, a)) {
+										double tq[3];
+										cross3(tq, rw[c], grav);
+										for (int k = 0; k < 3; k++) { fs[a][k] -= tq[k]; fs[a][3 + k] -= rw[c][3] * grav[k]; }
+									}
+								});
+							}
+						}
+					});
+					sfor<NB>([&](auto B) {
+						constexpr int b = B;
+						if constexpr (b > 0 && LD::needed(b) && SN::below(b, le_wrench_type)) {
+							constexpr int q0 = LD::slot(b), c0 = LD::cin_slot(b);
+							double ci[10], own[6];
+							if constexpr (c0 >= 0) {
+								for (int k = 0; k < 5; k++) {
+									const Pair c = lp[64 * (c0 + k)];
+									ci[2 * k] = c.a;
+									ci[2 * k + 1] = c.b;
+								}
+							} else {
+								for (int k = 0; k < 10; k++) ci[k] = cin[b][k];
+							}
+							const Pair f0 = lp[64 * q0], f1 = lp[64 * (q0 + 1)], f2 = lp[64 * (q0 + 2)];
+							mul_inert_vec(own, ci, dq[b]);
+							own[0] += f0.a; own[1] += f0.b; own[2] += f1.a; own[3] += f1.b; own[4] += f2.a; own[5] += f2.b;
+							if constexpr (LeGc<T>::on(b)) {  // (the sweep took (xd x F ; F), F = -gravity mass gravcomp, off the bias force; mass xd is cinert's [6 .. 8])
+								const double sc = pas_on ? -tb[b].pad[0] : 0.0;
+								double F[3], tq[3];
+								for (int k = 0; k < 3; k++) F[k] = sc * grav[k];
+								cross3(tq, ci + 6, F);
+								for (int k = 0; k < 3; k++) { own[k] += tq[k]; own[3 + k] += ci[9] * F[k]; }
+							}
+							sfor<NB>([&](auto A) {
+								constexpr int a = A;
+								if constexpr (a > 0 && SN::on(a, le_wrench_type) && SN::under(b, a)) for (int k = 0; k < 6; k++) fs[a][k] += own[k];
+							});
+						}
+					});
+					sfor<T::NSENSOR>([&](auto S) {
+						constexpr int i = S, type = T::sensor_type[i], adr = T::sensor_adr[i], b = SN::body(i);
+						if constexpr (le_acc_type(type)) {
+							double dif[3], R[9], w[3], out[3];
+							sens_frame(S, dif, R);
+							if constexpr (le_wrench_type(type)) {  // cfrc_int (torque ; force) about the root's origin, moved to the site and turned into its frame
+								if constexpr (type == MJB_SENS_FORCE) for (int k = 0; k < 3; k++) w[k] = fs[b][3 + k];
+								else {
+									double cr[3];
+									cross3(cr, dif, fs[b] + 3);
+									for (int k = 0; k < 3; k++) w[k] = fs[b][k] - cr[k];
+								}
+								matTvec3(out, R, w);
+							} else {  // mj_objectAcceleration: cacc moved to the object, + omega x v of its origin
+								if constexpr (!LD::needed(b)) {
+									for (int k = 0; k < 3; k++) w[k] = type == MJB_SENS_FRAMEANGACC ? 0.0 : -grav[k];
+								} else if constexpr (type == MJB_SENS_FRAMEANGACC) {
+									for (int k = 0; k < 3; k++) w[k] = pb[b][k] + dq[b][k];
+								} else {
+									double a6[6], ca[3], cv[3], vl[3], wv[3];
+									for (int k = 0; k < 6; k++) a6[k] = pb[b][k] + dq[b][k];
+									cross3(ca, dif, a6);
+									cross3(cv, dif, pv[b]);
+									for (int k = 0; k < 3; k++) vl[k] = pv[b][3 + k] - cv[k];
+									cross3(wv, pv[b], vl);
+									for (int k = 0; k < 3; k++) w[k] = a6[3 + k] - ca[k] + wv[k];
+								}
+								if constexpr (type == MJB_SENS_ACCELEROMETER) matTvec3(out, R, w);
+								else for (int k = 0; k < 3; k++) out[k] = w[k];
+							}
+							const double cut = m.sensor_cutoff[i];
+							for (int k = 0; k < 3; k++) sd[adr + k] = cut > 0 ? clampd(out[k], -cut, cut) : out[k];
+						}
+					});
+				}
 			}
 			// ---- mj_checkAcc: a bad qacc resets the env and the forward pass runs once more (mj_step)
 			if (attempt) break;

@@ -24,7 +24,13 @@ MODELS = [
     ("lane_env_tree", os.path.join(ROOT, "mujoco_ros_pkgs_amd", "assets", "lane_env_tree.xml")),
 ]
 
-SUPPORTED_SENSORS = {8, 9, 14, 23, 24, 35, 12, 13}  # jointpos, jointvel, actuatorfrc, framepos, framequat, clock, actuatorpos, actuatorvel
+SMOOTH_SENSORS = {8, 9, 14, 23, 24, 35, 12, 13}  # jointpos, jointvel, actuatorfrc, framepos, framequat, clock, actuatorpos, actuatorvel
+# ... and what the one-wavefront form of the lane = env kernel alone evaluates (LeSens, csrc/mjb_lane_env_kernel.h): a model with one of them is
+# hiprtc's, never a compiled-in topology.  On a frame (body / xbody / site) without a reference frame, or on a site
+FRAME_SENSORS = {23, 24, 25, 26, 27, 28, 29, 30, 31}  # framepos, framequat, frame[xyz]axis, framelinvel, frameangvel, framelinacc, frameangacc
+SITE_SENSORS = {1, 2, 3, 4, 5}                        # accelerometer, velocimeter, gyro, force, torque
+EXTRA_SENSORS = (FRAME_SENSORS - {23, 24}) | SITE_SENSORS
+SUPPORTED_SENSORS = SMOOTH_SENSORS | EXTRA_SENSORS
 
 
 def eligible(m):
@@ -46,8 +52,10 @@ def eligible(m):
     for i in range(m["nsensor"]):
         if int(m["sensor_type"][i]) not in SUPPORTED_SENSORS:
             return "sensor type %d" % m["sensor_type"][i]
-        if int(m["sensor_type"][i]) in (23, 24) and (m["sensor_refid"][i] >= 0 or int(m["sensor_objtype"][i]) not in (1, 2, 6)):
+        if int(m["sensor_type"][i]) in FRAME_SENSORS and (m["sensor_refid"][i] >= 0 or int(m["sensor_objtype"][i]) not in (1, 2, 6)):
             return "frame sensor with a reference frame / unsupported object"
+        if int(m["sensor_type"][i]) in SITE_SENSORS and int(m["sensor_objtype"][i]) != 6:
+            return "site sensor on another object"
     for i in range(m["nu"]):
         if m["actuator_trntype"][i] != 0 or int(m["actuator_dyntype"][i]) not in (0, 1, 2):  # none, integrator, filter
             return "actuator transmission / dynamics"
@@ -69,6 +77,22 @@ def emit(name, m):
         raise SystemExit("%s does not fit the lane = env kernel: %s" % (name, why))
     if "body_gravcomp" in m and any(m["body_gravcomp"][1:] != 0):  # (a hand-built dict from before the field has none)
         raise SystemExit("%s has gravity compensation: mjb_lane_env_match takes no such model for a compiled-in topology" % name)
+    if any(int(t) in EXTRA_SENSORS for t in m["sensor_type"][:m["nsensor"]]):
+        raise SystemExit("%s has a frame-axis, velocity- or acceleration-stage sensor: mjb_lane_env_match takes no such model for a compiled-in topology" % name)
+    return struct_text(name, m, [0] * m["nbody"])
+
+
+def rt_struct(m):
+    """The structure of any eligible model as the library writes it for hiprtc (topo_source, csrc/mjb_lane_env.hip): LeTopo_rt, with the gravity
+    compensation flags set.  For tools that build such a model's kernel offline (tools/lane_env_jit_meta.py)."""
+    why = eligible(m)
+    if why:
+        raise SystemExit("the model does not fit the lane = env kernel: %s" % why)
+    gc = [int(b > 0 and m["body_gravcomp"][b] != 0) for b in range(m["nbody"])]
+    return struct_text("rt", m, gc).replace('\tstatic constexpr const char *name = "rt";\n', "")
+
+
+def struct_text(name, m, body_gc):
     nb = m["nbody"]
     body_jnt = [int(m["body_jntadr"][b]) if m["body_jntnum"][b] == 1 else -1 for b in range(nb)]
     s = "struct LeTopo_%s {\n" % name
@@ -79,9 +103,9 @@ def emit(name, m):
     s += arr("body_rootid", m["body_rootid"])
     s += arr("body_jnt", body_jnt)
     s += arr("body_sameframe", m["body_sameframe"])
-    # gravity compensation: a flag per body (the coefficient is run-time data).  Always zeros here -- a model with gravcomp was refused above and is
-    # hiprtc's, whose topology text (mjb_lane_env.hip, topo_source) sets the flags
-    s += arr("body_gc", [0] * nb)
+    # gravity compensation: a flag per body (the coefficient is run-time data).  Always zeros from emit() -- it refuses a model with gravcomp, which is
+    # hiprtc's, whose topology text (mjb_lane_env.hip, topo_source; rt_struct here) sets the flags
+    s += arr("body_gc", body_gc)
     s += arr("jnt_type", m["jnt_type"])
     s += arr("jnt_bodyid", m["jnt_bodyid"])
     # off-centre anchors: a flag per joint, 1 where jnt_pos != 0 (the offset itself is run-time data).  mjb_lane_env_match compares it: the kernel has
@@ -129,7 +153,7 @@ def smooth_eligible(m):
     if m["nbody"] > 24 or m["nv"] > 20:
         return "size"
     for i in range(m["nsensor"]):
-        if int(m["sensor_type"][i]) not in SUPPORTED_SENSORS:
+        if int(m["sensor_type"][i]) not in SMOOTH_SENSORS:
             return "sensor type %d" % m["sensor_type"][i]
         if int(m["sensor_type"][i]) in (23, 24) and (m["sensor_refid"][i] >= 0 or int(m["sensor_objtype"][i]) not in (1, 2, 6)):
             return "frame sensor with a reference frame / unsupported object"
