@@ -363,6 +363,13 @@ enum LeRole : int {
 	// builds qM a second time beside C from those very numbers, factors M, solves qacc = M^-1 f and takes mj_checkAcc's decision; C factors M + h B alone, solves the acceleration Euler advances with
 	// and integrates SPECULATIVELY -- X's verdict, read by all four behind rendezvous B, either lets the step stand or has C put the old state back.
 	// Nothing but V's qfrc_smooth and the two mail slots crosses LDS, and the step has no barrier the trio's tail does not have.
+	// Where a phase's loads and stores sit (one wavefront per SIMD: nobody covers a wait): O and X fetch the next body's tape record at the top of a phase
+	// and pin it at its end; X reads C's cdof beside O's quaternion at the top.  C holds its body's record (ipos, ibody, mass, jaxis, an off-centre jpos:
+	// hC) from the phase BEFORE -- the first from ahead of the phases --, so the pose ring's six reads are waited for by count, in the order of their
+	// use, and fetches the next record once they have landed, under the rest of cinert and the cdof half.  V runs a body's force half one phase BEHIND
+	// its velocity half: a phase issues its body's nine reads (cinert, cdof, qvel), works off the previous body's cfrc from registers while they land --
+	// the three cfrc writes leave mid-phase and drain under the velocities --, then takes its body's cvel / cacc; the cinert waits in registers across
+	// the barrier, and the last body's forces come behind the sweep's last barrier with its velocities.
 	LE_QUAD_O = 8,
 	LE_QUAD_X = 9,
 	LE_QUAD_C = 10,
@@ -408,7 +415,7 @@ DEVI void lane_env_body(const KernelParams MJB_AS4 *__restrict__ P, const int ns
 	constexpr bool DP = ROLE == LE_SOLO || ROLE == LE_DUO_P || ROLE == LE_PIPE_P || ROLE == LE_TRIO_C || ROLE == LE_QUAD_C, DV = ROLE == LE_SOLO || ROLE == LE_DUO_V || ROLE == LE_PIPE_V || ROLE == LE_TRIO_V || ROLE == LE_QUAD_V, DUO = ROLE != LE_SOLO;  // this wavefront does the position half (inertias, factors, solves, Euler) / the velocity half
 	constexpr bool PIPE = le_pipelined_duo(ROLE) || TRIQ;  // bodies pass between wavefronts through the pose ring
 	constexpr bool POSE = HALVES || ROLE == LE_PIPE_P || ROLE == LE_TRIO_P, RINGC = ROLE == LE_PIPE_V || ROLE == LE_TRIO_C || ROLE == LE_TRIO_V;  // computes the poses / takes them from the ring (the quartet's roles have a sweep of their own below)
-	constexpr bool VLDS = ROLE == LE_TRIO_V || ROLE == LE_QUAD_V;  // V of three / four wavefronts: cinert from C through LDS
+	constexpr bool VLDS = ROLE == LE_TRIO_V;  // V of three wavefronts: cinert from C through LDS (the quartet's V reads it in v_fetch)
 	constexpr bool EPOS = ROLE == LE_SOLO || ROLE == LE_DUO_P || ROLE == LE_PIPE_P || ROLE == LE_TRIO_P || ROLE == LE_QUAD_X;                     // gathers mj_energyPos along its pose sweep
 	constexpr bool SENSF = ROLE == LE_SOLO || ROLE == LE_DUO_V || ROLE == LE_PIPE_P || ROLE == LE_TRIO_P || ROLE == LE_QUAD_X;  // frame sensors: who holds the poses (and, of two, who has the time)
 	[[maybe_unused]] constexpr bool XW = ROLE == LE_QUAD_X;               // X of four wavefronts: the walk's position half, the M factor, the qacc solve, mj_checkAcc
@@ -491,7 +498,7 @@ DEVI void lane_env_body(const KernelParams MJB_AS4 *__restrict__ P, const int ns
 	const bool zpre = zhalf_i >= 0;
 
 #ifdef MJB_LE_PROBE  // (measurement build: cycle stamps of the step's phases, summed over the launch, into the env-0 sensordata of the role)
-	unsigned long long pk_t = 0, pk_acc[8] = { 0, 0, 0, 0, 0, 0, 0, 0 };
+	unsigned long long pk_t = 0, pk_acc[9] = { 0, 0, 0, 0, 0, 0, 0, 0, 0 };  // ([8], the quartet's C and V: from a sweep barrier to where the phase's reads have landed -- V: and the previous body's forces are done)
 #define LE_PK0() pk_t = __builtin_readcyclecounter()
 #define LE_PK(i) do { const unsigned long long n_ = __builtin_readcyclecounter(); pk_acc[i] += n_ - pk_t; pk_t = n_; } while (0)
 #else
@@ -644,6 +651,29 @@ DEVI void lane_env_body(const KernelParams MJB_AS4 *__restrict__ P, const int ns
 			double hA[NB + 1][16], hB[NB][16];
 			[[maybe_unused]] double vB[PE ? NB : 1][7];  // (PE) the env's mass | ibody[6] of a body, fetched with the body's inertial half record
 			[[maybe_unused]] double xw[XF ? NB : 1][6];  // (XF) the env's wrench on a moving body, fetched with the body's inertial half record
+			// (the quartet's C) what C reads of a needed body's record -- ipos[3] ibody[6] mass | jaxis[3] | jpos[3] --, fetched one phase ahead as O and X
+			// fetch theirs: with no scalar load in flight while C works off the pose ring, its waits for the ring's reads are counted ones
+			[[maybe_unused]] double hC[ROLE == LE_QUAD_C ? NB + 1 : 1][16];
+			[[maybe_unused]] auto c_fetch = [&](auto Bn) {
+				constexpr int nb = Bn, jn = T::body_jnt[nb];
+				const double MJB_AS4 *const rec = reinterpret_cast<const double MJB_AS4 *>(tb + nb);
+				for (int k = 0; k < 10; k++) hC[nb][k] = rec[16 + k];
+				if constexpr (jn >= 0) {
+					for (int k = 0; k < 3; k++) hC[nb][10 + k] = rec[7 + k];
+					if constexpr (T::jnt_type[jn < 0 ? 0 : jn] != MJB_JNT_SLIDE && (!LeOffc<T>::known || LeOffc<T>::on(jn < 0 ? 0 : jn))) for (int k = 0; k < 3; k++) hC[nb][13 + k] = rec[10 + k];
+				}
+			};
+			// ... pinned at the end of the region that issued the loads (the entries C reads, no others: see touch_rec)
+			[[maybe_unused]] auto c_touch = [&](auto Bn) {
+				constexpr int nb = Bn, jn = T::body_jnt[nb];
+				const double *const h = hC[nb];
+				asm volatile("" ::"s"(h[3]), "s"(h[4]), "s"(h[5]), "s"(h[6]), "s"(h[7]), "s"(h[8]), "s"(h[9]));
+				if constexpr (!T::body_sameframe[nb]) asm volatile("" ::"s"(h[0]), "s"(h[1]), "s"(h[2]));
+				if constexpr (jn >= 0) {
+					asm volatile("" ::"s"(h[10]), "s"(h[11]), "s"(h[12]));
+					if constexpr (T::jnt_type[jn < 0 ? 0 : jn] != MJB_JNT_SLIDE && (!LeOffc<T>::known || LeOffc<T>::on(jn < 0 ? 0 : jn))) asm volatile("" ::"s"(h[13]), "s"(h[14]), "s"(h[15]));
+				}
+			};
 			for (int k = 0; k < 14; k++) hA[1][k] = reinterpret_cast<const double MJB_AS4 *>(tb + 1)[k];
 			// ... and the (qpos, qvel) pair of the next jointed body: LDS reads and scalar loads share one counter, so a read issued where
 			// it is needed would wait for the record fetched beside it
@@ -774,9 +804,13 @@ DEVI void lane_env_body(const KernelParams MJB_AS4 *__restrict__ P, const int ns
 				constexpr int p = T::body_parentid[b], j = T::body_jnt[b];
 				constexpr int ord = (LD::slot(b) - NV) / 3, rg = RING + 6 * (ord % RINGN), c0 = LD::cin_slot(b);
 				static_assert(c0 >= 0, "pipelined forms: every needed body's cinert lives in LDS");
+				static_assert(ROLE != LE_QUAD_V || b < 0, "the quartet's V takes a body in pieces: v_fetch, v_kin, v_force");
 				[[maybe_unused]] double xp[3], xm[9];
 				double ci[10];
-				if constexpr (ROLE != LE_QUAD_V) {
+				if constexpr (ROLE == LE_QUAD_C) {  // (the quartet's C: the ring's six reads in the order of their first use -- the matrix rows, then the position)
+					const Pair a1 = lp[64 * (rg + 1)], a2 = lp[64 * (rg + 2)], a3 = lp[64 * (rg + 3)], a4 = lp[64 * (rg + 4)], a5 = lp[64 * (rg + 5)], a0 = lp[64 * rg];
+					xp[0] = a0.a; xp[1] = a0.b; xp[2] = a1.a; xm[0] = a1.b; xm[1] = a2.a; xm[2] = a2.b; xm[3] = a3.a; xm[4] = a3.b; xm[5] = a4.a; xm[6] = a4.b; xm[7] = a5.a; xm[8] = a5.b;
+				} else {
 					const Pair a0 = lp[64 * rg], a1 = lp[64 * (rg + 1)], a2 = lp[64 * (rg + 2)], a3 = lp[64 * (rg + 3)], a4 = lp[64 * (rg + 4)], a5 = lp[64 * (rg + 5)];
 					xp[0] = a0.a; xp[1] = a0.b; xp[2] = a1.a; xm[0] = a1.b; xm[1] = a2.a; xm[2] = a2.b; xm[3] = a3.a; xm[4] = a3.b; xm[5] = a4.a; xm[6] = a4.b; xm[7] = a5.a; xm[8] = a5.b;
 				}
@@ -792,21 +826,37 @@ DEVI void lane_env_body(const KernelParams MJB_AS4 *__restrict__ P, const int ns
 				{
 					// cinert about the tree root's origin, as in the fused sweep: X Ib X' + the com offset's terms; handed to P's composite-inertia sweep
 					const LeTapeBody MJB_AS4 &tj = tb[b];
+					constexpr bool CREC = ROLE == LE_QUAD_C;  // (the quartet's C: the record is in hC[b], fetched a phase ago)
+					[[maybe_unused]] const double *const hc = hC[CREC ? b : 0];
 					double dif[3] = { xp[0], xp[1], xp[2] };
 					if constexpr (!T::body_sameframe[b]) {
-						const double ip[3] = { tj.ipos[0], tj.ipos[1], tj.ipos[2] };
+						double ip[3];
+						if constexpr (CREC) { ip[0] = hc[0]; ip[1] = hc[1]; ip[2] = hc[2]; }
+						else { ip[0] = tj.ipos[0]; ip[1] = tj.ipos[1]; ip[2] = tj.ipos[2]; }
 						double v[3];
 						matvec3(v, xm, ip);
 						for (int k = 0; k < 3; k++) dif[k] += v[k];
 					}
-					const double mass = tj.mass;
+					double mass, ixx, iyy, izz, ixy, ixz, iyz;
+					if constexpr (CREC) { mass = hc[9]; ixx = hc[3]; iyy = hc[4]; izz = hc[5]; ixy = hc[6]; ixz = hc[7]; iyz = hc[8]; }
+					else { mass = tj.mass; ixx = tj.ibody[0]; iyy = tj.ibody[1]; izz = tj.ibody[2]; ixy = tj.ibody[3]; ixz = tj.ibody[4]; iyz = tj.ibody[5]; }
 					const double *X = xm;
-					const double ixx = tj.ibody[0], iyy = tj.ibody[1], izz = tj.ibody[2], ixy = tj.ibody[3], ixz = tj.ibody[4], iyz = tj.ibody[5];
 					double Tm[9];
 					for (int rr = 0; rr < 3; rr++) {
 						Tm[3 * rr + 0] = X[3 * rr] * ixx + X[3 * rr + 1] * ixy + X[3 * rr + 2] * ixz;
 						Tm[3 * rr + 1] = X[3 * rr] * ixy + X[3 * rr + 1] * iyy + X[3 * rr + 2] * iyz;
 						Tm[3 * rr + 2] = X[3 * rr] * ixz + X[3 * rr + 1] * iyz + X[3 * rr + 2] * izz;
+					}
+					if constexpr (CREC) {
+						// (every read of the ring has landed: the next needed body's record is fetched from here on, under the rest of cinert and the cdof
+						//  half -- the compiler may not lift its loads into the counted waits above)
+						constexpr int nx = [] { for (int q = b + 1; q < T::NBODY; q++) if (LD::needed(q)) return q; return T::NBODY; }();
+						touch_v(dif[0]);
+						touch_v(dif[1]);
+						touch_v(dif[2]);
+						LE_PK(8);
+						__builtin_amdgcn_sched_barrier(0);
+						if constexpr (nx < NB) c_fetch(IC<nx>{});
 					}
 					ci[0] = Tm[0] * X[0] + Tm[1] * X[1] + Tm[2] * X[2] + mass * (dif[1] * dif[1] + dif[2] * dif[2]);
 					ci[1] = Tm[3] * X[3] + Tm[4] * X[4] + Tm[5] * X[5] + mass * (dif[0] * dif[0] + dif[2] * dif[2]);
@@ -834,13 +884,13 @@ DEVI void lane_env_body(const KernelParams MJB_AS4 *__restrict__ P, const int ns
 					if constexpr (DV) qv = lp[64 * j].b;
 					double *cd = cdof[j];
 					constexpr int cq = CD0 + 3 * (ord % 2);  // (quartet) the body's slots of the cdof ring
-					if constexpr (ROLE == LE_QUAD_V) {  // (the quartet's V: C's cdof, one phase old)
-						const Pair d0 = lp[64 * cq], d1 = lp[64 * (cq + 1)], d2 = lp[64 * (cq + 2)];
-						cd[0] = d0.a; cd[1] = d0.b; cd[2] = d1.a; cd[3] = d1.b; cd[4] = d2.a; cd[5] = d2.b;
-						if constexpr (T::jnt_type[j] == MJB_JNT_SLIDE) cd[0] = cd[1] = cd[2] = 0;
-					} else {
+					{
 					const LeTapeBody MJB_AS4 &tj = tb[b];
-					const double ax[3] = { tj.jaxis[0], tj.jaxis[1], tj.jaxis[2] };
+					constexpr bool CREC = ROLE == LE_QUAD_C;
+					[[maybe_unused]] const double *const hc = hC[CREC ? b : 0];
+					double ax[3];
+					if constexpr (CREC) { ax[0] = hc[10]; ax[1] = hc[11]; ax[2] = hc[12]; }
+					else { ax[0] = tj.jaxis[0]; ax[1] = tj.jaxis[1]; ax[2] = tj.jaxis[2]; }
 					double xaxis[3];
 					matvec3(xaxis, xm, ax);
 					if constexpr (T::jnt_type[j] == MJB_JNT_SLIDE) {
@@ -848,7 +898,9 @@ DEVI void lane_env_body(const KernelParams MJB_AS4 *__restrict__ P, const int ns
 						for (int k = 0; k < 3; k++) cd[3 + k] = xaxis[k];
 					} else {
 						// (the anchor from the body's FINAL frame: xpos + xmat jnt_pos -- the point mj_kinematics' off-centre correction keeps fixed)
-						const double jp[3] = { tj.jpos[0], tj.jpos[1], tj.jpos[2] };
+						double jp[3] = { 0, 0, 0 };
+						if constexpr (!CREC) { jp[0] = tj.jpos[0]; jp[1] = tj.jpos[1]; jp[2] = tj.jpos[2]; }
+						else if constexpr (!LeOffc<T>::known || LeOffc<T>::on(j)) { jp[0] = hc[13]; jp[1] = hc[14]; jp[2] = hc[15]; }
 						double xanch[3] = { xp[0], xp[1], xp[2] }, off[3];
 						if (le_offc<T, QUAD, j>(jp[0], jp[1], jp[2])) {
 							double v[3];
@@ -1344,13 +1396,19 @@ DEVI void lane_env_body(const KernelParams MJB_AS4 *__restrict__ P, const int ns
 						if constexpr (T::jnt_type[j] == MJB_JNT_SLIDE) cd[0] = cd[1] = cd[2] = 0;
 					}
 				};
-				auto x_phase = [&](auto Bq) {
+				auto x_phase = [&](auto Bq, auto Cq) {  // (Cq: the body whose cdof this phase takes from C's ring, 0: none yet)
 					constexpr int b = Bq, nx = NEXTN(b);
 					touch_s(hA[b][0]);
 					touch_s(hB[b][0]);
 					if constexpr (nx < NB) {
 						for (int k = 0; k < 14; k++) hA[nx][k] = reinterpret_cast<const double MJB_AS4 *>(tb + nx)[k];
 						for (int k = 0; k < 10; k++) hB[nx][k] = reinterpret_cast<const double MJB_AS4 *>(tb + nx)[16 + k];
+					}
+					// (the cdof reads beside the quaternion's at the top of the phase, not between the pose writes and the barrier: they land under the body)
+					constexpr int cb = Cq;
+					if constexpr (cb > 0) {
+						x_cdof(Cq);
+						__builtin_amdgcn_sched_barrier(0);
 					}
 					x_body(Bq);
 					if constexpr (nx < NB) {
@@ -1366,6 +1424,68 @@ DEVI void lane_env_body(const KernelParams MJB_AS4 *__restrict__ P, const int ns
 						}
 					}
 				};
+				// V, body b: consume's velocity half in three pieces, so that the force half runs ONE BODY BEHIND the kinematic half.  A phase issues its body's
+				// nine reads (C's cinert and cdof, qvel), works off the PREVIOUS body's forces from registers while they land -- the three cfrc writes leave
+				// early in the phase and have drained long before the barrier; nobody reads them ahead of V's own leaf -> root walk -- and then takes its own
+				// body's velocities.  The body's cinert waits in registers across the barrier.  The arithmetic is consume's, expression for expression.
+				[[maybe_unused]] double vci[ROLE == LE_QUAD_V ? NB : 1][10], vqv[ROLE == LE_QUAD_V ? NB : 1];
+				[[maybe_unused]] auto v_fetch = [&](auto Bq) {
+					constexpr int b = Bq, j = T::body_jnt[b], c0 = LD::cin_slot(b);
+					static_assert(c0 >= 0, "the quartet: every needed body's cinert lives in LDS");
+					if constexpr (j >= 0) {
+						constexpr int cq = CD0 + 3 * (((LD::slot(b) - NV) / 3) % 2);
+						const Pair d0 = lp[64 * cq], d1 = lp[64 * (cq + 1)], d2 = lp[64 * (cq + 2)];
+						vqv[b] = lp[64 * j].b;
+						double *cd = cdof[j];
+						cd[0] = d0.a; cd[1] = d0.b; cd[2] = d1.a; cd[3] = d1.b; cd[4] = d2.a; cd[5] = d2.b;
+						if constexpr (T::jnt_type[j] == MJB_JNT_SLIDE) cd[0] = cd[1] = cd[2] = 0;
+					}
+					for (int k = 0; k < 5; k++) {
+						const Pair c = lp[64 * (c0 + k)];
+						vci[b][2 * k] = c.a;
+						vci[b][2 * k + 1] = c.b;
+					}
+				};
+				[[maybe_unused]] auto v_kin = [&](auto Bq) {
+					constexpr int b = Bq, p = T::body_parentid[b], j = T::body_jnt[b];
+					double pv[6], pa[6];
+					if constexpr (p == 0 || !LD::needed(p)) {  // the world, or a jointless chain down from it: at rest
+						for (int k = 0; k < 6; k++) pv[k] = 0;
+						pa[0] = pa[1] = pa[2] = 0;
+						for (int k = 0; k < 3; k++) pa[3 + k] = -grav[k];
+					} else {
+						for (int k = 0; k < 6; k++) { pv[k] = cvel[p][k]; pa[k] = cacc[p][k]; }
+					}
+					if constexpr (j >= 0) {
+						const double qv = vqv[b];
+						const double *cd = cdof[j];
+						if constexpr (p == 0 || !LD::needed(p)) {
+							for (int k = 0; k < 6; k++) { cvel[b][k] = cd[k] * qv; cacc[b][k] = pa[k]; }
+						} else {
+							double cdd[6];
+							cross_motion(cdd, pv, cd);
+							for (int k = 0; k < 6; k++) { cvel[b][k] = pv[k] + cd[k] * qv; cacc[b][k] = pa[k] + cdd[k] * qv; }
+						}
+					} else {
+						for (int k = 0; k < 6; k++) { cvel[b][k] = pv[k]; cacc[b][k] = pa[k]; }
+					}
+				};
+				[[maybe_unused]] auto v_force = [&](auto Bq) {
+					constexpr int b = Bq, q0 = LD::slot(b);
+					double cf[6], t0[6], t1[6];
+					mul_inert_vec(cf, vci[b], cacc[b]);
+					mul_inert_vec(t0, vci[b], cvel[b]);
+					cross_force(t1, cvel[b], t0);
+					lp[64 * q0] = Pair{ cf[0] + t1[0], cf[1] + t1[1] };
+					lp[64 * (q0 + 1)] = Pair{ cf[2] + t1[2], cf[3] + t1[3] };
+					lp[64 * (q0 + 2)] = Pair{ cf[4] + t1[4], cf[5] + t1[5] };
+				};
+				if constexpr (ROLE == LE_QUAD_C) {  // the first needed body's record, ahead of the phases as O's and X's
+					if constexpr (N1 < NB) {
+						c_fetch(IC<(N1 < NB ? N1 : 1)>{});
+						c_touch(IC<(N1 < NB ? N1 : 1)>{});
+					}
+				}
 				if constexpr (ROLE == LE_QUAD_O || ROLE == LE_QUAD_X) {
 					// the bodies at rest, then the first needed body's record
 					sfor<NB>([&](auto Bq) {
@@ -1398,14 +1518,30 @@ DEVI void lane_env_body(const KernelParams MJB_AS4 *__restrict__ P, const int ns
 				sfor<KN + 3>([&](auto Ki) {
 					constexpr int k = Ki + 1;
 					constexpr int kk = k - (ROLE - LE_QUAD_O);  // this role's body, counted among the needed ones
+					// (X) cdof of the body C handled one phase ago, beside V's read of the same slot; in phase KN + 3, behind the last barrier, the last body's
+					constexpr bool xcd = ROLE == LE_QUAD_X && k - 3 >= 1 && k - 3 <= KN;
+					constexpr int xcb = xcd ? NTH(k - 3 >= 1 ? k - 3 : 1) : 0;
 					if constexpr (kk >= 1 && kk <= KN) {
 						constexpr int bb = NTH(kk);
 						if constexpr (ROLE == LE_QUAD_O) o_phase(IC<bb>{});
-						else if constexpr (ROLE == LE_QUAD_X) x_phase(IC<bb>{});
-						else consume(IC<bb>{});
-					}
-					// (X) cdof of the body C handled one phase ago, beside V's read of the same slot; in phase KN + 3, behind the last barrier, the last body's
-					if constexpr (ROLE == LE_QUAD_X && k - 3 >= 1 && k - 3 <= KN) x_cdof(IC<NTH(k - 3 >= 1 ? k - 3 : 1)>{});
+						else if constexpr (ROLE == LE_QUAD_X) x_phase(IC<bb>{}, IC<xcb>{});
+						else if constexpr (ROLE == LE_QUAD_C) {
+							consume(IC<bb>{});
+							if constexpr (kk < KN) c_touch(IC<NTH(kk < KN ? kk + 1 : 1)>{});
+						} else {
+							// (V) this body's reads, the previous body's forces, this body's velocities; behind the sweep's last barrier the last body's forces too
+							v_fetch(IC<bb>{});
+							__builtin_amdgcn_sched_barrier(0);
+							if constexpr (kk > 1) v_force(IC<NTH(kk > 1 ? kk - 1 : 1)>{});
+							__builtin_amdgcn_sched_barrier(0);  // (the cfrc writes leave here, ahead of the body's velocities, and drain under them)
+#ifdef MJB_LE_PROBE
+							if constexpr (T::body_jnt[bb] >= 0) touch_v(vqv[bb]);
+							LE_PK(8);
+#endif
+							v_kin(IC<bb>{});
+							if constexpr (kk == KN) v_force(IC<bb>{});
+						}
+					} else if constexpr (xcd) x_cdof(IC<xcb>{});
 					if constexpr (DV && k == 1) sfor<NV>([&](auto I) { qfa[I] = s.qfrc_applied[ev * NV + I]; });  // (read by the force block behind the sweep: a trip to HBM)
 					if constexpr (k <= KN + 2) {
 						LE_PK(0);
@@ -2091,6 +2227,7 @@ DEVI void lane_env_body(const KernelParams MJB_AS4 *__restrict__ P, const int ns
 		}
 	}
 #ifdef MJB_LE_PROBE
+	if (env_raw == env_lo && QUAD) P->s.sensordata[32 + (ROLE - LE_QUAD_O)] = (double)pk_acc[8] / nsteps;  // (behind X's eight, in env 1's sensordata)
 	if (env_raw == env_lo) for (int k = 0; k < 8; k++) P->s.sensordata[(ROLE == LE_PIPE_V || ROLE == LE_DUO_V || ROLE == LE_TRIO_C || ROLE == LE_QUAD_C ? 8 : (ROLE == LE_TRIO_V || ROLE == LE_QUAD_V ? 16 : (ROLE == LE_QUAD_X ? 24 : 0))) + k] = (double)pk_acc[k] / nsteps;
 #endif
 
