@@ -307,7 +307,26 @@ int mjb_fused_frame(const mjb_batch *b);
  * table has no slot for such a body; mjb_lane_env_plan answers -1 for the xfrc builds).  Measured on config 2's arm with a wrist IMU, a wrist force /
  * torque pair, an end-effector framelinvel and a base force sensor (tools/lane_env_sensors_rate.py, profiles/lane_env_sensors.txt): 262 against the
  * generic kernel's 69 M env-steps/s at 4096 envs (3.8 x), 2783 against 93 at 65 536 (30.1 x); 0.87 / 0.74 of the same arm's rate without those sensors,
- * and 0.76 / 0.68 of its own rate when sensors are evaluated at every step.  No reference counterpart. */
+ * and 0.76 / 0.68 of its own rate when sensors are evaluated at every step.  No reference counterpart.
+ * Joint limits under PGS: a hinge / slide tree whose ONLY constraint rows are joint-limit rows is eligible too (mjb_model_lane_env() == -2) -- solver PGS,
+ * no contacts, equalities, tendons or dry friction (dof_frictionloss), every limited joint's range wider than twice its margin (at most one row per
+ * joint at a time), and nefcmax equal to the number of limited joints (a <size njmax> that lowered the capacity keeps the generic kernels: truncation and
+ * MJB_WARN_CNSTRFULL live there); Newton and CG models keep the generic kernels.  Such a model is never a compiled-in topology: its limit set is part of
+ * the structure hiprtc builds the kernel for, and its launches run the one-wavefront form (mjb_lane_env_last_form() == 0) whatever form is asked for, in
+ * the PLAIN build only -- with activation states, gravity compensation and the sensors above (the acceleration stage sees the constrained qacc).  The
+ * constraint stage is mj_step's for one env per lane: the active rows from qpos (a wavefront in which no lane has a row pays the comparisons and nothing
+ * else), mj_makeImpedance, AR = J M^-1 J' + R from the L'DL factor of M, the warmstart from qacc_warmstart -- read at the launch's start, carried across
+ * its steps, zero after a mj_check* reset, written back at its end: launch splits and hand-overs to and from the generic kernels carry it --, mj_solPGS
+ * with each lane's own stopping test, mj_checkAcc on the constrained qacc.  Beside the state and sensordata the launch leaves, of its LAST step,
+ * qfrc_constraint, nefc (the env's active rows) and solver_iter, which mjb_get / mjb_get_int serve after such a launch without mjb_set_keep_frame; the
+ * efc_* arrays are NOT written.  A batch with per-env gravity or parameter blocks (mode 2), a device hwsim stage or a written xfrc_applied keeps the generic
+ * kernels for such a model (no overlay, hwsim or xfrc build has the stage; mjb_lane_env_plan answers -1 for builds 1 - 4), bit-equal to a mode-0 batch.
+ * The automatic mode (-1) KEEPS THE GENERIC KERNELS for these models at every batch size: modes 1 and 2 (without overrides) take the kernel, at any batch
+ * size.  Measured on config 2's arm with limited="true" on its nine joints under the benchmark's ctrl noise, where 59 % of the env-steps have at least one
+ * active row and a step with rows takes 2.2 sweeps on average (tools/lane_env_limits_rate.py, profiles/lane_env_limits.txt; the median of 5): 90.8
+ * against the generic kernels' 44.8 M env-steps/s at 4096 envs (2.03 x), 660 against 45.5 at 65 536 (14.5 x); 0.31 / 0.18 of plain franka_like's rate in
+ * the same one-wavefront form -- with 64 envs to a wavefront nearly every step finds some lane at a limit, and the PGS loop runs as long as its slowest
+ * lane.  The kernel is ahead at 4096 envs; switching the automatic rule is left to a later change.  No reference counterpart. */
 int mjb_set_lane_env(mjb_batch *b, int mode);
 /* Opt-in (default off): with on = 1 the device hwsim stage (mjb_hwsim_configure, below) no longer stands the lane = env kernel down.  The batch's
  * eligible launches then run the kernel's one-wavefront form (mjb_lane_env_last_form() == 0, at the LDS budget the batch size gives, whatever form is
@@ -365,7 +384,7 @@ int mjb_model_frame_info(const mjb_model *m, int *full_hbm, int *fused_hbm);
 /* >= 0: index of the compiled-in topology the batch's model matches; -2: none compiled in, but the model's structure fits the kernel -- its
  * first eligible launch builds the kernel for it through hiprtc (libhiprtc.so and csrc/mjb_lane_env_kernel.h next to libmjb.so; a few
  * seconds, cached per process); -3: that build was not possible (mjb_lane_env_error says why) and the generic kernels run; -1: the model does not
- * fit (constraint rows, free / ball joints, RK4, a sensor outside the list at mjb_compile, ...).  *used_last (may be NULL) = 1 when the last fused launch ran the lane = env kernel. */
+ * fit (constraint rows other than PGS joint limits alone, free / ball joints, RK4, a sensor outside the list at mjb_compile, ...).  *used_last (may be NULL) = 1 when the last fused launch ran the lane = env kernel. */
 int mjb_lane_env_info(const mjb_batch *b, int *used_last);
 /* hiprtc builds of the lane = env kernel are kept on disk: $MJB_JIT_CACHE (default $XDG_CACHE_HOME/mjb_jit or ~/.cache/mjb_jit; "0" = off), one code
  * object per (gfx arch, kernel-header fingerprint, LDS budget, form, topology).  Counts of this process: kernels compiled / taken from the cache. */
@@ -379,6 +398,10 @@ int mjb_model_lane_env(const mjb_model *m);
  * ipos[3] ibody[6] mass damping armature hdamping pad[3] | per actuator, 16: gear ctrlrange[2] gain[3] bias[3] forcerange[2] dyntau actrange[2] pad[2]; ibody =
  * R(iquat) diag(inertia) R(iquat)' as xx yy zz xy xz yz, hdamping = timestep * damping, dyntau = max(mjMINVAL, dynprm[0]) of a filter actuator -- the
  * time constant itself, which act_dot divides by, not its reciprocal -- and 0 for every other; dyntau and actrange are 0 for a stateless actuator.
+ * A model with joint-limit rows has, BEHIND those records (their offsets stay), 8 doubles: meaninertia tolerance iterations 1/(meaninertia max(1, nv))
+ * mjDSBL_WARMSTART mjDSBL_REFSAFE pad[2] | per limited joint, in joint order, 16: range[2] margin solref[2] solimp[5] dof_invweight0 K B powa powb pad --
+ * solref / solimp as getsolparam leaves them (a mixed-sign solref replaced by the default, refsafe, solimp clamped to its legal ranges), K / B the row's
+ * stiffness and damping from them (mj_makeImpedance), powa / powb = 1 / mid^(power - 1) and 1 / (1 - mid)^(power - 1) of the impedance curve.
  * mjb_model_lane_env_overlay: one env's column of the per-env table of mjb_set_lane_env's mode 2, here with the model's own values -- gravity[3] | per
  * jointed body: stiffness damping armature hdamping | per moving body (a joint on its path to the world): mass ibody[6] | per actuator: gain[3] bias[3]
  * | the mass of every other body but the world (mjENBL_ENERGY reads it). */
@@ -392,7 +415,8 @@ int mjb_model_lane_env_overlay(const mjb_model *m, double *out, int cap);
  * 40 / 80 / 160 as MJB_LANE_ENV_LDS_KB.  Fills (each may be NULL) the form, form 3's sweep wavefronts (0 otherwise) and the LDS budget in KB, the
  * values mjb_lane_env_last_form / mjb_lane_env_last_sweep_waves report after such a launch.  A model with activation states (na > 0): form 0 whatever
  * is asked for, and no variant at all for build 2.  A model with a frame-axis, velocity- or acceleration-stage sensor: form 0 whatever is asked for,
- * and no variant for builds 3 and 4 when a force / torque sensor sits on a body without a joint on its path to the world.  Returns 0; -1: the model is not eligible or needs more LDS than a CU has, there is no such variant,
+ * and no variant for builds 3 and 4 when a force / torque sensor sits on a body without a joint on its path to the world.  A model with joint-limit
+ * rows: form 0 whatever is asked for, at the smallest budget its packed AR fits beside the state, and no variant for builds 1 - 4.  Returns 0; -1: the model is not eligible or needs more LDS than a CU has, there is no such variant,
  * or an argument is out of range. */
 int mjb_lane_env_plan(const mjb_model *m, int ncu, int nenv, int build, int form, int sweep_waves, int lds_kb, int *out_form, int *out_sweep_waves, int *out_lds_kb);
 const char *mjb_lane_env_error(void);

@@ -189,6 +189,8 @@ struct mjb_batch {
 	double *le_xfrc = nullptr;     // their wrench table, [6 * mjb_lane_env_xfrc_slots][nenv] (DevState::le_xfrc), built at the first such launch
 	bool le_xfrc_stale = true;     // xfrc_applied has been written (or reset) since the table was last filled
 	int lane_env_mode = -1;        // mjb_set_lane_env: -1 automatic, 0 never, 1 whenever eligible, 2 whenever eligible, also with per-env gravity / parameter blocks
+	double *le_con = nullptr;      // lane = env kernel, a model with joint limits: qfrc_constraint | nefc | solver_iter of a launch's last step, [nenv][nv + 2] (KernelParams::le_con), allocated at the first such launch
+	bool le_con_valid = false;     // ... and the last launch was one: mjb_get / mjb_get_int serve those three fields from it
 	double *le_overlay = nullptr;  // mode 2: the per-env overlay of the lane = env kernel, [mjb_lane_env_overlay_slots][nenv] (DevState::le_overlay), built at the first such launch
 	int le_ov_lo = 0, le_ov_hi = 0;  // envs [lo, hi) whose overlay columns a setter has outdated since (empty: lo >= hi)
 	// the split step (mjb_set_split_step): smooth half in lane = env form + constraint half per wavefront, alternating on a few streams of env slices
@@ -1487,6 +1489,7 @@ void mjb_free_batch(mjb_batch *b)
 	if (b->env_mass) hipFree(b->env_mass);
 	if (b->le_overlay) hipFree(b->le_overlay);
 	if (b->le_xfrc) hipFree(b->le_xfrc);
+	if (b->le_con) hipFree(b->le_con);
 	if (b->hw_ints) hipFree(b->hw_ints);
 	if (b->hw_gains) hipFree(b->hw_gains);
 	if (b->hw_cmd) hipFree(b->hw_cmd);
@@ -1796,6 +1799,7 @@ static int sync_params(mjb_batch *b)
 		kp.s = b->st;
 		kp.nz = b->nz;
 		kp.hw = b->hw;
+		kp.le_con = b->le_con;
 		// pageable source: the copy is staged before the call returns, so the local may go out of scope
 		HIP_TRY(hipStreamSynchronize(b->stream));
 		// (the fused launch of the non-callback envs, mjb_step_rest, runs on its own non-blocking stream and reads *params_dev lazily
@@ -2178,16 +2182,22 @@ static int speculate_ctrl_noise(mjb_batch *b, const LaunchReq &q, int zhalf_now)
 // keep the generic kernels.
 // (mjb_lane_env_set_hwsim: the hwsim stage rides along in the kernel's HW build -- unless the batch has per-env gravity or parameter blocks too)
 // (... or the model has activation states: no build of the kernel has both, mjb_lane_env_plan answers -1)
-static bool le_hwsim(const mjb_batch *b) { return b->hw.n > 0 && b->lane_env_hwsim && b->hw_le_ok && !b->env_mass && !b->env_gravity && b->model->h.na <= 0; }
+// (... or joint limits: the plain build alone has the constraint stage -- no overlay, hwsim or xfrc build of such a model, mjb_lane_env_plan answers -1)
+static bool le_limits(const mjb_batch *b) { return b->model->le_topo == MJB_LE_TOPO_JIT && mjb_lane_env_limits(&b->model->h) > 0; }
+static bool le_hwsim(const mjb_batch *b) { return b->hw.n > 0 && b->lane_env_hwsim && b->hw_le_ok && !b->env_mass && !b->env_gravity && b->model->h.na <= 0 && !le_limits(b); }
 // (mjb_lane_env_set_xfrc: a written xfrc_applied rides along in the kernel's XF builds -- unless the batch has a hwsim stage, there is no build with both.
 //  LaunchReq::compact stays what the generic path's frame choice reads; for this kernel, which has no frame, the xfrc term of it is lifted)
 // (... or the model has a force / torque sensor on a body at rest: the wrench table has no slot for that body's xfrc_applied, mjb_lane_env_plan answers -1)
-static bool le_xfrc(const mjb_batch *b) { return b->st.use_xfrc && b->lane_env_xfrc && b->hw.n == 0 && !mjb_lane_env_wrench_at_rest(&b->model->h); }
+static bool le_xfrc(const mjb_batch *b) { return b->st.use_xfrc && b->lane_env_xfrc && b->hw.n == 0 && !mjb_lane_env_wrench_at_rest(&b->model->h) && !le_limits(b); }
 static bool want_lane_env(const mjb_batch *b, const LaunchReq &q, int variant)
 {
 	const bool frameless = q.compact || (le_xfrc(b) && !b->st.keep_frame);
-	if (!(q.mode == MJB_MODE_STEP && frameless && variant == MJB_KV_NONE && b->model->le_topo != MJB_LE_TOPO_NONE && !b->le_unavailable && b->lane_env_mode != 0 &&
-	      (no_env_overrides(b) || (b->lane_env_mode == 2 && b->hw.n == 0) || le_hwsim(b)) && !b->st.stats))  // (mode 2: per-env gravity and parameter blocks ride along, le_overlay_sync)
+	// (a model with joint limits is a PGS model to the generic kernels: the lane = env kernel takes it when asked to, modes 1 and 2 -- the automatic mode
+	//  keeps the generic kernels for it -- and without per-env overrides of any kind)
+	const bool lim = le_limits(b);
+	if (!(q.mode == MJB_MODE_STEP && frameless && (lim ? (mjb_kv_pgs(variant) && b->lane_env_mode >= 1) : variant == MJB_KV_NONE) && b->model->le_topo != MJB_LE_TOPO_NONE &&
+	      !b->le_unavailable && b->lane_env_mode != 0 &&
+	      (no_env_overrides(b) || (b->lane_env_mode == 2 && b->hw.n == 0 && !lim) || le_hwsim(b)) && !b->st.stats))  // (mode 2: per-env gravity and parameter blocks ride along, le_overlay_sync)
 		return false;
 	static const int min_envs = mjb_env_int("MJB_LANE_ENV_MIN_ENVS", 4096);
 	return b->lane_env_mode >= 1 || q.env_hi - q.env_lo >= min_envs;  // (also the fused launch of a split step's non-callback envs, mjb_step_rest)
@@ -2293,6 +2303,11 @@ static int launch(mjb_batch *b, int mode, int nsteps, int env_lo = 0, int env_hi
 	if (le_per_env && (rc = le_overlay_sync(b))) return rc;
 	const bool le_xf = le_xfrc(b) && !use_split && want_lane_env(b, q, variant);
 	if (le_xf && (rc = le_xfrc_sync(b, q.stream))) return rc;
+	if (!b->le_con && le_limits(b) && !use_split && want_lane_env(b, q, variant)) {  // what the kernel leaves of its constraint stage: allocated at the first such launch
+		b->le_con = dev_alloc<double>((size_t)b->nenv * (size_t)(b->model->h.nv + 2));
+		if (!b->le_con) return fail(MJB_ENOMEM, "lane = env kernel: allocation of the constraint stage's output failed");
+		b->params_dirty = true;
+	}
 	if ((rc = sync_params(b))) return rc;
 	if (use_split) {
 		if (b->zvalid) {  // (the pre-generated ctrl-noise buffer names an older launch: this path draws its normals in the smooth kernel)
@@ -2300,11 +2315,13 @@ static int launch(mjb_batch *b, int mode, int nsteps, int env_lo = 0, int env_hi
 			b->zvalid = false;
 		}
 		b->lane_env_used = false;
+		b->le_con_valid = false;
 		b->noise_mode = 0;
 		return launch_split(b, nsteps, env_lo, env_hi, q.stream);
 	}
 	variant = pgs_build(b, q, variant);
-	if ((rc = choose_chunk(b, q, variant, &chunk))) return rc;
+	chunk = 0;
+	if (!(le_limits(b) && want_lane_env(b, q, variant)) && (rc = choose_chunk(b, q, variant, &chunk))) return rc;  // (a limit model on the lane = env kernel: no work queue)
 	if ((rc = stage_ctrl_noise(b, q, variant, &zuse, &zhalf_now))) return rc;
 	const bool zspec = zuse && b->zdouble;
 	if (zspec) HIP_TRY(hipEventRecord(b->ev_noise_go, q.stream));  // (everything before this launch -- the last reader of the other half -- is done)
@@ -2319,6 +2336,7 @@ static int launch(mjb_batch *b, int mode, int nsteps, int env_lo = 0, int env_hi
 			b->lane_env_used = use_le = false;
 		}
 	}
+	b->le_con_valid = use_le && q.whole && le_limits(b);
 	if (!use_le) {
 		const StepLaunch a = { b->params_dev, q.compact ? (b->wide ? &b->model->Lw : &b->model->Lc) : &b->L, env_lo, env_hi, mode, nsteps, b->step_counter,
 			                   b->lanes, b->epb, variant, chunk, dense_build(b, mode), q.stream };
@@ -2556,6 +2574,7 @@ int mjb_reset(mjb_batch *b, const uint8_t *mask)
 	if (rc != 0) return fail(MJB_ENODEVICE, "reset launch failed: %s", hipGetErrorString((hipError_t)rc));
 	if (mask) HIP_TRY(hipStreamSynchronize(b->stream));
 	b->frame_valid = false;
+	b->le_con_valid = false;
 	b->le_xfrc_stale = true;  // (mj_resetData zeroes xfrc_applied)
 	if (!mask) b->rowstat_ever = false;  // (a new workload: the next long launch probes its rows first)
 	return MJB_OK;
@@ -2603,6 +2622,12 @@ int mjb_get(mjb_batch *b, int field, int env_lo, int env_hi, double *host)
 		                  hipMemcpyDeviceToHost));
 		return MJB_OK;
 	}
+	if (b->le_con_valid && !b->frame_valid && !strcmp(kFields[field].name, "qfrc_constraint")) {  // (what the lane = env kernel left of a limit model's last step)
+		const size_t ld = (size_t)b->model->h.nv + 2;
+		HIP_TRY(hipMemcpy2D(host, (size_t)n * sizeof(double), b->le_con + (size_t)env_lo * ld, ld * sizeof(double), (size_t)n * sizeof(double), (size_t)(env_hi - env_lo),
+		                    hipMemcpyDeviceToHost));
+		return MJB_OK;
+	}
 	if (!b->frame_valid || !b->st.frame_ws || env_hi > b->frame_hi)
 		return fail(MJB_EINVAL, "derived field %s is only readable after mjb_forward / mjb_step1 / mjb_step2",
 		            kFields[field].name);
@@ -2621,6 +2646,16 @@ int mjb_get_int(mjb_batch *b, int field, int env_lo, int env_hi, int *host)
 	const int n = b->model->field_size[field];
 	if (n == 0 || env_lo == env_hi) return MJB_OK;
 	if (!host) return fail(MJB_EINVAL, "null host buffer");
+	if (b->le_con_valid && !b->frame_valid && (!strcmp(kFields[field].name, "nefc") || !strcmp(kFields[field].name, "solver_iter"))) {  // (the lane = env kernel keeps the two counts as doubles)
+		const size_t ld = (size_t)b->model->h.nv + 2, nrow = (size_t)(env_hi - env_lo);
+		std::vector<double> v(nrow);
+		HIP_TRY(hipSetDevice(b->device));
+		HIP_TRY(hipStreamSynchronize(b->stream));
+		HIP_TRY(hipMemcpy2D(v.data(), sizeof(double), b->le_con + (size_t)env_lo * ld + (size_t)b->model->h.nv + (strcmp(kFields[field].name, "nefc") ? 1 : 0), ld * sizeof(double),
+		                    sizeof(double), nrow, hipMemcpyDeviceToHost));
+		for (size_t e = 0; e < nrow; e++) host[e] = (int)v[e];
+		return MJB_OK;
+	}
 	if (!b->frame_valid || !b->st.frame_ws || env_hi > b->frame_hi)
 		return fail(MJB_EINVAL, "int field %s is only readable after mjb_forward / mjb_step1 / mjb_step2",
 		            kFields[field].name);

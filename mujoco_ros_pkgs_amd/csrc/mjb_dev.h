@@ -102,6 +102,13 @@ struct LeTapeBody {
 // (dyntau: a filter actuator's max(mjMINVAL, dynprm[0]) -- the divisor of act_dot, not its reciprocal; actlo / acthi: actrange.  Zero for a stateless actuator)
 struct LeTapeAct { double gear, ctrllo, ctrlhi, gain[3], bias[3], forcelo, forcehi, dyntau, actlo, acthi, pad[2]; };
 static_assert(sizeof(LeTapeHdr) == 64 && sizeof(LeTapeBody) == 256 && sizeof(LeTapeAct) == 128, "lane = env tape records");
+// Joint limits (a model whose only constraint rows are hinge / slide joint-limit rows under PGS, mjb_lane_env_eligible): BEHIND the records above -- their
+// offsets stay where they are -- one LeTapeLimHdr, then one LeTapeLim per limited joint, in joint order.  solref / solimp are stored as getsolparam
+// leaves them (a mixed-sign solref replaced by the default, refsafe, solimp clamped to its legal ranges); K and B are mj_makeImpedance's stiffness and
+// damping of the row from them, powa / powb the two wave-uniform factors of the impedance curve, 1 / mid^(power - 1) and 1 / (1 - mid)^(power - 1).
+struct LeTapeLimHdr { double meaninertia, tolerance, iterations, scale /* 1 / (meaninertia max(1, nv)) */, nowarm /* mjDSBL_WARMSTART */, norefsafe /* mjDSBL_REFSAFE */, pad[2]; };
+struct LeTapeLim { double range[2], margin, solref[2], solimp[5], invweight0, K, B, powa, powb, pad; };
+static_assert(sizeof(LeTapeLimHdr) == 64 && sizeof(LeTapeLim) == 128, "lane = env tape records of the joint limits");
 
 // Offsets (in doubles / ints) of every data field inside one per-env frame.
 struct FrameLayout {
@@ -299,6 +306,9 @@ struct KernelParams {
 	DevState s;
 	NoiseCfg nz;
 	HwSim hw;
+	// (behind everything the kernels compiled before it read: their offsets stay) lane = env kernel, a model with joint limits: what the launch leaves of the
+	// constraint stage of its last step, [nenv][nv + 2] = qfrc_constraint[nv] | nefc | solver_iter (as doubles); NULL until such a launch allocates it
+	double *le_con;
 };
 
 // ---- the step kernel's variants: the value of mjb_step_kernel's template parameter CON (TAG in the constraint stages), of MJB_DEV_ONLY_CON and
@@ -371,6 +381,7 @@ void mjb_lane_env_tape(const mjb_model_desc *h, double *tape);  // fills it
 const char *mjb_lane_env_name(int topo);
 enum { MJB_LE_TOPO_NONE = -1, MJB_LE_TOPO_JIT = -2, MJB_LE_UNAVAILABLE = -1000 };
 int mjb_lane_env_eligible(const mjb_model_desc *h);   // the model's structure fits the kernel (compiled in or not)
+int mjb_lane_env_limits(const mjb_model_desc *h);     // the joint-limit rows of a model the kernel takes WITH constraint rows (its limited joints), 0: it has none
 const char *mjb_lane_env_jit_error(void);                    // why the last hiprtc build of a topology was not available ("" if none failed)
 void mjb_lane_env_jit_stats(int *compiled, int *disk_hits);  // hiprtc builds of this process / builds taken from the disk cache instead
 // which build of the kernel a launch runs: the plain one (any form), or one of the two that exist for the solo form only and run it whatever the batch size --

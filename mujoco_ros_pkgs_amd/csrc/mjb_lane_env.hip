@@ -31,6 +31,7 @@
 #include <sys/stat.h>
 #include <unistd.h>
 
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 
@@ -119,11 +120,35 @@ template <class T> bool topo_matches(const mjb_model_desc &h)
 
 }  // namespace
 
-// what both classifications below ask first: an unconstrained Euler model of one-dof joints, without mocap bodies, tendons or equalities
+// Constraint rows the kernel takes: every row the model can ever have is a joint-limit row (of a hinge or slide: mjb_lane_env_eligible asks for the joint
+// kinds) swept by PGS -- no dry friction, a range wider than twice the margin on every limited joint (at most one row per joint at a time), and room for
+// all of them (a model whose <size njmax> lowered the capacity keeps the generic kernels: truncation and mjWARN_CNSTRFULL live there)
+static bool le_limit_rows(const mjb_model_desc *h)
+{
+	if (h->solver != MJB_SOL_PGS) return false;
+	for (int d = 0; d < h->nv; d++)
+		if (h->dof_frictionloss[d] > 0) return false;
+	int nl = 0;
+	for (int j = 0; j < h->njnt; j++)
+		if (h->jnt_limited[j]) {
+			if (!(h->jnt_range[2 * j + 1] - h->jnt_range[2 * j] > 2 * h->jnt_margin[j])) return false;
+			nl++;
+		}
+	return nl > 0 && h->nefcmax == nl;
+}
+// what both classifications below ask first: an Euler model of one-dof joints, without contacts, mocap bodies, tendons or equalities, and without constraint
+// rows -- or with joint-limit rows alone
 static bool le_plain_tree(const mjb_model_desc *h)
 {
-	return h && h->nefcmax <= 0 && h->nconmax <= 0 && h->integrator == MJB_INT_EULER && h->nmocap <= 0 && h->ntendon <= 0 && h->neq <= 0 &&
-	       h->nq == h->nv && h->njnt == h->nv;
+	return h && h->nconmax <= 0 && h->integrator == MJB_INT_EULER && h->nmocap <= 0 && h->ntendon <= 0 && h->neq <= 0 && h->nq == h->nv && h->njnt == h->nv &&
+	       (h->nefcmax <= 0 || le_limit_rows(h));
+}
+int mjb_lane_env_limits(const mjb_model_desc *h)
+{
+	int nl = 0;
+	if (h && h->nefcmax > 0 && mjb_lane_env_eligible(h))
+		for (int j = 0; j < h->njnt; j++) nl += h->jnt_limited[j] != 0;
+	return nl;
 }
 // an actuator's dynamics the kernel runs: none, or an activation state of its own that integrates ctrl / filters it (muscle and user dynamics: the loader's refusal)
 static bool le_dyntype_ok(const mjb_model_desc *h, int i)
@@ -146,7 +171,7 @@ static bool le_wrench_at_rest(const mjb_model_desc *h);
 // Index of the compiled-in topology the model has, or -1 (mjb_compile; the generic kernels run every model).
 int mjb_lane_env_match(const mjb_model_desc *h)
 {
-	if (!le_plain_tree(h)) return -1;
+	if (!le_plain_tree(h) || h->nefcmax > 0) return -1;  // (joint limits are a compile-time list of rows, LeLim: such a model is hiprtc's)
 	for (int b = 1; b < h->nbody; b++)
 		if (h->body_gravcomp[b] != 0) return -1;  // (gravity compensation is a compile-time flag per body, LeGc: no compiled-in topology has one set)
 	if (le_extra_sensors(h)) return -1;  // (... and none carries a frame-axis, velocity- or acceleration-stage sensor, LeSens: such a model is hiprtc's)
@@ -269,6 +294,7 @@ std::string topo_source(const mjb_model_desc &h)
 	arr("sensor_objtype", h.nsensor, [&](int i) { return h.sensor_objtype[i]; });
 	arr("sensor_objid", h.nsensor, [&](int i) { return h.sensor_objid[i]; });
 	arr("sensor_adr", h.nsensor, [&](int i) { return h.sensor_adr[i]; });
+	if (h.nefcmax > 0) arr("jnt_limited", h.njnt, [&](int i) { return h.jnt_limited[i] != 0; });  // (the rows of the constraint stage, LeLim: a model without them has no such line)
 	s += "};\n";
 	return s;
 }
@@ -548,7 +574,9 @@ int mjb_lane_env_last_form(void) { return le_form_last; }
 
 size_t mjb_lane_env_tape_doubles(const mjb_model_desc *h)
 {
-	return (sizeof(LeTapeHdr) + (size_t)h->nbody * sizeof(LeTapeBody) + (size_t)h->nu * sizeof(LeTapeAct)) / sizeof(double);
+	const int nl = mjb_lane_env_limits(h);  // (joint limits: a header and a record per limited joint behind the rest)
+	return (sizeof(LeTapeHdr) + (size_t)h->nbody * sizeof(LeTapeBody) + (size_t)h->nu * sizeof(LeTapeAct) + (nl > 0 ? sizeof(LeTapeLimHdr) + (size_t)nl * sizeof(LeTapeLim) : 0)) /
+	       sizeof(double);
 }
 
 // Ib = R(iquat) diag(inertia) R(iquat)': xx yy zz xy xz yz
@@ -686,6 +714,42 @@ void mjb_lane_env_tape(const mjb_model_desc *h, double *tape)
 			a.acthi = h->actuator_actrange[2 * i + 1];
 		}
 	}
+	if (mjb_lane_env_limits(h) > 0) {
+		LeTapeLimHdr *lh = reinterpret_cast<LeTapeLimHdr *>(ta + h->nu);
+		LeTapeLim *tl = reinterpret_cast<LeTapeLim *>(lh + 1);
+		lh->meaninertia = h->meaninertia[0];
+		lh->tolerance = h->tolerance[0];
+		lh->iterations = h->iterations;
+		lh->scale = 1.0 / (h->meaninertia[0] * (h->nv > 1 ? h->nv : 1));
+		lh->nowarm = (h->disableflags & MJB_DSBL_WARMSTART) ? 1.0 : 0.0;
+		lh->norefsafe = (h->disableflags & MJB_DSBL_REFSAFE) ? 1.0 : 0.0;
+		for (int j = 0; j < h->njnt; j++) {
+			if (!h->jnt_limited[j]) continue;
+			LeTapeLim &l = *tl++;
+			l.range[0] = h->jnt_range[2 * j];
+			l.range[1] = h->jnt_range[2 * j + 1];
+			l.margin = h->jnt_margin[j];
+			// getsolparam: a mixed-sign solref is replaced by the default, refsafe, solimp clamped to its legal ranges (mjMINIMP, mjMAXIMP, width >= 0, power >= 1)
+			double sr[2] = { h->jnt_solref[2 * j], h->jnt_solref[2 * j + 1] };
+			if ((sr[0] > 0) != (sr[1] > 0)) sr[0] = 0.02, sr[1] = 1.0;
+			if (!(h->disableflags & MJB_DSBL_REFSAFE) && sr[0] > 0) sr[0] = fmax(sr[0], 2 * h->timestep[0]);
+			const double *si = h->jnt_solimp + 5 * j;
+			const double imp[5] = { fmin(0.9999, fmax(0.0001, si[0])), fmin(0.9999, fmax(0.0001, si[1])), fmax(0.0, si[2]), fmin(0.9999, fmax(0.0001, si[3])), fmax(1.0, si[4]) };
+			l.solref[0] = sr[0], l.solref[1] = sr[1];
+			for (int k = 0; k < 5; k++) l.solimp[k] = imp[k];
+			l.invweight0 = h->dof_invweight0[h->jnt_dofadr[j]];
+			// mj_makeImpedance's stiffness and damping of the row
+			if (sr[0] > 0) {
+				l.K = 1 / fmax(MJB_MINVAL, imp[1] * imp[1] * sr[0] * sr[0] * sr[1] * sr[1]);
+				l.B = 2 / fmax(MJB_MINVAL, imp[1] * sr[0]);
+			} else {
+				l.K = -sr[0] / fmax(MJB_MINVAL, imp[1] * imp[1]);
+				l.B = -sr[1] / fmax(MJB_MINVAL, imp[1]);
+			}
+			l.powa = 1 / pow(imp[3], imp[4] - 1);
+			l.powb = 1 / pow(1 - imp[3], imp[4] - 1);
+		}
+	}
 }
 
 const char *mjb_lane_env_name(int topo)
@@ -716,13 +780,14 @@ struct LePlanIn {
 	bool gc;            // ... and whether a body has gravity compensation: the one-wavefront form alone has the term, in every build
 	bool sens;          // ... and whether it has a frame-axis, velocity- or acceleration-stage sensor (LeSens): the one-wavefront form alone evaluates them, in every build
 	bool wrench_rest;   // ... one of them a force / torque sensor on a body at rest: not in the xfrc builds, whose wrench table has no slot for such a body
+	int nl;             // ... and its joint-limit rows (mjb_lane_env_limits): the plain build of the one-wavefront form alone has the constraint stage
 };
 
 LeVariant le_plan(const LePlanIn &in)
 {
 	LeVariant v{ 0, 0, 0, in.build, 64, nullptr };
 	const bool plain = in.build == MJB_LE_PLAIN;
-	if (plain && (in.wave_lanes == 16 || in.wave_lanes == 32)) v.wave_lanes = in.wave_lanes;  // (the overlay, hwsim and xfrc builds always run full wavefronts)
+	if (plain && in.nl == 0 && (in.wave_lanes == 16 || in.wave_lanes == 32)) v.wave_lanes = in.wave_lanes;  // (the overlay, hwsim and xfrc builds always run full wavefronts)
 	// the LDS budget per wavefront from the CUs the batch leaves idle: one wavefront per CU may take all of its LDS, two half of it each
 	const int ncu = in.ncu, waves = (in.nenv_batch + 63) / 64;
 	v.lds_kb = (in.lds_kb == 40 || in.lds_kb == 80 || in.lds_kb == 160) ? in.lds_kb : ((ncu > 0 && waves <= ncu) ? 160 : ((ncu > 0 && waves <= 2 * ncu) ? 80 : 40));
@@ -730,7 +795,7 @@ LeVariant le_plan(const LePlanIn &in)
 	// wavefront that assembles the forces and integrates), gravity compensation (the one-wavefront form alone has the term) or a sensor beyond poses and
 	// joint / actuator scalars (the one-wavefront form alone has the velocity sensors in its sweep and the pass behind the qacc solve) -- always hiprtc's --
 	// is planned as if form 0 had been asked for, whatever is: the same budget and lanes per wavefront as that request
-	const int form = (in.fit && (in.na > 0 || in.gc || in.sens)) ? 0 : in.form;
+	const int form = (in.fit && (in.na > 0 || in.gc || in.sens || in.nl > 0)) ? 0 : in.form;
 	if (plain && form > 0 && v.lds_kb < 80) {
 		// a forced multi-wavefront form on a batch that would run four wavefronts per CU: the two halves at two per CU
 		v.form = 1;
@@ -754,11 +819,15 @@ LeVariant le_plan(const LePlanIn &in)
 		v.unavailable = "no xfrc build of the kernel has a force / torque sensor on a body at rest: the wrench table has no slot for that body";
 		return v;
 	}
+	if (in.nl > 0 && !plain) {
+		v.unavailable = "no overlay, hwsim or xfrc build of the kernel has the constraint stage of a model with joint limits";
+		return v;
+	}
 	// a hiprtc-built model may be larger than the compiled-in ones: the smallest budget its (qpos, qvel) pairs and body forces fit (fewer wavefronts per
 	// CU then), and of the forms the first one down whose layout fits
-	const int state = le_state_slots(in.nv, in.nmov);
+	const int state = le_state_slots(in.nv, in.nmov, in.nl);  // (with the packed AR and the warmstart of a model with joint limits)
 	if (state > LE_MAX_SLOTS) {
-		v.unavailable = "the model needs more than 160 KB of LDS per wavefront";
+		v.unavailable = in.nl > 0 ? "the model, with the packed AR of its joint limits, needs more than 160 KB of LDS per wavefront" : "the model needs more than 160 KB of LDS per wavefront";
 		return v;
 	}
 	const int least = state <= 40 ? 40 : (state <= 80 ? 80 : 160);
@@ -826,11 +895,12 @@ template <class T> int le_go_topo(const LeVariant &v, const LeLaunch &a)
 }
 LePlanIn le_plan_in(const mjb_model_desc *fit_model, int ncu, int nenv_batch, LeBuild build, int form, int duo_max_waves, int sweep, int lds_kb, int wave_lanes)
 {
-	LePlanIn in{ ncu, nenv_batch, build, form, duo_max_waves, sweep, lds_kb, wave_lanes, fit_model != nullptr, 0, 0, 0, 0, false, false, false };
+	LePlanIn in{ ncu, nenv_batch, build, form, duo_max_waves, sweep, lds_kb, wave_lanes, fit_model != nullptr, 0, 0, 0, 0, false, false, false, 0 };
 	if (fit_model) {
 		in.sens = le_extra_sensors(fit_model), in.wrench_rest = le_wrench_at_rest(fit_model);
 		in.nv = fit_model->nv, in.nmov = mjb_lane_env_xfrc_slots(fit_model), in.nbody = fit_model->nbody, in.na = fit_model->na;
 		for (int b = 1; b < fit_model->nbody; b++) in.gc = in.gc || fit_model->body_gravcomp[b] != 0;
+		in.nl = mjb_lane_env_limits(fit_model);
 	}
 	return in;
 }

@@ -103,6 +103,20 @@ template <int N> DEVI void touch_rec(const double *h)  // (the N entries the swe
 	asm volatile("" ::"s"(h[0]), "s"(h[1]), "s"(h[2]), "s"(h[3]), "s"(h[4]), "s"(h[5]), "s"(h[6]), "s"(h[7]), "s"(h[8]), "s"(h[9]));
 	if constexpr (N > 10) asm volatile("" ::"s"(h[10]), "s"(h[11]), "s"(h[12]), "s"(h[13]));
 }
+// ... and N loaded per-lane values at once (a row of the packed AR): their reads leave together and are waited for once, instead of one wait per use
+template <int N> DEVI void touch_vn(const double *a)
+{
+	if constexpr (N >= 8) {
+		asm volatile("" ::"v"(a[0]), "v"(a[1]), "v"(a[2]), "v"(a[3]), "v"(a[4]), "v"(a[5]), "v"(a[6]), "v"(a[7]));
+		touch_vn<N - 8>(a + 8);
+	} else if constexpr (N >= 4) {
+		asm volatile("" ::"v"(a[0]), "v"(a[1]), "v"(a[2]), "v"(a[3]));
+		touch_vn<N - 4>(a + 4);
+	} else if constexpr (N >= 2) {
+		asm volatile("" ::"v"(a[0]), "v"(a[1]));
+		touch_vn<N - 2>(a + 2);
+	} else if constexpr (N == 1) asm volatile("" ::"v"(a[0]));
+}
 DEVI double pins(double x)  // the same for a wave-uniform (scalar) value
 {
 	asm volatile("" : "+s"(x));
@@ -215,10 +229,13 @@ constexpr int RING_DUO2 = 2, RING_TRIO = 3;  // depth of the pose ring: the pipe
 constexpr int le_ring_slots(int depth) { return 6 * depth; }  // (xpos, xmat) of a body: 12 doubles
 // pair slots of a quartet block behind the trio's layout: O's quaternion ring (2 x 4), C's cdof ring (2 x 3), X's mail slot
 constexpr int QUARTET_EXTRA = 15;
-constexpr int le_state_slots(int nv, int nmov) { return nv + 3 * nmov; }  // (qpos, qvel) pairs + cfrc_body: what every form must hold
-constexpr int le_solo_slots(int nv, int nmov, int budget)                 // ... + five of cinert per body while the budget lasts
+// (nl: the joint-limit rows of a model that has them, LeLim -- the packed AR of the constraint stage, nl (nl + 1) / 2 doubles, and qacc_warmstart of the
+//  limited dofs, nl doubles, two to a pair slot, behind cfrc_body: one-wavefront form only)
+constexpr int le_lim_slots(int nl) { return (nl * (nl + 1) / 2 + nl + 1) / 2; }
+constexpr int le_state_slots(int nv, int nmov, int nl = 0) { return nv + 3 * nmov + le_lim_slots(nl); }  // (qpos, qvel) pairs + cfrc_body: what every form must hold
+constexpr int le_solo_slots(int nv, int nmov, int budget, int nl = 0)     // ... + five of cinert per body while the budget lasts
 {
-	int at = le_state_slots(nv, nmov);
+	int at = le_state_slots(nv, nmov, nl);
 	for (int k = 0; k < nmov; k++)
 		if (at + 5 <= budget) at += 5;
 	return at;
@@ -229,6 +246,20 @@ constexpr int le_duo_slots(int nv, int nmov, int budget) { return le_solo_slots(
 constexpr int le_duo2_slots(int nv, int nmov) { return le_full_slots(nv, nmov) + le_ring_slots(RING_DUO2) + le_exchange_slots(nv); }
 constexpr int le_trio_slots(int nv, int nmov, int nbody) { return le_full_slots(nv, nmov) + le_ring_slots(RING_TRIO) + le_exchange_slots(nv) + nbody; }  // (+ a (sin, cos) slot per body)
 constexpr int le_quartet_slots(int nv, int nmov, int nbody) { return le_trio_slots(nv, nmov, nbody) + QUARTET_EXTRA; }
+
+// Joint limits (mjModel.jnt_limited of a model whose only constraint rows are hinge / slide limit rows under PGS, mjb_lane_env_eligible): a topology may
+// list its limited joints, jnt_limited[NJNT] (the hiprtc-built ones of such models do; a topology without the array has no constraint stage).  Row r of the
+// static row list is the r-th limited joint; range, margin, solref and solimp are run-time data (LeTapeLim).  One-wavefront form, plain build only.
+template <class T, class = void> struct LeLim { static constexpr bool on(int) { return false; } };
+template <class T> struct LeLim<T, decltype((void)T::jnt_limited)> { static constexpr bool on(int j) { return T::jnt_limited[j] != 0; } };
+template <class T> struct LeLimQ {
+	static constexpr int n() { int k = 0; for (int j = 0; j < T::NJNT; j++) if (LeLim<T>::on(j)) k++; return k; }
+	static constexpr int jnt(int r) { int k = 0; for (int j = 0; j < T::NJNT; j++) if (LeLim<T>::on(j) && k++ == r) return j; return 0; }  // (= its dof: one-dof joints in dof order)
+	// entry a of M^-1 e_j is not a known zero: dofs a and j share an ancestor (or one is the other's)
+	static constexpr bool coupled(int a, int j) { for (int d = 0; d < T::NV; d++) if (Tq<T>::anc(d, a) && Tq<T>::anc(d, j)) return true; return false; }
+	static constexpr int ar(int i, int k) { const int a = i < k ? i : k, b = i < k ? k : i; return a * n() - a * (a - 1) / 2 + (b - a); }  // AR_ik = AR_ki in the packed triangle
+	static constexpr int ws(int r) { return n() * (n() + 1) / 2 + r; }  // row r's qacc_warmstart behind the triangle
+};
 
 template <class T, int LP> struct Lds {
 	using Q = Tq<T>;
@@ -248,7 +279,7 @@ template <class T, int LP> struct Lds {
 	}
 	static constexpr int cin_slot(int b)  // first of the body's five cinert slots, -1: the body's cinert stays in registers
 	{
-		int at = slot(T::NBODY);
+		int at = slot(T::NBODY) + le_lim_slots(LeLimQ<T>::n());
 		for (int a = T::NBODY - 1; a >= 1; a--) {
 			if (!needed(a)) continue;
 			if (at + 5 > LP) return -1;
@@ -258,7 +289,7 @@ template <class T, int LP> struct Lds {
 		return -1;
 	}
 	static constexpr int nmov() { return (slot(T::NBODY) - T::NV) / 3; }  // the needed bodies
-	static constexpr int nslots() { return le_solo_slots(T::NV, nmov(), LP); }
+	static constexpr int nslots() { return le_solo_slots(T::NV, nmov(), LP, LeLimQ<T>::n()); }
 	static constexpr int bytes() { return nslots() * LE_SLOT_BYTES; }
 };
 
@@ -435,7 +466,11 @@ DEVI void lane_env_body(const KernelParams MJB_AS4 *__restrict__ P, const int ns
 	using XS6 = XfSlots<T>;
 	constexpr int LPE = PIPE ? (1 << 20) : (DUO ? LP - DuoSlots<NV>::n : LP);
 	using LD = Lds<T, LPE>;
-	static_assert(LD::slot(T::NBODY) <= LPE, "lane = env kernel: state and forces of the topology need more LDS than this instantiation's budget");
+	using LM = LeLimQ<T>;
+	constexpr int NL = LM::n();  // joint-limit rows (0: the model has no constraint stage, and none of its code)
+	static_assert(NL == 0 || (ROLE == LE_SOLO && !PE && !HW && !XF), "lane = env kernel: joint limits run the plain build of the solo form");
+	static_assert(LD::slot(T::NBODY) + le_lim_slots(NL) <= LPE, "lane = env kernel: state and forces of the topology need more LDS than this instantiation's budget");
+	[[maybe_unused]] constexpr int LIM0 = LD::slot(T::NBODY);  // (NL > 0) first pair slot of the packed AR | qacc_warmstart doubles
 	// (trio) body b's half-angle (sin, cos) comes from C: a hinge whose two predecessors in the sweep are needed bodies too (C publishes them two barriers ahead)
 	constexpr auto SCUSE = [](int b) {
 		if (b < 3 || b >= T::NBODY || T::body_jnt[b] < 0) return false;
@@ -457,6 +492,17 @@ DEVI void lane_env_body(const KernelParams MJB_AS4 *__restrict__ P, const int ns
 	const bool live = env_raw < env_hi;
 	const int env = live ? env_raw : env_hi - 1;
 	const size_t ev = (size_t)env;
+	// (NL > 0) double k of this lane's constraint-stage storage: the packed AR triangle (LM::ar), then qacc_warmstart of the limited dofs (LM::ws)
+	[[maybe_unused]] auto lim_ld = [&](auto K) -> double {
+		constexpr int k = K;
+		if constexpr (k & 1) return lp[64 * (LIM0 + k / 2)].b;
+		else return lp[64 * (LIM0 + k / 2)].a;
+	};
+	[[maybe_unused]] auto lim_st = [&](auto K, const double v) {
+		constexpr int k = K;
+		if constexpr (k & 1) lp[64 * (LIM0 + k / 2)].b = v;
+		else lp[64 * (LIM0 + k / 2)].a = v;
+	};
 
 	// ---- the env's state: (qpos, qvel) in LDS, the OU noise state and the activation states (mjData.act, NA > 0) in registers
 	double cn[NU > 0 ? NU : 1];
@@ -476,6 +522,7 @@ DEVI void lane_env_body(const KernelParams MJB_AS4 *__restrict__ P, const int ns
 		}
 		sfor<NU>([&](auto I) { cn[I] = DV ? s.ctrlnoise[ev * NU + I] : 0.0; });
 		if constexpr (NA > 0) sfor<NA>([&](auto I) { act[I] = s.act[ev * NA + I]; });
+		if constexpr (NL > 0) sfor<NL>([&](auto R) { lim_st(IC<LM::ws(R)>{}, s.qacc_warmstart[ev * NV + LM::jnt(R)]); });  // (lives with the lane across the fused steps)
 		time = s.time[ev];
 		if constexpr (DUO) {  // the load is "Euler of step -1": P's verdicts on the loaded state go to V by mail
 			if constexpr (DP) lp[64 * MAIL] = Pair{ (double)((badp_next ? 2 : 0) | (badv_next ? 1 : 0)), 0.0 };
@@ -560,6 +607,7 @@ DEVI void lane_env_body(const KernelParams MJB_AS4 *__restrict__ P, const int ns
 					});
 				}
 				if constexpr (NA > 0) sfor<NA>([&](auto I) { act[I] = bad ? 0.0 : act[I]; });
+				if constexpr (NL > 0) sfor<NL>([&](auto R) { const double w = pinv(lim_ld(IC<LM::ws(R)>{})); lim_st(IC<LM::ws(R)>{}, bad ? 0.0 : w); });  // (mj_resetData: qacc_warmstart = 0)
 				time = bad ? 0.0 : time;
 				wasreset = wasreset || bad;
 				rs = bad;
@@ -568,6 +616,9 @@ DEVI void lane_env_body(const KernelParams MJB_AS4 *__restrict__ P, const int ns
 		}
 
 		double qacc[NV], qaccd[NV];  // M^-1 f, and the acceleration Euler advances with: (M + h B)^-1 f under implicit joint damping
+		// (NL > 0) what the constraint stage leaves: qfrc_constraint of the limited dofs (J' f: the row's signed force), the env's active rows, its PGS sweeps
+		[[maybe_unused]] double qfc[NL > 0 ? NL : 1];
+		[[maybe_unused]] int c_nefc = 0, c_iter = 0;
 		// (NA > 0) the activation states mj_Euler commits: act + h act_dot, clamped to actrange.  Formed where the forces are assembled, on either trip of the
 		// loop below from the trip's own act -- a lane mj_checkAcc reset forms it again from zero --, and committed once, behind the loop
 		[[maybe_unused]] double actn[NA > 0 ? NA : 1];
@@ -1951,6 +2002,210 @@ DEVI void lane_env_body(const KernelParams MJB_AS4 *__restrict__ P, const int ns
 			else
 			sfor<NV>([&](auto I) { qacc[I] = x[I]; qaccd[I] = damp_on ? y[I] : x[I]; });
 
+			// ================= the constraint stage of a model with joint limits: mj_makeConstraint, mj_projectConstraint, mj_referenceConstraint, mj_solPGS =================
+			// One env per lane, the oracle's mjo_make_constraint (hinge / slide limits) .. mjo_fwd_constraint (PGS) in its operation order.  The row list is static --
+			// row r = the r-th limited joint, J = +- e_j --; which rows an env has is per-lane data: selects.  Which rows ANY lane of the wavefront has is a
+			// ballot: rows nobody has are skipped by scalar branches, a wavefront without rows pays the NL comparisons and nothing else.  Row constants
+			// (LeTapeLim) are wave-uniform, and so are the branches on them.  qacc (= qacc_smooth so far) and qaccd come out constrained: the acceleration-stage
+			// sensors, mj_checkAcc and mj_Euler below see them.  On the retry of the attempt loop the stage runs again on the reset state.
+			if constexpr (NL > 0) {
+				const LeTapeLimHdr MJB_AS4 *const tlh = reinterpret_cast<const LeTapeLimHdr MJB_AS4 *>(ta + NU);
+				const LeTapeLim MJB_AS4 *const tl = reinterpret_cast<const LeTapeLim MJB_AS4 *>(tlh + 1);
+				const bool lim_on = !(m.disableflags & (MJB_DSBL_CONSTRAINT | MJB_DSBL_LIMIT));
+				bool ract[NL], rwav[NL], anyw = false, has = false;  // the lane has the row | some lane of the wavefront has it
+				double rsg[NL], rpos[NL];                            // the side: J = rsg e_j (lower +1, upper -1) | efc_pos
+				int nrow = 0;
+				sfor<NL>([&](auto R) {
+					constexpr int r = R, j = LM::jnt(r);
+					const double q = lp[64 * j].a, mg = tl[r].margin;
+					const double dlo = q - tl[r].range[0], dhi = tl[r].range[1] - q;
+					const bool up = dhi < mg, a = lim_on && ((dlo < mg) || up);  // (range > 2 margin: at most one side)
+					ract[r] = a;
+					rsg[r] = up ? -1.0 : 1.0;
+					rpos[r] = up ? dhi : dlo;
+					rwav[r] = __builtin_amdgcn_ballot_w64(a) != 0;
+					anyw = anyw || rwav[r];
+					has = has || a;
+					nrow += a ? 1 : 0;
+					qfc[r] = 0;
+				});
+				c_nefc = nrow;
+				c_iter = 0;
+				if (anyw) {  // (wave-uniform)
+					double rD[NL], raref[NL], rb[NL], rf[NL], rinv[NL];
+					// ---- row parameters (mj_makeImpedance: row_params_x / impedance), aref (mj_referenceConstraint), b = J qacc_smooth - aref
+					[[maybe_unused]] double rR[NL];
+					sfor<NL>([&](auto R) {
+						constexpr int r = R, j = LM::jnt(r);
+						rD[r] = 1, raref[r] = 0, rb[r] = 0, rf[r] = 0, rinv[r] = 1, rR[r] = 1;
+						if (rwav[r]) {
+							const LeTapeLim MJB_AS4 &L = tl[r];
+							const double d0 = L.solimp[0], d1 = L.solimp[1], wd = L.solimp[2], mid = L.solimp[3], pw = L.solimp[4], mg = L.margin;
+							const double pm = rpos[r] - mg;
+							double imp;
+							if (d0 == d1 || wd <= MJB_MINVAL) imp = 0.5 * (d0 + d1);
+							else {
+								const double xi = fabs(pm / wd);
+								double yv;
+								if (pw == 1) yv = xi;
+								else {
+									const bool lowh = xi <= mid;
+									const double xx = lowh ? xi : 1 - xi;
+									double px;
+									if (pw == 2) px = xx * xx;
+									else px = pow(xx, pw);
+									const double ya = L.powa * px, yb = 1 - L.powb * px;
+									yv = lowh ? ya : yb;
+								}
+								const double mixed = d0 + yv * (d1 - d0);
+								imp = (xi >= 1) ? d1 : ((xi <= 0) ? d0 : mixed);
+							}
+							const double Rr = fmax(MJB_MINVAL, (1 - imp) * L.invweight0 / imp);
+							const double Ra = ract[r] ? Rr : 1.0;  // (a lane without the row: harmless numbers, its force stays zero)
+							const Pair sj = lp[64 * j];
+							const double vel = rsg[r] * sj.b;
+							const double ar = -L.B * vel - L.K * imp * pm;
+							rR[r] = Ra;
+							rD[r] = 1.0 / Ra;
+							raref[r] = ract[r] ? ar : 0.0;
+							rb[r] = ract[r] ? rsg[r] * qacc[j] - ar : 0.0;
+						}
+					});
+					// ---- AR = J M^-1 J' + diag(R): the columns of M^-1 of the wave-active limited dofs from the L'DL factor of M (unit right-hand side, the
+					// known zeros skipped), symmetrised as the oracle does, signed and packed into LDS.  Column r leaves its entries for the rows behind it raw;
+					// the rows behind symmetrise them with their own where both rows are wave-active
+					sfor<NL>([&](auto R) {
+						constexpr int r = R, j = LM::jnt(r);
+						if (rwav[r]) {
+							double c[NV];
+							sfor<NV>([&](auto I) { c[I] = (int)I == j ? 1.0 : 0.0; });
+							sfor<NV>([&](auto Ii) {
+								constexpr int i = NV - 1 - Ii;
+								if constexpr (Q::anc(i, j))
+									sfor<NV>([&](auto A) {
+										constexpr int a = A;
+										if constexpr (a < i && Q::anc(a, i)) c[a] -= qM[i][a] * c[i];
+									});
+							});
+							sfor<NV>([&](auto I) { if constexpr (Q::anc(I, j)) c[I] *= dinv[I]; });
+							sfor<NV>([&](auto I) {
+								constexpr int i = I;
+								sfor<NV>([&](auto Ai) {
+									constexpr int a = NV - 1 - Ai;
+									if constexpr (a < i && Q::anc(a, i) && LM::coupled(a, j)) c[i] -= qM[i][a] * c[a];
+								});
+							});
+							sfor<NL>([&](auto K) {
+								constexpr int k = K, kj = LM::jnt(k);
+								if constexpr (k == r) {
+									const double aii = c[j] + rR[r];
+									lim_st(IC<LM::ar(r, r)>{}, aii);
+									rinv[r] = 1.0 / aii;
+								} else if constexpr (!LM::coupled(kj, j)) {
+									if constexpr (k > r) lim_st(IC<LM::ar(r, k)>{}, 0.0);  // (two trees: a known zero on both sides)
+								} else if constexpr (k > r) {
+									lim_st(IC<LM::ar(r, k)>{}, c[kj]);
+								} else {
+									if (rwav[k]) {
+										const double g = lim_ld(IC<LM::ar(k, r)>{});
+										lim_st(IC<LM::ar(k, r)>{}, (rsg[r] * rsg[k]) * (0.5 * (c[kj] + g)));
+									}
+								}
+							});
+						}
+					});
+					// (read unconditionally, zero by select where row k is nobody's: a row's reads leave together instead of one behind each scalar branch -- and a
+					//  stale entry of an inactive row never meets a force, not even a zero one)
+					auto AR = [&](auto I, auto K) -> double { const double a = lim_ld(IC<LM::ar(I, K)>{}); return rwav[K] ? a : 0.0; };
+					// ---- warmstart: the forces qacc_warmstart implies, kept if their dual cost 0.5 f' AR f + f' b is not positive
+					if (tlh->nowarm == 0) {
+						sfor<NL>([&](auto R) {
+							constexpr int r = R;
+							if (rwav[r]) {
+								const double w = lim_ld(IC<LM::ws(r)>{});
+								const double jar = rsg[r] * w - raref[r];
+								const double fw = jar < 0 ? -rD[r] * jar : 0.0;
+								rf[r] = ract[r] ? fw : 0.0;
+							}
+						});
+						double cost = 0;
+						sfor<NL>([&](auto I) {
+							constexpr int i = I;
+							if (rwav[i]) {
+								double sm = 0;
+								sfor<NL>([&](auto K) { sm += AR(I, K) * rf[K]; });
+								cost += 0.5 * rf[i] * sm + rf[i] * rb[i];
+							}
+						});
+						const bool drop = cost > 0;
+						sfor<NL>([&](auto R) { rf[R] = drop ? 0.0 : rf[R]; });
+					}
+					// ---- mj_solPGS: sweeps over the rows until the lane's improvement falls under the tolerance or its sweeps run out; a lane that is done keeps
+					// its forces, the loop runs while a lane is not
+					const double scale = tlh->scale, tol = tlh->tolerance;
+					const int itmax = (int)tlh->iterations;
+					bool done = !has || itmax <= 0;
+					int iter = 0;
+					while (__builtin_amdgcn_ballot_w64(!done)) {
+						double improvement = 0;
+						sfor<NL>([&](auto I) {
+							constexpr int i = I;
+							// (a row is swept while a lane that has it is still sweeping: the loop's long tail is a few lanes' rows, not the wavefront's)
+							if (__builtin_amdgcn_ballot_w64(ract[i] && !done)) {
+								double arow[NL];
+								sfor<NL>([&](auto K) { arow[K] = lim_ld(IC<LM::ar(I, K)>{}); });
+								touch_vn<NL>(arow);  // (the row's reads, issued together)
+								double res = rb[i];
+								sfor<NL>([&](auto K) { res += (rwav[K] ? arow[K] : 0.0) * rf[K]; });
+								const double aii = arow[i];
+								const double old = rf[i];
+								const double f1 = old - res * rinv[i];
+								const double f2 = f1 < 0 ? 0.0 : f1;
+								const double delta = f2 - old;
+								const double change = 0.5 * delta * delta * aii + delta * res;
+								const bool revert = change > 1e-10;
+								const bool upd = ract[i] && !done;
+								rf[i] = (upd && !revert) ? f2 : old;
+								improvement -= (upd && !revert) ? change : 0.0;
+							}
+						});
+						improvement *= scale;
+						iter += done ? 0 : 1;
+						done = done || improvement < tol || iter >= itmax;
+					}
+					c_iter = iter;
+					// ---- qfrc_constraint = J' f;  qacc = qacc_smooth + M^-1 qfrc_constraint;  Euler's acceleration + (M + h B)^-1 qfrc_constraint
+					double x2[NV], y2[NV];
+					sfor<NV>([&](auto I) { x2[I] = 0; y2[I] = 0; });
+					sfor<NL>([&](auto R) {
+						constexpr int r = R, j = LM::jnt(r);
+						qfc[r] = rsg[r] * rf[r];
+						x2[j] = qfc[r];
+						y2[j] = qfc[r];
+					});
+					sfor<NV>([&](auto Ii) {
+						constexpr int i = NV - 1 - Ii;
+						sfor<NV>([&](auto A) {
+							constexpr int a = A;
+							if constexpr (a < i && Q::anc(a, i)) { x2[a] -= qM[i][a] * x2[i]; y2[a] -= qH[i][a] * y2[i]; }
+						});
+					});
+					sfor<NV>([&](auto I) { x2[I] *= dinv[I]; y2[I] *= hinv[I]; });
+					sfor<NV>([&](auto I) {
+						constexpr int i = I;
+						sfor<NV>([&](auto Ai) {
+							constexpr int a = NV - 1 - Ai;
+							if constexpr (a < i && Q::anc(a, i)) { x2[i] -= qM[i][a] * x2[a]; y2[i] -= qH[i][a] * y2[a]; }
+						});
+					});
+					sfor<NV>([&](auto I) {
+						const double qd = qaccd[I] + y2[I];
+						qacc[I] += x2[I];
+						qaccd[I] = damp_on ? qd : qacc[I];
+					});
+				}
+			}
+
 			if constexpr (XW) {
 				// ---- (four wavefronts) mj_checkAcc on X: the verdict goes to the other three by mail -- bit 3 = some lane of the wavefront is bad, bit 2 = this
 				// lane is -- while C integrates on the assumption that nobody is.  The second trip checks nothing and mails 0.
@@ -2158,6 +2413,7 @@ DEVI void lane_env_body(const KernelParams MJB_AS4 *__restrict__ P, const int ns
 			});
 			sfor<NU>([&](auto I) { cn[I] = bada ? 0.0 : cn[I]; });
 			if constexpr (NA > 0) sfor<NA>([&](auto I) { act[I] = bada ? 0.0 : act[I]; });
+			if constexpr (NL > 0) sfor<NL>([&](auto R) { const double w = pinv(lim_ld(IC<LM::ws(R)>{})); lim_st(IC<LM::ws(R)>{}, bada ? 0.0 : w); });  // (the retry's warmstart is mj_resetData's)
 			time = bada ? 0.0 : time;
 			wasreset = wasreset || bada;
 			if constexpr (HW) hw_bad = bada;
@@ -2192,6 +2448,20 @@ DEVI void lane_env_body(const KernelParams MJB_AS4 *__restrict__ P, const int ns
 				if constexpr (EPOS) s.energy[2 * ev] = en_pe;
 				s.energy[2 * ev + 1] = en_ke;
 			}
+			if constexpr (NL > 0) {  // what the launch leaves of its last constraint stage (efc_* are not written): qfrc_constraint | nefc | solver_iter
+				double *const co = Pq->le_con;
+				if (co) {
+					double *const o = co + ev * (size_t)(NV + 2);
+					sfor<NV>([&](auto I) {
+						constexpr int j = I;
+						double v = 0;
+						if constexpr (LeLim<T>::on(j)) sfor<NL>([&](auto R) { if constexpr (LM::jnt(R) == j) v = qfc[R]; });
+						o[j] = v;
+					});
+					o[NV] = (double)c_nefc;
+					o[NV + 1] = (double)c_iter;
+				}
+			}
 		}
 		if constexpr (ROLE == LE_QUAD_C) {  // (four wavefronts: C has integrated inside the loop, ahead of X's verdict)
 			time += dt;
@@ -2218,6 +2488,7 @@ DEVI void lane_env_body(const KernelParams MJB_AS4 *__restrict__ P, const int ns
 			badv_next |= bad_val(s2.b);
 		});
 		if constexpr (NA > 0) sfor<NA>([&](auto I) { act[I] = actn[I]; });
+		if constexpr (NL > 0) sfor<NL>([&](auto R) { lim_st(IC<LM::ws(R)>{}, qacc[LM::jnt(R)]); });  // mj_advance: qacc_warmstart = qacc
 		time += dt;
 		if constexpr (DUO && DP) {
 			lp[64 * MAIL] = Pair{ (double)((badp_next ? 2 : 0) | (badv_next ? 1 : 0)), 0.0 };

@@ -361,7 +361,11 @@ class Batch:
         (set_env_gravity, set_env_body_mass, set_env_dof_params, set_env_joint_stiffness, set_env_actuator_params, ...), which the kernel then reads
         per env; such a batch runs the generic kernels in every other mode: the lane = env form of the unconstrained fused step (mjb_set_lane_env).
         Models with actuator activation states (integrator / filter; <intvelocity>, <cylinder>) are eligible too: the kernel carries `act` between
-        get("act") / set("act") and the generic kernels, in its one-wavefront form; not together with a device hwsim stage."""
+        get("act") / set("act") and the generic kernels, in its one-wavefront form; not together with a device hwsim stage.
+        A hinge / slide tree whose only constraint rows are joint limits under PGS is eligible too (no contacts, equalities, tendons or frictionloss): in
+        modes 1 and 2 its launches run the kernel's one-wavefront form with the constraint stage (joint-limit rows, PGS with warmstart) inside, and
+        get("qfrc_constraint") / get("nefc") / get("solver_iter") read the last step's values afterwards; the automatic mode keeps the generic kernels for
+        such a model, and so does a batch with per-env overrides, a hwsim stage or a written xfrc_applied."""
         _check(self.lib.mjb_set_lane_env(self.ptr, int(mode)), "mjb_set_lane_env")
 
     def set_lane_env_hwsim(self, on=True):

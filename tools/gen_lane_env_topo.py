@@ -33,10 +33,36 @@ EXTRA_SENSORS = (FRAME_SENSORS - {23, 24}) | SITE_SENSORS
 SUPPORTED_SENSORS = SMOOTH_SENSORS | EXTRA_SENSORS
 
 
+def limit_rows(m):
+    """None if every constraint row the model can ever have is a joint-limit row the lane = env kernel sweeps with PGS (le_limit_rows, csrc/mjb_lane_env.hip),
+    else the reason."""
+    if int(m["solver"]) != 0:
+        return "constraint rows under a solver other than PGS"
+    if any(float(v) > 0 for v in m["dof_frictionloss"][:m["nv"]]):
+        return "constraint rows: dry friction"
+    nl = 0
+    for j in range(m["njnt"]):
+        if m["jnt_limited"][j]:
+            r = m["jnt_range"][j]
+            if not (float(r[1]) - float(r[0]) > 2 * float(m["jnt_margin"][j])):
+                return "constraint rows: a range no wider than twice its margin"
+            nl += 1
+    if nl == 0 or m["nefcmax"] != nl:
+        return "constraint rows: other than one per limited joint"
+    return None
+
+
+def limited_joints(m):
+    """The joint-limit rows of an eligible model with constraint rows (mjb_lane_env_limits): 0 / 1 per joint."""
+    return [int(m["nefcmax"] > 0 and m["jnt_limited"][j] != 0) for j in range(m["njnt"])]
+
+
 def eligible(m):
     """None if the model fits the lane = env kernel, else the reason."""
-    if m["nefcmax"] > 0 or m["nconmax"] > 0:
+    if m["nconmax"] > 0:
         return "constraint rows"
+    if m["nefcmax"] > 0 and limit_rows(m):
+        return limit_rows(m)
     if m["integrator"] != 0:
         return "integrator"
     if m["nmocap"] or m["ntendon"] or m["neq"]:
@@ -75,6 +101,8 @@ def emit(name, m):
     why = eligible(m)
     if why:
         raise SystemExit("%s does not fit the lane = env kernel: %s" % (name, why))
+    if m["nefcmax"] > 0:
+        raise SystemExit("%s has joint limits: mjb_lane_env_match takes no such model for a compiled-in topology" % name)
     if "body_gravcomp" in m and any(m["body_gravcomp"][1:] != 0):  # (a hand-built dict from before the field has none)
         raise SystemExit("%s has gravity compensation: mjb_lane_env_match takes no such model for a compiled-in topology" % name)
     if any(int(t) in EXTRA_SENSORS for t in m["sensor_type"][:m["nsensor"]]):
@@ -89,7 +117,10 @@ def rt_struct(m):
     if why:
         raise SystemExit("the model does not fit the lane = env kernel: %s" % why)
     gc = [int(b > 0 and m["body_gravcomp"][b] != 0) for b in range(m["nbody"])]
-    return struct_text("rt", m, gc).replace('\tstatic constexpr const char *name = "rt";\n', "")
+    text = struct_text("rt", m, gc).replace('\tstatic constexpr const char *name = "rt";\n', "")
+    if m["nefcmax"] > 0:  # (the rows of the constraint stage, LeLim: a model without them has no such line)
+        text = text[:text.rindex("};\n")] + arr("jnt_limited", limited_joints(m)) + "};\n"
+    return text
 
 
 def struct_text(name, m, body_gc):
