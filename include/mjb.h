@@ -635,6 +635,10 @@ int mjb_hwsim_set_period(mjb_batch *b, double control_period);
  * buckets the reference's GUI profiler plots, viewer.cpp:335-346). */
 int mjb_debug_profile(mjb_batch *b, unsigned long long *out64, int clear);
 int mjb_debug_profile_window(mjb_batch *b, int first_id);
+/* Four 64-bit FNV-1a words over the members of a compiled model: [0] the copied description, [1] every table and scalar mjb_compile derives,
+ * [2] the three frame layouts, the field sizes and the frame residency, [3] the lane = env / split-step classification and tape.  Two models with
+ * equal words were compiled alike; which word differs says where to look.  Needs no device.  No reference counterpart. */
+int mjb_debug_model_digest(const mjb_model *m, unsigned long long out[4]);
 
 /* Timing helper for bench.py: run `nlaunch` launches of mjb_step(b, nsteps) bracketed by HIP
  * events recorded on the batch's stream; returns the mean per-launch duration in milliseconds

@@ -1,11 +1,12 @@
-// mjb_api.hip — host side of the C-ABI declared in include/mjb.h (libmjb.so).
-// Owns model validation, the device model blob, HBM state arrays, launches and host<->device copies.
+// mjb_api.hip — the batch side of the C-ABI declared in include/mjb.h (libmjb.so).
+// Owns batches: the device model blob, HBM state arrays, the launch policy and the launches, host<->device copies, the per-env parameter
+// setters, the device hwsim stage and the sensor messages, with the few small kernels they need.  The model itself -- mjb_compile, the frame
+// layouts, the getters that need no batch, mjb_derive_mass_params -- is mjb_model.hip's (struct mjb_model, fail(): mjb_model.h).
 // No CPU compute path exists here: every compute entry point needs a HIP device.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <cmath>
-#include <cstdarg>
 #include <cstdio>
 #include <cstring>
 #include <new>
@@ -13,116 +14,13 @@
 #include <vector>
 
 #include "mjb_dev.h"
-
-namespace {
-
-thread_local std::string g_err;
-
-int fail(int code, const char *fmt, ...)
-{
-	char buf[512];
-	va_list ap;
-	va_start(ap, fmt);
-	vsnprintf(buf, sizeof buf, fmt, ap);
-	va_end(ap);
-	g_err = buf;
-	return code;
-}
+#include "mjb_model.h"
 
 #define HIP_TRY(expr)                                                                                   \
 	do {                                                                                                \
 		hipError_t _e = (expr);                                                                         \
 		if (_e != hipSuccess) return fail(MJB_ENODEVICE, "%s: %s", #expr, hipGetErrorString(_e));     \
 	} while (0)
-
-struct FieldInfo {
-	const char *name;
-	const char *rows;
-	const char *cols;  // literal or size name (DD2)
-	int kind;          // 0 state, 1 derived double, 2 derived double (2 size names), 3 int
-};
-
-const FieldInfo kFields[] = {
-#define MJB_DS(name, rows, cols) { #name, #rows, #cols, 0 },
-#define MJB_DD(name, rows, cols) { #name, #rows, #cols, 1 },
-#define MJB_DD2(name, rows, cols) { #name, #rows, #cols, 2 },
-#define MJB_DI(name, rows, cols) { #name, #rows, #cols, 3 },
-#include "../../include/mjb_data_fields.def"
-#undef MJB_DS
-#undef MJB_DD
-#undef MJB_DD2
-#undef MJB_DI
-};
-
-// the FrameLayout member that holds data field i's offset (MJB_F_*)
-int FrameLayout::*const kFieldSlot[] = {
-#define MJB_DS(name, rows, cols) &FrameLayout::name,
-#define MJB_DD(name, rows, cols) &FrameLayout::name,
-#define MJB_DD2(name, rows, cols) &FrameLayout::name,
-#define MJB_DI(name, rows, cols) &FrameLayout::name,
-#include "../../include/mjb_data_fields.def"
-#undef MJB_DS
-#undef MJB_DD
-#undef MJB_DD2
-#undef MJB_DI
-};
-int &field_slot(FrameLayout &L, int i) { return L.*kFieldSlot[i]; }
-int field_slot(const FrameLayout &L, int i) { return L.*kFieldSlot[i]; }
-
-int size_by_name(const mjb_model_desc &d, const char *n)
-{
-#define MJB_SIZE(name) if (!strcmp(n, #name)) return d.name;
-#define MJB_OPT_I(name)
-#define MJB_OPT_D(name, k)
-#define MJB_ARR_I(name, rows, cols)
-#define MJB_ARR_D(name, rows, cols)
-#include "../../include/mjb_model_fields.def"
-#undef MJB_SIZE
-#undef MJB_OPT_I
-#undef MJB_OPT_D
-#undef MJB_ARR_I
-#undef MJB_ARR_D
-	if (!strcmp(n, "one")) return 1;
-	return atoi(n);
-}
-
-}  // namespace
-
-struct mjb_model {
-	mjb_model_desc h{};               // host copy (pointers into hint / hdbl)
-	std::vector<int> hint;            // all int arrays, concatenated
-	std::vector<double> hdbl;         // all double arrays, concatenated
-	std::vector<size_t> ioff, doff;   // offsets of each array inside hint / hdbl (declaration order)
-	std::vector<int> M_rowdof, M_coldof, dof_depth, dof_jstart, body_rec, body_rec2, dof_rec, fac_ops, fac_beg, body_dofmask, body_submask, M_dense, body_anc, dof_bodymask, M_sym, body_dofanc, dof_rec2, jnt_rec, flv_hdr, flv_rec, flv_ent;
-	std::vector<int> sens_copy, sens_slow, dof_act_adr, dof_act_id;
-	std::vector<int> pair_i;       // [ncollpair][8]  per candidate pair: g1, g2, type1, type2, condim, friction rule, collision-function override, 0
-	std::vector<double> pair_d;    // [ncollpair][24] size1[3] size2[3] margin gap rbound1 rbound2 solref[2] solimp[5] includemargin friction[3] tran pad[2]
-	std::vector<double> sub_S;     // 0/1 subtree matrix as MFMA A operands (mjb_dev.h)
-	std::vector<double> lim_d;     // [njnt + ntendon][24] limit items in pair_d's slots (mjb_dev.h)
-	std::vector<double> dof_act_mom;  // moment arm of entry t of the per-dof actuator lists (dof_act_adr / dof_act_id)
-	int act_tendon = 0;               // some actuator drives a tendon
-	std::vector<int> site_act;        // actuators with a site transmission, in actuator order (DevModel::site_act)
-	std::vector<int> gravcomp_body;   // bodies with body_gravcomp != 0, ascending (DevModel::gravcomp_body; its size is mjModel.ngravcomp)
-	std::vector<double> damp_int;  // [nv] -diag(D) of the integrator's implicit matrix M + h diag(.): dof_damping (Euler) / implicitfast's constant velocity derivative
-	std::vector<int> lim_i;        // [njnt + ntendon][4]
-	int sens_ncopy[3] = { 0, 0, 0 }, sens_nslow[3] = { 0, 0, 0 }, sens_ncopy_max = 0;
-	int eulerdamp = 0, maxdepth = 0, kin_rounds = 0, need_rnepost = 0, nfriction = 0, sub_nt = 0, dofanc_max = 0, flv_n = 0;
-	int field_size[MJB_F_COUNT]{};
-	FrameLayout L{}, Lc{};
-	// kernel variant 4 (Newton, capacity > 128 rows): a second, WIDE fused frame that holds 128 rows of efc_J and of every per-row
-	// array (two envs per CU instead of four).  A batch whose env-steps mostly exceed 64 rows runs its long launches on it: those steps
-	// take the two-rows-per-lane solver on LDS instead of the four-rows-per-lane one on the env's block in HBM (launch(), wide policy).
-	FrameLayout Lw{};
-	bool has_wide = false;
-	// the row-slot solver (kernel variants 10 - 13): Newton / CG models beyond the register-row kernels -- more than 256 rows of capacity, or
-	// a full frame larger than one CU's LDS.  Their fused frame holds every row (no efc_Jg, no wide frame); a launch whose frame exceeds
-	// the LDS budget runs it from the env's slot of DevState::frame_ws (variants 12 / 13)
-	bool slot = false;
-	bool hbm_full = false, hbm_fused = false;  // the full / fused frame lives in HBM
-	int le_topo = -1;  // compiled-in topology of the lane = env kernel the model matches (mjb_lane_env.hip); -1: none; -2: eligible, built by hiprtc on first use
-	std::vector<double> le_tape;  // its constant tape (mjb_dev.h), empty without a topology
-	int sm_topo = -1;  // compiled-in topology of the split step's smooth kernel (mjb_smooth.hip) when the model's constraint half fits mjb_cstep_kernel too; -1: none
-};
 
 struct mjb_batch {
 	const mjb_model *model = nullptr;
@@ -216,469 +114,6 @@ struct mjb_batch {
 
 namespace {
 
-// Frame layout.  compact == false: every field owns its storage (what mjb_forward / mjb_step1 dump and mjb_get
-// reads).  compact == true (fused mjb_step only): xfrc_applied is absent and fields whose lifetimes never
-// overlap inside one step share storage --
-//   region A: kinloc (kinematics)  |  crb + crbbuf (crb)  |  cacc + cfrc_body (rne)  |  eulerx (euler)
-//   region B: ximat (kinematics -> comPos)  |  cvel + cdof_dot (comVel -> rne / vel sensors)
-// which brings the Franka frame from 12.6 KB to 9.3 KB, i.e. from 12 to 16 resident envs per CU.
-//
-// compact AND constrained (nefcmax > 0) -- "lean": the fused step builds the constraint rows AFTER the velocity stage (nothing
-// between collision and the solver reads them; the kernel defers make_constraint whenever it runs on this layout), so
-//   * efc_J overlays everything that is dead by then (region U): regions A and B, cinert, geom_xpos / geom_xmat, xanchor / xaxis,
-//     site_xquat and -- without equalities -- xmat / xquat   [only when no sensor needs rne_post, which re-reads them];
-//   * row bookkeeping shrinks to what the solver reads: efc_pos / efc_margin / efc_KBIP / efc_vel are gone (efc_aref holds
-//     K imp (pos - margin) and efc_b the damping gain until reference_constraint folds them into aref), efc_D is gone for PGS
-//     (1 / R on the fly) and efc_R for the primal solvers;
-//   * contact_solref / contact_solimp are gone (make_constraint reads the pair record the contact came from);
-//   * the PGS triangle scratch sits on the dead contact arrays, the box - box clipping scratch at the start of U.
-// jrows_req > 0: rows of efc_J the fused frame of kernel variant 4 holds (choose_layout picks it); 0 = the default
-void compute_layout(mjb_model *M, FrameLayout &L, bool compact, int jrows_req = 0)
-{
-	const mjb_model_desc &d = M->h;
-	int off = 0, ioff = 0, nstate = 0;
-	int idx = 0;
-	auto dim = [&](const FieldInfo &fi) {
-		int r = size_by_name(d, fi.rows);
-		int c = size_by_name(d, fi.cols);
-		return r * c;
-	};
-	bool body_sensor = false;
-	for (int i = 0; i < d.nsensor; i++)
-		if (d.sensor_objtype[i] == MJB_OBJ_BODY || d.sensor_reftype[i] == MJB_OBJ_BODY) body_sensor = true;
-	const bool alias_b = compact && !body_sensor;
-	bool need_post = false;
-	for (int i = 0; i < d.nsensor; i++) {
-		const int t = d.sensor_type[i];
-		if (t == MJB_SENS_TOUCH || t == MJB_SENS_ACCELEROMETER || t == MJB_SENS_FORCE || t == MJB_SENS_TORQUE ||
-		    t == MJB_SENS_FRAMELINACC || t == MJB_SENS_FRAMEANGACC)
-			need_post = true;
-	}
-	M->need_rnepost = need_post ? 1 : 0;
-	const bool lean = compact && d.nefcmax > 0;
-	const bool u_ok = lean && !need_post;
-	const bool primal = d.solver == MJB_SOL_NEWTON || d.solver == MJB_SOL_CG;
-	const bool ell_con = d.cone == MJB_CONE_ELLIPTIC && d.nconmax > 0;
-	// kernel variant 4 (Newton, more than 128 rows of capacity), fused frame: the first 64 rows of efc_J only; an env-step with
-	// more rows keeps J in the env's block of DevState::efc_Jg (config 5 never has: what lets two of its envs share a CU's LDS)
-	int jrows = d.nefcmax;
-	if (compact && d.solver == MJB_SOL_NEWTON && d.nefcmax > 128 && !M->slot) {
-		jrows = jrows_req > 0 ? std::max(4, std::min(128, jrows_req)) : 64;
-		if (const char *v = getenv("MJB_DEBUG_JROWS")) jrows = std::max(4, std::min(64, atoi(v)));  // test knob: force the HBM path
-	}
-	L.jrows = jrows;
-	std::vector<int> u_members;  // field ids overlaid by efc_J, in placement order
-	// "X layout" -- lean frames of the Newton kernels (nv <= 32: M lives in registers inside the solver).  One region X is shared by
-	// three generations of data:
-	//   X = [ D | R ],  D = cdof | qM | qLD | qLDiagInv | contact dist / pos / frame / includemargin   (dead once the solver has
-	//                       gathered its rows of M: nothing after make_constraint / fwd_acceleration reads them)
-	//                   R = position / velocity-stage scratch (regions A, B, the U members)           (dead at make_constraint)
-	//   make_constraint .. solver:   efc_J | efc_D | efc_aref | efc_b | efc_force at the END of X
-	//   fwd_acceleration, Euler:     the dense-triangle scratch (tri | solvescr | eulerx) right below efc_J, inside R
-	//   solver only:                 nwt_H | nwt_vec | nwt_row | nwt_hc from the START of X (over D and the head of R)
-	// (a jointlimitfrc / tendonlimitfrc sensor reads efc_force of its row after the solve: such a model keeps every row array whole in the frame)
-	bool row_sensor = false;
-	for (int i = 0; i < d.nsensor; i++) row_sensor = row_sensor || d.sensor_type[i] == MJB_SENS_JOINTLIMITFRC || d.sensor_type[i] == MJB_SENS_TENDONLIMITFRC;
-	const bool xl = u_ok && !row_sensor && d.solver == MJB_SOL_NEWTON && d.nv <= 32;
-	// ... and, when the frame holds only `jrows` rows of efc_J (kernel variant 4), every other per-row array is capped at the same
-	// count: an env-step with more rows keeps all of its row data in the env's block of DevState::efc_Jg (mjb_dev.h, RowBlock).
-	// Config 5: 53.0 -> 40.9 KB = four envs per CU, one per SIMD.
-	const int rcap = (xl && jrows < d.nefcmax) ? jrows : d.nefcmax;
-	L.rcap = rcap;
-	L.hcrow = (rcap < d.nefcmax) ? 1 : 0;
-	std::vector<int> d_members, p2_members;
-	int fsize[MJB_F_COUNT];
-	for (const FieldInfo &fi : kFields) {
-		int n = dim(fi);
-		if (idx == MJB_F_efc_AR) n = 0;  // (the PGS kernel keeps each row of AR in its lane's registers)
-		if (idx == MJB_F_efc_frictionloss && M->nfriction == 0) n = 0;  // no dry-friction rows in this model
-		if (idx == MJB_F_efc_B && d.solver != MJB_SOL_PGS) n = 0;  // the primal solvers need no J M^-1
-		// (nv <= 16: the PGS kernel solves for its row of B in registers; the field only exists in the full layout, for mjb_get)
-		const bool no_B = idx == MJB_F_efc_B && n > 0 && compact && d.nv <= 16 && !(d.cone == MJB_CONE_ELLIPTIC && d.nconmax > 0);
-		if (!compact) M->field_size[idx] = n;
-		if ((idx == MJB_F_cfrc_int || idx == MJB_F_cfrc_ext) && !need_post) n = 0;  // computed only when a sensor needs them
-		// (with rne_post the true cacc is written between fwd_acceleration and Euler, whose rhs shares region A)
-		const bool in_a = compact && (idx == MJB_F_crb || (idx == MJB_F_cacc && !need_post) || idx == MJB_F_cfrc_body);
-		const bool in_b = alias_b && (idx == MJB_F_ximat || idx == MJB_F_cvel || idx == MJB_F_cdof_dot);
-		if (compact && idx == MJB_F_xfrc_applied) n = 0;
-		if (idx == MJB_F_efc_J && n > 0) n = jrows * d.nv;
-		if (rcap < d.nefcmax && n > 0 && (idx == MJB_F_efc_D || idx == MJB_F_efc_aref || idx == MJB_F_efc_b || idx == MJB_F_efc_force ||
-		                                  idx == MJB_F_efc_frictionloss || idx == MJB_F_efc_type || idx == MJB_F_efc_id))
-			n = n / d.nefcmax * rcap;
-		fsize[idx] = n;
-		const bool gone = lean && (idx == MJB_F_efc_pos || idx == MJB_F_efc_margin || idx == MJB_F_efc_KBIP || idx == MJB_F_efc_vel ||
-		                           (idx == MJB_F_efc_D && d.solver == MJB_SOL_PGS && !ell_con) || (idx == MJB_F_efc_R && primal) ||
-		                           idx == MJB_F_contact_solref || idx == MJB_F_contact_solimp);
-		const bool in_u = u_ok && (idx == MJB_F_efc_J || idx == MJB_F_cinert || idx == MJB_F_geom_xpos || idx == MJB_F_geom_xmat ||
-		                           idx == MJB_F_xanchor || idx == MJB_F_xaxis || idx == MJB_F_site_xquat ||
-		                           (d.neq == 0 && (idx == MJB_F_xmat || idx == MJB_F_xquat)));
-		if (gone) {
-			field_slot(L, idx) = -1;  // kernels test the offset
-			idx++;
-			continue;
-		}
-		if (xl && (idx == MJB_F_cdof || idx == MJB_F_qM || idx == MJB_F_qLD || idx == MJB_F_qLDiagInv || idx == MJB_F_contact_dist ||
-		           idx == MJB_F_contact_pos || idx == MJB_F_contact_frame || idx == MJB_F_contact_includemargin)) {
-			d_members.push_back(idx);
-			field_slot(L, idx) = -1;  // placed below
-			idx++;
-			continue;
-		}
-		if (xl && (idx == MJB_F_efc_D || idx == MJB_F_efc_aref || idx == MJB_F_efc_b || idx == MJB_F_efc_force || idx == MJB_F_efc_frictionloss)) {
-			p2_members.push_back(idx);
-			field_slot(L, idx) = -1;  // placed below
-			idx++;
-			continue;
-		}
-		if (in_u && !in_a && !in_b) {
-			if (idx != MJB_F_efc_J) u_members.push_back(idx);
-			field_slot(L, idx) = -1;  // placed below
-			idx++;
-			continue;
-		}
-		if (no_B) {
-			if (!compact) M->field_size[idx] = n;
-			field_slot(L, idx) = -1;  // kernels test L.efc_B >= 0
-			idx++;
-			continue;
-		}
-		if (fi.kind == 3) {
-			field_slot(L, idx) = ioff;
-			ioff += n;
-		} else if (in_a || in_b) {
-			field_slot(L, idx) = -1;  // placed below
-		} else {
-			field_slot(L, idx) = off;
-			off += n;
-			if (fi.kind == 0) nstate = off;
-		}
-		idx++;
-	}
-	const bool newton = d.nefcmax > 0 && (d.solver == MJB_SOL_NEWTON || d.solver == MJB_SOL_CG);  // primal solvers
-	const int off_before_nwt = off;
-	L.nwt_M = off;
-	off += (newton && d.nv > 32) ? d.nv * d.nv : 0;  // (nv <= 32: the solver keeps row `lane` of M in registers, host table M_sym)
-	L.nwt_H = off;
-	// (nv <= 32: the packed lower triangle + one dump slot, mjb_constraint.h MJB_HPACK; 16 < nv: at least chol_schur16's 16 x 17 scratch)
-	off += newton ? (d.nv <= 32 ? std::max(d.nv * (d.nv + 1) / 2 + 1, d.nv > 16 ? 272 : 0) : d.nv * d.nv) : 0;
-	L.nwt_vec = off;
-	off += newton ? 5 * d.nv : 0;  // qacc | M qacc | grad | search | (CG: M^-1 grad)
-	L.nwt_row = off;
-	off += newton ? 3 * rcap : 0;
-	L.nwt_hc = off;
-	// cone blocks: the primal solvers size them by the model's largest contact dimension (config 5: condim 4 -> 16 doubles instead
-	// of 36; at least 10, the line-search constants a contact parks there); PGS keeps its 6 x 6 blocks of AR
-	L.hcd = 6;
-	L.hcs = 36;
-	if (newton) {
-		int maxdim = 1;
-		for (int p = 0; p < d.ncollpair; p++) maxdim = std::max(maxdim, M->pair_i[(size_t)8 * p + 4]);
-		L.hcd = std::min(6, maxdim);
-		// (blocks laid out by row on a frame with more than one row per lane: the line search parks its ten constants per contact in the contact's block, and a
-		//  contact of dimension 3 owns 3 x hcd doubles -- nine at hcd = 3.  Round 5, tools/wide_dim3_check.py: the neighbour's first constant was overwritten)
-		if (L.hcrow && rcap > 64 && L.hcd < 4) L.hcd = 4;
-		L.hcs = std::max(L.hcd * L.hcd, 10);
-	}
-	// (hcrow: a contact's block sits at hcd * its first row -- rows, not contacts, bound the solver that runs on this frame)
-	off += ((newton || (d.nefcmax > 0 && d.solver == MJB_SOL_PGS)) && d.cone == MJB_CONE_ELLIPTIC) ? (L.hcrow ? L.hcd * rcap : L.hcs * d.nconmax) : 0;  // (PGS: the contacts' blocks of AR)
-	const int n_nwt = off - off_before_nwt;  // nwt_M | nwt_H | nwt_vec | nwt_row | nwt_hc
-	if (xl) off = off_before_nwt;            // (X layout: they overlay the head of X, placed below)
-	L.gravity = off;
-	off += 3;
-	// (lean frame: collision takes the mixed friction from the pair record, or from the per-env override in HBM)
-	L.gfriction = lean ? -1 : off;
-	off += (d.nconmax > 0 && !lean) ? 3 * d.ngeom : 0;
-	L.eqparam = off;
-	off += 19 * d.neq;
-	L.cwrench = off;
-	off += need_post ? 6 * d.nconmax : 0;
-	L.MhB = off;
-	off += d.nM;
-	L.qH = lean ? L.MhB : off;  // (lean frame: factorised in place -- nothing reads M + h B after its factor exists)
-	off += lean ? 0 : d.nM;
-	L.qHdi = off;
-	off += d.nv;
-	L.rk = d.integrator == MJB_INT_RK4 ? off : -1;  // (persistent across the evaluations of one step)
-	off += d.integrator == MJB_INT_RK4 ? d.nq + 4 * d.nv + d.nsensordata + 1 + 2 * d.na : 0;  // X0 | sums | warmstart | the step's sensordata | t0 | act0 | sum B act_dot
-	L.act_mom = off;  // (alive from the transmission stage to actuation, across the overlays of every layout: own storage)
-	off += (int)M->site_act.size() * d.nv;
-	// transient scratch of the constrained kernels: ntri doubles for the packed dense triangle of the L'DL factor (nv <= 16, PGS:
-	// the J M^-1 rows; 16 < nv <= 32: the M^-1 solves of fwd_acceleration / Euler, solve_tri32), 128 for the box - box narrow phase
-	const int ntri = d.nefcmax <= 0 ? 0 : ((d.nv <= 16 && d.solver == MJB_SOL_PGS) ? 128 : ((d.nv > 16 && d.nv <= 32) ? 496 : 0));
-	const int nbb = d.nconmax > 0 ? 216 : 0;  // (MJB_BBSCR of mjb_constraint.h)
-	const int n_kin = 7 * d.nbody, n_crb = 10 * d.nbody, n_buf = 6 * d.nv < 32 ? 32 : 6 * d.nv, n_c6 = 6 * d.nbody;  // (crbbuf doubles as the 32-double pivot-row scratch of the dense factor)
-	if (compact && xl) {
-		const int x0 = off;
-		for (int id : d_members) {
-			field_slot(L, id) = off;
-			off += fsize[id];
-		}
-		const int a0 = off;  // start of R
-		L.kinloc = a0;
-		L.crb = a0;
-		L.crbbuf = a0 + n_crb;
-		L.cacc = a0;
-		L.cfrc_body = a0 + n_c6;
-		L.bbscr = a0;
-		{
-			int sz = n_kin;
-			if (nbb > sz) sz = nbb;
-			if (n_crb + n_buf > sz) sz = n_crb + n_buf;
-			if (2 * n_c6 > sz) sz = 2 * n_c6;
-			if (d.nv > sz) sz = d.nv;
-			off += sz;
-		}
-		if (alias_b) {
-			const int b0 = off;
-			L.ximat = b0;
-			L.cvel = b0;
-			L.cdof_dot = b0 + n_c6;
-			int szb = 9 * d.nbody;
-			if (n_c6 + 6 * d.nv > szb) szb = n_c6 + 6 * d.nv;
-			off += szb;
-		}
-		for (int id : u_members) {
-			field_slot(L, id) = off;
-			off += fsize[id];
-		}
-		int n_p2 = fsize[MJB_F_efc_J];
-		for (int id : p2_members) n_p2 += fsize[id];
-		const int n_scr = ntri + 32 + d.nv;
-		// (the triangle scratch of fwd_acceleration / Euler: on the contact arrays at the end of D when they are large enough --
-		//  dist | pos | frame | includemargin are contiguous and dead after make_constraint, while qM / qLD next to them are still
-		//  read -- otherwise at the start of R)
-		const bool tri_in_d = 14 * d.nconmax >= n_scr;
-		int jstart = std::max(x0 + n_nwt, tri_in_d ? a0 : a0 + n_scr);  // the solver's arrays and the triangle scratch both end below efc_J, which never reaches into D (make_constraint reads cdof and the contacts while it writes J)
-		if (jstart + n_p2 > off) off = jstart + n_p2;
-		jstart = off - n_p2;                             // ... which sits at the end of X
-		L.efc_J = jstart;
-		{
-			int o = jstart + fsize[MJB_F_efc_J];
-			for (int id : p2_members) {
-				field_slot(L, id) = o;
-				o += fsize[id];
-			}
-		}
-		L.tri = tri_in_d ? L.contact_dist : jstart - n_scr;
-		L.solvescr = L.tri + ntri;
-		L.eulerx = L.solvescr + 32;
-		{
-			const int shift = x0 - off_before_nwt;
-			L.nwt_M += shift; L.nwt_H += shift; L.nwt_vec += shift; L.nwt_row += shift; L.nwt_hc += shift;
-		}
-	} else if (compact) {
-		const int a0 = off;
-		L.kinloc = a0;
-		L.crb = a0;
-		L.crbbuf = a0 + n_crb;
-		if (!need_post) L.cacc = a0;
-		L.cfrc_body = a0 + n_c6;
-		L.eulerx = a0;
-		L.tri = a0 + 32;  // (alive inside the PGS stage / the M^-1 solves: cacc / cfrc_body are dead by then; Euler's vector sits below it)
-		L.bbscr = a0;
-		L.solvescr = L.crbbuf;
-		int sz = n_kin;
-		if (ntri > 0 && sz < 32 + ntri) sz = 32 + ntri;
-		if (nbb > sz) sz = nbb;
-		if (n_crb + n_buf > sz) sz = n_crb + n_buf;
-		if (2 * n_c6 > sz) sz = 2 * n_c6;
-		if (d.nv > sz) sz = d.nv;
-		off += sz;
-		if (alias_b) {
-			const int b0 = off;
-			L.ximat = b0;
-			L.cvel = b0;
-			L.cdof_dot = b0 + n_c6;
-			int szb = 9 * d.nbody;
-			if (n_c6 + 6 * d.nv > szb) szb = n_c6 + 6 * d.nv;
-			off += szb;
-		}
-		if (u_ok) {
-			for (int id : u_members) {
-				field_slot(L, id) = off;
-				off += fsize[id];
-			}
-			L.efc_J = a0;
-			if (off - a0 < fsize[MJB_F_efc_J]) off = a0 + fsize[MJB_F_efc_J];
-			// (efc_J is alive from the end of the velocity stage to the end of the solver: what runs in between -- the dense
-			//  M^-1 solve of fwd_acceleration, the PGS stage's triangle -- takes its scratch, and Euler its right-hand side, from
-			//  the contact arrays nobody reads after make_constraint: dist | pos | frame | includemargin are contiguous, 14
-			//  doubles per contact; friction, which the elliptic solvers read, stays intact)
-			const int late = ntri + 32 + d.nv;
-			int ls = off;
-			if (14 * d.nconmax >= late) ls = L.contact_dist;
-			else off += late;
-			L.tri = ls;
-			L.solvescr = ls + ntri;
-			L.eulerx = L.solvescr + 32;
-		}
-	} else {
-		L.kinloc = off;
-		off += n_kin;
-		L.crbbuf = off;
-		off += n_buf;
-		L.eulerx = off;
-		off += d.nv;
-		L.solvescr = L.crbbuf;
-		L.tri = off;
-		off += ntri;
-		L.bbscr = off;
-		off += nbb;
-	}
-	if (off & 1) off++;
-	L.ndouble = off;
-	L.iscratch = ioff;
-	{
-		int a = d.ncollpair, b = d.neq + d.nv + d.njnt + 2 * d.ntendon + d.nconmax;
-		if (newton && rcap > a) a = rcap;  // (the primal solvers park one int of row metadata per constraint row here)
-		ioff += a > b ? a : b;
-	}
-	L.dadr = ioff;
-	ioff += (d.nefcmax > 0 && d.nv <= 16) ? 64 : 0;
-	L.nint = (ioff + 1) & ~1;
-	L.nstate = nstate;
-}
-
-// development knob MJB_DEBUG_LAYOUT: every field's offset in the fused frame, sorted (doubles, then ints)
-void dump_layout(const mjb_model *M, const FrameLayout &L)
-{
-	std::vector<std::pair<int, std::string>> dd, ii;
-	for (int i = 0; i < MJB_F_COUNT; i++)
-		if (field_slot(L, i) >= 0) (kFields[i].kind == 3 ? ii : dd).push_back({ field_slot(L, i), kFields[i].name });
-	const std::pair<int, const char *> extra[] = { { L.MhB, "MhB" }, { L.qH, "qH" }, { L.qHdi, "qHdi" }, { L.nwt_M, "nwt_M" }, { L.nwt_H, "nwt_H" },
-		{ L.nwt_vec, "nwt_vec" }, { L.nwt_row, "nwt_row" }, { L.nwt_hc, "nwt_hc" }, { L.gravity, "gravity" }, { L.gfriction, "gfriction" },
-		{ L.eqparam, "eqparam" }, { L.cwrench, "cwrench" }, { L.kinloc, "kinloc" }, { L.crbbuf, "crbbuf" }, { L.eulerx, "eulerx" },
-		{ L.tri, "tri" }, { L.solvescr, "solvescr" }, { L.bbscr, "bbscr" }, { L.act_mom, "act_mom" } };
-	for (auto &x : extra)
-		if (x.first >= 0) dd.push_back({ x.first, std::string("*") + x.second });
-	ii.push_back({ L.iscratch, "*iscratch" });
-	ii.push_back({ L.dadr, "*dadr" });
-	std::sort(dd.begin(), dd.end());
-	std::sort(ii.begin(), ii.end());
-	fprintf(stderr, "mjb fused layout: %d bytes, jrows %d, hcs %d, hcd %d, ndouble %d, nint %d, nstate %d\n doubles:", mjb_layout_bytes(L), L.jrows, L.hcs,
-	        L.hcd, L.ndouble, L.nint, L.nstate);
-	for (auto &x : dd) fprintf(stderr, " %s@%d", x.second.c_str(), x.first);
-	fprintf(stderr, "\n ints:");
-	for (auto &x : ii) fprintf(stderr, " %s@%d", x.second.c_str(), x.first);
-	fprintf(stderr, "\n");
-	(void)M;
-}
-
-// The fused frame of kernel variant 4 (Newton, capacity > 128 rows) keeps only `jrows` rows of efc_J in LDS (the rest, and all of J
-// of an env-step with more rows, live in DevState::efc_Jg).  Residency beats the price of the HBM path (measured 10 % on the steps
-// that take it): pick the row count that lets the most envs share a CU's LDS, and the largest such.
-void choose_fused_layout(mjb_model *M)
-{
-	compute_layout(M, M->Lc, true);
-	const mjb_model_desc &d = M->h;
-	M->Lw = M->Lc;
-	M->has_wide = false;
-	if (M->slot) {  // (the row-slot kernels: every row in the fused frame)
-		if (getenv("MJB_DEBUG_LAYOUT")) dump_layout(M, M->Lc);
-		return;
-	}
-	if (d.solver == MJB_SOL_NEWTON && d.nefcmax > 128 && getenv("MJB_DEBUG_FRAME_ROWS")) {  // measurement knob: rows of J in THE fused frame
-		compute_layout(M, M->Lc, true, atoi(getenv("MJB_DEBUG_FRAME_ROWS")));
-		M->Lw = M->Lc;
-		if (getenv("MJB_DEBUG_LAYOUT")) dump_layout(M, M->Lc);
-		return;
-	}
-	if (!(d.solver == MJB_SOL_NEWTON && d.nefcmax > 128) || getenv("MJB_DEBUG_JROWS")) {
-		if (getenv("MJB_DEBUG_LAYOUT")) dump_layout(M, M->Lc);
-		return;
-	}
-	auto occ = [&](int jr) {
-		FrameLayout t{};
-		compute_layout(M, t, true, jr);
-		// (gfx950 hands out its 160 KB of LDS in 128 granules of 1280 bytes -- measured: a 54000-byte frame runs two to a CU, a
-		//  50272-byte one three; 512-register kernels: one wave per SIMD, four envs per CU at most)
-		return std::min(4, 128 / ((mjb_layout_bytes(t) + 1279) / 1280));
-	};
-	const int best = occ(16);
-	int pick = 64;
-	if (best > occ(64))
-		for (pick = 60; pick > 16 && occ(pick) < best; pick -= 4) {}
-	compute_layout(M, M->Lc, true, pick);
-	if (getenv("MJB_DEBUG_LAYOUT"))  // development knob
-		dump_layout(M, M->Lc);
-	// the wide frame: up to 128 rows (two per lane) -- the largest multiple of four with which THREE frames share a CU's LDS when at least
-	// 96 rows do (the power grasp of config 5: p99 of nefc = 111, 112 rows fit three times; an env-step beyond them takes the HBM row block),
-	// else 128 when two fit
-	int wrows = 128;
-	for (int jr = 124; jr >= 96; jr -= 4)
-		if (occ(jr) >= 3) { wrows = jr; break; }
-	if (const char *v = getenv("MJB_WIDE_ROWS")) wrows = std::max(68, std::min(128, atoi(v)));  // measurement knob
-	compute_layout(M, M->Lw, true, wrows);
-	const int wbytes = mjb_layout_bytes(M->Lw);
-	M->has_wide = M->Lw.jrows > M->Lc.jrows && 2 * ((wbytes + 1279) / 1280) <= 128;
-	if (!M->has_wide) M->Lw = M->Lc;
-	compute_layout(M, M->Lc, true, pick);  // (compute_layout also sets model-wide derived fields: leave them as the default frame's)
-	if (getenv("MJB_DEBUG_LAYOUT") && M->has_wide) dump_layout(M, M->Lw);
-}
-
-// Sensors whose value is a plain copy of frame doubles (joint / actuator scalars, clock, subtree com, global
-// frame positions) become {dst, src} pairs resolved against both layouts; the rest stay on the general path.
-void build_sensor_tables(mjb_model *M)
-{
-	const mjb_model_desc &h = M->h;
-	std::vector<std::pair<int, int>> cp[3][3];  // layouts: 0 full, 1 fused, 2 wide fused (== 1 when the model has none)
-	std::vector<int> slow[3];
-	for (int i = 0; i < h.nsensor; i++) {
-		const int st = h.sensor_needstage[i] - 1;
-		if (st < 0 || st > 2) continue;
-		const int type = h.sensor_type[i], id = h.sensor_objid[i], ot = h.sensor_objtype[i];
-		bool simple = h.sensor_cutoff[i] <= 0;
-		for (int lay = 0; lay < 3 && simple; lay++) {
-			const FrameLayout &L = lay == 0 ? M->L : (lay == 1 ? M->Lc : M->Lw);
-			int src = -1, n = 1;
-			switch (type) {
-			case MJB_SENS_JOINTPOS: src = L.qpos + h.jnt_qposadr[id]; break;
-			case MJB_SENS_JOINTVEL: src = L.qvel + h.jnt_dofadr[id]; break;
-			case MJB_SENS_ACTUATORPOS: src = L.actuator_length + id; break;
-			case MJB_SENS_ACTUATORVEL: src = L.actuator_velocity + id; break;
-			case MJB_SENS_ACTUATORFRC: src = L.actuator_force + id; break;
-			case MJB_SENS_CLOCK: src = L.time; break;
-			case MJB_SENS_SUBTREECOM: src = L.subtree_com + 3 * id; n = 3; break;
-			case MJB_SENS_BALLANGVEL: src = L.qvel + h.jnt_dofadr[id]; n = 3; break;
-			case MJB_SENS_FRAMEQUAT:
-				if (h.sensor_refid[i] >= 0 || (ot != MJB_OBJ_XBODY && ot != MJB_OBJ_SITE)) { simple = false; break; }
-				n = 4;
-				src = ot == MJB_OBJ_XBODY ? L.xquat + 4 * id : L.site_xquat + 4 * id;
-				break;
-			case MJB_SENS_FRAMEPOS:
-				if (h.sensor_refid[i] >= 0) { simple = false; break; }
-				n = 3;
-				if (ot == MJB_OBJ_BODY) src = L.xipos + 3 * id;
-				else if (ot == MJB_OBJ_XBODY) src = L.xpos + 3 * id;
-				else if (ot == MJB_OBJ_GEOM) src = L.geom_xpos + 3 * id;
-				else src = L.site_xpos + 3 * id;
-				break;
-			default: simple = false;
-			}
-			if (simple)
-				for (int k = 0; k < n; k++) cp[lay][st].push_back({ h.sensor_adr[i] + k, src + k });
-		}
-		if (!simple) slow[st].push_back(i);
-	}
-	int mx = 0;
-	for (int st = 0; st < 3; st++) {
-		M->sens_ncopy[st] = (int)cp[0][st].size();
-		M->sens_nslow[st] = (int)slow[st].size();
-		if (M->sens_ncopy[st] > mx) mx = M->sens_ncopy[st];
-	}
-	M->sens_ncopy_max = mx;
-	M->sens_copy.assign((size_t)3 * 3 * (mx ? mx : 1) * 2, 0);
-	for (int lay = 0; lay < 3; lay++)
-		for (int st = 0; st < 3; st++)
-			for (size_t k = 0; k < cp[lay][st].size() && (int)k < M->sens_ncopy[st]; k++) {
-				M->sens_copy[((size_t)(lay * 3 + st) * (mx ? mx : 1) + k) * 2] = cp[lay][st][k].first;
-				M->sens_copy[((size_t)(lay * 3 + st) * (mx ? mx : 1) + k) * 2 + 1] = cp[lay][st][k].second;
-			}
-	M->sens_slow.assign((size_t)3 * (h.nsensor ? h.nsensor : 1), 0);
-	for (int st = 0; st < 3; st++)
-		for (size_t k = 0; k < slow[st].size(); k++) M->sens_slow[(size_t)st * (h.nsensor ? h.nsensor : 1) + k] = slow[st][k];
-}
-
 template <typename T> T *dev_alloc(size_t n)
 {
 	void *p = nullptr;
@@ -691,7 +126,6 @@ template <typename T> T *dev_alloc(size_t n)
 
 extern "C" {
 
-const char *mjb_last_error(void) { return g_err.c_str(); }
 int mjb_model_desc_size(void) { return (int)sizeof(mjb_model_desc); }
 int mjb_version(void) { return MJB_VERSION; }
 
@@ -700,745 +134,6 @@ int mjb_device_count(void)
 	int n = 0;
 	if (hipGetDeviceCount(&n) != hipSuccess) return 0;
 	return n;
-}
-
-mjb_model *mjb_compile(const mjb_model_desc *desc)
-{
-	if (!desc) {
-		fail(MJB_EINVAL, "mjb_compile: null desc");
-		return nullptr;
-	}
-	const mjb_model_desc &d = *desc;
-	if (d.nq < 0 || d.nv < 0 || d.nbody < 1 || d.njnt < 0 || d.nu < 0 || d.nM < 0) {
-		fail(MJB_EINVAL, "mjb_compile: negative size");
-		return nullptr;
-	}
-	{  // activations: one variable per stateful actuator, in actuator order; integrator / filter dynamics
-		int na = 0;
-		for (int i = 0; i < d.nu; i++) {
-			const int dt = d.actuator_dyntype[i];
-			if (dt != MJB_DYN_NONE && dt != MJB_DYN_INTEGRATOR && dt != MJB_DYN_FILTER) {
-				fail(MJB_EUNSUPPORTED, "mjb_compile: actuator dyntype (muscle / user dynamics) is not supported");
-				return nullptr;
-			}
-			if (d.na > 0 && d.actuator_actadr[i] != (dt != MJB_DYN_NONE ? na : -1)) {
-				fail(MJB_EINVAL, "mjb_compile: actuator_actadr must number the stateful actuators in order (-1: stateless)");
-				return nullptr;
-			}
-			if (d.na > 0 && dt != MJB_DYN_NONE && d.actuator_actlimited[i] && !(d.actuator_actrange[2 * i] < d.actuator_actrange[2 * i + 1])) {
-				fail(MJB_EINVAL, "mjb_compile: actlimited actuator with an empty actrange");
-				return nullptr;
-			}
-			na += dt != MJB_DYN_NONE ? 1 : 0;
-		}
-		if (na != d.na) {
-			fail(MJB_EINVAL, "mjb_compile: na does not match the number of stateful actuators");
-			return nullptr;
-		}
-	}
-	if (d.integrator != MJB_INT_EULER && d.integrator != MJB_INT_RK4 && d.integrator != MJB_INT_IMPLICITFAST) {
-		fail(MJB_EUNSUPPORTED, "mjb_compile: integrators Euler, RK4 and implicitfast are implemented (implicit is refused)");
-		return nullptr;
-	}
-	if (!(d.timestep[0] > 0)) {
-		fail(MJB_EINVAL, "mjb_compile: timestep must be positive");
-		return nullptr;
-	}
-	if (d.nv > 64 || d.nbody > 64) {
-		fail(MJB_EUNSUPPORTED, "mjb_compile: nv = %d, nbody = %d: the tree stages use 64-bit ancestor / subtree masks "
-		                       "(nv <= 64, nbody <= 64)", d.nv, d.nbody);
-		return nullptr;
-	}
-	// every array the description declares must be there before anything below reads it
-#define MJB_SIZE(name)                                                                    \
-	if (d.name < 0) {                                                                     \
-		fail(MJB_EINVAL, "mjb_compile: negative size %s", #name);                         \
-		return nullptr;                                                                   \
-	}
-#define MJB_OPT_I(name)
-#define MJB_OPT_D(name, n)
-#define MJB_ARR_I(name, rows, cols)                                                       \
-	if ((size_t)d.rows * (cols) && !d.name) {                                             \
-		fail(MJB_EINVAL, "mjb_compile: array %s is NULL", #name);                         \
-		return nullptr;                                                                   \
-	}
-#define MJB_ARR_D(name, rows, cols) MJB_ARR_I(name, rows, cols)
-#include "../../include/mjb_model_fields.def"
-#undef MJB_SIZE
-#undef MJB_OPT_I
-#undef MJB_OPT_D
-#undef MJB_ARR_I
-#undef MJB_ARR_D
-	for (int i = 0; i < d.nsensor; i++) {
-		static const int ok[] = { MJB_SENS_MAGNETOMETER, MJB_SENS_RANGEFINDER, MJB_SENS_TOUCH, MJB_SENS_ACCELEROMETER, MJB_SENS_VELOCIMETER, MJB_SENS_GYRO, MJB_SENS_FORCE,
-			                      MJB_SENS_TORQUE, MJB_SENS_JOINTPOS, MJB_SENS_JOINTVEL, MJB_SENS_TENDONPOS, MJB_SENS_TENDONVEL,
-			                      MJB_SENS_ACTUATORPOS, MJB_SENS_ACTUATORVEL, MJB_SENS_ACTUATORFRC, MJB_SENS_BALLQUAT,
-			                      MJB_SENS_BALLANGVEL, MJB_SENS_FRAMEPOS, MJB_SENS_FRAMEQUAT, MJB_SENS_FRAMEXAXIS,
-			                      MJB_SENS_FRAMEYAXIS, MJB_SENS_FRAMEZAXIS, MJB_SENS_FRAMELINVEL, MJB_SENS_FRAMEANGVEL,
-			                      MJB_SENS_FRAMELINACC, MJB_SENS_FRAMEANGACC, MJB_SENS_SUBTREECOM, MJB_SENS_CLOCK, MJB_SENS_JOINTLIMITPOS, MJB_SENS_JOINTLIMITVEL,
-			                      MJB_SENS_JOINTLIMITFRC, MJB_SENS_TENDONLIMITPOS, MJB_SENS_TENDONLIMITVEL, MJB_SENS_TENDONLIMITFRC, MJB_SENS_SUBTREELINVEL,
-			                      MJB_SENS_SUBTREEANGMOM, MJB_SENS_JOINTACTFRC };
-		bool found = false;
-		for (int t : ok) found = found || t == d.sensor_type[i];
-		if (!found) {
-			fail(MJB_EUNSUPPORTED, "mjb_compile: sensor %d has type %d, which is not implemented", i, d.sensor_type[i]);
-			return nullptr;
-		}
-	}
-	for (int i = 0; i < d.neq; i++) {
-		const int t = d.eq_type[i], a = d.eq_obj1id[i], b = d.eq_obj2id[i];
-		const bool body_ok = a >= 0 && a < d.nbody && b >= 0 && b < d.nbody;
-		const bool jnt_ok = a >= 0 && a < d.njnt && b >= -1 && b < d.njnt;
-		const bool ten_ok = a >= 0 && a < d.ntendon && b >= -1 && b < d.ntendon;
-		if (!((t == MJB_EQ_CONNECT || t == MJB_EQ_WELD) ? body_ok : ((t == MJB_EQ_JOINT && jnt_ok) || (t == MJB_EQ_TENDON && ten_ok)))) {
-			fail(MJB_EUNSUPPORTED, "mjb_compile: equality %d: type %d with objects (%d, %d) is not supported "
-			                       "(connect / weld between bodies, joint between hinge / slide joints)", i, t, a, b);
-			return nullptr;
-		}
-	}
-	if (d.neq > 0 && d.nefcmax <= 0) {
-		fail(MJB_EINVAL, "mjb_compile: equality constraints need nefcmax > 0");
-		return nullptr;
-	}
-	if (d.nefcmax > 0 || d.nconmax > 0) {
-		if (d.solver != MJB_SOL_PGS && d.solver != MJB_SOL_NEWTON && d.solver != MJB_SOL_CG) {
-			fail(MJB_EUNSUPPORTED, "mjb_compile: unknown solver (PGS = 0, CG = 1, Newton = 2)");
-			return nullptr;
-		}
-		const int rowcap = d.solver != MJB_SOL_PGS ? 1024 : ((d.cone == MJB_CONE_ELLIPTIC && d.nconmax > 0) ? 64 : 128);
-		if (d.nefcmax > rowcap || d.nv > 64) {
-			fail(MJB_EUNSUPPORTED, "mjb_compile: one env per wavefront: nv <= 64 and nefcmax <= 128 (PGS; 64 with elliptic cones) / "
-			                       "1024 (Newton / CG; lower <size njmax>); got nefcmax = %d, nv = %d", d.nefcmax, d.nv);
-			return nullptr;
-		}
-		if (!(d.meaninertia[0] > 0)) {
-			fail(MJB_EINVAL, "mjb_compile: meaninertia must be positive");
-			return nullptr;
-		}
-	}
-	mjb_model *M = new (std::nothrow) mjb_model;
-	if (!M) {
-		fail(MJB_ENOMEM, "mjb_compile: out of memory");
-		return nullptr;
-	}
-	M->h = d;
-	// copy arrays (declaration order)
-#define MJB_SIZE(name)
-#define MJB_OPT_I(name)
-#define MJB_OPT_D(name, n)
-#define MJB_ARR_I(name, rows, cols)                                                       \
-	{                                                                                     \
-		size_t n = (size_t)d.rows * (cols);                                               \
-		if (n && !d.name) {                                                               \
-			fail(MJB_EINVAL, "mjb_compile: array %s is NULL", #name);                     \
-			delete M;                                                                     \
-			return nullptr;                                                               \
-		}                                                                                 \
-		M->ioff.push_back(M->hint.size());                                                \
-		M->hint.insert(M->hint.end(), d.name, d.name + n);                                \
-		if ((M->hint.size() & 1)) M->hint.push_back(0);                                   \
-	}
-#define MJB_ARR_D(name, rows, cols)                                                       \
-	{                                                                                     \
-		size_t n = (size_t)d.rows * (cols);                                               \
-		if (n && !d.name) {                                                               \
-			fail(MJB_EINVAL, "mjb_compile: array %s is NULL", #name);                     \
-			delete M;                                                                     \
-			return nullptr;                                                               \
-		}                                                                                 \
-		M->doff.push_back(M->hdbl.size());                                                \
-		M->hdbl.insert(M->hdbl.end(), d.name, d.name + n);                                \
-	}
-#include "../../include/mjb_model_fields.def"
-#undef MJB_ARR_I
-#undef MJB_ARR_D
-	// re-point the host copy
-	{
-		size_t ii = 0, di = 0;
-#define MJB_ARR_I(name, rows, cols) M->h.name = M->hint.data() + M->ioff[ii++];
-#define MJB_ARR_D(name, rows, cols) M->h.name = M->hdbl.data() + M->doff[di++];
-#include "../../include/mjb_model_fields.def"
-#undef MJB_SIZE
-#undef MJB_OPT_I
-#undef MJB_OPT_D
-#undef MJB_ARR_I
-#undef MJB_ARR_D
-	}
-	const mjb_model_desc &h = M->h;
-	// ---- every index table a kernel uses as an LDS / HBM offset must stay inside its target
-	{
-		auto in = [](int v, int lo, int hi) { return v >= lo && v < hi; };
-		const char *bad = nullptr;
-		for (int b = 0; b < h.nbody && !bad; b++) {
-			if (!in(h.body_mocapid[b], -1, h.nmocap)) bad = "body_mocapid";
-			if (!in(h.body_rootid[b], 0, h.nbody) || !in(h.body_weldid[b], 0, h.nbody)) bad = "body_rootid / body_weldid";
-			if (h.body_jntnum[b] < 0 || h.body_dofnum[b] < 0 || (h.body_jntnum[b] && !in(h.body_jntadr[b], 0, h.njnt)) ||
-			    h.body_jntnum[b] + (h.body_jntnum[b] ? h.body_jntadr[b] : 0) > h.njnt || (h.body_dofnum[b] && !in(h.body_dofadr[b], 0, h.nv)) ||
-			    h.body_dofnum[b] + (h.body_dofnum[b] ? h.body_dofadr[b] : 0) > h.nv)
-				bad = "body_jntadr / body_jntnum / body_dofadr / body_dofnum";
-		}
-		for (int j = 0; j < h.njnt && !bad; j++) {
-			const int t = h.jnt_type[j], nq = t == MJB_JNT_FREE ? 7 : (t == MJB_JNT_BALL ? 4 : 1), nd = t == MJB_JNT_FREE ? 6 : (t == MJB_JNT_BALL ? 3 : 1);
-			if (!in(t, 0, 4)) bad = "jnt_type";
-			else if (!in(h.jnt_bodyid[j], 0, h.nbody)) bad = "jnt_bodyid";
-			else if (h.jnt_qposadr[j] < 0 || h.jnt_qposadr[j] + nq > h.nq) bad = "jnt_qposadr";
-			else if (h.jnt_dofadr[j] < 0 || h.jnt_dofadr[j] + nd > h.nv) bad = "jnt_dofadr";
-		}
-		for (int i = 0; i < h.nv && !bad; i++) {
-			if (!in(h.dof_bodyid[i], 0, h.nbody)) bad = "dof_bodyid";
-			if (!in(h.dof_jntid[i], 0, h.njnt)) bad = "dof_jntid";
-			if (!in(h.dof_parentid[i], -1, i)) bad = "dof_parentid";
-		}
-		for (int g = 0; g < h.ngeom && !bad; g++) {
-			if (!in(h.geom_bodyid[g], 0, h.nbody)) bad = "geom_bodyid";
-			const int t = h.geom_type[g];
-			if (t != MJB_GEOM_PLANE && t != MJB_GEOM_SPHERE && t != MJB_GEOM_CAPSULE && t != MJB_GEOM_BOX) bad = "geom_type (plane / sphere / capsule / box)";
-			if (!in(h.geom_condim[g], 1, 7) || h.geom_condim[g] == 2 || h.geom_condim[g] == 5) bad = "geom_condim (1, 3, 4, 6)";
-		}
-		for (int p = 0; p < 2 * h.ncollpair && !bad; p++)
-			if (!in(h.collpair_geom[p], 0, h.ngeom)) bad = "collpair_geom";
-		for (int p = 0; p < h.ncollpair && !bad; p++)
-			if (h.collpair_explicit[p] && h.collpair_condim[p] > 0 && h.collpair_condim[p] != 1 && h.collpair_condim[p] != 3 && h.collpair_condim[p] != 4 && h.collpair_condim[p] != 6)
-				bad = "collpair_condim (1, 3, 4, 6)";
-		for (int st = 0; st < h.nsite && !bad; st++)
-			if (!in(h.site_bodyid[st], 0, h.nbody)) bad = "site_bodyid";
-		for (int t = 0; t < h.ntendon && !bad; t++)
-			if (h.tendon_num[t] < 0 || h.tendon_adr[t] < 0 || h.tendon_adr[t] + h.tendon_num[t] > h.nwrap) bad = "tendon_adr / tendon_num";
-		for (int w = 0; w < h.nwrap && !bad; w++)
-			if (!in(h.wrap_objid[w], 0, h.njnt) || h.jnt_type[h.wrap_objid[w]] < MJB_JNT_SLIDE) bad = "wrap_objid (hinge / slide joints)";
-		auto objcount = [&](int ot) {
-			switch (ot) {
-			case MJB_OBJ_BODY: case MJB_OBJ_XBODY: return h.nbody;
-			case MJB_OBJ_JOINT: return h.njnt;
-			case MJB_OBJ_GEOM: return h.ngeom;
-			case MJB_OBJ_SITE: return h.nsite;
-			case MJB_OBJ_ACTUATOR: return h.nu;
-			default: return 0;
-			}
-		};
-		for (int i = 0; i < h.nsensor && !bad; i++) {
-			const int t = h.sensor_type[i];
-			int cnt;
-			if (t == MJB_SENS_JOINTPOS || t == MJB_SENS_JOINTVEL || t == MJB_SENS_BALLQUAT || t == MJB_SENS_BALLANGVEL || t == MJB_SENS_JOINTACTFRC ||
-			    (t >= MJB_SENS_JOINTLIMITPOS && t <= MJB_SENS_JOINTLIMITFRC))
-				cnt = h.njnt;
-			else if (t == MJB_SENS_TENDONPOS || t == MJB_SENS_TENDONVEL || (t >= MJB_SENS_TENDONLIMITPOS && t <= MJB_SENS_TENDONLIMITFRC)) cnt = h.ntendon;
-			else if (t == MJB_SENS_ACTUATORPOS || t == MJB_SENS_ACTUATORVEL || t == MJB_SENS_ACTUATORFRC) cnt = h.nu;
-			else if (t == MJB_SENS_SUBTREECOM || t == MJB_SENS_SUBTREELINVEL || t == MJB_SENS_SUBTREEANGMOM) cnt = h.nbody;
-			else if (t == MJB_SENS_CLOCK) cnt = 1 << 30;
-			else if (t >= MJB_SENS_FRAMEPOS && t <= MJB_SENS_FRAMEANGACC) cnt = objcount(h.sensor_objtype[i]);
-			else cnt = h.nsite;  // touch, accelerometer, velocimeter, gyro, force, torque
-			if (t != MJB_SENS_CLOCK && !in(h.sensor_objid[i], 0, cnt)) bad = "sensor_objid";
-			else if (t >= MJB_SENS_JOINTLIMITPOS && t <= MJB_SENS_JOINTLIMITFRC && h.jnt_type[h.sensor_objid[i]] < MJB_JNT_SLIDE) bad = "sensor_objid (joint limit sensors: hinge / slide joints)";
-			if (h.sensor_refid[i] >= 0 && !in(h.sensor_refid[i], 0, objcount(h.sensor_reftype[i]))) bad = "sensor_refid";
-			if (!in(h.sensor_dim[i], 1, 5) || h.sensor_adr[i] < 0 || h.sensor_adr[i] + h.sensor_dim[i] > h.nsensordata) bad = "sensor_adr / sensor_dim";
-			if (!in(h.sensor_needstage[i], 1, 4)) bad = "sensor_needstage";
-		}
-		if (bad) {
-			fail(MJB_EINVAL, "mjb_compile: index table %s is out of range", bad);
-			delete M;
-			return nullptr;
-		}
-		// the kinematics (every kernel's, and mj_setConst's mirror below) takes `jntnum == 1 && FREE` as the only free-joint case
-		for (int b = 0; b < h.nbody; b++)
-			for (int j = h.body_jntadr[b]; j < h.body_jntadr[b] + h.body_jntnum[b]; j++)
-				if (h.jnt_type[j] == MJB_JNT_FREE && (h.body_jntnum[b] != 1 || h.body_parentid[b] != 0)) {
-					fail(MJB_EINVAL, "mjb_compile: the free joint %d must be the only joint of a top-level body (body %d has %d joints, parent %d)", j, b,
-					     h.body_jntnum[b], h.body_parentid[b]);
-					delete M;
-					return nullptr;
-				}
-	}
-	// ---- validation of the tree tables the kernels index with
-	for (int b = 1; b < h.nbody; b++)
-		if (h.body_parentid[b] < 0 || h.body_parentid[b] >= b) {
-			fail(MJB_EINVAL, "mjb_compile: body_parentid[%d] must precede the body", b);
-			delete M;
-			return nullptr;
-		}
-	int nM = 0;
-	for (int i = 0; i < h.nv; i++) {
-		if (h.dof_parentid[i] >= i || h.dof_Madr[i] != nM) {
-			fail(MJB_EINVAL, "mjb_compile: inconsistent dof_parentid / dof_Madr at dof %d", i);
-			delete M;
-			return nullptr;
-		}
-		int depth = 0;
-		for (int j = i; j >= 0; j = h.dof_parentid[j]) {
-			M->M_rowdof.push_back(i);
-			M->M_coldof.push_back(j);
-			depth++;
-		}
-		M->dof_depth.push_back(depth);
-		if (depth > M->maxdepth) M->maxdepth = depth;
-		nM += depth;
-	}
-	if (nM != h.nM) {
-		fail(MJB_EINVAL, "mjb_compile: nM = %d does not match the dof tree (%d)", h.nM, nM);
-		delete M;
-		return nullptr;
-	}
-	for (int j = 0; j < h.njnt; j++) {
-		int t = h.jnt_type[j];
-		if (t < 0 || t > 3) {
-			fail(MJB_EINVAL, "mjb_compile: bad jnt_type[%d]", j);
-			delete M;
-			return nullptr;
-		}
-	}
-	for (int i = 0; i < h.nu; i++) {
-		int j = h.actuator_trnid[2 * i];
-		const int r = h.actuator_trnid[2 * i + 1];
-		const bool okj = h.actuator_trntype[i] == MJB_TRN_JOINT && j >= 0 && j < h.njnt && h.jnt_type[j] >= MJB_JNT_SLIDE;
-		const bool okt = h.actuator_trntype[i] == MJB_TRN_TENDON && j >= 0 && j < h.ntendon;
-		// site transmission: the site, and no refsite (-1) or another site
-		const bool oks = h.actuator_trntype[i] == MJB_TRN_SITE && j >= 0 && j < h.nsite && (r == -1 || (r >= 0 && r < h.nsite && r != j));
-		if (!okj && !okt && !oks) {
-			fail(MJB_EUNSUPPORTED, "mjb_compile: actuator %d: joint transmission on hinge / slide joints, fixed-tendon and site transmissions "
-			                       "(refsite -1 or another site) are supported", i);
-			delete M;
-			return nullptr;
-		}
-		if (oks) M->site_act.push_back(i);
-	}
-	// gravity compensation: any finite coefficient (above 1 and below 0 too); the bodies that have one
-	for (int b = 0; b < h.nbody; b++) {
-		if (!std::isfinite(h.body_gravcomp[b])) {
-			fail(MJB_EINVAL, "mjb_compile: body_gravcomp[%d] is not finite", b);
-			delete M;
-			return nullptr;
-		}
-		if (b > 0 && h.body_gravcomp[b] != 0) M->gravcomp_body.push_back(b);
-	}
-	// velocity-group start of each dof (hinge/slide: itself; ball: first of 3; free: first of each triple)
-	M->dof_jstart.resize(h.nv);
-	for (int dd = 0; dd < h.nv; dd++) {
-		int j = h.dof_jntid[dd], t = h.jnt_type[j], da = h.jnt_dofadr[j];
-		if (t == MJB_JNT_HINGE || t == MJB_JNT_SLIDE) M->dof_jstart[dd] = dd;
-		else if (t == MJB_JNT_BALL) M->dof_jstart[dd] = da;
-		else M->dof_jstart[dd] = (dd - da < 3) ? da : da + 3;
-	}
-	// packed per-body / per-dof records and the factorisation micro-program
-	for (int b = 0; b < h.nbody; b++) {
-		int rec[4] = { h.body_parentid[b], h.body_dofadr[b], h.body_dofnum[b], h.body_rootid[b] };
-		int rec2[4] = { h.body_jntadr[b], h.body_jntnum[b], h.body_sameframe[b], h.body_weldid[b] };
-		M->body_rec.insert(M->body_rec.end(), rec, rec + 4);
-		M->body_rec2.insert(M->body_rec2.end(), rec2, rec2 + 4);
-	}
-	for (int dd = 0; dd < h.nv; dd++) {
-		int rec[4] = { h.dof_Madr[dd], M->dof_depth[dd] - 1, h.dof_bodyid[dd], h.dof_parentid[dd] };
-		M->dof_rec.insert(M->dof_rec.end(), rec, rec + 4);
-	}
-	// what the per-dof / per-joint phases of com_vel / com_pos look up, one 16-byte record each (the chains of dependent table reads --
-	// dof -> joint -> type, joint -> body -> root -- cost a trip to L2 per link)
-	for (int dd = 0; dd < h.nv; dd++) {
-		const int j = h.dof_jntid[dd], bd = h.dof_bodyid[dd];
-		int rec[4] = { (h.jnt_type[j] == MJB_JNT_FREE && dd - h.jnt_dofadr[j] < 3) ? 1 : 0, M->dof_jstart[dd] == h.body_dofadr[bd] ? 1 : 0,
-			           h.body_parentid[bd], bd };
-		M->dof_rec2.insert(M->dof_rec2.end(), rec, rec + 4);
-	}
-	for (int j = 0; j < h.njnt; j++) {
-		const int bi = h.jnt_bodyid[j];
-		int rec[4] = { bi, h.jnt_type[j], h.jnt_dofadr[j], h.body_rootid[bi] };
-		M->jnt_rec.insert(M->jnt_rec.end(), rec, rec + 4);
-	}
-	if (M->dof_rec2.empty()) M->dof_rec2.assign(4, 0);
-	if (M->jnt_rec.empty()) M->jnt_rec.assign(4, 0);
-	for (int k = 0; k < h.nv; k++) {
-		M->fac_beg.push_back((int)M->fac_ops.size() / 4);
-		const int kk = h.dof_Madr[k], na = M->dof_depth[k] - 1;
-		for (int a = 0; a < na; a++) {
-			const int i = M->M_coldof[kk + 1 + a];
-			for (int bb = a; bb < na; bb++) {
-				int op[4] = { h.dof_Madr[i] + (bb - a), kk + 1 + a, kk + 1 + bb, 0 };
-				M->fac_ops.insert(M->fac_ops.end(), op, op + 4);
-			}
-		}
-	}
-	M->fac_beg.push_back((int)M->fac_ops.size() / 4);
-	// the same updates scheduled by LEVELS of the elimination tree (= the dof tree): pivots of equal height touch disjoint rows of
-	// their own and only meet in the entries of common ancestors, so a level runs in one round: one lane per contribution
-	// LD[dst] -= LD[srcA] / D_pivot * LD[srcB], the contributions to one entry combined by its first lane in descending pivot order.
-	// flv_hdr [level][4] = { slots, longest list of slot 0 / 1 / 2 };  flv_rec [level][3][64][4] (below).  flv_n == 0 (a level with
-	// more than 192 contributions, a list longer than 6, more than 64 levels): the kernels keep the pivot-by-pivot factorisation
-	{
-		std::vector<int> hgt((size_t)(h.nv > 0 ? h.nv : 1), 0);
-		int nlev = 0, nseg = 0;
-		bool flv_ok = true;
-		for (int k = h.nv - 1; k >= 0; k--) {
-			const int pk = h.dof_parentid[k];
-			if (pk >= 0 && hgt[pk] < hgt[k] + 1) hgt[pk] = hgt[k] + 1;
-			if (hgt[k] + 1 > nlev) nlev = hgt[k] + 1;
-		}
-		for (int lev = 0; lev < nlev; lev++) {
-			std::vector<int> dsts;
-			std::vector<std::vector<int>> lists;
-			for (int k = h.nv - 1; k >= 0; k--) {
-				if (hgt[k] != lev) continue;
-				const int kk = h.dof_Madr[k], na = M->dof_depth[k] - 1;
-				for (int a = 0; a < na; a++) {
-					const int i = M->M_coldof[kk + 1 + a];
-					for (int bb = a; bb < na; bb++) {
-						const int dst = h.dof_Madr[i] + (bb - a);
-						size_t at = 0;
-						while (at < dsts.size() && dsts[at] != dst) at++;
-						if (at == dsts.size()) {
-							dsts.push_back(dst);
-							lists.emplace_back();
-						}
-						lists[at].push_back(kk + 1 + a);
-						lists[at].push_back(kk + 1 + bb);
-						lists[at].push_back(k);
-					}
-				}
-			}
-			// a level's CONTRIBUTIONS at fixed places, one 16-byte word per lane in up to three slots: { dst | (row + 1 of a diagonal
-			// dst) << 16, valid | owner << 1 | list length << 8, srcA | srcB << 16, pivot }.  The contributions to one entry sit in
-			// consecutive lanes of one 16-lane row, the entry's owner first: it collects the others' products by DPP row shifts.
-			// The lists go first (they must not straddle a row), the single contributions fill up.
-			if (dsts.empty()) continue;
-			std::vector<int> W;
-			int tm[3] = { 0, 0, 0 };
-			auto put = [&](size_t it) {
-				const int d = dsts[it], n = (int)lists[it].size() / 3;
-				const int drow1 = M->M_rowdof[d] == M->M_coldof[d] ? M->M_rowdof[d] + 1 : 0;
-				while ((int)(W.size() / 4) % 16 + n > 16) W.insert(W.end(), 4, 0);
-				for (int t = 0; t < n; t++) {
-					const int slot = (int)(W.size() / 4) / 64;
-					if (slot < 3 && n > tm[slot]) tm[slot] = n;
-					int r[4] = { d | (drow1 << 16), 1 | (t == 0 ? 2 : 0) | (n << 8), lists[it][3 * t] | (lists[it][3 * t + 1] << 16), lists[it][3 * t + 2] };
-					W.insert(W.end(), r, r + 4);
-				}
-			};
-			for (size_t it = 0; it < dsts.size(); it++) {
-				if (lists[it].size() / 3 > 6) flv_ok = false;
-				else if (lists[it].size() / 3 > 1) put(it);
-			}
-			for (size_t it = 0; it < dsts.size(); it++)
-				if (lists[it].size() / 3 == 1) put(it);
-			const int nslot = ((int)(W.size() / 4) + 63) / 64;
-			if (nslot > 3) flv_ok = false;
-			W.resize((size_t)3 * 64 * 4, 0);
-			int hdr[4] = { nslot, tm[0], tm[1], tm[2] };
-			M->flv_hdr.insert(M->flv_hdr.end(), hdr, hdr + 4);
-			M->flv_rec.insert(M->flv_rec.end(), W.begin(), W.end());
-			nseg++;
-		}
-		if (h.nM >= 65536 || nseg > 64) flv_ok = false;
-		if (!flv_ok) {
-			nseg = 0;
-			M->flv_hdr.clear();
-			M->flv_rec.clear();
-		}
-		// (three empty levels behind the last: the kernel's look-ahead fetches need no bounds test)
-		M->flv_rec.insert(M->flv_rec.end(), (size_t)3 * (3 * 64 * 4), 0);
-		M->flv_n = nseg;
-		// per qM entry: its row, and whether it is the diagonal one (the first and the last round of factor_levels)
-		M->flv_ent.assign((size_t)((h.nM + 255) / 256 * 256 + 256), 0);
-		for (int en = 0; en < h.nM; en++) M->flv_ent[en] = M->M_rowdof[en] | (M->M_rowdof[en] == M->M_coldof[en] ? 0x10000 : 0);
-		if (M->flv_hdr.empty()) M->flv_hdr.assign(4, 0);
-		if (M->flv_rec.empty()) M->flv_rec.assign(4, 0);
-	}
-	// ancestor-dof bit masks per body (contact Jacobians)
-	M->body_dofmask.assign((size_t)2 * h.nbody, 0);
-	for (int b = 1; b < h.nbody; b++) {
-			int bb = b;
-			while (bb > 0 && h.body_dofnum[bb] == 0) bb = h.body_parentid[bb];
-			if (bb == 0) continue;
-			for (int i = h.body_dofadr[bb] + h.body_dofnum[bb] - 1; i >= 0; i = h.dof_parentid[i])
-				M->body_dofmask[2 * b + (i >> 5)] |= (int)(1u << (i & 31));
-		}
-	// dense address map of the joint-space inertia for the register-resident factor / solve (nv <= 16)
-	M->M_dense.assign(256, -1);
-	if (h.nv <= 16)
-		for (int en = 0; en < h.nM; en++) M->M_dense[16 * M->M_rowdof[en] + M->M_coldof[en]] = en;
-	// symmetric dense address map (nv <= 32): qM address of entry (i, j) = (j, i), -1 where the tree leaves a zero.  The primal
-	// solvers keep row `lane` of M in registers (fwd_constraint_newton) instead of a dense nv x nv copy in the frame.
-	M->M_sym.assign(1024, -1);
-	if (h.nv <= 32)
-		for (int en = 0; en < h.nM; en++) {
-			M->M_sym[32 * M->M_rowdof[en] + M->M_coldof[en]] = en;
-			M->M_sym[32 * M->M_coldof[en] + M->M_rowdof[en]] = en;
-		}
-	// ancestors at distance 2^r for the pointer-jumping kinematics (0 = world or beyond the root)
-	{
-		int maxd = 0;
-		std::vector<int> depth((size_t)h.nbody, 0);
-		for (int b = 1; b < h.nbody; b++) {
-			depth[b] = depth[h.body_parentid[b]] + 1;
-			if (depth[b] > maxd) maxd = depth[b];
-		}
-		M->kin_rounds = 0;
-		while ((1 << M->kin_rounds) < maxd) M->kin_rounds++;
-		M->body_anc.assign((size_t)(M->kin_rounds + 2) * h.nbody, 0);
-		for (int b = 1; b < h.nbody; b++) M->body_anc[b] = h.body_parentid[b];
-		for (int r = 1; r < M->kin_rounds + 2; r++)
-			for (int b = 1; b < h.nbody; b++) {
-				const int a = M->body_anc[(size_t)(r - 1) * h.nbody + b];
-				M->body_anc[(size_t)r * h.nbody + b] = a ? M->body_anc[(size_t)(r - 1) * h.nbody + a] : 0;
-			}
-	}
-	// ancestor dof lists for the root-to-leaf sums
-	{
-		M->body_dofanc.assign((size_t)4 * h.nbody, -1);
-		bool aok = h.nv <= 255 && h.nv > 0;
-		int amax = 0;
-		for (int b = 1; b < h.nbody && aok; b++) {
-			int n = 0;
-			for (int i = 0; i < h.nv && i < 64; i++)
-				if ((M->body_dofmask[2 * b + (i >> 5)] >> (i & 31)) & 1) {
-					if (n >= 16) { aok = false; break; }
-					unsigned int w = (unsigned int)M->body_dofanc[4 * b + (n >> 2)];
-					w = (w & ~(0xFFu << (8 * (n & 3)))) | ((unsigned int)i << (8 * (n & 3)));
-					M->body_dofanc[4 * b + (n >> 2)] = (int)w;
-					n++;
-				}
-			if (n > amax) amax = n;
-		}
-		if (h.nv > 64) aok = false;
-		M->dofanc_max = aok ? amax : 0;
-	}
-	// subtree membership masks (subtree com, composite inertia)
-	M->body_submask.assign((size_t)2 * h.nbody, 0);
-	for (int b = 0; b < h.nbody && h.nbody <= 64; b++)
-		for (int a = b;; a = h.body_parentid[a]) {
-			M->body_submask[2 * a + (b >> 5)] |= (int)(1u << (b & 31));
-			if (a == 0) break;
-		}
-	M->sub_nt = h.nbody <= 16 ? 1 : (h.nbody <= 32 ? 2 : 0);
-	M->sub_S.assign((size_t)(M->sub_nt > 0 ? M->sub_nt * 4 * M->sub_nt * 64 : 1), 0.0);
-	for (int t = 0; t < M->sub_nt; t++)
-		for (int k = 0; k < 4 * M->sub_nt; k++)
-			for (int l = 0; l < 64; l++) {
-				const int a = 16 * t + (l & 15), b = 4 * k + (l >> 4);
-				if (a < h.nbody && b < h.nbody && ((M->body_submask[2 * a + (b >> 5)] >> (b & 31)) & 1))
-					M->sub_S[((size_t)t * 4 * M->sub_nt + k) * 64 + l] = 1.0;
-			}
-	M->dof_bodymask.assign((size_t)2 * (h.nv > 0 ? h.nv : 1), 0);
-	for (int b = 1; b < h.nbody; b++)
-		for (int i = 0; i < h.nv; i++)
-			if ((M->body_dofmask[2 * b + (i >> 5)] >> (i & 31)) & 1) M->dof_bodymask[2 * i + (b >> 5)] |= (int)(1u << (b & 31));
-	const bool gravcomp = !M->gravcomp_body.empty();  // (such a model matches no compiled-in topology; the split step's smooth kernel has no such term and stands down)
-	M->le_topo = mjb_lane_env_match(&h);
-	if (M->le_topo < 0 && mjb_lane_env_eligible(&h)) M->le_topo = MJB_LE_TOPO_JIT;
-	// the split step (smooth half in lane = env form, constraint half one env per wavefront): the constraint half is kernel variant 9's -- plain PGS,
-	// pyramidal / frictionless contacts, nv <= 16, no stage that needs mj_rnePostConstraint
-	M->sm_topo = -1;
-	if (!gravcomp && h.nefcmax > 0 && h.solver == MJB_SOL_PGS && !(h.cone == MJB_CONE_ELLIPTIC && h.nconmax > 0) && h.nv <= 16 && !M->need_rnepost && h.nefcmax <= 128)
-		M->sm_topo = mjb_smooth_match(&h);
-	if (M->le_topo != MJB_LE_TOPO_NONE || M->sm_topo >= 0) {
-		M->le_tape.assign(mjb_lane_env_tape_doubles(&h), 0.0);
-		mjb_lane_env_tape(&h, M->le_tape.data());
-	}
-	M->eulerdamp = 0;
-	M->damp_int.assign(h.dof_damping, h.dof_damping + h.nv);
-	if (h.integrator == MJB_INT_IMPLICITFAST) {
-		// mj_implicit, mjINT_IMPLICITFAST: qH = M - h D, D = mjd_passive_vel + mjd_actuator_vel; a model constant on the diagonal here
-		for (int t = 0; t < h.ntendon; t++)
-			if (h.tendon_damping[t] != 0) {
-				fail(MJB_EUNSUPPORTED, "mjb_compile: integrator implicitfast with tendon damping is not supported");
-				delete M;
-				return nullptr;
-			}
-		for (int i = 0; i < h.nv; i++) M->damp_int[i] = (h.disableflags & MJB_DSBL_PASSIVE) ? 0.0 : h.dof_damping[i];
-		for (int i = 0; i < h.nu; i++) {
-			if (h.actuator_gaintype[i] == MJB_GAIN_AFFINE && h.actuator_gainprm[3 * i + 2] != 0) {
-				fail(MJB_EUNSUPPORTED, "mjb_compile: integrator implicitfast with a velocity term in an affine actuator gain is not supported");
-				delete M;
-				return nullptr;
-			}
-			if (h.disableflags & MJB_DSBL_ACTUATION) continue;
-			const double bv = h.actuator_biastype[i] == MJB_BIAS_AFFINE ? h.actuator_biasprm[3 * i + 2] : 0.0, g = h.actuator_gear[6 * i];
-			if (h.actuator_trntype[i] == MJB_TRN_SITE) {
-				if (bv != 0) {  // (moment' bv moment depends on the configuration and is not diagonal)
-					fail(MJB_EUNSUPPORTED, "mjb_compile: integrator implicitfast with a velocity-dependent actuator on a site is not supported");
-					delete M;
-					return nullptr;
-				}
-				continue;
-			}
-			if (h.actuator_trntype[i] == MJB_TRN_TENDON) {
-				if (bv != 0) {  // (moment' bv moment couples the tendon's joints: not diagonal)
-					fail(MJB_EUNSUPPORTED, "mjb_compile: integrator implicitfast with a velocity-dependent actuator on a tendon is not supported");
-					delete M;
-					return nullptr;
-				}
-				continue;
-			}
-			M->damp_int[h.jnt_dofadr[h.actuator_trnid[2 * i]]] -= g * g * bv;
-		}
-		for (int i = 0; i < h.nv; i++)
-			if (M->damp_int[i] != 0) M->eulerdamp = 1;
-	} else if (!(h.disableflags & MJB_DSBL_EULERDAMP))
-		for (int i = 0; i < h.nv; i++)
-			if (h.dof_damping[i] > 0) M->eulerdamp = 1;
-	M->nfriction = 0;
-	if (!(h.disableflags & MJB_DSBL_FRICTIONLOSS))
-		for (int i = 0; i < h.nv; i++)
-			if (h.dof_frictionloss[i] > 0) M->nfriction++;
-	if (!(h.disableflags & MJB_DSBL_FRICTIONLOSS))
-		for (int t = 0; t < h.ntendon; t++)
-			if (h.tendon_frictionloss[t] > 0) M->nfriction++;
-	// per-pair records of the static candidate list: everything mj_collision / mj_contactParam derive from the two geoms'
-	// constants, resolved once (friction stays per env: rule 0 = max of both geoms, 1 = geom1, 2 = geom2)
-	M->pair_i.assign((size_t)8 * (h.ncollpair > 0 ? h.ncollpair : 1), 0);
-	M->pair_d.assign((size_t)24 * (h.ncollpair > 0 ? h.ncollpair : 1), 0.0);
-	for (int p = 0; p < h.ncollpair; p++) {
-		const int g1 = h.collpair_geom[2 * p], g2 = h.collpair_geom[2 * p + 1];
-		int *pi = M->pair_i.data() + 8 * p;
-		double *pd = M->pair_d.data() + 24 * p;
-		pi[0] = g1; pi[1] = g2; pi[2] = h.geom_type[g1]; pi[3] = h.geom_type[g2];
-		pi[6] = MJB_COLFUNC_DEFAULT;  // collision-function override (mjb_register_collision patches the batch's copy)
-		pi[7] = 0;
-		for (int k = 0; k < 3; k++) {
-			pd[k] = h.geom_size[3 * g1 + k];
-			pd[3 + k] = h.geom_size[3 * g2 + k];
-		}
-		const double margin = std::max(h.geom_margin[g1], h.geom_margin[g2]), gap = std::max(h.geom_gap[g1], h.geom_gap[g2]);
-		pd[6] = margin; pd[7] = gap; pd[8] = h.geom_rbound[g1]; pd[9] = h.geom_rbound[g2];
-		double *solref = pd + 10, *solimp = pd + 12;
-		const int pr1 = h.geom_priority[g1], pr2 = h.geom_priority[g2];
-		if (pr1 != pr2) {  // mj_contactParam: the geom with the higher priority decides
-			const int g = pr1 > pr2 ? g1 : g2;
-			pi[4] = h.geom_condim[g];
-			pi[5] = pr1 > pr2 ? 1 : 2;
-			for (int k = 0; k < 2; k++) solref[k] = h.geom_solref[2 * g + k];
-			for (int k = 0; k < 5; k++) solimp[k] = h.geom_solimp[5 * g + k];
-		} else {
-			pi[4] = std::max(h.geom_condim[g1], h.geom_condim[g2]);
-			pi[5] = 0;
-			const double s1 = h.geom_solmix[g1], s2 = h.geom_solmix[g2];
-			double mix;
-			if (s1 >= 1e-15 && s2 >= 1e-15) mix = s1 / (s1 + s2);
-			else if (s1 < 1e-15 && s2 < 1e-15) mix = 0.5;
-			else if (s1 < 1e-15) mix = 0.0;
-			else mix = 1.0;
-			const double r10 = h.geom_solref[2 * g1], r20 = h.geom_solref[2 * g2];
-			for (int k = 0; k < 2; k++) {
-				const double a = h.geom_solref[2 * g1 + k], b = h.geom_solref[2 * g2 + k];
-				solref[k] = (r10 > 0 && r20 > 0) ? mix * a + (1 - mix) * b : std::min(a, b);
-			}
-			for (int k = 0; k < 5; k++) solimp[k] = mix * h.geom_solimp[5 * g1 + k] + (1 - mix) * h.geom_solimp[5 * g2 + k];
-		}
-		pd[17] = margin - gap;
-		pd[21] = h.body_invweight0[2 * h.geom_bodyid[g1]] + h.body_invweight0[2 * h.geom_bodyid[g2]];
-		for (int k = 0; k < 3; k++) {  // mj_contactParam's friction of the MODEL's geoms (per-env overrides are mixed on the device)
-			const double a = h.geom_friction[3 * g1 + k], b = h.geom_friction[3 * g2 + k];
-			pd[18 + k] = pi[5] == 0 ? std::max(a, b) : (pi[5] == 1 ? a : b);
-		}
-		if (h.collpair_explicit[p]) {
-			// <contact><pair>: what the pair states goes on top of the geoms' mix (collpair_param: friction[5] solref[2] solimp[5] margin gap, NaN = not stated)
-			const double *pp = h.collpair_param + 14 * p;
-			if (h.collpair_condim[p] > 0) pi[4] = h.collpair_condim[p];
-			if (!std::isnan(pp[5])) { solref[0] = pp[5]; solref[1] = pp[6]; }
-			if (!std::isnan(pp[7])) for (int k = 0; k < 5; k++) solimp[k] = pp[7 + k];
-			if (!std::isnan(pp[12])) pd[6] = pp[12];
-			if (!std::isnan(pp[13])) pd[7] = pp[13];
-			pd[17] = pd[6] - pd[7];
-			if (!std::isnan(pp[0])) {  // the pair's five friction numbers: tangent 1, spin, roll 1 in the slots of the geoms' three; tangent 2, roll 2 in the pads
-				pi[5] = 4;
-				pd[18] = pp[0]; pd[19] = pp[2]; pd[20] = pp[3]; pd[22] = pp[1]; pd[23] = pp[4];
-			}
-		}
-	}
-	{  // limit records (see mjb_dev.h)
-		const int nl = h.njnt + h.ntendon;
-		M->lim_d.assign((size_t)24 * (nl > 0 ? nl : 1), 0.0);
-		M->lim_i.assign((size_t)4 * (nl > 0 ? nl : 1), 0);
-		for (int j = 0; j < h.njnt; j++) {
-			double *r = M->lim_d.data() + 24 * j;
-			int *ri = M->lim_i.data() + 4 * j;
-			ri[0] = !h.jnt_limited[j] ? 0 : (h.jnt_type[j] >= MJB_JNT_SLIDE ? 1 : (h.jnt_type[j] == MJB_JNT_BALL ? 2 : 0));  // (2: a ball joint's angle limit)
-			ri[1] = h.jnt_qposadr[j];
-			ri[2] = h.jnt_dofadr[j];
-			r[0] = h.jnt_range[2 * j]; r[1] = h.jnt_range[2 * j + 1]; r[6] = h.jnt_margin[j];
-			r[10] = h.jnt_solref[2 * j]; r[11] = h.jnt_solref[2 * j + 1];
-			for (int k = 0; k < 5; k++) r[12 + k] = h.jnt_solimp[5 * j + k];
-			r[21] = h.dof_invweight0[h.jnt_dofadr[j]];
-		}
-		for (int t = 0; t < h.ntendon; t++) {
-			double *r = M->lim_d.data() + 24 * (h.njnt + t);
-			int *ri = M->lim_i.data() + 4 * (h.njnt + t);
-			ri[0] = h.tendon_limited[t] ? 1 : 0;
-			ri[1] = t;
-			r[0] = h.tendon_range[2 * t]; r[1] = h.tendon_range[2 * t + 1]; r[6] = h.tendon_margin[t];
-			r[10] = h.tendon_solref_lim[2 * t]; r[11] = h.tendon_solref_lim[2 * t + 1];
-			for (int k = 0; k < 5; k++) r[12 + k] = h.tendon_solimp_lim[5 * t + k];
-			r[21] = h.tendon_invweight0[t];
-		}
-	}
-	compute_layout(M, M->L, false);
-	{
-		const bool primal = h.nefcmax > 0 && (h.solver == MJB_SOL_NEWTON || h.solver == MJB_SOL_CG);
-		M->slot = primal && (h.nefcmax > 256 || mjb_layout_bytes(M->L) > mjb_max_lds_bytes());
-	}
-	choose_fused_layout(M);
-	M->hbm_full = M->slot && mjb_layout_bytes(M->L) > mjb_max_lds_bytes();
-	M->hbm_fused = M->slot && mjb_layout_bytes(M->Lc) > mjb_max_lds_bytes();
-	build_sensor_tables(M);
-	// actuators per dof (CSR, ascending actuator id)
-	M->dof_act_adr.assign((size_t)h.nv + 1, 0);
-	// (one entry per (dof, actuator) with the actuator's moment arm on that dof: gear for a joint transmission, gear * coefficient for every
-	//  joint of a fixed tendon)
-	M->act_tendon = 0;
-	auto each_arm = [&](auto &&fn) {
-		for (int i = 0; i < h.nu; i++) {
-			if (h.actuator_trntype[i] == MJB_TRN_SITE) continue;  // (configuration-dependent: the kernels compute its moment, FrameLayout::act_mom)
-			const int id = h.actuator_trnid[2 * i];
-			if (h.actuator_trntype[i] == MJB_TRN_TENDON) {
-				M->act_tendon = 1;
-				for (int w = h.tendon_adr[id]; w < h.tendon_adr[id] + h.tendon_num[id]; w++)
-					fn(h.jnt_dofadr[h.wrap_objid[w]], i, h.actuator_gear[6 * i] * h.wrap_prm[w]);
-			} else
-				fn(h.jnt_dofadr[id], i, h.actuator_gear[6 * i]);
-		}
-	};
-	each_arm([&](int dof, int, double) { M->dof_act_adr[dof + 1]++; });
-	for (int dd = 0; dd < h.nv; dd++) M->dof_act_adr[dd + 1] += M->dof_act_adr[dd];
-	M->dof_act_id.assign((size_t)M->dof_act_adr[h.nv], 0);
-	M->dof_act_mom.assign((size_t)M->dof_act_adr[h.nv], 0.0);
-	{
-		std::vector<int> fill(M->dof_act_adr.begin(), M->dof_act_adr.end() - 1);
-		each_arm([&](int dof, int i, double arm) {
-			M->dof_act_id[fill[dof]] = i;
-			M->dof_act_mom[fill[dof]++] = arm;
-		});
-	}
-	{
-		const int frame_bytes = mjb_layout_bytes(M->L);
-		if (frame_bytes > mjb_max_lds_bytes() && !M->slot) {  // (the row-slot kernels run such a frame from HBM)
-			fail(MJB_EUNSUPPORTED, "mjb_compile: the per-env working set (%d bytes) exceeds one CU's LDS (%d bytes); "
-			                       "lower nconmax / nefcmax", frame_bytes, mjb_max_lds_bytes());
-			delete M;
-			return nullptr;
-		}
-	}
-	g_err.clear();
-	return M;
-}
-
-void mjb_free_model(mjb_model *m) { delete m; }
-
-int mjb_field_size(const mjb_model *m, int field)
-{
-	if (!m || field < 0 || field >= MJB_F_COUNT) return fail(MJB_EINVAL, "mjb_field_size: bad argument");
-	return m->field_size[field];
-}
-int mjb_field_is_int(int field) { return field >= 0 && field < MJB_F_COUNT && kFields[field].kind == 3; }
-int mjb_field_is_state(int field) { return field >= 0 && field < MJB_F_COUNT && kFields[field].kind == 0; }
-const char *mjb_field_name(int field) { return field >= 0 && field < MJB_F_COUNT ? kFields[field].name : ""; }
-int mjb_frame_doubles(const mjb_model *m) { return m ? m->L.ndouble + m->L.nint / 2 : fail(MJB_EINVAL, "null model"); }
-int mjb_frame_bytes(const mjb_model *m, int fused)
-{
-	if (!m) return fail(MJB_EINVAL, "null model");
-	const FrameLayout &L = fused == 2 ? m->Lw : (fused ? m->Lc : m->L);  // (2: the wide fused frame of kernel variant 4, == 1 when the model has none)
-	return mjb_layout_bytes(L);
-}
-int mjb_frame_offset(const mjb_model *m, int field, int fused)
-{
-	if (!m || field < 0 || field >= MJB_F_COUNT) return fail(MJB_EINVAL, "bad model / field");
-	const FrameLayout &L = fused ? m->Lc : m->L;
-	return field_slot(L, field);
 }
 
 void mjb_free_batch(mjb_batch *b)
@@ -1751,7 +446,7 @@ mjb_batch *mjb_make_batch(const mjb_model *M, int nenv, int device)
 		mjb_free_batch(b);
 		return nullptr;
 	}
-	g_err.clear();
+	clear_error();
 	return b;
 }
 
@@ -3020,30 +1715,8 @@ int mjb_split_step_info(const mjb_batch *b, int *used_last, int *slices)
 	if (slices) *slices = b ? b->split_slices_last : 0;
 	return b ? b->model->sm_topo : -1;
 }
-int mjb_model_split_step(const mjb_model *m) { return m ? m->sm_topo : -1; }
-int mjb_model_frame_info(const mjb_model *m, int *full_hbm, int *fused_hbm)
-{
-	if (full_hbm) *full_hbm = m && m->hbm_full ? 1 : 0;
-	if (fused_hbm) *fused_hbm = m && m->hbm_fused ? 1 : 0;
-	return m ? (m->slot ? 1 : 0) : fail(MJB_EINVAL, "null model");
-}
 const char *mjb_lane_env_error(void) { return mjb_lane_env_jit_error(); }
 void mjb_lane_env_jit_counts(int *compiled, int *disk_hits) { mjb_lane_env_jit_stats(compiled, disk_hits); }
-int mjb_model_lane_env(const mjb_model *m) { return m ? m->le_topo : -1; }
-int mjb_model_lane_env_tape(const mjb_model *m, double *out, int cap)
-{
-	if (!m || m->le_topo == MJB_LE_TOPO_NONE) return -1;
-	const int n = (int)m->le_tape.size();
-	if (out && cap >= n) memcpy(out, m->le_tape.data(), (size_t)n * sizeof(double));
-	return n;
-}
-int mjb_model_lane_env_overlay(const mjb_model *m, double *out, int cap)
-{
-	if (!m || m->le_topo == MJB_LE_TOPO_NONE) return -1;
-	const int n = mjb_lane_env_overlay_slots(&m->h);
-	if (out && cap >= n) mjb_lane_env_overlay_row(&m->h, nullptr, nullptr, out);
-	return n;
-}
 int mjb_lane_env_plan(const mjb_model *m, int ncu, int nenv, int build, int form, int sweep_waves, int lds_kb, int *out_form, int *out_sweep_waves, int *out_lds_kb)
 {
 	if (m && m->le_topo == MJB_LE_TOPO_NONE) return -1;
@@ -3285,12 +1958,6 @@ int mjb_set_env_equality(mjb_batch *b, int env_lo, int env_hi, const double *par
 	return env_param(b, &b->env_equality, &b->st.env_equality, 19 * h.neq, packed.data(), env_lo, env_hi, params, "mjb_set_env_equality");
 }
 
-int mjb_env_mass_stride(const mjb_model *m)
-{
-	if (!m) return fail(MJB_EINVAL, "null model");
-	return 7 * m->h.nbody + m->h.nv + m->h.ntendon + 1;
-}
-
 // The env's block of inertial, joint and actuator constants (DevState::env_mass, mjb_dev.h): one allocation, mirrored on the host.  The
 // first override of either family fills every env's block with the model's values; a setter then edits its rows in the mirror and
 // uploads them.  EnvBlock: where the arrays of the joint section sit, behind the public mass block (jnt0 = mjb_env_mass_stride).
@@ -3402,232 +2069,6 @@ int mjb_set_env_mass_params(mjb_batch *b, int env_lo, int env_hi, const double *
 	return MJB_OK;
 }
 
-// ---- mj_setConst for new body masses (callbacks.cpp:251-256, :582), host side, plain C++ ----
-// What mj_setConst's set0 stage derives from the masses at qpos0: body_subtreemass, dof_invweight0 (diagonal of M^-1; joint-wise
-// mean over the 3 dofs of a ball joint / each half of a free joint), body_invweight0 (mean translational / rotational diagonal of
-// J M^-1 J' at the body's inertial frame; 0 for bodies welded to the world), tendon_invweight0 (J_t M^-1 J_t') and
-// stat.meaninertia (mean diagonal of M).  M is assembled from body Jacobians (m Jp'Jp + Jr' R I R' Jr + armature), the same
-// formulation as mujoco_ros_pkgs_amd/refdyn.py, which tests/test_setconst_cpp.py compares it with.
-namespace {
-struct SC {  // tiny dense helpers (row-major)
-	static void quat2mat(const double *q, double *R)
-	{
-		const double w = q[0], x = q[1], y = q[2], z = q[3];
-		R[0] = 1 - 2 * (y * y + z * z); R[1] = 2 * (x * y - w * z); R[2] = 2 * (x * z + w * y);
-		R[3] = 2 * (x * y + w * z); R[4] = 1 - 2 * (x * x + z * z); R[5] = 2 * (y * z - w * x);
-		R[6] = 2 * (x * z - w * y); R[7] = 2 * (y * z + w * x); R[8] = 1 - 2 * (x * x + y * y);
-	}
-	static void qmul(const double *a, const double *b, double *o)
-	{
-		const double r[4] = { a[0] * b[0] - a[1] * b[1] - a[2] * b[2] - a[3] * b[3], a[0] * b[1] + a[1] * b[0] + a[2] * b[3] - a[3] * b[2],
-			                  a[0] * b[2] - a[1] * b[3] + a[2] * b[0] + a[3] * b[1], a[0] * b[3] + a[1] * b[2] - a[2] * b[1] + a[3] * b[0] };
-		for (int k = 0; k < 4; k++) o[k] = r[k];
-	}
-	static void mv(const double *R, const double *v, double *o)
-	{
-		const double r[3] = { R[0] * v[0] + R[1] * v[1] + R[2] * v[2], R[3] * v[0] + R[4] * v[1] + R[5] * v[2], R[6] * v[0] + R[7] * v[1] + R[8] * v[2] };
-		for (int k = 0; k < 3; k++) o[k] = r[k];
-	}
-	static void cross(const double *a, const double *b, double *o)
-	{
-		const double r[3] = { a[1] * b[2] - a[2] * b[1], a[2] * b[0] - a[0] * b[2], a[0] * b[1] - a[1] * b[0] };
-		for (int k = 0; k < 3; k++) o[k] = r[k];
-	}
-};
-}  // namespace
-
-int mjb_derive_mass_params(const mjb_model *model, const double *body_mass, const double *body_inertia, double *out)
-{
-	if (!model || !body_mass || !out) return fail(MJB_EINVAL, "mjb_derive_mass_params: bad argument");
-	return mjb_derive_mass_params_armature(model, body_mass, body_inertia, nullptr, out);
-}
-
-int mjb_derive_mass_params_armature(const mjb_model *model, const double *body_mass, const double *body_inertia, const double *dof_armature, double *out)
-{
-	if (!model || !body_mass || !out) return fail(MJB_EINVAL, "mjb_derive_mass_params_armature: bad argument");
-	const mjb_model_desc &h = model->h;
-	const double *armature = dof_armature ? dof_armature : h.dof_armature;
-	const int nb = h.nbody, nv = h.nv, nj = h.njnt, nt = h.ntendon;
-	const double *inertia = body_inertia ? body_inertia : h.body_inertia;
-	double *o_mass = out, *o_sub = out + nb, *o_inert = out + 2 * nb, *o_dof = out + 5 * nb, *o_body = out + 5 * nb + nv,
-	       *o_ten = out + 7 * nb + nv, *o_mean = out + 7 * nb + nv + nt;
-	for (int b = 0; b < nb; b++) {
-		o_mass[b] = body_mass[b];
-		o_sub[b] = body_mass[b];
-		for (int k = 0; k < 3; k++) o_inert[3 * b + k] = inertia[3 * b + k];
-		o_body[2 * b] = o_body[2 * b + 1] = 0;
-	}
-	for (int b = nb - 1; b > 0; b--) o_sub[h.body_parentid[b]] += o_sub[b];
-	for (int i = 0; i < nv; i++) o_dof[i] = 0;
-	for (int t = 0; t < nt; t++) o_ten[t] = 0;
-	*o_mean = 1.0;
-	if (nv == 0) return MJB_OK;
-	// kinematics at qpos0
-	std::vector<double> xpos(3 * nb, 0.0), xquat(4 * nb, 0.0), xmat(9 * nb, 0.0), xipos(3 * nb, 0.0), ximat(9 * nb, 0.0), xanchor(3 * std::max(1, nj), 0.0),
-	    xaxis(3 * std::max(1, nj), 0.0);
-	xquat[0] = 1;
-	SC::quat2mat(&xquat[0], &xmat[0]);
-	for (int b = 1; b < nb; b++) {
-		const int p = h.body_parentid[b], ja = h.body_jntadr[b], jn = h.body_jntnum[b];
-		double pos[3], q[4];
-		if (jn == 1 && h.jnt_type[ja] == MJB_JNT_FREE) {
-			const int qa = h.jnt_qposadr[ja];
-			double nrm = 0;
-			for (int k = 0; k < 4; k++) nrm += h.qpos0[qa + 3 + k] * h.qpos0[qa + 3 + k];
-			nrm = std::sqrt(nrm);
-			for (int k = 0; k < 3; k++) pos[k] = h.qpos0[qa + k];
-			for (int k = 0; k < 4; k++) q[k] = h.qpos0[qa + 3 + k] / nrm;
-			for (int k = 0; k < 3; k++) { xanchor[3 * ja + k] = pos[k]; xaxis[3 * ja + k] = h.jnt_axis[3 * ja + k]; }
-		} else {
-			double v[3];
-			SC::mv(&xmat[9 * p], &h.body_pos[3 * b], v);
-			for (int k = 0; k < 3; k++) pos[k] = xpos[3 * p + k] + v[k];
-			SC::qmul(&xquat[4 * p], &h.body_quat[4 * b], q);
-			for (int j = ja; j < ja + jn; j++) {
-				double R[9], w[3];
-				SC::quat2mat(q, R);
-				SC::mv(R, &h.jnt_axis[3 * j], &xaxis[3 * j]);
-				SC::mv(R, &h.jnt_pos[3 * j], w);
-				for (int k = 0; k < 3; k++) xanchor[3 * j + k] = pos[k] + w[k];
-				if (h.jnt_type[j] == MJB_JNT_BALL) {  // (hinge / slide sit at qpos0: no motion)
-					const int qa = h.jnt_qposadr[j];
-					double ql[4], nrm = 0;
-					for (int k = 0; k < 4; k++) nrm += h.qpos0[qa + k] * h.qpos0[qa + k];
-					nrm = std::sqrt(nrm);
-					for (int k = 0; k < 4; k++) ql[k] = h.qpos0[qa + k] / nrm;
-					SC::qmul(q, ql, q);
-					SC::quat2mat(q, R);
-					SC::mv(R, &h.jnt_pos[3 * j], w);
-					for (int k = 0; k < 3; k++) pos[k] = xanchor[3 * j + k] - w[k];
-				}
-			}
-		}
-		double nrm = std::sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
-		for (int k = 0; k < 3; k++) xpos[3 * b + k] = pos[k];
-		for (int k = 0; k < 4; k++) xquat[4 * b + k] = q[k] / nrm;
-		SC::quat2mat(&xquat[4 * b], &xmat[9 * b]);
-	}
-	for (int b = 0; b < nb; b++) {
-		double v[3], Ri[9];
-		SC::mv(&xmat[9 * b], &h.body_ipos[3 * b], v);
-		for (int k = 0; k < 3; k++) xipos[3 * b + k] = xpos[3 * b + k] + v[k];
-		SC::quat2mat(&h.body_iquat[4 * b], Ri);
-		for (int r = 0; r < 3; r++)
-			for (int c = 0; c < 3; c++) {
-				double a = 0;
-				for (int k = 0; k < 3; k++) a += xmat[9 * b + 3 * r + k] * Ri[3 * k + c];
-				ximat[9 * b + 3 * r + c] = a;
-			}
-	}
-	// Jacobians of a point fixed to `body` (3 x nv each)
-	auto jac = [&](int body, const double *point, std::vector<double> &jp, std::vector<double> &jr) {
-		std::fill(jp.begin(), jp.end(), 0.0);
-		std::fill(jr.begin(), jr.end(), 0.0);
-		for (int b = body; b > 0; b = h.body_parentid[b])
-			for (int j = h.body_jntadr[b]; j < h.body_jntadr[b] + h.body_jntnum[b]; j++) {
-				const int d = h.jnt_dofadr[j], t = h.jnt_type[j];
-				auto rot_dof = [&](int dof, const double *ax, const double *about) {
-					const double off[3] = { point[0] - about[0], point[1] - about[1], point[2] - about[2] };
-					double c[3];
-					SC::cross(ax, off, c);
-					for (int k = 0; k < 3; k++) { jr[(size_t)k * nv + dof] = ax[k]; jp[(size_t)k * nv + dof] = c[k]; }
-				};
-				if (t == MJB_JNT_HINGE) rot_dof(d, &xaxis[3 * j], &xanchor[3 * j]);
-				else if (t == MJB_JNT_SLIDE) for (int k = 0; k < 3; k++) jp[(size_t)k * nv + d] = xaxis[3 * j + k];
-				else {
-					const int r0 = t == MJB_JNT_FREE ? d + 3 : d;
-					if (t == MJB_JNT_FREE) for (int k = 0; k < 3; k++) jp[(size_t)k * nv + d + k] = 1.0;
-					for (int k = 0; k < 3; k++) {
-						const double ax[3] = { xmat[9 * b + k], xmat[9 * b + 3 + k], xmat[9 * b + 6 + k] };
-						rot_dof(r0 + k, ax, t == MJB_JNT_FREE ? &xpos[3 * b] : &xanchor[3 * j]);
-					}
-				}
-			}
-	};
-	std::vector<double> M((size_t)nv * nv, 0.0), jp((size_t)3 * nv), jr((size_t)3 * nv);
-	for (int i = 0; i < nv; i++) M[(size_t)i * nv + i] = armature[i];
-	for (int b = 1; b < nb; b++) {
-		const double mb = body_mass[b], *I = inertia + 3 * b;
-		if (mb == 0 && I[0] == 0 && I[1] == 0 && I[2] == 0) continue;
-		jac(b, &xipos[3 * b], jp, jr);
-		double Iw[9];  // R diag(I) R'
-		for (int r = 0; r < 3; r++)
-			for (int c = 0; c < 3; c++) {
-				double a = 0;
-				for (int k = 0; k < 3; k++) a += ximat[9 * b + 3 * r + k] * I[k] * ximat[9 * b + 3 * c + k];
-				Iw[3 * r + c] = a;
-			}
-		for (int i = 0; i < nv; i++)
-			for (int j = 0; j < nv; j++) {
-				double a = 0;
-				for (int k = 0; k < 3; k++) a += mb * jp[(size_t)k * nv + i] * jp[(size_t)k * nv + j];
-				for (int r = 0; r < 3; r++) {
-					double t = 0;
-					for (int c = 0; c < 3; c++) t += Iw[3 * r + c] * jr[(size_t)c * nv + j];
-					a += jr[(size_t)r * nv + i] * t;
-				}
-				M[(size_t)i * nv + j] += a;
-			}
-	}
-	double mean = 0;
-	for (int i = 0; i < nv; i++) mean += M[(size_t)i * nv + i];
-	*o_mean = mean / nv;
-	// M^-1 by Gauss-Jordan with partial pivoting (nv <= 64)
-	std::vector<double> A(M), Minv((size_t)nv * nv, 0.0);
-	for (int i = 0; i < nv; i++) Minv[(size_t)i * nv + i] = 1.0;
-	for (int c = 0; c < nv; c++) {
-		int piv = c;
-		for (int r = c + 1; r < nv; r++)
-			if (std::fabs(A[(size_t)r * nv + c]) > std::fabs(A[(size_t)piv * nv + c])) piv = r;
-		if (std::fabs(A[(size_t)piv * nv + c]) < 1e-300) return fail(MJB_EINVAL, "mjb_derive_mass_params: singular joint-space inertia (dof %d)", c);
-		if (piv != c)
-			for (int k = 0; k < nv; k++) { std::swap(A[(size_t)piv * nv + k], A[(size_t)c * nv + k]); std::swap(Minv[(size_t)piv * nv + k], Minv[(size_t)c * nv + k]); }
-		const double d = 1.0 / A[(size_t)c * nv + c];
-		for (int k = 0; k < nv; k++) { A[(size_t)c * nv + k] *= d; Minv[(size_t)c * nv + k] *= d; }
-		for (int r = 0; r < nv; r++) {
-			if (r == c) continue;
-			const double f = A[(size_t)r * nv + c];
-			if (f == 0) continue;
-			for (int k = 0; k < nv; k++) { A[(size_t)r * nv + k] -= f * A[(size_t)c * nv + k]; Minv[(size_t)r * nv + k] -= f * Minv[(size_t)c * nv + k]; }
-		}
-	}
-	auto quad = [&](const double *ja, const double *jb) {  // ja' M^-1 jb for two nv-vectors
-		double a = 0;
-		for (int i = 0; i < nv; i++) {
-			if (ja[i] == 0) continue;
-			double t = 0;
-			for (int j = 0; j < nv; j++) t += Minv[(size_t)i * nv + j] * jb[j];
-			a += ja[i] * t;
-		}
-		return a;
-	};
-	for (int b = 1; b < nb; b++) {
-		if (h.body_weldid[b] == 0) continue;
-		jac(b, &xipos[3 * b], jp, jr);
-		double tr = 0, ro = 0;
-		for (int k = 0; k < 3; k++) { tr += quad(&jp[(size_t)k * nv], &jp[(size_t)k * nv]); ro += quad(&jr[(size_t)k * nv], &jr[(size_t)k * nv]); }
-		o_body[2 * b] = tr / 3;
-		o_body[2 * b + 1] = ro / 3;
-	}
-	for (int j = 0; j < nj; j++) {
-		const int d = h.jnt_dofadr[j], t = h.jnt_type[j];
-		auto tr3 = [&](int a) { return (Minv[(size_t)a * nv + a] + Minv[(size_t)(a + 1) * nv + a + 1] + Minv[(size_t)(a + 2) * nv + a + 2]) / 3; };
-		if (t == MJB_JNT_HINGE || t == MJB_JNT_SLIDE) o_dof[d] = Minv[(size_t)d * nv + d];
-		else if (t == MJB_JNT_BALL) o_dof[d] = o_dof[d + 1] = o_dof[d + 2] = tr3(d);
-		else {
-			o_dof[d] = o_dof[d + 1] = o_dof[d + 2] = tr3(d);
-			o_dof[d + 3] = o_dof[d + 4] = o_dof[d + 5] = tr3(d + 3);
-		}
-	}
-	std::vector<double> jt((size_t)nv);
-	for (int t = 0; t < nt; t++) {
-		std::fill(jt.begin(), jt.end(), 0.0);
-		for (int w = h.tendon_adr[t]; w < h.tendon_adr[t] + h.tendon_num[t]; w++) jt[h.jnt_dofadr[h.wrap_objid[w]]] += h.wrap_prm[w];
-		o_ten[t] = quad(jt.data(), jt.data());
-	}
-	return MJB_OK;
-}
-
 int mjb_set_env_body_mass(mjb_batch *b, int env_lo, int env_hi, const double *body_mass, const double *body_inertia)
 {
 	if (!b || !body_mass) return fail(MJB_EINVAL, "mjb_set_env_body_mass: bad argument");
@@ -3657,12 +2098,6 @@ int mjb_set_env_body_mass(mjb_batch *b, int env_lo, int env_hi, const double *bo
 }
 
 // ---- per-env joint and actuator parameters ----
-int mjb_env_joint_stride(const mjb_model *m)
-{
-	if (!m) return fail(MJB_EINVAL, "null model");
-	return 3 * m->h.nv + m->h.njnt + 6 * m->h.nu;
-}
-
 // One implementation behind the four setters: every array is optional and comes with its own per-env stride (the packed form hands
 // over six views of one block).  Everything is checked before anything is written: a refused call leaves the batch as it was.
 static int env_joint_set(mjb_batch *b, int env_lo, int env_hi, const double *damping, const double *armature, const double *frictionloss,
