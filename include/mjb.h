@@ -639,6 +639,13 @@ int mjb_debug_profile_window(mjb_batch *b, int first_id);
  * [2] the three frame layouts, the field sizes and the frame residency, [3] the lane = env / split-step classification and tape.  Two models with
  * equal words were compiled alike; which word differs says where to look.  Needs no device.  No reference counterpart. */
 int mjb_debug_model_digest(const mjb_model *m, unsigned long long out[4]);
+/* Three such words over the device model blob a batch of the model would upload: [0] the offset of every table from the blob's base (16-byte
+ * aligned int tables, the lane = env tape on a 64-byte boundary: checked on the way, a broken promise is MJB_EINVAL), [1] the tables' contents,
+ * [2] the sizes, options and derived scalars the kernels read next to them.  Needs no device.  No reference counterpart. */
+int mjb_debug_blob_digest(const mjb_model *m, unsigned long long out[3]);
+/* How many device buffers, pinned host buffers, streams and events the library's batches hold right now, over all batches of the process: back at
+ * its earlier value once a batch is freed.  No reference counterpart. */
+int mjb_debug_live_resources(void);
 
 /* Timing helper for bench.py: run `nlaunch` launches of mjb_step(b, nsteps) bracketed by HIP
  * events recorded on the batch's stream; returns the mean per-launch duration in milliseconds

@@ -244,6 +244,8 @@ def load_library(path=None):
         "mjb_debug_profile": (ci, [vp, C.POINTER(C.c_uint64), ci]),
         "mjb_debug_profile_window": (ci, [vp, ci]),
         "mjb_debug_model_digest": (ci, [vp, C.POINTER(C.c_ulonglong)]),
+        "mjb_debug_blob_digest": (ci, [vp, C.POINTER(C.c_ulonglong)]),
+        "mjb_debug_live_resources": (ci, []),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)  # AttributeError if the library lacks a declared symbol

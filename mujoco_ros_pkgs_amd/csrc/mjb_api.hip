@@ -2,6 +2,7 @@
 // Owns batches: the device model blob, HBM state arrays, the launch policy and the launches, host<->device copies, the per-env parameter
 // setters, the device hwsim stage and the sensor messages, with the few small kernels they need.  The model itself -- mjb_compile, the frame
 // layouts, the getters that need no batch, mjb_derive_mass_params -- is mjb_model.hip's (struct mjb_model, fail(): mjb_model.h).
+// What a batch holds on the device is held through the owner types of mjb_resources.h: no raw allocation, stream or event call here.
 // No CPU compute path exists here: every compute entry point needs a HIP device.
 #include <hip/hip_runtime.h>
 
@@ -9,12 +10,14 @@
 #include <cmath>
 #include <cstdio>
 #include <cstring>
+#include <memory>
 #include <new>
 #include <string>
 #include <vector>
 
 #include "mjb_dev.h"
 #include "mjb_model.h"
+#include "mjb_resources.h"
 
 #define HIP_TRY(expr)                                                                                   \
 	do {                                                                                                \
@@ -22,107 +25,154 @@
 		if (_e != hipSuccess) return fail(MJB_ENODEVICE, "%s: %s", #expr, hipGetErrorString(_e));     \
 	} while (0)
 
+// Groups of resources that are created together, in one function each, and go together
+struct RestStream {  // mjb_step_rest: the fused launch of the non-callback envs runs beside the callback envs' second half
+	Stream stream;
+	Event fork, join;
+	int create();
+};
+struct NoiseStream {  // the NEXT launch's ctrl-noise normals are generated here while the current launch runs
+	Stream stream;
+	Event done, go;
+	int create();
+};
+struct HwSimBufs {  // device-side DefaultRobotHWSim (mjb_hwsim_*): what HwSim points into
+	DevBuf<int> ints;      // joint | method | kind | antiwindup, [4][n], then the same by dof [nv][4]
+	DevBuf<double> gains;  // [n][8], then by dof [nv][8]
+	DevBuf<double> cmd;    // pos | vel | eff | hold, [4][nenv][n]
+	DevBuf<double> pid;    // [nenv][n][2]
+	DevBuf<double> cad;    // [nenv][2 + 2 n] controller cadence (mjb_hwsim_set_period)
+};
+struct SensorBufs {  // sensors-plugin equivalent (mjb_sensor_*): device copy of the noise models and the packed messages
+	DevBuf<int> flag;
+	DevBuf<double> mean, sigma;
+	DevBuf<float> value, truth;
+	bool alloc(size_t nsensor, size_t ndata) { return flag.alloc_zeroed(nsensor) && mean.alloc_zeroed(3 * nsensor) && sigma.alloc_zeroed(3 * nsensor) && value.alloc_zeroed(ndata) && truth.alloc_zeroed(ndata); }
+};
+
+// Every stream, event and buffer below has ONE owner, here; DevState, HwSim and KernelParams::le_con hold the raw views the kernels read, installed by
+// set_view().  Members are destroyed in reverse order of declaration: the buffers are released first, then the side streams and the events, the batch's
+// own stream last (mjb_free_batch has drained them all by then).
 struct mjb_batch {
 	const mjb_model *model = nullptr;
 	int device = 0, nenv = 0;
-	void *blob = nullptr;  // device model blob
+	Stream stream;                // the batch's own, or the caller's (mjb_set_stream)
+	RestStream rest;
+	NoiseStream noise;
+	std::vector<Stream> split_streams;  // the split step's env slices
+	std::vector<Event> split_events;
+	Event ev_split_fork, ev_rowstat;
+	DevBuf<unsigned char> blob;   // device model blob
 	DevModel dm{};
 	DevState st{};
+	DevBuf<double> state[MJB_F_COUNT];  // the state fields' arrays (MJB_DS of include/mjb_data_fields.def; the other entries stay empty)
+	DevBuf<double> frame_ws, efc_Jg, pgs_B;
+	DevBuf<unsigned long long> nwarn, prof;
+	DevBuf<int> sched;
 	FrameLayout L{};
 	NoiseCfg nz{};
-	hipStream_t stream = nullptr;
-	bool own_stream = false;
 	int lanes = 0, epb = 0;
 	unsigned int step_counter = 0;
 	bool frame_valid = false;
 	int frame_hi = 0;             // the frame workspace is current for envs [0, frame_hi) (a prefix after mjb_step1_prefix)
 	int split_ncb = -1;           // inside a split step of this prefix (mjb_step1_prefix .. mjb_step2_prefix)
 	bool split_rest_done = false;
-	hipStream_t rest_stream = nullptr;  // the fused launch of the non-callback envs runs beside the callback envs' second half
-	hipEvent_t ev_fork = nullptr, ev_join = nullptr;
 	bool rest_pending = false;
 	// wide-frame policy of kernel variant 4 (launch()): counters of the last long fused launch -- env-steps, those beyond 64 rows, those
 	// beyond 128 -- copied to pinned host memory behind it; the next long launch waits for that copy (the launch has ended by then or is
 	// about to) and picks its frame from them: deterministic for a given sequence of launches
 	bool wide = false;
-	unsigned long long *rowstat_dev = nullptr, *rowstat_host = nullptr;  // (64-bit: envs x steps of one launch may exceed 2^32)
-	hipEvent_t ev_rowstat = nullptr;
+	DevBuf<unsigned long long> rowstat_dev;  // (64-bit: envs x steps of one launch may exceed 2^32)
+	PinnedBuf<unsigned long long> rowstat_host;
 	bool rowstat_pending = false;
 	bool rowstat_ever = false;     // a sample of the CURRENT workload has been looked at (cleared by mjb_reset / a new qpos: the next long launch probes first)
 	bool probe_now = false, decide_now = false;  // mjb_step's probe launch / the launch behind it (launch())
-	unsigned char *mask_dev = nullptr;
-	KernelParams *params_dev = nullptr;  // device copy of {dm, L, st, nz}
-	double *metrics_dev = nullptr;       // [16] mjb_metrics
-	unsigned long long *stats_dev = nullptr;  // [MJB_NSTATS] mjb_set_stats (st.stats points here while counting)
+	DevBuf<unsigned char> mask_dev;
+	DevBuf<KernelParams> params_dev;  // device copy of {dm, L, st, nz}
+	DevBuf<double> metrics_dev;       // [16] mjb_metrics
+	DevBuf<unsigned long long> stats_dev;  // [MJB_NSTATS] mjb_set_stats (st.stats points here while counting)
 	int *pair_i_dev = nullptr;           // device address of the per-pair int records inside the blob (mjb_register_collision patches them)
 	unsigned long long steps_taken = 0;  // steps since the batch was made (step_counter is the 32-bit Philox counter)
 	bool params_dirty = true;
 	// sensors-plugin equivalent (mjb_sensor_*): noise models (host mirror + device copy) and the packed messages
 	std::vector<int> sens_flag;
 	std::vector<double> sens_mean, sens_sigma;
-	int *sens_flag_dev = nullptr;
-	double *sens_mean_dev = nullptr, *sens_sigma_dev = nullptr;
-	float *sens_value = nullptr, *sens_truth = nullptr;
+	SensorBufs sens;
 	bool sens_dirty = true, sens_packed = false;
-	double *pack_dev = nullptr;          // staging block of mjb_get_packed / mjb_set_packed
+	DevBuf<double> pack_dev;          // staging block of mjb_get_packed / mjb_set_packed
 	size_t pack_cap = 0;
-	double *env_geom_size = nullptr;
-	int *env_geom_type = nullptr;
-	double *env_gravity = nullptr, *env_geom_friction = nullptr, *env_equality = nullptr, *env_mass = nullptr;  // per-env model parameter overrides (mjb_set_env_*)
+	DevBuf<double> env_geom_size;
+	DevBuf<int> env_geom_type;
+	DevBuf<double> env_gravity, env_geom_friction, env_equality, env_mass;  // per-env model parameter overrides (mjb_set_env_*)
 	std::vector<double> env_block;  // host mirror of env_mass, [nenv][mjb_env_block_doubles]: what an armature or mass change re-derives the env's mj_setConst constants from
 	// device-side DefaultRobotHWSim (mjb_hwsim_*)
 	HwSim hw{};
-	int *hw_ints = nullptr;        // joint | method | kind | antiwindup, [4][n]
-	double *hw_gains = nullptr;    // [n][8]
-	double *hw_cmd = nullptr;      // pos | vel | eff | hold, [4][nenv][n]
-	double *hw_pid = nullptr;      // [nenv][n][2]
-	double *hw_cad = nullptr;      // [nenv][2 + 2 n] controller cadence (mjb_hwsim_set_period)
-	double *zbuf = nullptr;        // pre-generated ctrl-noise normals of one fused launch (launch())
+	HwSimBufs hwb;
+	DevBuf<double> zbuf;           // pre-generated ctrl-noise normals of one fused launch (launch())
 	size_t zcap = 0;               // its capacity in doubles PER HALF
 	bool zdouble = false;          // two halves allocated (side-stream speculation possible)
 	size_t zfail = (size_t)-1;     // smallest total allocation (doubles) that failed: not retried
 	bool lane_env_hwsim = false;   // mjb_lane_env_set_hwsim: a batch with the device hwsim stage may run the lane = env kernel's HW build
 	bool hw_le_ok = false;         // the hwsim configuration has a per-dof table (HwSim::le_tab): no dof controlled by two entries
 	bool lane_env_xfrc = false;    // mjb_lane_env_set_xfrc: a batch whose xfrc_applied has been written may run the lane = env kernel's XF builds
-	double *le_xfrc = nullptr;     // their wrench table, [6 * mjb_lane_env_xfrc_slots][nenv] (DevState::le_xfrc), built at the first such launch
+	DevBuf<double> le_xfrc;        // their wrench table, [6 * mjb_lane_env_xfrc_slots][nenv] (DevState::le_xfrc), built at the first such launch
 	bool le_xfrc_stale = true;     // xfrc_applied has been written (or reset) since the table was last filled
 	int lane_env_mode = -1;        // mjb_set_lane_env: -1 automatic, 0 never, 1 whenever eligible, 2 whenever eligible, also with per-env gravity / parameter blocks
-	double *le_con = nullptr;      // lane = env kernel, a model with joint limits: qfrc_constraint | nefc | solver_iter of a launch's last step, [nenv][nv + 2] (KernelParams::le_con), allocated at the first such launch
+	DevBuf<double> le_con;         // lane = env kernel, a model with joint limits: qfrc_constraint | nefc | solver_iter of a launch's last step, [nenv][nv + 2] (KernelParams::le_con), allocated at the first such launch
 	bool le_con_valid = false;     // ... and the last launch was one: mjb_get / mjb_get_int serve those three fields from it
-	double *le_overlay = nullptr;  // mode 2: the per-env overlay of the lane = env kernel, [mjb_lane_env_overlay_slots][nenv] (DevState::le_overlay), built at the first such launch
+	DevBuf<double> le_overlay;     // mode 2: the per-env overlay of the lane = env kernel, [mjb_lane_env_overlay_slots][nenv] (DevState::le_overlay), built at the first such launch
 	int le_ov_lo = 0, le_ov_hi = 0;  // envs [lo, hi) whose overlay columns a setter has outdated since (empty: lo >= hi)
 	// the split step (mjb_set_split_step): smooth half in lane = env form + constraint half per wavefront, alternating on a few streams of env slices
 	int split_mode = -1;           // -1 automatic (whole-batch fused launches of >= MJB_SPLIT_MIN_ENVS envs), 0 never, 1 whenever eligible
 	bool split_used = false;       // the last fused launch ran that way
 	int split_slices_last = 0;
-	std::vector<hipStream_t> split_streams;
-	std::vector<hipEvent_t> split_events;
-	hipEvent_t ev_split_fork = nullptr;
-	double *handoff_dev = nullptr; // DevState::handoff
-	double *reset_step_dev = nullptr;  // DevState::reset_step
+	DevBuf<double> handoff_dev;    // DevState::handoff
+	DevBuf<double> reset_step_dev; // DevState::reset_step
 	bool lane_env_used = false;    // the last fused launch ran the lane = env kernel
 	bool le_unavailable = false;   // the model's topology had to be built by hiprtc and that failed (mjb_lane_env_jit_error): generic kernels from then on
 	int noise_mode = 0;            // how the last fused launch got its ctrl-noise normals: 0 in-kernel, 1 same-stream, 2 side-stream (mjb_noise_mode)
-	unsigned int *zinfo = nullptr; // two records (one per half of zbuf)
+	DevBuf<unsigned int> zinfo;    // two records (one per half of zbuf)
 	bool zvalid = false;           // a record names a launch: cleared (on the stream) before any step launch that does not use the buffer
-	hipStream_t noise_stream = nullptr;  // the NEXT launch's normals are generated here while the current launch runs
-	hipEvent_t ev_noise = nullptr, ev_noise_go = nullptr;
-	bool spec_valid = false;       // half `spec_half` holds (or will, once ev_noise fires) the normals of launch (spec_step0, spec_nsteps)
+	bool spec_valid = false;       // half `spec_half` holds (or will, once noise.done fires) the normals of launch (spec_step0, spec_nsteps)
 	int spec_half = 0, spec_nsteps = 0;
 	unsigned int spec_step0 = 0;
 };
 
 namespace {
 
-template <typename T> T *dev_alloc(size_t n)
+// the kernels' raw view of one of the batch's buffers (a member of b->st or b->hw): assigned here, so that the parameter block is uploaded again
+template <typename V, typename P> void set_view(mjb_batch *b, V &view, P p)
 {
-	void *p = nullptr;
-	if (hipMalloc(&p, (n ? n : 1) * sizeof(T)) != hipSuccess) return nullptr;
-	hipMemset(p, 0, (n ? n : 1) * sizeof(T));
-	return static_cast<T *>(p);
+	view = p;
+	b->params_dirty = true;
 }
 
+struct BatchDeleter {
+	void operator()(mjb_batch *b) const { mjb_free_batch(b); }
+};
+typedef std::unique_ptr<mjb_batch, BatchDeleter> BatchPtr;
+
 }  // namespace
+
+// (all three or none: a group that exists is whole)
+int RestStream::create()
+{
+	hipError_t e = stream.create();
+	if (e == hipSuccess) e = fork.create();
+	if (e == hipSuccess) e = join.create();
+	if (e == hipSuccess) return MJB_OK;
+	*this = RestStream{};
+	return fail(MJB_ENODEVICE, "rest stream: %s", hipGetErrorString(e));
+}
+int NoiseStream::create()
+{
+	hipError_t e = stream.create();
+	if (e == hipSuccess) e = done.create();
+	if (e == hipSuccess) e = go.create();
+	if (e == hipSuccess) return MJB_OK;
+	*this = NoiseStream{};
+	return fail(MJB_ENODEVICE, "noise stream: %s", hipGetErrorString(e));
+}
 
 extern "C" {
 
@@ -136,76 +186,115 @@ int mjb_device_count(void)
 	return n;
 }
 
+int mjb_debug_live_resources(void) { return g_live_resources.load(); }
+
 void mjb_free_batch(mjb_batch *b)
 {
 	if (!b) return;
 	hipSetDevice(b->device);
-	if (b->stream) hipStreamSynchronize(b->stream);
-#define MJB_DS(name, rows, cols) if (b->st.name) hipFree(b->st.name);
-#define MJB_DD(name, rows, cols)
-#define MJB_DD2(name, rows, cols)
-#define MJB_DI(name, rows, cols)
+	if (b->stream.get()) hipStreamSynchronize(b->stream.get());
+	if (b->rest.stream.get()) hipStreamSynchronize(b->rest.stream.get());
+	if (b->noise.stream.get()) hipStreamSynchronize(b->noise.stream.get());
+	for (const Stream &st : b->split_streams) hipStreamSynchronize(st.get());
+	delete b;
+}
+
+}  // extern "C"
+
+// ---- mjb_make_batch, step by step: each returns false after fail()
+static bool batch_check_device(int device)
+{
+	const int ndev = mjb_device_count();
+	if (ndev <= 0) return fail(MJB_ENODEVICE, "mjb_make_batch: no HIP device available (this engine has no CPU fallback)"), false;
+	if (device < 0 || device >= ndev) return fail(MJB_EINVAL, "mjb_make_batch: device %d out of range (%d devices)", device, ndev), false;
+	if (hipSetDevice(device) != hipSuccess) return fail(MJB_ENODEVICE, "mjb_make_batch: hipSetDevice(%d) failed", device), false;
+	return true;
+}
+
+// the model blob (build_model_blob, mjb_model.hip) as it stands, and the DevModel that points into it
+static bool batch_upload_model(mjb_batch *b)
+{
+	ModelBlob B = build_model_blob(*b->model);
+	if (!b->blob.alloc(B.image.size())) return fail(MJB_ENOMEM, "mjb_make_batch: hipMalloc(model blob) failed"), false;  // (the upload writes all of it)
+	if (hipMemcpy(b->blob.get(), B.image.data(), B.image.size(), hipMemcpyHostToDevice) != hipSuccess) return fail(MJB_ENODEVICE, "mjb_make_batch: model upload failed"), false;
+	b->dm = B.dm;
+	rebase_model_blob(*b->model, b->dm, b->blob.get());
+	b->pair_i_dev = reinterpret_cast<int *>(b->blob.get() + B.pair_i_offset);
+	return true;
+}
+
+static bool batch_alloc_state(mjb_batch *b)
+{
+	const mjb_model *M = b->model;
+	DevState &s = b->st;
+	s.nenv = b->nenv;
+	bool ok = true;
+	int fidx = 0;
+#define MJB_DS(name, rows, cols)                                                                       \
+	ok = ok && b->state[fidx].alloc_zeroed((size_t)b->nenv * M->field_size[fidx]);                     \
+	s.name = b->state[fidx].get();                                                                     \
+	fidx++;
+#define MJB_DD(name, rows, cols) fidx++;
+#define MJB_DD2(name, rows, cols) fidx++;
+#define MJB_DI(name, rows, cols) fidx++;
 #include "../../include/mjb_data_fields.def"
 #undef MJB_DS
 #undef MJB_DD
 #undef MJB_DD2
 #undef MJB_DI
-	if (b->st.frame_ws) hipFree(b->st.frame_ws);
-	if (b->st.nwarn) hipFree(b->st.nwarn);
-	if (b->stats_dev) hipFree(b->stats_dev);
-	if (b->st.pgs_B) hipFree(b->st.pgs_B);
-	if (b->st.efc_Jg) hipFree(b->st.efc_Jg);
-	if (b->rowstat_dev) hipFree(b->rowstat_dev);
-	if (b->handoff_dev) hipFree(b->handoff_dev);
-	if (b->reset_step_dev) hipFree(b->reset_step_dev);
-	for (hipStream_t st : b->split_streams) hipStreamDestroy(st);
-	for (hipEvent_t ev : b->split_events) hipEventDestroy(ev);
-	if (b->ev_split_fork) hipEventDestroy(b->ev_split_fork);
-	if (b->rowstat_host) hipHostFree(b->rowstat_host);
-	if (b->ev_rowstat) hipEventDestroy(b->ev_rowstat);
-	if (b->pack_dev) hipFree(b->pack_dev);
-	if (b->rest_stream) {
-		hipStreamSynchronize(b->rest_stream);
-		hipStreamDestroy(b->rest_stream);
-		hipEventDestroy(b->ev_fork);
-		hipEventDestroy(b->ev_join);
-	}
-	if (b->st.sched) hipFree(b->st.sched);
-	if (b->metrics_dev) hipFree(b->metrics_dev);
-	if (b->st.prof) hipFree(b->st.prof);
-	if (b->blob) hipFree(b->blob);
-	if (b->mask_dev) hipFree(b->mask_dev);
-	if (b->params_dev) hipFree(b->params_dev);
-	if (b->env_gravity) hipFree(b->env_gravity);
-	if (b->env_geom_friction) hipFree(b->env_geom_friction);
-	if (b->env_geom_size) hipFree(b->env_geom_size);
-	if (b->env_geom_type) hipFree(b->env_geom_type);
-	if (b->env_equality) hipFree(b->env_equality);
-	if (b->env_mass) hipFree(b->env_mass);
-	if (b->le_overlay) hipFree(b->le_overlay);
-	if (b->le_xfrc) hipFree(b->le_xfrc);
-	if (b->le_con) hipFree(b->le_con);
-	if (b->hw_ints) hipFree(b->hw_ints);
-	if (b->hw_gains) hipFree(b->hw_gains);
-	if (b->hw_cmd) hipFree(b->hw_cmd);
-	if (b->hw_pid) hipFree(b->hw_pid);
-	if (b->hw_cad) hipFree(b->hw_cad);
-	if (b->noise_stream) {
-		hipStreamSynchronize(b->noise_stream);
-		hipStreamDestroy(b->noise_stream);
-		hipEventDestroy(b->ev_noise);
-		hipEventDestroy(b->ev_noise_go);
-	}
-	if (b->zbuf) hipFree(b->zbuf);
-	if (b->zinfo) hipFree(b->zinfo);
-	if (b->sens_flag_dev) hipFree(b->sens_flag_dev);
-	if (b->sens_mean_dev) hipFree(b->sens_mean_dev);
-	if (b->sens_sigma_dev) hipFree(b->sens_sigma_dev);
-	if (b->sens_value) hipFree(b->sens_value);
-	if (b->sens_truth) hipFree(b->sens_truth);
-	if (b->own_stream && b->stream) hipStreamDestroy(b->stream);
-	delete b;
+	ok = ok && b->nwarn.alloc_zeroed(MJB_NWARNING) && b->prof.alloc_zeroed(64);
+	s.nwarn = b->nwarn.get();
+	s.prof = b->prof.get();
+	s.frame_stride = b->L.ndouble + b->L.nint / 2;
+	if (M->slot) s.frame_stride = std::max(s.frame_stride, M->Lc.ndouble + M->Lc.nint / 2);  // (row-slot kernels: fused frames in HBM live there too)
+	for (int k = 0; k < 64; k++) s.colfunc[k] = MJB_COLFUNC_DEFAULT;
+	if (!ok) fail(MJB_ENOMEM, "mjb_make_batch: hipMalloc(state) failed for %d envs", b->nenv);
+	return ok;
 }
+
+// what the model's solver needs beside the frames
+static bool batch_alloc_solver_scratch(mjb_batch *b)
+{
+	const mjb_model *M = b->model;
+	const mjb_model_desc &h = M->h;
+	const int nenv = b->nenv;
+	DevState &s = b->st;
+	bool ok = true;
+	if (h.nefcmax > 0) {  // constrained kernels: work queue of the chunked fused launches
+		ok = ok && b->sched.alloc_zeroed((size_t)nenv + 1);
+		s.sched = b->sched.get();
+	}
+	if (M->hbm_full) {  // row-slot kernels: launches on the full frame (and on the fused one, when it is too large too) run in the workspace
+		ok = ok && b->frame_ws.alloc_zeroed((size_t)nenv * s.frame_stride);
+		s.frame_ws = b->frame_ws.get();
+	}
+	if (h.solver == MJB_SOL_NEWTON && h.nefcmax > 128 && !M->slot) {  // kernel variant 4: row data of the env-steps beyond the fused frame's 64 rows
+		// (stride: the kernels index the block with the cone-block stride of the frame THEY run on -- the wide frame of an all-condim-3 model has
+		//  hcs 16 where the default frame has 10 (ADVICE r05): size for the largest of the three layouts)
+		s.efc_Jg_stride = mjb_rowblock_doubles(h.nefcmax, h.nv, h.nconmax, std::max(M->L.hcs, std::max(M->Lc.hcs, M->Lw.hcs)));
+		ok = ok && b->efc_Jg.alloc_zeroed((size_t)nenv * s.efc_Jg_stride);
+		s.efc_Jg = b->efc_Jg.get();
+		if (M->has_wide)  // row counters of the wide-frame policy (launch(), which points DevState::rowstat at them for the launches that count)
+			ok = ok && b->rowstat_dev.alloc_zeroed(4) && b->rowstat_host.alloc_zeroed(4) && b->ev_rowstat.create() == hipSuccess;
+	}
+	if (h.solver == MJB_SOL_PGS && h.nv <= 16 && h.nefcmax > 64) {
+		ok = ok && b->pgs_B.alloc_zeroed((size_t)nenv * h.nefcmax * h.nv);  // (elliptic PGS never exceeds 64 rows: mjb_compile)
+		s.pgs_B = b->pgs_B.get();
+	}
+	if (!ok) fail(MJB_ENOMEM, "mjb_make_batch: hipMalloc(state) failed for %d envs", nenv);
+	return ok;
+}
+
+static bool batch_create_stream(mjb_batch *b)
+{
+	if (b->stream.create() != hipSuccess) return fail(MJB_ENODEVICE, "mjb_make_batch: hipStreamCreate failed"), false;
+	mjb_set_launch(b, 0, 0);
+	return true;
+}
+
+static bool batch_first_reset(mjb_batch *b) { return mjb_reset(b, nullptr) == MJB_OK && mjb_synchronize(b) == MJB_OK; }
+
+extern "C" {
 
 mjb_batch *mjb_make_batch(const mjb_model *M, int nenv, int device)
 {
@@ -213,20 +302,8 @@ mjb_batch *mjb_make_batch(const mjb_model *M, int nenv, int device)
 		fail(MJB_EINVAL, "mjb_make_batch: bad argument");
 		return nullptr;
 	}
-	int ndev = mjb_device_count();
-	if (ndev <= 0) {
-		fail(MJB_ENODEVICE, "mjb_make_batch: no HIP device available (this engine has no CPU fallback)");
-		return nullptr;
-	}
-	if (device < 0 || device >= ndev) {
-		fail(MJB_EINVAL, "mjb_make_batch: device %d out of range (%d devices)", device, ndev);
-		return nullptr;
-	}
-	if (hipSetDevice(device) != hipSuccess) {
-		fail(MJB_ENODEVICE, "mjb_make_batch: hipSetDevice(%d) failed", device);
-		return nullptr;
-	}
-	mjb_batch *b = new (std::nothrow) mjb_batch;
+	if (!batch_check_device(device)) return nullptr;
+	BatchPtr b(new (std::nothrow) mjb_batch);
 	if (!b) {
 		fail(MJB_ENOMEM, "mjb_make_batch: out of memory");
 		return nullptr;
@@ -239,215 +316,10 @@ mjb_batch *mjb_make_batch(const mjb_model *M, int nenv, int device)
 		const int k = atoi(v);
 		if (k >= -1 && k <= 2) b->lane_env_mode = k;
 	}
-	const mjb_model_desc &h = M->h;
-	// ---- device model blob: [ints | doubles | derived int tables]
-	size_t ni = M->hint.size(), nd = M->hdbl.size();
-	size_t nt = M->M_rowdof.size() + M->M_coldof.size() + M->dof_depth.size() + M->dof_jstart.size() +
-	            M->body_rec.size() + M->body_rec2.size() + M->dof_rec.size() + M->fac_ops.size() + M->fac_beg.size() +
-	            M->body_dofmask.size() + M->body_submask.size() + M->M_dense.size() + M->M_sym.size() + M->body_anc.size() + M->dof_bodymask.size() + M->body_dofanc.size() + M->dof_rec2.size() + M->jnt_rec.size() + M->flv_hdr.size() + M->flv_rec.size() + M->flv_ent.size() + M->sens_copy.size() + M->sens_slow.size() + M->dof_act_adr.size() +
-	            M->dof_act_id.size() + M->pair_i.size() + M->lim_i.size() + M->site_act.size() + M->gravcomp_body.size() + 112;
-	size_t bytes_i = ((ni + nt) * sizeof(int) + 15) & ~size_t(15);
-	// (the lane = env tape starts on a 64-byte boundary of the blob: wide scalar loads)
-	const size_t o_damp = nd + M->pair_d.size() + M->lim_d.size() + M->sub_S.size();
-	const size_t o_mom = o_damp + M->damp_int.size();
-	size_t o_tape = o_mom + M->dof_act_mom.size();
-	while ((bytes_i + o_tape * sizeof(double)) % 64) o_tape++;
-	size_t bytes = bytes_i + (o_tape + M->le_tape.size()) * sizeof(double) + 16;
-	if (hipMalloc(&b->blob, bytes) != hipSuccess) {
-		fail(MJB_ENOMEM, "mjb_make_batch: hipMalloc(model blob) failed");
-		mjb_free_batch(b);
+	if (!batch_upload_model(b.get()) || !batch_alloc_state(b.get()) || !batch_alloc_solver_scratch(b.get()) || !batch_create_stream(b.get()) || !batch_first_reset(b.get()))
 		return nullptr;
-	}
-	std::vector<unsigned char> hostblob(bytes, 0);
-	int *hi = reinterpret_cast<int *>(hostblob.data());
-	double *hd = reinterpret_cast<double *>(hostblob.data() + bytes_i);
-	if (ni) memcpy(hi, M->hint.data(), ni * sizeof(int));
-	size_t t0 = ni;
-	auto put = [&](const std::vector<int> &v) {
-		t0 = (t0 + 3) & ~size_t(3);  // 16-byte aligned tables (wide scalar loads)
-		size_t at = t0;
-		if (!v.empty()) memcpy(hi + t0, v.data(), v.size() * sizeof(int));
-		t0 += v.size();
-		return at;
-	};
-	size_t o_row = put(M->M_rowdof), o_col = put(M->M_coldof), o_dep = put(M->dof_depth), o_js = put(M->dof_jstart);
-	size_t o_br = put(M->body_rec), o_br2 = put(M->body_rec2), o_dr = put(M->dof_rec), o_fo = put(M->fac_ops),
-	       o_fb = put(M->fac_beg), o_dm = put(M->body_dofmask), o_sm = put(M->body_submask), o_md = put(M->M_dense), o_ms = put(M->M_sym), o_an = put(M->body_anc), o_db = put(M->dof_bodymask), o_sc = put(M->sens_copy), o_ss = put(M->sens_slow),
-	       o_aa = put(M->dof_act_adr), o_ai = put(M->dof_act_id), o_pi = put(M->pair_i), o_li = put(M->lim_i), o_da = put(M->body_dofanc), o_dr2 = put(M->dof_rec2), o_jr = put(M->jnt_rec), o_fh = put(M->flv_hdr), o_fr = put(M->flv_rec), o_fe = put(M->flv_ent), o_sa = put(M->site_act), o_gc = put(M->gravcomp_body);
-	if (nd) memcpy(hd, M->hdbl.data(), nd * sizeof(double));
-	memcpy(hd + nd, M->pair_d.data(), M->pair_d.size() * sizeof(double));
-	memcpy(hd + nd + M->pair_d.size(), M->lim_d.data(), M->lim_d.size() * sizeof(double));
-	memcpy(hd + nd + M->pair_d.size() + M->lim_d.size(), M->sub_S.data(), M->sub_S.size() * sizeof(double));
-	if (!M->damp_int.empty()) memcpy(hd + o_damp, M->damp_int.data(), M->damp_int.size() * sizeof(double));
-	if (!M->dof_act_mom.empty()) memcpy(hd + o_mom, M->dof_act_mom.data(), M->dof_act_mom.size() * sizeof(double));
-	if (!M->le_tape.empty()) memcpy(hd + o_tape, M->le_tape.data(), M->le_tape.size() * sizeof(double));
-	if (hipMemcpy(b->blob, hostblob.data(), bytes, hipMemcpyHostToDevice) != hipSuccess) {
-		fail(MJB_ENODEVICE, "mjb_make_batch: model upload failed");
-		mjb_free_batch(b);
-		return nullptr;
-	}
-	int *di = reinterpret_cast<int *>(b->blob);
-	double *dd = reinterpret_cast<double *>(reinterpret_cast<unsigned char *>(b->blob) + bytes_i);
-	DevModel &dm = b->dm;
-	{
-		size_t ii = 0, dj = 0;
-#define MJB_SIZE(name) dm.name = h.name;
-#define MJB_OPT_I(name) dm.name = h.name;
-#define MJB_OPT_D(name, n) for (int k = 0; k < n; k++) dm.name[k] = h.name[k];
-#define MJB_ARR_I(name, rows, cols) dm.name = (mjb_ciptr)(di + M->ioff[ii++]);
-#define MJB_ARR_D(name, rows, cols) dm.name = (mjb_cdptr)(dd + M->doff[dj++]);
-#include "../../include/mjb_model_fields.def"
-#undef MJB_SIZE
-#undef MJB_OPT_I
-#undef MJB_OPT_D
-#undef MJB_ARR_I
-#undef MJB_ARR_D
-	}
-	dm.M_rowdof = (mjb_ciptr)(di + o_row);
-	dm.M_coldof = (mjb_ciptr)(di + o_col);
-	dm.dof_depth = (mjb_ciptr)(di + o_dep);
-	dm.dof_jstart = (mjb_ciptr)(di + o_js);
-	dm.body_rec = (mjb_ciptr)(di + o_br);
-	dm.body_rec2 = (mjb_ciptr)(di + o_br2);
-	dm.dof_rec = (mjb_ciptr)(di + o_dr);
-	dm.fac_ops = (mjb_ciptr)(di + o_fo);
-	dm.fac_beg = (mjb_ciptr)(di + o_fb);
-	dm.body_dofmask = (mjb_ciptr)(di + o_dm);
-	dm.body_submask = (mjb_ciptr)(di + o_sm);
-	dm.M_dense = (mjb_ciptr)(di + o_md);
-	dm.M_sym = (mjb_ciptr)(di + o_ms);
-	dm.body_anc = (mjb_ciptr)(di + o_an);
-	dm.kin_rounds = M->kin_rounds;
-	dm.body_dofanc = (mjb_ciptr)(di + o_da);
-	dm.dofanc_max = M->dofanc_max;
-	dm.dof_rec2 = (mjb_ciptr)(di + o_dr2);
-	dm.jnt_rec = (mjb_ciptr)(di + o_jr);
-	dm.flv_hdr = (mjb_ciptr)(di + o_fh);
-	dm.flv_rec = (mjb_ciptr)(di + o_fr);
-	dm.flv_n = M->flv_n;
-	dm.flv_ent = (mjb_ciptr)(di + o_fe);
-	dm.dof_bodymask = (mjb_ciptr)(di + o_db);
-	dm.need_rnepost = M->need_rnepost;
-	dm.sens_copy = (mjb_ciptr)(di + o_sc);
-	dm.sens_slow = (mjb_ciptr)(di + o_ss);
-	dm.dof_act_adr = (mjb_ciptr)(di + o_aa);
-	dm.dof_act_id = (mjb_ciptr)(di + o_ai);
-	dm.pair_i = (mjb_ciptr)(di + o_pi);
-	b->pair_i_dev = di + o_pi;
-	dm.pair_d = (mjb_cdptr)(dd + nd);
-	dm.lim_d = (mjb_cdptr)(dd + nd + M->pair_d.size());
-	dm.sub_S = (mjb_cdptr)(dd + nd + M->pair_d.size() + M->lim_d.size());
-	dm.dof_damping_int = (mjb_cdptr)(dd + o_damp);
-	dm.dof_act_mom = (mjb_cdptr)(dd + o_mom);
-	dm.act_tendon = M->act_tendon;
-	dm.site_act = (mjb_ciptr)(di + o_sa);
-	dm.nsite_act = (int)M->site_act.size();
-	dm.gravcomp_body = (mjb_ciptr)(di + o_gc);
-	dm.ngravcomp = (int)M->gravcomp_body.size();
-	dm.sub_nt = M->sub_nt;
-	dm.le_tape = M->le_tape.empty() ? (mjb_cdptr) nullptr : (mjb_cdptr)(dd + o_tape);
-	dm.lim_i = (mjb_ciptr)(di + o_li);
-	for (int k = 0; k < 3; k++) {
-		dm.sens_ncopy[k] = M->sens_ncopy[k];
-		dm.sens_nslow[k] = M->sens_nslow[k];
-	}
-	dm.sens_ncopy_max = M->sens_ncopy_max ? M->sens_ncopy_max : 1;
-	dm.eulerdamp = M->eulerdamp;
-	dm.nfriction = M->nfriction;
-	dm.maxdepth = M->maxdepth;
-
-	// ---- state arrays
-	DevState &s = b->st;
-	s.nenv = nenv;
-	bool ok = true;
-	int fidx = 0;
-#define MJB_DS(name, rows, cols)                                                        \
-	s.name = dev_alloc<double>((size_t)nenv * M->field_size[fidx]);                     \
-	ok = ok && s.name;                                                                  \
-	fidx++;
-#define MJB_DD(name, rows, cols) fidx++;
-#define MJB_DD2(name, rows, cols) fidx++;
-#define MJB_DI(name, rows, cols) fidx++;
-#include "../../include/mjb_data_fields.def"
-#undef MJB_DS
-#undef MJB_DD
-#undef MJB_DD2
-#undef MJB_DI
-	s.nwarn = dev_alloc<unsigned long long>(MJB_NWARNING);
-	ok = ok && s.nwarn;
-	s.stats = nullptr;
-	s.prof = dev_alloc<unsigned long long>(64);
-	ok = ok && s.prof;
-	s.frame_ws = nullptr;
-	s.frame_stride = b->L.ndouble + b->L.nint / 2;
-	if (M->slot) s.frame_stride = std::max(s.frame_stride, M->Lc.ndouble + M->Lc.nint / 2);  // (row-slot kernels: fused frames in HBM live there too)
-	s.use_xfrc = 0;
-	s.env_gravity = nullptr;
-	s.env_geom_friction = nullptr;
-	s.env_geom_size = nullptr;
-	s.env_geom_type = nullptr;
-	s.env_equality = nullptr;
-	s.env_mass = nullptr;
-	s.pgs_B = nullptr;
-	s.efc_Jg = nullptr;
-	s.efc_Jg_stride = 0;
-	s.handoff = nullptr;
-	s.handoff_stride = 0;
-	s.reset_step = nullptr;
-	s.le_overlay = nullptr;
-	s.le_xfrc = nullptr;
-	s.sens_every_step = 0;
-	for (int k = 0; k < 64; k++) s.colfunc[k] = MJB_COLFUNC_DEFAULT;
-	s.sched = nullptr;
-	if (h.nefcmax > 0) {  // constrained kernels: work queue of the chunked fused launches
-		s.sched = dev_alloc<int>((size_t)nenv + 1);
-		ok = ok && s.sched;
-	}
-	if (M->hbm_full) {  // row-slot kernels: launches on the full frame (and on the fused one, when it is too large too) run in the workspace
-		s.frame_ws = dev_alloc<double>((size_t)nenv * s.frame_stride);
-		ok = ok && s.frame_ws;
-	}
-	if (h.solver == MJB_SOL_NEWTON && h.nefcmax > 128 && !M->slot) {  // kernel variant 4: row data of the env-steps beyond the fused frame's 64 rows
-		// (stride: the kernels index the block with the cone-block stride of the frame THEY run on -- the wide frame of an all-condim-3 model has
-		//  hcs 16 where the default frame has 10 (ADVICE r05): size for the largest of the three layouts)
-		s.efc_Jg_stride = mjb_rowblock_doubles(h.nefcmax, h.nv, h.nconmax, std::max(M->L.hcs, std::max(M->Lc.hcs, M->Lw.hcs)));
-		s.efc_Jg = dev_alloc<double>((size_t)nenv * s.efc_Jg_stride);
-		ok = ok && s.efc_Jg;
-		if (M->has_wide) {  // row counters of the wide-frame policy (launch())
-			b->rowstat_dev = dev_alloc<unsigned long long>(4);
-			ok = ok && b->rowstat_dev && hipHostMalloc((void **)&b->rowstat_host, 4 * sizeof(unsigned long long), hipHostMallocDefault) == hipSuccess &&
-			     hipEventCreateWithFlags(&b->ev_rowstat, hipEventDisableTiming) == hipSuccess;
-			if (ok) {
-				memset(b->rowstat_host, 0, 4 * sizeof(unsigned long long));
-				ok = hipMemset(b->rowstat_dev, 0, 4 * sizeof(unsigned long long)) == hipSuccess;
-			}
-		}
-	}
-	s.rowstat = nullptr;  // (set by launch() for the launches that count)
-	if (h.solver == MJB_SOL_PGS && h.nv <= 16 && h.nefcmax > 64) {
-		s.pgs_B = dev_alloc<double>((size_t)nenv * h.nefcmax * h.nv);  // (elliptic PGS never exceeds 64 rows: mjb_compile)
-		ok = ok && s.pgs_B;
-	}
-	s.keep_frame = 0;
-	s.prof_base = 0;
-	if (!ok) {
-		fail(MJB_ENOMEM, "mjb_make_batch: hipMalloc(state) failed for %d envs", nenv);
-		mjb_free_batch(b);
-		return nullptr;
-	}
-	if (hipStreamCreateWithFlags(&b->stream, hipStreamNonBlocking) != hipSuccess) {
-		fail(MJB_ENODEVICE, "mjb_make_batch: hipStreamCreate failed");
-		mjb_free_batch(b);
-		return nullptr;
-	}
-	b->own_stream = true;
-	mjb_set_launch(b, 0, 0);
-	if (mjb_reset(b, nullptr) != MJB_OK || mjb_synchronize(b) != MJB_OK) {
-		mjb_free_batch(b);
-		return nullptr;
-	}
 	clear_error();
-	return b;
+	return b.release();
 }
 
 int mjb_nenv(const mjb_batch *b) { return b ? b->nenv : fail(MJB_EINVAL, "null batch"); }
@@ -470,10 +342,9 @@ int mjb_set_launch(mjb_batch *b, int lanes_per_env, int envs_per_block)
 
 static int ensure_ws(mjb_batch *b)
 {
-	if (b->st.frame_ws) return MJB_OK;
-	b->st.frame_ws = dev_alloc<double>((size_t)b->nenv * b->st.frame_stride);
-	if (!b->st.frame_ws) return fail(MJB_ENOMEM, "frame workspace allocation failed");
-	b->params_dirty = true;
+	if (b->frame_ws) return MJB_OK;
+	if (!b->frame_ws.alloc_zeroed((size_t)b->nenv * b->st.frame_stride)) return fail(MJB_ENOMEM, "frame workspace allocation failed");
+	set_view(b, b->st.frame_ws, b->frame_ws.get());
 	return MJB_OK;
 }
 
@@ -481,7 +352,7 @@ static int ensure_ws(mjb_batch *b)
 static int sync_params(mjb_batch *b)
 {
 	if (!b->params_dev) {
-		HIP_TRY(hipMalloc((void **)&b->params_dev, sizeof(KernelParams)));
+		if (!b->params_dev.alloc(1)) return fail(MJB_ENOMEM, "launch parameters: allocation failed");  // (uploaded whole below)
 		b->params_dirty = true;
 	}
 	if (b->params_dirty) {
@@ -494,15 +365,15 @@ static int sync_params(mjb_batch *b)
 		kp.s = b->st;
 		kp.nz = b->nz;
 		kp.hw = b->hw;
-		kp.le_con = b->le_con;
+		kp.le_con = b->le_con.get();
 		// pageable source: the copy is staged before the call returns, so the local may go out of scope
-		HIP_TRY(hipStreamSynchronize(b->stream));
+		HIP_TRY(hipStreamSynchronize(b->stream.get()));
 		// (the fused launch of the non-callback envs, mjb_step_rest, runs on its own non-blocking stream and reads *params_dev lazily
 		//  through scalar loads -- use_compact, use_xfrc, the layouts: an upload between mjb_step_rest and the second half, e.g. the
 		//  first pushViews that carries a non-zero xfrc_applied, must not overtake it)
-		if (b->rest_pending && b->rest_stream) HIP_TRY(hipStreamSynchronize(b->rest_stream));
-		if (b->spec_valid && b->noise_stream) HIP_TRY(hipStreamSynchronize(b->noise_stream));  // (the side-stream noise generator reads nz)
-		HIP_TRY(hipMemcpy(b->params_dev, &kp, sizeof kp, hipMemcpyHostToDevice));
+		if (b->rest_pending && b->rest.stream.get()) HIP_TRY(hipStreamSynchronize(b->rest.stream.get()));
+		if (b->spec_valid && b->noise.stream.get()) HIP_TRY(hipStreamSynchronize(b->noise.stream.get()));  // (the side-stream noise generator reads nz)
+		HIP_TRY(hipMemcpy(b->params_dev.get(), &kp, sizeof kp, hipMemcpyHostToDevice));
 		b->params_dirty = false;
 	}
 	return MJB_OK;
@@ -513,7 +384,7 @@ static int sync_params(mjb_batch *b)
 static int join_rest(mjb_batch *b)
 {
 	if (b->rest_pending) {
-		HIP_TRY(hipStreamWaitEvent(b->stream, b->ev_join, 0));
+		HIP_TRY(hipStreamWaitEvent(b->stream.get(), b->rest.join.get(), 0));
 		b->rest_pending = false;
 	}
 	return MJB_OK;
@@ -536,7 +407,7 @@ static int kernel_variant(const mjb_model *M)
 static int dense_build(const mjb_batch *b, int mode)
 {
 	const mjb_model_desc &h = b->model->h;
-	if (!(b->lanes == 16 && !b->env_mass && mode != MJB_MODE_STEP21 && h.integrator == MJB_INT_EULER && h.nefcmax <= 0 && h.nv <= 16 && h.nbody <= 16 && h.nu <= 16 &&
+	if (!(b->lanes == 16 && !b->env_mass.get() && mode != MJB_MODE_STEP21 && h.integrator == MJB_INT_EULER && h.nefcmax <= 0 && h.nv <= 16 && h.nbody <= 16 && h.nu <= 16 &&
 	      h.njnt <= 16))
 		return 0;
 	return h.nv <= 8 ? 8 : (h.nv <= 12 ? 12 : 16);
@@ -573,7 +444,8 @@ static int split_slices(const mjb_batch *b, int nenv)
 static int split_reset_state(mjb_batch *b)
 {
 	const mjb_model_desc &h = b->model->h;
-	mjb_batch *t = mjb_make_batch(b->model, 1, b->device);
+	BatchPtr owner(mjb_make_batch(b->model, 1, b->device));
+	mjb_batch *t = owner.get();
 	if (!t) return MJB_ENOMEM;
 	t->split_mode = 0;
 	std::vector<double> buf((size_t)h.nq + 2 * h.nv);
@@ -582,11 +454,14 @@ static int split_reset_state(mjb_batch *b)
 	if (rc == MJB_OK) rc = mjb_get(t, MJB_F_qpos, 0, 1, buf.data());
 	if (rc == MJB_OK) rc = mjb_get(t, MJB_F_qvel, 0, 1, buf.data() + h.nq);
 	if (rc == MJB_OK) rc = mjb_get(t, MJB_F_qacc_warmstart, 0, 1, buf.data() + h.nq + h.nv);
-	mjb_free_batch(t);
+	owner.reset();
 	if (rc != MJB_OK) return rc;
 	HIP_TRY(hipSetDevice(b->device));
-	HIP_TRY(hipMalloc((void **)&b->reset_step_dev, buf.size() * sizeof(double)));
-	HIP_TRY(hipMemcpy(b->reset_step_dev, buf.data(), buf.size() * sizeof(double), hipMemcpyHostToDevice));
+	DevBuf<double> dev;
+	if (!dev.alloc(buf.size())) return fail(MJB_ENOMEM, "split step: reset state");  // (the upload writes all of it)
+	HIP_TRY(hipMemcpy(dev.get(), buf.data(), buf.size() * sizeof(double), hipMemcpyHostToDevice));
+	b->reset_step_dev = std::move(dev);
+	set_view(b, b->st.reset_step, b->reset_step_dev.get());
 	return MJB_OK;
 }
 
@@ -596,19 +471,14 @@ static int split_prepare(mjb_batch *b)
 	if (!b->reset_step_dev) {
 		int rc = split_reset_state(b);
 		if (rc) return rc;
-		b->st.reset_step = b->reset_step_dev;
-		b->params_dirty = true;
 	}
 	if (!b->handoff_dev) {
 		const HandoffLayout hl = mjb_handoff_layout(h.ngeom, h.nv, h.nbody, h.nM);
-		b->handoff_dev = dev_alloc<double>((size_t)b->nenv * hl.stride);
-		if (!b->handoff_dev) return fail(MJB_ENOMEM, "split step: hand-off records");
-		HIP_TRY(hipMemset(b->handoff_dev, 0, (size_t)b->nenv * hl.stride * sizeof(double)));
-		b->st.handoff = b->handoff_dev;
+		if (!b->handoff_dev.alloc_zeroed((size_t)b->nenv * hl.stride)) return fail(MJB_ENOMEM, "split step: hand-off records");
 		b->st.handoff_stride = hl.stride;
-		b->params_dirty = true;
+		set_view(b, b->st.handoff, b->handoff_dev.get());
 	}
-	if (!b->ev_split_fork) HIP_TRY(hipEventCreateWithFlags(&b->ev_split_fork, hipEventDisableTiming));
+	if (!b->ev_split_fork) HIP_TRY(b->ev_split_fork.create());
 	return MJB_OK;
 }
 
@@ -616,33 +486,33 @@ static int launch_split(mjb_batch *b, int nsteps, int env_lo, int env_hi, hipStr
 {
 	const int nenv = env_hi - env_lo;
 	const int ns = split_slices(b, nenv);
-	while ((int)b->split_streams.size() < ns) {
-		hipStream_t st = nullptr;
-		hipEvent_t ev = nullptr;
-		HIP_TRY(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
-		b->split_streams.push_back(st);
-		HIP_TRY(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-		b->split_events.push_back(ev);
+	while ((int)b->split_streams.size() < ns) {  // (a slice's stream and its event: in step)
+		Stream st;
+		Event ev;
+		HIP_TRY(st.create());
+		HIP_TRY(ev.create());
+		b->split_streams.push_back(std::move(st));
+		b->split_events.push_back(std::move(ev));
 	}
 	const FrameLayout &Lc = b->model->Lc;
 	const int cflags = b->st.stats ? 1 : 0;
 	// slices of whole wavefronts of the smooth kernel
 	const int waves = (nenv + 63) / 64;
-	HIP_TRY(hipEventRecord(b->ev_split_fork, stream));
+	HIP_TRY(hipEventRecord(b->ev_split_fork.get(), stream));
 	for (int k = 0; k < ns; k++) {
 		const int w0 = (int)((long long)waves * k / ns), w1 = (int)((long long)waves * (k + 1) / ns);
 		const int lo = env_lo + 64 * w0, hi = std::min(env_hi, env_lo + 64 * w1);
 		if (hi <= lo) continue;
-		hipStream_t st = ns == 1 ? stream : b->split_streams[k];
-		if (ns > 1) HIP_TRY(hipStreamWaitEvent(st, b->ev_split_fork, 0));
+		hipStream_t st = ns == 1 ? stream : b->split_streams[k].get();
+		if (ns > 1) HIP_TRY(hipStreamWaitEvent(st, b->ev_split_fork.get(), 0));
 		for (int i = 0; i < nsteps; i++) {
-			int rc = mjb_launch_smooth(b->params_dev, b->model->sm_topo, lo, hi, b->step_counter + (unsigned int)i, i == nsteps - 1 ? 1 : 0, st);
-			if (rc == 0) rc = mjb_launch_cstep(b->params_dev, Lc, lo, hi, b->epb, cflags, st);
+			int rc = mjb_launch_smooth(b->params_dev.get(), b->model->sm_topo, lo, hi, b->step_counter + (unsigned int)i, i == nsteps - 1 ? 1 : 0, st);
+			if (rc == 0) rc = mjb_launch_cstep(b->params_dev.get(), Lc, lo, hi, b->epb, cflags, st);
 			if (rc != 0) return fail(MJB_ENODEVICE, "split step launch failed: %s", hipGetErrorString((hipError_t)rc));
 		}
 		if (ns > 1) {
-			HIP_TRY(hipEventRecord(b->split_events[k], st));
-			HIP_TRY(hipStreamWaitEvent(stream, b->split_events[k], 0));
+			HIP_TRY(hipEventRecord(b->split_events[k].get(), st));
+			HIP_TRY(hipStreamWaitEvent(stream, b->split_events[k].get(), 0));
 		}
 	}
 	b->split_slices_last = ns;
@@ -658,7 +528,7 @@ struct LaunchReq {
 };
 
 // facts more than one decision asks
-static bool no_env_overrides(const mjb_batch *b) { return b->hw.n == 0 && !b->env_mass && !b->env_gravity; }  // no per-env inertia / gravity, no device hwsim stage
+static bool no_env_overrides(const mjb_batch *b) { return b->hw.n == 0 && !b->env_mass.get() && !b->env_gravity.get(); }  // no per-env inertia / gravity, no device hwsim stage
 static bool eight_lean_frames_fit(const mjb_model *M) { return 8 * mjb_frame_bytes(M, 1) <= mjb_max_lds_bytes(); }  // ... one CU's LDS
 static bool chained_mode(int mode) { return mode == MJB_MODE_STEP21 || mode == MJB_MODE_RKMID || mode == MJB_MODE_RKLAST; }
 
@@ -681,7 +551,7 @@ static int frame_variant(mjb_batch *b, const LaunchReq &q, int *variant)
 static int choose_fused_frame(mjb_batch *b, const LaunchReq &q, int variant, bool *count_rows)
 {
 	*count_rows = false;
-	if (!(variant == MJB_KV_NEWTON4 && b->model->has_wide && b->rowstat_dev)) return MJB_OK;
+	if (!(variant == MJB_KV_NEWTON4 && b->model->has_wide && b->rowstat_dev.get())) return MJB_OK;
 	static const int pinned = mjb_env_int("MJB_WIDE_FRAME", -1);
 	bool want = b->wide;
 	if (pinned >= 0) want = pinned != 0;
@@ -694,11 +564,11 @@ static int choose_fused_frame(mjb_batch *b, const LaunchReq &q, int variant, boo
 			// (back-to-back launches stay enqueued ahead of the device; which launch switches frames then depends on timing, results agree to
 			// rounding).  Right behind mjb_step's probe launch the wait is the point.
 			static const bool nowait = [] { const char *v = getenv("MJB_WIDE_POLICY_NOWAIT"); return v && *v == '1'; }();
-			const hipError_t e = (b->decide_now || !nowait) ? hipEventSynchronize(b->ev_rowstat) : hipEventQuery(b->ev_rowstat);
+			const hipError_t e = (b->decide_now || !nowait) ? hipEventSynchronize(b->ev_rowstat.get()) : hipEventQuery(b->ev_rowstat.get());
 			if (e == hipSuccess) {
 				b->rowstat_pending = false;
 				b->rowstat_ever = true;
-				const double tot = (double)b->rowstat_host[0], gt64 = (double)b->rowstat_host[1];
+				const double tot = (double)b->rowstat_host.get()[0], gt64 = (double)b->rowstat_host.get()[1];
 				if (tot > 0) {
 					if (!b->wide && gt64 > 0.25 * tot) want = true;
 					else if (b->wide && gt64 < 0.05 * tot) want = false;
@@ -721,7 +591,7 @@ static int choose_fused_frame(mjb_batch *b, const LaunchReq &q, int variant, boo
 static int choose_split_step(mjb_batch *b, const LaunchReq &q, int variant, bool *use_split)
 {
 	*use_split = false;
-	if (q.mode == MJB_MODE_STEP && q.compact && variant == MJB_KV_PGS && b->model->sm_topo >= 0 && b->split_mode != 0 && no_env_overrides(b) && !b->env_equality &&
+	if (q.mode == MJB_MODE_STEP && q.compact && variant == MJB_KV_PGS && b->model->sm_topo >= 0 && b->split_mode != 0 && no_env_overrides(b) && !b->env_equality.get() &&
 	    eight_lean_frames_fit(b->model) && !stream_capturing(q.stream)) {
 		// (automatic mode: OFF unless MJB_SPLIT_MIN_ENVS names a batch size.  Measured on config 3 at 32 768 envs, profiles/r06_split_step.txt: +21 % in the
 		//  rollout's light-contact phase, +12 % over steps 1000 - 4000, -5 % over steps 500 - 2000 -- a launch pair per step ends with the slice's slowest env,
@@ -780,28 +650,20 @@ static int grow_noise_buffer(mjb_batch *b, const LaunchReq &q, size_t need, bool
 {
 	const size_t total = want_double ? 2 * need : need;
 	HIP_TRY(hipStreamSynchronize(q.stream));
-	if (b->noise_stream) HIP_TRY(hipStreamSynchronize(b->noise_stream));
-	if (b->zbuf) hipFree(b->zbuf);
+	if (b->noise.stream.get()) HIP_TRY(hipStreamSynchronize(b->noise.stream.get()));
 	b->spec_valid = false;
-	b->zbuf = dev_alloc<double>(total);
-	if (!b->zbuf) {
-		(void)hipGetLastError();
-		b->zfail = total;  // (remembered: a launch of this size or larger generates in the kernel from now on)
-	}
+	if (!b->zbuf.alloc_zeroed(total)) b->zfail = total;  // (the old one is gone; remembered: a launch of this size or larger generates in the kernel from now on)
 	b->zcap = b->zbuf ? need : 0;
 	b->zdouble = b->zbuf && want_double;
-	if (!b->zinfo) b->zinfo = dev_alloc<unsigned int>(8);
-	if (b->zinfo) HIP_TRY(hipMemset(b->zinfo, 0xff, 8 * sizeof(unsigned int)));
+	if (!b->zinfo) b->zinfo.alloc_zeroed(8);
+	if (b->zinfo) HIP_TRY(hipMemset(b->zinfo.get(), 0xff, 8 * sizeof(unsigned int)));
 	b->zvalid = false;
-	if (b->zdouble && !b->noise_stream) {
-		HIP_TRY(hipStreamCreateWithFlags(&b->noise_stream, hipStreamNonBlocking));
-		HIP_TRY(hipEventCreateWithFlags(&b->ev_noise, hipEventDisableTiming));
-		HIP_TRY(hipEventCreateWithFlags(&b->ev_noise_go, hipEventDisableTiming));
+	if (b->zdouble && !b->noise.stream) {
+		if (int rc = b->noise.create()) return rc;
 	}
-	b->st.zbuf = b->zbuf;
-	b->st.zinfo = b->zbuf ? b->zinfo : nullptr;
 	b->st.zhalf = (unsigned long long)b->zcap;
-	b->params_dirty = true;
+	set_view(b, b->st.zbuf, b->zbuf.get());
+	set_view(b, b->st.zinfo, b->zbuf ? b->zinfo.get() : nullptr);
 	return sync_params(b);
 }
 
@@ -829,15 +691,15 @@ static int stage_ctrl_noise(mjb_batch *b, const LaunchReq &q, int variant, bool 
 			if (need > b->zcap || (want_double && !b->zdouble)) {
 				if (int rc = grow_noise_buffer(b, q, need, want_double)) return rc;
 			}
-			if (b->zbuf && b->zinfo) {
+			if (b->zbuf.get() && b->zinfo.get()) {
 				if (b->spec_valid && b->spec_step0 == b->step_counter && b->spec_nsteps == q.nsteps) {
 					*zhalf = b->spec_half;
-					HIP_TRY(hipStreamWaitEvent(q.stream, b->ev_noise, 0));  // generated while the previous launch ran
+					HIP_TRY(hipStreamWaitEvent(q.stream, b->noise.done.get(), 0));  // generated while the previous launch ran
 					b->noise_mode = 2;
 				} else {
-					if (b->spec_valid) HIP_TRY(hipStreamWaitEvent(q.stream, b->ev_noise, 0));  // (a generator still writing its half: let it finish first)
-					HIP_TRY(hipMemsetAsync(b->zinfo + 4, 0xff, 4 * sizeof(unsigned int), q.stream));
-					int nrc = mjb_launch_noise(b->params_dev, b->zbuf, b->zinfo, b->nenv, nu, q.nsteps, b->step_counter, q.stream);
+					if (b->spec_valid) HIP_TRY(hipStreamWaitEvent(q.stream, b->noise.done.get(), 0));  // (a generator still writing its half: let it finish first)
+					HIP_TRY(hipMemsetAsync(b->zinfo.get() + 4, 0xff, 4 * sizeof(unsigned int), q.stream));
+					int nrc = mjb_launch_noise(b->params_dev.get(), b->zbuf.get(), b->zinfo.get(), b->nenv, nu, q.nsteps, b->step_counter, q.stream);
 					if (nrc != 0) return fail(MJB_ENODEVICE, "noise kernel launch failed: %s", hipGetErrorString((hipError_t)nrc));
 					b->noise_mode = 1;
 				}
@@ -847,9 +709,9 @@ static int stage_ctrl_noise(mjb_batch *b, const LaunchReq &q, int variant, bool 
 		}
 	}
 	if (!*zuse && b->zvalid) {  // (a launch that generates its normals itself must not match a record left by an earlier one)
-		if (b->spec_valid) HIP_TRY(hipStreamWaitEvent(q.stream, b->ev_noise, 0));
+		if (b->spec_valid) HIP_TRY(hipStreamWaitEvent(q.stream, b->noise.done.get(), 0));
 		b->spec_valid = false;
-		HIP_TRY(hipMemsetAsync(b->zinfo, 0xff, 8 * sizeof(unsigned int), q.stream));
+		HIP_TRY(hipMemsetAsync(b->zinfo.get(), 0xff, 8 * sizeof(unsigned int), q.stream));
 		b->zvalid = false;
 	}
 	return MJB_OK;
@@ -860,10 +722,10 @@ static int speculate_ctrl_noise(mjb_batch *b, const LaunchReq &q, int zhalf_now)
 {
 	const int other = 1 - zhalf_now;
 	const unsigned int next0 = b->step_counter + (unsigned int)q.nsteps;
-	HIP_TRY(hipStreamWaitEvent(b->noise_stream, b->ev_noise_go, 0));
-	int nrc = mjb_launch_noise(b->params_dev, b->zbuf + (size_t)other * b->zcap, b->zinfo + 4 * other, b->nenv, b->model->h.nu, q.nsteps, next0, b->noise_stream);
+	HIP_TRY(hipStreamWaitEvent(b->noise.stream.get(), b->noise.go.get(), 0));
+	int nrc = mjb_launch_noise(b->params_dev.get(), b->zbuf.get() + (size_t)other * b->zcap, b->zinfo.get() + 4 * other, b->nenv, b->model->h.nu, q.nsteps, next0, b->noise.stream.get());
 	if (nrc == 0) {
-		HIP_TRY(hipEventRecord(b->ev_noise, b->noise_stream));
+		HIP_TRY(hipEventRecord(b->noise.done.get(), b->noise.stream.get()));
 		b->spec_valid = true;
 		b->spec_half = other;
 		b->spec_step0 = next0;
@@ -879,7 +741,7 @@ static int speculate_ctrl_noise(mjb_batch *b, const LaunchReq &q, int zhalf_now)
 // (... or the model has activation states: no build of the kernel has both, mjb_lane_env_plan answers -1)
 // (... or joint limits: the plain build alone has the constraint stage -- no overlay, hwsim or xfrc build of such a model, mjb_lane_env_plan answers -1)
 static bool le_limits(const mjb_batch *b) { return b->model->le_topo == MJB_LE_TOPO_JIT && mjb_lane_env_limits(&b->model->h) > 0; }
-static bool le_hwsim(const mjb_batch *b) { return b->hw.n > 0 && b->lane_env_hwsim && b->hw_le_ok && !b->env_mass && !b->env_gravity && b->model->h.na <= 0 && !le_limits(b); }
+static bool le_hwsim(const mjb_batch *b) { return b->hw.n > 0 && b->lane_env_hwsim && b->hw_le_ok && !b->env_mass.get() && !b->env_gravity.get() && b->model->h.na <= 0 && !le_limits(b); }
 // (mjb_lane_env_set_xfrc: a written xfrc_applied rides along in the kernel's XF builds -- unless the batch has a hwsim stage, there is no build with both.
 //  LaunchReq::compact stays what the generic path's frame choice reads; for this kernel, which has no frame, the xfrc term of it is lifted)
 // (... or the model has a force / torque sensor on a body at rest: the wrench table has no slot for that body's xfrc_applied, mjb_lane_env_plan answers -1)
@@ -903,7 +765,7 @@ static bool want_lane_env(const mjb_batch *b, const LaunchReq &q, int variant)
 // derived again ahead of the next launch.  Sources: env_gravity, the env's block of env_mass (its host mirror when there is one), else the model.
 static void le_overlay_touch(mjb_batch *b, int env_lo, int env_hi)
 {
-	if (!b->le_overlay || env_lo >= env_hi) return;
+	if (!b->le_overlay.get() || env_lo >= env_hi) return;
 	const bool none = b->le_ov_lo >= b->le_ov_hi;
 	b->le_ov_lo = none ? env_lo : std::min(b->le_ov_lo, env_lo);
 	b->le_ov_hi = none ? env_hi : std::max(b->le_ov_hi, env_hi);
@@ -913,28 +775,26 @@ static int le_overlay_sync(mjb_batch *b)
 	const mjb_model_desc &h = b->model->h;
 	const int ns = mjb_lane_env_overlay_slots(&h), nenv = b->nenv;
 	if (!b->le_overlay) {
-		b->le_overlay = dev_alloc<double>((size_t)ns * nenv);
-		if (!b->le_overlay) return fail(MJB_ENOMEM, "lane = env kernel: allocation of the per-env overlay failed");
-		b->st.le_overlay = b->le_overlay;
-		b->params_dirty = true;
+		if (!b->le_overlay.alloc_zeroed((size_t)ns * nenv)) return fail(MJB_ENOMEM, "lane = env kernel: allocation of the per-env overlay failed");
+		set_view(b, b->st.le_overlay, b->le_overlay.get());
 		b->le_ov_lo = 0;
 		b->le_ov_hi = nenv;
 	}
 	const int lo = b->le_ov_lo, hi = b->le_ov_hi, n = hi - lo;
 	if (n <= 0) return MJB_OK;
-	HIP_TRY(hipStreamSynchronize(b->stream));  // (an earlier launch may still read the columns)
-	if (b->rest_pending && b->rest_stream) HIP_TRY(hipStreamSynchronize(b->rest_stream));
+	HIP_TRY(hipStreamSynchronize(b->stream.get()));  // (an earlier launch may still read the columns)
+	if (b->rest_pending && b->rest.stream.get()) HIP_TRY(hipStreamSynchronize(b->rest.stream.get()));
 	const size_t stride = (size_t)mjb_env_block_doubles(h.nbody, h.nv, h.ntendon, h.njnt, h.nu);
 	std::vector<double> grav, blk;
 	const double *rows = nullptr;
-	if (b->env_gravity) {
+	if (b->env_gravity.get()) {
 		grav.resize((size_t)3 * n);
-		HIP_TRY(hipMemcpy(grav.data(), b->env_gravity + (size_t)3 * lo, grav.size() * sizeof(double), hipMemcpyDeviceToHost));
+		HIP_TRY(hipMemcpy(grav.data(), b->env_gravity.get() + (size_t)3 * lo, grav.size() * sizeof(double), hipMemcpyDeviceToHost));
 	}
-	if (b->env_mass && !b->env_block.empty()) rows = b->env_block.data() + (size_t)lo * stride;
-	else if (b->env_mass) {
+	if (b->env_mass.get() && !b->env_block.empty()) rows = b->env_block.data() + (size_t)lo * stride;
+	else if (b->env_mass.get()) {
 		blk.resize(stride * n);
-		HIP_TRY(hipMemcpy(blk.data(), b->env_mass + (size_t)lo * stride, blk.size() * sizeof(double), hipMemcpyDeviceToHost));
+		HIP_TRY(hipMemcpy(blk.data(), b->env_mass.get() + (size_t)lo * stride, blk.size() * sizeof(double), hipMemcpyDeviceToHost));
 		rows = blk.data();
 	}
 	std::vector<double> col((size_t)ns), stage((size_t)ns * n);
@@ -943,7 +803,7 @@ static int le_overlay_sync(mjb_batch *b)
 		for (int k = 0; k < ns; k++) stage[(size_t)k * n + e] = col[k];
 	}
 	// slot k of envs [lo, hi): n consecutive doubles at le_overlay + k * nenv + lo
-	HIP_TRY(hipMemcpy2D(b->le_overlay + lo, (size_t)nenv * sizeof(double), stage.data(), (size_t)n * sizeof(double), (size_t)n * sizeof(double), (size_t)ns,
+	HIP_TRY(hipMemcpy2D(b->le_overlay.get() + lo, (size_t)nenv * sizeof(double), stage.data(), (size_t)n * sizeof(double), (size_t)n * sizeof(double), (size_t)ns,
 	                    hipMemcpyHostToDevice));
 	b->le_ov_lo = b->le_ov_hi = 0;
 	return MJB_OK;
@@ -956,21 +816,14 @@ static int le_xfrc_sync(mjb_batch *b, hipStream_t stream)
 {
 	const mjb_model_desc &h = b->model->h;
 	if (!b->le_xfrc) {
-		// (no dev_alloc: its memset runs on the null stream, which the batch's non-blocking stream does not wait for -- it could land behind the fill below,
-		//  which writes every entry anyway)
-		const size_t bytes = std::max<size_t>(1, (size_t)6 * mjb_lane_env_xfrc_slots(&h) * b->nenv) * sizeof(double);
-		if (hipMalloc((void **)&b->le_xfrc, bytes) != hipSuccess) {
-			(void)hipGetLastError();
-			b->le_xfrc = nullptr;
+		if (!b->le_xfrc.alloc((size_t)6 * mjb_lane_env_xfrc_slots(&h) * b->nenv))  // (the fill below writes every entry)
 			return fail(MJB_ENOMEM, "lane = env kernel: allocation of the xfrc_applied table failed");
-		}
-		b->st.le_xfrc = b->le_xfrc;
-		b->params_dirty = true;
+		set_view(b, b->st.le_xfrc, b->le_xfrc.get());
 		b->le_xfrc_stale = true;
 	}
 	if (!b->le_xfrc_stale) return MJB_OK;
-	if (b->rest_pending && b->rest_stream && b->rest_stream != stream) HIP_TRY(hipStreamSynchronize(b->rest_stream));  // (an earlier launch may still read the table)
-	const int rc = mjb_lane_env_xfrc_fill(&h, b->st.xfrc_applied, b->le_xfrc, b->nenv, stream);
+	if (b->rest_pending && b->rest.stream.get() && b->rest.stream.get() != stream) HIP_TRY(hipStreamSynchronize(b->rest.stream.get()));  // (an earlier launch may still read the table)
+	const int rc = mjb_lane_env_xfrc_fill(&h, b->st.xfrc_applied, b->le_xfrc.get(), b->nenv, stream);
 	if (rc != 0) return fail(MJB_ENODEVICE, "lane = env kernel: xfrc_applied table fill failed: %s", hipGetErrorString((hipError_t)rc));
 	b->le_xfrc_stale = false;
 	return MJB_OK;
@@ -979,7 +832,7 @@ static int le_xfrc_sync(mjb_batch *b, hipStream_t stream)
 static int launch(mjb_batch *b, int mode, int nsteps, int env_lo = 0, int env_hi = -1, hipStream_t on = nullptr)
 {
 	if (env_hi < 0) env_hi = b->nenv;
-	LaunchReq q = { mode, nsteps, env_lo, env_hi, on ? on : b->stream, env_lo == 0 && env_hi == b->nenv, mode == MJB_MODE_STEP && !b->st.use_xfrc && !b->st.keep_frame };
+	LaunchReq q = { mode, nsteps, env_lo, env_hi, on ? on : b->stream.get(), env_lo == 0 && env_hi == b->nenv, mode == MJB_MODE_STEP && !b->st.use_xfrc && !b->st.keep_frame };
 	HIP_TRY(hipSetDevice(b->device));
 	int variant, chunk, zhalf_now, rc;
 	bool count_rows, use_split, zuse;
@@ -988,25 +841,21 @@ static int launch(mjb_batch *b, int mode, int nsteps, int env_lo = 0, int env_hi
 	if ((rc = choose_split_step(b, q, variant, &use_split))) return rc;
 	b->split_used = use_split;
 	{  // the kernels count rows (three atomics per env-step on one address) only in the launches whose counters are read
-		unsigned long long *rs = count_rows ? b->rowstat_dev : nullptr;
-		if (b->st.rowstat != rs) {
-			b->st.rowstat = rs;
-			b->params_dirty = true;
-		}
+		unsigned long long *rs = count_rows ? b->rowstat_dev.get() : nullptr;
+		if (b->st.rowstat != rs) set_view(b, b->st.rowstat, rs);
 	}
-	const bool le_per_env = b->lane_env_mode == 2 && (b->env_mass || b->env_gravity) && !use_split && want_lane_env(b, q, variant);
+	const bool le_per_env = b->lane_env_mode == 2 && (b->env_mass.get() || b->env_gravity.get()) && !use_split && want_lane_env(b, q, variant);
 	if (le_per_env && (rc = le_overlay_sync(b))) return rc;
 	const bool le_xf = le_xfrc(b) && !use_split && want_lane_env(b, q, variant);
 	if (le_xf && (rc = le_xfrc_sync(b, q.stream))) return rc;
 	if (!b->le_con && le_limits(b) && !use_split && want_lane_env(b, q, variant)) {  // what the kernel leaves of its constraint stage: allocated at the first such launch
-		b->le_con = dev_alloc<double>((size_t)b->nenv * (size_t)(b->model->h.nv + 2));
-		if (!b->le_con) return fail(MJB_ENOMEM, "lane = env kernel: allocation of the constraint stage's output failed");
-		b->params_dirty = true;
+		if (!b->le_con.alloc_zeroed((size_t)b->nenv * (size_t)(b->model->h.nv + 2))) return fail(MJB_ENOMEM, "lane = env kernel: allocation of the constraint stage's output failed");
+		b->params_dirty = true;  // (KernelParams::le_con: sync_params reads the owner)
 	}
 	if ((rc = sync_params(b))) return rc;
 	if (use_split) {
 		if (b->zvalid) {  // (the pre-generated ctrl-noise buffer names an older launch: this path draws its normals in the smooth kernel)
-			HIP_TRY(hipMemsetAsync(b->zinfo, 0xff, 8 * sizeof(unsigned int), q.stream));
+			HIP_TRY(hipMemsetAsync(b->zinfo.get(), 0xff, 8 * sizeof(unsigned int), q.stream));
 			b->zvalid = false;
 		}
 		b->lane_env_used = false;
@@ -1019,12 +868,12 @@ static int launch(mjb_batch *b, int mode, int nsteps, int env_lo = 0, int env_hi
 	if (!(le_limits(b) && want_lane_env(b, q, variant)) && (rc = choose_chunk(b, q, variant, &chunk))) return rc;  // (a limit model on the lane = env kernel: no work queue)
 	if ((rc = stage_ctrl_noise(b, q, variant, &zuse, &zhalf_now))) return rc;
 	const bool zspec = zuse && b->zdouble;
-	if (zspec) HIP_TRY(hipEventRecord(b->ev_noise_go, q.stream));  // (everything before this launch -- the last reader of the other half -- is done)
-	if (count_rows) HIP_TRY(hipMemsetAsync(b->rowstat_dev, 0, 4 * sizeof(unsigned long long), q.stream));
+	if (zspec) HIP_TRY(hipEventRecord(b->noise.go.get(), q.stream));  // (everything before this launch -- the last reader of the other half -- is done)
+	if (count_rows) HIP_TRY(hipMemsetAsync(b->rowstat_dev.get(), 0, 4 * sizeof(unsigned long long), q.stream));
 	bool use_le = want_lane_env(b, q, variant);
 	b->lane_env_used = use_le;
 	if (use_le) {
-		rc = mjb_launch_lane_env(b->params_dev, b->model->le_topo, &b->model->h, b->nenv, env_lo, env_hi, nsteps, b->step_counter, q.stream,
+		rc = mjb_launch_lane_env(b->params_dev.get(), b->model->le_topo, &b->model->h, b->nenv, env_lo, env_hi, nsteps, b->step_counter, q.stream,
 		                         le_xf ? (le_per_env ? MJB_LE_OVERLAY_XFRC : MJB_LE_XFRC) : le_per_env ? MJB_LE_OVERLAY : (b->hw.n > 0 ? MJB_LE_HWSIM : MJB_LE_PLAIN));
 		if (rc == MJB_LE_UNAVAILABLE) {  // (no hiprtc / no kernel header / compile error: remembered, the generic kernel runs -- mjb_lane_env_info says why)
 			b->le_unavailable = true;
@@ -1033,14 +882,14 @@ static int launch(mjb_batch *b, int mode, int nsteps, int env_lo = 0, int env_hi
 	}
 	b->le_con_valid = use_le && q.whole && le_limits(b);
 	if (!use_le) {
-		const StepLaunch a = { b->params_dev, q.compact ? (b->wide ? &b->model->Lw : &b->model->Lc) : &b->L, env_lo, env_hi, mode, nsteps, b->step_counter,
+		const StepLaunch a = { b->params_dev.get(), q.compact ? (b->wide ? &b->model->Lw : &b->model->Lc) : &b->L, env_lo, env_hi, mode, nsteps, b->step_counter,
 			                   b->lanes, b->epb, variant, chunk, dense_build(b, mode), q.stream };
 		rc = mjb_launch_step(a);
 	}
 	if (rc != 0) return fail(MJB_ENODEVICE, "kernel launch failed: %s", hipGetErrorString((hipError_t)rc));
 	if (count_rows) {  // this launch's row counters, to pinned host memory behind it
-		HIP_TRY(hipMemcpyAsync(b->rowstat_host, b->rowstat_dev, 4 * sizeof(unsigned long long), hipMemcpyDeviceToHost, q.stream));
-		HIP_TRY(hipEventRecord(b->ev_rowstat, q.stream));
+		HIP_TRY(hipMemcpyAsync(b->rowstat_host.get(), b->rowstat_dev.get(), 4 * sizeof(unsigned long long), hipMemcpyDeviceToHost, q.stream));
+		HIP_TRY(hipEventRecord(b->ev_rowstat.get(), q.stream));
 		b->rowstat_pending = true;
 	}
 	if (zspec) return speculate_ctrl_noise(b, q, zhalf_now);
@@ -1059,7 +908,7 @@ int mjb_step(mjb_batch *b, int nsteps)
 	// high-contact batch used to run on the default frame (r05: 1461 ms against 288 ms in steady state).  A launch cut in two is the same
 	// rollout (the state crosses HBM between launches exactly as between the chunks of one).
 	int rc = MJB_OK;
-	if (nsteps >= 100 && b->rowstat_dev && b->model->has_wide && !b->rowstat_ever && !b->rowstat_pending && !b->st.use_xfrc && !b->st.keep_frame) {
+	if (nsteps >= 100 && b->rowstat_dev.get() && b->model->has_wide && !b->rowstat_ever && !b->rowstat_pending && !b->st.use_xfrc && !b->st.keep_frame) {
 		const int probe = 4;
 		b->probe_now = true;
 		rc = launch(b, MJB_MODE_STEP, probe);
@@ -1163,17 +1012,15 @@ int mjb_step_rest(mjb_batch *b, int ncb)
 	// on its own stream, forked from the batch's stream here and joined in mjb_step2_prefix: the two groups of envs are independent,
 	// so the callback envs' second half does not queue behind this launch
 	HIP_TRY(hipSetDevice(b->device));
-	if (!b->rest_stream) {
-		HIP_TRY(hipStreamCreateWithFlags(&b->rest_stream, hipStreamNonBlocking));
-		HIP_TRY(hipEventCreateWithFlags(&b->ev_fork, hipEventDisableTiming));
-		HIP_TRY(hipEventCreateWithFlags(&b->ev_join, hipEventDisableTiming));
+	if (!b->rest.stream) {
+		if (int crc = b->rest.create()) return crc;
 	}
 	int prc = sync_params(b);  // (uploads, if any, on the batch's stream BEFORE the fork)
 	if (prc) return prc;
-	HIP_TRY(hipEventRecord(b->ev_fork, b->stream));
-	HIP_TRY(hipStreamWaitEvent(b->rest_stream, b->ev_fork, 0));
-	int rc = launch(b, MJB_MODE_STEP, 1, ncb, b->nenv, b->rest_stream);
-	HIP_TRY(hipEventRecord(b->ev_join, b->rest_stream));
+	HIP_TRY(hipEventRecord(b->rest.fork.get(), b->stream.get()));
+	HIP_TRY(hipStreamWaitEvent(b->rest.stream.get(), b->rest.fork.get(), 0));
+	int rc = launch(b, MJB_MODE_STEP, 1, ncb, b->nenv, b->rest.stream.get());
+	HIP_TRY(hipEventRecord(b->rest.join.get(), b->rest.stream.get()));
 	b->rest_pending = true;
 	return rc;
 }
@@ -1256,18 +1103,18 @@ int mjb_reset(mjb_batch *b, const uint8_t *mask)
 	HIP_TRY(hipSetDevice(b->device));
 	const unsigned char *md = nullptr;
 	if (mask) {
-		if (!b->mask_dev) HIP_TRY(hipMalloc((void **)&b->mask_dev, (size_t)b->nenv));
-		HIP_TRY(hipMemcpyAsync(b->mask_dev, mask, (size_t)b->nenv, hipMemcpyHostToDevice, b->stream));
-		md = b->mask_dev;
+		if (!b->mask_dev && !b->mask_dev.alloc((size_t)b->nenv)) return fail(MJB_ENOMEM, "mjb_reset: mask allocation failed");  // (the copy below writes all of it)
+		HIP_TRY(hipMemcpyAsync(b->mask_dev.get(), mask, (size_t)b->nenv, hipMemcpyHostToDevice, b->stream.get()));
+		md = b->mask_dev.get();
 	}
 	int prc = join_rest(b);
 	if (prc) return prc;
 	b->split_ncb = -1;  // (an open split step is abandoned: mjb_step1_prefix starts the next one)
 	prc = sync_params(b);
 	if (prc) return prc;
-	int rc = mjb_launch_reset(b->params_dev, b->nenv, md, b->stream);
+	int rc = mjb_launch_reset(b->params_dev.get(), b->nenv, md, b->stream.get());
 	if (rc != 0) return fail(MJB_ENODEVICE, "reset launch failed: %s", hipGetErrorString((hipError_t)rc));
-	if (mask) HIP_TRY(hipStreamSynchronize(b->stream));
+	if (mask) HIP_TRY(hipStreamSynchronize(b->stream.get()));
 	b->frame_valid = false;
 	b->le_con_valid = false;
 	b->le_xfrc_stale = true;  // (mj_resetData zeroes xfrc_applied)
@@ -1310,7 +1157,7 @@ int mjb_get(mjb_batch *b, int field, int env_lo, int env_hi, double *host)
 	if (n == 0 || env_lo == env_hi) return MJB_OK;
 	if (!host) return fail(MJB_EINVAL, "null host buffer");
 	HIP_TRY(hipSetDevice(b->device));
-	HIP_TRY(hipStreamSynchronize(b->stream));
+	HIP_TRY(hipStreamSynchronize(b->stream.get()));
 	if (kFields[field].kind == 0) {
 		double *p = state_ptr(b, field);
 		HIP_TRY(hipMemcpy(host, p + (size_t)env_lo * n, (size_t)(env_hi - env_lo) * n * sizeof(double),
@@ -1319,7 +1166,7 @@ int mjb_get(mjb_batch *b, int field, int env_lo, int env_hi, double *host)
 	}
 	if (b->le_con_valid && !b->frame_valid && !strcmp(kFields[field].name, "qfrc_constraint")) {  // (what the lane = env kernel left of a limit model's last step)
 		const size_t ld = (size_t)b->model->h.nv + 2;
-		HIP_TRY(hipMemcpy2D(host, (size_t)n * sizeof(double), b->le_con + (size_t)env_lo * ld, ld * sizeof(double), (size_t)n * sizeof(double), (size_t)(env_hi - env_lo),
+		HIP_TRY(hipMemcpy2D(host, (size_t)n * sizeof(double), b->le_con.get() + (size_t)env_lo * ld, ld * sizeof(double), (size_t)n * sizeof(double), (size_t)(env_hi - env_lo),
 		                    hipMemcpyDeviceToHost));
 		return MJB_OK;
 	}
@@ -1345,8 +1192,8 @@ int mjb_get_int(mjb_batch *b, int field, int env_lo, int env_hi, int *host)
 		const size_t ld = (size_t)b->model->h.nv + 2, nrow = (size_t)(env_hi - env_lo);
 		std::vector<double> v(nrow);
 		HIP_TRY(hipSetDevice(b->device));
-		HIP_TRY(hipStreamSynchronize(b->stream));
-		HIP_TRY(hipMemcpy2D(v.data(), sizeof(double), b->le_con + (size_t)env_lo * ld + (size_t)b->model->h.nv + (strcmp(kFields[field].name, "nefc") ? 1 : 0), ld * sizeof(double),
+		HIP_TRY(hipStreamSynchronize(b->stream.get()));
+		HIP_TRY(hipMemcpy2D(v.data(), sizeof(double), b->le_con.get() + (size_t)env_lo * ld + (size_t)b->model->h.nv + (strcmp(kFields[field].name, "nefc") ? 1 : 0), ld * sizeof(double),
 		                    sizeof(double), nrow, hipMemcpyDeviceToHost));
 		for (size_t e = 0; e < nrow; e++) host[e] = (int)v[e];
 		return MJB_OK;
@@ -1355,7 +1202,7 @@ int mjb_get_int(mjb_batch *b, int field, int env_lo, int env_hi, int *host)
 		return fail(MJB_EINVAL, "int field %s is only readable after mjb_forward / mjb_step1 / mjb_step2",
 		            kFields[field].name);
 	HIP_TRY(hipSetDevice(b->device));
-	HIP_TRY(hipStreamSynchronize(b->stream));
+	HIP_TRY(hipStreamSynchronize(b->stream.get()));
 	const int off = frame_offset(b, field);
 	const int *base = reinterpret_cast<const int *>(b->st.frame_ws + (size_t)env_lo * b->st.frame_stride + b->L.ndouble) + off;
 	HIP_TRY(hipMemcpy2D(host, (size_t)n * sizeof(int), base, (size_t)b->st.frame_stride * sizeof(double),
@@ -1371,7 +1218,7 @@ int mjb_set(mjb_batch *b, int field, int env_lo, int env_hi, const double *host)
 	if (n == 0 || env_lo == env_hi) return MJB_OK;
 	if (!host) return fail(MJB_EINVAL, "null host buffer");
 	HIP_TRY(hipSetDevice(b->device));
-	HIP_TRY(hipStreamSynchronize(b->stream));
+	HIP_TRY(hipStreamSynchronize(b->stream.get()));
 	if (kFields[field].kind == 0) {
 		double *p = state_ptr(b, field);
 		HIP_TRY(hipMemcpy(p + (size_t)env_lo * n, host, (size_t)(env_hi - env_lo) * n * sizeof(double),
@@ -1406,7 +1253,7 @@ int mjb_register_collision(mjb_batch *b, int geom_type1, int geom_type2, int fun
 	const int np = M->h.ncollpair;
 	if (np == 0) return MJB_OK;
 	HIP_TRY(hipSetDevice(b->device));
-	HIP_TRY(hipStreamSynchronize(b->stream));
+	HIP_TRY(hipStreamSynchronize(b->stream.get()));
 	const int lo = geom_type1 < geom_type2 ? geom_type1 : geom_type2, hi = geom_type1 < geom_type2 ? geom_type2 : geom_type1;
 	if (b->st.colfunc[8 * lo + hi] != func) {  // the table by current types (read when per-env geom types are in play)
 		b->st.colfunc[8 * lo + hi] = func;
@@ -1440,13 +1287,13 @@ int mjb_get_many(mjb_batch *b, int n, const int *fields, int env_lo, int env_hi,
 		if (sz == 0 || env_lo == env_hi) continue;
 		if (kFields[field].kind == 0)
 			err = hipMemcpyAsync(host[k], state_ptr(b, field) + (size_t)env_lo * sz, (size_t)(env_hi - env_lo) * sz * sizeof(double),
-			                     hipMemcpyDeviceToHost, b->stream);
+			                     hipMemcpyDeviceToHost, b->stream.get());
 		else
 			err = hipMemcpy2DAsync(host[k], (size_t)sz * sizeof(double), b->st.frame_ws + (size_t)env_lo * b->st.frame_stride + frame_offset(b, field),
 			                       (size_t)b->st.frame_stride * sizeof(double), (size_t)sz * sizeof(double), (size_t)(env_hi - env_lo),
-			                       hipMemcpyDeviceToHost, b->stream);
+			                       hipMemcpyDeviceToHost, b->stream.get());
 	}
-	const hipError_t serr = hipStreamSynchronize(b->stream);  // (also after a failed enqueue: the copies before it are drained)
+	const hipError_t serr = hipStreamSynchronize(b->stream.get());  // (also after a failed enqueue: the copies before it are drained)
 	if (err != hipSuccess) return fail(MJB_ENODEVICE, "mjb_get_many: %s", hipGetErrorString(err));
 	if (serr != hipSuccess) return fail(MJB_ENODEVICE, "mjb_get_many: %s", hipGetErrorString(serr));
 	return MJB_OK;
@@ -1476,7 +1323,7 @@ int mjb_set_many(mjb_batch *b, int n, const int *fields, int env_lo, int env_hi,
 		if (sz == 0 || env_lo == env_hi) continue;
 		if (kFields[field].kind == 0) {
 			err = hipMemcpyAsync(state_ptr(b, field) + (size_t)env_lo * sz, host[k], (size_t)(env_hi - env_lo) * sz * sizeof(double),
-			                     hipMemcpyHostToDevice, b->stream);
+			                     hipMemcpyHostToDevice, b->stream.get());
 			if (field == MJB_F_xfrc_applied) b->le_xfrc_stale = true;
 			if (field == MJB_F_xfrc_applied && !b->st.use_xfrc) {
 				b->st.use_xfrc = 1;
@@ -1485,11 +1332,11 @@ int mjb_set_many(mjb_batch *b, int n, const int *fields, int env_lo, int env_hi,
 		} else {
 			err = hipMemcpy2DAsync(b->st.frame_ws + (size_t)env_lo * b->st.frame_stride + frame_offset(b, field),
 			                       (size_t)b->st.frame_stride * sizeof(double), host[k], (size_t)sz * sizeof(double), (size_t)sz * sizeof(double),
-			                       (size_t)(env_hi - env_lo), hipMemcpyHostToDevice, b->stream);
+			                       (size_t)(env_hi - env_lo), hipMemcpyHostToDevice, b->stream.get());
 		}
 	}
 	if (err != hipSuccess) {
-		hipStreamSynchronize(b->stream);  // drain what was enqueued before the failure
+		hipStreamSynchronize(b->stream.get());  // drain what was enqueued before the failure
 		return fail(MJB_ENODEVICE, "mjb_set_many: %s", hipGetErrorString(err));
 	}
 	return MJB_OK;
@@ -1565,9 +1412,7 @@ static int packed_transfer(mjb_batch *b, int n, const int *fields, int env_lo, i
 	if (total == 0 || env_lo == env_hi) return MJB_OK;
 	a.nenv = env_hi - env_lo;
 	if ((long long)b->pack_cap < total) {
-		if (b->pack_dev) hipFree(b->pack_dev);
-		b->pack_dev = dev_alloc<double>((size_t)total);
-		if (!b->pack_dev) {
+		if (!b->pack_dev.alloc_zeroed((size_t)total)) {
 			b->pack_cap = 0;
 			return fail(MJB_ENOMEM, "%s: staging allocation failed", who);
 		}
@@ -1577,12 +1422,12 @@ static int packed_transfer(mjb_batch *b, int n, const int *fields, int env_lo, i
 	int bx = (int)std::min<long long>(((long long)a.nenv * maxdim + threads - 1) / threads, 64);
 	if (bx < 1) bx = 1;
 	if (!to_host)
-		HIP_TRY(hipMemcpyAsync(b->pack_dev, host_block, (size_t)total * sizeof(double), hipMemcpyHostToDevice, b->stream));
-	hipLaunchKernelGGL(mjb_pack_kernel, dim3(bx, a.n), dim3(threads), 0, b->stream, a, b->pack_dev, env_lo, to_host ? 0 : 1);
+		HIP_TRY(hipMemcpyAsync(b->pack_dev.get(), host_block, (size_t)total * sizeof(double), hipMemcpyHostToDevice, b->stream.get()));
+	hipLaunchKernelGGL(mjb_pack_kernel, dim3(bx, a.n), dim3(threads), 0, b->stream.get(), a, b->pack_dev.get(), env_lo, to_host ? 0 : 1);
 	HIP_TRY(hipGetLastError());
 	if (to_host) {
-		HIP_TRY(hipMemcpyAsync(host_block, b->pack_dev, (size_t)total * sizeof(double), hipMemcpyDeviceToHost, b->stream));
-		HIP_TRY(hipStreamSynchronize(b->stream));
+		HIP_TRY(hipMemcpyAsync(host_block, b->pack_dev.get(), (size_t)total * sizeof(double), hipMemcpyDeviceToHost, b->stream.get()));
+		HIP_TRY(hipStreamSynchronize(b->stream.get()));
 	}
 	return MJB_OK;
 }
@@ -1635,11 +1480,11 @@ int mjb_set_ctrl_noise(mjb_batch *b, double ctrl_noise_std, double ctrl_noise_ra
 	b->nz.env_offset = env_offset;
 	b->nz.enabled = ctrl_noise_std > 0;
 	b->params_dirty = true;
-	if (b->zinfo) {  // normals generated under the old key (also the ones a side-stream generator is still writing) are void
+	if (b->zinfo.get()) {  // normals generated under the old key (also the ones a side-stream generator is still writing) are void
 		HIP_TRY(hipSetDevice(b->device));
-		if (b->noise_stream) HIP_TRY(hipStreamSynchronize(b->noise_stream));
-		HIP_TRY(hipStreamSynchronize(b->stream));
-		HIP_TRY(hipMemset(b->zinfo, 0xff, 8 * sizeof(unsigned int)));
+		if (b->noise.stream.get()) HIP_TRY(hipStreamSynchronize(b->noise.stream.get()));
+		HIP_TRY(hipStreamSynchronize(b->stream.get()));
+		HIP_TRY(hipMemset(b->zinfo.get(), 0xff, 8 * sizeof(unsigned int)));
 		b->spec_valid = false;
 		b->zvalid = false;
 	}
@@ -1652,26 +1497,24 @@ int mjb_set_stats(mjb_batch *b, int on)
 	HIP_TRY(hipSetDevice(b->device));
 	int rc = join_rest(b);
 	if (rc) return rc;
-	HIP_TRY(hipStreamSynchronize(b->stream));
+	HIP_TRY(hipStreamSynchronize(b->stream.get()));
 	if (on) {
-		if (!b->stats_dev) b->stats_dev = dev_alloc<unsigned long long>(MJB_NSTATS);
-		if (!b->stats_dev) return fail(MJB_ENOMEM, "mjb_set_stats: allocation failed");
-		HIP_TRY(hipMemset(b->stats_dev, 0, MJB_NSTATS * sizeof(unsigned long long)));
+		if (!b->stats_dev && !b->stats_dev.alloc_zeroed(MJB_NSTATS)) return fail(MJB_ENOMEM, "mjb_set_stats: allocation failed");
+		HIP_TRY(hipMemset(b->stats_dev.get(), 0, MJB_NSTATS * sizeof(unsigned long long)));
 	}
-	b->st.stats = on ? b->stats_dev : nullptr;
-	b->params_dirty = true;
+	set_view(b, b->st.stats, on ? b->stats_dev.get() : nullptr);
 	return MJB_OK;
 }
 
 int mjb_get_stats(mjb_batch *b, unsigned long long *out)
 {
 	if (!b || !out) return fail(MJB_EINVAL, "mjb_get_stats: bad argument");
-	if (!b->stats_dev) return fail(MJB_EINVAL, "mjb_get_stats before mjb_set_stats(b, 1)");
+	if (!b->stats_dev.get()) return fail(MJB_EINVAL, "mjb_get_stats before mjb_set_stats(b, 1)");
 	HIP_TRY(hipSetDevice(b->device));
 	int rc = join_rest(b);
 	if (rc) return rc;
-	HIP_TRY(hipStreamSynchronize(b->stream));
-	HIP_TRY(hipMemcpy(out, b->stats_dev, MJB_NSTATS * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+	HIP_TRY(hipStreamSynchronize(b->stream.get()));
+	HIP_TRY(hipMemcpy(out, b->stats_dev.get(), MJB_NSTATS * sizeof(unsigned long long), hipMemcpyDeviceToHost));
 	return MJB_OK;
 }
 
@@ -1729,16 +1572,14 @@ int mjb_lane_env_info(const mjb_batch *b, int *used_last)
 }
 int mjb_fused_frame(const mjb_batch *b) { return b && b->wide ? 2 : 1; }
 
-void *mjb_get_stream(mjb_batch *b) { return b ? (void *)b->stream : nullptr; }
+void *mjb_get_stream(mjb_batch *b) { return b ? (void *)b->stream.get() : nullptr; }
 
 int mjb_set_stream(mjb_batch *b, void *hip_stream)
 {
 	if (!b) return fail(MJB_EINVAL, "null batch");
 	HIP_TRY(hipSetDevice(b->device));
-	if (b->stream) HIP_TRY(hipStreamSynchronize(b->stream));
-	if (b->own_stream && b->stream) hipStreamDestroy(b->stream);
-	b->stream = (hipStream_t)hip_stream;
-	b->own_stream = false;
+	if (b->stream) HIP_TRY(hipStreamSynchronize(b->stream.get()));
+	b->stream.borrow((hipStream_t)hip_stream);  // (a stream of the batch's own is destroyed)
 	return MJB_OK;
 }
 
@@ -1746,7 +1587,7 @@ int mjb_synchronize(mjb_batch *b)
 {
 	if (!b) return fail(MJB_EINVAL, "null batch");
 	HIP_TRY(hipSetDevice(b->device));
-	HIP_TRY(hipStreamSynchronize(b->stream));
+	HIP_TRY(hipStreamSynchronize(b->stream.get()));
 	return MJB_OK;
 }
 
@@ -1754,7 +1595,7 @@ int mjb_debug_profile(mjb_batch *b, unsigned long long *out64, int clear)
 {
 	if (!b || !out64) return fail(MJB_EINVAL, "mjb_debug_profile: bad argument");
 	HIP_TRY(hipSetDevice(b->device));
-	HIP_TRY(hipStreamSynchronize(b->stream));
+	HIP_TRY(hipStreamSynchronize(b->stream.get()));
 	HIP_TRY(hipMemcpy(out64, b->st.prof, 64 * sizeof(unsigned long long), hipMemcpyDeviceToHost));
 	if (clear) HIP_TRY(hipMemset(b->st.prof, 0, 64 * sizeof(unsigned long long)));
 	return MJB_OK;
@@ -1774,7 +1615,7 @@ int mjb_warning(mjb_batch *b, int which, unsigned long long *count)
 {
 	if (!b || !count || which < 0 || which >= MJB_NWARNING) return fail(MJB_EINVAL, "mjb_warning: bad argument");
 	HIP_TRY(hipSetDevice(b->device));
-	HIP_TRY(hipStreamSynchronize(b->stream));
+	HIP_TRY(hipStreamSynchronize(b->stream.get()));
 	HIP_TRY(hipMemcpy(count, b->st.nwarn + which, sizeof(unsigned long long), hipMemcpyDeviceToHost));
 	return MJB_OK;
 }
@@ -1784,7 +1625,7 @@ int mjb_warning_count(mjb_batch *b, unsigned long long *count)
 	if (!b || !count) return fail(MJB_EINVAL, "mjb_warning_count: bad argument");
 	unsigned long long w[MJB_NWARNING];
 	HIP_TRY(hipSetDevice(b->device));
-	HIP_TRY(hipStreamSynchronize(b->stream));
+	HIP_TRY(hipStreamSynchronize(b->stream.get()));
 	HIP_TRY(hipMemcpy(w, b->st.nwarn, sizeof w, hipMemcpyDeviceToHost));
 	*count = w[MJB_WARN_BADQPOS] + w[MJB_WARN_BADQVEL] + w[MJB_WARN_BADQACC];
 	return MJB_OK;
@@ -1847,19 +1688,18 @@ void *mjb_metrics_device(mjb_batch *b)
 	}
 	if (hipSetDevice(b->device) != hipSuccess) return nullptr;
 	if (!b->metrics_dev) {
-		b->metrics_dev = dev_alloc<double>(16);
-		if (!b->metrics_dev) {
+		if (!b->metrics_dev.alloc_zeroed(16)) {
 			fail(MJB_ENOMEM, "mjb_metrics: allocation failed");
 			return nullptr;
 		}
 	}
-	hipLaunchKernelGGL(mjb_metrics_kernel, dim3(1), dim3(256), 0, b->stream, b->st.qacc, b->st.qvel, b->st.time, b->st.energy,
-	                   b->st.nwarn, b->nenv, b->model->h.nv, (double)b->nenv * (double)b->steps_taken, b->metrics_dev);
+	hipLaunchKernelGGL(mjb_metrics_kernel, dim3(1), dim3(256), 0, b->stream.get(), b->st.qacc, b->st.qvel, b->st.time, b->st.energy,
+	                   b->st.nwarn, b->nenv, b->model->h.nv, (double)b->nenv * (double)b->steps_taken, b->metrics_dev.get());
 	if (hipGetLastError() != hipSuccess) {
 		fail(MJB_ENODEVICE, "mjb_metrics: launch failed");
 		return nullptr;
 	}
-	return b->metrics_dev;
+	return b->metrics_dev.get();
 }
 
 int mjb_metrics(mjb_batch *b, double *out16)
@@ -1867,37 +1707,37 @@ int mjb_metrics(mjb_batch *b, double *out16)
 	if (!b || !out16) return fail(MJB_EINVAL, "mjb_metrics: bad argument");
 	void *p = mjb_metrics_device(b);
 	if (!p) return MJB_ENODEVICE;
-	HIP_TRY(hipStreamSynchronize(b->stream));
+	HIP_TRY(hipStreamSynchronize(b->stream.get()));
 	HIP_TRY(hipMemcpy(out16, p, 16 * sizeof(double), hipMemcpyDeviceToHost));
 	return MJB_OK;
 }
 
 // ---- per-env model parameters (the subset that needs no mj_setConst) ----
-static int env_param(mjb_batch *b, double **arr, const double **slot, int per_env, const double *model_vals, int env_lo, int env_hi,
+static int env_param(mjb_batch *b, DevBuf<double> &arr, const double *&view, int per_env, const double *model_vals, int env_lo, int env_hi,
                      const double *vals, const char *what)
 {
 	if (!b || !vals) return fail(MJB_EINVAL, "%s: bad argument", what);
 	if (env_lo < 0 || env_hi > b->nenv || env_lo > env_hi) return fail(MJB_EINVAL, "%s: bad env range", what);
 	if (per_env <= 0) return fail(MJB_EINVAL, "%s: the model has nothing to override", what);
 	HIP_TRY(hipSetDevice(b->device));
-	HIP_TRY(hipStreamSynchronize(b->stream));
-	if (!*arr) {  // first use: every env starts from the model's values
-		*arr = dev_alloc<double>((size_t)b->nenv * per_env);
-		if (!*arr) return fail(MJB_ENOMEM, "%s: allocation failed", what);
+	HIP_TRY(hipStreamSynchronize(b->stream.get()));
+	if (!arr) {  // first use: every env starts from the model's values (uploaded for every env: no zeroing)
+		DevBuf<double> dev;
+		if (!dev.alloc((size_t)b->nenv * per_env)) return fail(MJB_ENOMEM, "%s: allocation failed", what);
 		std::vector<double> init((size_t)b->nenv * per_env);
 		for (int e = 0; e < b->nenv; e++) memcpy(init.data() + (size_t)e * per_env, model_vals, (size_t)per_env * sizeof(double));
-		HIP_TRY(hipMemcpy(*arr, init.data(), init.size() * sizeof(double), hipMemcpyHostToDevice));
-		*slot = *arr;
-		b->params_dirty = true;
+		HIP_TRY(hipMemcpy(dev.get(), init.data(), init.size() * sizeof(double), hipMemcpyHostToDevice));
+		arr = std::move(dev);
+		set_view(b, view, arr.get());
 	}
-	HIP_TRY(hipMemcpy(*arr + (size_t)env_lo * per_env, vals, (size_t)(env_hi - env_lo) * per_env * sizeof(double), hipMemcpyHostToDevice));
+	HIP_TRY(hipMemcpy(arr.get() + (size_t)env_lo * per_env, vals, (size_t)(env_hi - env_lo) * per_env * sizeof(double), hipMemcpyHostToDevice));
 	return MJB_OK;
 }
 
 int mjb_set_env_gravity(mjb_batch *b, int env_lo, int env_hi, const double *gravity)
 {
 	if (!b) return fail(MJB_EINVAL, "null batch");
-	const int rc = env_param(b, &b->env_gravity, &b->st.env_gravity, 3, b->model->h.gravity, env_lo, env_hi, gravity, "mjb_set_env_gravity");
+	const int rc = env_param(b, b->env_gravity, b->st.env_gravity, 3, b->model->h.gravity, env_lo, env_hi, gravity, "mjb_set_env_gravity");
 	if (rc == MJB_OK) le_overlay_touch(b, env_lo, env_hi);
 	return rc;
 }
@@ -1906,7 +1746,7 @@ int mjb_set_env_geom_friction(mjb_batch *b, int env_lo, int env_hi, const double
 {
 	if (!b) return fail(MJB_EINVAL, "null batch");
 	const mjb_model_desc &h = b->model->h;
-	return env_param(b, &b->env_geom_friction, &b->st.env_geom_friction, h.nconmax > 0 ? 3 * h.ngeom : 0, h.geom_friction, env_lo,
+	return env_param(b, b->env_geom_friction, b->st.env_geom_friction, h.nconmax > 0 ? 3 * h.ngeom : 0, h.geom_friction, env_lo,
 	                 env_hi, friction, "mjb_set_env_geom_friction");
 }
 
@@ -1914,7 +1754,7 @@ int mjb_set_env_geom_size(mjb_batch *b, int env_lo, int env_hi, const double *si
 {
 	if (!b) return fail(MJB_EINVAL, "null batch");
 	const mjb_model_desc &h = b->model->h;
-	return env_param(b, &b->env_geom_size, &b->st.env_geom_size, h.nconmax > 0 ? 3 * h.ngeom : 0, h.geom_size, env_lo, env_hi, size,
+	return env_param(b, b->env_geom_size, b->st.env_geom_size, h.nconmax > 0 ? 3 * h.ngeom : 0, h.geom_size, env_lo, env_hi, size,
 	                 "mjb_set_env_geom_size");
 }
 
@@ -1929,17 +1769,17 @@ int mjb_set_env_geom_type(mjb_batch *b, int env_lo, int env_hi, const int *type)
 		    type[k] != 4 && type[k] != 5)  // (mjGEOM_ELLIPSOID / mjGEOM_CYLINDER are accepted as "no pair function": the geom yields no contacts)
 			return fail(MJB_EUNSUPPORTED, "mjb_set_env_geom_type: geom type %d is neither a primitive of the engine nor ellipsoid / cylinder", type[k]);
 	HIP_TRY(hipSetDevice(b->device));
-	HIP_TRY(hipStreamSynchronize(b->stream));
+	HIP_TRY(hipStreamSynchronize(b->stream.get()));
 	if (!b->env_geom_type) {
-		b->env_geom_type = dev_alloc<int>((size_t)b->nenv * h.ngeom);
-		if (!b->env_geom_type) return fail(MJB_ENOMEM, "mjb_set_env_geom_type: allocation failed");
+		DevBuf<int> dev;
+		if (!dev.alloc((size_t)b->nenv * h.ngeom)) return fail(MJB_ENOMEM, "mjb_set_env_geom_type: allocation failed");  // (uploaded for every env)
 		std::vector<int> init((size_t)b->nenv * h.ngeom);
 		for (int e = 0; e < b->nenv; e++) memcpy(init.data() + (size_t)e * h.ngeom, h.geom_type, (size_t)h.ngeom * sizeof(int));
-		HIP_TRY(hipMemcpy(b->env_geom_type, init.data(), init.size() * sizeof(int), hipMemcpyHostToDevice));
-		b->st.env_geom_type = b->env_geom_type;
-		b->params_dirty = true;
+		HIP_TRY(hipMemcpy(dev.get(), init.data(), init.size() * sizeof(int), hipMemcpyHostToDevice));
+		b->env_geom_type = std::move(dev);
+		set_view(b, b->st.env_geom_type, b->env_geom_type.get());
 	}
-	HIP_TRY(hipMemcpy(b->env_geom_type + (size_t)env_lo * h.ngeom, type, (size_t)(env_hi - env_lo) * h.ngeom * sizeof(int), hipMemcpyHostToDevice));
+	HIP_TRY(hipMemcpy(b->env_geom_type.get() + (size_t)env_lo * h.ngeom, type, (size_t)(env_hi - env_lo) * h.ngeom * sizeof(int), hipMemcpyHostToDevice));
 	return MJB_OK;
 }
 
@@ -1955,7 +1795,7 @@ int mjb_set_env_equality(mjb_batch *b, int env_lo, int env_hi, const double *par
 		for (int k = 0; k < 2; k++) o[12 + k] = h.eq_solref[2 * q + k];
 		for (int k = 0; k < 5; k++) o[14 + k] = h.eq_solimp[5 * q + k];
 	}
-	return env_param(b, &b->env_equality, &b->st.env_equality, 19 * h.neq, packed.data(), env_lo, env_hi, params, "mjb_set_env_equality");
+	return env_param(b, b->env_equality, b->st.env_equality, 19 * h.neq, packed.data(), env_lo, env_hi, params, "mjb_set_env_equality");
 }
 
 // The env's block of inertial, joint and actuator constants (DevState::env_mass, mjb_dev.h): one allocation, mirrored on the host.  The
@@ -2012,17 +1852,13 @@ static int env_block_ensure(mjb_batch *b, const char *what)
 	}
 	for (int j = 0; j < h.njnt; j++) o[B.stiffness() + j] = h.jnt_stiffness[j];
 	for (int k = 0; k < 3 * h.nu; k++) { o[B.gainprm() + k] = h.actuator_gainprm[k]; o[B.biasprm() + k] = h.actuator_biasprm[k]; }
-	double *dev = dev_alloc<double>((size_t)b->nenv * B.stride);
-	if (!dev) return fail(MJB_ENOMEM, "%s: allocation failed", what);
+	DevBuf<double> dev;
+	if (!dev.alloc((size_t)b->nenv * B.stride)) return fail(MJB_ENOMEM, "%s: allocation failed", what);  // (uploaded for every env)
 	std::vector<double> init((size_t)b->nenv * B.stride);
 	for (int e = 0; e < b->nenv; e++) memcpy(init.data() + (size_t)e * B.stride, o, (size_t)B.stride * sizeof(double));
-	if (hipMemcpy(dev, init.data(), init.size() * sizeof(double), hipMemcpyHostToDevice) != hipSuccess) {
-		hipFree(dev);
-		return fail(MJB_ENODEVICE, "%s: upload failed", what);
-	}
-	b->env_mass = dev;
-	b->st.env_mass = dev;
-	b->params_dirty = true;
+	if (hipMemcpy(dev.get(), init.data(), init.size() * sizeof(double), hipMemcpyHostToDevice) != hipSuccess) return fail(MJB_ENODEVICE, "%s: upload failed", what);
+	b->env_mass = std::move(dev);
+	set_view(b, b->st.env_mass, b->env_mass.get());
 	return MJB_OK;
 }
 
@@ -2032,7 +1868,7 @@ static int env_block_mirror(mjb_batch *b)
 	if (!b->env_block.empty()) return MJB_OK;
 	const size_t n = (size_t)b->nenv * EnvBlock(b->model->h).stride;
 	b->env_block.resize(n);
-	if (hipMemcpy(b->env_block.data(), b->env_mass, n * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess) {
+	if (hipMemcpy(b->env_block.data(), b->env_mass.get(), n * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess) {
 		b->env_block.clear();
 		return fail(MJB_ENODEVICE, "reading the per-env constants back failed");
 	}
@@ -2042,7 +1878,7 @@ static int env_block_mirror(mjb_batch *b)
 static int env_block_upload(mjb_batch *b, int env_lo, int env_hi)
 {
 	const size_t stride = (size_t)EnvBlock(b->model->h).stride;
-	HIP_TRY(hipMemcpy(b->env_mass + (size_t)env_lo * stride, b->env_block.data() + (size_t)env_lo * stride, (size_t)(env_hi - env_lo) * stride * sizeof(double),
+	HIP_TRY(hipMemcpy(b->env_mass.get() + (size_t)env_lo * stride, b->env_block.data() + (size_t)env_lo * stride, (size_t)(env_hi - env_lo) * stride * sizeof(double),
 	                  hipMemcpyHostToDevice));
 	le_overlay_touch(b, env_lo, env_hi);
 	return MJB_OK;
@@ -2056,14 +1892,14 @@ int mjb_set_env_mass_params(mjb_batch *b, int env_lo, int env_hi, const double *
 	if (env_lo < 0 || env_hi > b->nenv || env_lo > env_hi) return fail(MJB_EINVAL, "%s: bad env range", what);
 	const EnvBlock B(b->model->h);
 	HIP_TRY(hipSetDevice(b->device));
-	HIP_TRY(hipStreamSynchronize(b->stream));
+	HIP_TRY(hipStreamSynchronize(b->stream.get()));
 	const int rc = env_block_ensure(b, what);
 	if (rc != MJB_OK) return rc;
 	if (!b->env_block.empty())
 		for (int e = env_lo; e < env_hi; e++)
 			memcpy(b->env_block.data() + (size_t)e * B.stride, params + (size_t)(e - env_lo) * B.jnt0, (size_t)B.jnt0 * sizeof(double));
 	if (env_hi > env_lo)  // the mass section of each env's row: rows of jnt0 doubles into rows of stride doubles
-		HIP_TRY(hipMemcpy2D(b->env_mass + (size_t)env_lo * B.stride, (size_t)B.stride * sizeof(double), params, (size_t)B.jnt0 * sizeof(double),
+		HIP_TRY(hipMemcpy2D(b->env_mass.get() + (size_t)env_lo * B.stride, (size_t)B.stride * sizeof(double), params, (size_t)B.jnt0 * sizeof(double),
 		                    (size_t)B.jnt0 * sizeof(double), (size_t)(env_hi - env_lo), hipMemcpyHostToDevice));
 	le_overlay_touch(b, env_lo, env_hi);
 	return MJB_OK;
@@ -2158,8 +1994,8 @@ static int env_joint_set(mjb_batch *b, int env_lo, int env_hi, const double *dam
 				}
 	}
 	HIP_TRY(hipSetDevice(b->device));
-	if (b->env_mass) {
-		HIP_TRY(hipStreamSynchronize(b->stream));
+	if (b->env_mass.get()) {
+		HIP_TRY(hipStreamSynchronize(b->stream.get()));
 		if ((rc = env_block_mirror(b)) != MJB_OK) return rc;
 	}
 	// the model's frames hold M + h B and its factor only when mjb_compile found something to put there (DevModel::eulerdamp)
@@ -2179,7 +2015,7 @@ static int env_joint_set(mjb_batch *b, int env_lo, int env_hi, const double *dam
 		}
 	}
 	HIP_TRY(hipSetDevice(b->device));
-	HIP_TRY(hipStreamSynchronize(b->stream));
+	HIP_TRY(hipStreamSynchronize(b->stream.get()));
 	if ((rc = env_block_ensure(b, what)) != MJB_OK) return rc;
 	if ((rc = env_block_mirror(b)) != MJB_OK) return rc;
 	std::vector<double> saved;  // (a failed derivation -- a singular inertia -- restores the rows)
@@ -2251,16 +2087,10 @@ int mjb_hwsim_configure(mjb_batch *b, int n, const mjb_hwsim_joint *joints)
 			return fail(MJB_EINVAL, "mjb_hwsim_configure: entry %d: bad control method / joint kind", k);
 	}
 	HIP_TRY(hipSetDevice(b->device));
-	HIP_TRY(hipStreamSynchronize(b->stream));
-	if (b->hw_ints) hipFree(b->hw_ints);
-	if (b->hw_gains) hipFree(b->hw_gains);
-	if (b->hw_cmd) hipFree(b->hw_cmd);
-	if (b->hw_pid) hipFree(b->hw_pid);
-	if (b->hw_cad) hipFree(b->hw_cad);
-	b->hw_ints = nullptr; b->hw_gains = nullptr; b->hw_cmd = nullptr; b->hw_pid = nullptr; b->hw_cad = nullptr;
-	b->hw = HwSim{};
+	HIP_TRY(hipStreamSynchronize(b->stream.get()));
+	b->hwb = HwSimBufs{};
+	set_view(b, b->hw, HwSim{});
 	b->hw_le_ok = false;
-	b->params_dirty = true;
 	if (n == 0) return MJB_OK;
 	// (behind the [n] arrays: the same entries by dof for the lane = env kernel, HwSim::le_tab / le_gains; a dof two entries claim has no such table)
 	const int nv = h.nv;
@@ -2279,23 +2109,22 @@ int mjb_hwsim_configure(mjb_batch *b, int n, const mjb_hwsim_joint *joints)
 		for (int q = 0; q < 8; q++) gains[(size_t)8 * n + (size_t)8 * h.jnt_dofadr[j.joint] + q] = g[q];
 	}
 	const size_t per = (size_t)b->nenv * n;
-	b->hw_ints = dev_alloc<int>(ints.size());
-	b->hw_gains = dev_alloc<double>(gains.size());
-	b->hw_cmd = dev_alloc<double>(4 * per);
-	b->hw_pid = dev_alloc<double>(2 * per);
-	if (!b->hw_ints || !b->hw_gains || !b->hw_cmd || !b->hw_pid) return fail(MJB_ENOMEM, "mjb_hwsim_configure: allocation failed");
-	HIP_TRY(hipMemcpy(b->hw_ints, ints.data(), ints.size() * sizeof(int), hipMemcpyHostToDevice));
-	HIP_TRY(hipMemcpy(b->hw_gains, gains.data(), gains.size() * sizeof(double), hipMemcpyHostToDevice));
-	HIP_TRY(hipMemset(b->hw_cmd, 0, 4 * per * sizeof(double)));
-	HIP_TRY(hipMemset(b->hw_pid, 0, 2 * per * sizeof(double)));
-	b->hw.n = n;
-	b->hw.estop = 0;
-	b->hw.joint = b->hw_ints; b->hw.method = b->hw_ints + n; b->hw.kind = b->hw_ints + 2 * n; b->hw.antiwindup = b->hw_ints + 3 * n;
-	b->hw.gains = b->hw_gains;
-	b->hw.le_tab = (mjb_ciptr)(b->hw_ints + 4 * n);
-	b->hw.le_gains = (mjb_cdptr)(b->hw_gains + (size_t)8 * n);
-	b->hw.cmd_pos = b->hw_cmd; b->hw.cmd_vel = b->hw_cmd + per; b->hw.cmd_eff = b->hw_cmd + 2 * per; b->hw.cmd_hold = b->hw_cmd + 3 * per;
-	b->hw.pid = b->hw_pid;
+	HwSimBufs &B = b->hwb;
+	if (!B.ints.alloc(ints.size()) || !B.gains.alloc(gains.size()) /* (both uploaded whole) */ || !B.cmd.alloc_zeroed(4 * per) || !B.pid.alloc_zeroed(2 * per)) {
+		B = HwSimBufs{};
+		return fail(MJB_ENOMEM, "mjb_hwsim_configure: allocation failed");
+	}
+	HIP_TRY(hipMemcpy(B.ints.get(), ints.data(), ints.size() * sizeof(int), hipMemcpyHostToDevice));
+	HIP_TRY(hipMemcpy(B.gains.get(), gains.data(), gains.size() * sizeof(double), hipMemcpyHostToDevice));
+	HwSim hw{};
+	hw.n = n;
+	hw.joint = B.ints.get(); hw.method = B.ints.get() + n; hw.kind = B.ints.get() + 2 * n; hw.antiwindup = B.ints.get() + 3 * n;
+	hw.gains = B.gains.get();
+	hw.le_tab = (mjb_ciptr)(B.ints.get() + 4 * n);
+	hw.le_gains = (mjb_cdptr)(B.gains.get() + (size_t)8 * n);
+	hw.cmd_pos = B.cmd.get(); hw.cmd_vel = B.cmd.get() + per; hw.cmd_eff = B.cmd.get() + 2 * per; hw.cmd_hold = B.cmd.get() + 3 * per;
+	hw.pid = B.pid.get();
+	set_view(b, b->hw, hw);
 	return MJB_OK;
 }
 
@@ -2305,9 +2134,9 @@ int mjb_hwsim_set_command(mjb_batch *b, int which, int env_lo, int env_hi, const
 	if (b->hw.n <= 0) return fail(MJB_EINVAL, "mjb_hwsim_set_command before mjb_hwsim_configure");
 	if (env_lo < 0 || env_hi > b->nenv || env_lo > env_hi) return fail(MJB_EINVAL, "mjb_hwsim_set_command: bad env range");
 	HIP_TRY(hipSetDevice(b->device));
-	HIP_TRY(hipStreamSynchronize(b->stream));
+	HIP_TRY(hipStreamSynchronize(b->stream.get()));
 	const size_t per = (size_t)b->nenv * b->hw.n;
-	HIP_TRY(hipMemcpy(b->hw_cmd + which * per + (size_t)env_lo * b->hw.n, cmd, (size_t)(env_hi - env_lo) * b->hw.n * sizeof(double),
+	HIP_TRY(hipMemcpy(b->hwb.cmd.get() + which * per + (size_t)env_lo * b->hw.n, cmd, (size_t)(env_hi - env_lo) * b->hw.n * sizeof(double),
 	                  hipMemcpyHostToDevice));
 	return MJB_OK;
 }
@@ -2315,7 +2144,7 @@ int mjb_hwsim_set_command(mjb_batch *b, int which, int env_lo, int env_hi, const
 void *mjb_hwsim_command_ptr(mjb_batch *b, int which)
 {
 	if (!b || which < 0 || which > 2 || b->hw.n <= 0) return nullptr;
-	return b->hw_cmd + (size_t)which * b->nenv * b->hw.n;
+	return b->hwb.cmd.get() + (size_t)which * b->nenv * b->hw.n;
 }
 
 // MujocoRosControlPlugin::controlCallback's cadence (mujoco_ros_control_plugin.cpp:153-194) for the device-side stage: with a control
@@ -2332,24 +2161,22 @@ int mjb_hwsim_set_period(mjb_batch *b, double control_period)
 		fprintf(stderr, "mjb_hwsim_set_period: desired controller update period (%g s) is faster than the simulation timestep (%g s)\n",
 		        control_period, b->model->h.timestep[0]);
 	HIP_TRY(hipSetDevice(b->device));
-	HIP_TRY(hipStreamSynchronize(b->stream));
+	HIP_TRY(hipStreamSynchronize(b->stream.get()));
 	const int n = b->hw.n;
 	if (control_period > 0) {
 		const size_t per = 2 + 2 * (size_t)n;
 		std::vector<double> init((size_t)b->nenv * per, 0.0);
 		for (int e = 0; e < b->nenv; e++)
 			for (int k = 0; k < n; k++) init[(size_t)e * per + 2 + k] = 1.0;  // joint_position_ starts at 1.0 (default_robot_hw_sim.cpp:129)
-		if (!b->hw_cad) b->hw_cad = dev_alloc<double>(init.size());
-		if (!b->hw_cad) return fail(MJB_ENOMEM, "mjb_hwsim_set_period: allocation failed");
-		HIP_TRY(hipMemcpy(b->hw_cad, init.data(), init.size() * sizeof(double), hipMemcpyHostToDevice));
+		if (!b->hwb.cad && !b->hwb.cad.alloc(init.size())) return fail(MJB_ENOMEM, "mjb_hwsim_set_period: allocation failed");  // (uploaded whole below)
+		HIP_TRY(hipMemcpy(b->hwb.cad.get(), init.data(), init.size() * sizeof(double), hipMemcpyHostToDevice));
 		const double sec = std::floor(control_period);
 		b->hw.period_ns = (long long)sec * 1000000000LL + (long long)std::floor((control_period - sec) * 1e9 + 0.5);
-		b->hw.cad = b->hw_cad;
+		set_view(b, b->hw.cad, b->hwb.cad.get());
 	} else {
 		b->hw.period_ns = 0;
-		b->hw.cad = nullptr;
+		set_view(b, b->hw.cad, nullptr);
 	}
-	b->params_dirty = true;
 	return MJB_OK;
 }
 
@@ -2360,10 +2187,10 @@ int mjb_hwsim_estop(mjb_batch *b, int active)
 	const int on = active ? 1 : 0;
 	if (on == b->hw.estop) return MJB_OK;
 	HIP_TRY(hipSetDevice(b->device));
-	HIP_TRY(hipStreamSynchronize(b->stream));
+	HIP_TRY(hipStreamSynchronize(b->stream.get()));
 	if (on) {  // position-controlled joints hold the command they had when the e-stop came (default_robot_hw_sim.cpp:251-258)
 		const size_t per = (size_t)b->nenv * b->hw.n;
-		HIP_TRY(hipMemcpy(b->hw_cmd + 3 * per, b->hw_cmd, per * sizeof(double), hipMemcpyDeviceToDevice));
+		HIP_TRY(hipMemcpy(b->hwb.cmd.get() + 3 * per, b->hwb.cmd.get(), per * sizeof(double), hipMemcpyDeviceToDevice));
 	}
 	b->hw.estop = on;
 	b->params_dirty = true;
@@ -2380,14 +2207,11 @@ static int sensor_buffers(mjb_batch *b)
 		b->sens_mean.assign(3 * ns, 0.0);
 		b->sens_sigma.assign(3 * ns, 0.0);
 	}
-	if (!b->sens_value) {
-		b->sens_flag_dev = dev_alloc<int>(ns);
-		b->sens_mean_dev = dev_alloc<double>(3 * ns);
-		b->sens_sigma_dev = dev_alloc<double>(3 * ns);
-		b->sens_value = dev_alloc<float>(nd);
-		b->sens_truth = dev_alloc<float>(nd);
-		if (!b->sens_flag_dev || !b->sens_mean_dev || !b->sens_sigma_dev || !b->sens_value || !b->sens_truth)
+	if (!b->sens.truth) {
+		if (!b->sens.alloc(ns, nd)) {
+			b->sens = SensorBufs{};
 			return fail(MJB_ENOMEM, "sensor message buffers: allocation failed");
+		}
 		b->sens_dirty = true;
 	}
 	return MJB_OK;
@@ -2426,14 +2250,14 @@ int mjb_sensor_pack(mjb_batch *b, uint64_t seed)
 	rc = sync_params(b);
 	if (rc) return rc;
 	if (b->sens_dirty) {
-		HIP_TRY(hipStreamSynchronize(b->stream));
-		HIP_TRY(hipMemcpy(b->sens_flag_dev, b->sens_flag.data(), b->sens_flag.size() * sizeof(int), hipMemcpyHostToDevice));
-		HIP_TRY(hipMemcpy(b->sens_mean_dev, b->sens_mean.data(), b->sens_mean.size() * sizeof(double), hipMemcpyHostToDevice));
-		HIP_TRY(hipMemcpy(b->sens_sigma_dev, b->sens_sigma.data(), b->sens_sigma.size() * sizeof(double), hipMemcpyHostToDevice));
+		HIP_TRY(hipStreamSynchronize(b->stream.get()));
+		HIP_TRY(hipMemcpy(b->sens.flag.get(), b->sens_flag.data(), b->sens_flag.size() * sizeof(int), hipMemcpyHostToDevice));
+		HIP_TRY(hipMemcpy(b->sens.mean.get(), b->sens_mean.data(), b->sens_mean.size() * sizeof(double), hipMemcpyHostToDevice));
+		HIP_TRY(hipMemcpy(b->sens.sigma.get(), b->sens_sigma.data(), b->sens_sigma.size() * sizeof(double), hipMemcpyHostToDevice));
 		b->sens_dirty = false;
 	}
-	rc = mjb_launch_sensor_pack(b->params_dev, b->nenv, h.nsensor, b->sens_flag_dev, b->sens_mean_dev, b->sens_sigma_dev, seed,
-	                            b->nz.env_offset, b->step_counter, b->sens_value, b->sens_truth, b->stream);
+	rc = mjb_launch_sensor_pack(b->params_dev.get(), b->nenv, h.nsensor, b->sens.flag.get(), b->sens.mean.get(), b->sens.sigma.get(), seed,
+	                            b->nz.env_offset, b->step_counter, b->sens.value.get(), b->sens.truth.get(), b->stream.get());
 	if (rc != 0) return fail(MJB_ENODEVICE, "sensor pack launch failed: %s", hipGetErrorString((hipError_t)rc));
 	b->sens_packed = true;
 	return MJB_OK;
@@ -2446,8 +2270,8 @@ int mjb_sensor_get(mjb_batch *b, int which, int env_lo, int env_hi, float *host)
 	if (env_lo < 0 || env_hi > b->nenv || env_lo > env_hi) return fail(MJB_EINVAL, "mjb_sensor_get: bad env range");
 	const size_t S = (size_t)b->model->h.nsensordata;
 	HIP_TRY(hipSetDevice(b->device));
-	HIP_TRY(hipStreamSynchronize(b->stream));
-	const float *src = (which == 0 ? b->sens_value : b->sens_truth) + (size_t)env_lo * S;
+	HIP_TRY(hipStreamSynchronize(b->stream.get()));
+	const float *src = (which == 0 ? b->sens.value.get() : b->sens.truth.get()) + (size_t)env_lo * S;
 	HIP_TRY(hipMemcpy(host, src, (size_t)(env_hi - env_lo) * S * sizeof(float), hipMemcpyDeviceToHost));
 	return MJB_OK;
 }
@@ -2455,27 +2279,25 @@ int mjb_sensor_get(mjb_batch *b, int which, int env_lo, int env_hi, float *host)
 void *mjb_sensor_device_ptr(mjb_batch *b, int which)
 {
 	if (!b || which < 0 || which > 1 || sensor_buffers(b) != MJB_OK) return nullptr;
-	return which == 0 ? (void *)b->sens_value : (void *)b->sens_truth;
+	return which == 0 ? (void *)b->sens.value.get() : (void *)b->sens.truth.get();
 }
 
 int mjb_time_steps(mjb_batch *b, int nsteps, int nlaunch, double *ms_per_launch)
 {
 	if (!b || nsteps <= 0 || nlaunch <= 0 || !ms_per_launch) return fail(MJB_EINVAL, "mjb_time_steps: bad argument");
 	HIP_TRY(hipSetDevice(b->device));
-	hipEvent_t e0, e1;
-	HIP_TRY(hipEventCreate(&e0));
-	HIP_TRY(hipEventCreate(&e1));
-	HIP_TRY(hipEventRecord(e0, b->stream));
+	Event e0, e1;
+	HIP_TRY(e0.create(hipEventDefault));
+	HIP_TRY(e1.create(hipEventDefault));
+	HIP_TRY(hipEventRecord(e0.get(), b->stream.get()));
 	for (int i = 0; i < nlaunch; i++) {
 		int rc = mjb_step(b, nsteps);
 		if (rc) return rc;
 	}
-	HIP_TRY(hipEventRecord(e1, b->stream));
-	HIP_TRY(hipEventSynchronize(e1));
+	HIP_TRY(hipEventRecord(e1.get(), b->stream.get()));
+	HIP_TRY(hipEventSynchronize(e1.get()));
 	float ms = 0;
-	HIP_TRY(hipEventElapsedTime(&ms, e0, e1));
-	hipEventDestroy(e0);
-	hipEventDestroy(e1);
+	HIP_TRY(hipEventElapsedTime(&ms, e0.get(), e1.get()));
 	*ms_per_launch = (double)ms / nlaunch;
 	return MJB_OK;
 }

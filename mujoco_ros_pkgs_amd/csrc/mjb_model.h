@@ -27,6 +27,18 @@ int field_slot(const FrameLayout &L, int i);
 // the value of a size of the description by its name in the .def tables ("one": 1, a literal: itself)
 int size_by_name(const mjb_model_desc &d, const char *n);
 
+// The device model blob, built on the host (mjb_model.hip, one list of tables): what mjb_make_batch uploads as it stands.
+struct mjb_model;
+struct ModelBlob {
+	std::vector<unsigned char> image;  // [ints | doubles]
+	size_t dbl_offset = 0;             // byte offset of the double part
+	size_t pair_i_offset = 0;          // ... of the per-pair int records (mjb_register_collision patches them on the device)
+	DevModel dm{};                     // sizes, options and derived scalars filled in; every pointer member holds its table's byte offset into the image (all ones: a null pointer, the absent tape)
+};
+ModelBlob build_model_blob(const mjb_model &M);
+// ... and once the image sits at `base`: the pointer members of dm, from offsets to addresses
+void rebase_model_blob(const mjb_model &M, DevModel &dm, const void *base);
+
 #pragma GCC visibility pop
 
 struct mjb_model {

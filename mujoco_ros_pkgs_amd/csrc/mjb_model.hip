@@ -1631,6 +1631,143 @@ int mjb_derive_mass_params_armature(const mjb_model *model, const double *body_m
 
 }  // extern "C"
 
+// ---- the device model blob: [ints | doubles].  The arrays of the description come first in each part (hint / hdbl, where ioff / doff put them);
+// behind them the derived tables, each named ONCE below, in blob order: the image's size, the copies, the offsets in the DevModel, the rebase onto the
+// device address and mjb_debug_blob_digest all walk these two lists.
+namespace {
+struct IntTable {
+	std::vector<int> mjb_model::*src;
+	mjb_ciptr DevModel::*dst;
+};
+struct DblTable {
+	std::vector<double> mjb_model::*src;
+	mjb_cdptr DevModel::*dst;
+	bool tape;  // starts on a 64-byte boundary of the blob (wide scalar loads off one base); a null pointer when empty
+};
+#define T(src, dst) { &mjb_model::src, &DevModel::dst }
+const IntTable kIntTables[] = {  // each on a 16-byte boundary (wide scalar loads)
+	T(M_rowdof, M_rowdof), T(M_coldof, M_coldof), T(dof_depth, dof_depth), T(dof_jstart, dof_jstart), T(body_rec, body_rec), T(body_rec2, body_rec2),
+	T(dof_rec, dof_rec), T(fac_ops, fac_ops), T(fac_beg, fac_beg), T(body_dofmask, body_dofmask), T(body_submask, body_submask), T(M_dense, M_dense),
+	T(M_sym, M_sym), T(body_anc, body_anc), T(dof_bodymask, dof_bodymask), T(sens_copy, sens_copy), T(sens_slow, sens_slow), T(dof_act_adr, dof_act_adr),
+	T(dof_act_id, dof_act_id), T(pair_i, pair_i), T(lim_i, lim_i), T(body_dofanc, body_dofanc), T(dof_rec2, dof_rec2), T(jnt_rec, jnt_rec),
+	T(flv_hdr, flv_hdr), T(flv_rec, flv_rec), T(flv_ent, flv_ent), T(site_act, site_act), T(gravcomp_body, gravcomp_body),
+};
+#undef T
+const DblTable kDblTables[] = {
+	{ &mjb_model::pair_d, &DevModel::pair_d, false },    { &mjb_model::lim_d, &DevModel::lim_d, false },
+	{ &mjb_model::sub_S, &DevModel::sub_S, false },      { &mjb_model::damp_int, &DevModel::dof_damping_int, false },
+	{ &mjb_model::dof_act_mom, &DevModel::dof_act_mom, false }, { &mjb_model::le_tape, &DevModel::le_tape, true },
+};
+// The double part has always started this many ints behind the int tables' unpadded sizes (once a bound on their alignment padding).  Kept as a
+// constant of the layout: the offsets of the double tables, and with them the tape's position, stay the ones every measurement was taken on.
+const size_t kIntPartSlack = 112;
+static_assert(3 * (sizeof kIntTables / sizeof kIntTables[0]) <= kIntPartSlack, "the int tables' alignment padding (at most 3 ints each) must fit the gap");
+const size_t kTailBytes = 16;  // behind the last table, as ever: a 16-byte load that starts inside it ends inside the allocation
+const uintptr_t kNullOffset = ~(uintptr_t)0;
+
+// f(pointer member, elements of its table, the alignment in bytes the layout promises it) for every pointer member of a DevModel: the description's
+// arrays, then the two lists
+template <typename DM, typename F> void each_blob_pointer(const mjb_model &M, DM &dm, F f)
+{
+	const mjb_model_desc &h = M.h;
+#define MJB_SIZE(name)
+#define MJB_OPT_I(name)
+#define MJB_OPT_D(name, n)
+#define MJB_ARR_I(name, rows, cols) f(dm.name, (size_t)h.rows * (cols), sizeof(int));
+#define MJB_ARR_D(name, rows, cols) f(dm.name, (size_t)h.rows * (cols), sizeof(double));
+#include "../../include/mjb_model_fields.def"
+#undef MJB_SIZE
+#undef MJB_OPT_I
+#undef MJB_OPT_D
+#undef MJB_ARR_I
+#undef MJB_ARR_D
+	for (const IntTable &t : kIntTables) f(dm.*t.dst, (M.*t.src).size(), (size_t)16);
+	for (const DblTable &t : kDblTables) f(dm.*t.dst, (M.*t.src).size(), t.tape ? (size_t)64 : sizeof(double));
+}
+template <typename P> void set_offset(P &p, uintptr_t off) { p = (P)off; }
+}  // namespace
+
+ModelBlob build_model_blob(const mjb_model &M)
+{
+	ModelBlob B;
+	const mjb_model_desc &h = M.h;
+	const size_t ni = M.hint.size(), nd = M.hdbl.size();
+	// where everything goes (ints from the image's start, doubles from the double part's)
+	size_t it = ni, unpadded = ni;
+	std::vector<size_t> iat, dat;
+	for (const IntTable &t : kIntTables) {
+		it = (it + 3) & ~size_t(3);
+		iat.push_back(it);
+		it += (M.*t.src).size();
+		unpadded += (M.*t.src).size();
+	}
+	B.dbl_offset = ((unpadded + kIntPartSlack) * sizeof(int) + 15) & ~size_t(15);
+	size_t dt = nd;
+	for (const DblTable &t : kDblTables) {
+		const size_t n = (M.*t.src).size();
+		while (t.tape && n && (B.dbl_offset + dt * sizeof(double)) % 64) dt++;
+		dat.push_back(dt);
+		dt += n;
+	}
+	B.image.assign(B.dbl_offset + dt * sizeof(double) + kTailBytes, 0);
+	int *hi = reinterpret_cast<int *>(B.image.data());
+	double *hd = reinterpret_cast<double *>(B.image.data() + B.dbl_offset);
+	if (ni) memcpy(hi, M.hint.data(), ni * sizeof(int));
+	if (nd) memcpy(hd, M.hdbl.data(), nd * sizeof(double));
+	DevModel &dm = B.dm;
+	{
+		size_t ii = 0, dj = 0;
+#define MJB_SIZE(name) dm.name = h.name;
+#define MJB_OPT_I(name) dm.name = h.name;
+#define MJB_OPT_D(name, n) for (int k = 0; k < n; k++) dm.name[k] = h.name[k];
+#define MJB_ARR_I(name, rows, cols) set_offset(dm.name, M.ioff[ii++] * sizeof(int));
+#define MJB_ARR_D(name, rows, cols) set_offset(dm.name, B.dbl_offset + M.doff[dj++] * sizeof(double));
+#include "../../include/mjb_model_fields.def"
+#undef MJB_SIZE
+#undef MJB_OPT_I
+#undef MJB_OPT_D
+#undef MJB_ARR_I
+#undef MJB_ARR_D
+	}
+	for (size_t k = 0; k < iat.size(); k++) {
+		const std::vector<int> &v = M.*kIntTables[k].src;
+		if (!v.empty()) memcpy(hi + iat[k], v.data(), v.size() * sizeof(int));
+		set_offset(dm.*kIntTables[k].dst, iat[k] * sizeof(int));
+	}
+	for (size_t k = 0; k < dat.size(); k++) {
+		const std::vector<double> &v = M.*kDblTables[k].src;
+		if (!v.empty()) memcpy(hd + dat[k], v.data(), v.size() * sizeof(double));
+		set_offset(dm.*kDblTables[k].dst, kDblTables[k].tape && v.empty() ? kNullOffset : B.dbl_offset + dat[k] * sizeof(double));
+	}
+	B.pair_i_offset = (uintptr_t)dm.pair_i;
+	dm.kin_rounds = M.kin_rounds;
+	dm.dofanc_max = M.dofanc_max;
+	dm.flv_n = M.flv_n;
+	dm.need_rnepost = M.need_rnepost;
+	dm.act_tendon = M.act_tendon;
+	dm.nsite_act = (int)M.site_act.size();
+	dm.ngravcomp = (int)M.gravcomp_body.size();
+	dm.sub_nt = M.sub_nt;
+	for (int k = 0; k < 3; k++) {
+		dm.sens_ncopy[k] = M.sens_ncopy[k];
+		dm.sens_nslow[k] = M.sens_nslow[k];
+	}
+	dm.sens_ncopy_max = M.sens_ncopy_max ? M.sens_ncopy_max : 1;
+	dm.eulerdamp = M.eulerdamp;
+	dm.nfriction = M.nfriction;
+	dm.maxdepth = M.maxdepth;
+	return B;
+}
+
+void rebase_model_blob(const mjb_model &M, DevModel &dm, const void *base)
+{
+	each_blob_pointer(M, dm, [base](auto &p, size_t, size_t) {
+		typedef std::remove_reference_t<decltype(p)> P;
+		const uintptr_t off = (uintptr_t)p;
+		p = off == kNullOffset ? (P) nullptr : (P)(static_cast<const unsigned char *>(base) + off);
+	});
+}
+
 // ---- mjb_debug_model_digest: 64-bit FNV-1a over the members of a compiled model, in declaration order (never over raw struct bytes) ----
 namespace {
 struct Fnv {
@@ -1692,5 +1829,56 @@ extern "C" int mjb_debug_model_digest(const mjb_model *m, unsigned long long out
 	// [3] the lane = env / split-step classification
 	d3(m->le_topo); d3(m->sm_topo); d3(m->le_tape);
 	out[0] = d0.h; out[1] = d1.h; out[2] = d2.h; out[3] = d3.h;
+	return MJB_OK;
+}
+
+// ---- mjb_debug_blob_digest: the device model blob as build_model_blob lays it out.  [0] where every pointer member of the DevModel points, as an
+// offset from the blob's base, in declaration order (a null pointer: ~0); [1] what each table holds, read through those offsets over the table's
+// length (never the raw image: padding and slack stay out); [2] every other member of the DevModel, in declaration order ----
+extern "C" int mjb_debug_blob_digest(const mjb_model *m, unsigned long long out[3])
+{
+	if (!m || !out) return fail(MJB_EINVAL, "mjb_debug_blob_digest: bad argument");
+	const ModelBlob B = build_model_blob(*m);
+	const DevModel &dm = B.dm;
+	struct Entry { size_t member, offset, bytes, align; };  // (member: where the pointer sits inside the DevModel)
+	std::vector<Entry> tab;
+	each_blob_pointer(*m, dm, [&](const auto &p, size_t n, size_t align) {
+		tab.push_back({ (size_t)(reinterpret_cast<const char *>(&p) - reinterpret_cast<const char *>(&dm)), (size_t)(uintptr_t)p, n * sizeof(*p), align });
+	});
+	// the layout's promises, checked on the way: alignment (16 bytes for the int tables, 64 for the tape), no table overlaps the next, all inside the image
+	std::sort(tab.begin(), tab.end(), [](const Entry &a, const Entry &b) { return a.offset != b.offset ? a.offset < b.offset : a.bytes < b.bytes; });  // (an empty table may share its offset with the next)
+	size_t end = 0;
+	for (const Entry &e : tab) {
+		if (e.offset == kNullOffset) continue;
+		if (e.offset % e.align) return fail(MJB_EINVAL, "mjb_debug_blob_digest: the table at byte %zu is not on a %zu-byte boundary", e.offset, e.align);
+		if (e.offset < end) return fail(MJB_EINVAL, "mjb_debug_blob_digest: the table at byte %zu overlaps the one before it", e.offset);
+		end = e.offset + e.bytes;
+	}
+	if (end > B.image.size()) return fail(MJB_EINVAL, "mjb_debug_blob_digest: the last table ends outside the image");
+	std::sort(tab.begin(), tab.end(), [](const Entry &a, const Entry &b) { return a.member < b.member; });
+	Fnv d0, d1, d2;
+	for (const Entry &e : tab) {
+		const bool null = e.offset == kNullOffset;
+		d0(null ? ~(size_t)0 : e.offset);
+		d1(null ? (size_t)0 : e.bytes);
+		if (!null) d1.bytes(B.image.data() + e.offset, e.bytes);
+	}
+#define MJB_SIZE(name) d2(dm.name);
+#define MJB_OPT_I(name) d2(dm.name);
+#define MJB_OPT_D(name, n) for (int k = 0; k < (n); k++) d2(dm.name[k]);
+#define MJB_ARR_I(name, rows, cols)
+#define MJB_ARR_D(name, rows, cols)
+#include "../../include/mjb_model_fields.def"
+#undef MJB_SIZE
+#undef MJB_OPT_I
+#undef MJB_OPT_D
+#undef MJB_ARR_I
+#undef MJB_ARR_D
+	d2(dm.flv_n); d2(dm.act_tendon);
+	for (int k = 0; k < 3; k++) d2(dm.sens_ncopy[k]);
+	for (int k = 0; k < 3; k++) d2(dm.sens_nslow[k]);
+	d2(dm.sens_ncopy_max); d2(dm.eulerdamp); d2(dm.nfriction); d2(dm.need_rnepost); d2(dm.kin_rounds); d2(dm.maxdepth); d2(dm.sub_nt); d2(dm.dofanc_max);
+	d2(dm.nsite_act); d2(dm.ngravcomp);
+	out[0] = d0.h; out[1] = d1.h; out[2] = d2.h;
 	return MJB_OK;
 }
