@@ -544,6 +544,48 @@ DEVI void lane_env_body(const KernelParams MJB_AS4 *__restrict__ P, const int ns
 	}
 	const bool zpre = zhalf_i >= 0;
 
+	// ---- (the quartet's O and X) a body at rest -- no joint on its path to the world -- has a pose made of model constants alone: computed ONCE per launch,
+	// here, and kept in registers.  O keeps the quaternion its moving children chain from; X the frame its children, the tree root's offset, mj_energyPos and
+	// the frame sensors read (what nobody reads is dead code).  The expressions are the sweep's for such a body; neither the retry trip of the attempt loop
+	// nor an in-launch mj_resetData changes a rest pose.
+	constexpr bool RESTO = ROLE == LE_QUAD_O || ROLE == LE_QUAD_X, RESTX = ROLE == LE_QUAD_X;
+	[[maybe_unused]] double rxq[RESTO ? NB : 1][4], rxm[RESTX ? NB : 1][9], rxp[RESTX ? NB : 1][3], rxi[RESTX ? NB : 1][3];
+	if constexpr (RESTO) {
+		const LeTapeBody MJB_AS4 *const tb0 = reinterpret_cast<const LeTapeBody MJB_AS4 *>(reinterpret_cast<const LeTapeHdr MJB_AS4 *>(P->m.le_tape) + 1);
+		sfor<NB>([&](auto Bq) {
+			constexpr int b = Bq;
+			if constexpr (b > 0 && !LD::needed(b)) {
+				constexpr int p = T::body_parentid[b];
+				const double MJB_AS4 *const A = reinterpret_cast<const double MJB_AS4 *>(tb0 + b);  // pos[3] quat[4] ... | ipos[3] ...
+				double quat[4] = { A[3], A[4], A[5], A[6] };
+				if constexpr (p != 0) {
+					double q[4];
+					qmul(q, rxq[p], quat);
+					for (int k = 0; k < 4; k++) quat[k] = q[k];
+				}
+				normalize4_sel(quat);
+				for (int k = 0; k < 4; k++) rxq[b][k] = quat[k];
+				if constexpr (RESTX) {
+					double pos[3] = { A[0], A[1], A[2] };
+					if constexpr (p != 0) {
+						double v[3];
+						matvec3(v, rxm[p], pos);
+						for (int k = 0; k < 3; k++) pos[k] = v[k] + rxp[p][k];
+					}
+					quat2mat_nocheck(rxm[b], quat);
+					for (int k = 0; k < 3; k++) rxp[b][k] = pos[k];
+					if constexpr (T::body_sameframe[b]) {
+						for (int k = 0; k < 3; k++) rxi[b][k] = rxp[b][k];
+					} else {
+						double ip[3] = { A[16], A[17], A[18] }, v[3];
+						matvec3(v, rxm[b], ip);
+						for (int k = 0; k < 3; k++) rxi[b][k] = v[k] + rxp[b][k];
+					}
+				}
+			}
+		});
+	}
+
 #ifdef MJB_LE_PROBE  // (measurement build: cycle stamps of the step's phases, summed over the launch, into the env-0 sensordata of the role)
 	unsigned long long pk_t = 0, pk_acc[9] = { 0, 0, 0, 0, 0, 0, 0, 0, 0 };  // ([8], the quartet's C and V: from a sweep barrier to where the phase's reads have landed -- V: and the previous body's forces are done)
 #define LE_PK0() pk_t = __builtin_readcyclecounter()
@@ -1292,7 +1334,7 @@ DEVI void lane_env_body(const KernelParams MJB_AS4 *__restrict__ P, const int ns
 
 			// ============ the quartet's sweep: the same quantities, dealt over four wavefronts in phases (see the roles at the top) ============
 			// A body without a joint on its path to the world never moves and nobody downstream takes anything of it through LDS: O (its quaternion) and
-			// X (its frame, sensors, energy) each compute those bodies for themselves ahead of the phases, which count the NEEDED bodies only.
+			// X (its frame, sensors, energy) each compute those bodies for themselves ahead of the step loop, once per launch; the phases count the NEEDED bodies only.
 			if constexpr (QUAD) {
 				constexpr auto HINGE = [](int c) {
 					if (c < 1 || c >= T::NBODY || T::body_jnt[c < T::NBODY ? (c < 0 ? 0 : c) : 0] < 0) return false;
@@ -1308,6 +1350,7 @@ DEVI void lane_env_body(const KernelParams MJB_AS4 *__restrict__ P, const int ns
 				auto o_body = [&](auto Bq) {
 					constexpr int b = Bq;
 					constexpr int p = T::body_parentid[b], j = T::body_jnt[b];
+					static_assert(LD::needed(b), "the quartet: a body at rest has its quaternion from ahead of the step loop");
 					const double *const A = hA[b];  // pos[3] quat[4] jaxis[3] jpos[3] qpos0
 					constexpr int qr = QR0 + 4 * (((LD::slot(b) - NV) / 3) % 2);
 					double quat[4] = { A[3], A[4], A[5], A[6] };
@@ -1356,16 +1399,10 @@ DEVI void lane_env_body(const KernelParams MJB_AS4 *__restrict__ P, const int ns
 					constexpr int qr = QR0 + 4 * (((LD::slot(b) - NV) / 3) % 2);
 					const double *const A = hA[b];
 					double pos[3] = { A[0], A[1], A[2] }, quat[4] = { A[3], A[4], A[5], A[6] };
-					if constexpr (LD::needed(b)) {
+					static_assert(LD::needed(b), "the quartet: a body at rest has its pose from ahead of the step loop");
+					{
 						const Pair g0 = lp[64 * qr], g1 = lp[64 * (qr + 1)];
 						quat[0] = g0.a; quat[1] = g0.b; quat[2] = g1.a; quat[3] = g1.b;
-					} else {  // (at rest: the same chain O runs for it)
-						if constexpr (p != 0) {
-							double q[4];
-							qmul(q, xquat[p], quat);
-							for (int k = 0; k < 4; k++) quat[k] = q[k];
-						}
-						normalize4_sel(quat);
 					}
 					[[maybe_unused]] Pair sp{ 0, 0 };
 					if constexpr (j >= 0) sp = lp[64 * j];
@@ -1538,14 +1575,18 @@ DEVI void lane_env_body(const KernelParams MJB_AS4 *__restrict__ P, const int ns
 					}
 				}
 				if constexpr (ROLE == LE_QUAD_O || ROLE == LE_QUAD_X) {
-					// the bodies at rest, then the first needed body's record
+					// the bodies at rest: their poses from the launch's registers -- what is left per step is X's mj_energyPos term and frame sensors, at the
+					// last step (or at every one, mjb_set_sensors_every_step) under their wave-uniform tests --, then the first needed body's record
 					sfor<NB>([&](auto Bq) {
 						constexpr int b = Bq;
 						if constexpr (b > 0 && !LD::needed(b)) {
-							for (int k = 0; k < 14; k++) hA[b][k] = reinterpret_cast<const double MJB_AS4 *>(tb + b)[k];
-							if constexpr (ROLE == LE_QUAD_X) for (int k = 0; k < 10; k++) hB[b][k] = reinterpret_cast<const double MJB_AS4 *>(tb + b)[16 + k];
-							if constexpr (ROLE == LE_QUAD_O) o_body(Bq);
-							else x_body(Bq);
+							for (int k = 0; k < 4; k++) xquat[b][k] = rxq[b][k];
+							if constexpr (ROLE == LE_QUAD_X) {
+								for (int k = 0; k < 9; k++) xmat[b][k] = rxm[b][k];
+								for (int k = 0; k < 3; k++) xpos[b][k] = rxp[b][k];
+								if (eg_on) pe -= tb[b].mass * (grav[0] * rxi[b][0] + grav[1] * rxi[b][1] + grav[2] * rxi[b][2]);
+								frame_sensors(Bq, rxi[b]);
+							}
 						}
 					});
 					if constexpr (N1 < NB) {
