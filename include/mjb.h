@@ -326,7 +326,29 @@ int mjb_fused_frame(const mjb_batch *b);
  * active row and a step with rows takes 2.2 sweeps on average (tools/lane_env_limits_rate.py, profiles/lane_env_limits.txt; the median of 5): 90.8
  * against the generic kernels' 44.8 M env-steps/s at 4096 envs (2.03 x), 660 against 45.5 at 65 536 (14.5 x); 0.31 / 0.18 of plain franka_like's rate in
  * the same one-wavefront form -- with 64 envs to a wavefront nearly every step finds some lane at a limit, and the PGS loop runs as long as its slowest
- * lane.  The kernel is ahead at 4096 envs; switching the automatic rule is left to a later change.  No reference counterpart. */
+ * lane.  The kernel is ahead at 4096 envs; switching the automatic rule is left to a later change.  No reference counterpart.
+ * Fixed-tendon actuators and joint equalities under PGS (a gripper: two finger slides coupled by <equality><joint>, one actuator on a <tendon><fixed>
+ * over both): taken in addition, under the same rules as the limit models (mjb_model_lane_env() == -2, form 0 of the PLAIN build whatever form is asked
+ * for, modes 1 and 2 only, mjb_lane_env_plan -1 for builds 1 - 4, the generic kernels -- bit-equal to mode 0 -- for a batch with per-env overrides,
+ * mjb_set_env_equality included, a hwsim stage or a written xfrc_applied).  TAKEN: fixed tendons that carry actuators and nothing else (no tendon is
+ * limited; tendon_frictionloss, tendon_stiffness and tendon_damping are 0; no tendon sensor, no tendon equality); actuators with trntype MJB_TRN_TENDON on
+ * them, in every gain / bias / dyntype combination the kernel runs for joint actuators, activation states and ctrl / force / act limits included
+ * (actuator_length = gear sum_w coef_w qpos_w, actuator_velocity likewise from qvel, qfrc_actuator[dof_w] += gear coef_w force, and their actuatorpos /
+ * actuatorvel / actuatorfrc sensors); joint equalities (MJB_EQ_JOINT) on hinge / slide joints in both forms, q1 - q1_0 = poly(q2 - q2_0) on two
+ * different joints and q1 - q1_0 = polycoef[0] on one -- an equality with eq_active == 0 has no row and costs nothing.  Constraint rows may be
+ * joint-equality rows and joint-limit rows together, equality rows first (MuJoCo's order): PGS, no dof friction loss, range > 2 margin on limited
+ * joints, and nefcmax EXACTLY the active joint equalities + the limited joints (a model with equalities and no limits qualifies; one whose capacity
+ * leaves room for an inactive equality does not).  An equality row is every env's at every step (unless mjDSBL_EQUALITY / mjDSBL_CONSTRAINT): its
+ * J = e_d1 - poly'(x) e_d2 carries a per-env coefficient, its force is not clamped at 0 and its warmstart force is -D jar unconditionally; nefc counts
+ * equality rows + active limit rows, qfrc_constraint = J' f reaches the equality dofs.  REFUSED as before (the generic kernels): a tendon with a spring,
+ * a damper, a limit or friction; tendonpos / tendonvel sensors; connect, weld and tendon equalities; dof frictionloss; Newton and CG; a model whose packed
+ * AR (rows (rows + 1) / 2 doubles per env) does not fit a CU's LDS beside the state -- refused at classification, not at the launch.  Measured on
+ * assets/gripper/franka_gripper.xml (config 2's arm, nine limits, the fingers coupled by a joint equality and driven through a fixed tendon; 10 rows) with
+ * tools/lane_env_gripper_rate.py, profiles/lane_env_gripper.txt (the benchmark's ctrl noise, K = 200, the median of 5): 38.7 against the generic kernels'
+ * 34.4 M env-steps/s at 4096 envs (1.12 x), 285 against 34.9 at 65 536 (8.2 x); 0.13 / 0.08 of plain franka_like's rate in the same one-wavefront form.
+ * 87 % of the env-steps have a limit row beside the equality row (mean nefc 3.0, max 7) and the mean solver_iter is 27: the finger equality and the
+ * finger limits pull against each other through one small mass, and the PGS loop of a wavefront runs as long as its slowest lane.  The kernel is ahead
+ * at both sizes, barely at 4096 envs; the automatic rule is untouched.  No reference counterpart. */
 int mjb_set_lane_env(mjb_batch *b, int mode);
 /* Opt-in (default off): with on = 1 the device hwsim stage (mjb_hwsim_configure, below) no longer stands the lane = env kernel down.  The batch's
  * eligible launches then run the kernel's one-wavefront form (mjb_lane_env_last_form() == 0, at the LDS budget the batch size gives, whatever form is
@@ -384,7 +406,7 @@ int mjb_model_frame_info(const mjb_model *m, int *full_hbm, int *fused_hbm);
 /* >= 0: index of the compiled-in topology the batch's model matches; -2: none compiled in, but the model's structure fits the kernel -- its
  * first eligible launch builds the kernel for it through hiprtc (libhiprtc.so and csrc/mjb_lane_env_kernel.h next to libmjb.so; a few
  * seconds, cached per process); -3: that build was not possible (mjb_lane_env_error says why) and the generic kernels run; -1: the model does not
- * fit (constraint rows other than PGS joint limits alone, free / ball joints, RK4, a sensor outside the list at mjb_compile, ...).  *used_last (may be NULL) = 1 when the last fused launch ran the lane = env kernel. */
+ * fit (constraint rows other than PGS joint equalities and joint limits alone, free / ball joints, RK4, a sensor outside the list at mjb_compile, ...).  *used_last (may be NULL) = 1 when the last fused launch ran the lane = env kernel. */
 int mjb_lane_env_info(const mjb_batch *b, int *used_last);
 /* hiprtc builds of the lane = env kernel are kept on disk: $MJB_JIT_CACHE (default $XDG_CACHE_HOME/mjb_jit or ~/.cache/mjb_jit; "0" = off), one code
  * object per (gfx arch, kernel-header fingerprint, LDS budget, form, topology).  Counts of this process: kernels compiled / taken from the cache. */
@@ -402,6 +424,11 @@ int mjb_model_lane_env(const mjb_model *m);
  * mjDSBL_WARMSTART mjDSBL_REFSAFE pad[2] | per limited joint, in joint order, 16: range[2] margin solref[2] solimp[5] dof_invweight0 K B powa powb pad --
  * solref / solimp as getsolparam leaves them (a mixed-sign solref replaced by the default, refsafe, solimp clamped to its legal ranges), K / B the row's
  * stiffness and damping from them (mj_makeImpedance), powa / powb = 1 / mid^(power - 1) and 1 / (1 - mid)^(power - 1) of the impedance curve.
+ * The 8-double header is there whenever the model has rows of either kind; BEHIND the limit records, per ACTIVE joint equality, in equality order, 24:
+ * polycoef[5] qpos0[2] (of joint1, joint2; the second 0 in the one-joint form) solref[2] solimp[5] (as getsolparam leaves them)
+ * dof_invweight0[d1] + dof_invweight0[d2] K B powa powb pad[5]; BEHIND those, per tendon wrap of a model with fixed tendons, in wrap order, 8: the PLAIN
+ * coefficient (wrap_prm) pad[7] -- the actuator's gear, in its own record, multiplies it in the kernel.  A model without equalities and tendons has
+ * none of these records.
  * mjb_model_lane_env_overlay: one env's column of the per-env table of mjb_set_lane_env's mode 2, here with the model's own values -- gravity[3] | per
  * jointed body: stiffness damping armature hdamping | per moving body (a joint on its path to the world): mass ibody[6] | per actuator: gain[3] bias[3]
  * | the mass of every other body but the world (mjENBL_ENERGY reads it). */
@@ -415,10 +442,14 @@ int mjb_model_lane_env_overlay(const mjb_model *m, double *out, int cap);
  * 40 / 80 / 160 as MJB_LANE_ENV_LDS_KB.  Fills (each may be NULL) the form, form 3's sweep wavefronts (0 otherwise) and the LDS budget in KB, the
  * values mjb_lane_env_last_form / mjb_lane_env_last_sweep_waves report after such a launch.  A model with activation states (na > 0): form 0 whatever
  * is asked for, and no variant at all for build 2.  A model with a frame-axis, velocity- or acceleration-stage sensor: form 0 whatever is asked for,
- * and no variant for builds 3 and 4 when a force / torque sensor sits on a body without a joint on its path to the world.  A model with joint-limit
- * rows: form 0 whatever is asked for, at the smallest budget its packed AR fits beside the state, and no variant for builds 1 - 4.  Returns 0; -1: the model is not eligible or needs more LDS than a CU has, there is no such variant,
+ * and no variant for builds 3 and 4 when a force / torque sensor sits on a body without a joint on its path to the world.  A model with constraint
+ * rows (joint equalities, joint limits) or fixed tendons: form 0 whatever is asked for, at the smallest budget its packed AR fits beside the state, and no variant for builds 1 - 4.  Returns 0; -1: the model is not eligible or needs more LDS than a CU has, there is no such variant,
  * or an argument is out of range. */
 int mjb_lane_env_plan(const mjb_model *m, int ncu, int nenv, int build, int form, int sweep_waves, int lds_kb, int *out_form, int *out_sweep_waves, int *out_lds_kb);
+/* The static row list of the lane = env kernel's constraint stage for this model: the joint-equality rows (its active joint equalities, first in the
+ * list) and the joint-limit rows (its limited joints, behind them), each may be NULL.  Returns their sum; 0 for a model without a constraint stage
+ * (not eligible, unconstrained, or its rows switched off by mjDSBL_EQUALITY / mjDSBL_LIMIT). */
+int mjb_lane_env_rows(const mjb_model *m, int *neq_rows, int *nlimit_rows);
 const char *mjb_lane_env_error(void);
 /* The lane = env kernel's FORM, process-wide: how many wavefronts share the 64 envs of a block.  0 = one (the whole step in one instruction stream);
  * 1 = two, the step's position half (poses, cinert, composite inertias, qM, factors, solves, Euler) and velocity half (velocities, forces,

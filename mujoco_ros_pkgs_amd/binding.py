@@ -226,6 +226,7 @@ def load_library(path=None):
         "mjb_model_lane_env_tape": (ci, [vp, C.POINTER(C.c_double), ci]),
         "mjb_model_lane_env_overlay": (ci, [vp, C.POINTER(C.c_double), ci]),
         "mjb_lane_env_plan": (ci, [vp, ci, ci, ci, ci, ci, ci, C.POINTER(ci), C.POINTER(ci), C.POINTER(ci)]),
+        "mjb_lane_env_rows": (ci, [vp, C.POINTER(ci), C.POINTER(ci)]),
         "mjb_lane_env_jit_counts": (None, [C.POINTER(ci), C.POINTER(ci)]),
         "mjb_set_split_step": (ci, [vp, ci]),
         "mjb_split_step_info": (ci, [vp, C.POINTER(ci), C.POINTER(ci)]),

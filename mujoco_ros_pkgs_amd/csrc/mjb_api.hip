@@ -740,20 +740,23 @@ static int speculate_ctrl_noise(mjb_batch *b, const LaunchReq &q, int zhalf_now)
 // (mjb_lane_env_set_hwsim: the hwsim stage rides along in the kernel's HW build -- unless the batch has per-env gravity or parameter blocks too)
 // (... or the model has activation states: no build of the kernel has both, mjb_lane_env_plan answers -1)
 // (... or joint limits: the plain build alone has the constraint stage -- no overlay, hwsim or xfrc build of such a model, mjb_lane_env_plan answers -1)
-static bool le_limits(const mjb_batch *b) { return b->model->le_topo == MJB_LE_TOPO_JIT && mjb_lane_env_limits(&b->model->h) > 0; }
-static bool le_hwsim(const mjb_batch *b) { return b->hw.n > 0 && b->lane_env_hwsim && b->hw_le_ok && !b->env_mass.get() && !b->env_gravity.get() && b->model->h.na <= 0 && !le_limits(b); }
+// (... or joint equalities, or fixed tendons under its actuators: the same -- le_solo_only; le_limits: the model has rows, of either kind)
+static bool le_limits(const mjb_batch *b) { return b->model->le_topo == MJB_LE_TOPO_JIT && mjb_lane_env_limits(&b->model->h) + mjb_lane_env_eq_rows(&b->model->h) > 0; }
+static bool le_solo_only(const mjb_batch *b) { return b->model->le_topo == MJB_LE_TOPO_JIT && mjb_lane_env_solo_only(&b->model->h) != 0; }
+static bool le_hwsim(const mjb_batch *b) { return b->hw.n > 0 && b->lane_env_hwsim && b->hw_le_ok && !b->env_mass.get() && !b->env_gravity.get() && b->model->h.na <= 0 && !le_solo_only(b); }
 // (mjb_lane_env_set_xfrc: a written xfrc_applied rides along in the kernel's XF builds -- unless the batch has a hwsim stage, there is no build with both.
 //  LaunchReq::compact stays what the generic path's frame choice reads; for this kernel, which has no frame, the xfrc term of it is lifted)
 // (... or the model has a force / torque sensor on a body at rest: the wrench table has no slot for that body's xfrc_applied, mjb_lane_env_plan answers -1)
-static bool le_xfrc(const mjb_batch *b) { return b->st.use_xfrc && b->lane_env_xfrc && b->hw.n == 0 && !mjb_lane_env_wrench_at_rest(&b->model->h) && !le_limits(b); }
+static bool le_xfrc(const mjb_batch *b) { return b->st.use_xfrc && b->lane_env_xfrc && b->hw.n == 0 && !mjb_lane_env_wrench_at_rest(&b->model->h) && !le_solo_only(b); }
 static bool want_lane_env(const mjb_batch *b, const LaunchReq &q, int variant)
 {
 	const bool frameless = q.compact || (le_xfrc(b) && !b->st.keep_frame);
 	// (a model with joint limits is a PGS model to the generic kernels: the lane = env kernel takes it when asked to, modes 1 and 2 -- the automatic mode
 	//  keeps the generic kernels for it -- and without per-env overrides of any kind)
-	const bool lim = le_limits(b);
-	if (!(q.mode == MJB_MODE_STEP && frameless && (lim ? (mjb_kv_pgs(variant) && b->lane_env_mode >= 1) : variant == MJB_KV_NONE) && b->model->le_topo != MJB_LE_TOPO_NONE &&
-	      !b->le_unavailable && b->lane_env_mode != 0 &&
+	// (... nor per-env equality parameters; a model with fixed tendons and no rows is an unconstrained model to the generic kernels, and treated alike)
+	const bool lim = le_solo_only(b);
+	if (!(q.mode == MJB_MODE_STEP && frameless && (lim ? ((le_limits(b) ? mjb_kv_pgs(variant) : variant == MJB_KV_NONE) && b->lane_env_mode >= 1 && !b->env_equality.get()) : variant == MJB_KV_NONE) &&
+	      b->model->le_topo != MJB_LE_TOPO_NONE && !b->le_unavailable && b->lane_env_mode != 0 &&
 	      (no_env_overrides(b) || (b->lane_env_mode == 2 && b->hw.n == 0 && !lim) || le_hwsim(b)) && !b->st.stats))  // (mode 2: per-env gravity and parameter blocks ride along, le_overlay_sync)
 		return false;
 	static const int min_envs = mjb_env_int("MJB_LANE_ENV_MIN_ENVS", 4096);
@@ -1564,6 +1567,14 @@ int mjb_lane_env_plan(const mjb_model *m, int ncu, int nenv, int build, int form
 {
 	if (m && m->le_topo == MJB_LE_TOPO_NONE) return -1;
 	return mjb_lane_env_plan_for(m && m->le_topo == MJB_LE_TOPO_JIT ? &m->h : nullptr, ncu, nenv, build, form, sweep_waves, lds_kb, out_form, out_sweep_waves, out_lds_kb);
+}
+int mjb_lane_env_rows(const mjb_model *m, int *neq_rows, int *nlimit_rows)
+{
+	const bool rows = m && m->le_topo == MJB_LE_TOPO_JIT;
+	const int ne = rows ? mjb_lane_env_eq_rows(&m->h) : 0, nl = rows ? mjb_lane_env_limits(&m->h) : 0;
+	if (neq_rows) *neq_rows = ne;
+	if (nlimit_rows) *nlimit_rows = nl;
+	return ne + nl;
 }
 int mjb_lane_env_info(const mjb_batch *b, int *used_last)
 {

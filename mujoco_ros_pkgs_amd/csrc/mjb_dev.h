@@ -109,6 +109,14 @@ static_assert(sizeof(LeTapeHdr) == 64 && sizeof(LeTapeBody) == 256 && sizeof(LeT
 struct LeTapeLimHdr { double meaninertia, tolerance, iterations, scale /* 1 / (meaninertia max(1, nv)) */, nowarm /* mjDSBL_WARMSTART */, norefsafe /* mjDSBL_REFSAFE */, pad[2]; };
 struct LeTapeLim { double range[2], margin, solref[2], solimp[5], invweight0, K, B, powa, powb, pad; };
 static_assert(sizeof(LeTapeLimHdr) == 64 && sizeof(LeTapeLim) == 128, "lane = env tape records of the joint limits");
+// Joint equalities and fixed tendons (mjb_lane_env_eligible): BEHIND the limit records, one LeTapeEq per active joint equality in equality order (the
+// header above is there whenever the model has rows of either kind), then one LeTapeWrap per tendon wrap in wrap order (mjModel.wrap_prm).  An equality
+// record holds polycoef, qpos0 of its two joints (the second 0 in the one-joint form), solref / solimp as getsolparam leaves them, the sum of the two
+// dofs' invweight0 and K / B / powa / powb as LeTapeLim does.  A wrap record holds the PLAIN coefficient: the actuator's gear (LeTapeAct) multiplies it
+// in the kernel, actuator_length = gear sum_w coef_w qpos_w.
+struct LeTapeEq { double polycoef[5], qpos0[2], solref[2], solimp[5], invweight0, K, B, powa, powb, pad[5]; };
+struct LeTapeWrap { double coef, pad[7]; };
+static_assert(sizeof(LeTapeEq) == 192 && sizeof(LeTapeWrap) == 64, "lane = env tape records of the joint equalities and tendon wraps");
 
 // Offsets (in doubles / ints) of every data field inside one per-env frame.
 struct FrameLayout {
@@ -382,6 +390,9 @@ const char *mjb_lane_env_name(int topo);
 enum { MJB_LE_TOPO_NONE = -1, MJB_LE_TOPO_JIT = -2, MJB_LE_UNAVAILABLE = -1000 };
 int mjb_lane_env_eligible(const mjb_model_desc *h);   // the model's structure fits the kernel (compiled in or not)
 int mjb_lane_env_limits(const mjb_model_desc *h);     // the joint-limit rows of a model the kernel takes WITH constraint rows (its limited joints), 0: it has none
+int mjb_lane_env_eq_rows(const mjb_model_desc *h);    // ... and its joint-equality rows (the active joint equalities), 0: it has none
+const char *mjb_lane_env_refusal(void);               // why mjb_lane_env_eligible last refused a model for its size ("" if it did not)
+int mjb_lane_env_solo_only(const mjb_model_desc *h);  // 1: constraint rows or fixed tendons -- the plain build of the one-wavefront form alone runs such a model
 const char *mjb_lane_env_jit_error(void);                    // why the last hiprtc build of a topology was not available ("" if none failed)
 void mjb_lane_env_jit_stats(int *compiled, int *disk_hits);  // hiprtc builds of this process / builds taken from the disk cache instead
 // which build of the kernel a launch runs: the plain one (any form), or one of the two that exist for the solo form only and run it whatever the batch size --

@@ -120,35 +120,88 @@ template <class T> bool topo_matches(const mjb_model_desc &h)
 
 }  // namespace
 
-// Constraint rows the kernel takes: every row the model can ever have is a joint-limit row (of a hinge or slide: mjb_lane_env_eligible asks for the joint
-// kinds) swept by PGS -- no dry friction, a range wider than twice the margin on every limited joint (at most one row per joint at a time), and room for
-// all of them (a model whose <size njmax> lowered the capacity keeps the generic kernels: truncation and mjWARN_CNSTRFULL live there)
+// Constraint rows the kernel takes: every row the model can ever have is a joint-equality row or a joint-limit row (of hinges and slides:
+// mjb_lane_env_eligible asks for the joint kinds) swept by PGS -- no dry friction, a range wider than twice the margin on every limited joint (at most
+// one row per joint at a time), every equality a joint equality (on two different joints, or on one), and room for exactly these rows: the active joint
+// equalities and the limited joints (a model whose <size njmax> lowered the capacity keeps the generic kernels: truncation and mjWARN_CNSTRFULL live
+// there; one with room to spare could activate an equality per env).  A row kind mjDSBL_EQUALITY / mjDSBL_LIMIT switches off has no rows.
+static thread_local const char *le_refusal = "";  // why mjb_lane_env_eligible last refused a model for its size (mjb_lane_env_refusal)
+static int le_count_limits(const mjb_model_desc *h)
+{
+	int nl = 0;
+	if (!(h->disableflags & MJB_DSBL_LIMIT))
+		for (int j = 0; j < h->njnt; j++) nl += h->jnt_limited[j] != 0;
+	return nl;
+}
+static int le_count_eqs(const mjb_model_desc *h)
+{
+	int ne = 0;
+	if (!(h->disableflags & MJB_DSBL_EQUALITY))
+		for (int e = 0; e < h->neq; e++) ne += h->eq_active[e] != 0;
+	return ne;
+}
 static bool le_limit_rows(const mjb_model_desc *h)
 {
 	if (h->solver != MJB_SOL_PGS) return false;
 	for (int d = 0; d < h->nv; d++)
 		if (h->dof_frictionloss[d] > 0) return false;
-	int nl = 0;
-	for (int j = 0; j < h->njnt; j++)
-		if (h->jnt_limited[j]) {
-			if (!(h->jnt_range[2 * j + 1] - h->jnt_range[2 * j] > 2 * h->jnt_margin[j])) return false;
-			nl++;
-		}
-	return nl > 0 && h->nefcmax == nl;
+	if (!(h->disableflags & MJB_DSBL_LIMIT))
+		for (int j = 0; j < h->njnt; j++)
+			if (h->jnt_limited[j] && !(h->jnt_range[2 * j + 1] - h->jnt_range[2 * j] > 2 * h->jnt_margin[j])) return false;
+	const int nr = le_count_limits(h) + le_count_eqs(h);
+	return nr > 0 && h->nefcmax == nr;
 }
-// what both classifications below ask first: an Euler model of one-dof joints, without contacts, mocap bodies, tendons or equalities, and without constraint
-// rows -- or with joint-limit rows alone
+// equalities: joint equalities alone, each on one joint or on two different ones (their rows: le_limit_rows)
+static bool le_joint_equalities(const mjb_model_desc *h)
+{
+	for (int e = 0; e < h->neq; e++) {
+		const int j1 = h->eq_obj1id[e], j2 = h->eq_obj2id[e];
+		if (h->eq_type[e] != MJB_EQ_JOINT || j1 < 0 || j1 >= h->njnt || j2 >= h->njnt || j2 == j1) return false;
+	}
+	return true;
+}
+// tendons: fixed tendons that do nothing but carry actuators -- no limit, dry friction, spring or damper (tendon sensors and tendon equalities are refused
+// with the sensors and the equalities)
+static bool le_bare_tendons(const mjb_model_desc *h)
+{
+	for (int t = 0; t < h->ntendon; t++) {
+		if (h->tendon_limited[t] || h->tendon_frictionloss[t] != 0 || h->tendon_stiffness[t] != 0 || h->tendon_damping[t] != 0) return false;
+		if (h->tendon_num[t] < 1 || h->tendon_adr[t] < 0 || h->tendon_adr[t] + h->tendon_num[t] > h->nwrap) return false;
+		for (int w = h->tendon_adr[t]; w < h->tendon_adr[t] + h->tendon_num[t]; w++)
+			if (h->wrap_objid[w] < 0 || h->wrap_objid[w] >= h->njnt) return false;
+	}
+	return true;
+}
+// what both classifications below ask first: an Euler model of one-dof joints, without contacts or mocap bodies, and without constraint rows -- or with
+// joint-equality and joint-limit rows alone
 static bool le_plain_tree(const mjb_model_desc *h)
 {
-	return h && h->nconmax <= 0 && h->integrator == MJB_INT_EULER && h->nmocap <= 0 && h->ntendon <= 0 && h->neq <= 0 && h->nq == h->nv && h->njnt == h->nv &&
-	       (h->nefcmax <= 0 || le_limit_rows(h));
+	return h && h->nconmax <= 0 && h->integrator == MJB_INT_EULER && h->nmocap <= 0 && h->nq == h->nv && h->njnt == h->nv &&
+	       (h->ntendon <= 0 || le_bare_tendons(h)) && (h->neq <= 0 || le_joint_equalities(h)) && (h->nefcmax <= 0 || le_limit_rows(h));
+}
+// the dofs the rows touch (one-dof joints in dof order: a joint's id is its dof)
+static int le_row_dofs(const mjb_model_desc *h)
+{
+	int n = 0;
+	for (int j = 0; j < h->njnt; j++) {
+		bool in = h->jnt_limited[j] != 0 && !(h->disableflags & MJB_DSBL_LIMIT);
+		if (!(h->disableflags & MJB_DSBL_EQUALITY))
+			for (int e = 0; e < h->neq; e++) in = in || (h->eq_active[e] && (h->eq_obj1id[e] == j || h->eq_obj2id[e] == j));
+		n += in;
+	}
+	return n;
 }
 int mjb_lane_env_limits(const mjb_model_desc *h)
 {
-	int nl = 0;
-	if (h && h->nefcmax > 0 && mjb_lane_env_eligible(h))
-		for (int j = 0; j < h->njnt; j++) nl += h->jnt_limited[j] != 0;
-	return nl;
+	return (h && h->nefcmax > 0 && mjb_lane_env_eligible(h)) ? le_count_limits(h) : 0;
+}
+int mjb_lane_env_eq_rows(const mjb_model_desc *h)
+{
+	return (h && h->nefcmax > 0 && mjb_lane_env_eligible(h)) ? le_count_eqs(h) : 0;
+}
+int mjb_lane_env_solo_only(const mjb_model_desc *h)
+{
+	return (h && (h->nefcmax > 0 || h->ntendon > 0) && mjb_lane_env_eligible(h)) ? 1 : 0;
 }
 // an actuator's dynamics the kernel runs: none, or an activation state of its own that integrates ctrl / filters it (muscle and user dynamics: the loader's refusal)
 static bool le_dyntype_ok(const mjb_model_desc *h, int i)
@@ -172,6 +225,7 @@ static bool le_wrench_at_rest(const mjb_model_desc *h);
 int mjb_lane_env_match(const mjb_model_desc *h)
 {
 	if (!le_plain_tree(h) || h->nefcmax > 0) return -1;  // (joint limits are a compile-time list of rows, LeLim: such a model is hiprtc's)
+	if (h->ntendon > 0 || h->neq > 0) return -1;         // (... and so are the tendons' wraps, LeTen, and the joint equalities, LeEq)
 	for (int b = 1; b < h->nbody; b++)
 		if (h->body_gravcomp[b] != 0) return -1;  // (gravity compensation is a compile-time flag per body, LeGc: no compiled-in topology has one set)
 	if (le_extra_sensors(h)) return -1;  // (... and none carries a frame-axis, velocity- or acceleration-stage sensor, LeSens: such a model is hiprtc's)
@@ -250,11 +304,20 @@ int mjb_lane_env_eligible(const mjb_model_desc *h)
 		if (site && ot != MJB_OBJ_SITE) return 0;
 	}
 	for (int i = 0; i < h->nu; i++)
-		if (h->actuator_trntype[i] != MJB_TRN_JOINT || !le_dyntype_ok(h, i)) return 0;
+		if (!(h->actuator_trntype[i] == MJB_TRN_JOINT || (h->actuator_trntype[i] == MJB_TRN_TENDON && h->actuator_trnid[2 * i] >= 0 && h->actuator_trnid[2 * i] < h->ntendon)) ||
+		    !le_dyntype_ok(h, i))
+			return 0;
 	int owned = 0;  // (every slot of act has its one actuator: the kernel writes a slot where it runs its owner)
 	for (int i = 0; i < h->nu; i++) owned += h->actuator_dyntype[i] != MJB_DYN_NONE;
-	return owned == (h->na > 0 ? h->na : 0);
+	if (owned != (h->na > 0 ? h->na : 0)) return 0;
+	// (constraint rows: the packed AR and the rows' qacc_warmstart beside the state must fit the largest LDS budget -- refused here, not at the launch)
+	if (h->nefcmax > 0 && le_state_slots(h->nv, mjb_lane_env_xfrc_slots(h), le_count_limits(h) + le_count_eqs(h), le_row_dofs(h)) > LE_MAX_SLOTS) {
+		le_refusal = "the packed AR of the model's constraint rows needs more than 160 KB of LDS per wavefront";
+		return 0;
+	}
+	return 1;
 }
+const char *mjb_lane_env_refusal(void) { return le_refusal; }
 
 namespace {
 
@@ -294,7 +357,23 @@ std::string topo_source(const mjb_model_desc &h)
 	arr("sensor_objtype", h.nsensor, [&](int i) { return h.sensor_objtype[i]; });
 	arr("sensor_objid", h.nsensor, [&](int i) { return h.sensor_objid[i]; });
 	arr("sensor_adr", h.nsensor, [&](int i) { return h.sensor_adr[i]; });
-	if (h.nefcmax > 0) arr("jnt_limited", h.njnt, [&](int i) { return h.jnt_limited[i] != 0; });  // (the rows of the constraint stage, LeLim: a model without them has no such line)
+	if (h.nefcmax > 0) arr("jnt_limited", h.njnt, [&](int i) { return h.jnt_limited[i] != 0 && !(h.disableflags & MJB_DSBL_LIMIT); });  // (the rows of the constraint stage, LeLim: a model without them has no such line)
+	if (h.ntendon > 0) {  // (fixed tendons, LeTen: which actuators drive one, and every tendon's wraps -- a model without tendons has none of these lines)
+		arr("act_trntype", h.nu, [&](int i) { return h.actuator_trntype[i]; });
+		arr("act_tendon", h.nu, [&](int i) { return h.actuator_trntype[i] == MJB_TRN_TENDON ? h.actuator_trnid[2 * i] : -1; });
+		arr("tendon_adr", h.ntendon, [&](int i) { return h.tendon_adr[i]; });
+		arr("tendon_num", h.ntendon, [&](int i) { return h.tendon_num[i]; });
+		arr("wrap_jnt", h.nwrap, [&](int i) { return h.wrap_objid[i]; });
+	}
+	if (h.nefcmax > 0 && !(h.disableflags & MJB_DSBL_EQUALITY)) {  // (the equality rows, LeEq: the joint pairs of the ACTIVE joint equalities, -1 = the one-joint form)
+		std::vector<int> e1, e2;
+		for (int e = 0; e < h.neq; e++)
+			if (h.eq_active[e]) e1.push_back(h.eq_obj1id[e]), e2.push_back(h.eq_obj2id[e] >= 0 ? h.eq_obj2id[e] : -1);
+		if (!e1.empty()) {
+			arr("eq_jnt1", (int)e1.size(), [&](int i) { return e1[i]; });
+			arr("eq_jnt2", (int)e2.size(), [&](int i) { return e2[i]; });
+		}
+	}
 	s += "};\n";
 	return s;
 }
@@ -574,8 +653,10 @@ int mjb_lane_env_last_form(void) { return le_form_last; }
 
 size_t mjb_lane_env_tape_doubles(const mjb_model_desc *h)
 {
-	const int nl = mjb_lane_env_limits(h);  // (joint limits: a header and a record per limited joint behind the rest)
-	return (sizeof(LeTapeHdr) + (size_t)h->nbody * sizeof(LeTapeBody) + (size_t)h->nu * sizeof(LeTapeAct) + (nl > 0 ? sizeof(LeTapeLimHdr) + (size_t)nl * sizeof(LeTapeLim) : 0)) /
+	// (constraint rows: a header, a record per limited joint and one per active joint equality behind the rest; fixed tendons: a record per wrap behind those)
+	const int nl = mjb_lane_env_limits(h), ne = mjb_lane_env_eq_rows(h), nw = mjb_lane_env_solo_only(h) && h->ntendon > 0 ? h->nwrap : 0;
+	return (sizeof(LeTapeHdr) + (size_t)h->nbody * sizeof(LeTapeBody) + (size_t)h->nu * sizeof(LeTapeAct) +
+	        (nl + ne > 0 ? sizeof(LeTapeLimHdr) + (size_t)nl * sizeof(LeTapeLim) + (size_t)ne * sizeof(LeTapeEq) : 0) + (size_t)nw * sizeof(LeTapeWrap)) /
 	       sizeof(double);
 }
 
@@ -714,8 +795,29 @@ void mjb_lane_env_tape(const mjb_model_desc *h, double *tape)
 			a.acthi = h->actuator_actrange[2 * i + 1];
 		}
 	}
-	if (mjb_lane_env_limits(h) > 0) {
-		LeTapeLimHdr *lh = reinterpret_cast<LeTapeLimHdr *>(ta + h->nu);
+	// getsolparam + mj_makeImpedance's constants of one row: a mixed-sign solref is replaced by the default, refsafe, solimp clamped to its legal ranges
+	// (mjMINIMP, mjMAXIMP, width >= 0, power >= 1); K, B the row's stiffness and damping; powa, powb the two constant factors of the impedance curve
+	auto solparam = [&](const double *sr_in, const double *si, double *solref, double *solimp, double &K, double &B, double &powa, double &powb) {
+		double sr[2] = { sr_in[0], sr_in[1] };
+		if ((sr[0] > 0) != (sr[1] > 0)) sr[0] = 0.02, sr[1] = 1.0;
+		if (!(h->disableflags & MJB_DSBL_REFSAFE) && sr[0] > 0) sr[0] = fmax(sr[0], 2 * h->timestep[0]);
+		const double imp[5] = { fmin(0.9999, fmax(0.0001, si[0])), fmin(0.9999, fmax(0.0001, si[1])), fmax(0.0, si[2]), fmin(0.9999, fmax(0.0001, si[3])), fmax(1.0, si[4]) };
+		solref[0] = sr[0], solref[1] = sr[1];
+		for (int k = 0; k < 5; k++) solimp[k] = imp[k];
+		if (sr[0] > 0) {
+			K = 1 / fmax(MJB_MINVAL, imp[1] * imp[1] * sr[0] * sr[0] * sr[1] * sr[1]);
+			B = 2 / fmax(MJB_MINVAL, imp[1] * sr[0]);
+		} else {
+			K = -sr[0] / fmax(MJB_MINVAL, imp[1] * imp[1]);
+			B = -sr[1] / fmax(MJB_MINVAL, imp[1]);
+		}
+		powa = 1 / pow(imp[3], imp[4] - 1);
+		powb = 1 / pow(1 - imp[3], imp[4] - 1);
+	};
+	const int nlim = mjb_lane_env_limits(h), neqr = mjb_lane_env_eq_rows(h);
+	unsigned char *behind = reinterpret_cast<unsigned char *>(ta + h->nu);
+	if (nlim + neqr > 0) {
+		LeTapeLimHdr *lh = reinterpret_cast<LeTapeLimHdr *>(behind);
 		LeTapeLim *tl = reinterpret_cast<LeTapeLim *>(lh + 1);
 		lh->meaninertia = h->meaninertia[0];
 		lh->tolerance = h->tolerance[0];
@@ -723,32 +825,31 @@ void mjb_lane_env_tape(const mjb_model_desc *h, double *tape)
 		lh->scale = 1.0 / (h->meaninertia[0] * (h->nv > 1 ? h->nv : 1));
 		lh->nowarm = (h->disableflags & MJB_DSBL_WARMSTART) ? 1.0 : 0.0;
 		lh->norefsafe = (h->disableflags & MJB_DSBL_REFSAFE) ? 1.0 : 0.0;
-		for (int j = 0; j < h->njnt; j++) {
+		for (int j = 0; j < h->njnt && nlim > 0; j++) {
 			if (!h->jnt_limited[j]) continue;
 			LeTapeLim &l = *tl++;
 			l.range[0] = h->jnt_range[2 * j];
 			l.range[1] = h->jnt_range[2 * j + 1];
 			l.margin = h->jnt_margin[j];
-			// getsolparam: a mixed-sign solref is replaced by the default, refsafe, solimp clamped to its legal ranges (mjMINIMP, mjMAXIMP, width >= 0, power >= 1)
-			double sr[2] = { h->jnt_solref[2 * j], h->jnt_solref[2 * j + 1] };
-			if ((sr[0] > 0) != (sr[1] > 0)) sr[0] = 0.02, sr[1] = 1.0;
-			if (!(h->disableflags & MJB_DSBL_REFSAFE) && sr[0] > 0) sr[0] = fmax(sr[0], 2 * h->timestep[0]);
-			const double *si = h->jnt_solimp + 5 * j;
-			const double imp[5] = { fmin(0.9999, fmax(0.0001, si[0])), fmin(0.9999, fmax(0.0001, si[1])), fmax(0.0, si[2]), fmin(0.9999, fmax(0.0001, si[3])), fmax(1.0, si[4]) };
-			l.solref[0] = sr[0], l.solref[1] = sr[1];
-			for (int k = 0; k < 5; k++) l.solimp[k] = imp[k];
+			solparam(h->jnt_solref + 2 * j, h->jnt_solimp + 5 * j, l.solref, l.solimp, l.K, l.B, l.powa, l.powb);
 			l.invweight0 = h->dof_invweight0[h->jnt_dofadr[j]];
-			// mj_makeImpedance's stiffness and damping of the row
-			if (sr[0] > 0) {
-				l.K = 1 / fmax(MJB_MINVAL, imp[1] * imp[1] * sr[0] * sr[0] * sr[1] * sr[1]);
-				l.B = 2 / fmax(MJB_MINVAL, imp[1] * sr[0]);
-			} else {
-				l.K = -sr[0] / fmax(MJB_MINVAL, imp[1] * imp[1]);
-				l.B = -sr[1] / fmax(MJB_MINVAL, imp[1]);
-			}
-			l.powa = 1 / pow(imp[3], imp[4] - 1);
-			l.powb = 1 / pow(1 - imp[3], imp[4] - 1);
 		}
+		LeTapeEq *te = reinterpret_cast<LeTapeEq *>(tl);
+		for (int e = 0; e < h->neq && neqr > 0; e++) {
+			if (!h->eq_active[e]) continue;
+			LeTapeEq &q = *te++;
+			const int j1 = h->eq_obj1id[e], j2 = h->eq_obj2id[e];
+			for (int k = 0; k < 5; k++) q.polycoef[k] = h->eq_data[11 * e + k];
+			q.qpos0[0] = h->qpos0[h->jnt_qposadr[j1]];
+			q.qpos0[1] = j2 >= 0 ? h->qpos0[h->jnt_qposadr[j2]] : 0.0;
+			solparam(h->eq_solref + 2 * e, h->eq_solimp + 5 * e, q.solref, q.solimp, q.K, q.B, q.powa, q.powb);
+			q.invweight0 = h->dof_invweight0[h->jnt_dofadr[j1]] + (j2 >= 0 ? h->dof_invweight0[h->jnt_dofadr[j2]] : 0.0);
+		}
+		behind = reinterpret_cast<unsigned char *>(te);
+	}
+	if (mjb_lane_env_solo_only(h) && h->ntendon > 0) {
+		LeTapeWrap *tw = reinterpret_cast<LeTapeWrap *>(behind);
+		for (int w = 0; w < h->nwrap; w++) tw[w].coef = h->wrap_prm[w];
 	}
 }
 
@@ -780,14 +881,16 @@ struct LePlanIn {
 	bool gc;            // ... and whether a body has gravity compensation: the one-wavefront form alone has the term, in every build
 	bool sens;          // ... and whether it has a frame-axis, velocity- or acceleration-stage sensor (LeSens): the one-wavefront form alone evaluates them, in every build
 	bool wrench_rest;   // ... one of them a force / torque sensor on a body at rest: not in the xfrc builds, whose wrench table has no slot for such a body
-	int nl;             // ... and its joint-limit rows (mjb_lane_env_limits): the plain build of the one-wavefront form alone has the constraint stage
+	int nl;             // ... and its constraint rows (mjb_lane_env_eq_rows + mjb_lane_env_limits): the plain build of the one-wavefront form alone has the constraint stage
+	int nwd;            // ... the dofs those rows touch (their qacc_warmstart lives in LDS beside the packed AR)
+	bool solo;          // ... rows or fixed tendons (mjb_lane_env_solo_only): form 0 of the plain build and no other variant
 };
 
 LeVariant le_plan(const LePlanIn &in)
 {
 	LeVariant v{ 0, 0, 0, in.build, 64, nullptr };
 	const bool plain = in.build == MJB_LE_PLAIN;
-	if (plain && in.nl == 0 && (in.wave_lanes == 16 || in.wave_lanes == 32)) v.wave_lanes = in.wave_lanes;  // (the overlay, hwsim and xfrc builds always run full wavefronts)
+	if (plain && !in.solo && (in.wave_lanes == 16 || in.wave_lanes == 32)) v.wave_lanes = in.wave_lanes;  // (the overlay, hwsim and xfrc builds always run full wavefronts)
 	// the LDS budget per wavefront from the CUs the batch leaves idle: one wavefront per CU may take all of its LDS, two half of it each
 	const int ncu = in.ncu, waves = (in.nenv_batch + 63) / 64;
 	v.lds_kb = (in.lds_kb == 40 || in.lds_kb == 80 || in.lds_kb == 160) ? in.lds_kb : ((ncu > 0 && waves <= ncu) ? 160 : ((ncu > 0 && waves <= 2 * ncu) ? 80 : 40));
@@ -795,7 +898,7 @@ LeVariant le_plan(const LePlanIn &in)
 	// wavefront that assembles the forces and integrates), gravity compensation (the one-wavefront form alone has the term) or a sensor beyond poses and
 	// joint / actuator scalars (the one-wavefront form alone has the velocity sensors in its sweep and the pass behind the qacc solve) -- always hiprtc's --
 	// is planned as if form 0 had been asked for, whatever is: the same budget and lanes per wavefront as that request
-	const int form = (in.fit && (in.na > 0 || in.gc || in.sens || in.nl > 0)) ? 0 : in.form;
+	const int form = (in.fit && (in.na > 0 || in.gc || in.sens || in.solo)) ? 0 : in.form;
 	if (plain && form > 0 && v.lds_kb < 80) {
 		// a forced multi-wavefront form on a batch that would run four wavefronts per CU: the two halves at two per CU
 		v.form = 1;
@@ -819,15 +922,15 @@ LeVariant le_plan(const LePlanIn &in)
 		v.unavailable = "no xfrc build of the kernel has a force / torque sensor on a body at rest: the wrench table has no slot for that body";
 		return v;
 	}
-	if (in.nl > 0 && !plain) {
-		v.unavailable = "no overlay, hwsim or xfrc build of the kernel has the constraint stage of a model with joint limits";
+	if (in.solo && !plain) {
+		v.unavailable = "no overlay, hwsim or xfrc build of the kernel has the constraint stage or the tendon actuators of a model with constraint rows or fixed tendons";
 		return v;
 	}
 	// a hiprtc-built model may be larger than the compiled-in ones: the smallest budget its (qpos, qvel) pairs and body forces fit (fewer wavefronts per
 	// CU then), and of the forms the first one down whose layout fits
-	const int state = le_state_slots(in.nv, in.nmov, in.nl);  // (with the packed AR and the warmstart of a model with joint limits)
+	const int state = le_state_slots(in.nv, in.nmov, in.nl, in.nwd);  // (with the packed AR and the warmstart of a model with constraint rows)
 	if (state > LE_MAX_SLOTS) {
-		v.unavailable = in.nl > 0 ? "the model, with the packed AR of its joint limits, needs more than 160 KB of LDS per wavefront" : "the model needs more than 160 KB of LDS per wavefront";
+		v.unavailable = in.nl > 0 ? "the model, with the packed AR of its constraint rows, needs more than 160 KB of LDS per wavefront" : "the model needs more than 160 KB of LDS per wavefront";
 		return v;
 	}
 	const int least = state <= 40 ? 40 : (state <= 80 ? 80 : 160);
@@ -895,12 +998,14 @@ template <class T> int le_go_topo(const LeVariant &v, const LeLaunch &a)
 }
 LePlanIn le_plan_in(const mjb_model_desc *fit_model, int ncu, int nenv_batch, LeBuild build, int form, int duo_max_waves, int sweep, int lds_kb, int wave_lanes)
 {
-	LePlanIn in{ ncu, nenv_batch, build, form, duo_max_waves, sweep, lds_kb, wave_lanes, fit_model != nullptr, 0, 0, 0, 0, false, false, false, 0 };
+	LePlanIn in{ ncu, nenv_batch, build, form, duo_max_waves, sweep, lds_kb, wave_lanes, fit_model != nullptr, 0, 0, 0, 0, false, false, false, 0, 0, false };
 	if (fit_model) {
 		in.sens = le_extra_sensors(fit_model), in.wrench_rest = le_wrench_at_rest(fit_model);
 		in.nv = fit_model->nv, in.nmov = mjb_lane_env_xfrc_slots(fit_model), in.nbody = fit_model->nbody, in.na = fit_model->na;
 		for (int b = 1; b < fit_model->nbody; b++) in.gc = in.gc || fit_model->body_gravcomp[b] != 0;
-		in.nl = mjb_lane_env_limits(fit_model);
+		in.nl = mjb_lane_env_limits(fit_model) + mjb_lane_env_eq_rows(fit_model);
+		in.nwd = in.nl > 0 ? le_row_dofs(fit_model) : 0;
+		in.solo = mjb_lane_env_solo_only(fit_model) != 0;
 	}
 	return in;
 }

@@ -229,13 +229,13 @@ constexpr int RING_DUO2 = 2, RING_TRIO = 3;  // depth of the pose ring: the pipe
 constexpr int le_ring_slots(int depth) { return 6 * depth; }  // (xpos, xmat) of a body: 12 doubles
 // pair slots of a quartet block behind the trio's layout: O's quaternion ring (2 x 4), C's cdof ring (2 x 3), X's mail slot
 constexpr int QUARTET_EXTRA = 15;
-// (nl: the joint-limit rows of a model that has them, LeLim -- the packed AR of the constraint stage, nl (nl + 1) / 2 doubles, and qacc_warmstart of the
-//  limited dofs, nl doubles, two to a pair slot, behind cfrc_body: one-wavefront form only)
-constexpr int le_lim_slots(int nl) { return (nl * (nl + 1) / 2 + nl + 1) / 2; }
-constexpr int le_state_slots(int nv, int nmov, int nl = 0) { return nv + 3 * nmov + le_lim_slots(nl); }  // (qpos, qvel) pairs + cfrc_body: what every form must hold
-constexpr int le_solo_slots(int nv, int nmov, int budget, int nl = 0)     // ... + five of cinert per body while the budget lasts
+// (nr: the constraint rows of a model that has them, LeLimQ -- the packed AR of the constraint stage, nr (nr + 1) / 2 doubles, and qacc_warmstart of the
+//  nw dofs the rows touch (a limit-only model: nw = nr), two doubles to a pair slot, behind cfrc_body: one-wavefront form only)
+constexpr int le_lim_slots(int nr, int nw) { return (nr * (nr + 1) / 2 + nw + 1) / 2; }
+constexpr int le_state_slots(int nv, int nmov, int nr = 0, int nw = 0) { return nv + 3 * nmov + le_lim_slots(nr, nw); }  // (qpos, qvel) pairs + cfrc_body: what every form must hold
+constexpr int le_solo_slots(int nv, int nmov, int budget, int nr = 0, int nw = 0)  // ... + five of cinert per body while the budget lasts
 {
-	int at = le_state_slots(nv, nmov, nl);
+	int at = le_state_slots(nv, nmov, nr, nw);
 	for (int k = 0; k < nmov; k++)
 		if (at + 5 <= budget) at += 5;
 	return at;
@@ -247,18 +247,68 @@ constexpr int le_duo2_slots(int nv, int nmov) { return le_full_slots(nv, nmov) +
 constexpr int le_trio_slots(int nv, int nmov, int nbody) { return le_full_slots(nv, nmov) + le_ring_slots(RING_TRIO) + le_exchange_slots(nv) + nbody; }  // (+ a (sin, cos) slot per body)
 constexpr int le_quartet_slots(int nv, int nmov, int nbody) { return le_trio_slots(nv, nmov, nbody) + QUARTET_EXTRA; }
 
-// Joint limits (mjModel.jnt_limited of a model whose only constraint rows are hinge / slide limit rows under PGS, mjb_lane_env_eligible): a topology may
-// list its limited joints, jnt_limited[NJNT] (the hiprtc-built ones of such models do; a topology without the array has no constraint stage).  Row r of the
-// static row list is the r-th limited joint; range, margin, solref and solimp are run-time data (LeTapeLim).  One-wavefront form, plain build only.
+// Constraint rows (a model whose only rows are joint-equality rows and hinge / slide joint-limit rows under PGS, mjb_lane_env_eligible): a topology may
+// list its limited joints, jnt_limited[NJNT], and the joint pairs of its active joint equalities, eq_jnt1[] / eq_jnt2[] (-1: the one-joint form) -- the
+// hiprtc-built ones of such models do; a topology without the arrays has no constraint stage.  The static row list is MuJoCo's: the equalities in equality
+// order, then the limited joints in joint order; every number of a row is run-time data (LeTapeEq, LeTapeLim).  One-wavefront form, plain build only.
 template <class T, class = void> struct LeLim { static constexpr bool on(int) { return false; } };
 template <class T> struct LeLim<T, decltype((void)T::jnt_limited)> { static constexpr bool on(int j) { return T::jnt_limited[j] != 0; } };
+template <class T, class = void> struct LeEq {
+	static constexpr int n = 0;
+	static constexpr int j1(int) { return 0; }
+	static constexpr int j2(int) { return -1; }
+};
+template <class T> struct LeEq<T, decltype((void)T::eq_jnt1)> {
+	static constexpr int n = (int)(sizeof(T::eq_jnt1) / sizeof(int));
+	static constexpr int j1(int e) { return T::eq_jnt1[e]; }
+	static constexpr int j2(int e) { return T::eq_jnt2[e]; }
+};
 template <class T> struct LeLimQ {
-	static constexpr int n() { int k = 0; for (int j = 0; j < T::NJNT; j++) if (LeLim<T>::on(j)) k++; return k; }
-	static constexpr int jnt(int r) { int k = 0; for (int j = 0; j < T::NJNT; j++) if (LeLim<T>::on(j) && k++ == r) return j; return 0; }  // (= its dof: one-dof joints in dof order)
+	static constexpr int ne() { return LeEq<T>::n; }                                                                     // equality rows: the first ne()
+	static constexpr int nl() { int k = 0; for (int j = 0; j < T::NJNT; j++) if (LeLim<T>::on(j)) k++; return k; }  // limit rows: behind them
+	static constexpr int n() { return ne() + nl(); }
+	static constexpr bool is_eq(int r) { return r < ne(); }
+	// the row's joint (= its dof: one-dof joints in dof order), and an equality row's second joint (-1: none)
+	static constexpr int jnt(int r)
+	{
+		if (r < ne()) return LeEq<T>::j1(r);
+		int k = ne();
+		for (int j = 0; j < T::NJNT; j++) if (LeLim<T>::on(j) && k++ == r) return j;
+		return 0;
+	}
+	static constexpr int jnt2(int r) { return r < ne() ? LeEq<T>::j2(r) : -1; }
 	// entry a of M^-1 e_j is not a known zero: dofs a and j share an ancestor (or one is the other's)
 	static constexpr bool coupled(int a, int j) { for (int d = 0; d < T::NV; d++) if (Tq<T>::anc(d, a) && Tq<T>::anc(d, j)) return true; return false; }
+	// ... of M^-1 J_r': the union over the row's dofs;  dof i is one of the row's dofs or an ancestor of one;  AR_kr is not a known zero
+	static constexpr bool rcoupled(int a, int r) { return coupled(a, jnt(r)) || (jnt2(r) >= 0 && coupled(a, jnt2(r))); }
+	static constexpr bool ranc(int i, int r) { return Tq<T>::anc(i, jnt(r)) || (jnt2(r) >= 0 && Tq<T>::anc(i, jnt2(r))); }
+	static constexpr bool rows_coupled(int k, int r) { return rcoupled(jnt(k), r) || (jnt2(k) >= 0 && rcoupled(jnt2(k), r)); }
+	// the dofs some row touches, in dof order: their qacc_warmstart and qfrc_constraint live with the stage (a limit-only model: the limited dofs, row order)
+	static constexpr bool in_rows(int d) { for (int r = 0; r < n(); r++) if (jnt(r) == d || jnt2(r) == d) return true; return false; }
+	static constexpr int nw() { int k = 0; for (int d = 0; d < T::NV; d++) if (in_rows(d)) k++; return k; }
+	static constexpr int widx(int d) { int k = 0; for (int a = 0; a < d; a++) if (in_rows(a)) k++; return k; }
+	static constexpr int wdof(int w) { int k = 0; for (int d = 0; d < T::NV; d++) if (in_rows(d) && k++ == w) return d; return 0; }
 	static constexpr int ar(int i, int k) { const int a = i < k ? i : k, b = i < k ? k : i; return a * n() - a * (a - 1) / 2 + (b - a); }  // AR_ik = AR_ki in the packed triangle
-	static constexpr int ws(int r) { return n() * (n() + 1) / 2 + r; }  // row r's qacc_warmstart behind the triangle
+	static constexpr int ws(int w) { return n() * (n() + 1) / 2 + w; }  // qacc_warmstart of the w-th such dof, behind the triangle
+	static constexpr int slots() { return le_lim_slots(n(), nw()); }
+};
+// Fixed tendons (mjb_lane_env_eligible: they carry actuators and nothing else): a topology may list which actuators drive a tendon, act_tendon[NU] (-1:
+// a joint actuator), and every tendon's wraps, tendon_adr[] / tendon_num[] / wrap_jnt[] -- the hiprtc-built ones of such models do; for a topology without
+// the arrays every actuator is a joint actuator.  The moment arm of a tendon actuator is the compile-time list of its wraps' dofs; the coefficients are
+// run-time data (LeTapeWrap, behind the row records of the tape).
+template <class T, class = void> struct LeTen {
+	static constexpr int nwrap = 0;
+	static constexpr bool on(int) { return false; }
+	static constexpr int num(int) { return 0; }
+	static constexpr int wrap(int, int) { return 0; }
+	static constexpr int jnt(int, int) { return 0; }
+};
+template <class T> struct LeTen<T, decltype((void)T::act_tendon)> {
+	static constexpr int nwrap = (int)(sizeof(T::wrap_jnt) / sizeof(int));
+	static constexpr bool on(int i) { return T::act_tendon[i] >= 0; }
+	static constexpr int num(int i) { return on(i) ? T::tendon_num[T::act_tendon[i]] : 0; }
+	static constexpr int wrap(int i, int k) { return T::tendon_adr[T::act_tendon[i]] + k; }  // the actuator's k-th wrap: its record of the tape ...
+	static constexpr int jnt(int i, int k) { return T::wrap_jnt[wrap(i, k)]; }               // ... and its dof
 };
 
 template <class T, int LP> struct Lds {
@@ -279,7 +329,7 @@ template <class T, int LP> struct Lds {
 	}
 	static constexpr int cin_slot(int b)  // first of the body's five cinert slots, -1: the body's cinert stays in registers
 	{
-		int at = slot(T::NBODY) + le_lim_slots(LeLimQ<T>::n());
+		int at = slot(T::NBODY) + LeLimQ<T>::slots();
 		for (int a = T::NBODY - 1; a >= 1; a--) {
 			if (!needed(a)) continue;
 			if (at + 5 > LP) return -1;
@@ -289,7 +339,7 @@ template <class T, int LP> struct Lds {
 		return -1;
 	}
 	static constexpr int nmov() { return (slot(T::NBODY) - T::NV) / 3; }  // the needed bodies
-	static constexpr int nslots() { return le_solo_slots(T::NV, nmov(), LP, LeLimQ<T>::n()); }
+	static constexpr int nslots() { return le_solo_slots(T::NV, nmov(), LP, LeLimQ<T>::n(), LeLimQ<T>::nw()); }
 	static constexpr int bytes() { return nslots() * LE_SLOT_BYTES; }
 };
 
@@ -467,10 +517,12 @@ DEVI void lane_env_body(const KernelParams MJB_AS4 *__restrict__ P, const int ns
 	constexpr int LPE = PIPE ? (1 << 20) : (DUO ? LP - DuoSlots<NV>::n : LP);
 	using LD = Lds<T, LPE>;
 	using LM = LeLimQ<T>;
-	constexpr int NL = LM::n();  // joint-limit rows (0: the model has no constraint stage, and none of its code)
-	static_assert(NL == 0 || (ROLE == LE_SOLO && !PE && !HW && !XF), "lane = env kernel: joint limits run the plain build of the solo form");
-	static_assert(LD::slot(T::NBODY) + le_lim_slots(NL) <= LPE, "lane = env kernel: state and forces of the topology need more LDS than this instantiation's budget");
-	[[maybe_unused]] constexpr int LIM0 = LD::slot(T::NBODY);  // (NL > 0) first pair slot of the packed AR | qacc_warmstart doubles
+	// constraint rows: equality rows first, limit rows behind (NR == 0: the model has no constraint stage, and none of its code) | the dofs they touch
+	constexpr int NR = LM::n(), NE = LM::ne(), NL = LM::nl(), NW = LM::nw();
+	constexpr bool TEN = [] { for (int i = 0; i < NU; i++) if (LeTen<T>::on(i)) return true; return false; }();  // some actuator drives a fixed tendon
+	static_assert((NR == 0 && !TEN) || (ROLE == LE_SOLO && !PE && !HW && !XF), "lane = env kernel: constraint rows and tendon actuators run the plain build of the solo form");
+	static_assert(LD::slot(T::NBODY) + LM::slots() <= LPE, "lane = env kernel: state and forces of the topology need more LDS than this instantiation's budget");
+	[[maybe_unused]] constexpr int LIM0 = LD::slot(T::NBODY);  // (NR > 0) first pair slot of the packed AR | qacc_warmstart doubles
 	// (trio) body b's half-angle (sin, cos) comes from C: a hinge whose two predecessors in the sweep are needed bodies too (C publishes them two barriers ahead)
 	constexpr auto SCUSE = [](int b) {
 		if (b < 3 || b >= T::NBODY || T::body_jnt[b] < 0) return false;
@@ -492,7 +544,7 @@ DEVI void lane_env_body(const KernelParams MJB_AS4 *__restrict__ P, const int ns
 	const bool live = env_raw < env_hi;
 	const int env = live ? env_raw : env_hi - 1;
 	const size_t ev = (size_t)env;
-	// (NL > 0) double k of this lane's constraint-stage storage: the packed AR triangle (LM::ar), then qacc_warmstart of the limited dofs (LM::ws)
+	// (NR > 0) double k of this lane's constraint-stage storage: the packed AR triangle (LM::ar), then qacc_warmstart of the rows' dofs (LM::ws)
 	[[maybe_unused]] auto lim_ld = [&](auto K) -> double {
 		constexpr int k = K;
 		if constexpr (k & 1) return lp[64 * (LIM0 + k / 2)].b;
@@ -522,7 +574,7 @@ DEVI void lane_env_body(const KernelParams MJB_AS4 *__restrict__ P, const int ns
 		}
 		sfor<NU>([&](auto I) { cn[I] = DV ? s.ctrlnoise[ev * NU + I] : 0.0; });
 		if constexpr (NA > 0) sfor<NA>([&](auto I) { act[I] = s.act[ev * NA + I]; });
-		if constexpr (NL > 0) sfor<NL>([&](auto R) { lim_st(IC<LM::ws(R)>{}, s.qacc_warmstart[ev * NV + LM::jnt(R)]); });  // (lives with the lane across the fused steps)
+		if constexpr (NR > 0) sfor<NW>([&](auto W) { lim_st(IC<LM::ws(W)>{}, s.qacc_warmstart[ev * NV + LM::wdof(W)]); });  // (lives with the lane across the fused steps)
 		time = s.time[ev];
 		if constexpr (DUO) {  // the load is "Euler of step -1": P's verdicts on the loaded state go to V by mail
 			if constexpr (DP) lp[64 * MAIL] = Pair{ (double)((badp_next ? 2 : 0) | (badv_next ? 1 : 0)), 0.0 };
@@ -649,7 +701,7 @@ DEVI void lane_env_body(const KernelParams MJB_AS4 *__restrict__ P, const int ns
 					});
 				}
 				if constexpr (NA > 0) sfor<NA>([&](auto I) { act[I] = bad ? 0.0 : act[I]; });
-				if constexpr (NL > 0) sfor<NL>([&](auto R) { const double w = pinv(lim_ld(IC<LM::ws(R)>{})); lim_st(IC<LM::ws(R)>{}, bad ? 0.0 : w); });  // (mj_resetData: qacc_warmstart = 0)
+				if constexpr (NR > 0) sfor<NW>([&](auto W) { const double w = pinv(lim_ld(IC<LM::ws(W)>{})); lim_st(IC<LM::ws(W)>{}, bad ? 0.0 : w); });  // (mj_resetData: qacc_warmstart = 0)
 				time = bad ? 0.0 : time;
 				wasreset = wasreset || bad;
 				rs = bad;
@@ -658,8 +710,8 @@ DEVI void lane_env_body(const KernelParams MJB_AS4 *__restrict__ P, const int ns
 		}
 
 		double qacc[NV], qaccd[NV];  // M^-1 f, and the acceleration Euler advances with: (M + h B)^-1 f under implicit joint damping
-		// (NL > 0) what the constraint stage leaves: qfrc_constraint of the limited dofs (J' f: the row's signed force), the env's active rows, its PGS sweeps
-		[[maybe_unused]] double qfc[NL > 0 ? NL : 1];
+		// (NR > 0) what the constraint stage leaves: qfrc_constraint = J' f on the dofs the rows touch, the env's active rows, its PGS sweeps
+		[[maybe_unused]] double qfc[NW > 0 ? NW : 1];
 		[[maybe_unused]] int c_nefc = 0, c_iter = 0;
 		// (NA > 0) the activation states mj_Euler commits: act + h act_dot, clamped to actrange.  Formed where the forces are assembled, on either trip of the
 		// loop below from the trip's own act -- a lane mj_checkAcc reset forms it again from zero --, and committed once, behind the loop
@@ -1774,11 +1826,32 @@ DEVI void lane_env_body(const KernelParams MJB_AS4 *__restrict__ P, const int ns
 				});
 				const bool act_on = !(m.disableflags & MJB_DSBL_ACTUATION);
 				const bool clamp_on = !(m.disableflags & MJB_DSBL_CLAMPCTRL);
+				// (TEN) the wrap records of the tape, behind the row records: the coefficients of the tendons' moment arms
+				[[maybe_unused]] const LeTapeWrap MJB_AS4 *const tw = reinterpret_cast<const LeTapeWrap MJB_AS4 *>(
+					reinterpret_cast<const unsigned char MJB_AS4 *>(ta + NU) + (NR > 0 ? sizeof(LeTapeLimHdr) + NL * sizeof(LeTapeLim) + NE * sizeof(LeTapeEq) : 0));
 				sfor<NU>([&](auto U) {
-					constexpr int i = U, j = T::act_jnt[i];
+					// (an actuator on a fixed tendon, LeTen: its moment arm is the compile-time list of its wraps' dofs, gear * the tape's coefficients)
+					constexpr int i = U;
+					constexpr bool ten = LeTen<T>::on(i);
+					constexpr int j = ten ? 0 : T::act_jnt[i], nwr = LeTen<T>::num(i);
 					double force = 0;
 					const LeTapeAct MJB_AS4 &A = ta[i];
 					const double gear = A.gear;
+					// actuator_length = gear * the joint's position | the tendon's length, sum_w coef_w qpos_w;  actuator_velocity = moment . qvel
+					auto alen = [&]() -> double {
+						if constexpr (ten) {
+							double sm = 0;
+							sfor<nwr>([&](auto K) { sm += tw[LeTen<T>::wrap(i, K)].coef * sq[LeTen<T>::jnt(i, K)].a; });
+							return sm * gear;
+						} else return sq[j].a * gear;
+					};
+					auto avel = [&]() -> double {
+						if constexpr (ten) {
+							double sm = 0;
+							sfor<nwr>([&](auto K) { sm += gear * tw[LeTen<T>::wrap(i, K)].coef * sq[LeTen<T>::jnt(i, K)].b; });
+							return sm;
+						} else return sq[j].b * gear;
+					};
 					// (NA > 0) an actuator with an activation state: its force is gain * act + bias on the CURRENT act, and the clamped ctrl drives act_dot
 					constexpr bool stateful = NA > 0 && T::act_dyntype[i] != MJB_DYN_NONE;
 					constexpr int ja = stateful ? T::act_actadr[i] : 0;
@@ -1795,7 +1868,7 @@ DEVI void lane_env_body(const KernelParams MJB_AS4 *__restrict__ P, const int ns
 							else dot = (c - a0) / A.dyntau;  // (filter: the tape holds max(mjMINVAL, dynprm[0]))
 							c = a0;
 						}
-						const double len = sq[j].a * gear, vel = sq[j].b * gear;
+						const double len = alen(), vel = avel();
 						double gain = 0, bs = 0;
 						if constexpr (PE) {
 							gain = pe_ld(OV::act(i, 0));
@@ -1808,6 +1881,8 @@ DEVI void lane_env_body(const KernelParams MJB_AS4 *__restrict__ P, const int ns
 						}
 						force = gain * c + bs;
 						if constexpr (T::act_forcelimited[i]) force = clampd(force, A.forcelo, A.forcehi);
+						if constexpr (ten) sfor<nwr>([&](auto K) { f[LeTen<T>::jnt(i, K)] += gear * tw[LeTen<T>::wrap(i, K)].coef * force; });
+						else
 						f[j] += gear * force;
 					}
 					if constexpr (stateful) {  // mj_advance's half of mj_Euler for this actuator (advance_act, mjb_step.hip)
@@ -1819,7 +1894,7 @@ DEVI void lane_env_body(const KernelParams MJB_AS4 *__restrict__ P, const int ns
 						sfor<T::NSENSOR>([&](auto S) {
 							constexpr int q = S;
 							if constexpr (T::sensor_objid[q] == i && (T::sensor_type[q] == MJB_SENS_ACTUATORFRC || T::sensor_type[q] == MJB_SENS_ACTUATORPOS || T::sensor_type[q] == MJB_SENS_ACTUATORVEL)) {
-								double v = T::sensor_type[q] == MJB_SENS_ACTUATORFRC ? force : (T::sensor_type[q] == MJB_SENS_ACTUATORPOS ? sq[j].a * gear : sq[j].b * gear);
+								double v = T::sensor_type[q] == MJB_SENS_ACTUATORFRC ? force : (T::sensor_type[q] == MJB_SENS_ACTUATORPOS ? alen() : avel());
 								const double cut = m.sensor_cutoff[q];
 								sd[T::sensor_adr[q]] = cut > 0 ? clampd(v, -cut, cut) : v;
 							}
@@ -2043,113 +2118,165 @@ DEVI void lane_env_body(const KernelParams MJB_AS4 *__restrict__ P, const int ns
 			else
 			sfor<NV>([&](auto I) { qacc[I] = x[I]; qaccd[I] = damp_on ? y[I] : x[I]; });
 
-			// ================= the constraint stage of a model with joint limits: mj_makeConstraint, mj_projectConstraint, mj_referenceConstraint, mj_solPGS =================
-			// One env per lane, the oracle's mjo_make_constraint (hinge / slide limits) .. mjo_fwd_constraint (PGS) in its operation order.  The row list is static --
-			// row r = the r-th limited joint, J = +- e_j --; which rows an env has is per-lane data: selects.  Which rows ANY lane of the wavefront has is a
-			// ballot: rows nobody has are skipped by scalar branches, a wavefront without rows pays the NL comparisons and nothing else.  Row constants
-			// (LeTapeLim) are wave-uniform, and so are the branches on them.  qacc (= qacc_smooth so far) and qaccd come out constrained: the acceleration-stage
-			// sensors, mj_checkAcc and mj_Euler below see them.  On the retry of the attempt loop the stage runs again on the reset state.
-			if constexpr (NL > 0) {
+			// ================= the constraint stage of a model with constraint rows: mj_makeConstraint, mj_projectConstraint, mj_referenceConstraint, mj_solPGS =================
+			// One env per lane, the oracle's mjo_make_constraint (joint equalities, hinge / slide limits) .. mjo_fwd_constraint (PGS) in its operation order.  The
+			// row list is static, in MuJoCo's order: the NE joint-equality rows -- J = e_d1 - poly'(x) e_d2, the second coefficient per-lane data --, then the NL
+			// limit rows -- the r-th limited joint, J = +- e_j.  An equality row is every lane's unless mjDSBL_EQUALITY / mjDSBL_CONSTRAINT is set (wave-uniform):
+			// its gates are compile-time.  Which limit rows an env has is per-lane data: selects.  Which of them ANY lane of the wavefront has is a ballot: rows
+			// nobody has are skipped by scalar branches, a wavefront without rows pays the NL comparisons and nothing else.  Row constants (LeTapeEq, LeTapeLim)
+			// are wave-uniform, and so are the branches on them.  qacc (= qacc_smooth so far) and qaccd come out constrained: the acceleration-stage sensors,
+			// mj_checkAcc and mj_Euler below see them.  On the retry of the attempt loop the stage runs again on the reset state.
+			if constexpr (NR > 0) {
 				const LeTapeLimHdr MJB_AS4 *const tlh = reinterpret_cast<const LeTapeLimHdr MJB_AS4 *>(ta + NU);
 				const LeTapeLim MJB_AS4 *const tl = reinterpret_cast<const LeTapeLim MJB_AS4 *>(tlh + 1);
-				const bool lim_on = !(m.disableflags & (MJB_DSBL_CONSTRAINT | MJB_DSBL_LIMIT));
-				bool ract[NL], rwav[NL], anyw = false, has = false;  // the lane has the row | some lane of the wavefront has it
-				double rsg[NL], rpos[NL];                            // the side: J = rsg e_j (lower +1, upper -1) | efc_pos
+				[[maybe_unused]] const LeTapeEq MJB_AS4 *const te = reinterpret_cast<const LeTapeEq MJB_AS4 *>(tl + NL);
+				[[maybe_unused]] const bool lim_on = !(m.disableflags & (MJB_DSBL_CONSTRAINT | MJB_DSBL_LIMIT));
+				[[maybe_unused]] const bool eq_on = !(m.disableflags & (MJB_DSBL_CONSTRAINT | MJB_DSBL_EQUALITY));
+				bool ract[NR], rwav[NR], anyw = false, has = false;  // the lane has the row | some lane of the wavefront has it (an equality row: always)
+				double rsg[NR], rpos[NR];                            // J's entry at the row's joint (equality +1; limit: lower +1, upper -1) | efc_pos
+				[[maybe_unused]] double rc2[NE > 0 ? NE : 1];        // an equality row's entry at its second joint, -poly'(x)
 				int nrow = 0;
-				sfor<NL>([&](auto R) {
+				sfor<NW>([&](auto W) { qfc[W] = 0; });
+				sfor<NR>([&](auto R) {
 					constexpr int r = R, j = LM::jnt(r);
-					const double q = lp[64 * j].a, mg = tl[r].margin;
-					const double dlo = q - tl[r].range[0], dhi = tl[r].range[1] - q;
-					const bool up = dhi < mg, a = lim_on && ((dlo < mg) || up);  // (range > 2 margin: at most one side)
-					ract[r] = a;
-					rsg[r] = up ? -1.0 : 1.0;
-					rpos[r] = up ? dhi : dlo;
-					rwav[r] = __builtin_amdgcn_ballot_w64(a) != 0;
-					anyw = anyw || rwav[r];
-					has = has || a;
-					nrow += a ? 1 : 0;
-					qfc[r] = 0;
+					if constexpr (LM::is_eq(r)) {
+						constexpr int j2 = LM::jnt2(r);
+						const LeTapeEq MJB_AS4 &E = te[r];
+						double poly = E.polycoef[0], der = 0;
+						if constexpr (j2 >= 0) {
+							const double x = lp[64 * (j2 < 0 ? 0 : j2)].a - E.qpos0[1];
+							poly = E.polycoef[0] + x * (E.polycoef[1] + x * (E.polycoef[2] + x * (E.polycoef[3] + x * E.polycoef[4])));
+							der = E.polycoef[1] + x * (2 * E.polycoef[2] + x * (3 * E.polycoef[3] + x * 4 * E.polycoef[4]));
+						}
+						ract[r] = eq_on;
+						rwav[r] = true;
+						rsg[r] = 1.0;
+						rc2[r] = -der;
+						rpos[r] = lp[64 * j].a - E.qpos0[0] - poly;
+						anyw = anyw || eq_on;
+						has = has || eq_on;
+						nrow += eq_on ? 1 : 0;
+					} else {
+						constexpr int l = r - NE;
+						const double q = lp[64 * j].a, mg = tl[l].margin;
+						const double dlo = q - tl[l].range[0], dhi = tl[l].range[1] - q;
+						const bool up = dhi < mg, a = lim_on && ((dlo < mg) || up);  // (range > 2 margin: at most one side)
+						ract[r] = a;
+						rsg[r] = up ? -1.0 : 1.0;
+						rpos[r] = up ? dhi : dlo;
+						rwav[r] = __builtin_amdgcn_ballot_w64(a) != 0;
+						anyw = anyw || rwav[r];
+						has = has || a;
+						nrow += a ? 1 : 0;
+					}
 				});
 				c_nefc = nrow;
 				c_iter = 0;
 				if (anyw) {  // (wave-uniform)
-					double rD[NL], raref[NL], rb[NL], rf[NL], rinv[NL];
-					// ---- row parameters (mj_makeImpedance: row_params_x / impedance), aref (mj_referenceConstraint), b = J qacc_smooth - aref
-					[[maybe_unused]] double rR[NL];
-					sfor<NL>([&](auto R) {
-						constexpr int r = R, j = LM::jnt(r);
+					double rD[NR], raref[NR], rb[NR], rf[NR], rinv[NR];
+					// J_r . v for a vector held per dof: the row's one or two entries
+					auto jdot = [&](auto R, const double *v) -> double {
+						constexpr int r = R, j = LM::jnt(r), j2 = LM::jnt2(r);
+						if constexpr (j2 >= 0) return rsg[r] * v[j] + rc2[r < NE ? r : 0] * v[j2 < 0 ? 0 : j2];
+						else return rsg[r] * v[j];
+					};
+					// mj_makeImpedance's impedance of a row at pm = pos - margin (row_params_x / impedance) from its clamped solimp and the curve's two constants
+					auto impedance = [&](const double MJB_AS4 *si, const double powa, const double powb, const double pm) -> double {
+						const double d0 = si[0], d1 = si[1], wd = si[2], mid = si[3], pw = si[4];
+						double imp;
+						if (d0 == d1 || wd <= MJB_MINVAL) imp = 0.5 * (d0 + d1);
+						else {
+							const double xi = fabs(pm / wd);
+							double yv;
+							if (pw == 1) yv = xi;
+							else {
+								const bool lowh = xi <= mid;
+								const double xx = lowh ? xi : 1 - xi;
+								double px;
+								if (pw == 2) px = xx * xx;
+								else px = pow(xx, pw);
+								const double ya = powa * px, yb = 1 - powb * px;
+								yv = lowh ? ya : yb;
+							}
+							const double mixed = d0 + yv * (d1 - d0);
+							imp = (xi >= 1) ? d1 : ((xi <= 0) ? d0 : mixed);
+						}
+						return imp;
+					};
+					// ---- row parameters (mj_makeImpedance), aref (mj_referenceConstraint), b = J qacc_smooth - aref
+					[[maybe_unused]] double rR[NR];
+					sfor<NR>([&](auto R) {
+						constexpr int r = R, j = LM::jnt(r), j2 = LM::jnt2(r);
 						rD[r] = 1, raref[r] = 0, rb[r] = 0, rf[r] = 0, rinv[r] = 1, rR[r] = 1;
 						if (rwav[r]) {
-							const LeTapeLim MJB_AS4 &L = tl[r];
-							const double d0 = L.solimp[0], d1 = L.solimp[1], wd = L.solimp[2], mid = L.solimp[3], pw = L.solimp[4], mg = L.margin;
-							const double pm = rpos[r] - mg;
-							double imp;
-							if (d0 == d1 || wd <= MJB_MINVAL) imp = 0.5 * (d0 + d1);
-							else {
-								const double xi = fabs(pm / wd);
-								double yv;
-								if (pw == 1) yv = xi;
-								else {
-									const bool lowh = xi <= mid;
-									const double xx = lowh ? xi : 1 - xi;
-									double px;
-									if (pw == 2) px = xx * xx;
-									else px = pow(xx, pw);
-									const double ya = L.powa * px, yb = 1 - L.powb * px;
-									yv = lowh ? ya : yb;
-								}
-								const double mixed = d0 + yv * (d1 - d0);
-								imp = (xi >= 1) ? d1 : ((xi <= 0) ? d0 : mixed);
+							double imp, pm, invw, Kk, Bb;
+							if constexpr (LM::is_eq(r)) {
+								const LeTapeEq MJB_AS4 &E = te[r];
+								pm = rpos[r];  // (margin 0)
+								imp = impedance(E.solimp, E.powa, E.powb, pm);
+								invw = E.invweight0, Kk = E.K, Bb = E.B;
+							} else {
+								const LeTapeLim MJB_AS4 &L = tl[r - NE];
+								pm = rpos[r] - L.margin;
+								imp = impedance(L.solimp, L.powa, L.powb, pm);
+								invw = L.invweight0, Kk = L.K, Bb = L.B;
 							}
-							const double Rr = fmax(MJB_MINVAL, (1 - imp) * L.invweight0 / imp);
+							const double Rr = fmax(MJB_MINVAL, (1 - imp) * invw / imp);
 							const double Ra = ract[r] ? Rr : 1.0;  // (a lane without the row: harmless numbers, its force stays zero)
-							const Pair sj = lp[64 * j];
-							const double vel = rsg[r] * sj.b;
-							const double ar = -L.B * vel - L.K * imp * pm;
+							double vel = rsg[r] * lp[64 * j].b, acc = rsg[r] * qacc[j];
+							if constexpr (j2 >= 0) {
+								vel += rc2[r < NE ? r : 0] * lp[64 * (j2 < 0 ? 0 : j2)].b;
+								acc += rc2[r < NE ? r : 0] * qacc[j2 < 0 ? 0 : j2];
+							}
+							const double ar = -Bb * vel - Kk * imp * pm;
 							rR[r] = Ra;
 							rD[r] = 1.0 / Ra;
 							raref[r] = ract[r] ? ar : 0.0;
-							rb[r] = ract[r] ? rsg[r] * qacc[j] - ar : 0.0;
+							rb[r] = ract[r] ? acc - ar : 0.0;
 						}
 					});
-					// ---- AR = J M^-1 J' + diag(R): the columns of M^-1 of the wave-active limited dofs from the L'DL factor of M (unit right-hand side, the
-					// known zeros skipped), symmetrised as the oracle does, signed and packed into LDS.  Column r leaves its entries for the rows behind it raw;
-					// the rows behind symmetrise them with their own where both rows are wave-active
-					sfor<NL>([&](auto R) {
-						constexpr int r = R, j = LM::jnt(r);
+					// ---- AR = J M^-1 J' + diag(R): M^-1 J_r' of the wave-active rows from the L'DL factor of M (the right-hand side is the row's one or two
+					// entries, the known zeros skipped on the union of their patterns), AR_kr = J_k . (M^-1 J_r'), symmetrised as the oracle does and packed into
+					// LDS.  Column r leaves its entries for the rows behind it raw; the rows behind symmetrise them with their own where both rows are wave-active
+					sfor<NR>([&](auto R) {
+						constexpr int r = R, j = LM::jnt(r), j2 = LM::jnt2(r);
 						if (rwav[r]) {
 							double c[NV];
-							sfor<NV>([&](auto I) { c[I] = (int)I == j ? 1.0 : 0.0; });
+							sfor<NV>([&](auto I) {
+								if constexpr ((int)I == j) c[I] = rsg[r];
+								else if constexpr ((int)I == j2) c[I] = rc2[r < NE ? r : 0];
+								else c[I] = 0.0;
+							});
 							sfor<NV>([&](auto Ii) {
 								constexpr int i = NV - 1 - Ii;
-								if constexpr (Q::anc(i, j))
+								if constexpr (LM::ranc(i, r))
 									sfor<NV>([&](auto A) {
 										constexpr int a = A;
 										if constexpr (a < i && Q::anc(a, i)) c[a] -= qM[i][a] * c[i];
 									});
 							});
-							sfor<NV>([&](auto I) { if constexpr (Q::anc(I, j)) c[I] *= dinv[I]; });
+							sfor<NV>([&](auto I) { if constexpr (LM::ranc(I, r)) c[I] *= dinv[I]; });
 							sfor<NV>([&](auto I) {
 								constexpr int i = I;
 								sfor<NV>([&](auto Ai) {
 									constexpr int a = NV - 1 - Ai;
-									if constexpr (a < i && Q::anc(a, i) && LM::coupled(a, j)) c[i] -= qM[i][a] * c[a];
+									if constexpr (a < i && Q::anc(a, i) && LM::rcoupled(a, r)) c[i] -= qM[i][a] * c[a];
 								});
 							});
-							sfor<NL>([&](auto K) {
-								constexpr int k = K, kj = LM::jnt(k);
+							sfor<NR>([&](auto K) {
+								constexpr int k = K;
 								if constexpr (k == r) {
-									const double aii = c[j] + rR[r];
+									const double aii = jdot(R, c) + rR[r];
 									lim_st(IC<LM::ar(r, r)>{}, aii);
 									rinv[r] = 1.0 / aii;
-								} else if constexpr (!LM::coupled(kj, j)) {
+								} else if constexpr (!LM::rows_coupled(k, r)) {
 									if constexpr (k > r) lim_st(IC<LM::ar(r, k)>{}, 0.0);  // (two trees: a known zero on both sides)
 								} else if constexpr (k > r) {
-									lim_st(IC<LM::ar(r, k)>{}, c[kj]);
+									lim_st(IC<LM::ar(r, k)>{}, jdot(K, c));
 								} else {
 									if (rwav[k]) {
 										const double g = lim_ld(IC<LM::ar(k, r)>{});
-										lim_st(IC<LM::ar(k, r)>{}, (rsg[r] * rsg[k]) * (0.5 * (c[kj] + g)));
+										lim_st(IC<LM::ar(k, r)>{}, 0.5 * (jdot(K, c) + g));
 									}
 								}
 							});
@@ -2158,50 +2285,55 @@ DEVI void lane_env_body(const KernelParams MJB_AS4 *__restrict__ P, const int ns
 					// (read unconditionally, zero by select where row k is nobody's: a row's reads leave together instead of one behind each scalar branch -- and a
 					//  stale entry of an inactive row never meets a force, not even a zero one)
 					auto AR = [&](auto I, auto K) -> double { const double a = lim_ld(IC<LM::ar(I, K)>{}); return rwav[K] ? a : 0.0; };
-					// ---- warmstart: the forces qacc_warmstart implies, kept if their dual cost 0.5 f' AR f + f' b is not positive
+					// ---- warmstart: the forces qacc_warmstart implies -- an equality row's unconditionally, a limit row's where it pushes --, kept if their dual
+					// cost 0.5 f' AR f + f' b is not positive
 					if (tlh->nowarm == 0) {
-						sfor<NL>([&](auto R) {
-							constexpr int r = R;
+						sfor<NR>([&](auto R) {
+							constexpr int r = R, j = LM::jnt(r), j2 = LM::jnt2(r);
 							if (rwav[r]) {
-								const double w = lim_ld(IC<LM::ws(r)>{});
-								const double jar = rsg[r] * w - raref[r];
-								const double fw = jar < 0 ? -rD[r] * jar : 0.0;
+								double jw = rsg[r] * lim_ld(IC<LM::ws(LM::widx(j))>{});
+								if constexpr (j2 >= 0) jw += rc2[r < NE ? r : 0] * lim_ld(IC<LM::ws(LM::widx(j2 < 0 ? 0 : j2))>{});
+								const double jar = jw - raref[r];
+								double fw;
+								if constexpr (LM::is_eq(r)) fw = -rD[r] * jar;
+								else fw = jar < 0 ? -rD[r] * jar : 0.0;
 								rf[r] = ract[r] ? fw : 0.0;
 							}
 						});
 						double cost = 0;
-						sfor<NL>([&](auto I) {
+						sfor<NR>([&](auto I) {
 							constexpr int i = I;
 							if (rwav[i]) {
 								double sm = 0;
-								sfor<NL>([&](auto K) { sm += AR(I, K) * rf[K]; });
+								sfor<NR>([&](auto K) { sm += AR(I, K) * rf[K]; });
 								cost += 0.5 * rf[i] * sm + rf[i] * rb[i];
 							}
 						});
 						const bool drop = cost > 0;
-						sfor<NL>([&](auto R) { rf[R] = drop ? 0.0 : rf[R]; });
+						sfor<NR>([&](auto R) { rf[R] = drop ? 0.0 : rf[R]; });
 					}
 					// ---- mj_solPGS: sweeps over the rows until the lane's improvement falls under the tolerance or its sweeps run out; a lane that is done keeps
-					// its forces, the loop runs while a lane is not
+					// its forces, the loop runs while a lane is not.  A limit row's force is clamped at zero, an equality row's is not
 					const double scale = tlh->scale, tol = tlh->tolerance;
 					const int itmax = (int)tlh->iterations;
 					bool done = !has || itmax <= 0;
 					int iter = 0;
 					while (__builtin_amdgcn_ballot_w64(!done)) {
 						double improvement = 0;
-						sfor<NL>([&](auto I) {
+						sfor<NR>([&](auto I) {
 							constexpr int i = I;
 							// (a row is swept while a lane that has it is still sweeping: the loop's long tail is a few lanes' rows, not the wavefront's)
 							if (__builtin_amdgcn_ballot_w64(ract[i] && !done)) {
-								double arow[NL];
-								sfor<NL>([&](auto K) { arow[K] = lim_ld(IC<LM::ar(I, K)>{}); });
-								touch_vn<NL>(arow);  // (the row's reads, issued together)
+								double arow[NR];
+								sfor<NR>([&](auto K) { arow[K] = lim_ld(IC<LM::ar(I, K)>{}); });
+								touch_vn<NR>(arow);  // (the row's reads, issued together)
 								double res = rb[i];
-								sfor<NL>([&](auto K) { res += (rwav[K] ? arow[K] : 0.0) * rf[K]; });
+								sfor<NR>([&](auto K) { res += (rwav[K] ? arow[K] : 0.0) * rf[K]; });
 								const double aii = arow[i];
 								const double old = rf[i];
 								const double f1 = old - res * rinv[i];
-								const double f2 = f1 < 0 ? 0.0 : f1;
+								double f2 = f1;
+								if constexpr (!LM::is_eq(i)) f2 = f1 < 0 ? 0.0 : f1;
 								const double delta = f2 - old;
 								const double change = 0.5 * delta * delta * aii + delta * res;
 								const bool revert = change > 1e-10;
@@ -2218,11 +2350,17 @@ DEVI void lane_env_body(const KernelParams MJB_AS4 *__restrict__ P, const int ns
 					// ---- qfrc_constraint = J' f;  qacc = qacc_smooth + M^-1 qfrc_constraint;  Euler's acceleration + (M + h B)^-1 qfrc_constraint
 					double x2[NV], y2[NV];
 					sfor<NV>([&](auto I) { x2[I] = 0; y2[I] = 0; });
-					sfor<NL>([&](auto R) {
-						constexpr int r = R, j = LM::jnt(r);
-						qfc[r] = rsg[r] * rf[r];
-						x2[j] = qfc[r];
-						y2[j] = qfc[r];
+					sfor<NW>([&](auto W) {
+						constexpr int d = LM::wdof(W);
+						double sacc = 0;
+						sfor<NR>([&](auto R) {
+							constexpr int r = R;
+							if constexpr (LM::jnt(r) == d) sacc += rsg[r] * rf[r];
+							else if constexpr (LM::jnt2(r) == d) sacc += rc2[r < NE ? r : 0] * rf[r];
+						});
+						qfc[W] = sacc;
+						x2[d] = sacc;
+						y2[d] = sacc;
 					});
 					sfor<NV>([&](auto Ii) {
 						constexpr int i = NV - 1 - Ii;
@@ -2454,7 +2592,7 @@ DEVI void lane_env_body(const KernelParams MJB_AS4 *__restrict__ P, const int ns
 			});
 			sfor<NU>([&](auto I) { cn[I] = bada ? 0.0 : cn[I]; });
 			if constexpr (NA > 0) sfor<NA>([&](auto I) { act[I] = bada ? 0.0 : act[I]; });
-			if constexpr (NL > 0) sfor<NL>([&](auto R) { const double w = pinv(lim_ld(IC<LM::ws(R)>{})); lim_st(IC<LM::ws(R)>{}, bada ? 0.0 : w); });  // (the retry's warmstart is mj_resetData's)
+			if constexpr (NR > 0) sfor<NW>([&](auto W) { const double w = pinv(lim_ld(IC<LM::ws(W)>{})); lim_st(IC<LM::ws(W)>{}, bada ? 0.0 : w); });  // (the retry's warmstart is mj_resetData's)
 			time = bada ? 0.0 : time;
 			wasreset = wasreset || bada;
 			if constexpr (HW) hw_bad = bada;
@@ -2489,14 +2627,14 @@ DEVI void lane_env_body(const KernelParams MJB_AS4 *__restrict__ P, const int ns
 				if constexpr (EPOS) s.energy[2 * ev] = en_pe;
 				s.energy[2 * ev + 1] = en_ke;
 			}
-			if constexpr (NL > 0) {  // what the launch leaves of its last constraint stage (efc_* are not written): qfrc_constraint | nefc | solver_iter
+			if constexpr (NR > 0) {  // what the launch leaves of its last constraint stage (efc_* are not written): qfrc_constraint | nefc | solver_iter
 				double *const co = Pq->le_con;
 				if (co) {
 					double *const o = co + ev * (size_t)(NV + 2);
 					sfor<NV>([&](auto I) {
 						constexpr int j = I;
 						double v = 0;
-						if constexpr (LeLim<T>::on(j)) sfor<NL>([&](auto R) { if constexpr (LM::jnt(R) == j) v = qfc[R]; });
+						if constexpr (LM::in_rows(j)) v = qfc[LM::widx(j)];
 						o[j] = v;
 					});
 					o[NV] = (double)c_nefc;
@@ -2529,7 +2667,7 @@ DEVI void lane_env_body(const KernelParams MJB_AS4 *__restrict__ P, const int ns
 			badv_next |= bad_val(s2.b);
 		});
 		if constexpr (NA > 0) sfor<NA>([&](auto I) { act[I] = actn[I]; });
-		if constexpr (NL > 0) sfor<NL>([&](auto R) { lim_st(IC<LM::ws(R)>{}, qacc[LM::jnt(R)]); });  // mj_advance: qacc_warmstart = qacc
+		if constexpr (NR > 0) sfor<NW>([&](auto W) { lim_st(IC<LM::ws(W)>{}, qacc[LM::wdof(W)]); });  // mj_advance: qacc_warmstart = qacc
 		time += dt;
 		if constexpr (DUO && DP) {
 			lp[64 * MAIL] = Pair{ (double)((badp_next ? 2 : 0) | (badv_next ? 1 : 0)), 0.0 };

@@ -78,6 +78,13 @@ class CompiledModel:
         """The lane = env kernel's constant tape of the model (mjb_model_lane_env_tape), or None when the model is not eligible."""
         return self._lane_env_doubles(self.lib.mjb_model_lane_env_tape)
 
+    def lane_env_rows(self):
+        """(total, joint-equality rows, joint-limit rows) of the lane = env kernel's constraint stage for this model (mjb_lane_env_rows); (0, 0, 0): the
+        model has no such stage."""
+        ne, nl = C.c_int(0), C.c_int(0)
+        total = int(self.lib.mjb_lane_env_rows(self.ptr, C.byref(ne), C.byref(nl)))
+        return total, ne.value, nl.value
+
     def lane_env_overlay(self):
         """One env's column of the per-env table of Batch.set_lane_env(2), with the model's own values (mjb_model_lane_env_overlay); None: not eligible."""
         return self._lane_env_doubles(self.lib.mjb_model_lane_env_overlay)
@@ -365,7 +372,10 @@ class Batch:
         A hinge / slide tree whose only constraint rows are joint limits under PGS is eligible too (no contacts, equalities, tendons or frictionloss): in
         modes 1 and 2 its launches run the kernel's one-wavefront form with the constraint stage (joint-limit rows, PGS with warmstart) inside, and
         get("qfrc_constraint") / get("nefc") / get("solver_iter") read the last step's values afterwards; the automatic mode keeps the generic kernels for
-        such a model, and so does a batch with per-env overrides, a hwsim stage or a written xfrc_applied."""
+        such a model, and so does a batch with per-env overrides, a hwsim stage or a written xfrc_applied.
+        The same holds for a model with fixed tendons that only carry actuators (actuators with a tendon transmission) and with joint equalities, whose
+        rows join the limit rows under PGS at exact njmax (CompiledModel.lane_env_rows()); per-env equality parameters (set_env_equality) keep the
+        generic kernels."""
         _check(self.lib.mjb_set_lane_env(self.ptr, int(mode)), "mjb_set_lane_env")
 
     def set_lane_env_hwsim(self, on=True):

@@ -33,42 +33,89 @@ EXTRA_SENSORS = (FRAME_SENSORS - {23, 24}) | SITE_SENSORS
 SUPPORTED_SENSORS = SMOOTH_SENSORS | EXTRA_SENSORS
 
 
+DSBL_EQUALITY, DSBL_LIMIT = 1 << 1, 1 << 3  # mjDSBL_*
+LE_MAX_SLOTS = 160                           # a CU's LDS in 1 KB pair slots (csrc/mjb_lane_env_kernel.h)
+
+
+def limited_joints(m):
+    """The joint-limit rows of an eligible model with constraint rows (mjb_lane_env_limits): 0 / 1 per joint -- none under mjDSBL_LIMIT."""
+    on = m["nefcmax"] > 0 and not (int(m["disableflags"]) & DSBL_LIMIT)
+    return [int(on and m["jnt_limited"][j] != 0) for j in range(m["njnt"])]
+
+
+def equality_rows(m):
+    """The joint-equality rows of such a model (mjb_lane_env_eq_rows): (joint1, joint2 or -1) of every ACTIVE equality, in equality order -- none under
+    mjDSBL_EQUALITY."""
+    if m["nefcmax"] <= 0 or (int(m["disableflags"]) & DSBL_EQUALITY):
+        return []
+    return [(int(m["eq_obj1id"][e]), int(m["eq_obj2id"][e]) if int(m["eq_obj2id"][e]) >= 0 else -1) for e in range(m["neq"]) if m["eq_active"][e]]
+
+
 def limit_rows(m):
-    """None if every constraint row the model can ever have is a joint-limit row the lane = env kernel sweeps with PGS (le_limit_rows, csrc/mjb_lane_env.hip),
-    else the reason."""
+    """None if every constraint row the model can ever have is a joint-equality or joint-limit row the lane = env kernel sweeps with PGS (le_limit_rows,
+    csrc/mjb_lane_env.hip), else the reason."""
     if int(m["solver"]) != 0:
         return "constraint rows under a solver other than PGS"
     if any(float(v) > 0 for v in m["dof_frictionloss"][:m["nv"]]):
         return "constraint rows: dry friction"
-    nl = 0
-    for j in range(m["njnt"]):
-        if m["jnt_limited"][j]:
-            r = m["jnt_range"][j]
-            if not (float(r[1]) - float(r[0]) > 2 * float(m["jnt_margin"][j])):
-                return "constraint rows: a range no wider than twice its margin"
-            nl += 1
-    if nl == 0 or m["nefcmax"] != nl:
-        return "constraint rows: other than one per limited joint"
+    if not (int(m["disableflags"]) & DSBL_LIMIT):
+        for j in range(m["njnt"]):
+            if m["jnt_limited"][j]:
+                r = m["jnt_range"][j]
+                if not (float(r[1]) - float(r[0]) > 2 * float(m["jnt_margin"][j])):
+                    return "constraint rows: a range no wider than twice its margin"
+    nr = sum(limited_joints(m)) + len(equality_rows(m))
+    if nr == 0 or m["nefcmax"] != nr:
+        return "constraint rows: other than one per active joint equality and one per limited joint"
     return None
 
 
-def limited_joints(m):
-    """The joint-limit rows of an eligible model with constraint rows (mjb_lane_env_limits): 0 / 1 per joint."""
-    return [int(m["nefcmax"] > 0 and m["jnt_limited"][j] != 0) for j in range(m["njnt"])]
+def tendons_equalities(m):
+    """None if the model's tendons are fixed tendons that only carry actuators and its equalities are joint equalities (le_bare_tendons,
+    le_joint_equalities), else the reason."""
+    for t in range(m["ntendon"]):
+        if m["tendon_limited"][t] or float(m["tendon_frictionloss"][t]) != 0 or float(m["tendon_stiffness"][t]) != 0 or float(m["tendon_damping"][t]) != 0:
+            return "a tendon with a limit, dry friction, a spring or a damper"
+    for e in range(m["neq"]):
+        j1, j2 = int(m["eq_obj1id"][e]), int(m["eq_obj2id"][e])
+        if int(m["eq_type"][e]) != 2 or not (0 <= j1 < m["njnt"]) or j2 >= m["njnt"] or j2 == j1:
+            return "an equality other than a joint equality"
+    return None
+
+
+def row_lds_slots(m):
+    """Pair slots of the state, the body forces, the packed AR and the rows' qacc_warmstart (le_state_slots): what the smallest build must hold."""
+    moving = set()
+    for b in range(1, m["nbody"]):
+        a, jointed = b, False
+        while a > 0:
+            jointed = jointed or m["body_jntnum"][a] > 0
+            a = int(m["body_parentid"][a])
+        if jointed:
+            moving.add(b)
+    rows = equality_rows(m)
+    lim = limited_joints(m)
+    nr = len(rows) + sum(lim)
+    dofs = {j for j in range(m["njnt"]) if lim[j]} | {j for pair in rows for j in pair if j >= 0}
+    return m["nv"] + 3 * len(moving) + (nr * (nr + 1) // 2 + len(dofs) + 1) // 2
 
 
 def eligible(m):
     """None if the model fits the lane = env kernel, else the reason."""
     if m["nconmax"] > 0:
         return "constraint rows"
-    if m["nefcmax"] > 0 and limit_rows(m):
-        return limit_rows(m)
     if m["integrator"] != 0:
         return "integrator"
-    if m["nmocap"] or m["ntendon"] or m["neq"]:
-        return "mocap / tendon / equality"
+    if m["nmocap"]:
+        return "mocap"
+    if (m["ntendon"] or m["neq"]) and tendons_equalities(m):
+        return tendons_equalities(m)
+    if m["nefcmax"] > 0 and limit_rows(m):
+        return limit_rows(m)
     if m["nq"] != m["nv"] or m["njnt"] != m["nv"]:
         return "a joint with more than one dof"
+    if m["nv"] < 1 or m["nbody"] > 24 or m["nv"] > 20:
+        return "size"
     for j in range(m["njnt"]):
         if m["jnt_type"][j] not in (2, 3) or m["jnt_qposadr"][j] != j or m["jnt_dofadr"][j] != j:
             return "joint kind / addressing"
@@ -83,10 +130,12 @@ def eligible(m):
         if int(m["sensor_type"][i]) in SITE_SENSORS and int(m["sensor_objtype"][i]) != 6:
             return "site sensor on another object"
     for i in range(m["nu"]):
-        if m["actuator_trntype"][i] != 0 or int(m["actuator_dyntype"][i]) not in (0, 1, 2):  # none, integrator, filter
+        if int(m["actuator_trntype"][i]) not in (0, 3) or int(m["actuator_dyntype"][i]) not in (0, 1, 2):  # joint / fixed tendon; none, integrator, filter
             return "actuator transmission / dynamics"
     if sum(int(d) != 0 for d in m["actuator_dyntype"]) != m["na"]:
         return "activation states without an actuator of their own"
+    if m["nefcmax"] > 0 and row_lds_slots(m) > LE_MAX_SLOTS:
+        return "constraint rows: the packed AR needs more than 160 KB of LDS per wavefront"
     return None
 
 
@@ -103,6 +152,8 @@ def emit(name, m):
         raise SystemExit("%s does not fit the lane = env kernel: %s" % (name, why))
     if m["nefcmax"] > 0:
         raise SystemExit("%s has joint limits: mjb_lane_env_match takes no such model for a compiled-in topology" % name)
+    if m["ntendon"] or m["neq"]:
+        raise SystemExit("%s has tendons or equalities: mjb_lane_env_match takes no such model for a compiled-in topology" % name)
     if "body_gravcomp" in m and any(m["body_gravcomp"][1:] != 0):  # (a hand-built dict from before the field has none)
         raise SystemExit("%s has gravity compensation: mjb_lane_env_match takes no such model for a compiled-in topology" % name)
     if any(int(t) in EXTRA_SENSORS for t in m["sensor_type"][:m["nsensor"]]):
@@ -120,6 +171,13 @@ def rt_struct(m):
     text = struct_text("rt", m, gc).replace('\tstatic constexpr const char *name = "rt";\n', "")
     if m["nefcmax"] > 0:  # (the rows of the constraint stage, LeLim: a model without them has no such line)
         text = text[:text.rindex("};\n")] + arr("jnt_limited", limited_joints(m)) + "};\n"
+    if m["ntendon"] > 0:  # (fixed tendons, LeTen: which actuators drive one, and every tendon's wraps)
+        ten = [int(m["actuator_trnid"][i][0]) if int(m["actuator_trntype"][i]) == 3 else -1 for i in range(m["nu"])]
+        text = (text[:text.rindex("};\n")] + arr("act_trntype", m["actuator_trntype"]) + arr("act_tendon", ten) + arr("tendon_adr", m["tendon_adr"]) +
+                arr("tendon_num", m["tendon_num"]) + arr("wrap_jnt", m["wrap_objid"]) + "};\n")
+    rows = equality_rows(m)
+    if rows:  # (the equality rows, LeEq: the joint pairs of the active joint equalities)
+        text = text[:text.rindex("};\n")] + arr("eq_jnt1", [r[0] for r in rows]) + arr("eq_jnt2", [r[1] for r in rows]) + "};\n"
     return text
 
 
