@@ -417,7 +417,7 @@ int mjb_model_lane_env(const mjb_model *m);
  * the kernel reads them, without a batch or a device.  Both return the
  * number of doubles and fill `out` when it is not NULL and `cap` is large enough; -1: the model is not eligible.
  * mjb_model_lane_env_tape: the constant tape -- dt gravity[3] pad[4] | per body, 32 doubles: pos[3] quat[4] jaxis[3] jpos[3] qpos0 stiffness spring
- * ipos[3] ibody[6] mass damping armature hdamping pad[3] | per actuator, 16: gear ctrlrange[2] gain[3] bias[3] forcerange[2] dyntau actrange[2] pad[2]; ibody =
+ * ipos[3] ibody[6] mass damping armature hdamping gravcomp pad[2] | per actuator, 16: gear ctrlrange[2] gain[3] bias[3] forcerange[2] dyntau actrange[2] pad[2]; ibody =
  * R(iquat) diag(inertia) R(iquat)' as xx yy zz xy xz yz, hdamping = timestep * damping, dyntau = max(mjMINVAL, dynprm[0]) of a filter actuator -- the
  * time constant itself, which act_dot divides by, not its reciprocal -- and 0 for every other; dyntau and actrange are 0 for a stateless actuator.
  * A model with joint-limit rows has, BEHIND those records (their offsets stay), 8 doubles: meaninertia tolerance iterations 1/(meaninertia max(1, nv))

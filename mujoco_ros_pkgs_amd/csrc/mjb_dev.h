@@ -97,8 +97,19 @@ struct LeTapeBody {
 	// pose half: what mj_kinematics needs of the body and its (single) joint
 	double pos[3], quat[4], jaxis[3], jpos[3], qpos0, stiffness, spring;
 	// inertial half
-	double ipos[3], ibody[6] /* R(iquat) diag(inertia) R(iquat)': xx yy zz xy xz yz */, mass, damping, armature, hdamping /* timestep * damping */, pad[3];
+	double ipos[3], ibody[6] /* R(iquat) diag(inertia) R(iquat)': xx yy zz xy xz yz */, mass, damping, armature, hdamping /* timestep * damping */, gravcomp /* mjModel.body_gravcomp */, pad[2];
 };
+// The record as the kernels fetch it, 16 doubles a half: LE_<FIELD> is the field's index in the whole record, LE_I_<FIELD> its index in the inertial half
+#define LE_OFS(f) ((int)(__builtin_offsetof(LeTapeBody, f) / sizeof(double)))  /* (offsetof without <cstddef>: hiprtc compiles this header too) */
+enum {
+	LE_POS = LE_OFS(pos), LE_QUAT = LE_OFS(quat), LE_JAXIS = LE_OFS(jaxis), LE_JPOS = LE_OFS(jpos), LE_QPOS0 = LE_OFS(qpos0), LE_STIFFNESS = LE_OFS(stiffness), LE_SPRING = LE_OFS(spring),
+	LE_HALF = 16,
+	LE_IPOS = LE_OFS(ipos), LE_IBODY = LE_OFS(ibody), LE_MASS = LE_OFS(mass), LE_DAMPING = LE_OFS(damping), LE_ARMATURE = LE_OFS(armature), LE_HDAMPING = LE_OFS(hdamping), LE_GRAVCOMP = LE_OFS(gravcomp),
+	LE_I_IPOS = LE_IPOS - LE_HALF, LE_I_IBODY = LE_IBODY - LE_HALF, LE_I_MASS = LE_MASS - LE_HALF,
+	LE_A_N = LE_QPOS0 + 1, LE_I_N = LE_I_MASS + 1,  // what the sweep fetches of either half: up to qpos0 | up to mass
+};
+#undef LE_OFS
+static_assert(LE_POS == 0 && LE_SPRING == LE_HALF - 1 && LE_IPOS == LE_HALF && LE_GRAVCOMP == 29 && sizeof(LeTapeBody) == 2 * LE_HALF * sizeof(double), "lane = env body record: the pose half is doubles 0 - 15, the inertial half 16 - 31");
 // (dyntau: a filter actuator's max(mjMINVAL, dynprm[0]) -- the divisor of act_dot, not its reciprocal; actlo / acthi: actrange.  Zero for a stateless actuator)
 struct LeTapeAct { double gear, ctrllo, ctrlhi, gain[3], bias[3], forcelo, forcehi, dyntau, actlo, acthi, pad[2]; };
 static_assert(sizeof(LeTapeHdr) == 64 && sizeof(LeTapeBody) == 256 && sizeof(LeTapeAct) == 128, "lane = env tape records");

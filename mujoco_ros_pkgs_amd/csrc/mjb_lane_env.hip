@@ -768,7 +768,7 @@ void mjb_lane_env_tape(const mjb_model_desc *h, double *tape)
 		for (int k = 0; k < 4; k++) t.quat[k] = h->body_quat[4 * b + k];
 		le_ibody(h->body_iquat + 4 * b, h->body_inertia + 3 * b, t.ibody);
 		t.mass = h->body_mass[b];
-		t.pad[0] = h->body_gravcomp[b];  // (gravity compensation: read where the topology flags the body, LeGc)
+		t.gravcomp = h->body_gravcomp[b];  // (gravity compensation: read where the topology flags the body, LeGc)
 		if (h->body_jntnum[b] == 1) {
 			const int j = h->body_jntadr[b];
 			for (int k = 0; k < 3; k++) { t.jaxis[k] = h->jnt_axis[3 * j + k]; t.jpos[k] = h->jnt_pos[3 * j + k]; }

@@ -1,6 +1,18 @@
 // mjb_lane_env_kernel.h -- device code of the lane = env kernel (see mjb_lane_env.hip for what it is): a template over the model's integer
 // structure `T` (a LeTopo_* struct: csrc/lane_env_topos.h, or the one mjb_lane_env.hip writes for hiprtc) and the LDS budget LP.
 // Included by mjb_lane_env.hip (the compiled-in topologies) and by the source hiprtc compiles for any other eligible model.
+//
+// One body of the root -> leaf sweep as helpers, each per-body quantity once for `consume`, the quartet's o_body / x_body / v_* and the rest-pose prologue:
+//   mj_kinematics   le_xipos (a frame's point in the world: a child's origin, xipos, an anchor), le_xquat, le_anchor, le_hinge_quat, le_pos_slide / _offcentre
+//   mj_comPos       le_inert_rot + le_cinert_com (cinert in two halves: the quartet's C fetches between them), le_cdof_hinge / le_cdof_slide
+//   mj_comVel, RNE  le_parent_motion (at rest | the parent's), le_body_motion<REST> (cvel, cacc), le_cfrc (cfrc_body's two summands)       (all: mjb_math.h)
+//   across LDS      le_pairs_put / _get (cinert: 5 pairs, cdof: 3, a quaternion: 2), le_cfrc_put, le_ring_put / le_ring_get<MATFIRST>, le_cdof_ring_get<SLIDE>
+// RULE: a helper holds arithmetic and LDS pair accesses only.  Every wait, pin and fetch (sched_barrier, touch_*, pinv / pins, LE_PK, le_barrier, loads of a
+// tape record, an overlay or a wrench value) stays at the call site, in its order relative to the arithmetic.  Record fields are read by name (LE_*, mjb_dev.h).
+// NOT on the helpers: the fused sweep (solo, two halves, the P of the pipelined duo and of the trio) and mjb_smooth_kernel.h keep the same expressions written
+// out.  Under -ffp-contract=fast the backend picks which product of a sum of two it fuses, and moving those two bodies behind the helpers flipped some picks:
+// same f64 opcode counts, results off by an ulp in a few envs (profiles/lane_env_body_math.txt).  Change a formula there AND in its helper.  `consume` also
+// writes its cfrc store out (le_cfrc_put is v_force's): behind the helper the pipelined duo of franka_like gained 15 register copies and lost 0.2 % of its rate.
 #pragma once
 #ifndef __HIPCC_RTC__  // (hiprtc brings its own runtime header)
 #include <hip/hip_runtime.h>
@@ -371,7 +383,7 @@ template <class T> struct XfSlots {
 };
 
 // Gravity compensation (mjModel.body_gravcomp): a topology may flag its compensated bodies, body_gc[NBODY] (the hiprtc-built ones do; a topology
-// without the array has none).  The coefficient itself is run-time data, LeTapeBody::pad[0].
+// without the array has none).  The coefficient itself is run-time data, LeTapeBody::gravcomp.
 template <class T, class = void> struct LeGc { static constexpr bool on(int) { return false; } };
 template <class T> struct LeGc<T, decltype((void)T::body_gc)> { static constexpr bool on(int b) { return T::body_gc[b] != 0; } };
 template <class T> constexpr bool le_any_gc() { for (int b = 1; b < T::NBODY; b++) if (LeGc<T>::on(b)) return true; return false; }
@@ -464,6 +476,47 @@ constexpr bool le_quartet(int role) { return role == LE_QUAD_O || role == LE_QUA
 // loads -- V's ctrl-noise normals and qfrc_applied are fetched a sweep ahead of their use precisely so that nobody waits for HBM)
 DEVI void le_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 template <int NV> struct DuoSlots { static constexpr int n = le_exchange_slots(NV); };  // qfrc_smooth pairs + the mail slot
+// ---- the per-body quantities that cross LDS, each layout once (slot: the lane's first pair slot of the quantity, pair k at slot[64 * k]); no wait, pin or fetch
+template <int N> DEVI void le_pairs_put(Pair *slot, const double *v) { for (int k = 0; k < N; k++) slot[64 * k] = Pair{ v[2 * k], v[2 * k + 1] }; }  // cinert: 5 | cdof: 3
+template <int N> DEVI void le_pairs_get(double *v, const Pair *slot)
+{
+	for (int k = 0; k < N; k++) {
+		const Pair c = slot[64 * k];
+		v[2 * k] = c.a;
+		v[2 * k + 1] = c.b;
+	}
+}
+DEVI void le_cfrc_put(Pair *slot, const double *cf, const double *t1)
+{
+	slot[0] = Pair{ cf[0] + t1[0], cf[1] + t1[1] };
+	slot[64] = Pair{ cf[2] + t1[2], cf[3] + t1[3] };
+	slot[128] = Pair{ cf[4] + t1[4], cf[5] + t1[5] };
+}
+// the pose ring, six pairs a body: its position relative to the tree root's origin, then its frame.  MATFIRST (the quartet's C): the reads in the
+// order of their first use -- the matrix rows, then the position --, so that its counted waits release the cinert chain first
+DEVI void le_ring_put(Pair *slot, const double *xp, const double *xm)
+{
+	slot[0] = Pair{ xp[0], xp[1] };
+	slot[64] = Pair{ xp[2], xm[0] };
+	slot[128] = Pair{ xm[1], xm[2] };
+	slot[192] = Pair{ xm[3], xm[4] };
+	slot[256] = Pair{ xm[5], xm[6] };
+	slot[320] = Pair{ xm[7], xm[8] };
+}
+template <bool MATFIRST> DEVI void le_ring_get(double *xp, double *xm, const Pair *slot)
+{
+	Pair a0, a1, a2, a3, a4, a5;
+	if constexpr (MATFIRST) { a1 = slot[64]; a2 = slot[128]; a3 = slot[192]; a4 = slot[256]; a5 = slot[320]; a0 = slot[0]; }
+	else { a0 = slot[0]; a1 = slot[64]; a2 = slot[128]; a3 = slot[192]; a4 = slot[256]; a5 = slot[320]; }
+	xp[0] = a0.a; xp[1] = a0.b; xp[2] = a1.a; xm[0] = a1.b; xm[1] = a2.a; xm[2] = a2.b; xm[3] = a3.a; xm[4] = a3.b; xm[5] = a4.a; xm[6] = a4.b; xm[7] = a5.a; xm[8] = a5.b;
+}
+// the quartet's cdof ring (C's le_pairs_put<3>): a slide's rotational half is zero whatever the slots hold
+template <bool SLIDE> DEVI void le_cdof_ring_get(double *cd, const Pair *slot)
+{
+	const Pair d0 = slot[0], d1 = slot[64], d2 = slot[128];
+	cd[0] = d0.a; cd[1] = d0.b; cd[2] = d1.a; cd[3] = d1.b; cd[4] = d2.a; cd[5] = d2.b;
+	if constexpr (SLIDE) cd[0] = cd[1] = cd[2] = 0;
+}
 // PE: the batch carries per-env overrides (mjb_set_lane_env mode 2): gravity, the joint constants, masses / inertias and the actuator gains come
 // per lane from DevState::le_overlay instead of the tape (solo form only).
 // HW: the batch has a device hwsim stage (KernelParams::hw, mjb_lane_env_set_hwsim): DefaultRobotHWSim::writeSim runs per lane where the forces are
@@ -608,30 +661,21 @@ DEVI void lane_env_body(const KernelParams MJB_AS4 *__restrict__ P, const int ns
 			constexpr int b = Bq;
 			if constexpr (b > 0 && !LD::needed(b)) {
 				constexpr int p = T::body_parentid[b];
-				const double MJB_AS4 *const A = reinterpret_cast<const double MJB_AS4 *>(tb0 + b);  // pos[3] quat[4] ... | ipos[3] ...
-				double quat[4] = { A[3], A[4], A[5], A[6] };
-				if constexpr (p != 0) {
-					double q[4];
-					qmul(q, rxq[p], quat);
-					for (int k = 0; k < 4; k++) quat[k] = q[k];
-				}
+				const double MJB_AS4 *const A = reinterpret_cast<const double MJB_AS4 *>(tb0 + b);
+				double quat[4] = { A[LE_QUAT], A[LE_QUAT + 1], A[LE_QUAT + 2], A[LE_QUAT + 3] };
+				if constexpr (p != 0) le_xquat(quat, rxq[p]);
 				normalize4_sel(quat);
 				for (int k = 0; k < 4; k++) rxq[b][k] = quat[k];
 				if constexpr (RESTX) {
-					double pos[3] = { A[0], A[1], A[2] };
-					if constexpr (p != 0) {
-						double v[3];
-						matvec3(v, rxm[p], pos);
-						for (int k = 0; k < 3; k++) pos[k] = v[k] + rxp[p][k];
-					}
+					double pos[3] = { A[LE_POS], A[LE_POS + 1], A[LE_POS + 2] };
+					if constexpr (p != 0) le_xipos(pos, rxm[p], rxp[p], pos);
 					quat2mat_nocheck(rxm[b], quat);
 					for (int k = 0; k < 3; k++) rxp[b][k] = pos[k];
 					if constexpr (T::body_sameframe[b]) {
 						for (int k = 0; k < 3; k++) rxi[b][k] = rxp[b][k];
 					} else {
-						double ip[3] = { A[16], A[17], A[18] }, v[3];
-						matvec3(v, rxm[b], ip);
-						for (int k = 0; k < 3; k++) rxi[b][k] = v[k] + rxp[b][k];
+						const double ip[3] = { A[LE_IPOS], A[LE_IPOS + 1], A[LE_IPOS + 2] };
+						le_xipos(rxi[b], rxm[b], rxp[b], ip);
 					}
 				}
 			}
@@ -796,30 +840,31 @@ DEVI void lane_env_body(const KernelParams MJB_AS4 *__restrict__ P, const int ns
 			double hA[NB + 1][16], hB[NB][16];
 			[[maybe_unused]] double vB[PE ? NB : 1][7];  // (PE) the env's mass | ibody[6] of a body, fetched with the body's inertial half record
 			[[maybe_unused]] double xw[XF ? NB : 1][6];  // (XF) the env's wrench on a moving body, fetched with the body's inertial half record
-			// (the quartet's C) what C reads of a needed body's record -- ipos[3] ibody[6] mass | jaxis[3] | jpos[3] --, fetched one phase ahead as O and X
+			// (the quartet's C) what C reads of a needed body's record -- the inertial half up to the mass, as it stands (LE_I_*) | jaxis[3] | jpos[3] --, fetched one phase ahead as O and X
 			// fetch theirs: with no scalar load in flight while C works off the pose ring, its waits for the ring's reads are counted ones
 			[[maybe_unused]] double hC[ROLE == LE_QUAD_C ? NB + 1 : 1][16];
+			constexpr int HC_JAXIS = LE_I_N, HC_JPOS = HC_JAXIS + 3;
 			[[maybe_unused]] auto c_fetch = [&](auto Bn) {
 				constexpr int nb = Bn, jn = T::body_jnt[nb];
 				const double MJB_AS4 *const rec = reinterpret_cast<const double MJB_AS4 *>(tb + nb);
-				for (int k = 0; k < 10; k++) hC[nb][k] = rec[16 + k];
+				for (int k = 0; k < LE_I_N; k++) hC[nb][k] = rec[LE_HALF + k];
 				if constexpr (jn >= 0) {
-					for (int k = 0; k < 3; k++) hC[nb][10 + k] = rec[7 + k];
-					if constexpr (T::jnt_type[jn < 0 ? 0 : jn] != MJB_JNT_SLIDE && (!LeOffc<T>::known || LeOffc<T>::on(jn < 0 ? 0 : jn))) for (int k = 0; k < 3; k++) hC[nb][13 + k] = rec[10 + k];
+					for (int k = 0; k < 3; k++) hC[nb][HC_JAXIS + k] = rec[LE_JAXIS + k];
+					if constexpr (T::jnt_type[jn < 0 ? 0 : jn] != MJB_JNT_SLIDE && (!LeOffc<T>::known || LeOffc<T>::on(jn < 0 ? 0 : jn))) for (int k = 0; k < 3; k++) hC[nb][HC_JPOS + k] = rec[LE_JPOS + k];
 				}
 			};
 			// ... pinned at the end of the region that issued the loads (the entries C reads, no others: see touch_rec)
 			[[maybe_unused]] auto c_touch = [&](auto Bn) {
 				constexpr int nb = Bn, jn = T::body_jnt[nb];
 				const double *const h = hC[nb];
-				asm volatile("" ::"s"(h[3]), "s"(h[4]), "s"(h[5]), "s"(h[6]), "s"(h[7]), "s"(h[8]), "s"(h[9]));
-				if constexpr (!T::body_sameframe[nb]) asm volatile("" ::"s"(h[0]), "s"(h[1]), "s"(h[2]));
+				asm volatile("" ::"s"(h[LE_I_IBODY]), "s"(h[LE_I_IBODY + 1]), "s"(h[LE_I_IBODY + 2]), "s"(h[LE_I_IBODY + 3]), "s"(h[LE_I_IBODY + 4]), "s"(h[LE_I_IBODY + 5]), "s"(h[LE_I_MASS]));
+				if constexpr (!T::body_sameframe[nb]) asm volatile("" ::"s"(h[LE_I_IPOS]), "s"(h[LE_I_IPOS + 1]), "s"(h[LE_I_IPOS + 2]));
 				if constexpr (jn >= 0) {
-					asm volatile("" ::"s"(h[10]), "s"(h[11]), "s"(h[12]));
-					if constexpr (T::jnt_type[jn < 0 ? 0 : jn] != MJB_JNT_SLIDE && (!LeOffc<T>::known || LeOffc<T>::on(jn < 0 ? 0 : jn))) asm volatile("" ::"s"(h[13]), "s"(h[14]), "s"(h[15]));
+					asm volatile("" ::"s"(h[HC_JAXIS]), "s"(h[HC_JAXIS + 1]), "s"(h[HC_JAXIS + 2]));
+					if constexpr (T::jnt_type[jn < 0 ? 0 : jn] != MJB_JNT_SLIDE && (!LeOffc<T>::known || LeOffc<T>::on(jn < 0 ? 0 : jn))) asm volatile("" ::"s"(h[HC_JPOS]), "s"(h[HC_JPOS + 1]), "s"(h[HC_JPOS + 2]));
 				}
 			};
-			for (int k = 0; k < 14; k++) hA[1][k] = reinterpret_cast<const double MJB_AS4 *>(tb + 1)[k];
+			for (int k = 0; k < LE_A_N; k++) hA[1][k] = reinterpret_cast<const double MJB_AS4 *>(tb + 1)[k];
 			// ... and the (qpos, qvel) pair of the next jointed body: LDS reads and scalar loads share one counter, so a read issued where
 			// it is needed would wait for the record fetched beside it
 			double qfa[NV > 0 ? NV : 1];  // qfrc_applied: fetched in the sweep's last region, read by the force block behind it
@@ -952,46 +997,31 @@ DEVI void lane_env_body(const KernelParams MJB_AS4 *__restrict__ P, const int ns
 				static_assert(ROLE != LE_QUAD_V || b < 0, "the quartet's V takes a body in pieces: v_fetch, v_kin, v_force");
 				[[maybe_unused]] double xp[3], xm[9];
 				double ci[10];
-				if constexpr (ROLE == LE_QUAD_C) {  // (the quartet's C: the ring's six reads in the order of their first use -- the matrix rows, then the position)
-					const Pair a1 = lp[64 * (rg + 1)], a2 = lp[64 * (rg + 2)], a3 = lp[64 * (rg + 3)], a4 = lp[64 * (rg + 4)], a5 = lp[64 * (rg + 5)], a0 = lp[64 * rg];
-					xp[0] = a0.a; xp[1] = a0.b; xp[2] = a1.a; xm[0] = a1.b; xm[1] = a2.a; xm[2] = a2.b; xm[3] = a3.a; xm[4] = a3.b; xm[5] = a4.a; xm[6] = a4.b; xm[7] = a5.a; xm[8] = a5.b;
-				} else {
-					const Pair a0 = lp[64 * rg], a1 = lp[64 * (rg + 1)], a2 = lp[64 * (rg + 2)], a3 = lp[64 * (rg + 3)], a4 = lp[64 * (rg + 4)], a5 = lp[64 * (rg + 5)];
-					xp[0] = a0.a; xp[1] = a0.b; xp[2] = a1.a; xm[0] = a1.b; xm[1] = a2.a; xm[2] = a2.b; xm[3] = a3.a; xm[4] = a3.b; xm[5] = a4.a; xm[6] = a4.b; xm[7] = a5.a; xm[8] = a5.b;
-				}
+				le_ring_get<ROLE == LE_QUAD_C>(xp, xm, lp + 64 * rg);
 				if constexpr ((ROLE == LE_PIPE_V && b == LASTB) || VLDS) {
 					// the LAST needed body's cinert came with its pose: P computes that one itself and goes from its last pose straight into the
 					// composite-inertia sweep, which starts at this body -- it never waits for V's last phase
-					for (int k = 0; k < 5; k++) {
-						const Pair c = lp[64 * (c0 + k)];
-						ci[2 * k] = c.a;
-						ci[2 * k + 1] = c.b;
-					}
+					le_pairs_get<5>(ci, lp + 64 * c0);
 				} else
 				{
-					// cinert about the tree root's origin, as in the fused sweep: X Ib X' + the com offset's terms; handed to P's composite-inertia sweep
+					// cinert about the tree root's origin; handed to P's composite-inertia sweep
 					const LeTapeBody MJB_AS4 &tj = tb[b];
 					constexpr bool CREC = ROLE == LE_QUAD_C;  // (the quartet's C: the record is in hC[b], fetched a phase ago)
 					[[maybe_unused]] const double *const hc = hC[CREC ? b : 0];
 					double dif[3] = { xp[0], xp[1], xp[2] };
 					if constexpr (!T::body_sameframe[b]) {
 						double ip[3];
-						if constexpr (CREC) { ip[0] = hc[0]; ip[1] = hc[1]; ip[2] = hc[2]; }
+						if constexpr (CREC) { ip[0] = hc[LE_I_IPOS]; ip[1] = hc[LE_I_IPOS + 1]; ip[2] = hc[LE_I_IPOS + 2]; }
 						else { ip[0] = tj.ipos[0]; ip[1] = tj.ipos[1]; ip[2] = tj.ipos[2]; }
 						double v[3];
 						matvec3(v, xm, ip);
 						for (int k = 0; k < 3; k++) dif[k] += v[k];
 					}
-					double mass, ixx, iyy, izz, ixy, ixz, iyz;
-					if constexpr (CREC) { mass = hc[9]; ixx = hc[3]; iyy = hc[4]; izz = hc[5]; ixy = hc[6]; ixz = hc[7]; iyz = hc[8]; }
-					else { mass = tj.mass; ixx = tj.ibody[0]; iyy = tj.ibody[1]; izz = tj.ibody[2]; ixy = tj.ibody[3]; ixz = tj.ibody[4]; iyz = tj.ibody[5]; }
-					const double *X = xm;
+					double mass, ib[6];
+					if constexpr (CREC) { mass = hc[LE_I_MASS]; for (int k = 0; k < 6; k++) ib[k] = hc[LE_I_IBODY + k]; }
+					else { mass = tj.mass; for (int k = 0; k < 6; k++) ib[k] = tj.ibody[k]; }
 					double Tm[9];
-					for (int rr = 0; rr < 3; rr++) {
-						Tm[3 * rr + 0] = X[3 * rr] * ixx + X[3 * rr + 1] * ixy + X[3 * rr + 2] * ixz;
-						Tm[3 * rr + 1] = X[3 * rr] * ixy + X[3 * rr + 1] * iyy + X[3 * rr + 2] * iyz;
-						Tm[3 * rr + 2] = X[3 * rr] * ixz + X[3 * rr + 1] * iyz + X[3 * rr + 2] * izz;
-					}
+					le_inert_rot(Tm, xm, ib[0], ib[1], ib[2], ib[3], ib[4], ib[5]);
 					if constexpr (CREC) {
 						// (every read of the ring has landed: the next needed body's record is fetched from here on, under the rest of cinert and the cdof
 						//  half -- the compiler may not lift its loads into the counted waits above)
@@ -1003,27 +1033,14 @@ DEVI void lane_env_body(const KernelParams MJB_AS4 *__restrict__ P, const int ns
 						__builtin_amdgcn_sched_barrier(0);
 						if constexpr (nx < NB) c_fetch(IC<nx>{});
 					}
-					ci[0] = Tm[0] * X[0] + Tm[1] * X[1] + Tm[2] * X[2] + mass * (dif[1] * dif[1] + dif[2] * dif[2]);
-					ci[1] = Tm[3] * X[3] + Tm[4] * X[4] + Tm[5] * X[5] + mass * (dif[0] * dif[0] + dif[2] * dif[2]);
-					ci[2] = Tm[6] * X[6] + Tm[7] * X[7] + Tm[8] * X[8] + mass * (dif[0] * dif[0] + dif[1] * dif[1]);
-					ci[3] = Tm[0] * X[3] + Tm[1] * X[4] + Tm[2] * X[5] - mass * dif[0] * dif[1];
-					ci[4] = Tm[0] * X[6] + Tm[1] * X[7] + Tm[2] * X[8] - mass * dif[0] * dif[2];
-					ci[5] = Tm[3] * X[6] + Tm[4] * X[7] + Tm[5] * X[8] - mass * dif[1] * dif[2];
-					ci[6] = mass * dif[0];
-					ci[7] = mass * dif[1];
-					ci[8] = mass * dif[2];
-					ci[9] = mass;
-					if constexpr (OWNCIN) for (int k = 0; k < 5; k++) lp[64 * (c0 + k)] = Pair{ ci[2 * k], ci[2 * k + 1] };  // (for the composite-inertia sweep of P / of C itself)
+					le_cinert_com(ci, Tm, xm, mass, dif);
+					if constexpr (OWNCIN) le_pairs_put<5>(lp + 64 * c0, ci);  // (for the composite-inertia sweep of P / of C itself)
 				}
+				constexpr bool prest = p == 0 || !LD::needed(p);  // the world, or a jointless chain down from it: at rest
 				[[maybe_unused]] double pv[6], pa[6];
 				if constexpr (!DV) {
-				} else if constexpr (p == 0 || !LD::needed(p)) {  // the world, or a jointless chain down from it: at rest
-					for (int k = 0; k < 6; k++) pv[k] = 0;
-					pa[0] = pa[1] = pa[2] = 0;
-					for (int k = 0; k < 3; k++) pa[3 + k] = -grav[k];
-				} else {
-					for (int k = 0; k < 6; k++) { pv[k] = cvel[p][k]; pa[k] = cacc[p][k]; }
-				}
+				} else if constexpr (prest) le_parent_motion(pv, pa, grav);
+				else le_parent_motion(pv, pa, cvel[p], cacc[p]);
 				if constexpr (j >= 0) {
 					[[maybe_unused]] double qv = 0;
 					if constexpr (DV) qv = lp[64 * j].b;
@@ -1034,50 +1051,30 @@ DEVI void lane_env_body(const KernelParams MJB_AS4 *__restrict__ P, const int ns
 					constexpr bool CREC = ROLE == LE_QUAD_C;
 					[[maybe_unused]] const double *const hc = hC[CREC ? b : 0];
 					double ax[3];
-					if constexpr (CREC) { ax[0] = hc[10]; ax[1] = hc[11]; ax[2] = hc[12]; }
+					if constexpr (CREC) { ax[0] = hc[HC_JAXIS]; ax[1] = hc[HC_JAXIS + 1]; ax[2] = hc[HC_JAXIS + 2]; }
 					else { ax[0] = tj.jaxis[0]; ax[1] = tj.jaxis[1]; ax[2] = tj.jaxis[2]; }
 					double xaxis[3];
 					matvec3(xaxis, xm, ax);
-					if constexpr (T::jnt_type[j] == MJB_JNT_SLIDE) {
-						cd[0] = cd[1] = cd[2] = 0;
-						for (int k = 0; k < 3; k++) cd[3 + k] = xaxis[k];
-					} else {
+					if constexpr (T::jnt_type[j] == MJB_JNT_SLIDE) le_cdof_slide(cd, xaxis);
+					else {
 						// (the anchor from the body's FINAL frame: xpos + xmat jnt_pos -- the point mj_kinematics' off-centre correction keeps fixed)
 						double jp[3] = { 0, 0, 0 };
 						if constexpr (!CREC) { jp[0] = tj.jpos[0]; jp[1] = tj.jpos[1]; jp[2] = tj.jpos[2]; }
-						else if constexpr (!LeOffc<T>::known || LeOffc<T>::on(j)) { jp[0] = hc[13]; jp[1] = hc[14]; jp[2] = hc[15]; }
+						else if constexpr (!LeOffc<T>::known || LeOffc<T>::on(j)) { jp[0] = hc[HC_JPOS]; jp[1] = hc[HC_JPOS + 1]; jp[2] = hc[HC_JPOS + 2]; }
 						double xanch[3] = { xp[0], xp[1], xp[2] }, off[3];
-						if (le_offc<T, QUAD, j>(jp[0], jp[1], jp[2])) {
-							double v[3];
-							matvec3(v, xm, jp);
-							for (int k = 0; k < 3; k++) xanch[k] += v[k];
-						}
+						if (le_offc<T, QUAD, j>(jp[0], jp[1], jp[2])) le_xipos(xanch, xm, xanch, jp);
 						for (int k = 0; k < 3; k++) off[k] = -xanch[k];  // (root origin - anchor)
-						for (int k = 0; k < 3; k++) cd[k] = xaxis[k];
-						cross3(cd + 3, xaxis, off);
+						le_cdof_hinge(cd, xaxis, off);
 					}
-					if constexpr (ROLE == LE_QUAD_C) {  // (the quartet's C: cdof to V)
-						lp[64 * cq] = Pair{ cd[0], cd[1] };
-						lp[64 * (cq + 1)] = Pair{ cd[2], cd[3] };
-						lp[64 * (cq + 2)] = Pair{ cd[4], cd[5] };
+					if constexpr (ROLE == LE_QUAD_C) le_pairs_put<3>(lp + 64 * cq, cd);  // (the quartet's C: cdof to V)
 					}
-					}
-					if constexpr (!DV) {
-					} else if constexpr (p == 0 || !LD::needed(p)) {
-						for (int k = 0; k < 6; k++) { cvel[b][k] = cd[k] * qv; cacc[b][k] = pa[k]; }
-					} else {
-						double cdd[6];
-						cross_motion(cdd, pv, cd);
-						for (int k = 0; k < 6; k++) { cvel[b][k] = pv[k] + cd[k] * qv; cacc[b][k] = pa[k] + cdd[k] * qv; }
-					}
+					if constexpr (DV) le_body_motion<prest>(cvel[b], cacc[b], pv, pa, cd, qv);
 				} else if constexpr (DV) {
 					for (int k = 0; k < 6; k++) { cvel[b][k] = pv[k]; cacc[b][k] = pa[k]; }
 				}
 				if constexpr (DV) {
-					double cf[6], t0[6], t1[6];
-					mul_inert_vec(cf, ci, cacc[b]);
-					mul_inert_vec(t0, ci, cvel[b]);
-					cross_force(t1, cvel[b], t0);
+					double cf[6], t1[6];
+					le_cfrc(cf, t1, ci, cvel[b], cacc[b]);
 					constexpr int q0 = LD::slot(b);
 					lp[64 * q0] = Pair{ cf[0] + t1[0], cf[1] + t1[1] };
 					lp[64 * (q0 + 1)] = Pair{ cf[2] + t1[2], cf[3] + t1[3] };
@@ -1153,19 +1150,19 @@ DEVI void lane_env_body(const KernelParams MJB_AS4 *__restrict__ P, const int ns
 				constexpr int p = T::body_parentid[b], j = T::body_jnt[b], r = T::body_rootid[b];
 				touch_s(hA[b][0]);
 				if constexpr (j >= 0) touch_v(pq[b].a);
-				for (int k = 0; k < 10; k++) hB[b][k] = reinterpret_cast<const double MJB_AS4 *>(tb + b)[16 + k];
+				for (int k = 0; k < LE_I_N; k++) hB[b][k] = reinterpret_cast<const double MJB_AS4 *>(tb + b)[LE_HALF + k];
 				if constexpr (PE) {
 					if constexpr (OV::moving(b)) for (int k = 0; k < 7; k++) vB[b][k] = pe_ld(OV::inert(b, k));
 					else vB[b][0] = pe_ld(OV::rest(b));
 				}
 				if constexpr (XF && LD::needed(b)) for (int k = 0; k < 6; k++) xw[b][k] = xf_ld(6 * XS6::slot(b) + k);
-				const double *const A = hA[b];  // pos[3] quat[4] jaxis[3] jpos[3] qpos0 stiffness spring
+				const double *const A = hA[b];  // the pose half (LE_POS .. LE_QPOS0)
 				if constexpr (ROLE == LE_TRIO_P && b == 1 && b + 1 < NB) {
 					if constexpr (T::body_jnt[b + 1] >= 0) {
 						if constexpr (T::jnt_type[T::body_jnt[b + 1]] == MJB_JNT_HINGE) sincos_nb((pqn[b + 1].a - q0n[b + 1]) * 0.5, &psn[b + 1], &pcs[b + 1]);
 					}
 				}
-				double pos[3] = { A[0], A[1], A[2] }, quat[4] = { A[3], A[4], A[5], A[6] };
+				double pos[3] = { A[LE_POS], A[LE_POS + 1], A[LE_POS + 2] }, quat[4] = { A[LE_QUAT], A[LE_QUAT + 1], A[LE_QUAT + 2], A[LE_QUAT + 3] };
 				if constexpr (p != 0) {
 					double v[3], q[4];
 					matvec3(v, xmat[p], pos);
@@ -1181,7 +1178,7 @@ DEVI void lane_env_body(const KernelParams MJB_AS4 *__restrict__ P, const int ns
 					// The joint's world axis is its local axis through the body's FINAL orientation (a hinge turns about it, a slide does not
 					// turn), and a hinge's anchor stays where it was: the frame before the joint motion -- mj_kinematics' xaxis / xanchor
 					// source -- is only needed for an off-centre anchor (jnt_pos != 0, wave-uniform).
-					const double jp[3] = { A[10], A[11], A[12] };
+					const double jp[3] = { A[LE_JPOS], A[LE_JPOS + 1], A[LE_JPOS + 2] };
 					offc = jp[0] != 0 || jp[1] != 0 || jp[2] != 0;
 					for (int k = 0; k < 3; k++) xanch[k] = pos[k];
 					if (offc) {
@@ -1194,8 +1191,8 @@ DEVI void lane_env_body(const KernelParams MJB_AS4 *__restrict__ P, const int ns
 						double sn, cs, ql[4], q[4];
 						if constexpr (ROLE == LE_TRIO_P && SCUSE(b)) { sn = scq[b].a; cs = scq[b].b; }  // (C's, fetched in the previous body's second region)
 						else if constexpr (ROLE == LE_TRIO_P && b == 2) { sn = psn[b]; cs = pcs[b]; }  // (computed beside the first body's chain)
-						else sincos_nb((qp - A[13]) * 0.5, &sn, &cs);
-						ql[0] = cs; ql[1] = A[7] * sn; ql[2] = A[8] * sn; ql[3] = A[9] * sn;
+						else sincos_nb((qp - A[LE_QPOS0]) * 0.5, &sn, &cs);
+						ql[0] = cs; ql[1] = A[LE_JAXIS] * sn; ql[2] = A[LE_JAXIS + 1] * sn; ql[3] = A[LE_JAXIS + 2] * sn;
 						qmul(q, quat, ql);
 						for (int k = 0; k < 4; k++) quat[k] = q[k];
 					}
@@ -1210,40 +1207,40 @@ DEVI void lane_env_body(const KernelParams MJB_AS4 *__restrict__ P, const int ns
 				for (int k = 0; k < 4; k++) xquat[b][k] = quat[k];
 				quat2mat_nocheck(xmat[b], quat);
 				if constexpr (j >= 0) {
-					const double ax[3] = { A[7], A[8], A[9] };
+					const double ax[3] = { A[LE_JAXIS], A[LE_JAXIS + 1], A[LE_JAXIS + 2] };
 					matvec3(xaxis, xmat[b], ax);
 					if constexpr (T::jnt_type[j] == MJB_JNT_SLIDE) {
-						const double dq = qp - A[13];
+						const double dq = qp - A[LE_QPOS0];
 						for (int k = 0; k < 3; k++) pos[k] += xaxis[k] * dq;
 					} else if (offc) {  // correct for off-centre rotation
-						const double jp[3] = { A[10], A[11], A[12] };
+						const double jp[3] = { A[LE_JPOS], A[LE_JPOS + 1], A[LE_JPOS + 2] };
 						double v[3];
 						matvec3(v, xmat[b], jp);
 						for (int k = 0; k < 3; k++) pos[k] = xanch[k] - v[k];
 					}
 				}
 				for (int k = 0; k < 3; k++) xpos[b][k] = pos[k];
-				touch_rec<10>(hB[b]);
+				touch_rec<LE_I_N>(hB[b]);
 				__builtin_amdgcn_sched_barrier(0);
 				// ---- second region: inertial frame, cinert, velocities, forces; the next body's pose half on its way
 				touch_s(hB[b][0]);
-				if constexpr (b + 1 < NB) for (int k = 0; k < 14; k++) hA[b + 1][k] = reinterpret_cast<const double MJB_AS4 *>(tb + b + 1)[k];
+				if constexpr (b + 1 < NB) for (int k = 0; k < LE_A_N; k++) hA[b + 1][k] = reinterpret_cast<const double MJB_AS4 *>(tb + b + 1)[k];
 				{
 					constexpr int nb = [] { for (int c = b + 1; c < NB; c++) if (T::body_jnt[c] >= 0) return c; return -1; }();
 					if constexpr (nb >= 0) pq[nb] = lp[64 * T::body_jnt[nb]];
 				}
 				if constexpr (ROLE == LE_TRIO_P && SCUSE(b + 1)) scq[b + 1] = lp[64 * (SC0 + b + 1)];
-				const double *const Bh = hB[b];  // ipos[3] ibody[6] mass damping armature hdamping
+				const double *const Bh = hB[b];  // the inertial half (LE_I_IPOS .. LE_I_MASS)
 				// inertial frame
 				double xipos[3];
 				if constexpr (T::body_sameframe[b]) {
 					for (int k = 0; k < 3; k++) xipos[k] = xpos[b][k];
 				} else {
-					double ip[3] = { Bh[0], Bh[1], Bh[2] }, v[3];
+					double ip[3] = { Bh[LE_I_IPOS], Bh[LE_I_IPOS + 1], Bh[LE_I_IPOS + 2] }, v[3];
 					matvec3(v, xmat[b], ip);
 					for (int k = 0; k < 3; k++) xipos[k] = v[k] + xpos[b][k];
 				}
-				const double mass = [&] { if constexpr (PE) return vB[b][0]; else return Bh[9]; }();
+				const double mass = [&] { if constexpr (PE) return vB[b][0]; else return Bh[LE_I_MASS]; }();
 				if (eg_on) pe -= mass * (grav[0] * xipos[0] + grav[1] * xipos[1] + grav[2] * xipos[2]);
 				frame_sensors(B, xipos);
 				if constexpr (LD::needed(b)) {
@@ -1256,7 +1253,7 @@ DEVI void lane_env_body(const KernelParams MJB_AS4 *__restrict__ P, const int ns
 						// world inertia X Ib X' with the body-frame inertia matrix Ib = R(iquat) diag(inertia) R(iquat)' from the tape
 						// (mju_inertCom builds the same matrix as ximat diag ximat', ximat = X R(iquat))
 						const double *X = xmat[b];
-						const double *const Ib = [&] { if constexpr (PE) return vB[b] + 1; else return Bh + 3; }();
+						const double *const Ib = [&] { if constexpr (PE) return vB[b] + 1; else return Bh + LE_I_IBODY; }();
 						const double ixx = Ib[0], iyy = Ib[1], izz = Ib[2], ixy = Ib[3], ixz = Ib[4], iyz = Ib[5];
 						double Tm[9];
 						for (int rr = 0; rr < 3; rr++) {
@@ -1276,14 +1273,10 @@ DEVI void lane_env_body(const KernelParams MJB_AS4 *__restrict__ P, const int ns
 						res[8] = mass * dif[2];
 						res[9] = mass;
 					}
-					// parent's velocity / acceleration (world: zero velocity, -gravity)
+					// parent's velocity / acceleration (the world, or a jointless chain down from it: at rest)
 					[[maybe_unused]] double pv[6], pa[6];
 					if constexpr (!DV) {
-					} else if constexpr (p == 0) {
-						for (int k = 0; k < 6; k++) pv[k] = 0;
-						pa[0] = pa[1] = pa[2] = 0;
-						for (int k = 0; k < 3; k++) pa[3 + k] = -grav[k];
-					} else if constexpr (!LD::needed(p)) {  // a jointless chain down from the world: at rest
+					} else if constexpr (p == 0 || !LD::needed(p)) {
 						for (int k = 0; k < 6; k++) pv[k] = 0;
 						pa[0] = pa[1] = pa[2] = 0;
 						for (int k = 0; k < 3; k++) pa[3 + k] = -grav[k];
@@ -1344,7 +1337,7 @@ DEVI void lane_env_body(const KernelParams MJB_AS4 *__restrict__ P, const int ns
 							double xd[3], F[3], tq[3];
 							if constexpr (r == b) for (int k = 0; k < 3; k++) xd[k] = xipos[k] - pos[k];
 							else for (int k = 0; k < 3; k++) xd[k] = xipos[k] - xpos[r][k];
-							const double sc = pas_on ? -mass * tb[b].pad[0] : 0.0;
+							const double sc = pas_on ? -mass * tb[b].gravcomp : 0.0;
 							for (int k = 0; k < 3; k++) F[k] = sc * grav[k];
 							cross3(tq, xd, F);
 							for (int k = 0; k < 3; k++) { cf[k] -= tq[k]; cf[3 + k] -= F[k]; }
@@ -1356,15 +1349,9 @@ DEVI void lane_env_body(const KernelParams MJB_AS4 *__restrict__ P, const int ns
 					}
 					if constexpr (ROLE == LE_PIPE_P || ROLE == LE_TRIO_P) {  // the pose to V (and, of three, to C)
 						constexpr int ord = (LD::slot(b) - NV) / 3, rg = RING + 6 * (ord % RINGN);
-						const double *xm = xmat[b];
 						double xp[3] = { 0, 0, 0 };  // relative to the tree root's origin: what cdof is taken about
 						if constexpr (r != b) for (int k = 0; k < 3; k++) xp[k] = xpos[b][k] - xpos[r][k];
-						lp[64 * rg] = Pair{ xp[0], xp[1] };
-						lp[64 * (rg + 1)] = Pair{ xp[2], xm[0] };
-						lp[64 * (rg + 2)] = Pair{ xm[1], xm[2] };
-						lp[64 * (rg + 3)] = Pair{ xm[3], xm[4] };
-						lp[64 * (rg + 4)] = Pair{ xm[5], xm[6] };
-						lp[64 * (rg + 5)] = Pair{ xm[7], xm[8] };
+						le_ring_put(lp + 64 * rg, xp, xmat[b]);
 						LE_PK(0);
 						le_barrier();
 						LE_PK(2);
@@ -1376,7 +1363,7 @@ DEVI void lane_env_body(const KernelParams MJB_AS4 *__restrict__ P, const int ns
 						rw[b][3] = mass;
 					}
 				}
-				if constexpr (b + 1 < NB) touch_rec<14>(hA[b + 1]);
+				if constexpr (b + 1 < NB) touch_rec<LE_A_N>(hA[b + 1]);
 				if constexpr (DV && b == NB - 1) sfor<NV>([&](auto I) { qfa[I] = s.qfrc_applied[ev * NV + I]; });
 				if constexpr (HW && b == NB - 1) hw_fetch();
 				__builtin_amdgcn_sched_barrier(0);
@@ -1403,38 +1390,23 @@ DEVI void lane_env_body(const KernelParams MJB_AS4 *__restrict__ P, const int ns
 					constexpr int b = Bq;
 					constexpr int p = T::body_parentid[b], j = T::body_jnt[b];
 					static_assert(LD::needed(b), "the quartet: a body at rest has its quaternion from ahead of the step loop");
-					const double *const A = hA[b];  // pos[3] quat[4] jaxis[3] jpos[3] qpos0
+					const double *const A = hA[b];  // the pose half
 					constexpr int qr = QR0 + 4 * (((LD::slot(b) - NV) / 3) % 2);
-					double quat[4] = { A[3], A[4], A[5], A[6] };
-					if constexpr (p != 0) {
-						double q[4];
-						qmul(q, xquat[p], quat);
-						for (int k = 0; k < 4; k++) quat[k] = q[k];
-					}
+					double quat[4] = { A[LE_QUAT], A[LE_QUAT + 1], A[LE_QUAT + 2], A[LE_QUAT + 3] };
+					if constexpr (p != 0) le_xquat(quat, xquat[p]);
 					if constexpr (j >= 0) {
 						// (an off-centre anchor -- the topology's flag, or wave-uniform: X needs the frame before the joint motion too)
-						if (le_offc<T, true, j>(A[10], A[11], A[12])) {
-							lp[64 * (qr + 2)] = Pair{ quat[0], quat[1] };
-							lp[64 * (qr + 3)] = Pair{ quat[2], quat[3] };
-						}
-						if constexpr (T::jnt_type[j] == MJB_JNT_HINGE) {
-							double ql[4], q[4];
-							ql[0] = ocs[b]; ql[1] = A[7] * osn[b]; ql[2] = A[8] * osn[b]; ql[3] = A[9] * osn[b];
-							qmul(q, quat, ql);
-							for (int k = 0; k < 4; k++) quat[k] = q[k];
-						}
+						if (le_offc<T, true, j>(A[LE_JPOS], A[LE_JPOS + 1], A[LE_JPOS + 2])) le_pairs_put<2>(lp + 64 * (qr + 2), quat);
+						if constexpr (T::jnt_type[j] == MJB_JNT_HINGE) le_hinge_quat(quat, A + LE_JAXIS, osn[b], ocs[b]);
 					}
 					normalize4_sel(quat);
 					for (int k = 0; k < 4; k++) xquat[b][k] = quat[k];
-					if constexpr (LD::needed(b)) {
-						lp[64 * qr] = Pair{ quat[0], quat[1] };
-						lp[64 * (qr + 1)] = Pair{ quat[2], quat[3] };
-					}
+					if constexpr (LD::needed(b)) le_pairs_put<2>(lp + 64 * qr, quat);
 				};
 				auto o_phase = [&](auto Bq) {
 					constexpr int b = Bq, nx = NEXTN(b), nx2 = NEXTN(nx < NB ? nx : NB - 1);
 					touch_s(hA[b][0]);
-					if constexpr (nx < NB) for (int k = 0; k < 14; k++) hA[nx][k] = reinterpret_cast<const double MJB_AS4 *>(tb + nx)[k];
+					if constexpr (nx < NB) for (int k = 0; k < LE_A_N; k++) hA[nx][k] = reinterpret_cast<const double MJB_AS4 *>(tb + nx)[k];
 					if constexpr (nx < NB && HINGE(nx2)) {
 						opq[nx2] = lp[64 * T::body_jnt[nx2 < NB ? nx2 : 0]];
 						oq0[nx2] = tb[nx2].qpos0;
@@ -1442,7 +1414,7 @@ DEVI void lane_env_body(const KernelParams MJB_AS4 *__restrict__ P, const int ns
 					// (the next hinge's two polynomial chains depend on qpos alone: they fill this body's dependency stalls)
 					if constexpr (HINGE(nx)) sincos_nb((opq[nx].a - oq0[nx]) * 0.5, &osn[nx], &ocs[nx]);
 					o_body(Bq);
-					if constexpr (nx < NB) touch_rec<14>(hA[nx]);
+					if constexpr (nx < NB) touch_rec<LE_A_N>(hA[nx]);
 				};
 				// X, body b: O's quaternion into the frame, the position chain, what hangs on the pose (hA[b], hB[b] are there)
 				auto x_body = [&](auto Bq) {
@@ -1450,33 +1422,23 @@ DEVI void lane_env_body(const KernelParams MJB_AS4 *__restrict__ P, const int ns
 					constexpr int p = T::body_parentid[b], j = T::body_jnt[b], r = T::body_rootid[b];
 					constexpr int qr = QR0 + 4 * (((LD::slot(b) - NV) / 3) % 2);
 					const double *const A = hA[b];
-					double pos[3] = { A[0], A[1], A[2] }, quat[4] = { A[3], A[4], A[5], A[6] };
+					double pos[3] = { A[LE_POS], A[LE_POS + 1], A[LE_POS + 2] }, quat[4];
 					static_assert(LD::needed(b), "the quartet: a body at rest has its pose from ahead of the step loop");
-					{
-						const Pair g0 = lp[64 * qr], g1 = lp[64 * (qr + 1)];
-						quat[0] = g0.a; quat[1] = g0.b; quat[2] = g1.a; quat[3] = g1.b;
-					}
+					le_pairs_get<2>(quat, lp + 64 * qr);
 					[[maybe_unused]] Pair sp{ 0, 0 };
 					if constexpr (j >= 0) sp = lp[64 * j];
-					if constexpr (p != 0) {
-						double v[3];
-						matvec3(v, xmat[p], pos);
-						for (int k = 0; k < 3; k++) pos[k] = v[k] + xpos[p][k];
-					}
+					if constexpr (p != 0) le_xipos(pos, xmat[p], xpos[p], pos);
 					[[maybe_unused]] double xanch[3], qp = 0;
 					[[maybe_unused]] bool offc = false;
 					if constexpr (j >= 0) {
 						qp = sp.a;
-						const double jp[3] = { A[10], A[11], A[12] };
+						const double *const jp = A + LE_JPOS;
 						offc = le_offc<T, true, j>(jp[0], jp[1], jp[2]);
 						for (int k = 0; k < 3; k++) xanch[k] = pos[k];
 						if (offc) {
-							const Pair h0 = lp[64 * (qr + 2)], h1 = lp[64 * (qr + 3)];
-							const double q0[4] = { h0.a, h0.b, h1.a, h1.b };
-							double M0[9], v[3];
-							quat2mat_nocheck(M0, q0);
-							matvec3(v, M0, jp);
-							for (int k = 0; k < 3; k++) xanch[k] += v[k];
+							double q0[4];
+							le_pairs_get<2>(q0, lp + 64 * (qr + 2));
+							le_anchor(xanch, q0, jp);
 						}
 						if (ep_on && pas_on) {  // mj_energyPos: the joint spring
 							const double dqs = qp - tb[b].spring;  // (last step only)
@@ -1487,41 +1449,23 @@ DEVI void lane_env_body(const KernelParams MJB_AS4 *__restrict__ P, const int ns
 					quat2mat_nocheck(xmat[b], quat);
 					if constexpr (j >= 0) {
 						if constexpr (T::jnt_type[j] == MJB_JNT_SLIDE) {
-							const double ax[3] = { A[7], A[8], A[9] };
 							double xaxis[3];
-							matvec3(xaxis, xmat[b], ax);
-							const double dq = qp - A[13];
-							for (int k = 0; k < 3; k++) pos[k] += xaxis[k] * dq;
-						} else if (offc) {  // correct for off-centre rotation
-							const double jp[3] = { A[10], A[11], A[12] };
-							double v[3];
-							matvec3(v, xmat[b], jp);
-							for (int k = 0; k < 3; k++) pos[k] = xanch[k] - v[k];
-						}
+							matvec3(xaxis, xmat[b], A + LE_JAXIS);
+							le_pos_slide(pos, xaxis, qp - A[LE_QPOS0]);
+						} else if (offc) le_pos_offcentre(pos, xanch, xmat[b], A + LE_JPOS);  // correct for off-centre rotation
 					}
 					for (int k = 0; k < 3; k++) xpos[b][k] = pos[k];
-					const double *const Bh = hB[b];  // ipos[3] ibody[6] mass
+					const double *const Bh = hB[b];  // the inertial half
 					double xipos[3];
-					if constexpr (T::body_sameframe[b]) {
-						for (int k = 0; k < 3; k++) xipos[k] = xpos[b][k];
-					} else {
-						double ip[3] = { Bh[0], Bh[1], Bh[2] }, v[3];
-						matvec3(v, xmat[b], ip);
-						for (int k = 0; k < 3; k++) xipos[k] = v[k] + xpos[b][k];
-					}
-					if (eg_on) pe -= Bh[9] * (grav[0] * xipos[0] + grav[1] * xipos[1] + grav[2] * xipos[2]);
+					if constexpr (T::body_sameframe[b]) for (int k = 0; k < 3; k++) xipos[k] = xpos[b][k];
+					else le_xipos(xipos, xmat[b], xpos[b], Bh + LE_I_IPOS);
+					if (eg_on) pe -= Bh[LE_I_MASS] * (grav[0] * xipos[0] + grav[1] * xipos[1] + grav[2] * xipos[2]);
 					frame_sensors(Bq, xipos);
 					if constexpr (LD::needed(b)) {  // the pose to C
 						constexpr int ord = (LD::slot(b) - NV) / 3, rg = RING + 6 * (ord % RINGN);
-						const double *xm = xmat[b];
 						double xp[3] = { 0, 0, 0 };  // relative to the tree root's origin: what cdof is taken about
 						if constexpr (r != b) for (int k = 0; k < 3; k++) xp[k] = xpos[b][k] - xpos[r][k];
-						lp[64 * rg] = Pair{ xp[0], xp[1] };
-						lp[64 * (rg + 1)] = Pair{ xp[2], xm[0] };
-						lp[64 * (rg + 2)] = Pair{ xm[1], xm[2] };
-						lp[64 * (rg + 3)] = Pair{ xm[3], xm[4] };
-						lp[64 * (rg + 4)] = Pair{ xm[5], xm[6] };
-						lp[64 * (rg + 5)] = Pair{ xm[7], xm[8] };
+						le_ring_put(lp + 64 * rg, xp, xmat[b]);
 					}
 				};
 				// X, cdof for its own leaf -> root walk: the six doubles C publishes for V (consume), taken from the ring where V takes them -- the phase after
@@ -1530,10 +1474,7 @@ DEVI void lane_env_body(const KernelParams MJB_AS4 *__restrict__ P, const int ns
 					constexpr int b = Bq, j = T::body_jnt[b];
 					if constexpr (j >= 0) {
 						constexpr int cq = CD0 + 3 * (((LD::slot(b) - NV) / 3) % 2);
-						const Pair d0 = lp[64 * cq], d1 = lp[64 * (cq + 1)], d2 = lp[64 * (cq + 2)];
-						double *cd = cdof[j];
-						cd[0] = d0.a; cd[1] = d0.b; cd[2] = d1.a; cd[3] = d1.b; cd[4] = d2.a; cd[5] = d2.b;
-						if constexpr (T::jnt_type[j] == MJB_JNT_SLIDE) cd[0] = cd[1] = cd[2] = 0;
+						le_cdof_ring_get<T::jnt_type[j] == MJB_JNT_SLIDE>(cdof[j], lp + 64 * cq);
 					}
 				};
 				auto x_phase = [&](auto Bq, auto Cq) {  // (Cq: the body whose cdof this phase takes from C's ring, 0: none yet)
@@ -1541,8 +1482,8 @@ DEVI void lane_env_body(const KernelParams MJB_AS4 *__restrict__ P, const int ns
 					touch_s(hA[b][0]);
 					touch_s(hB[b][0]);
 					if constexpr (nx < NB) {
-						for (int k = 0; k < 14; k++) hA[nx][k] = reinterpret_cast<const double MJB_AS4 *>(tb + nx)[k];
-						for (int k = 0; k < 10; k++) hB[nx][k] = reinterpret_cast<const double MJB_AS4 *>(tb + nx)[16 + k];
+						for (int k = 0; k < LE_A_N; k++) hA[nx][k] = reinterpret_cast<const double MJB_AS4 *>(tb + nx)[k];
+						for (int k = 0; k < LE_I_N; k++) hB[nx][k] = reinterpret_cast<const double MJB_AS4 *>(tb + nx)[LE_HALF + k];
 					}
 					// (the cdof reads beside the quaternion's at the top of the phase, not between the pose writes and the barrier: they land under the body)
 					constexpr int cb = Cq;
@@ -1556,11 +1497,11 @@ DEVI void lane_env_body(const KernelParams MJB_AS4 *__restrict__ P, const int ns
 						//  slide's business here, jpos an off-centre anchor's, and the inertia matrix nobody's)
 						constexpr int jn = T::body_jnt[nx];
 						const double *const a = hA[nx], *const h = hB[nx];
-						asm volatile("" ::"s"(a[0]), "s"(a[1]), "s"(a[2]), "s"(h[9]));
-						if constexpr (!T::body_sameframe[nx]) asm volatile("" ::"s"(h[0]), "s"(h[1]), "s"(h[2]));
+						asm volatile("" ::"s"(a[LE_POS]), "s"(a[LE_POS + 1]), "s"(a[LE_POS + 2]), "s"(h[LE_I_MASS]));
+						if constexpr (!T::body_sameframe[nx]) asm volatile("" ::"s"(h[LE_I_IPOS]), "s"(h[LE_I_IPOS + 1]), "s"(h[LE_I_IPOS + 2]));
 						if constexpr (jn >= 0) {
-							if constexpr (T::jnt_type[jn < 0 ? 0 : jn] == MJB_JNT_SLIDE) asm volatile("" ::"s"(a[7]), "s"(a[8]), "s"(a[9]), "s"(a[13]));
-							if constexpr (!LeOffc<T>::known || LeOffc<T>::on(jn < 0 ? 0 : jn)) asm volatile("" ::"s"(a[10]), "s"(a[11]), "s"(a[12]));
+							if constexpr (T::jnt_type[jn < 0 ? 0 : jn] == MJB_JNT_SLIDE) asm volatile("" ::"s"(a[LE_JAXIS]), "s"(a[LE_JAXIS + 1]), "s"(a[LE_JAXIS + 2]), "s"(a[LE_QPOS0]));
+							if constexpr (!LeOffc<T>::known || LeOffc<T>::on(jn < 0 ? 0 : jn)) asm volatile("" ::"s"(a[LE_JPOS]), "s"(a[LE_JPOS + 1]), "s"(a[LE_JPOS + 2]));
 						}
 					}
 				};
@@ -1574,51 +1515,25 @@ DEVI void lane_env_body(const KernelParams MJB_AS4 *__restrict__ P, const int ns
 					static_assert(c0 >= 0, "the quartet: every needed body's cinert lives in LDS");
 					if constexpr (j >= 0) {
 						constexpr int cq = CD0 + 3 * (((LD::slot(b) - NV) / 3) % 2);
-						const Pair d0 = lp[64 * cq], d1 = lp[64 * (cq + 1)], d2 = lp[64 * (cq + 2)];
+						le_cdof_ring_get<T::jnt_type[j] == MJB_JNT_SLIDE>(cdof[j], lp + 64 * cq);
 						vqv[b] = lp[64 * j].b;
-						double *cd = cdof[j];
-						cd[0] = d0.a; cd[1] = d0.b; cd[2] = d1.a; cd[3] = d1.b; cd[4] = d2.a; cd[5] = d2.b;
-						if constexpr (T::jnt_type[j] == MJB_JNT_SLIDE) cd[0] = cd[1] = cd[2] = 0;
 					}
-					for (int k = 0; k < 5; k++) {
-						const Pair c = lp[64 * (c0 + k)];
-						vci[b][2 * k] = c.a;
-						vci[b][2 * k + 1] = c.b;
-					}
+					le_pairs_get<5>(vci[b], lp + 64 * c0);
 				};
 				[[maybe_unused]] auto v_kin = [&](auto Bq) {
 					constexpr int b = Bq, p = T::body_parentid[b], j = T::body_jnt[b];
+					constexpr bool prest = p == 0 || !LD::needed(p);  // the world, or a jointless chain down from it: at rest
 					double pv[6], pa[6];
-					if constexpr (p == 0 || !LD::needed(p)) {  // the world, or a jointless chain down from it: at rest
-						for (int k = 0; k < 6; k++) pv[k] = 0;
-						pa[0] = pa[1] = pa[2] = 0;
-						for (int k = 0; k < 3; k++) pa[3 + k] = -grav[k];
-					} else {
-						for (int k = 0; k < 6; k++) { pv[k] = cvel[p][k]; pa[k] = cacc[p][k]; }
-					}
-					if constexpr (j >= 0) {
-						const double qv = vqv[b];
-						const double *cd = cdof[j];
-						if constexpr (p == 0 || !LD::needed(p)) {
-							for (int k = 0; k < 6; k++) { cvel[b][k] = cd[k] * qv; cacc[b][k] = pa[k]; }
-						} else {
-							double cdd[6];
-							cross_motion(cdd, pv, cd);
-							for (int k = 0; k < 6; k++) { cvel[b][k] = pv[k] + cd[k] * qv; cacc[b][k] = pa[k] + cdd[k] * qv; }
-						}
-					} else {
-						for (int k = 0; k < 6; k++) { cvel[b][k] = pv[k]; cacc[b][k] = pa[k]; }
-					}
+					if constexpr (prest) le_parent_motion(pv, pa, grav);
+					else le_parent_motion(pv, pa, cvel[p], cacc[p]);
+					if constexpr (j >= 0) le_body_motion<prest>(cvel[b], cacc[b], pv, pa, cdof[j], vqv[b]);
+					else for (int k = 0; k < 6; k++) { cvel[b][k] = pv[k]; cacc[b][k] = pa[k]; }
 				};
 				[[maybe_unused]] auto v_force = [&](auto Bq) {
-					constexpr int b = Bq, q0 = LD::slot(b);
-					double cf[6], t0[6], t1[6];
-					mul_inert_vec(cf, vci[b], cacc[b]);
-					mul_inert_vec(t0, vci[b], cvel[b]);
-					cross_force(t1, cvel[b], t0);
-					lp[64 * q0] = Pair{ cf[0] + t1[0], cf[1] + t1[1] };
-					lp[64 * (q0 + 1)] = Pair{ cf[2] + t1[2], cf[3] + t1[3] };
-					lp[64 * (q0 + 2)] = Pair{ cf[4] + t1[4], cf[5] + t1[5] };
+					constexpr int b = Bq;
+					double cf[6], t1[6];
+					le_cfrc(cf, t1, vci[b], cvel[b], cacc[b]);
+					le_cfrc_put(lp + 64 * LD::slot(b), cf, t1);
 				};
 				if constexpr (ROLE == LE_QUAD_C) {  // the first needed body's record, ahead of the phases as O's and X's
 					if constexpr (N1 < NB) {
@@ -1642,8 +1557,8 @@ DEVI void lane_env_body(const KernelParams MJB_AS4 *__restrict__ P, const int ns
 						}
 					});
 					if constexpr (N1 < NB) {
-						for (int k = 0; k < 14; k++) hA[N1][k] = reinterpret_cast<const double MJB_AS4 *>(tb + N1)[k];
-						if constexpr (ROLE == LE_QUAD_X) for (int k = 0; k < 10; k++) hB[N1][k] = reinterpret_cast<const double MJB_AS4 *>(tb + N1)[16 + k];
+						for (int k = 0; k < LE_A_N; k++) hA[N1][k] = reinterpret_cast<const double MJB_AS4 *>(tb + N1)[k];
+						if constexpr (ROLE == LE_QUAD_X) for (int k = 0; k < LE_I_N; k++) hB[N1][k] = reinterpret_cast<const double MJB_AS4 *>(tb + N1)[LE_HALF + k];
 					}
 					if constexpr (ROLE == LE_QUAD_O) {
 						if constexpr (HINGE(N1)) {
@@ -2518,20 +2433,13 @@ DEVI void lane_env_body(const KernelParams MJB_AS4 *__restrict__ P, const int ns
 						if constexpr (b > 0 && LD::needed(b) && SN::below(b, le_wrench_type)) {
 							constexpr int q0 = LD::slot(b), c0 = LD::cin_slot(b);
 							double ci[10], own[6];
-							if constexpr (c0 >= 0) {
-								for (int k = 0; k < 5; k++) {
-									const Pair c = lp[64 * (c0 + k)];
-									ci[2 * k] = c.a;
-									ci[2 * k + 1] = c.b;
-								}
-							} else {
-								for (int k = 0; k < 10; k++) ci[k] = cin[b][k];
-							}
+							if constexpr (c0 >= 0) le_pairs_get<5>(ci, lp + 64 * c0);
+							else for (int k = 0; k < 10; k++) ci[k] = cin[b][k];
 							const Pair f0 = lp[64 * q0], f1 = lp[64 * (q0 + 1)], f2 = lp[64 * (q0 + 2)];
 							mul_inert_vec(own, ci, dq[b]);
 							own[0] += f0.a; own[1] += f0.b; own[2] += f1.a; own[3] += f1.b; own[4] += f2.a; own[5] += f2.b;
 							if constexpr (LeGc<T>::on(b)) {  // (the sweep took (xd x F ; F), F = -gravity mass gravcomp, off the bias force; mass xd is cinert's [6 .. 8])
-								const double sc = pas_on ? -tb[b].pad[0] : 0.0;
+								const double sc = pas_on ? -tb[b].gravcomp : 0.0;
 								double F[3], tq[3];
 								for (int k = 0; k < 3; k++) F[k] = sc * grav[k];
 								cross3(tq, ci + 6, F);

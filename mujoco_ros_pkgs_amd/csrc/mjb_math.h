@@ -86,22 +86,7 @@ DEVI void quat2mat(double *r, const double *q)
 	r[6] = 2 * (q13 - q02);
 	r[7] = 2 * (q23 + q01);
 }
-// same map without the exact-identity shortcut (value-identical: the formula yields exactly I for (1,0,0,0))
-DEVI void quat2mat_nocheck(double *r, const double *q)
-{
-	const double q00 = q[0] * q[0], q01 = q[0] * q[1], q02 = q[0] * q[2], q03 = q[0] * q[3];
-	const double q11 = q[1] * q[1], q12 = q[1] * q[2], q13 = q[1] * q[3];
-	const double q22 = q[2] * q[2], q23 = q[2] * q[3], q33 = q[3] * q[3];
-	r[0] = q00 + q11 - q22 - q33;
-	r[4] = q00 - q11 + q22 - q33;
-	r[8] = q00 - q11 - q22 + q33;
-	r[1] = 2 * (q12 - q03);
-	r[2] = 2 * (q13 + q02);
-	r[3] = 2 * (q12 + q03);
-	r[5] = 2 * (q23 - q01);
-	r[6] = 2 * (q13 - q02);
-	r[7] = 2 * (q23 + q01);
-}
+DEVI void quat2mat_nocheck(double *r, const double *q) { quat2mat(r, q); }  // (the older name of the same map)
 DEVI void matvec3(double *r, const double *M, const double *v)
 {
 	double t0 = M[0] * v[0] + M[1] * v[1] + M[2] * v[2];
@@ -215,6 +200,112 @@ DEVI void mul_inert_vec(double *res, const double *i, const double *v)
 	res[3] = i[8] * v[1] - i[7] * v[2] + i[9] * v[3];
 	res[4] = i[6] * v[2] - i[8] * v[0] + i[9] * v[4];
 	res[5] = i[7] * v[0] - i[6] * v[1] + i[9] * v[5];
+}
+
+// ---- one body of the root -> leaf sweep, each per-body quantity once (who calls them, and who does not yet: the head of mjb_lane_env_kernel.h).
+// Registers in, registers out -- arithmetic only: no wait, no pin, no fetch of a tape record.  Spatial quantities are about the tree root's origin.
+// Operand order and association are part of the definition: results are compared bit for bit.
+// mj_kinematics: a point / an orientation of the body's frame (xmat, xpos | xquat) in the world -- a child's frame before its joint, xipos, a site
+DEVI void le_xipos(double *r, const double *xmat, const double *xpos, const double *local)
+{
+	double v[3];
+	matvec3(v, xmat, local);
+	for (int k = 0; k < 3; k++) r[k] = v[k] + xpos[k];
+}
+DEVI void le_xquat(double *quat, const double *pquat)
+{
+	double q[4];
+	qmul(q, pquat, quat);
+	for (int k = 0; k < 4; k++) quat[k] = q[k];
+}
+// mj_kinematics: xanchor of an off-centre joint, from the frame BEFORE the joint motion (xanch holds that frame's origin on entry)
+DEVI void le_anchor(double *xanch, const double *quat, const double *jp)
+{
+	double M0[9], v[3];
+	quat2mat_nocheck(M0, quat);
+	matvec3(v, M0, jp);
+	for (int k = 0; k < 3; k++) xanch[k] += v[k];
+}
+// mj_kinematics: a hinge's turn about its local axis, half angle (sn, cs), applied to the orientation
+DEVI void le_hinge_quat(double *quat, const double *ax, const double sn, const double cs)
+{
+	const double ql[4] = { cs, ax[0] * sn, ax[1] * sn, ax[2] * sn };
+	double q[4];
+	qmul(q, quat, ql);
+	for (int k = 0; k < 4; k++) quat[k] = q[k];
+}
+// mj_kinematics: the position after the joint -- a slide moves along its world axis | an off-centre rotation keeps the anchor where it was
+DEVI void le_pos_slide(double *pos, const double *xaxis, const double dq) { for (int k = 0; k < 3; k++) pos[k] += xaxis[k] * dq; }
+DEVI void le_pos_offcentre(double *pos, const double *xanch, const double *xmat, const double *jp)
+{
+	double v[3];
+	matvec3(v, xmat, jp);
+	for (int k = 0; k < 3; k++) pos[k] = xanch[k] - v[k];
+}
+// mj_comPos, cinert = mju_inertCom(X Ib X', mass, dif) in two halves (a caller may fetch between them): Tm = X Ib, Ib the body-frame inertia matrix
+// R(iquat) diag(inertia) R(iquat)' (xx yy zz xy xz yz) | the rest, dif = xipos - the tree root's origin
+DEVI void le_inert_rot(double *Tm, const double *X, const double ixx, const double iyy, const double izz, const double ixy, const double ixz, const double iyz)
+{
+	for (int rr = 0; rr < 3; rr++) {
+		Tm[3 * rr + 0] = X[3 * rr] * ixx + X[3 * rr + 1] * ixy + X[3 * rr + 2] * ixz;
+		Tm[3 * rr + 1] = X[3 * rr] * ixy + X[3 * rr + 1] * iyy + X[3 * rr + 2] * iyz;
+		Tm[3 * rr + 2] = X[3 * rr] * ixz + X[3 * rr + 1] * iyz + X[3 * rr + 2] * izz;
+	}
+}
+DEVI void le_cinert_com(double *ci, const double *Tm, const double *X, const double mass, const double *dif)
+{
+	ci[0] = Tm[0] * X[0] + Tm[1] * X[1] + Tm[2] * X[2] + mass * (dif[1] * dif[1] + dif[2] * dif[2]);
+	ci[1] = Tm[3] * X[3] + Tm[4] * X[4] + Tm[5] * X[5] + mass * (dif[0] * dif[0] + dif[2] * dif[2]);
+	ci[2] = Tm[6] * X[6] + Tm[7] * X[7] + Tm[8] * X[8] + mass * (dif[0] * dif[0] + dif[1] * dif[1]);
+	ci[3] = Tm[0] * X[3] + Tm[1] * X[4] + Tm[2] * X[5] - mass * dif[0] * dif[1];
+	ci[4] = Tm[0] * X[6] + Tm[1] * X[7] + Tm[2] * X[8] - mass * dif[0] * dif[2];
+	ci[5] = Tm[3] * X[6] + Tm[4] * X[7] + Tm[5] * X[8] - mass * dif[1] * dif[2];
+	ci[6] = mass * dif[0];
+	ci[7] = mass * dif[1];
+	ci[8] = mass * dif[2];
+	ci[9] = mass;
+}
+// mj_comPos, cdof of a hinge (world axis; off = the tree root's origin - xanchor) | of a slide
+DEVI void le_cdof_hinge(double *cd, const double *xaxis, const double *off)
+{
+	for (int k = 0; k < 3; k++) cd[k] = xaxis[k];
+	cross3(cd + 3, xaxis, off);
+}
+DEVI void le_cdof_slide(double *cd, const double *xaxis)
+{
+	cd[0] = cd[1] = cd[2] = 0;
+	for (int k = 0; k < 3; k++) cd[3 + k] = xaxis[k];
+}
+// mj_comVel / mj_rne: what a body inherits -- (cvel, cacc) of a parent at rest (the world, or a jointless chain down from it): (0, -gravity) | the parent's
+DEVI void le_parent_motion(double *pv, double *pa, const double *grav)
+{
+	for (int k = 0; k < 6; k++) pv[k] = 0;
+	pa[0] = pa[1] = pa[2] = 0;
+	for (int k = 0; k < 3; k++) pa[3 + k] = -grav[k];
+}
+DEVI void le_parent_motion(double *pv, double *pa, const double *pcvel, const double *pcacc)
+{
+	for (int k = 0; k < 6; k++) { pv[k] = pcvel[k]; pa[k] = pcacc[k]; }
+}
+// mj_comVel / mj_rne of a one-dof body: cvel = pv + cdof qvel, cacc = pa + cdof_dot qvel, cdof_dot = pv x cdof.  REST: pv is zero by construction and
+// its terms are left out (pv + x and x differ in the sign of a zero; a kernel that adds them regardless passes REST = false)
+template <bool REST> DEVI void le_body_motion(double *cv, double *ca, const double *pv, const double *pa, const double *cd, const double qv)
+{
+	if constexpr (REST) {
+		for (int k = 0; k < 6; k++) { cv[k] = cd[k] * qv; ca[k] = pa[k]; }
+	} else {
+		double cdd[6];
+		cross_motion(cdd, pv, cd);
+		for (int k = 0; k < 6; k++) { cv[k] = pv[k] + cd[k] * qv; ca[k] = pa[k] + cdd[k] * qv; }
+	}
+}
+// mj_rne, forward pass: cfrc_body = cinert cacc + cvel x* (cinert cvel), as its two summands (cf, t1)
+DEVI void le_cfrc(double *cf, double *t1, const double *ci, const double *cv, const double *ca)
+{
+	double t0[6];
+	mul_inert_vec(cf, ci, ca);
+	mul_inert_vec(t0, ci, cv);
+	cross_force(t1, cv, t0);
 }
 
 // ---- Philox-4x32-10 counter-based generator + Box-Muller (identical stream to oracle/mjo_smooth.c)
