@@ -541,6 +541,27 @@ int mjb_sensor_pack(mjb_batch *b, uint64_t seed);
 int mjb_sensor_get(mjb_batch *b, int which, int env_lo, int env_hi, float *host);
 void *mjb_sensor_device_ptr(mjb_batch *b, int which);
 
+/* ---- batched ray casting: mj_ray for many rays of every env at once ----
+ * A lidar ring or a small depth image per env, cast on the device against the geom poses of the frame workspace (plane, sphere, capsule
+ * and box: the rangefinder sensor's intersection, bit for bit).  Ray r hangs on site[r]: it starts at site_xpos + site_xmat pnt[r] and runs
+ * along site_xmat vec[r]; site -1 gives pnt and vec in the world frame.  vec is not normalised (mj_ray): a result is in units of |vec|.
+ * The result of a ray is the smallest x >= 0 over the geoms it may hit and that geom's id, -1 and -1 for a miss; the lower geom id keeps a
+ * tie.  A geom is skipped when its geom_mask entry is 0 (NULL mask: when its geom_rgba alpha is 0, the rangefinder's rule), or when the ray
+ * excludes its own body and the geom belongs to the site's body.  Per-env geom sizes and types (mjb_set_env_geom_size / _type) are honoured.
+ * mjb_rays_configure validates (MJB_EINVAL: nray < 1, a site outside [-1, nsite), a non-finite entry, a zero vec, a model without geoms),
+ * uploads the tables and (re)allocates the results; a second call replaces the first.  mjb_rays_cast reads derived fields, so like mjb_get
+ * it is MJB_EINVAL unless the frame workspace is current for every env (after mjb_forward / mjb_step1 / mjb_step2, or a fused step with
+ * keep_frame); it runs on the batch's stream behind the launch that produced the frame.  No reference counterpart (its depth images are
+ * OpenGL renderings). */
+int mjb_rays_configure(mjb_batch *b, int nray, const int *site /*[nray], -1 = world frame*/,
+                       const double *pnt /*[nray][3], NULL = the frame's origin*/, const double *vec /*[nray][3]*/,
+                       const unsigned char *exclude_own_body /*[nray], NULL = all 1; ignored for site -1*/,
+                       const unsigned char *geom_mask /*[ngeom], NULL = visible geoms*/);
+int mjb_rays_cast(mjb_batch *b);                       /* asynchronous on the batch's stream */
+int mjb_rays_get(mjb_batch *b, int env_lo, int env_hi, double *dist, int *geomid);  /* synchronises; either pointer may be NULL */
+void *mjb_rays_device_ptr(mjb_batch *b, int which);    /* 0: dist [nenv][nray] double, 1: geomid [nenv][nray] int */
+int mjb_rays_count(const mjb_batch *b);
+
 /* ---- collision-function overrides (MujocoEnv::registerCollisionFunction, /root/reference mujoco_ros/src/mujoco_env.cpp:163-176) ----
  * The reference lets a plugin replace MuJoCo's pair function for a geom-type pair (the mjCOLLISIONFUNC table) with a host
  * callback until the next reload (:950-954).  Host callbacks cannot run inside the fused device step, so the override names

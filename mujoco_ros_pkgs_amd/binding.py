@@ -195,6 +195,11 @@ def load_library(path=None):
         "mjb_sensor_pack": (ci, [vp, C.c_uint64]),
         "mjb_sensor_get": (ci, [vp, ci, ci, ci, C.POINTER(C.c_float)]),
         "mjb_sensor_device_ptr": (vp, [vp, ci]),
+        "mjb_rays_configure": (ci, [vp, ci, C.POINTER(ci), C.POINTER(cd), C.POINTER(cd), C.POINTER(C.c_uint8), C.POINTER(C.c_uint8)]),
+        "mjb_rays_cast": (ci, [vp]),
+        "mjb_rays_get": (ci, [vp, ci, ci, C.POINTER(cd), C.POINTER(ci)]),
+        "mjb_rays_device_ptr": (vp, [vp, ci]),
+        "mjb_rays_count": (ci, [vp]),
         "mjb_step": (ci, [vp, ci]),
         "mjb_step1": (ci, [vp]),
         "mjb_step2": (ci, [vp]),

@@ -43,6 +43,11 @@ struct HwSimBufs {  // device-side DefaultRobotHWSim (mjb_hwsim_*): what HwSim p
 	DevBuf<double> pid;    // [nenv][n][2]
 	DevBuf<double> cad;    // [nenv][2 + 2 n] controller cadence (mjb_hwsim_set_period)
 };
+struct RayBufs {  // batched ray casting (mjb_rays_*): the ray / mask table of mjb_launch_rays and the results
+	DevBuf<double> tab;
+	DevBuf<double> dist;
+	DevBuf<int> geomid;
+};
 struct SensorBufs {  // sensors-plugin equivalent (mjb_sensor_*): device copy of the noise models and the packed messages
 	DevBuf<int> flag;
 	DevBuf<double> mean, sigma;
@@ -99,6 +104,8 @@ struct mjb_batch {
 	std::vector<double> sens_mean, sens_sigma;
 	SensorBufs sens;
 	bool sens_dirty = true, sens_packed = false;
+	RayBufs rays;                     // mjb_rays_configure
+	int nray = 0;                     // rays per env of that configuration (0: none yet)
 	DevBuf<double> pack_dev;          // staging block of mjb_get_packed / mjb_set_packed
 	size_t pack_cap = 0;
 	DevBuf<double> env_geom_size;
@@ -2292,6 +2299,79 @@ void *mjb_sensor_device_ptr(mjb_batch *b, int which)
 	if (!b || which < 0 || which > 1 || sensor_buffers(b) != MJB_OK) return nullptr;
 	return which == 0 ? (void *)b->sens.value.get() : (void *)b->sens.truth.get();
 }
+
+// ---- batched ray casting (kernel in mjb_ray.hip) ----
+int mjb_rays_configure(mjb_batch *b, int nray, const int *site, const double *pnt, const double *vec, const unsigned char *exclude_own_body, const unsigned char *geom_mask)
+{
+	if (!b) return fail(MJB_EINVAL, "null batch");
+	const mjb_model_desc &h = b->model->h;
+	if (nray < 1 || !site || !vec) return fail(MJB_EINVAL, "mjb_rays_configure: nray must be at least 1, with a site and a vec per ray");
+	if (h.ngeom < 1) return fail(MJB_EINVAL, "mjb_rays_configure: the model has no geoms");
+	// the table of mjb_launch_rays: pnt[3][nray] | vec[3][nray] as doubles, then {site, exclude own body}[nray] and visible[ngeom] as ints
+	const size_t n = (size_t)nray, nints = 2 * n + (size_t)h.ngeom, ndoubles = 6 * n + (nints + 1) / 2;
+	std::vector<double> tab(ndoubles, 0.0);
+	int *itab = reinterpret_cast<int *>(tab.data() + 6 * n);
+	for (size_t r = 0; r < n; r++) {
+		if (site[r] < -1 || site[r] >= h.nsite) return fail(MJB_EINVAL, "mjb_rays_configure: ray %zu: site %d outside [-1, %d)", r, site[r], h.nsite);
+		for (int k = 0; k < 3; k++) {
+			const double p = pnt ? pnt[3 * r + k] : 0.0, v = vec[3 * r + k];
+			if (!std::isfinite(p) || !std::isfinite(v)) return fail(MJB_EINVAL, "mjb_rays_configure: ray %zu: non-finite pnt or vec", r);
+			tab[(size_t)k * n + r] = p;
+			tab[(size_t)(3 + k) * n + r] = v;
+		}
+		if (vec[3 * r] == 0 && vec[3 * r + 1] == 0 && vec[3 * r + 2] == 0) return fail(MJB_EINVAL, "mjb_rays_configure: ray %zu: vec is zero", r);
+		itab[2 * r] = site[r];
+		itab[2 * r + 1] = (site[r] >= 0 && (!exclude_own_body || exclude_own_body[r])) ? 1 : 0;
+	}
+	for (int g = 0; g < h.ngeom; g++) itab[2 * n + g] = geom_mask ? (geom_mask[g] != 0) : (h.geom_rgba[4 * g + 3] != 0);
+	HIP_TRY(hipSetDevice(b->device));
+	HIP_TRY(hipStreamSynchronize(b->stream.get()));  // (a cast of the previous configuration may still read what goes now)
+	RayBufs rb;
+	if (!rb.tab.alloc(ndoubles) || !rb.dist.alloc_zeroed((size_t)b->nenv * n) || !rb.geomid.alloc_zeroed((size_t)b->nenv * n))
+		return fail(MJB_ENOMEM, "mjb_rays_configure: allocation failed for %d envs x %d rays", b->nenv, nray);
+	HIP_TRY(hipMemcpy(rb.tab.get(), tab.data(), ndoubles * sizeof(double), hipMemcpyHostToDevice));
+	b->rays = std::move(rb);
+	b->nray = nray;
+	return MJB_OK;
+}
+
+int mjb_rays_cast(mjb_batch *b)
+{
+	if (!b) return fail(MJB_EINVAL, "null batch");
+	if (b->nray < 1) return fail(MJB_EINVAL, "mjb_rays_cast before mjb_rays_configure");
+	if (!b->frame_valid || !b->st.frame_ws || b->frame_hi < b->nenv)
+		return fail(MJB_EINVAL, "mjb_rays_cast reads the geom and site poses of every env: only after mjb_forward / mjb_step1 / mjb_step2, or a fused step with keep_frame");
+	HIP_TRY(hipSetDevice(b->device));
+	if (int rc = join_rest(b)) return rc;
+	if (int rc = sync_params(b)) return rc;
+	const int rc = mjb_launch_rays(b->params_dev.get(), b->rays.tab.get(), b->nenv, b->nray, b->rays.dist.get(), b->rays.geomid.get(), b->stream.get());
+	if (rc != 0) return fail(MJB_ENODEVICE, "ray launch failed: %s", hipGetErrorString((hipError_t)rc));
+	return MJB_OK;
+}
+
+int mjb_rays_get(mjb_batch *b, int env_lo, int env_hi, double *dist, int *geomid)
+{
+	if (!b) return fail(MJB_EINVAL, "null batch");
+	if (b->nray < 1) return fail(MJB_EINVAL, "mjb_rays_get before mjb_rays_configure");
+	if (env_lo < 0 || env_hi > b->nenv || env_lo > env_hi) return fail(MJB_ERANGE, "env range [%d,%d) outside [0,%d)", env_lo, env_hi, b->nenv);
+	const size_t n = (size_t)(env_hi - env_lo) * b->nray, off = (size_t)env_lo * b->nray;
+	HIP_TRY(hipSetDevice(b->device));
+	HIP_TRY(hipStreamSynchronize(b->stream.get()));
+	if (dist && n) HIP_TRY(hipMemcpy(dist, b->rays.dist.get() + off, n * sizeof(double), hipMemcpyDeviceToHost));
+	if (geomid && n) HIP_TRY(hipMemcpy(geomid, b->rays.geomid.get() + off, n * sizeof(int), hipMemcpyDeviceToHost));
+	return MJB_OK;
+}
+
+void *mjb_rays_device_ptr(mjb_batch *b, int which)
+{
+	if (!b || which < 0 || which > 1 || b->nray < 1) {
+		fail(MJB_EINVAL, "mjb_rays_device_ptr: bad argument, or no mjb_rays_configure yet");
+		return nullptr;
+	}
+	return which == 0 ? (void *)b->rays.dist.get() : (void *)b->rays.geomid.get();
+}
+
+int mjb_rays_count(const mjb_batch *b) { return b ? b->nray : fail(MJB_EINVAL, "null batch"); }
 
 int mjb_time_steps(mjb_batch *b, int nsteps, int nlaunch, double *ms_per_launch)
 {

@@ -429,6 +429,10 @@ int mjb_smooth_match(const mjb_model_desc *h);  // index of the compiled-in SmTo
 const char *mjb_smooth_name(int topo);
 int mjb_launch_smooth(const KernelParams *Pdev, int topo, int env_lo, int env_hi, unsigned int step, int flags, void *stream);
 int mjb_launch_cstep(const KernelParams *Pdev, const FrameLayout &L, int env_lo, int env_hi, int envs_per_block, int flags, void *stream);
+// batched ray casting (mjb_ray.hip): every ray of the table `tab` (pnt[3][nray] | vec[3][nray] as doubles, then {site, exclude own body}[nray] and visible[ngeom] as
+// ints) against the geoms of every env, from the poses in DevState::frame_ws; results [nenv][nray].  The kernel stages geoms through LDS MJB_RAY_TILE records at a time
+#define MJB_RAY_TILE 64
+int mjb_launch_rays(const KernelParams *Pdev, const double *tab, int nenv, int nray, double *dist, int *geomid, void *stream);
 // sensors-plugin equivalent (mjb_sensor_pack.hip)
 int mjb_launch_sensor_pack(const KernelParams *Pdev, int nenv, int nsensor, const int *set_flag, const double *mean,
                            const double *sigma, unsigned long long seed, long long env_offset, unsigned int step,

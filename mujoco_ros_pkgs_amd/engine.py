@@ -32,6 +32,44 @@ def device_count():
     return _lib().mjb_device_count()
 
 
+def pinhole_rays(width, height, fovy_deg):
+    """Ray directions of a width x height pinhole image in MuJoCo's camera frame (the camera looks along -z, +y is up, +x is right): returns
+    (vec [height*width, 3] unit vectors, cosz [height*width] = -vec_z).  Rows run from the top, pixels are sampled at their centres, and fovy_deg is the
+    vertical angle between the outer pixel edges.  With dist from Batch.cast_rays, a z-depth image is dist * cosz wherever dist >= 0.  Plain numpy."""
+    width, height = int(width), int(height)
+    if width < 1 or height < 1 or not 0.0 < float(fovy_deg) < 180.0:
+        raise ValueError("pinhole_rays: width and height must be at least 1, fovy_deg inside (0, 180)")
+    half_h = np.tan(np.radians(float(fovy_deg)) / 2)
+    half_w = half_h * width / height
+    x = ((np.arange(width) + 0.5) / width * 2 - 1) * half_w
+    y = (1 - (np.arange(height) + 0.5) / height * 2) * half_h
+    v = np.empty((height, width, 3))
+    v[..., 0] = x[None, :]
+    v[..., 1] = y[:, None]
+    v[..., 2] = -1.0
+    v /= np.linalg.norm(v, axis=-1, keepdims=True)
+    v = v.reshape(-1, 3)
+    return v, -v[:, 2]
+
+
+def lidar_rays(n_azimuth, elevations_deg=(0.0,), azimuth_range_deg=(0.0, 360.0)):
+    """Unit ray directions of a lidar in the site's frame: n_azimuth rays per elevation ring, azimuth counter-clockwise from +x in the x-y plane and running
+    fastest, elevation positive towards +z.  The end of the azimuth range is left out when the range is a full turn, included otherwise.  Returns
+    [len(elevations_deg) * n_azimuth, 3].  Plain numpy."""
+    n = int(n_azimuth)
+    if n < 1:
+        raise ValueError("lidar_rays: n_azimuth must be at least 1")
+    a0, a1 = (float(a) for a in azimuth_range_deg)
+    full = abs(abs(a1 - a0) - 360.0) < 1e-9
+    az = np.radians(np.linspace(a0, a1, n, endpoint=not full)) if n > 1 else np.radians(np.array([a0]))
+    el = np.radians(np.atleast_1d(np.asarray(elevations_deg, dtype=np.float64)))
+    v = np.empty((el.size, n, 3))
+    v[..., 0] = np.cos(el)[:, None] * np.cos(az)[None, :]
+    v[..., 1] = np.cos(el)[:, None] * np.sin(az)[None, :]
+    v[..., 2] = np.sin(el)[:, None]
+    return v.reshape(-1, 3)
+
+
 class CompiledModel:
     def __init__(self, model):
         self.model = model
@@ -318,6 +356,56 @@ class Batch:
         _check(self.lib.mjb_sensor_get(self.ptr, 0 if which == "value" else 1, lo, hi, out.ctypes.data_as(C.POINTER(C.c_float))),
                "mjb_sensor_get")
         return out
+
+    # ---- batched ray casting (mjb_rays_*) ----
+    def set_rays(self, site, vec, pnt=None, exclude_own_body=True, geom_mask=None):
+        """The ray set every env casts (mjb_rays_configure): vec [nray, 3] (and pnt [nray, 3], default the origin) in the frame of `site` -- a site id, a
+        site name, or one of either per ray; -1 = the world frame.  vec is not normalised: distances come in units of |vec|.  exclude_own_body (a bool or one
+        per ray) skips the geoms of the site's body; geom_mask [ngeom] (0 = skip) replaces the default rule, which skips geoms with alpha 0.  A second call
+        replaces the first.  pinhole_rays / lidar_rays build common patterns."""
+        vec = np.ascontiguousarray(np.asarray(vec, dtype=np.float64).reshape(-1, 3))
+        n = vec.shape[0]
+        sites = [site] * n if isinstance(site, (str, int, np.integer)) else list(site)
+        if len(sites) != n:
+            raise ValueError(f"set_rays: {len(sites)} sites for {n} rays")
+        names = self.cm.model["names"]["site"] if any(isinstance(s, str) for s in sites) else ()
+        unknown = [s for s in sites if isinstance(s, str) and s not in names]
+        if unknown:
+            raise ValueError(f"set_rays: no site named {unknown[0]!r}")
+        sid = np.ascontiguousarray([names.index(s) if isinstance(s, str) else int(s) for s in sites], dtype=np.int32)
+        pd, pb = C.POINTER(C.c_double), C.POINTER(C.c_uint8)
+        p = None if pnt is None else np.ascontiguousarray(np.broadcast_to(np.asarray(pnt, dtype=np.float64), (n, 3)))
+        ex = np.ascontiguousarray(np.broadcast_to(np.asarray(exclude_own_body, dtype=bool), (n,)), dtype=np.uint8)
+        gm = None
+        if geom_mask is not None:
+            gm = np.ascontiguousarray(np.asarray(geom_mask).reshape(-1) != 0, dtype=np.uint8)
+            if gm.size != int(self.cm.model["ngeom"]):
+                raise ValueError(f"set_rays: geom_mask has {gm.size} entries, the model {int(self.cm.model['ngeom'])} geoms")
+        _check(self.lib.mjb_rays_configure(self.ptr, n, sid.ctypes.data_as(C.POINTER(C.c_int)), None if p is None else p.ctypes.data_as(pd), vec.ctypes.data_as(pd),
+                                           ex.ctypes.data_as(pb), None if gm is None else gm.ctypes.data_as(pb)), "mjb_rays_configure")
+
+    def cast_rays_async(self):
+        """Cast the configured rays of every env on the batch's stream (mjb_rays_cast); needs current frames: forward(), step1() / step2(), or step() with
+        set_keep_frame().  The results stay on the device (rays_device_ptr) until cast_rays or the next cast."""
+        _check(self.lib.mjb_rays_cast(self.ptr), "mjb_rays_cast")
+
+    def cast_rays(self, lo=0, hi=None):
+        """Cast, wait, and return (dist float64 [hi-lo, nray], geomid int32 [hi-lo, nray]) of envs [lo, hi): the distance to the nearest geom along each ray in
+        units of |vec| and that geom's id, -1 and -1 for a miss."""
+        hi = self.nenv if hi is None else hi
+        self.cast_rays_async()
+        n = int(self.lib.mjb_rays_count(self.ptr))
+        dist = np.empty((hi - lo, n), dtype=np.float64)
+        gid = np.empty((hi - lo, n), dtype=np.int32)
+        _check(self.lib.mjb_rays_get(self.ptr, lo, hi, dist.ctypes.data_as(C.POINTER(C.c_double)), gid.ctypes.data_as(C.POINTER(C.c_int))), "mjb_rays_get")
+        return dist, gid
+
+    def rays_device_ptr(self, which):
+        """Device address of the ray results: 0 = dist [nenv, nray] float64, 1 = geomid [nenv, nray] int32 (mjb_rays_device_ptr)."""
+        p = self.lib.mjb_rays_device_ptr(self.ptr, int(which))
+        if not p:
+            raise EngineError(self.lib.mjb_last_error().decode())
+        return p
 
     def set_keep_frame(self, on=True):
         """Fused step() also leaves the derived fields of its last step readable through get()."""
