@@ -562,6 +562,39 @@ int mjb_rays_get(mjb_batch *b, int env_lo, int env_hi, double *dist, int *geomid
 void *mjb_rays_device_ptr(mjb_batch *b, int which);    /* 0: dist [nenv][nray] double, 1: geomid [nenv][nray] int */
 int mjb_rays_count(const mjb_batch *b);
 
+/* ---- batched Jacobians: mj_jacSite / mj_jacBody / mj_jacBodyCom / mj_jacGeom and mj_solveM for every env at once ----
+ * Point k is fixed to the body of its object and sits at the object's world position plus its world rotation times pnt[k]: a site
+ * (site_xpos, site_xmat, site_bodyid), a body (xpos, xmat), a body's inertial frame (xipos, ximat) or a geom (geom_xpos, geom_xmat,
+ * geom_bodyid), all read from the frame workspace.  A point on the world body is legal; every output of it is zero.
+ * Results are fp64, env-major and world-oriented, translational rows first (MuJoCo's jacp, then jacr):
+ *   MJB_JAC_OUT_J       [nenv][npoint][6][nv]  column d = (cdof_ang x (p - subtree_com[root]) + cdof_lin, cdof_ang) when dof d moves the body,
+ *                                              exactly 0.0 otherwise -- the arithmetic of the site transmission's moment arms
+ *   MJB_JAC_OUT_MINVJT  [nenv][npoint][6][nv]  row r = M^-1 J[r]', mj_solveM on the frame's L'DL factor of qM (qLD / qLDiagInv as mjb_get
+ *                                              serves them: the factor of M, never of the M + h B of implicit joint damping)
+ *   MJB_JAC_OUT_AINV    [nenv][npoint][6][6]   J M^-1 J' of the point, the inverse operational-space inertia; summed in a fixed order over
+ *                                              the half-solved rows, so it equals its transpose to the bit.  No blocks between two points.
+ *   MJB_JAC_OUT_VEL     [nenv][npoint][6]      J qvel, LINEAR then angular -- mj_objectVelocity orders its result the other way round
+ *                                              (angular first), and can rotate it into the object's frame; this one stays in world axes.
+ * No result depends on the shape of the launch.
+ * mjb_jac_configure validates (MJB_EINVAL: npoint < 1, an unknown object type, an id out of range, a non-finite pnt, outputs 0 or with
+ * unknown bits, a model with nv == 0), uploads the point table and (re)allocates the requested outputs only; a second call replaces the
+ * first.  mjb_jac_eval reads derived fields, so like mjb_get it is MJB_EINVAL unless the frame workspace is current for every env (after
+ * mjb_forward / mjb_step1 / mjb_step2, or a fused step with keep_frame); it runs on the batch's stream behind the launch that produced
+ * the frame.  It is MJB_EINVAL, too, once qpos or a mocap pose has been written through mjb_set / mjb_set_many / mjb_set_packed and no such call
+ * has followed: mjb_get goes on serving the old frame (mjData's rule), but a Jacobian is applied to the state as it is now.  Only
+ * writes through those three calls are seen: a caller that writes qpos through mjb_device_ptr calls mjb_forward itself before it evaluates.  VEL multiplies J with
+ * the batch's qvel as it is when the evaluation runs.  After a step the frame holds the step's forward pass, that is the poses BEFORE the integration, as mjData does after
+ * mj_step: J then belongs to site_xpos of that same frame, not to the new qpos.  mjb_jac_get / mjb_jac_device_ptr of an output that was not
+ * configured: MJB_EINVAL / NULL. */
+enum { MJB_JAC_SITE = 0, MJB_JAC_BODY = 1, MJB_JAC_BODYCOM = 2, MJB_JAC_GEOM = 3 };   /* mj_jacSite / mj_jacBody / mj_jacBodyCom / mj_jacGeom */
+enum { MJB_JAC_OUT_J = 1, MJB_JAC_OUT_MINVJT = 2, MJB_JAC_OUT_AINV = 4, MJB_JAC_OUT_VEL = 8 };
+int mjb_jac_configure(mjb_batch *b, int npoint, const int *objtype /*[npoint] MJB_JAC_SITE ...*/,const int *objid /*[npoint]*/,
+                      const double *pnt /*[npoint][3] offset in the object's own frame, NULL = 0*/, int outputs /*MJB_JAC_OUT_* bits*/);
+int mjb_jac_eval(mjb_batch *b);                                   /* asynchronous on the batch's stream */
+int mjb_jac_get(mjb_batch *b, int which, int env_lo, int env_hi, double *host);   /* synchronises; which = one MJB_JAC_OUT_* bit */
+void *mjb_jac_device_ptr(mjb_batch *b, int which);                /* which = one MJB_JAC_OUT_* bit */
+int mjb_jac_count(const mjb_batch *b);                            /* points per env of the configuration, 0: none yet */
+
 /* ---- collision-function overrides (MujocoEnv::registerCollisionFunction, /root/reference mujoco_ros/src/mujoco_env.cpp:163-176) ----
  * The reference lets a plugin replace MuJoCo's pair function for a geom-type pair (the mjCOLLISIONFUNC table) with a host
  * callback until the next reload (:950-954).  Host callbacks cannot run inside the fused device step, so the override names

@@ -200,6 +200,11 @@ def load_library(path=None):
         "mjb_rays_get": (ci, [vp, ci, ci, C.POINTER(cd), C.POINTER(ci)]),
         "mjb_rays_device_ptr": (vp, [vp, ci]),
         "mjb_rays_count": (ci, [vp]),
+        "mjb_jac_configure": (ci, [vp, ci, C.POINTER(ci), C.POINTER(ci), C.POINTER(cd), ci]),
+        "mjb_jac_eval": (ci, [vp]),
+        "mjb_jac_get": (ci, [vp, ci, ci, ci, C.POINTER(cd)]),
+        "mjb_jac_device_ptr": (vp, [vp, ci]),
+        "mjb_jac_count": (ci, [vp]),
         "mjb_step": (ci, [vp, ci]),
         "mjb_step1": (ci, [vp]),
         "mjb_step2": (ci, [vp]),

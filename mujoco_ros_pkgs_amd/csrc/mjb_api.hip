@@ -16,6 +16,7 @@
 #include <vector>
 
 #include "mjb_dev.h"
+#include "mjb_jac.h"
 #include "mjb_model.h"
 #include "mjb_resources.h"
 
@@ -47,6 +48,10 @@ struct RayBufs {  // batched ray casting (mjb_rays_*): the ray / mask table of m
 	DevBuf<double> tab;
 	DevBuf<double> dist;
 	DevBuf<int> geomid;
+};
+struct JacBufs {  // batched Jacobians (mjb_jac_*): the point table of mjb_launch_jac and the outputs that were asked for (the others stay empty)
+	DevBuf<double> tab;
+	DevBuf<double> J, MinvJT, Ainv, vel;
 };
 struct SensorBufs {  // sensors-plugin equivalent (mjb_sensor_*): device copy of the noise models and the packed messages
 	DevBuf<int> flag;
@@ -106,6 +111,10 @@ struct mjb_batch {
 	bool sens_dirty = true, sens_packed = false;
 	RayBufs rays;                     // mjb_rays_configure
 	int nray = 0;                     // rays per env of that configuration (0: none yet)
+	JacBufs jac;                      // mjb_jac_configure
+	int njac = 0, jac_outputs = 0;    // points per env of that configuration (0: none yet), its MJB_JAC_OUT_* bits
+	bool pose_written = false;        // qpos or a mocap pose has been written through mjb_set* since the frame workspace was last made current: mjb_get still serves
+	                                  // the old frame (mjData's rule); mjb_jac_eval, whose results a controller applies to the NEW state, refuses it
 	DevBuf<double> pack_dev;          // staging block of mjb_get_packed / mjb_set_packed
 	size_t pack_cap = 0;
 	DevBuf<double> env_geom_size;
@@ -146,6 +155,9 @@ struct mjb_batch {
 };
 
 namespace {
+
+// a state field the poses of the frame are computed from (mjb_batch::pose_written)
+bool pose_field(int field) { return field == MJB_F_qpos || field == MJB_F_mocap_pos || field == MJB_F_mocap_quat; }
 
 // the kernels' raw view of one of the batch's buffers (a member of b->st or b->hw): assigned here, so that the parameter block is uploaded again
 template <typename V, typename P> void set_view(mjb_batch *b, V &view, P p)
@@ -936,6 +948,7 @@ int mjb_step(mjb_batch *b, int nsteps)
 		b->steps_taken += (unsigned long long)nsteps;
 		b->frame_valid = b->st.keep_frame != 0;
 		b->frame_hi = b->nenv;
+		b->pose_written = false;
 	}
 	return rc;
 }
@@ -965,6 +978,7 @@ static int forward_whole(mjb_batch *b, int mode)
 	if (rc == MJB_OK) {
 		b->frame_valid = true;
 		b->frame_hi = b->nenv;
+		b->pose_written = false;
 	}
 	return rc;
 }
@@ -1009,6 +1023,7 @@ int mjb_step1_prefix(mjb_batch *b, int ncb)
 	if (rc == MJB_OK) {
 		b->frame_valid = true;
 		b->frame_hi = ncb;
+		b->pose_written = false;
 	}
 	return rc;
 }
@@ -1082,6 +1097,7 @@ int mjb_step21_prefix(mjb_batch *b, int ncb)
 		b->split_rest_done = false;
 		b->frame_valid = true;
 		b->frame_hi = ncb;
+		b->pose_written = false;
 	}
 	return rc;
 }
@@ -1239,6 +1255,7 @@ int mjb_set(mjb_batch *b, int field, int env_lo, int env_hi, const double *host)
 			b->params_dirty = true;
 		}
 		if (field == MJB_F_qpos && env_lo == 0 && env_hi == b->nenv) b->rowstat_ever = false;  // (wide-frame policy: a new workload)
+		if (pose_field(field)) b->pose_written = true;
 		return MJB_OK;
 	}
 	if (field != MJB_F_qfrc_passive)
@@ -1334,6 +1351,7 @@ int mjb_set_many(mjb_batch *b, int n, const int *fields, int env_lo, int env_hi,
 		if (kFields[field].kind == 0) {
 			err = hipMemcpyAsync(state_ptr(b, field) + (size_t)env_lo * sz, host[k], (size_t)(env_hi - env_lo) * sz * sizeof(double),
 			                     hipMemcpyHostToDevice, b->stream.get());
+			if (pose_field(field)) b->pose_written = true;
 			if (field == MJB_F_xfrc_applied) b->le_xfrc_stale = true;
 			if (field == MJB_F_xfrc_applied && !b->st.use_xfrc) {
 				b->st.use_xfrc = 1;
@@ -1390,6 +1408,7 @@ static int packed_transfer(mjb_batch *b, int n, const int *fields, int env_lo, i
 	PackArgs a{};
 	long long total = 0;
 	int maxdim = 1;
+	bool writes_pose = false;
 	for (int k = 0; k < n; k++) {
 		const int field = fields[k];
 		int rc = check_range(b, field, env_lo, env_hi);
@@ -1413,6 +1432,7 @@ static int packed_transfer(mjb_batch *b, int n, const int *fields, int env_lo, i
 		total += (long long)(env_hi - env_lo) * sz;
 		if (sz > 0) a.n++;
 		if (sz > maxdim) maxdim = sz;
+		if (!to_host && sz > 0 && pose_field(field)) writes_pose = true;
 		if (!to_host && field == MJB_F_xfrc_applied) b->le_xfrc_stale = true;
 		if (!to_host && field == MJB_F_xfrc_applied && !b->st.use_xfrc) {
 			b->st.use_xfrc = 1;
@@ -1420,6 +1440,7 @@ static int packed_transfer(mjb_batch *b, int n, const int *fields, int env_lo, i
 		}
 	}
 	if (total == 0 || env_lo == env_hi) return MJB_OK;
+	if (writes_pose) b->pose_written = true;  // (every field has been checked: the write goes ahead)
 	a.nenv = env_hi - env_lo;
 	if ((long long)b->pack_cap < total) {
 		if (!b->pack_dev.alloc_zeroed((size_t)total)) {
@@ -2372,6 +2393,117 @@ void *mjb_rays_device_ptr(mjb_batch *b, int which)
 }
 
 int mjb_rays_count(const mjb_batch *b) { return b ? b->nray : fail(MJB_EINVAL, "null batch"); }
+
+// ---- batched Jacobians (kernel in mjb_jac.hip) ----
+static const int kJacOutputs = MJB_JAC_OUT_J | MJB_JAC_OUT_MINVJT | MJB_JAC_OUT_AINV | MJB_JAC_OUT_VEL;
+// the buffer of one output bit and its doubles per (env, point); NULL: not one bit, or not configured
+static DevBuf<double> *jac_output(mjb_batch *b, int which, size_t *per_point)
+{
+	const size_t nv = (size_t)b->model->h.nv;
+	if (!(which & b->jac_outputs)) return nullptr;
+	switch (which) {
+	case MJB_JAC_OUT_J: *per_point = 6 * nv; return &b->jac.J;
+	case MJB_JAC_OUT_MINVJT: *per_point = 6 * nv; return &b->jac.MinvJT;
+	case MJB_JAC_OUT_AINV: *per_point = 36; return &b->jac.Ainv;
+	case MJB_JAC_OUT_VEL: *per_point = 6; return &b->jac.vel;
+	default: return nullptr;
+	}
+}
+
+int mjb_jac_configure(mjb_batch *b, int npoint, const int *objtype, const int *objid, const double *pnt, int outputs)
+{
+	if (!b) return fail(MJB_EINVAL, "null batch");
+	const mjb_model_desc &h = b->model->h;
+	if (npoint < 1 || !objtype || !objid) return fail(MJB_EINVAL, "mjb_jac_configure: npoint must be at least 1, with an object type and an id per point");
+	if (outputs == 0 || (outputs & ~kJacOutputs)) return fail(MJB_EINVAL, "mjb_jac_configure: outputs 0x%x: at least one of the MJB_JAC_OUT_* bits and no other", (unsigned)outputs);
+	if (h.nv < 1) return fail(MJB_EINVAL, "mjb_jac_configure: the model has no dofs");
+	// the table of mjb_launch_jac (mjb_jac.h): pnt[npoint][3] as doubles, then one JacPoint per point
+	const size_t n = (size_t)npoint, ndoubles = 3 * n + n * (sizeof(JacPoint) / sizeof(double));
+	std::vector<double> tab(ndoubles, 0.0);
+	JacPoint *rec = reinterpret_cast<JacPoint *>(tab.data() + 3 * n);
+	for (size_t k = 0; k < n; k++) {
+		const int ty = objtype[k], id = objid[k];
+		int count, body;
+		switch (ty) {
+		case MJB_JAC_SITE: count = h.nsite; break;
+		case MJB_JAC_BODY: case MJB_JAC_BODYCOM: count = h.nbody; break;
+		case MJB_JAC_GEOM: count = h.ngeom; break;
+		default: return fail(MJB_EINVAL, "mjb_jac_configure: point %zu: unknown object type %d", k, ty);
+		}
+		if (id < 0 || id >= count) return fail(MJB_EINVAL, "mjb_jac_configure: point %zu: id %d outside [0, %d)", k, id, count);
+		body = ty == MJB_JAC_SITE ? h.site_bodyid[id] : (ty == MJB_JAC_GEOM ? h.geom_bodyid[id] : id);
+		for (int c = 0; c < 3; c++) {
+			const double p = pnt ? pnt[3 * k + c] : 0.0;
+			if (!std::isfinite(p)) return fail(MJB_EINVAL, "mjb_jac_configure: point %zu: non-finite pnt", k);
+			tab[3 * k + c] = p;
+		}
+		rec[k].type = ty;
+		rec[k].id = id;
+		rec[k].body = body;
+		rec[k].root = h.body_rootid[body];
+		rec[k].mask[0] = (unsigned int)b->model->body_dofmask[2 * body];
+		rec[k].mask[1] = (unsigned int)b->model->body_dofmask[2 * body + 1];
+	}
+	HIP_TRY(hipSetDevice(b->device));
+	HIP_TRY(hipStreamSynchronize(b->stream.get()));  // (an evaluation of the previous configuration may still read what goes now)
+	JacBufs jb;
+	const size_t np = (size_t)b->nenv * n, nv = (size_t)h.nv;
+	if (!jb.tab.alloc(ndoubles) || ((outputs & MJB_JAC_OUT_J) && !jb.J.alloc_zeroed(np * 6 * nv)) || ((outputs & MJB_JAC_OUT_MINVJT) && !jb.MinvJT.alloc_zeroed(np * 6 * nv)) ||
+	    ((outputs & MJB_JAC_OUT_AINV) && !jb.Ainv.alloc_zeroed(np * 36)) || ((outputs & MJB_JAC_OUT_VEL) && !jb.vel.alloc_zeroed(np * 6)))
+		return fail(MJB_ENOMEM, "mjb_jac_configure: allocation failed for %d envs x %d points", b->nenv, npoint);
+	HIP_TRY(hipMemcpy(jb.tab.get(), tab.data(), ndoubles * sizeof(double), hipMemcpyHostToDevice));
+	b->jac = std::move(jb);
+	b->njac = npoint;
+	b->jac_outputs = outputs;
+	return MJB_OK;
+}
+
+int mjb_jac_eval(mjb_batch *b)
+{
+	if (!b) return fail(MJB_EINVAL, "null batch");
+	if (b->njac < 1) return fail(MJB_EINVAL, "mjb_jac_eval before mjb_jac_configure");
+	if (!b->frame_valid || !b->st.frame_ws || b->frame_hi < b->nenv)
+		return fail(MJB_EINVAL, "mjb_jac_eval reads cdof, the poses and the factor of qM of every env: only after mjb_forward / mjb_step1 / mjb_step2, or a fused step with keep_frame");
+	if (b->pose_written)
+		return fail(MJB_EINVAL, "mjb_jac_eval: qpos or a mocap pose has been written since the frame was computed, its Jacobians belong to the old poses: only after mjb_forward / mjb_step1 / "
+		                        "mjb_step2, or a fused step with keep_frame");
+	HIP_TRY(hipSetDevice(b->device));
+	if (int rc = join_rest(b)) return rc;
+	if (int rc = sync_params(b)) return rc;
+	const int rc = mjb_launch_jac(b->params_dev.get(), b->jac.tab.get(), b->nenv, b->njac, b->model->h.nv, b->model->h.nM, b->jac.J.get(), b->jac.MinvJT.get(), b->jac.Ainv.get(),
+	                              b->jac.vel.get(), b->stream.get());
+	if (rc != 0) return fail(MJB_ENODEVICE, "Jacobian launch failed: %s", hipGetErrorString((hipError_t)rc));
+	return MJB_OK;
+}
+
+int mjb_jac_get(mjb_batch *b, int which, int env_lo, int env_hi, double *host)
+{
+	if (!b) return fail(MJB_EINVAL, "null batch");
+	if (b->njac < 1) return fail(MJB_EINVAL, "mjb_jac_get before mjb_jac_configure");
+	size_t per_point = 0;
+	DevBuf<double> *buf = jac_output(b, which, &per_point);
+	if (!buf) return fail(MJB_EINVAL, "mjb_jac_get: output 0x%x is not one MJB_JAC_OUT_* bit of the configuration (0x%x)", (unsigned)which, (unsigned)b->jac_outputs);
+	if (env_lo < 0 || env_hi > b->nenv || env_lo > env_hi) return fail(MJB_ERANGE, "env range [%d,%d) outside [0,%d)", env_lo, env_hi, b->nenv);
+	const size_t n = (size_t)(env_hi - env_lo) * b->njac * per_point, off = (size_t)env_lo * b->njac * per_point;
+	if (n && !host) return fail(MJB_EINVAL, "null host buffer");
+	HIP_TRY(hipSetDevice(b->device));
+	HIP_TRY(hipStreamSynchronize(b->stream.get()));
+	if (n) HIP_TRY(hipMemcpy(host, buf->get() + off, n * sizeof(double), hipMemcpyDeviceToHost));
+	return MJB_OK;
+}
+
+void *mjb_jac_device_ptr(mjb_batch *b, int which)
+{
+	size_t per_point = 0;
+	DevBuf<double> *buf = (b && b->njac >= 1) ? jac_output(b, which, &per_point) : nullptr;
+	if (!buf) {
+		fail(MJB_EINVAL, "mjb_jac_device_ptr: bad argument, or an output that mjb_jac_configure was not asked for");
+		return nullptr;
+	}
+	return buf->get();
+}
+
+int mjb_jac_count(const mjb_batch *b) { return b ? b->njac : fail(MJB_EINVAL, "null batch"); }
 
 int mjb_time_steps(mjb_batch *b, int nsteps, int nlaunch, double *ms_per_launch)
 {

@@ -407,6 +407,74 @@ class Batch:
             raise EngineError(self.lib.mjb_last_error().decode())
         return p
 
+    # ---- batched Jacobians (mjb_jac_*) ----
+    _JAC_KINDS = {"site": 0, "body": 1, "bodycom": 2, "geom": 3}   # MJB_JAC_SITE ... of include/mjb.h; a body's names serve "bodycom" too
+    _JAC_OUTPUTS = {"J": 1, "MinvJT": 2, "Ainv": 4, "vel": 8}      # MJB_JAC_OUT_*
+
+    def _jac_shape(self, key, n, npoint):
+        nv = int(self.cm.model["nv"])
+        return {"J": (n, npoint, 6, nv), "MinvJT": (n, npoint, 6, nv), "Ainv": (n, npoint, 6, 6), "vel": (n, npoint, 6)}[key]
+
+    def set_jac_points(self, points, outputs=("J",), pnt=None):
+        """The points whose Jacobians every env evaluates (mjb_jac_configure): `points` is a sequence of site names or ids, or of (kind, name_or_id)
+        pairs with kind one of "site", "body", "bodycom", "geom" (mj_jacSite / mj_jacBody / mj_jacBodyCom / mj_jacGeom).  pnt [npoint, 3], default 0,
+        moves a point off its object's origin, in the object's own frame.  outputs: any of "J", "MinvJT", "Ainv", "vel" -- only these are allocated
+        and computed.  A second call replaces the first."""
+        pts = [("site", p) if isinstance(p, (str, int, np.integer)) else tuple(p) for p in points]
+        n = len(pts)
+        ty, oid = np.zeros(n, np.int32), np.zeros(n, np.int32)
+        for k, (kind, ref) in enumerate(pts):
+            if kind not in self._JAC_KINDS:
+                raise ValueError(f"set_jac_points: unknown kind {kind!r} (site, body, bodycom, geom)")
+            ty[k] = self._JAC_KINDS[kind]
+            if isinstance(ref, str):
+                names = self.cm.model["names"]["body" if kind == "bodycom" else kind]
+                if ref not in names:
+                    raise ValueError(f"set_jac_points: no {kind} named {ref!r}")
+                ref = names.index(ref)
+            oid[k] = int(ref)
+        outs = (outputs,) if isinstance(outputs, str) else tuple(outputs)
+        unknown = [o for o in outs if o not in self._JAC_OUTPUTS]
+        if unknown:
+            raise ValueError(f"set_jac_points: unknown output {unknown[0]!r} (J, MinvJT, Ainv, vel)")
+        bits = 0
+        for o in outs:
+            bits |= self._JAC_OUTPUTS[o]
+        p = None if pnt is None else np.ascontiguousarray(np.broadcast_to(np.asarray(pnt, dtype=np.float64), (n, 3)))
+        pi, pd = C.POINTER(C.c_int), C.POINTER(C.c_double)
+        _check(self.lib.mjb_jac_configure(self.ptr, n, ty.ctypes.data_as(pi), oid.ctypes.data_as(pi), None if p is None else p.ctypes.data_as(pd), bits),
+               "mjb_jac_configure")
+        self._jac_outputs = tuple(k for k in self._JAC_OUTPUTS if bits & self._JAC_OUTPUTS[k])
+
+    def eval_jacobians_async(self):
+        """Evaluate the configured outputs for every env on the batch's stream (mjb_jac_eval); needs current frames: forward(), step1() / step2(), or
+        step() with set_keep_frame() -- after a step the frame, and so J, belongs to the poses before the integration.  The results stay on the device
+        (jac_device_ptr) until jacobians() or the next evaluation."""
+        _check(self.lib.mjb_jac_eval(self.ptr), "mjb_jac_eval")
+
+    def jacobians(self, lo=0, hi=None):
+        """Evaluate, wait, and return the configured outputs of envs [lo, hi) as a dict of float64 arrays: "J" [n, npoint, 6, nv] (rows 0-2 translational,
+        3-5 rotational, world axes), "MinvJT" [n, npoint, 6, nv] (row r = M^-1 J[r]'), "Ainv" [n, npoint, 6, 6] (J M^-1 J') and "vel" [n, npoint, 6]
+        (J qvel: linear, then angular)."""
+        hi = self.nenv if hi is None else hi
+        self.eval_jacobians_async()
+        npoint = int(self.lib.mjb_jac_count(self.ptr))
+        out = {}
+        for key in getattr(self, "_jac_outputs", ()):
+            a = np.empty(self._jac_shape(key, hi - lo, npoint), dtype=np.float64)
+            _check(self.lib.mjb_jac_get(self.ptr, self._JAC_OUTPUTS[key], lo, hi, a.ctypes.data_as(C.POINTER(C.c_double))), "mjb_jac_get")
+            out[key] = a
+        return out
+
+    def jac_device_ptr(self, which):
+        """Device address of one output, by name ("J", "MinvJT", "Ainv", "vel") or MJB_JAC_OUT_* bit: float64, env-major, the shapes of jacobians()."""
+        if isinstance(which, str) and which not in self._JAC_OUTPUTS:
+            raise ValueError(f"jac_device_ptr: unknown output {which!r} (J, MinvJT, Ainv, vel)")
+        p = self.lib.mjb_jac_device_ptr(self.ptr, self._JAC_OUTPUTS[which] if isinstance(which, str) else int(which))
+        if not p:
+            raise EngineError(self.lib.mjb_last_error().decode())
+        return p
+
     def set_keep_frame(self, on=True):
         """Fused step() also leaves the derived fields of its last step readable through get()."""
         _check(self.lib.mjb_set_keep_frame(self.ptr, 1 if on else 0), "mjb_set_keep_frame")
