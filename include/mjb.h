@@ -595,6 +595,47 @@ int mjb_jac_get(mjb_batch *b, int which, int env_lo, int env_hi, double *host); 
 void *mjb_jac_device_ptr(mjb_batch *b, int which);                /* which = one MJB_JAC_OUT_* bit */
 int mjb_jac_count(const mjb_batch *b);                            /* points per env of the configuration, 0: none yet */
 
+/* ---- device-side episode resets (MujocoEnv::resetSim: mj_resetData, then loadInitialJointStates, /root/reference mujoco_ros/src/mujoco_env.cpp:246-264) ----
+ * mjb_reset takes a host mask and can only put an env back to qpos0.  These calls end and restart episodes without leaving the device: ONE launch
+ * on the batch's stream decides for every env whether its episode is over, writes done[nenv] (uint8, 1 / 0) and ndone (one uint32, their sum), and
+ * resets the done envs -- each to a row of an initial-state bank of its own drawing, perturbed by seeded noise.  Nothing synchronises.
+ *   done   mjb_episode_step: the rule fires, or extra_mask_dev[env] != 0.  The rule reads state arrays only:  time_limit > 0 and time >= time_limit,
+ *          or some coordinate k with !(qpos[k] >= lo[k] && qpos[k] <= hi[k]) -- a NaN is outside, an infinite bound is none.
+ *          mjb_episode_reset: mask_dev[env] != 0, NULL = every env; the rule is ignored.
+ *   reset  what mjb_reset does to an env (ctrl, ctrlnoise, qacc_warmstart, qfrc_applied, xfrc_applied, qacc, sensordata, time, energy zeroed, mocap
+ *          poses back to the model's), except that  qpos = integrate_pos(bank_qpos[k], dq),  qvel = bank_qvel[k] + dv,  act = bank_act[k]:
+ *          k = min(ninit - 1, floor(u(2 nv) ninit)) picks the bank row (no bank: qpos0, 0, 0);  dq[d] = lo[d] + (hi[d] - lo[d]) u(d) and
+ *          dv[d] = lo[d] + (hi[d] - lo[d]) u(nv + d) are tangent-space vectors [nv];  integrate_pos adds on hinge and slide joints, right-multiplies
+ *          a ball joint's quaternion by exp(dq) (after normalising it) and moves a free joint's position and quaternion likewise.  Without a qpos
+ *          range the bank row's qpos is copied as it stands, without a qvel range its qvel.  clamp: limited hinge / slide joints are clipped to
+ *          jnt_range afterwards.  episode[env] (uint32, 0 at first) is the draw's episode and is incremented by the reset.
+ *   u(idx) = (w0 + 0.5) / 2^32, w0 the first word of Philox-4x32-10 with counter (genv lo32, genv hi32, episode, 0x80000000 + idx) and the 64-bit
+ *          seed as key, low word first; genv = env_offset + env.  The generator of the ctrl-noise and sensor-noise streams; the top bit of the fourth
+ *          counter word keeps this stream apart from theirs under one seed.  A draw depends on (seed, genv, episode, idx) alone, never on the
+ *          batch's size or the launch.
+ * Stream order: mask_dev / extra_mask_dev are DEVICE pointers to nenv bytes that the kernel reads on the batch's stream; the caller orders their
+ * producer ahead of it (mjb_set_stream lets both run on one stream; a done buffer, mjb_episode_device_ptr(any batch, 0), is a legal mask -- this
+ * batch's own too: the kernel has read an env's mask byte before it writes the env's done byte).
+ * What the rule sees: it is evaluated between launches, on the state as the last launch left it.  With K fused steps (mjb_step(b, K)) an env may run
+ * up to K - 1 steps past its limit before it is reset; resets inside the step kernel are out of scope (the step's own mj_check* auto-reset to qpos0
+ * is unchanged).
+ * Like mjb_reset, both calls abandon an open split step and leave the derived fields unreadable (mjb_get of one, mjb_rays_cast, mjb_jac_eval:
+ * MJB_EINVAL) until mjb_forward or a step. */
+/* The initial-state bank: qpos [ninit][nq], qvel [ninit][nv], act [ninit][na], copied to the device.  ninit == 0 clears it; qvel / act NULL = zeros.
+ * MJB_EINVAL: ninit < 0, a non-finite entry, a zero quaternion in a ball or free joint. */
+int mjb_episode_set_init(mjb_batch *b, int ninit, const double *qpos, const double *qvel, const double *act);
+/* Seed, global index of env 0 and the ranges [nv] of dq and dv; a NULL pair = no perturbation of that part.  MJB_EINVAL: one end of a pair without the
+ * other, lo > hi, a non-finite value. */
+int mjb_episode_set_noise(mjb_batch *b, uint64_t seed, int64_t env_offset, const double *qpos_lo, const double *qpos_hi,
+                          const double *qvel_lo, const double *qvel_hi, int clamp);
+/* The done rule: time_limit <= 0 = no time rule; the bounds are [nq], either may be NULL (no bound on that side).  MJB_EINVAL: a NaN. */
+int mjb_episode_set_rule(mjb_batch *b, double time_limit, const double *qpos_lo, const double *qpos_hi);
+int mjb_episode_reset(mjb_batch *b, const uint8_t *mask_dev);        /* asynchronous; resets mask_dev[env] != 0 (NULL: every env), writes done / ndone */
+int mjb_episode_step(mjb_batch *b, const uint8_t *extra_mask_dev);   /* asynchronous; done = rule OR extra mask (may be NULL) */
+/* Synchronises; done / episode [env_hi - env_lo], ndone one word, any of them may be NULL.  MJB_EINVAL: an env range outside the batch. */
+int mjb_episode_get(mjb_batch *b, int env_lo, int env_hi, uint8_t *done, uint32_t *episode, uint32_t *ndone);
+void *mjb_episode_device_ptr(mjb_batch *b, int which);               /* 0 done [nenv] uint8, 1 episode [nenv] uint32, 2 ndone uint32; NULL: unknown `which` */
+
 /* ---- collision-function overrides (MujocoEnv::registerCollisionFunction, /root/reference mujoco_ros/src/mujoco_env.cpp:163-176) ----
  * The reference lets a plugin replace MuJoCo's pair function for a geom-type pair (the mjCOLLISIONFUNC table) with a host
  * callback until the next reload (:950-954).  Host callbacks cannot run inside the fused device step, so the override names

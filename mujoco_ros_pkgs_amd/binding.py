@@ -205,6 +205,13 @@ def load_library(path=None):
         "mjb_jac_get": (ci, [vp, ci, ci, ci, C.POINTER(cd)]),
         "mjb_jac_device_ptr": (vp, [vp, ci]),
         "mjb_jac_count": (ci, [vp]),
+        "mjb_episode_set_init": (ci, [vp, ci, C.POINTER(cd), C.POINTER(cd), C.POINTER(cd)]),
+        "mjb_episode_set_noise": (ci, [vp, C.c_uint64, C.c_int64, C.POINTER(cd), C.POINTER(cd), C.POINTER(cd), C.POINTER(cd), ci]),
+        "mjb_episode_set_rule": (ci, [vp, cd, C.POINTER(cd), C.POINTER(cd)]),
+        "mjb_episode_reset": (ci, [vp, vp]),
+        "mjb_episode_step": (ci, [vp, vp]),
+        "mjb_episode_get": (ci, [vp, ci, ci, C.POINTER(C.c_uint8), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
+        "mjb_episode_device_ptr": (vp, [vp, ci]),
         "mjb_step": (ci, [vp, ci]),
         "mjb_step1": (ci, [vp]),
         "mjb_step2": (ci, [vp]),

@@ -16,6 +16,7 @@
 #include <vector>
 
 #include "mjb_dev.h"
+#include "mjb_episode.h"
 #include "mjb_jac.h"
 #include "mjb_model.h"
 #include "mjb_resources.h"
@@ -52,6 +53,13 @@ struct RayBufs {  // batched ray casting (mjb_rays_*): the ray / mask table of m
 struct JacBufs {  // batched Jacobians (mjb_jac_*): the point table of mjb_launch_jac and the outputs that were asked for (the others stay empty)
 	DevBuf<double> tab;
 	DevBuf<double> J, MinvJT, Ainv, vel;
+};
+struct EpisodeBufs {  // device-side episode resets (mjb_episode_*): the configuration the kernel reads and its outputs
+	DevBuf<double> bank;          // qpos[ninit][nq] | qvel[ninit][nv] | act[ninit][na] (mjb_episode_set_init)
+	DevBuf<double> qrange, vrange;  // lo[nv] | hi[nv] each (mjb_episode_set_noise; empty: no perturbation of that part)
+	DevBuf<double> box;           // lo[nq] | hi[nq] (mjb_episode_set_rule; empty: no box)
+	DevBuf<unsigned char> done;   // [nenv]
+	DevBuf<unsigned int> episode, ndone;  // [nenv] | one word
 };
 struct SensorBufs {  // sensors-plugin equivalent (mjb_sensor_*): device copy of the noise models and the packed messages
 	DevBuf<int> flag;
@@ -113,6 +121,11 @@ struct mjb_batch {
 	int nray = 0;                     // rays per env of that configuration (0: none yet)
 	JacBufs jac;                      // mjb_jac_configure
 	int njac = 0, jac_outputs = 0;    // points per env of that configuration (0: none yet), its MJB_JAC_OUT_* bits
+	EpisodeBufs epi;                  // mjb_episode_*: the outputs are allocated at the first call that needs them
+	int ep_ninit = 0, ep_clamp = 0;   // rows of the bank, clip limited hinge / slide joints to their range
+	unsigned long long ep_seed = 0;   // Philox key of the episode stream ...
+	long long ep_env_offset = 0;      // ... and the global index of env 0
+	double ep_time_limit = 0;         // <= 0: no time rule
 	bool pose_written = false;        // qpos or a mocap pose has been written through mjb_set* since the frame workspace was last made current: mjb_get still serves
 	                                  // the old frame (mjData's rule); mjb_jac_eval, whose results a controller applies to the NEW state, refuses it
 	DevBuf<double> pack_dev;          // staging block of mjb_get_packed / mjb_set_packed
@@ -2504,6 +2517,165 @@ void *mjb_jac_device_ptr(mjb_batch *b, int which)
 }
 
 int mjb_jac_count(const mjb_batch *b) { return b ? b->njac : fail(MJB_EINVAL, "null batch"); }
+
+// ---- device-side episode resets (kernel in mjb_episode.hip) ----
+// done | episode | ndone, zeroed: made by the first call that launches the kernel or hands out their addresses
+static int episode_outputs(mjb_batch *b)
+{
+	if (b->epi.done) return MJB_OK;
+	HIP_TRY(hipSetDevice(b->device));
+	DevBuf<unsigned char> done;
+	DevBuf<unsigned int> episode, ndone;
+	if (!done.alloc_zeroed((size_t)b->nenv) || !episode.alloc_zeroed((size_t)b->nenv) || !ndone.alloc_zeroed(1))
+		return fail(MJB_ENOMEM, "mjb_episode: allocation failed for %d envs", b->nenv);
+	b->epi.done = std::move(done);
+	b->epi.episode = std::move(episode);
+	b->epi.ndone = std::move(ndone);
+	return MJB_OK;
+}
+
+// a configuration array of the episode kernel replaces the one before it (n == 0: none); an earlier launch may still read what goes
+static int episode_upload(mjb_batch *b, DevBuf<double> &dst, const std::vector<double> &v)
+{
+	HIP_TRY(hipSetDevice(b->device));
+	HIP_TRY(hipStreamSynchronize(b->stream.get()));
+	DevBuf<double> buf;
+	if (!v.empty()) {
+		if (!buf.alloc(v.size())) return fail(MJB_ENOMEM, "mjb_episode: allocation failed for %zu doubles", v.size());  // (the upload writes all of it)
+		HIP_TRY(hipMemcpy(buf.get(), v.data(), v.size() * sizeof(double), hipMemcpyHostToDevice));
+	}
+	dst = std::move(buf);
+	return MJB_OK;
+}
+
+int mjb_episode_set_init(mjb_batch *b, int ninit, const double *qpos, const double *qvel, const double *act)
+{
+	if (!b) return fail(MJB_EINVAL, "null batch");
+	const mjb_model_desc &h = b->model->h;
+	if (ninit < 0) return fail(MJB_EINVAL, "mjb_episode_set_init: ninit %d is negative", ninit);
+	const size_t n = (size_t)ninit, nq = (size_t)h.nq, nv = (size_t)h.nv, na = (size_t)h.na;
+	if (ninit > 0 && nq > 0 && !qpos) return fail(MJB_EINVAL, "mjb_episode_set_init: a bank of %d rows needs qpos", ninit);
+	std::vector<double> bank(n * (nq + nv + na), 0.0);
+	for (size_t k = 0; k < n * nq; k++) bank[k] = qpos[k];
+	for (size_t k = 0; qvel && k < n * nv; k++) bank[n * nq + k] = qvel[k];
+	for (size_t k = 0; act && k < n * na; k++) bank[n * (nq + nv) + k] = act[k];
+	for (size_t k = 0; k < bank.size(); k++)
+		if (!std::isfinite(bank[k])) return fail(MJB_EINVAL, "mjb_episode_set_init: non-finite entry in %s", k < n * nq ? "qpos" : (k < n * (nq + nv) ? "qvel" : "act"));
+	for (size_t r = 0; r < n; r++)
+		for (int j = 0; j < h.njnt; j++) {
+			if (h.jnt_type[j] != MJB_JNT_FREE && h.jnt_type[j] != MJB_JNT_BALL) continue;
+			const double *q = bank.data() + r * nq + h.jnt_qposadr[j] + (h.jnt_type[j] == MJB_JNT_FREE ? 3 : 0);
+			if (std::sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]) < 1e-15)  // (mjMINVAL: what normalize4 replaces by the identity)
+				return fail(MJB_EINVAL, "mjb_episode_set_init: row %zu: zero quaternion in joint %d", r, j);
+		}
+	if (int rc = episode_upload(b, b->epi.bank, bank)) return rc;
+	b->ep_ninit = b->epi.bank ? ninit : 0;  // (a model without state has no bank to pick from)
+	return MJB_OK;
+}
+
+int mjb_episode_set_noise(mjb_batch *b, uint64_t seed, int64_t env_offset, const double *qpos_lo, const double *qpos_hi, const double *qvel_lo, const double *qvel_hi, int clamp)
+{
+	if (!b) return fail(MJB_EINVAL, "null batch");
+	const size_t nv = (size_t)b->model->h.nv;
+	if (!qpos_lo != !qpos_hi || !qvel_lo != !qvel_hi) return fail(MJB_EINVAL, "mjb_episode_set_noise: a range needs both of its ends (or neither)");
+	std::vector<double> range[2];
+	const double *ends[2][2] = { { qpos_lo, qpos_hi }, { qvel_lo, qvel_hi } };
+	for (int part = 0; part < 2; part++) {
+		if (!ends[part][0] || nv == 0) continue;
+		range[part].resize(2 * nv);
+		for (size_t d = 0; d < nv; d++) {
+			const double lo = ends[part][0][d], hi = ends[part][1][d];
+			if (!std::isfinite(lo) || !std::isfinite(hi) || lo > hi)
+				return fail(MJB_EINVAL, "mjb_episode_set_noise: %s range of dof %zu: [%g, %g] is not finite or has lo > hi", part ? "qvel" : "qpos", d, lo, hi);
+			range[part][d] = lo;
+			range[part][nv + d] = hi;
+		}
+	}
+	if (int rc = episode_upload(b, b->epi.qrange, range[0])) return rc;
+	if (int rc = episode_upload(b, b->epi.vrange, range[1])) return rc;
+	b->ep_seed = seed;
+	b->ep_env_offset = env_offset;
+	b->ep_clamp = clamp != 0;
+	return MJB_OK;
+}
+
+int mjb_episode_set_rule(mjb_batch *b, double time_limit, const double *qpos_lo, const double *qpos_hi)
+{
+	if (!b) return fail(MJB_EINVAL, "null batch");
+	const size_t nq = (size_t)b->model->h.nq;
+	if (std::isnan(time_limit)) return fail(MJB_EINVAL, "mjb_episode_set_rule: time_limit is NaN");
+	std::vector<double> box;
+	if ((qpos_lo || qpos_hi) && nq > 0) {
+		box.resize(2 * nq);
+		for (size_t k = 0; k < nq; k++) {
+			box[k] = qpos_lo ? qpos_lo[k] : -INFINITY;
+			box[nq + k] = qpos_hi ? qpos_hi[k] : INFINITY;
+			if (std::isnan(box[k]) || std::isnan(box[nq + k])) return fail(MJB_EINVAL, "mjb_episode_set_rule: bound of coordinate %zu is NaN", k);
+		}
+	}
+	if (int rc = episode_upload(b, b->epi.box, box)) return rc;
+	b->ep_time_limit = time_limit;
+	return MJB_OK;
+}
+
+// one launch of the episode kernel with the host-side bookkeeping of a masked mjb_reset, minus its synchronise
+static int episode_launch(mjb_batch *b, const uint8_t *mask_dev, int use_rule)
+{
+	if (!b) return fail(MJB_EINVAL, "null batch");
+	HIP_TRY(hipSetDevice(b->device));
+	if (int rc = episode_outputs(b)) return rc;
+	if (int rc = join_rest(b)) return rc;
+	b->split_ncb = -1;  // (an open split step is abandoned: mjb_step1_prefix starts the next one)
+	if (int rc = sync_params(b)) return rc;
+	EpisodeArgs a{};
+	a.mask = mask_dev;
+	a.use_rule = use_rule;
+	a.ninit = b->ep_ninit;
+	a.time_limit = b->ep_time_limit;
+	a.box = b->epi.box.get();
+	a.bank = b->epi.bank.get();
+	a.qrange = b->epi.qrange.get();
+	a.vrange = b->epi.vrange.get();
+	a.clamp = b->ep_clamp;
+	a.seed = b->ep_seed;
+	a.env_offset = b->ep_env_offset;
+	a.done = b->epi.done.get();
+	a.episode = b->epi.episode.get();
+	a.ndone = b->epi.ndone.get();
+	const int rc = mjb_launch_episode(b->params_dev.get(), a, b->nenv, b->stream.get());
+	if (rc != 0) return fail(MJB_ENODEVICE, "episode launch failed: %s", hipGetErrorString((hipError_t)rc));
+	b->frame_valid = false;
+	b->le_con_valid = false;
+	b->le_xfrc_stale = true;  // (a reset env's xfrc_applied is zero again)
+	return MJB_OK;
+}
+
+int mjb_episode_reset(mjb_batch *b, const uint8_t *mask_dev) { return episode_launch(b, mask_dev, 0); }
+int mjb_episode_step(mjb_batch *b, const uint8_t *extra_mask_dev) { return episode_launch(b, extra_mask_dev, 1); }
+
+int mjb_episode_get(mjb_batch *b, int env_lo, int env_hi, uint8_t *done, uint32_t *episode, uint32_t *ndone)
+{
+	if (!b) return fail(MJB_EINVAL, "null batch");
+	if (env_lo < 0 || env_hi > b->nenv || env_lo > env_hi) return fail(MJB_EINVAL, "mjb_episode_get: env range [%d,%d) outside [0,%d)", env_lo, env_hi, b->nenv);
+	if (int rc = episode_outputs(b)) return rc;
+	const size_t n = (size_t)(env_hi - env_lo);
+	HIP_TRY(hipSetDevice(b->device));
+	HIP_TRY(hipStreamSynchronize(b->stream.get()));
+	if (done && n) HIP_TRY(hipMemcpy(done, b->epi.done.get() + env_lo, n, hipMemcpyDeviceToHost));
+	if (episode && n) HIP_TRY(hipMemcpy(episode, b->epi.episode.get() + env_lo, n * sizeof(uint32_t), hipMemcpyDeviceToHost));
+	if (ndone) HIP_TRY(hipMemcpy(ndone, b->epi.ndone.get(), sizeof(uint32_t), hipMemcpyDeviceToHost));
+	return MJB_OK;
+}
+
+void *mjb_episode_device_ptr(mjb_batch *b, int which)
+{
+	if (!b || which < 0 || which > 2) {
+		fail(MJB_EINVAL, "mjb_episode_device_ptr: null batch, or `which` %d outside 0 (done), 1 (episode), 2 (ndone)", which);
+		return nullptr;
+	}
+	if (episode_outputs(b)) return nullptr;
+	return which == 0 ? (void *)b->epi.done.get() : (which == 1 ? (void *)b->epi.episode.get() : (void *)b->epi.ndone.get());
+}
 
 int mjb_time_steps(mjb_batch *b, int nsteps, int nlaunch, double *ms_per_launch)
 {

@@ -475,6 +475,107 @@ class Batch:
             raise EngineError(self.lib.mjb_last_error().decode())
         return p
 
+    # ---- device-side episode resets (mjb_episode_*) ----
+    _EPISODE_PTRS = {"done": 0, "episode": 1, "ndone": 2}
+
+    def set_episode_init(self, qpos=None, qvel=None, act=None):
+        """The initial-state bank a reset env starts from (mjb_episode_set_init): qpos [ninit, nq], optionally qvel [ninit, nv] and act [ninit, na] (default
+        zeros); each reset draws one row.  qpos=None clears the bank: qpos0, zero velocity, zero activation."""
+        m = self.cm.model
+        pd = C.POINTER(C.c_double)
+        if qpos is None:
+            _check(self.lib.mjb_episode_set_init(self.ptr, 0, None, None, None), "mjb_episode_set_init")
+            return
+        q = np.ascontiguousarray(np.asarray(qpos, dtype=np.float64).reshape(-1, int(m["nq"])))
+        n = q.shape[0]
+        v = None if qvel is None else np.ascontiguousarray(np.asarray(qvel, dtype=np.float64).reshape(n, int(m["nv"])))
+        a = None if act is None else np.ascontiguousarray(np.asarray(act, dtype=np.float64).reshape(n, int(m["na"])))
+        _check(self.lib.mjb_episode_set_init(self.ptr, n, q.ctypes.data_as(pd), None if v is None else v.ctypes.data_as(pd), None if a is None else a.ctypes.data_as(pd)),
+               "mjb_episode_set_init")
+
+    def set_episode_noise(self, seed, qpos_range=None, qvel_range=None, clamp=False, env_offset=0):
+        """Seeded noise on the bank row (mjb_episode_set_noise): qpos_range / qvel_range are (lo, hi) pairs of [nv] arrays (or scalars) in tangent space, a
+        uniform draw per dof and reset; None: no perturbation of that part.  clamp clips limited hinge / slide joints to jnt_range.  The draws are keyed by
+        (seed, env_offset + env, the env's episode count, dof): shards of one population pass their first env's global index as env_offset."""
+        nv = int(self.cm.model["nv"])
+        pd = C.POINTER(C.c_double)
+        keep, args = [], []
+        for r in (qpos_range, qvel_range):
+            for end in ((None, None) if r is None else r):
+                if end is None:
+                    args.append(None)
+                else:
+                    keep.append(np.ascontiguousarray(np.broadcast_to(np.asarray(end, dtype=np.float64), (nv,))))
+                    args.append(keep[-1].ctypes.data_as(pd))
+        _check(self.lib.mjb_episode_set_noise(self.ptr, int(seed), int(env_offset), args[0], args[1], args[2], args[3], 1 if clamp else 0), "mjb_episode_set_noise")
+
+    def set_episode_rule(self, time_limit=0.0, qpos_box=None):
+        """When an episode is over (mjb_episode_set_rule): time >= time_limit (<= 0: no time rule), or a qpos coordinate outside qpos_box = (lo, hi), [nq]
+        arrays either of which may be None; a NaN coordinate is outside, an infinite bound is none."""
+        nq = int(self.cm.model["nq"])
+        pd = C.POINTER(C.c_double)
+        lo, hi = (None, None) if qpos_box is None else qpos_box
+        lo = None if lo is None else np.ascontiguousarray(np.broadcast_to(np.asarray(lo, dtype=np.float64), (nq,)))
+        hi = None if hi is None else np.ascontiguousarray(np.broadcast_to(np.asarray(hi, dtype=np.float64), (nq,)))
+        _check(self.lib.mjb_episode_set_rule(self.ptr, float(time_limit), None if lo is None else lo.ctypes.data_as(pd), None if hi is None else hi.ctypes.data_as(pd)),
+               "mjb_episode_set_rule")
+
+    def _episode_mask(self, mask):
+        """A mask argument as a device address: None, an int (a device pointer to nenv bytes, e.g. tensor.data_ptr() or another batch's done buffer), or
+        an array, which is uploaded.  The upload waits for the stream and goes into this batch's own done buffer -- the kernel has read an env's mask
+        byte before it writes the env's done byte, so the two may be one array.  Pass a device address to stay asynchronous."""
+        if mask is None or isinstance(mask, (int, np.integer)):
+            return None if mask is None else int(mask)
+        m = np.ascontiguousarray(np.asarray(mask).reshape(-1) != 0, dtype=np.uint8)
+        if m.shape != (self.nenv,):
+            raise ValueError("mask must have shape (nenv,)")
+        dst = self.episode_device_ptr("done")
+        self.synchronize()
+        hip = C.CDLL("libamdhip64.so")
+        hip.hipMemcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
+        if hip.hipMemcpy(dst, m.ctypes.data, m.nbytes, 1) != 0:
+            raise EngineError("episode mask upload failed")
+        return dst
+
+    def episode_reset(self, mask=None):
+        """Reset the envs of `mask` (None: every env) to a drawn initial state on the batch's stream, without a synchronise (mjb_episode_reset); the rule
+        is ignored.  Derived fields are unreadable until forward() or a step."""
+        _check(self.lib.mjb_episode_reset(self.ptr, self._episode_mask(mask)), "mjb_episode_reset")
+
+    def episode_step(self, extra_mask=None):
+        """Evaluate the done rule for every env, OR extra_mask in, and reset the done envs, in one launch on the batch's stream (mjb_episode_step).  The
+        decisions stay on the device (episode_device_ptr) until episode_done() / episode_ndone()."""
+        _check(self.lib.mjb_episode_step(self.ptr, self._episode_mask(extra_mask)), "mjb_episode_step")
+
+    def episode_done(self, lo=0, hi=None):
+        """Wait, and return done uint8 [hi-lo] of the last episode_step / episode_reset."""
+        hi = self.nenv if hi is None else hi
+        out = np.zeros(max(hi - lo, 0), dtype=np.uint8)
+        _check(self.lib.mjb_episode_get(self.ptr, lo, hi, out.ctypes.data_as(C.POINTER(C.c_uint8)), None, None), "mjb_episode_get")
+        return out
+
+    def episode_counts(self, lo=0, hi=None):
+        """Wait, and return the resets so far of envs [lo, hi) as uint32: the episode index of an env's next draw."""
+        hi = self.nenv if hi is None else hi
+        out = np.zeros(max(hi - lo, 0), dtype=np.uint32)
+        _check(self.lib.mjb_episode_get(self.ptr, lo, hi, None, out.ctypes.data_as(C.POINTER(C.c_uint32)), None), "mjb_episode_get")
+        return out
+
+    def episode_ndone(self):
+        """Wait, and return how many envs the last episode_step / episode_reset found done."""
+        n = C.c_uint32(0)
+        _check(self.lib.mjb_episode_get(self.ptr, 0, 0, None, None, C.byref(n)), "mjb_episode_get")
+        return int(n.value)
+
+    def episode_device_ptr(self, name):
+        """Device address of "done" [nenv] uint8, "episode" [nenv] uint32 or "ndone" (one uint32), or of the same by number (mjb_episode_device_ptr)."""
+        if isinstance(name, str) and name not in self._EPISODE_PTRS:
+            raise ValueError(f"episode_device_ptr: unknown buffer {name!r} (done, episode, ndone)")
+        p = self.lib.mjb_episode_device_ptr(self.ptr, self._EPISODE_PTRS[name] if isinstance(name, str) else int(name))
+        if not p:
+            raise EngineError(self.lib.mjb_last_error().decode())
+        return p
+
     def set_keep_frame(self, on=True):
         """Fused step() also leaves the derived fields of its last step readable through get()."""
         _check(self.lib.mjb_set_keep_frame(self.ptr, 1 if on else 0), "mjb_set_keep_frame")
