@@ -670,8 +670,9 @@ int mjb_set_env_equality(mjb_batch *b, int env_lo, int env_hi, const double *par
  * what mj_setConst derives from them -- the caller computes those (the reference has libmujoco: mj_setConst on a scratch
  * mjModel; mujoco_ros_pkgs_amd/engine.py does it with its own numpy dynamics).  params[env][mjb_env_mass_stride(model)] =
  * body_mass[nbody] | body_subtreemass[nbody] | body_inertia[nbody][3] | dof_invweight0[nv] | body_invweight0[nbody][2] |
- * tendon_invweight0[ntendon] | meaninertia.  (Batches carrying these overrides run the generic kernels.)  On the device the block is the head of
- * a longer per-env row that also holds the joint and actuator parameters below (model values until set): 4 nv + njnt + 6 nu doubles more per env. */
+ * tendon_invweight0[ntendon] | meaninertia.  (Batches carrying these overrides run the generic kernels.)  This is the mass section of the per-env
+ * block that EnvBlockLayout (csrc/mjb_dev.h) defines, the one statement of the format in the library; the block goes on with the joint and actuator
+ * parameters below (model values until set). */
 int mjb_env_mass_stride(const mjb_model *m);
 int mjb_set_env_mass_params(mjb_batch *b, int env_lo, int env_hi, const double *params);
 /* The same without the caller having MuJoCo (or Python) at hand: mj_setConst's derivation is done here, host side, in plain C++
@@ -694,7 +695,8 @@ int mjb_set_env_body_mass(mjb_batch *b, int env_lo, int env_hi, const double *bo
  *   mjb_set_env_joint_stiffness  stiffness: [env][njnt], finite and >= 0.
  *   mjb_set_env_actuator_params  gainprm, biasprm: [env][nu][3] each, or NULL: the three parameters of fixed / affine gain and bias.
  *   mjb_set_env_joint_params     all six as one block per env, params[env][mjb_env_joint_stride(model)] =
- *                                dof_damping[nv] | dof_armature[nv] | dof_frictionloss[nv] | jnt_stiffness[njnt] | gainprm[nu][3] | biasprm[nu][3].
+ *                                dof_damping[nv] | dof_armature[nv] | dof_frictionloss[nv] | jnt_stiffness[njnt] | gainprm[nu][3] | biasprm[nu][3]:
+ *                                the joint section of EnvBlockLayout without the dof_damping_int the engine derives (mjb_env_joint_packed, csrc/mjb_dev.h).
  * What the integrator adds to M's diagonal (damping under Euler, -diag(D) under implicitfast incl. gear^2 biasprm[2] of joint actuators) is
  * derived per env from these values.  Refused, with mjb_last_error naming the reason and the batch left as it was:
  *   MJB_EINVAL        an env range outside the batch; a non-finite or negative damping / armature / frictionloss / stiffness; a non-finite gain / bias

@@ -133,7 +133,7 @@ struct mjb_batch {
 	DevBuf<double> env_geom_size;
 	DevBuf<int> env_geom_type;
 	DevBuf<double> env_gravity, env_geom_friction, env_equality, env_mass;  // per-env model parameter overrides (mjb_set_env_*)
-	std::vector<double> env_block;  // host mirror of env_mass, [nenv][mjb_env_block_doubles]: what an armature or mass change re-derives the env's mj_setConst constants from
+	std::vector<double> env_block;  // host mirror of env_mass, there whenever env_mass is: what an armature or mass change re-derives the env's mj_setConst constants from
 	// device-side DefaultRobotHWSim (mjb_hwsim_*)
 	HwSim hw{};
 	HwSimBufs hwb;
@@ -795,9 +795,15 @@ static bool want_lane_env(const mjb_batch *b, const LaunchReq &q, int variant)
 	return b->lane_env_mode >= 1 || q.env_hi - q.env_lo >= min_envs;  // (also the fused launch of a split step's non-callback envs, mjb_step_rest)
 }
 
+// an env's row of the host mirror of env_mass; NULL while the batch has no block, i.e. every env still runs on the model's values
+static double *env_block_row(mjb_batch *b, int env)
+{
+	return b->env_mass ? b->env_block.data() + (size_t)env * mjb_env_block_layout(b->model->h).doubles : nullptr;
+}
+
 // Mode 2 of mjb_set_lane_env: the per-env overlay (DevState::le_overlay; PeSlots, mjb_lane_env_kernel.h) of a batch with per-env gravity or parameter
 // blocks.  Built for every env at the first such launch; afterwards the columns of the envs a mjb_set_env_* call has touched (le_overlay_touch) are
-// derived again ahead of the next launch.  Sources: env_gravity, the env's block of env_mass (its host mirror when there is one), else the model.
+// derived again ahead of the next launch.  Sources: env_gravity, the env's block of env_mass (its host mirror), else the model.
 static void le_overlay_touch(mjb_batch *b, int env_lo, int env_hi)
 {
 	if (!b->le_overlay.get() || env_lo >= env_hi) return;
@@ -819,22 +825,14 @@ static int le_overlay_sync(mjb_batch *b)
 	if (n <= 0) return MJB_OK;
 	HIP_TRY(hipStreamSynchronize(b->stream.get()));  // (an earlier launch may still read the columns)
 	if (b->rest_pending && b->rest.stream.get()) HIP_TRY(hipStreamSynchronize(b->rest.stream.get()));
-	const size_t stride = (size_t)mjb_env_block_doubles(h.nbody, h.nv, h.ntendon, h.njnt, h.nu);
-	std::vector<double> grav, blk;
-	const double *rows = nullptr;
+	std::vector<double> grav;
 	if (b->env_gravity.get()) {
 		grav.resize((size_t)3 * n);
 		HIP_TRY(hipMemcpy(grav.data(), b->env_gravity.get() + (size_t)3 * lo, grav.size() * sizeof(double), hipMemcpyDeviceToHost));
 	}
-	if (b->env_mass.get() && !b->env_block.empty()) rows = b->env_block.data() + (size_t)lo * stride;
-	else if (b->env_mass.get()) {
-		blk.resize(stride * n);
-		HIP_TRY(hipMemcpy(blk.data(), b->env_mass.get() + (size_t)lo * stride, blk.size() * sizeof(double), hipMemcpyDeviceToHost));
-		rows = blk.data();
-	}
 	std::vector<double> col((size_t)ns), stage((size_t)ns * n);
 	for (int e = 0; e < n; e++) {
-		mjb_lane_env_overlay_row(&h, grav.empty() ? nullptr : grav.data() + (size_t)3 * e, rows ? rows + (size_t)e * stride : nullptr, col.data());
+		mjb_lane_env_overlay_row(&h, grav.empty() ? nullptr : grav.data() + (size_t)3 * e, env_block_row(b, lo + e), col.data());
 		for (int k = 0; k < ns; k++) stage[(size_t)k * n + e] = col[k];
 	}
 	// slot k of envs [lo, hi): n consecutive doubles at le_overlay + k * nenv + lo
@@ -1730,6 +1728,28 @@ __global__ void mjb_metrics_kernel(const double *qacc, const double *qvel, const
 	}
 }
 
+// one per-env override array of the mjb_set_env_* setters below that need no mj_setConst
+template <typename T>
+static int env_param(mjb_batch *b, DevBuf<T> &arr, const T *&view, int per_env, const T *model_vals, int env_lo, int env_hi, const T *vals, const char *what)
+{
+	if (!b || !vals) return fail(MJB_EINVAL, "%s: bad argument", what);
+	if (env_lo < 0 || env_hi > b->nenv || env_lo > env_hi) return fail(MJB_EINVAL, "%s: bad env range", what);
+	if (per_env <= 0) return fail(MJB_EINVAL, "%s: the model has nothing to override", what);
+	HIP_TRY(hipSetDevice(b->device));
+	HIP_TRY(hipStreamSynchronize(b->stream.get()));
+	if (!arr) {  // first use: every env starts from the model's values (uploaded for every env: no zeroing)
+		DevBuf<T> dev;
+		if (!dev.alloc((size_t)b->nenv * per_env)) return fail(MJB_ENOMEM, "%s: allocation failed", what);
+		std::vector<T> init((size_t)b->nenv * per_env);
+		for (int e = 0; e < b->nenv; e++) memcpy(init.data() + (size_t)e * per_env, model_vals, (size_t)per_env * sizeof(T));
+		HIP_TRY(hipMemcpy(dev.get(), init.data(), init.size() * sizeof(T), hipMemcpyHostToDevice));
+		arr = std::move(dev);
+		set_view(b, view, arr.get());
+	}
+	HIP_TRY(hipMemcpy(arr.get() + (size_t)env_lo * per_env, vals, (size_t)(env_hi - env_lo) * per_env * sizeof(T), hipMemcpyHostToDevice));
+	return MJB_OK;
+}
+
 extern "C" {
 
 void *mjb_metrics_device(mjb_batch *b)
@@ -1765,27 +1785,6 @@ int mjb_metrics(mjb_batch *b, double *out16)
 }
 
 // ---- per-env model parameters (the subset that needs no mj_setConst) ----
-static int env_param(mjb_batch *b, DevBuf<double> &arr, const double *&view, int per_env, const double *model_vals, int env_lo, int env_hi,
-                     const double *vals, const char *what)
-{
-	if (!b || !vals) return fail(MJB_EINVAL, "%s: bad argument", what);
-	if (env_lo < 0 || env_hi > b->nenv || env_lo > env_hi) return fail(MJB_EINVAL, "%s: bad env range", what);
-	if (per_env <= 0) return fail(MJB_EINVAL, "%s: the model has nothing to override", what);
-	HIP_TRY(hipSetDevice(b->device));
-	HIP_TRY(hipStreamSynchronize(b->stream.get()));
-	if (!arr) {  // first use: every env starts from the model's values (uploaded for every env: no zeroing)
-		DevBuf<double> dev;
-		if (!dev.alloc((size_t)b->nenv * per_env)) return fail(MJB_ENOMEM, "%s: allocation failed", what);
-		std::vector<double> init((size_t)b->nenv * per_env);
-		for (int e = 0; e < b->nenv; e++) memcpy(init.data() + (size_t)e * per_env, model_vals, (size_t)per_env * sizeof(double));
-		HIP_TRY(hipMemcpy(dev.get(), init.data(), init.size() * sizeof(double), hipMemcpyHostToDevice));
-		arr = std::move(dev);
-		set_view(b, view, arr.get());
-	}
-	HIP_TRY(hipMemcpy(arr.get() + (size_t)env_lo * per_env, vals, (size_t)(env_hi - env_lo) * per_env * sizeof(double), hipMemcpyHostToDevice));
-	return MJB_OK;
-}
-
 int mjb_set_env_gravity(mjb_batch *b, int env_lo, int env_hi, const double *gravity)
 {
 	if (!b) return fail(MJB_EINVAL, "null batch");
@@ -1812,27 +1811,15 @@ int mjb_set_env_geom_size(mjb_batch *b, int env_lo, int env_hi, const double *si
 
 int mjb_set_env_geom_type(mjb_batch *b, int env_lo, int env_hi, const int *type)
 {
-	if (!b || !type) return fail(MJB_EINVAL, "mjb_set_env_geom_type: bad argument");
+	if (!b) return fail(MJB_EINVAL, "mjb_set_env_geom_type: bad argument");
 	const mjb_model_desc &h = b->model->h;
-	if (env_lo < 0 || env_hi > b->nenv || env_lo > env_hi) return fail(MJB_EINVAL, "mjb_set_env_geom_type: bad env range");
-	if (h.nconmax <= 0 || h.ngeom <= 0) return fail(MJB_EINVAL, "mjb_set_env_geom_type: the model has nothing to override");
-	for (size_t k = 0; k < (size_t)(env_hi - env_lo) * h.ngeom; k++)
-		if (type[k] != MJB_GEOM_PLANE && type[k] != MJB_GEOM_SPHERE && type[k] != MJB_GEOM_CAPSULE && type[k] != MJB_GEOM_BOX &&
-		    type[k] != 4 && type[k] != 5)  // (mjGEOM_ELLIPSOID / mjGEOM_CYLINDER are accepted as "no pair function": the geom yields no contacts)
-			return fail(MJB_EUNSUPPORTED, "mjb_set_env_geom_type: geom type %d is neither a primitive of the engine nor ellipsoid / cylinder", type[k]);
-	HIP_TRY(hipSetDevice(b->device));
-	HIP_TRY(hipStreamSynchronize(b->stream.get()));
-	if (!b->env_geom_type) {
-		DevBuf<int> dev;
-		if (!dev.alloc((size_t)b->nenv * h.ngeom)) return fail(MJB_ENOMEM, "mjb_set_env_geom_type: allocation failed");  // (uploaded for every env)
-		std::vector<int> init((size_t)b->nenv * h.ngeom);
-		for (int e = 0; e < b->nenv; e++) memcpy(init.data() + (size_t)e * h.ngeom, h.geom_type, (size_t)h.ngeom * sizeof(int));
-		HIP_TRY(hipMemcpy(dev.get(), init.data(), init.size() * sizeof(int), hipMemcpyHostToDevice));
-		b->env_geom_type = std::move(dev);
-		set_view(b, b->st.env_geom_type, b->env_geom_type.get());
-	}
-	HIP_TRY(hipMemcpy(b->env_geom_type.get() + (size_t)env_lo * h.ngeom, type, (size_t)(env_hi - env_lo) * h.ngeom * sizeof(int), hipMemcpyHostToDevice));
-	return MJB_OK;
+	const int per_env = h.nconmax > 0 ? h.ngeom : 0;
+	if (type && env_lo >= 0 && env_hi <= b->nenv && env_lo <= env_hi)  // (any other call is env_param's to refuse)
+		for (size_t k = 0; k < (size_t)(env_hi - env_lo) * per_env; k++)
+			if (type[k] != MJB_GEOM_PLANE && type[k] != MJB_GEOM_SPHERE && type[k] != MJB_GEOM_CAPSULE && type[k] != MJB_GEOM_BOX &&
+			    type[k] != 4 && type[k] != 5)  // (mjGEOM_ELLIPSOID / mjGEOM_CYLINDER are accepted as "no pair function": the geom yields no contacts)
+				return fail(MJB_EUNSUPPORTED, "mjb_set_env_geom_type: geom type %d is neither a primitive of the engine nor ellipsoid / cylinder", type[k]);
+	return env_param(b, b->env_geom_type, b->st.env_geom_type, per_env, h.geom_type, env_lo, env_hi, type, "mjb_set_env_geom_type");
 }
 
 int mjb_set_env_equality(mjb_batch *b, int env_lo, int env_hi, const double *params)
@@ -1850,23 +1837,9 @@ int mjb_set_env_equality(mjb_batch *b, int env_lo, int env_hi, const double *par
 	return env_param(b, b->env_equality, b->st.env_equality, 19 * h.neq, packed.data(), env_lo, env_hi, params, "mjb_set_env_equality");
 }
 
-// The env's block of inertial, joint and actuator constants (DevState::env_mass, mjb_dev.h): one allocation, mirrored on the host.  The
-// first override of either family fills every env's block with the model's values; a setter then edits its rows in the mirror and
-// uploads them.  EnvBlock: where the arrays of the joint section sit, behind the public mass block (jnt0 = mjb_env_mass_stride).
-namespace {
-struct EnvBlock {
-	int nb, nv, nt, nj, nu, jnt0, stride;
-	explicit EnvBlock(const mjb_model_desc &h) : nb(h.nbody), nv(h.nv), nt(h.ntendon), nj(h.njnt), nu(h.nu), jnt0(7 * h.nbody + h.nv + h.ntendon + 1),
-	                                             stride(mjb_env_block_doubles(h.nbody, h.nv, h.ntendon, h.njnt, h.nu)) {}
-	int damping() const { return jnt0; }
-	int armature() const { return jnt0 + nv; }
-	int frictionloss() const { return jnt0 + 2 * nv; }
-	int damping_int() const { return jnt0 + 3 * nv; }
-	int stiffness() const { return jnt0 + 4 * nv; }
-	int gainprm() const { return jnt0 + 4 * nv + nj; }
-	int biasprm() const { return jnt0 + 4 * nv + nj + 3 * nu; }
-};
-}  // namespace
+// The env's block of inertial, joint and actuator constants (DevState::env_mass, laid out by EnvBlockLayout, mjb_dev.h): one allocation, and its
+// host mirror b->env_block from the same moment on.  The first override of either family fills every env's block with the model's values; a setter
+// then edits its rows in the mirror (env_block_row) and uploads them.
 
 // what the integrator adds to M's diagonal per unit of h, from an env's damping and bias parameters: mjb_compile's rule (damp_int)
 static void env_damping_int(const mjb_model_desc &h, const double *damping, const double *biasprm, double *out)
@@ -1886,50 +1859,29 @@ static int env_block_ensure(mjb_batch *b, const char *what)
 {
 	if (b->env_mass) return MJB_OK;
 	const mjb_model_desc &h = b->model->h;
-	const EnvBlock B(h);
-	std::vector<double> row((size_t)B.stride);
-	double *o = row.data();
-	for (int i = 0; i < h.nbody; i++) o[i] = h.body_mass[i];
-	for (int i = 0; i < h.nbody; i++) o[h.nbody + i] = h.body_subtreemass[i];
-	for (int i = 0; i < 3 * h.nbody; i++) o[2 * h.nbody + i] = h.body_inertia[i];
-	for (int i = 0; i < h.nv; i++) o[5 * h.nbody + i] = h.dof_invweight0[i];
-	for (int i = 0; i < 2 * h.nbody; i++) o[5 * h.nbody + h.nv + i] = h.body_invweight0[i];
-	for (int i = 0; i < h.ntendon; i++) o[7 * h.nbody + h.nv + i] = h.tendon_invweight0[i];
-	o[7 * h.nbody + h.nv + h.ntendon] = h.meaninertia[0];
-	for (int i = 0; i < h.nv; i++) {
-		o[B.damping() + i] = h.dof_damping[i];
-		o[B.armature() + i] = h.dof_armature[i];
-		o[B.frictionloss() + i] = h.dof_frictionloss[i];
-		o[B.damping_int() + i] = b->model->damp_int[i];
-	}
-	for (int j = 0; j < h.njnt; j++) o[B.stiffness() + j] = h.jnt_stiffness[j];
-	for (int k = 0; k < 3 * h.nu; k++) { o[B.gainprm() + k] = h.actuator_gainprm[k]; o[B.biasprm() + k] = h.actuator_biasprm[k]; }
+	const EnvBlockLayout B = mjb_env_block_layout(h);
+	const struct { int off; const double *src; int n; } sections[] = {
+		{ B.body_mass, h.body_mass, h.nbody }, { B.body_subtreemass, h.body_subtreemass, h.nbody }, { B.body_inertia, h.body_inertia, 3 * h.nbody },
+		{ B.dof_invweight0, h.dof_invweight0, h.nv }, { B.body_invweight0, h.body_invweight0, 2 * h.nbody }, { B.tendon_invweight0, h.tendon_invweight0, h.ntendon },
+		{ B.meaninertia, h.meaninertia, 1 }, { B.dof_damping, h.dof_damping, h.nv }, { B.dof_armature, h.dof_armature, h.nv },
+		{ B.dof_frictionloss, h.dof_frictionloss, h.nv }, { B.dof_damping_int, b->model->damp_int.data(), h.nv }, { B.jnt_stiffness, h.jnt_stiffness, h.njnt },
+		{ B.actuator_gainprm, h.actuator_gainprm, 3 * h.nu }, { B.actuator_biasprm, h.actuator_biasprm, 3 * h.nu },
+	};
+	std::vector<double> row((size_t)B.doubles), init((size_t)b->nenv * B.doubles);
+	for (const auto &s : sections) std::copy_n(s.src, s.n, row.data() + s.off);
+	for (int e = 0; e < b->nenv; e++) memcpy(init.data() + (size_t)e * B.doubles, row.data(), (size_t)B.doubles * sizeof(double));
 	DevBuf<double> dev;
-	if (!dev.alloc((size_t)b->nenv * B.stride)) return fail(MJB_ENOMEM, "%s: allocation failed", what);  // (uploaded for every env)
-	std::vector<double> init((size_t)b->nenv * B.stride);
-	for (int e = 0; e < b->nenv; e++) memcpy(init.data() + (size_t)e * B.stride, o, (size_t)B.stride * sizeof(double));
+	if (!dev.alloc(init.size())) return fail(MJB_ENOMEM, "%s: allocation failed", what);  // (uploaded for every env)
 	if (hipMemcpy(dev.get(), init.data(), init.size() * sizeof(double), hipMemcpyHostToDevice) != hipSuccess) return fail(MJB_ENODEVICE, "%s: upload failed", what);
 	b->env_mass = std::move(dev);
+	b->env_block = std::move(init);
 	set_view(b, b->st.env_mass, b->env_mass.get());
-	return MJB_OK;
-}
-
-// The host mirror exists from the first joint-parameter call on (a batch that only ever sets masses keeps none): read back once.
-static int env_block_mirror(mjb_batch *b)
-{
-	if (!b->env_block.empty()) return MJB_OK;
-	const size_t n = (size_t)b->nenv * EnvBlock(b->model->h).stride;
-	b->env_block.resize(n);
-	if (hipMemcpy(b->env_block.data(), b->env_mass.get(), n * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess) {
-		b->env_block.clear();
-		return fail(MJB_ENODEVICE, "reading the per-env constants back failed");
-	}
 	return MJB_OK;
 }
 
 static int env_block_upload(mjb_batch *b, int env_lo, int env_hi)
 {
-	const size_t stride = (size_t)EnvBlock(b->model->h).stride;
+	const size_t stride = (size_t)mjb_env_block_layout(b->model->h).doubles;
 	HIP_TRY(hipMemcpy(b->env_mass.get() + (size_t)env_lo * stride, b->env_block.data() + (size_t)env_lo * stride, (size_t)(env_hi - env_lo) * stride * sizeof(double),
 	                  hipMemcpyHostToDevice));
 	le_overlay_touch(b, env_lo, env_hi);
@@ -1942,17 +1894,15 @@ int mjb_set_env_mass_params(mjb_batch *b, int env_lo, int env_hi, const double *
 	if (!b) return fail(MJB_EINVAL, "null batch");
 	if (!params) return fail(MJB_EINVAL, "%s: bad argument", what);
 	if (env_lo < 0 || env_hi > b->nenv || env_lo > env_hi) return fail(MJB_EINVAL, "%s: bad env range", what);
-	const EnvBlock B(b->model->h);
+	const EnvBlockLayout B = mjb_env_block_layout(b->model->h);
 	HIP_TRY(hipSetDevice(b->device));
 	HIP_TRY(hipStreamSynchronize(b->stream.get()));
 	const int rc = env_block_ensure(b, what);
 	if (rc != MJB_OK) return rc;
-	if (!b->env_block.empty())
-		for (int e = env_lo; e < env_hi; e++)
-			memcpy(b->env_block.data() + (size_t)e * B.stride, params + (size_t)(e - env_lo) * B.jnt0, (size_t)B.jnt0 * sizeof(double));
-	if (env_hi > env_lo)  // the mass section of each env's row: rows of jnt0 doubles into rows of stride doubles
-		HIP_TRY(hipMemcpy2D(b->env_mass.get() + (size_t)env_lo * B.stride, (size_t)B.stride * sizeof(double), params, (size_t)B.jnt0 * sizeof(double),
-		                    (size_t)B.jnt0 * sizeof(double), (size_t)(env_hi - env_lo), hipMemcpyHostToDevice));
+	for (int e = env_lo; e < env_hi; e++) memcpy(env_block_row(b, e), params + (size_t)(e - env_lo) * B.mass_doubles, (size_t)B.mass_doubles * sizeof(double));
+	if (env_hi > env_lo)  // the mass section of each env's row: rows of mass_doubles into rows of the block's stride
+		HIP_TRY(hipMemcpy2D(b->env_mass.get() + (size_t)env_lo * B.doubles, (size_t)B.doubles * sizeof(double), params, (size_t)B.mass_doubles * sizeof(double),
+		                    (size_t)B.mass_doubles * sizeof(double), (size_t)(env_hi - env_lo), hipMemcpyHostToDevice));
 	le_overlay_touch(b, env_lo, env_hi);
 	return MJB_OK;
 }
@@ -1962,14 +1912,14 @@ int mjb_set_env_body_mass(mjb_batch *b, int env_lo, int env_hi, const double *bo
 	if (!b || !body_mass) return fail(MJB_EINVAL, "mjb_set_env_body_mass: bad argument");
 	if (env_lo < 0 || env_hi > b->nenv || env_lo > env_hi) return fail(MJB_EINVAL, "mjb_set_env_body_mass: bad env range");
 	const mjb_model_desc &h = b->model->h;
-	const EnvBlock B(h);
-	const int stride = B.jnt0, n = env_hi - env_lo;
+	const EnvBlockLayout B = mjb_env_block_layout(h);
+	const int stride = B.mass_doubles, n = env_hi - env_lo;
 	std::vector<double> packed((size_t)std::max(1, n) * stride);
 	// (the derivation is mj_setConst -- Jacobians of every body, an O(nbody nv^2) mass matrix and its inverse -- and a service call that
 	//  sets one mass on the whole batch, setBodyStateCB with the default env range, hands over nenv identical rows under the physics
 	//  mutex: derived once per DISTINCT row, the block of a row equal to its predecessor is copied)
-	// (an env that carries its own armature, mjb_set_env_dof_params, is derived with it: the mirror of its block has it)
-	auto arm = [&](int e) { return b->env_block.empty() ? h.dof_armature : b->env_block.data() + (size_t)(env_lo + e) * B.stride + B.armature(); };
+	// (an env that carries its own armature, mjb_set_env_dof_params, is derived with it: its row of the mirror has it)
+	auto arm = [&](int e) { return b->env_mass ? env_block_row(b, env_lo + e) + B.dof_armature : h.dof_armature; };
 	for (int e = 0; e < n; e++) {
 		const double *bm = body_mass + (size_t)e * h.nbody, *bi = body_inertia ? body_inertia + (size_t)e * 3 * h.nbody : nullptr;
 		double *dst = packed.data() + (size_t)e * stride;
@@ -1996,8 +1946,8 @@ static int env_joint_set(mjb_batch *b, int env_lo, int env_hi, const double *dam
 	if (env_lo < 0 || env_hi > b->nenv || env_lo > env_hi) return fail(MJB_EINVAL, "%s: bad env range", what);
 	const mjb_model *M = b->model;
 	const mjb_model_desc &h = M->h;
-	const EnvBlock B(h);
-	if (B.stride == B.jnt0) return fail(MJB_EINVAL, "%s: the model has nothing to override", what);
+	const EnvBlockLayout B = mjb_env_block_layout(h);
+	if (B.doubles == B.mass_doubles) return fail(MJB_EINVAL, "%s: the model has nothing to override", what);
 	const int n = env_hi - env_lo;
 	// a packed block (src_stride > 0) or a dense [env][len] array per argument
 	auto at = [&](const double *p, int e, int len) { return p + (size_t)e * (src_stride > 0 ? src_stride : len); };
@@ -2045,19 +1995,14 @@ static int env_joint_set(mjb_batch *b, int env_lo, int env_hi, const double *dam
 						            what, trn == MJB_TRN_SITE ? "site" : "tendon", env_lo + e, i);
 				}
 	}
-	HIP_TRY(hipSetDevice(b->device));
-	if (b->env_mass.get()) {
-		HIP_TRY(hipStreamSynchronize(b->stream.get()));
-		if ((rc = env_block_mirror(b)) != MJB_OK) return rc;
-	}
 	// the model's frames hold M + h B and its factor only when mjb_compile found something to put there (DevModel::eulerdamp)
 	const bool euler_implicit = h.integrator == MJB_INT_EULER && !(h.disableflags & MJB_DSBL_EULERDAMP);
 	if (M->eulerdamp == 0 && (euler_implicit || h.integrator == MJB_INT_IMPLICITFAST) && (damping || biasprm)) {
 		std::vector<double> di((size_t)std::max(1, h.nv));
 		for (int e = 0; e < n; e++) {
-			const double *cur = b->env_block.empty() ? nullptr : b->env_block.data() + (size_t)(env_lo + e) * B.stride;
-			const double *d = damping ? at(damping, e, h.nv) : (cur ? cur + B.damping() : h.dof_damping);
-			const double *bp = biasprm ? at(biasprm, e, 3 * h.nu) : (cur ? cur + B.biasprm() : h.actuator_biasprm);
+			const double *cur = env_block_row(b, env_lo + e);  // (no block yet: the model's values)
+			const double *d = damping ? at(damping, e, h.nv) : (cur ? cur + B.dof_damping : h.dof_damping);
+			const double *bp = biasprm ? at(biasprm, e, 3 * h.nu) : (cur ? cur + B.actuator_biasprm : h.actuator_biasprm);
 			env_damping_int(h, d, bp, di.data());
 			for (int i = 0; i < h.nv; i++)
 				if (di[i] != 0)
@@ -2069,30 +2014,30 @@ static int env_joint_set(mjb_batch *b, int env_lo, int env_hi, const double *dam
 	HIP_TRY(hipSetDevice(b->device));
 	HIP_TRY(hipStreamSynchronize(b->stream.get()));
 	if ((rc = env_block_ensure(b, what)) != MJB_OK) return rc;
-	if ((rc = env_block_mirror(b)) != MJB_OK) return rc;
 	std::vector<double> saved;  // (a failed derivation -- a singular inertia -- restores the rows)
-	if (armature) saved.assign(b->env_block.begin() + (size_t)env_lo * B.stride, b->env_block.begin() + (size_t)env_hi * B.stride);
+	if (armature) saved.assign(b->env_block.begin() + (size_t)env_lo * B.doubles, b->env_block.begin() + (size_t)env_hi * B.doubles);
 	for (int e = 0; e < n; e++) {
-		double *row = b->env_block.data() + (size_t)(env_lo + e) * B.stride;
-		if (damping) memcpy(row + B.damping(), at(damping, e, h.nv), sizeof(double) * h.nv);
-		if (armature) memcpy(row + B.armature(), at(armature, e, h.nv), sizeof(double) * h.nv);
-		if (frictionloss) memcpy(row + B.frictionloss(), at(frictionloss, e, h.nv), sizeof(double) * h.nv);
-		if (stiffness) memcpy(row + B.stiffness(), at(stiffness, e, h.njnt), sizeof(double) * h.njnt);
-		if (gainprm) memcpy(row + B.gainprm(), at(gainprm, e, 3 * h.nu), sizeof(double) * 3 * h.nu);
-		if (biasprm) memcpy(row + B.biasprm(), at(biasprm, e, 3 * h.nu), sizeof(double) * 3 * h.nu);
-		if (damping || biasprm) env_damping_int(h, row + B.damping(), row + B.biasprm(), row + B.damping_int());
+		double *row = env_block_row(b, env_lo + e);
+		if (damping) memcpy(row + B.dof_damping, at(damping, e, h.nv), sizeof(double) * h.nv);
+		if (armature) memcpy(row + B.dof_armature, at(armature, e, h.nv), sizeof(double) * h.nv);
+		if (frictionloss) memcpy(row + B.dof_frictionloss, at(frictionloss, e, h.nv), sizeof(double) * h.nv);
+		if (stiffness) memcpy(row + B.jnt_stiffness, at(stiffness, e, h.njnt), sizeof(double) * h.njnt);
+		if (gainprm) memcpy(row + B.actuator_gainprm, at(gainprm, e, 3 * h.nu), sizeof(double) * 3 * h.nu);
+		if (biasprm) memcpy(row + B.actuator_biasprm, at(biasprm, e, 3 * h.nu), sizeof(double) * 3 * h.nu);
+		if (damping || biasprm) env_damping_int(h, row + B.dof_damping, row + B.actuator_biasprm, row + B.dof_damping_int);
 		if (armature) {
 			// mj_setConst with the env's own masses, inertias and armature (derived once per distinct row, as mjb_set_env_body_mass does)
-			const double *prev = e > 0 ? row - B.stride : nullptr;
-			if (prev && std::memcmp(row, prev, sizeof(double) * h.nbody) == 0 && std::memcmp(row + 2 * h.nbody, prev + 2 * h.nbody, sizeof(double) * 3 * h.nbody) == 0 &&
-			    std::memcmp(row + B.armature(), prev + B.armature(), sizeof(double) * h.nv) == 0) {
-				memcpy(row, prev, sizeof(double) * B.jnt0);
+			const double *prev = e > 0 ? row - B.doubles : nullptr;
+			if (prev && std::memcmp(row + B.body_mass, prev + B.body_mass, sizeof(double) * h.nbody) == 0 &&
+			    std::memcmp(row + B.body_inertia, prev + B.body_inertia, sizeof(double) * 3 * h.nbody) == 0 &&
+			    std::memcmp(row + B.dof_armature, prev + B.dof_armature, sizeof(double) * h.nv) == 0) {
+				memcpy(row, prev, sizeof(double) * B.mass_doubles);
 				continue;
 			}
-			std::vector<double> mass(row, row + h.nbody), inertia(row + 2 * h.nbody, row + 5 * h.nbody);
-			rc = mjb_derive_mass_params_armature(M, mass.data(), inertia.data(), row + B.armature(), row);
+			const std::vector<double> mass(row + B.body_mass, row + B.body_mass + h.nbody), inertia(row + B.body_inertia, row + B.body_inertia + 3 * h.nbody);
+			rc = mjb_derive_mass_params_armature(M, mass.data(), inertia.data(), row + B.dof_armature, row);
 			if (rc != MJB_OK) {
-				std::copy(saved.begin(), saved.end(), b->env_block.begin() + (size_t)env_lo * B.stride);
+				std::copy(saved.begin(), saved.end(), b->env_block.begin() + (size_t)env_lo * B.doubles);
 				return rc;
 			}
 		}
@@ -2119,11 +2064,11 @@ int mjb_set_env_joint_params(mjb_batch *b, int env_lo, int env_hi, const double 
 {
 	if (!b || !params) return fail(MJB_EINVAL, "mjb_set_env_joint_params: bad argument");
 	const mjb_model_desc &h = b->model->h;
-	const double *p = params;
-	const double *damping = p, *armature = p + h.nv, *frictionloss = p + 2 * h.nv, *stiffness = p + 3 * h.nv, *gainprm = p + 3 * h.nv + h.njnt,
-	             *biasprm = p + 3 * h.nv + h.njnt + 3 * h.nu;
-	return env_joint_set(b, env_lo, env_hi, h.nv ? damping : nullptr, h.nv ? armature : nullptr, h.nv ? frictionloss : nullptr, h.njnt ? stiffness : nullptr,
-	                     h.nu ? gainprm : nullptr, h.nu ? biasprm : nullptr, mjb_env_joint_stride(b->model), "mjb_set_env_joint_params");
+	const EnvBlockLayout B = mjb_env_block_layout(h);
+	// the block's section at `off`, n entries: where the packed form has it, NULL when the model has none
+	auto view = [&](int off, int n) { return n ? params + mjb_env_joint_packed(B, off) : nullptr; };
+	return env_joint_set(b, env_lo, env_hi, view(B.dof_damping, h.nv), view(B.dof_armature, h.nv), view(B.dof_frictionloss, h.nv), view(B.jnt_stiffness, h.njnt),
+	                     view(B.actuator_gainprm, h.nu), view(B.actuator_biasprm, h.nu), mjb_env_joint_packed(B, B.doubles), "mjb_set_env_joint_params");
 }
 
 // ---- device-side DefaultRobotHWSim::writeSim (stage hwsim_write in mjb_step.hip) ----

@@ -196,9 +196,7 @@ struct DevState {
 	const double *env_geom_size;     // [nenv][ngeom][3] per-env geom sizes (NULL: the model's)
 	const int *env_geom_type;        // [nenv][ngeom] per-env geom types (NULL: the model's)
 	const double *env_equality;      // [nenv][neq][19] per-env equality parameters (NULL: the model's)
-	const double *env_mass;          // [nenv][mjb_env_block_doubles] per-env inertial, joint and actuator constants (NULL: the model's):
-	                                 // body_mass | body_subtreemass | body_inertia[3] | dof_invweight0 | body_invweight0[2] | tendon_invweight0 | meaninertia  (the public mass block,
-	                                 // mjb_env_mass_stride) | dof_damping | dof_armature | dof_frictionloss | dof_damping_int | jnt_stiffness | actuator_gainprm[3] | actuator_biasprm[3]
+	const double *env_mass;          // [nenv][EnvBlockLayout::doubles] per-env inertial, joint and actuator constants (NULL: the model's), laid out by EnvBlockLayout below
 	int *sched;                      // [1 + nenv] work counter | chunks done per env, of a chunked fused launch (constrained kernels); NULL otherwise
 	double *efc_Jg;                  // [nenv][mjb_rowblock_doubles] row data of the env-steps whose rows outnumber the fused frame's share (kernel variant 4, RowBlock); NULL otherwise
 	unsigned long long efc_Jg_stride;  // doubles per env of efc_Jg: sized for the largest cone-block stride of the model's three frame layouts (the kernels lay a block out with the stride of the frame they run on)
@@ -236,11 +234,54 @@ MJB_HD inline size_t mjb_rowblock_doubles(int nefcmax, int nv, int nconmax, int 
 {
 	return (size_t)nefcmax * nv + (size_t)8 * nefcmax + (size_t)hcs * nconmax + (size_t)2 * nefcmax;
 }
-// doubles per env of DevState::env_mass: the mass section (7 nbody + nv + ntendon + 1), then the joint section (4 nv + njnt + 6 nu)
-MJB_HD inline int mjb_env_block_doubles(int nbody, int nv, int ntendon, int njnt, int nu)
+// One env's block of DevState::env_mass: the offset of each section, in doubles and in this order.  The sections up to mass_doubles are the
+// public mass block (mjb_set_env_mass_params, mjb_env_mass_stride), the rest is the joint section; doubles is the stride.  Host, kernels and
+// the lane = env overlay all index the block through this one definition.
+struct EnvBlockLayout {
+	int body_mass, body_subtreemass, body_inertia /* [3] */, dof_invweight0, body_invweight0 /* [2] */, tendon_invweight0, meaninertia, mass_doubles;
+	int dof_damping, dof_armature, dof_frictionloss, dof_damping_int, jnt_stiffness, actuator_gainprm /* [3] */, actuator_biasprm /* [3] */, doubles;
+};
+MJB_HD constexpr EnvBlockLayout mjb_env_block_layout(int nbody, int nv, int ntendon, int njnt, int nu)
 {
-	return 7 * nbody + nv + ntendon + 1 + 4 * nv + njnt + 6 * nu;
+	EnvBlockLayout B{};
+	int o = 0;
+	B.body_mass = o, o += nbody;
+	B.body_subtreemass = o, o += nbody;
+	B.body_inertia = o, o += 3 * nbody;
+	B.dof_invweight0 = o, o += nv;
+	B.body_invweight0 = o, o += 2 * nbody;
+	B.tendon_invweight0 = o, o += ntendon;
+	B.meaninertia = o, o += 1;
+	B.mass_doubles = o;
+	B.dof_damping = o, o += nv;
+	B.dof_armature = o, o += nv;
+	B.dof_frictionloss = o, o += nv;
+	B.dof_damping_int = o, o += nv;
+	B.jnt_stiffness = o, o += njnt;
+	B.actuator_gainprm = o, o += 3 * nu;
+	B.actuator_biasprm = o, o += 3 * nu;
+	B.doubles = o;
+	return B;
 }
+inline EnvBlockLayout mjb_env_block_layout(const mjb_model_desc &h) { return mjb_env_block_layout(h.nbody, h.nv, h.ntendon, h.njnt, h.nu); }
+// The public packed joint block (mjb_set_env_joint_params, mjb_env_joint_stride) is the joint section without dof_damping_int, which the
+// engine derives: where the section at block offset `off` sits in it (off = doubles: its length)
+MJB_HD constexpr int mjb_env_joint_packed(const EnvBlockLayout &B, int off)
+{
+	return off - B.mass_doubles - (off > B.dof_damping_int ? B.jnt_stiffness - B.dof_damping_int : 0);
+}
+namespace mjb_env_block_sample {  // the format, pinned on (nbody, nv, ntendon, njnt, nu) = (3, 4, 2, 5, 6)
+constexpr EnvBlockLayout B = mjb_env_block_layout(3, 4, 2, 5, 6);
+static_assert(B.body_mass == 0 && B.body_subtreemass == 3 && B.body_inertia == 6 && B.dof_invweight0 == 15 && B.body_invweight0 == 19 &&
+                  B.tendon_invweight0 == 25 && B.meaninertia == 27 && B.mass_doubles == 28,
+              "mass section of the per-env block");
+static_assert(B.dof_damping == 28 && B.dof_armature == 32 && B.dof_frictionloss == 36 && B.dof_damping_int == 40 && B.jnt_stiffness == 44 &&
+                  B.actuator_gainprm == 49 && B.actuator_biasprm == 67 && B.doubles == 85,
+              "joint section of the per-env block");
+static_assert(mjb_env_joint_packed(B, B.dof_damping) == 0 && mjb_env_joint_packed(B, B.dof_frictionloss) == 8 && mjb_env_joint_packed(B, B.jnt_stiffness) == 12 &&
+                  mjb_env_joint_packed(B, B.actuator_biasprm) == 35 && mjb_env_joint_packed(B, B.doubles) == 53,
+              "public packed joint block: 3 nv + njnt + 6 nu");
+}  // namespace mjb_env_block_sample
 struct RowBlock {
 	double *J, *D, *aref, *b, *force, *fl, *nwt_row, *hc;
 	int *type, *id, *meta;

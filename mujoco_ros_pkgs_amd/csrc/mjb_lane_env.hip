@@ -726,11 +726,12 @@ int mjb_lane_env_xfrc_fill(const mjb_model_desc *h, const double *xfrc_applied, 
 // gravity: the env's (NULL: the model's); env_block: the env's block of DevState::env_mass, mass and joint section (NULL: the model's values)
 void mjb_lane_env_overlay_row(const mjb_model_desc *h, const double *gravity, const double *env_block, double *out)
 {
-	const int nb = h->nbody, nv = h->nv, jnt0 = 7 * nb + nv + h->ntendon + 1;
-	const double *mass = env_block ? env_block : h->body_mass, *inertia = env_block ? env_block + 2 * nb : h->body_inertia;
-	const double *damping = env_block ? env_block + jnt0 : h->dof_damping, *armature = env_block ? env_block + jnt0 + nv : h->dof_armature;
-	const double *stiffness = env_block ? env_block + jnt0 + 4 * nv : h->jnt_stiffness;
-	const double *gain = env_block ? env_block + jnt0 + 4 * nv + h->njnt : h->actuator_gainprm, *bias = env_block ? gain + 3 * h->nu : h->actuator_biasprm;
+	const int nb = h->nbody;
+	const EnvBlockLayout B = mjb_env_block_layout(*h);
+	const double *mass = env_block ? env_block + B.body_mass : h->body_mass, *inertia = env_block ? env_block + B.body_inertia : h->body_inertia;
+	const double *damping = env_block ? env_block + B.dof_damping : h->dof_damping, *armature = env_block ? env_block + B.dof_armature : h->dof_armature;
+	const double *stiffness = env_block ? env_block + B.jnt_stiffness : h->jnt_stiffness;
+	const double *gain = env_block ? env_block + B.actuator_gainprm : h->actuator_gainprm, *bias = env_block ? env_block + B.actuator_biasprm : h->actuator_biasprm;
 	double *o = out;
 	for (int k = 0; k < 3; k++) *o++ = gravity ? gravity[k] : h->gravity[k];
 	for (int b = 1; b < nb; b++)

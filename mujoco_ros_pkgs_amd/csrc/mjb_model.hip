@@ -1394,13 +1394,14 @@ int mjb_model_lane_env_overlay(const mjb_model *m, double *out, int cap)
 int mjb_env_mass_stride(const mjb_model *m)
 {
 	if (!m) return fail(MJB_EINVAL, "null model");
-	return 7 * m->h.nbody + m->h.nv + m->h.ntendon + 1;
+	return mjb_env_block_layout(m->h).mass_doubles;
 }
 
 int mjb_env_joint_stride(const mjb_model *m)
 {
 	if (!m) return fail(MJB_EINVAL, "null model");
-	return 3 * m->h.nv + m->h.njnt + 6 * m->h.nu;
+	const EnvBlockLayout B = mjb_env_block_layout(m->h);
+	return mjb_env_joint_packed(B, B.doubles);
 }
 
 // ---- mj_setConst for new body masses (callbacks.cpp:251-256, :582), host side, plain C++ ----
@@ -1450,18 +1451,17 @@ int mjb_derive_mass_params_armature(const mjb_model *model, const double *body_m
 	const double *armature = dof_armature ? dof_armature : h.dof_armature;
 	const int nb = h.nbody, nv = h.nv, nj = h.njnt, nt = h.ntendon;
 	const double *inertia = body_inertia ? body_inertia : h.body_inertia;
-	double *o_mass = out, *o_sub = out + nb, *o_inert = out + 2 * nb, *o_dof = out + 5 * nb, *o_body = out + 5 * nb + nv,
-	       *o_ten = out + 7 * nb + nv, *o_mean = out + 7 * nb + nv + nt;
+	const EnvBlockLayout B = mjb_env_block_layout(h);  // out: the mass section of an env's block
 	for (int b = 0; b < nb; b++) {
-		o_mass[b] = body_mass[b];
-		o_sub[b] = body_mass[b];
-		for (int k = 0; k < 3; k++) o_inert[3 * b + k] = inertia[3 * b + k];
-		o_body[2 * b] = o_body[2 * b + 1] = 0;
+		out[B.body_mass + b] = body_mass[b];
+		out[B.body_subtreemass + b] = body_mass[b];
+		for (int k = 0; k < 3; k++) out[B.body_inertia + 3 * b + k] = inertia[3 * b + k];
+		out[B.body_invweight0 + 2 * b] = out[B.body_invweight0 + 2 * b + 1] = 0;
 	}
-	for (int b = nb - 1; b > 0; b--) o_sub[h.body_parentid[b]] += o_sub[b];
-	for (int i = 0; i < nv; i++) o_dof[i] = 0;
-	for (int t = 0; t < nt; t++) o_ten[t] = 0;
-	*o_mean = 1.0;
+	for (int b = nb - 1; b > 0; b--) out[B.body_subtreemass + h.body_parentid[b]] += out[B.body_subtreemass + b];
+	for (int i = 0; i < nv; i++) out[B.dof_invweight0 + i] = 0;
+	for (int t = 0; t < nt; t++) out[B.tendon_invweight0 + t] = 0;
+	out[B.meaninertia] = 1.0;
 	if (nv == 0) return MJB_OK;
 	// kinematics at qpos0
 	std::vector<double> xpos(3 * nb, 0.0), xquat(4 * nb, 0.0), xmat(9 * nb, 0.0), xipos(3 * nb, 0.0), ximat(9 * nb, 0.0), xanchor(3 * std::max(1, nj), 0.0),
@@ -1572,7 +1572,7 @@ int mjb_derive_mass_params_armature(const mjb_model *model, const double *body_m
 	}
 	double mean = 0;
 	for (int i = 0; i < nv; i++) mean += M[(size_t)i * nv + i];
-	*o_mean = mean / nv;
+	out[B.meaninertia] = mean / nv;
 	// M^-1 by Gauss-Jordan with partial pivoting (nv <= 64)
 	std::vector<double> A(M), Minv((size_t)nv * nv, 0.0);
 	for (int i = 0; i < nv; i++) Minv[(size_t)i * nv + i] = 1.0;
@@ -1607,24 +1607,24 @@ int mjb_derive_mass_params_armature(const mjb_model *model, const double *body_m
 		jac(b, &xipos[3 * b], jp, jr);
 		double tr = 0, ro = 0;
 		for (int k = 0; k < 3; k++) { tr += quad(&jp[(size_t)k * nv], &jp[(size_t)k * nv]); ro += quad(&jr[(size_t)k * nv], &jr[(size_t)k * nv]); }
-		o_body[2 * b] = tr / 3;
-		o_body[2 * b + 1] = ro / 3;
+		out[B.body_invweight0 + 2 * b] = tr / 3;
+		out[B.body_invweight0 + 2 * b + 1] = ro / 3;
 	}
 	for (int j = 0; j < nj; j++) {
 		const int d = h.jnt_dofadr[j], t = h.jnt_type[j];
 		auto tr3 = [&](int a) { return (Minv[(size_t)a * nv + a] + Minv[(size_t)(a + 1) * nv + a + 1] + Minv[(size_t)(a + 2) * nv + a + 2]) / 3; };
-		if (t == MJB_JNT_HINGE || t == MJB_JNT_SLIDE) o_dof[d] = Minv[(size_t)d * nv + d];
-		else if (t == MJB_JNT_BALL) o_dof[d] = o_dof[d + 1] = o_dof[d + 2] = tr3(d);
+		double *w = out + B.dof_invweight0 + d;  // the joint's dofs
+		if (t == MJB_JNT_HINGE || t == MJB_JNT_SLIDE) w[0] = Minv[(size_t)d * nv + d];
 		else {
-			o_dof[d] = o_dof[d + 1] = o_dof[d + 2] = tr3(d);
-			o_dof[d + 3] = o_dof[d + 4] = o_dof[d + 5] = tr3(d + 3);
+			w[0] = w[1] = w[2] = tr3(d);
+			if (t != MJB_JNT_BALL) w[3] = w[4] = w[5] = tr3(d + 3);  // (free joint: its rotational half)
 		}
 	}
 	std::vector<double> jt((size_t)nv);
 	for (int t = 0; t < nt; t++) {
 		std::fill(jt.begin(), jt.end(), 0.0);
 		for (int w = h.tendon_adr[t]; w < h.tendon_adr[t] + h.tendon_num[t]; w++) jt[h.jnt_dofadr[h.wrap_objid[w]]] += h.wrap_prm[w];
-		o_ten[t] = quad(jt.data(), jt.data());
+		out[B.tendon_invweight0 + t] = quad(jt.data(), jt.data());
 	}
 	return MJB_OK;
 }

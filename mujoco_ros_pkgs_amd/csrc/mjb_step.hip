@@ -272,24 +272,25 @@ DEVI EnvLite lite(const Env &e) { return EnvLite{ e.f, e.fi, e.lane, e.env, e.mp
 
 // per-env inertial constants (what mj_setConst derives from the masses): the env's own block in HBM when the batch carries
 // overrides (mjb_set_env_mass_params; the dense kernels are not used then), else the model's tables
-#define MP_BODY_MASS(m, e, i) ((e).mp ? (e).mp[(i)] : (m).body_mass[(i)])
-#define MP_SUBTREEMASS(m, e, i) ((e).mp ? (e).mp[(m).nbody + (i)] : (m).body_subtreemass[(i)])
-#define MP_INERTIA(m, e, i, k) ((e).mp ? (e).mp[2 * (m).nbody + 3 * (i) + (k)] : (m).body_inertia[3 * (i) + (k)])
-#define MP_DOF_INVW(m, e, i) ((e).mp ? (e).mp[5 * (m).nbody + (i)] : (m).dof_invweight0[(i)])
-#define MP_BODY_INVW(m, e, i) ((e).mp ? (e).mp[5 * (m).nbody + (m).nv + (i)] : (m).body_invweight0[(i)])
-#define MP_TEN_INVW(m, e, i) ((e).mp ? (e).mp[7 * (m).nbody + (m).nv + (i)] : (m).tendon_invweight0[(i)])
-#define MP_MEANINERTIA(m, e) ((e).mp ? (e).mp[7 * (m).nbody + (m).nv + (m).ntendon] : (m).meaninertia[0])
-// ... and, behind the inertial section of the same block, the env's joint and actuator constants (mjb_set_env_dof_params /
-// mjb_set_env_joint_stiffness / mjb_set_env_actuator_params): dof_damping[nv] | dof_armature[nv] | dof_frictionloss[nv] |
-// dof_damping_int[nv] | jnt_stiffness[njnt] | actuator_gainprm[nu][3] | actuator_biasprm[nu][3]  (mjb_env_block_doubles, mjb_dev.h)
-#define MP_JNT0(m) (7 * (m).nbody + (m).nv + (m).ntendon + 1)
-#define MP_DOF_DAMPING(m, e, i) ((e).mp ? (e).mp[MP_JNT0(m) + (i)] : (m).dof_damping[(i)])
-#define MP_DOF_ARMATURE(m, e, i) ((e).mp ? (e).mp[MP_JNT0(m) + (m).nv + (i)] : (m).dof_armature[(i)])
-#define MP_DOF_FRICTIONLOSS(m, e, i) ((e).mp ? (e).mp[MP_JNT0(m) + 2 * (m).nv + (i)] : (m).dof_frictionloss[(i)])
-#define MP_DOF_DAMPING_INT(m, e, i) ((e).mp ? (e).mp[MP_JNT0(m) + 3 * (m).nv + (i)] : (m).dof_damping_int[(i)])
-#define MP_JNT_STIFFNESS(m, e, j) ((e).mp ? (e).mp[MP_JNT0(m) + 4 * (m).nv + (j)] : (m).jnt_stiffness[(j)])
-#define MP_ACT_GAINPRM(m, mp, k) ((mp) ? (mp)[MP_JNT0(m) + 4 * (m).nv + (m).njnt + (k)] : (m).actuator_gainprm[(k)])
-#define MP_ACT_BIASPRM(m, mp, k) ((mp) ? (mp)[MP_JNT0(m) + 4 * (m).nv + (m).njnt + 3 * (m).nu + (k)] : (m).actuator_biasprm[(k)])
+// ... and, behind them in the same block, the env's joint and actuator constants (mjb_set_env_dof_params / mjb_set_env_joint_stiffness /
+// mjb_set_env_actuator_params).  A section of the block carries the name of the model array it stands in for (EnvBlockLayout, mjb_dev.h);
+// the layout is computed at each use, nothing of it lives across stages.
+#define MP_ENV_LAYOUT(m) mjb_env_block_layout((m).nbody, (m).nv, (m).ntendon, (m).njnt, (m).nu)
+#define MP_GET(m, mp, field, i) ((mp) ? (mp)[MP_ENV_LAYOUT(m).field + (i)] : (m).field[(i)])
+#define MP_BODY_MASS(m, e, i) MP_GET(m, (e).mp, body_mass, i)
+#define MP_SUBTREEMASS(m, e, i) MP_GET(m, (e).mp, body_subtreemass, i)
+#define MP_INERTIA(m, e, i, k) MP_GET(m, (e).mp, body_inertia, 3 * (i) + (k))
+#define MP_DOF_INVW(m, e, i) MP_GET(m, (e).mp, dof_invweight0, i)
+#define MP_BODY_INVW(m, e, i) MP_GET(m, (e).mp, body_invweight0, i)
+#define MP_TEN_INVW(m, e, i) MP_GET(m, (e).mp, tendon_invweight0, i)
+#define MP_MEANINERTIA(m, e) MP_GET(m, (e).mp, meaninertia, 0)
+#define MP_DOF_DAMPING(m, e, i) MP_GET(m, (e).mp, dof_damping, i)
+#define MP_DOF_ARMATURE(m, e, i) MP_GET(m, (e).mp, dof_armature, i)
+#define MP_DOF_FRICTIONLOSS(m, e, i) MP_GET(m, (e).mp, dof_frictionloss, i)
+#define MP_DOF_DAMPING_INT(m, e, i) MP_GET(m, (e).mp, dof_damping_int, i)
+#define MP_JNT_STIFFNESS(m, e, j) MP_GET(m, (e).mp, jnt_stiffness, j)
+#define MP_ACT_GAINPRM(m, mp, k) MP_GET(m, mp, actuator_gainprm, k)
+#define MP_ACT_BIASPRM(m, mp, k) MP_GET(m, mp, actuator_biasprm, k)
 
 // ------------------------------------------------------------------------------------------------
 // A1  kinematics: body frames, joint anchors/axes, inertial / geom / site frames
@@ -3689,7 +3690,7 @@ __global__ void __launch_bounds__(256, mjb_kv_min_waves(CON, G, MJB_DEV_OCC))
 		}
 		if constexpr (G == 64) e.env = __builtin_amdgcn_readfirstlane(e.env);  // (one env per wavefront: keep the index and everything derived from it scalar)
 		if (e.env >= env_hi) continue;  // whole group idles together (group == slot)
-		if constexpr (DENSE == 0) e.mp = s.env_mass ? s.env_mass + (size_t)e.env * mjb_env_block_doubles(m.nbody, m.nv, m.ntendon, m.njnt, m.nu) : nullptr;
+		if constexpr (DENSE == 0) e.mp = s.env_mass ? s.env_mass + (size_t)e.env * MP_ENV_LAYOUT(m).doubles : nullptr;
 		else e.mp = nullptr;  // (batches with per-env masses / joint parameters never run the dense kernels)
 		double *ws = s.frame_ws ? s.frame_ws + (size_t)e.env * s.frame_stride : nullptr;
 		if constexpr (HBMF) {
