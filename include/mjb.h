@@ -595,6 +595,46 @@ int mjb_jac_get(mjb_batch *b, int which, int env_lo, int env_hi, double *host); 
 void *mjb_jac_device_ptr(mjb_batch *b, int which);                /* which = one MJB_JAC_OUT_* bit */
 int mjb_jac_count(const mjb_batch *b);                            /* points per env of the configuration, 0: none yet */
 
+/* ---- batched contact wrenches: mj_contactForce and net contact forces between geom sets, for every env at once ----
+ * Contact c of an env is read from the frame workspace (ncon, contact_geom, contact_dim, contact_efc_address, contact_frame, contact_pos,
+ * contact_dist, contact_friction, efc_force).  A contact with contact_efc_address[c] < 0 has no rows and takes no part in any output.
+ *   lf[6]  its local wrench, mj_contactForce: dim 1: lf[0] = efc_force[adr];  elliptic cone: lf[k] = efc_force[adr + k], k < dim;  pyramidal cone:
+ *          lf[0] = sum of the 2 (dim - 1) edge forces, lf[1 + k] = (efc_force[adr + 2 k] - efc_force[adr + 2 k + 1]) contact_friction[c][k] -- the
+ *          frame's contact_friction, so per-env geom friction (mjb_set_env_geom_friction) is honoured.  The other entries are 0.
+ *   F, T   its world force F = contact_frame' lf[0:3] and world torque at contact_pos T = contact_frame' lf[3:6].  (F, T) acts with + on the body
+ *          of contact_geom[c][1] and with - on the body of contact_geom[c][0] (mj_rnePostConstraint's sign).
+ * Query q is two geom sets A and B, byte masks over the model's geoms (non-zero = member).  Contact (g1, g2) = contact_geom[c] matches q with sign
+ * +1 when g2 is in A and g1 in B, with sign -1 when g1 is in A and g2 in B; A and B are disjoint, so no contact matches both ways.
+ * Results are env-major; only the requested outputs are allocated and computed:
+ *   MJB_CON_OUT_WRENCH    [nenv][nquery][6]  double  net force (3), then torque (3), in world axes, that the B side exerts on the A side.  The torque
+ *                                                    is taken about r_q = xpos[ref_body[q]] of the same frame (the world origin for ref_body -1): each
+ *                                                    matching contact adds sign (F, T + (contact_pos - r_q) x F), summed in ascending c
+ *   MJB_CON_OUT_NORMAL    [nenv][nquery]     double  sum of lf[0] over the matching contacts in ascending c: what a touch sensor reports for a zone that
+ *                                                    holds them all
+ *   MJB_CON_OUT_COUNT     [nenv][nquery]     int32   number of matching contacts
+ *   MJB_CON_OUT_DIST      [nenv][nquery]     double  smallest contact_dist of the matching contacts, +inf when there is none
+ *   MJB_CON_OUT_CONTACTS  [nenv][nconmax][6] double  lf of every contact c < ncon in the contact's own frame, normal first; exactly 0.0 for
+ *                                                    c >= ncon and for contacts without rows
+ * No result depends on the shape of the launch: every value is computed by one lane, in a fixed order, from operands that do not depend on the
+ * batch's size or on the number of queries.  An env without a matching contact has WRENCH and NORMAL exactly 0.0, COUNT 0 and DIST +inf.  Swapping A
+ * and B under the same ref_body negates WRENCH to the bit (the same terms in the same order with the opposite sign).
+ * Capacity: contacts dropped when an env's contact list is full (the CONTACTFULL warning) are not in the frame and therefore not in the sums.
+ * mjb_contact_configure validates (MJB_EINVAL: nquery < 1, a model with nconmax == 0 or ngeom == 0, an empty A or B, A and B with a common geom,
+ * a ref_body outside [-1, nbody), outputs 0 or with unknown bits), synchronises the stream, uploads the masks and (re)allocates the requested
+ * outputs only; a second call replaces the first.  mjb_contact_eval reads derived fields, so like mjb_get it is MJB_EINVAL unless the frame
+ * workspace is current for every env; it is MJB_EINVAL, too, when the frame was last written by mjb_step1 / mjb_step1_prefix and no mjb_step2* has
+ * followed: the frame's contacts are then this state's, but efc_force is not.  It is legal after mjb_forward, mjb_step2 and a fused step with
+ * keep_frame; not after mjb_reset / mjb_episode_* until the next forward pass or step.  It runs on the batch's stream behind the launch that
+ * produced the frame.  After a step the frame holds the step's forward pass: the contacts and forces BEFORE the integration, as mjData after mj_step.
+ * mjb_contact_get / mjb_contact_device_ptr of an output that was not configured: MJB_EINVAL / NULL. */
+enum { MJB_CON_OUT_WRENCH = 1, MJB_CON_OUT_NORMAL = 2, MJB_CON_OUT_COUNT = 4, MJB_CON_OUT_DIST = 8, MJB_CON_OUT_CONTACTS = 16 };
+int mjb_contact_configure(mjb_batch *b, int nquery, const unsigned char *geom_a /*[nquery][ngeom]*/, const unsigned char *geom_b /*[nquery][ngeom]*/,
+                          const int *ref_body /*[nquery], -1 = world origin; NULL = all -1*/, int outputs /*MJB_CON_OUT_* bits*/);
+int mjb_contact_eval(mjb_batch *b);                               /* asynchronous on the batch's stream */
+int mjb_contact_get(mjb_batch *b, int which, int env_lo, int env_hi, void *host);   /* synchronises; which = one MJB_CON_OUT_* bit (COUNT: int32, the others double) */
+void *mjb_contact_device_ptr(mjb_batch *b, int which);            /* which = one MJB_CON_OUT_* bit */
+int mjb_contact_count(const mjb_batch *b);                        /* queries of the configuration, 0: none yet */
+
 /* ---- device-side episode resets (MujocoEnv::resetSim: mj_resetData, then loadInitialJointStates, /root/reference mujoco_ros/src/mujoco_env.cpp:246-264) ----
  * mjb_reset takes a host mask and can only put an env back to qpos0.  These calls end and restart episodes without leaving the device: ONE launch
  * on the batch's stream decides for every env whether its episode is over, writes done[nenv] (uint8, 1 / 0) and ndone (one uint32, their sum), and
@@ -619,7 +659,7 @@ int mjb_jac_count(const mjb_batch *b);                            /* points per 
  * What the rule sees: it is evaluated between launches, on the state as the last launch left it.  With K fused steps (mjb_step(b, K)) an env may run
  * up to K - 1 steps past its limit before it is reset; resets inside the step kernel are out of scope (the step's own mj_check* auto-reset to qpos0
  * is unchanged).
- * Like mjb_reset, both calls abandon an open split step and leave the derived fields unreadable (mjb_get of one, mjb_rays_cast, mjb_jac_eval:
+ * Like mjb_reset, both calls abandon an open split step and leave the derived fields unreadable (mjb_get of one, mjb_rays_cast, mjb_jac_eval, mjb_contact_eval:
  * MJB_EINVAL) until mjb_forward or a step. */
 /* The initial-state bank: qpos [ninit][nq], qvel [ninit][nv], act [ninit][na], copied to the device.  ninit == 0 clears it; qvel / act NULL = zeros.
  * MJB_EINVAL: ninit < 0, a non-finite entry, a zero quaternion in a ball or free joint. */

@@ -205,6 +205,11 @@ def load_library(path=None):
         "mjb_jac_get": (ci, [vp, ci, ci, ci, C.POINTER(cd)]),
         "mjb_jac_device_ptr": (vp, [vp, ci]),
         "mjb_jac_count": (ci, [vp]),
+        "mjb_contact_configure": (ci, [vp, ci, C.POINTER(C.c_uint8), C.POINTER(C.c_uint8), C.POINTER(ci), ci]),
+        "mjb_contact_eval": (ci, [vp]),
+        "mjb_contact_get": (ci, [vp, ci, ci, ci, vp]),
+        "mjb_contact_device_ptr": (vp, [vp, ci]),
+        "mjb_contact_count": (ci, [vp]),
         "mjb_episode_set_init": (ci, [vp, ci, C.POINTER(cd), C.POINTER(cd), C.POINTER(cd)]),
         "mjb_episode_set_noise": (ci, [vp, C.c_uint64, C.c_int64, C.POINTER(cd), C.POINTER(cd), C.POINTER(cd), C.POINTER(cd), ci]),
         "mjb_episode_set_rule": (ci, [vp, cd, C.POINTER(cd), C.POINTER(cd)]),

@@ -17,6 +17,7 @@
 
 #include "mjb_dev.h"
 #include "mjb_episode.h"
+#include "mjb_contact.h"
 #include "mjb_jac.h"
 #include "mjb_model.h"
 #include "mjb_resources.h"
@@ -53,6 +54,11 @@ struct RayBufs {  // batched ray casting (mjb_rays_*): the ray / mask table of m
 struct JacBufs {  // batched Jacobians (mjb_jac_*): the point table of mjb_launch_jac and the outputs that were asked for (the others stay empty)
 	DevBuf<double> tab;
 	DevBuf<double> J, MinvJT, Ainv, vel;
+};
+struct ConBufs {  // batched contact wrenches (mjb_contact_*): the query table of mjb_launch_contact and the outputs that were asked for (the others stay empty)
+	DevBuf<unsigned int> tab;
+	DevBuf<double> wrench, normal, dist, contacts;
+	DevBuf<int> count;
 };
 struct EpisodeBufs {  // device-side episode resets (mjb_episode_*): the configuration the kernel reads and its outputs
 	DevBuf<double> bank;          // qpos[ninit][nq] | qvel[ninit][nv] | act[ninit][na] (mjb_episode_set_init)
@@ -92,6 +98,8 @@ struct mjb_batch {
 	int lanes = 0, epb = 0;
 	unsigned int step_counter = 0;
 	bool frame_valid = false;
+	bool frame_half = false;      // the frame's last writer was a step's first half (mjb_step1 / mjb_step1_prefix, or a closer that ends in one): its contacts are
+	                              // this state's, efc_force is not -- mjb_contact_eval refuses it
 	int frame_hi = 0;             // the frame workspace is current for envs [0, frame_hi) (a prefix after mjb_step1_prefix)
 	int split_ncb = -1;           // inside a split step of this prefix (mjb_step1_prefix .. mjb_step2_prefix)
 	bool split_rest_done = false;
@@ -121,6 +129,8 @@ struct mjb_batch {
 	int nray = 0;                     // rays per env of that configuration (0: none yet)
 	JacBufs jac;                      // mjb_jac_configure
 	int njac = 0, jac_outputs = 0;    // points per env of that configuration (0: none yet), its MJB_JAC_OUT_* bits
+	ConBufs con;                      // mjb_contact_configure
+	int ncquery = 0, con_outputs = 0; // queries of that configuration (0: none yet), its MJB_CON_OUT_* bits
 	EpisodeBufs epi;                  // mjb_episode_*: the outputs are allocated at the first call that needs them
 	int ep_ninit = 0, ep_clamp = 0;   // rows of the bank, clip limited hinge / slide joints to their range
 	unsigned long long ep_seed = 0;   // Philox key of the episode stream ...
@@ -958,6 +968,7 @@ int mjb_step(mjb_batch *b, int nsteps)
 		b->step_counter += (unsigned int)nsteps;
 		b->steps_taken += (unsigned long long)nsteps;
 		b->frame_valid = b->st.keep_frame != 0;
+		b->frame_half = false;
 		b->frame_hi = b->nenv;
 		b->pose_written = false;
 	}
@@ -988,6 +999,7 @@ static int forward_whole(mjb_batch *b, int mode)
 	int rc = launch(b, mode, 1);
 	if (rc == MJB_OK) {
 		b->frame_valid = true;
+		b->frame_half = mode == MJB_MODE_STEP1;
 		b->frame_hi = b->nenv;
 		b->pose_written = false;
 	}
@@ -1004,6 +1016,7 @@ int mjb_step2(mjb_batch *b)
 	if (rc == MJB_OK) {
 		b->step_counter += 1;
 		b->steps_taken += 1;
+		b->frame_half = false;
 	}
 	return rc;
 }
@@ -1033,6 +1046,7 @@ int mjb_step1_prefix(mjb_batch *b, int ncb)
 	rc = launch(b, MJB_MODE_STEP1, 1, 0, ncb);
 	if (rc == MJB_OK) {
 		b->frame_valid = true;
+		b->frame_half = true;
 		b->frame_hi = ncb;
 		b->pose_written = false;
 	}
@@ -1090,7 +1104,10 @@ int mjb_step2_prefix(mjb_batch *b, int ncb)
 	if (rc != MJB_OK) return rc;
 	if (ncb > 0) rc = launch(b, MJB_MODE_STEP2, 1, 0, ncb);
 	rc = prefix_step_done(b, rc);
-	if (rc == MJB_OK) b->split_ncb = -1;
+	if (rc == MJB_OK) {
+		b->split_ncb = -1;
+		b->frame_half = false;
+	}
 	return rc;
 }
 
@@ -1107,6 +1124,7 @@ int mjb_step21_prefix(mjb_batch *b, int ncb)
 		b->split_ncb = ncb;  // ... and the next split step is open: its first half has run
 		b->split_rest_done = false;
 		b->frame_valid = true;
+		b->frame_half = true;
 		b->frame_hi = ncb;
 		b->pose_written = false;
 	}
@@ -1126,9 +1144,12 @@ int mjb_step2_rk_prefix(mjb_batch *b, int ncb, int rk)
 	int rc = prefix_second_half(b, ncb, "mjb_step2_rk_prefix");
 	if (rc != MJB_OK) return rc;
 	if (ncb > 0) rc = launch(b, rk == 3 ? MJB_MODE_RKLAST : MJB_MODE_RKMID, rk, 0, ncb);  // (the evaluation index travels as the kernel's nsteps)
-	if (rc != MJB_OK || rk < 3) return rc;
+	if (rc != MJB_OK || rk < 3) return rc;  // (rk < 3 ends in the first half of the next evaluation: frame_half stays)
 	rc = prefix_step_done(b, rc);
-	if (rc == MJB_OK) b->split_ncb = -1;
+	if (rc == MJB_OK) {
+		b->split_ncb = -1;
+		b->frame_half = false;
+	}
 	return rc;
 }
 
@@ -2462,6 +2483,109 @@ void *mjb_jac_device_ptr(mjb_batch *b, int which)
 }
 
 int mjb_jac_count(const mjb_batch *b) { return b ? b->njac : fail(MJB_EINVAL, "null batch"); }
+
+// ---- batched contact wrenches (kernel in mjb_contact.hip) ----
+static const int kConOutputs = MJB_CON_OUT_WRENCH | MJB_CON_OUT_NORMAL | MJB_CON_OUT_COUNT | MJB_CON_OUT_DIST | MJB_CON_OUT_CONTACTS;
+// the device address of one output bit, its elements per env and their size; NULL: not one bit, or not configured
+static void *con_output(mjb_batch *b, int which, size_t *per_env, size_t *elem)
+{
+	if (!(which & b->con_outputs)) return nullptr;
+	const size_t nq = (size_t)b->ncquery;
+	*elem = sizeof(double);
+	switch (which) {
+	case MJB_CON_OUT_WRENCH: *per_env = nq * 6; return b->con.wrench.get();
+	case MJB_CON_OUT_NORMAL: *per_env = nq; return b->con.normal.get();
+	case MJB_CON_OUT_COUNT: *per_env = nq; *elem = sizeof(int); return b->con.count.get();
+	case MJB_CON_OUT_DIST: *per_env = nq; return b->con.dist.get();
+	case MJB_CON_OUT_CONTACTS: *per_env = (size_t)b->model->h.nconmax * 6; return b->con.contacts.get();
+	default: return nullptr;
+	}
+}
+
+int mjb_contact_configure(mjb_batch *b, int nquery, const unsigned char *geom_a, const unsigned char *geom_b, const int *ref_body, int outputs)
+{
+	if (!b) return fail(MJB_EINVAL, "null batch");
+	const mjb_model_desc &h = b->model->h;
+	if (nquery < 1 || !geom_a || !geom_b) return fail(MJB_EINVAL, "mjb_contact_configure: nquery must be at least 1, with two geom sets per query");
+	if (outputs == 0 || (outputs & ~kConOutputs)) return fail(MJB_EINVAL, "mjb_contact_configure: outputs 0x%x: at least one of the MJB_CON_OUT_* bits and no other", (unsigned)outputs);
+	if (h.nconmax < 1 || h.ngeom < 1) return fail(MJB_EINVAL, "mjb_contact_configure: the model has no contacts (nconmax %d, ngeom %d)", h.nconmax, h.ngeom);
+	// the table of mjb_launch_contact (mjb_contact.h): mask[nquery][2][nwords] as bit words, then ref_body[nquery]
+	const size_t n = (size_t)nquery, ng = (size_t)h.ngeom, nw = (size_t)mjb_contact_mask_words(h.ngeom), nwords = mjb_contact_table_words(h.ngeom, nquery);
+	std::vector<unsigned int> tab(nwords, 0u);
+	for (size_t q = 0; q < n; q++) {
+		size_t na = 0, nb = 0;
+		for (size_t g = 0; g < ng; g++) {
+			const bool a = geom_a[q * ng + g] != 0, bb = geom_b[q * ng + g] != 0;
+			if (a && bb) return fail(MJB_EINVAL, "mjb_contact_configure: query %zu: geom %zu is in both sets", q, g);
+			if (a) tab[(q * 2) * nw + (g >> 5)] |= 1u << (g & 31), na++;
+			if (bb) tab[(q * 2 + 1) * nw + (g >> 5)] |= 1u << (g & 31), nb++;
+		}
+		if (na == 0 || nb == 0) return fail(MJB_EINVAL, "mjb_contact_configure: query %zu: set %s is empty", q, na == 0 ? "A" : "B");
+		const int rb = ref_body ? ref_body[q] : -1;
+		if (rb < -1 || rb >= h.nbody) return fail(MJB_EINVAL, "mjb_contact_configure: query %zu: ref_body %d outside [-1, %d)", q, rb, h.nbody);
+		tab[n * 2 * nw + q] = (unsigned int)rb;
+	}
+	HIP_TRY(hipSetDevice(b->device));
+	HIP_TRY(hipStreamSynchronize(b->stream.get()));  // (an evaluation of the previous configuration may still read what goes now)
+	ConBufs cb;
+	const size_t ne = (size_t)b->nenv;
+	if (!cb.tab.alloc(nwords) || ((outputs & MJB_CON_OUT_WRENCH) && !cb.wrench.alloc_zeroed(ne * n * 6)) || ((outputs & MJB_CON_OUT_NORMAL) && !cb.normal.alloc_zeroed(ne * n)) ||
+	    ((outputs & MJB_CON_OUT_COUNT) && !cb.count.alloc_zeroed(ne * n)) || ((outputs & MJB_CON_OUT_DIST) && !cb.dist.alloc_zeroed(ne * n)) ||
+	    ((outputs & MJB_CON_OUT_CONTACTS) && !cb.contacts.alloc_zeroed(ne * (size_t)h.nconmax * 6)))
+		return fail(MJB_ENOMEM, "mjb_contact_configure: allocation failed for %d envs x %d queries", b->nenv, nquery);
+	HIP_TRY(hipMemcpy(cb.tab.get(), tab.data(), nwords * sizeof(unsigned int), hipMemcpyHostToDevice));
+	b->con = std::move(cb);
+	b->ncquery = nquery;
+	b->con_outputs = outputs;
+	return MJB_OK;
+}
+
+int mjb_contact_eval(mjb_batch *b)
+{
+	if (!b) return fail(MJB_EINVAL, "null batch");
+	if (b->ncquery < 1) return fail(MJB_EINVAL, "mjb_contact_eval before mjb_contact_configure");
+	if (!b->frame_valid || !b->st.frame_ws || b->frame_hi < b->nenv)
+		return fail(MJB_EINVAL, "mjb_contact_eval reads the contacts and efc_force of every env: only after mjb_forward / mjb_step2, or a fused step with keep_frame");
+	if (b->frame_half)
+		return fail(MJB_EINVAL, "mjb_contact_eval: the frame was written by mjb_step1 and no mjb_step2 has followed, its efc_force is not this state's: only after mjb_forward / "
+		                        "mjb_step2, or a fused step with keep_frame");
+	HIP_TRY(hipSetDevice(b->device));
+	if (int rc = join_rest(b)) return rc;
+	if (int rc = sync_params(b)) return rc;
+	const int rc = mjb_launch_contact(b->params_dev.get(), b->con.tab.get(), b->nenv, b->ncquery, b->model->h.ngeom, b->model->h.nconmax, b->con.wrench.get(), b->con.normal.get(),
+	                                  b->con.count.get(), b->con.dist.get(), b->con.contacts.get(), b->stream.get());
+	if (rc != 0) return fail(MJB_ENODEVICE, "contact wrench launch failed: %s", hipGetErrorString((hipError_t)rc));
+	return MJB_OK;
+}
+
+int mjb_contact_get(mjb_batch *b, int which, int env_lo, int env_hi, void *host)
+{
+	if (!b) return fail(MJB_EINVAL, "null batch");
+	if (b->ncquery < 1) return fail(MJB_EINVAL, "mjb_contact_get before mjb_contact_configure");
+	size_t per_env = 0, elem = 0;
+	const char *buf = static_cast<const char *>(con_output(b, which, &per_env, &elem));
+	if (!buf) return fail(MJB_EINVAL, "mjb_contact_get: output 0x%x is not one MJB_CON_OUT_* bit of the configuration (0x%x)", (unsigned)which, (unsigned)b->con_outputs);
+	if (env_lo < 0 || env_hi > b->nenv || env_lo > env_hi) return fail(MJB_ERANGE, "env range [%d,%d) outside [0,%d)", env_lo, env_hi, b->nenv);
+	const size_t n = (size_t)(env_hi - env_lo) * per_env * elem, off = (size_t)env_lo * per_env * elem;
+	if (n && !host) return fail(MJB_EINVAL, "null host buffer");
+	HIP_TRY(hipSetDevice(b->device));
+	HIP_TRY(hipStreamSynchronize(b->stream.get()));
+	if (n) HIP_TRY(hipMemcpy(host, buf + off, n, hipMemcpyDeviceToHost));
+	return MJB_OK;
+}
+
+void *mjb_contact_device_ptr(mjb_batch *b, int which)
+{
+	size_t per_env = 0, elem = 0;
+	void *buf = (b && b->ncquery >= 1) ? con_output(b, which, &per_env, &elem) : nullptr;
+	if (!buf) {
+		fail(MJB_EINVAL, "mjb_contact_device_ptr: bad argument, or an output that mjb_contact_configure was not asked for");
+		return nullptr;
+	}
+	return buf;
+}
+
+int mjb_contact_count(const mjb_batch *b) { return b ? b->ncquery : fail(MJB_EINVAL, "null batch"); }
 
 // ---- device-side episode resets (kernel in mjb_episode.hip) ----
 // done | episode | ndone, zeroed: made by the first call that launches the kernel or hands out their addresses

@@ -70,6 +70,27 @@ def lidar_rays(n_azimuth, elevations_deg=(0.0,), azimuth_range_deg=(0.0, 360.0))
     return v.reshape(-1, 3)
 
 
+def geoms_of_bodies(model, bodies, subtree=False):
+    """Geom ids (ascending) of the given bodies -- names or ids, one or a sequence -- and, with subtree=True, of every body below them: a geom set for
+    Batch.set_contact_queries.  Plain numpy."""
+    names = model["names"]["body"]
+    nbody = int(model["nbody"])
+    want = np.zeros(nbody, bool)
+    for b in ([bodies] if isinstance(bodies, (str, int, np.integer)) else list(bodies)):
+        if isinstance(b, str):
+            if b not in names:
+                raise ValueError(f"geoms_of_bodies: no body named {b!r}")
+            b = names.index(b)
+        if not 0 <= int(b) < nbody:
+            raise ValueError(f"geoms_of_bodies: body {int(b)} outside [0, {nbody})")
+        want[int(b)] = True
+    if subtree:
+        parent = np.asarray(model["body_parentid"], dtype=np.int64)
+        for b in range(1, nbody):   # (a body's parent has a lower id)
+            want[b] |= want[parent[b]]
+    return [g for g in range(int(model["ngeom"])) if want[int(model["geom_bodyid"][g])]]
+
+
 class CompiledModel:
     def __init__(self, model):
         self.model = model
@@ -471,6 +492,87 @@ class Batch:
         if isinstance(which, str) and which not in self._JAC_OUTPUTS:
             raise ValueError(f"jac_device_ptr: unknown output {which!r} (J, MinvJT, Ainv, vel)")
         p = self.lib.mjb_jac_device_ptr(self.ptr, self._JAC_OUTPUTS[which] if isinstance(which, str) else int(which))
+        if not p:
+            raise EngineError(self.lib.mjb_last_error().decode())
+        return p
+
+    # ---- batched contact wrenches (mjb_contact_*) ----
+    _CON_OUTPUTS = {"wrench": 1, "normal": 2, "count": 4, "dist": 8, "contacts": 16}   # MJB_CON_OUT_* of include/mjb.h
+
+    def _geom_mask(self, geoms, what):
+        m = self.cm.model
+        ngeom = int(m["ngeom"])
+        mask = np.zeros(ngeom, np.uint8)
+        for g in ([geoms] if isinstance(geoms, (str, int, np.integer)) else list(geoms)):
+            if isinstance(g, str):
+                if g not in m["names"]["geom"]:
+                    raise ValueError(f"set_contact_queries: {what}: no geom named {g!r}")
+                g = m["names"]["geom"].index(g)
+            g = int(g)
+            if not 0 <= g < ngeom:
+                raise ValueError(f"set_contact_queries: {what}: geom {g} outside [0, {ngeom})")
+            mask[g] = 1
+        return mask
+
+    def set_contact_queries(self, queries, outputs=("wrench",), ref_body=None):
+        """The queries every env evaluates (mjb_contact_configure): `queries` is a list of (A, B) pairs of geom sets, each a sequence of geom ids or geom
+        names (geoms_of_bodies builds one from bodies); B = None means every geom not in A.  A contact (g1, g2) matches with sign +1 when g2 is in A and
+        g1 in B, with sign -1 when g1 is in A and g2 in B; A and B must be disjoint and neither may be empty.  ref_body: one body id or name per query
+        (or one for all) about whose xpos the torque of "wrench" is taken; None or -1 = the world origin.  outputs: any of "wrench", "normal", "count",
+        "dist", "contacts" -- only these are allocated and computed.  A second call replaces the first."""
+        m = self.cm.model
+        qs = list(queries)
+        n, ngeom = len(qs), int(m["ngeom"])
+        ga, gb = np.zeros((max(n, 1), ngeom), np.uint8), np.zeros((max(n, 1), ngeom), np.uint8)
+        for q, (A, B) in enumerate(qs):
+            ga[q] = self._geom_mask(A, f"query {q}, A")
+            gb[q] = (1 - ga[q]) if B is None else self._geom_mask(B, f"query {q}, B")
+        refs = [ref_body] * n if ref_body is None or isinstance(ref_body, (str, int, np.integer)) else list(ref_body)
+        if len(refs) != n:
+            raise ValueError(f"set_contact_queries: {len(refs)} ref_body entries for {n} queries")
+        unknown = [r for r in refs if isinstance(r, str) and r not in m["names"]["body"]]
+        if unknown:
+            raise ValueError(f"set_contact_queries: no body named {unknown[0]!r}")
+        rb = np.ascontiguousarray([-1 if r is None else (m["names"]["body"].index(r) if isinstance(r, str) else int(r)) for r in refs] or [-1], dtype=np.int32)
+        outs = (outputs,) if isinstance(outputs, str) else tuple(outputs)
+        unknown = [o for o in outs if o not in self._CON_OUTPUTS]
+        if unknown:
+            raise ValueError(f"set_contact_queries: unknown output {unknown[0]!r} (wrench, normal, count, dist, contacts)")
+        bits = 0
+        for o in outs:
+            bits |= self._CON_OUTPUTS[o]
+        pb = C.POINTER(C.c_uint8)
+        _check(self.lib.mjb_contact_configure(self.ptr, n, ga.ctypes.data_as(pb), gb.ctypes.data_as(pb), rb.ctypes.data_as(C.POINTER(C.c_int)), bits), "mjb_contact_configure")
+        self._con_outputs = tuple(k for k in self._CON_OUTPUTS if bits & self._CON_OUTPUTS[k])
+
+    def eval_contact_wrenches_async(self):
+        """Evaluate the configured outputs for every env on the batch's stream (mjb_contact_eval); needs current frames WITH their efc_force: forward(),
+        step2(), or step() with set_keep_frame() -- not between step1() and step2().  After a step the frame holds the contacts and forces before the
+        integration.  The results stay on the device (contact_device_ptr) until contact_wrenches() or the next evaluation."""
+        _check(self.lib.mjb_contact_eval(self.ptr), "mjb_contact_eval")
+
+    def contact_wrenches(self, lo=0, hi=None):
+        """Evaluate, wait, and return the configured outputs of envs [lo, hi) as a dict of arrays: "wrench" float64 [n, nquery, 6] (net force, then torque
+        about r_q, in world axes, that the B side exerts on the A side), "normal" float64 [n, nquery] (sum of the normal forces lf[0]), "count" int32
+        [n, nquery], "dist" float64 [n, nquery] (smallest contact_dist, +inf without a matching contact) and "contacts" float64 [n, nconmax, 6] (lf of
+        every contact in its own frame, normal first; 0.0 beyond ncon)."""
+        hi = self.nenv if hi is None else hi
+        self.eval_contact_wrenches_async()
+        n, nq, ncm = hi - lo, int(self.lib.mjb_contact_count(self.ptr)), int(self.cm.model["nconmax"])
+        shapes = {"wrench": (n, nq, 6), "normal": (n, nq), "count": (n, nq), "dist": (n, nq), "contacts": (n, ncm, 6)}
+        out = {}
+        for key in getattr(self, "_con_outputs", ()):
+            a = np.empty(shapes[key], dtype=np.int32 if key == "count" else np.float64)
+            _check(self.lib.mjb_contact_get(self.ptr, self._CON_OUTPUTS[key], lo, hi, a.ctypes.data_as(C.c_void_p)), "mjb_contact_get")
+            out[key] = a
+        return out
+
+    def contact_device_ptr(self, which):
+        """Device address of one output, by name ("wrench", "normal", "count", "dist", "contacts") or MJB_CON_OUT_* bit: env-major, the shapes and dtypes of
+        contact_wrenches()."""
+        if isinstance(which, str) and which not in self._CON_OUTPUTS:
+            raise ValueError(f"contact_device_ptr: unknown output {which!r} (wrench, normal, count, dist, contacts)")
+        p = self.lib.mjb_contact_device_ptr(self.ptr, self._CON_OUTPUTS[which] if isinstance(which, str) else int(which))
         if not p:
             raise EngineError(self.lib.mjb_last_error().decode())
         return p
