@@ -595,6 +595,47 @@ int mjb_jac_get(mjb_batch *b, int which, int env_lo, int env_hi, double *host); 
 void *mjb_jac_device_ptr(mjb_batch *b, int which);                /* which = one MJB_JAC_OUT_* bit */
 int mjb_jac_count(const mjb_batch *b);                            /* points per env of the configuration, 0: none yet */
 
+/* ---- batched joint-space dynamics: mj_fullM, mj_mulM, mj_solveM, inverse dynamics and Jdot qvel for every env at once ----
+ * The other half of a model-based control law next to mjb_jac_*: everything is read from the frame workspace, V is a block of nvec vectors per
+ * env that the batch owns ([nenv][nvec][nv], zero at configure; written through mjb_dyn_device_ptr(b, MJB_DYN_IN_V) on the batch's stream, or
+ * from the host with mjb_dyn_set_vectors, which synchronises).  Results are fp64 and env-major; only the outputs asked for are allocated and computed:
+ *   MJB_DYN_OUT_M      [nenv][nv][nv]      mj_fullM of the frame's qM: entry (i, j) is the qM element of the pair when one dof is the other's
+ *                                          ancestor-or-self along dof_parentid, a literal +0.0 otherwise; symmetric to the bit
+ *   MJB_DYN_OUT_MV     [nenv][nvec][nv]    M V[k] (mj_mulM): each row summed in ascending j with fused multiply-adds, structural zeros skipped
+ *   MJB_DYN_OUT_MINVV  [nenv][nvec][nv]    M^-1 V[k] (mj_solveM) on the frame's L'DL factor of qM (qLD / qLDiagInv as mjb_get serves them: the
+ *                                          factor of M, never of the M + h B of implicit joint damping)
+ *   MJB_DYN_OUT_ID     [nenv][nvec][nv]    (M V[k] + qfrc_bias) - qfrc_passive, rounded in that order: the generalized force -- actuators + applied +
+ *                                          constraints together -- under which qacc = V[k].  mj_inverse's qfrc_inverse leaves the constraint forces
+ *                                          out: a caller who wants it subtracts the frame's qfrc_constraint (mjb_get) themselves.
+ *   MJB_DYN_OUT_JDOTV  [nenv][npoint][6]   Jdot qvel of each configured point, LINEAR then angular, world axes: the bias acceleration of
+ *                                          xddot = J qacc + Jdot qvel.  The points are mjb_jac_configure's (object types, ids, pnt, the same rules).
+ *                                          With c = subtree_com[body_rootid[body]], r = p - c, (w, v) = cvel[body] and A = the sum of
+ *                                          cdof_dot[d] qvel[d] over the dofs that move the body in ascending d: linear = A_lin + A_ang x r +
+ *                                          w x (v + w x r), angular = A_ang.  A point on the world body gives +0.0.  For ball and free joints only
+ *                                          the sum A is the physical derivative, the single cdof_dot columns are not: no Jdot matrix is offered.
+ *                                          A <framelinacc> sensor on the same site reads J qacc + JDOTV - gravity, a <frameangacc> J qacc + JDOTV.
+ * No result depends on the shape of the launch, on nvec, npoint or the set of outputs.
+ * mjb_dyn_configure validates (MJB_EINVAL: outputs 0, with unknown bits or with MJB_DYN_IN_V; nvec < 1 with MV, MINVV or ID, nvec < 0; npoint < 1
+ * or null arrays with JDOTV; a bad point by mjb_jac_configure's rules; a model with nv == 0), builds the dense index table of qM, and (re)allocates
+ * V and the requested outputs only; a second call replaces the first and zeroes V.  nvec without MV / MINVV / ID and the points without JDOTV are ignored.
+ * mjb_dyn_eval is MJB_EINVAL before mjb_dyn_configure and, like mjb_jac_eval, unless the frame workspace is current for every env (after mjb_forward /
+ * mjb_step1 / mjb_step2, or a fused step with keep_frame) and once qpos or a mocap pose has been written through mjb_set / mjb_set_many /
+ * mjb_set_packed since.  ID and JDOTV read the velocity stage (qfrc_bias, qfrc_passive, cvel, cdof_dot): with either configured the call refuses,
+ * too, once qvel has been written through those three calls since the workspace was made current; M, MV and MINVV do not care about qvel.  Writes
+ * through mjb_device_ptr are not seen: such a caller runs mjb_forward itself.  After a step (mjb_step2, a fused step with keep_frame) the frame holds
+ * the step's forward pass, the poses and velocities BEFORE the integration, as mjData does after mj_step: M, ID and JDOTV belong to that state.
+ * JDOTV then takes the step's update qvel += timestep * (the Euler stage's solution, kept in the frame) back to multiply cdof_dot with the
+ * velocities it was computed from; behind an RK4 step those are not recoverable and JDOTV is MJB_EINVAL until mjb_forward / mjb_step1.
+ * mjb_dyn_get / mjb_dyn_device_ptr of an output that was not configured: MJB_EINVAL / NULL. */
+enum { MJB_DYN_OUT_M = 1, MJB_DYN_OUT_MV = 2, MJB_DYN_OUT_MINVV = 4, MJB_DYN_OUT_ID = 8, MJB_DYN_OUT_JDOTV = 16, MJB_DYN_IN_V = 256 };
+int mjb_dyn_configure(mjb_batch *b, int nvec, int npoint, const int *objtype /*[npoint] MJB_JAC_SITE ...*/, const int *objid /*[npoint]*/,
+                      const double *pnt /*[npoint][3] offset in the object's own frame, NULL = 0*/, int outputs /*MJB_DYN_OUT_* bits*/);
+int mjb_dyn_set_vectors(mjb_batch *b, int env_lo, int env_hi, const double *host /*[envs][nvec][nv]*/);   /* synchronises */
+int mjb_dyn_eval(mjb_batch *b);                                   /* asynchronous on the batch's stream */
+int mjb_dyn_get(mjb_batch *b, int which, int env_lo, int env_hi, double *host);   /* synchronises; which = one MJB_DYN_OUT_* bit */
+void *mjb_dyn_device_ptr(mjb_batch *b, int which);                /* which = one MJB_DYN_OUT_* bit, or MJB_DYN_IN_V */
+int mjb_dyn_count(const mjb_batch *b, int *nvec, int *npoint);    /* vectors and points per env of the configuration (either pointer may be NULL) */
+
 /* ---- batched contact wrenches: mj_contactForce and net contact forces between geom sets, for every env at once ----
  * Contact c of an env is read from the frame workspace (ncon, contact_geom, contact_dim, contact_efc_address, contact_frame, contact_pos,
  * contact_dist, contact_friction, efc_force).  A contact with contact_efc_address[c] < 0 has no rows and takes no part in any output.

@@ -205,6 +205,12 @@ def load_library(path=None):
         "mjb_jac_get": (ci, [vp, ci, ci, ci, C.POINTER(cd)]),
         "mjb_jac_device_ptr": (vp, [vp, ci]),
         "mjb_jac_count": (ci, [vp]),
+        "mjb_dyn_configure": (ci, [vp, ci, ci, C.POINTER(ci), C.POINTER(ci), C.POINTER(cd), ci]),
+        "mjb_dyn_set_vectors": (ci, [vp, ci, ci, C.POINTER(cd)]),
+        "mjb_dyn_eval": (ci, [vp]),
+        "mjb_dyn_get": (ci, [vp, ci, ci, ci, C.POINTER(cd)]),
+        "mjb_dyn_device_ptr": (vp, [vp, ci]),
+        "mjb_dyn_count": (ci, [vp, C.POINTER(ci), C.POINTER(ci)]),
         "mjb_contact_configure": (ci, [vp, ci, C.POINTER(C.c_uint8), C.POINTER(C.c_uint8), C.POINTER(ci), ci]),
         "mjb_contact_eval": (ci, [vp]),
         "mjb_contact_get": (ci, [vp, ci, ci, ci, vp]),

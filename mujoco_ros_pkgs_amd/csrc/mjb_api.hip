@@ -19,6 +19,7 @@
 #include "mjb_episode.h"
 #include "mjb_contact.h"
 #include "mjb_jac.h"
+#include "mjb_dyn.h"
 #include "mjb_model.h"
 #include "mjb_resources.h"
 
@@ -54,6 +55,11 @@ struct RayBufs {  // batched ray casting (mjb_rays_*): the ray / mask table of m
 struct JacBufs {  // batched Jacobians (mjb_jac_*): the point table of mjb_launch_jac and the outputs that were asked for (the others stay empty)
 	DevBuf<double> tab;
 	DevBuf<double> J, MinvJT, Ainv, vel;
+};
+struct DynBufs {  // batched joint-space dynamics (mjb_dyn_*): the dense index table of qM, the point table of JDOTV, the input vectors and the outputs that were asked for (the others stay empty)
+	DevBuf<int> full_adr;
+	DevBuf<double> tab, V;
+	DevBuf<double> M, MV, MinvV, ID, Jdotv;
 };
 struct ConBufs {  // batched contact wrenches (mjb_contact_*): the query table of mjb_launch_contact and the outputs that were asked for (the others stay empty)
 	DevBuf<unsigned int> tab;
@@ -129,6 +135,8 @@ struct mjb_batch {
 	int nray = 0;                     // rays per env of that configuration (0: none yet)
 	JacBufs jac;                      // mjb_jac_configure
 	int njac = 0, jac_outputs = 0;    // points per env of that configuration (0: none yet), its MJB_JAC_OUT_* bits
+	DynBufs dyn;                      // mjb_dyn_configure
+	int dyn_nvec = 0, dyn_npoint = 0, dyn_outputs = 0;  // vectors and points per env of that configuration, its MJB_DYN_OUT_* bits (0: none yet)
 	ConBufs con;                      // mjb_contact_configure
 	int ncquery = 0, con_outputs = 0; // queries of that configuration (0: none yet), its MJB_CON_OUT_* bits
 	EpisodeBufs epi;                  // mjb_episode_*: the outputs are allocated at the first call that needs them
@@ -138,6 +146,10 @@ struct mjb_batch {
 	double ep_time_limit = 0;         // <= 0: no time rule
 	bool pose_written = false;        // qpos or a mocap pose has been written through mjb_set* since the frame workspace was last made current: mjb_get still serves
 	                                  // the old frame (mjData's rule); mjb_jac_eval, whose results a controller applies to the NEW state, refuses it
+	bool vel_written = false;         // the same for qvel: the frame's velocity-stage fields (cvel, cdof_dot, qfrc_bias, qfrc_passive) belong to the old velocities; mjb_dyn_eval
+	                                  // refuses it when ID or JDOTV is configured
+	bool vel_integrated = false;      // the launch that made the frame current also advanced qvel behind it (a fused step with keep_frame, a step's second half): the
+	                                  // frame's velocity stage belongs to qvel BEFORE that update (mjb_dyn_eval, JDOTV)
 	DevBuf<double> pack_dev;          // staging block of mjb_get_packed / mjb_set_packed
 	size_t pack_cap = 0;
 	DevBuf<double> env_geom_size;
@@ -971,6 +983,8 @@ int mjb_step(mjb_batch *b, int nsteps)
 		b->frame_half = false;
 		b->frame_hi = b->nenv;
 		b->pose_written = false;
+		b->vel_written = false;
+		b->vel_integrated = true;
 	}
 	return rc;
 }
@@ -1002,6 +1016,8 @@ static int forward_whole(mjb_batch *b, int mode)
 		b->frame_half = mode == MJB_MODE_STEP1;
 		b->frame_hi = b->nenv;
 		b->pose_written = false;
+		b->vel_written = false;
+		b->vel_integrated = false;
 	}
 	return rc;
 }
@@ -1017,6 +1033,7 @@ int mjb_step2(mjb_batch *b)
 		b->step_counter += 1;
 		b->steps_taken += 1;
 		b->frame_half = false;
+		b->vel_integrated = true;
 	}
 	return rc;
 }
@@ -1049,6 +1066,8 @@ int mjb_step1_prefix(mjb_batch *b, int ncb)
 		b->frame_half = true;
 		b->frame_hi = ncb;
 		b->pose_written = false;
+		b->vel_written = false;
+		b->vel_integrated = false;
 	}
 	return rc;
 }
@@ -1107,6 +1126,7 @@ int mjb_step2_prefix(mjb_batch *b, int ncb)
 	if (rc == MJB_OK) {
 		b->split_ncb = -1;
 		b->frame_half = false;
+		b->vel_integrated = true;
 	}
 	return rc;
 }
@@ -1127,6 +1147,8 @@ int mjb_step21_prefix(mjb_batch *b, int ncb)
 		b->frame_half = true;
 		b->frame_hi = ncb;
 		b->pose_written = false;
+		b->vel_written = false;
+		b->vel_integrated = false;
 	}
 	return rc;
 }
@@ -1149,6 +1171,7 @@ int mjb_step2_rk_prefix(mjb_batch *b, int ncb, int rk)
 	if (rc == MJB_OK) {
 		b->split_ncb = -1;
 		b->frame_half = false;
+		b->vel_integrated = true;
 	}
 	return rc;
 }
@@ -1288,6 +1311,7 @@ int mjb_set(mjb_batch *b, int field, int env_lo, int env_hi, const double *host)
 		}
 		if (field == MJB_F_qpos && env_lo == 0 && env_hi == b->nenv) b->rowstat_ever = false;  // (wide-frame policy: a new workload)
 		if (pose_field(field)) b->pose_written = true;
+		if (field == MJB_F_qvel) b->vel_written = true;
 		return MJB_OK;
 	}
 	if (field != MJB_F_qfrc_passive)
@@ -1384,6 +1408,7 @@ int mjb_set_many(mjb_batch *b, int n, const int *fields, int env_lo, int env_hi,
 			err = hipMemcpyAsync(state_ptr(b, field) + (size_t)env_lo * sz, host[k], (size_t)(env_hi - env_lo) * sz * sizeof(double),
 			                     hipMemcpyHostToDevice, b->stream.get());
 			if (pose_field(field)) b->pose_written = true;
+			if (field == MJB_F_qvel) b->vel_written = true;
 			if (field == MJB_F_xfrc_applied) b->le_xfrc_stale = true;
 			if (field == MJB_F_xfrc_applied && !b->st.use_xfrc) {
 				b->st.use_xfrc = 1;
@@ -1440,7 +1465,7 @@ static int packed_transfer(mjb_batch *b, int n, const int *fields, int env_lo, i
 	PackArgs a{};
 	long long total = 0;
 	int maxdim = 1;
-	bool writes_pose = false;
+	bool writes_pose = false, writes_vel = false;
 	for (int k = 0; k < n; k++) {
 		const int field = fields[k];
 		int rc = check_range(b, field, env_lo, env_hi);
@@ -1465,6 +1490,7 @@ static int packed_transfer(mjb_batch *b, int n, const int *fields, int env_lo, i
 		if (sz > 0) a.n++;
 		if (sz > maxdim) maxdim = sz;
 		if (!to_host && sz > 0 && pose_field(field)) writes_pose = true;
+		if (!to_host && sz > 0 && field == MJB_F_qvel) writes_vel = true;
 		if (!to_host && field == MJB_F_xfrc_applied) b->le_xfrc_stale = true;
 		if (!to_host && field == MJB_F_xfrc_applied && !b->st.use_xfrc) {
 			b->st.use_xfrc = 1;
@@ -1473,6 +1499,7 @@ static int packed_transfer(mjb_batch *b, int n, const int *fields, int env_lo, i
 	}
 	if (total == 0 || env_lo == env_hi) return MJB_OK;
 	if (writes_pose) b->pose_written = true;  // (every field has been checked: the write goes ahead)
+	if (writes_vel) b->vel_written = true;
 	a.nenv = env_hi - env_lo;
 	if ((long long)b->pack_cap < total) {
 		if (!b->pack_dev.alloc_zeroed((size_t)total)) {
@@ -2389,16 +2416,13 @@ static DevBuf<double> *jac_output(mjb_batch *b, int which, size_t *per_point)
 	}
 }
 
-int mjb_jac_configure(mjb_batch *b, int npoint, const int *objtype, const int *objid, const double *pnt, int outputs)
+// The point table of mjb_launch_jac and mjb_launch_dyn (mjb_jac.h): pnt[npoint][3] as doubles, then one JacPoint per point -- validated and resolved
+// for `who` (mjb_jac_configure, mjb_dyn_configure), whose name the refusals carry.
+static int resolve_points(const mjb_batch *b, const char *who, int npoint, const int *objtype, const int *objid, const double *pnt, std::vector<double> &tab)
 {
-	if (!b) return fail(MJB_EINVAL, "null batch");
 	const mjb_model_desc &h = b->model->h;
-	if (npoint < 1 || !objtype || !objid) return fail(MJB_EINVAL, "mjb_jac_configure: npoint must be at least 1, with an object type and an id per point");
-	if (outputs == 0 || (outputs & ~kJacOutputs)) return fail(MJB_EINVAL, "mjb_jac_configure: outputs 0x%x: at least one of the MJB_JAC_OUT_* bits and no other", (unsigned)outputs);
-	if (h.nv < 1) return fail(MJB_EINVAL, "mjb_jac_configure: the model has no dofs");
-	// the table of mjb_launch_jac (mjb_jac.h): pnt[npoint][3] as doubles, then one JacPoint per point
 	const size_t n = (size_t)npoint, ndoubles = 3 * n + n * (sizeof(JacPoint) / sizeof(double));
-	std::vector<double> tab(ndoubles, 0.0);
+	tab.assign(ndoubles, 0.0);
 	JacPoint *rec = reinterpret_cast<JacPoint *>(tab.data() + 3 * n);
 	for (size_t k = 0; k < n; k++) {
 		const int ty = objtype[k], id = objid[k];
@@ -2407,13 +2431,13 @@ int mjb_jac_configure(mjb_batch *b, int npoint, const int *objtype, const int *o
 		case MJB_JAC_SITE: count = h.nsite; break;
 		case MJB_JAC_BODY: case MJB_JAC_BODYCOM: count = h.nbody; break;
 		case MJB_JAC_GEOM: count = h.ngeom; break;
-		default: return fail(MJB_EINVAL, "mjb_jac_configure: point %zu: unknown object type %d", k, ty);
+		default: return fail(MJB_EINVAL, "%s: point %zu: unknown object type %d", who, k, ty);
 		}
-		if (id < 0 || id >= count) return fail(MJB_EINVAL, "mjb_jac_configure: point %zu: id %d outside [0, %d)", k, id, count);
+		if (id < 0 || id >= count) return fail(MJB_EINVAL, "%s: point %zu: id %d outside [0, %d)", who, k, id, count);
 		body = ty == MJB_JAC_SITE ? h.site_bodyid[id] : (ty == MJB_JAC_GEOM ? h.geom_bodyid[id] : id);
 		for (int c = 0; c < 3; c++) {
 			const double p = pnt ? pnt[3 * k + c] : 0.0;
-			if (!std::isfinite(p)) return fail(MJB_EINVAL, "mjb_jac_configure: point %zu: non-finite pnt", k);
+			if (!std::isfinite(p)) return fail(MJB_EINVAL, "%s: point %zu: non-finite pnt", who, k);
 			tab[3 * k + c] = p;
 		}
 		rec[k].type = ty;
@@ -2423,6 +2447,19 @@ int mjb_jac_configure(mjb_batch *b, int npoint, const int *objtype, const int *o
 		rec[k].mask[0] = (unsigned int)b->model->body_dofmask[2 * body];
 		rec[k].mask[1] = (unsigned int)b->model->body_dofmask[2 * body + 1];
 	}
+	return MJB_OK;
+}
+
+int mjb_jac_configure(mjb_batch *b, int npoint, const int *objtype, const int *objid, const double *pnt, int outputs)
+{
+	if (!b) return fail(MJB_EINVAL, "null batch");
+	const mjb_model_desc &h = b->model->h;
+	if (npoint < 1 || !objtype || !objid) return fail(MJB_EINVAL, "mjb_jac_configure: npoint must be at least 1, with an object type and an id per point");
+	if (outputs == 0 || (outputs & ~kJacOutputs)) return fail(MJB_EINVAL, "mjb_jac_configure: outputs 0x%x: at least one of the MJB_JAC_OUT_* bits and no other", (unsigned)outputs);
+	if (h.nv < 1) return fail(MJB_EINVAL, "mjb_jac_configure: the model has no dofs");
+	std::vector<double> tab;
+	if (int rc = resolve_points(b, "mjb_jac_configure", npoint, objtype, objid, pnt, tab)) return rc;
+	const size_t n = (size_t)npoint, ndoubles = tab.size();
 	HIP_TRY(hipSetDevice(b->device));
 	HIP_TRY(hipStreamSynchronize(b->stream.get()));  // (an evaluation of the previous configuration may still read what goes now)
 	JacBufs jb;
@@ -2483,6 +2520,136 @@ void *mjb_jac_device_ptr(mjb_batch *b, int which)
 }
 
 int mjb_jac_count(const mjb_batch *b) { return b ? b->njac : fail(MJB_EINVAL, "null batch"); }
+
+// ---- batched joint-space dynamics (kernel in mjb_dyn.hip) ----
+static const int kDynOutputs = MJB_DYN_OUT_M | MJB_DYN_OUT_MV | MJB_DYN_OUT_MINVV | MJB_DYN_OUT_ID | MJB_DYN_OUT_JDOTV;
+static const int kDynVecOutputs = MJB_DYN_OUT_MV | MJB_DYN_OUT_MINVV | MJB_DYN_OUT_ID;
+// the buffer of one output bit (or of MJB_DYN_IN_V) and its doubles per env; NULL: not one bit, or not configured
+static DevBuf<double> *dyn_buffer(mjb_batch *b, int which, size_t *per_env)
+{
+	const size_t nv = (size_t)b->model->h.nv, nvec = (size_t)b->dyn_nvec;
+	if (which == MJB_DYN_IN_V) {
+		*per_env = nvec * nv;
+		return b->dyn.V ? &b->dyn.V : nullptr;
+	}
+	if (!(which & b->dyn_outputs)) return nullptr;
+	switch (which) {
+	case MJB_DYN_OUT_M: *per_env = nv * nv; return &b->dyn.M;
+	case MJB_DYN_OUT_MV: *per_env = nvec * nv; return &b->dyn.MV;
+	case MJB_DYN_OUT_MINVV: *per_env = nvec * nv; return &b->dyn.MinvV;
+	case MJB_DYN_OUT_ID: *per_env = nvec * nv; return &b->dyn.ID;
+	case MJB_DYN_OUT_JDOTV: *per_env = (size_t)b->dyn_npoint * 6; return &b->dyn.Jdotv;
+	default: return nullptr;
+	}
+}
+
+int mjb_dyn_configure(mjb_batch *b, int nvec, int npoint, const int *objtype, const int *objid, const double *pnt, int outputs)
+{
+	if (!b) return fail(MJB_EINVAL, "null batch");
+	const mjb_model_desc &h = b->model->h;
+	if (outputs & MJB_DYN_IN_V) return fail(MJB_EINVAL, "mjb_dyn_configure: outputs 0x%x: MJB_DYN_IN_V names the input of mjb_dyn_device_ptr, it is not an output", (unsigned)outputs);
+	if (outputs == 0 || (outputs & ~kDynOutputs)) return fail(MJB_EINVAL, "mjb_dyn_configure: outputs 0x%x: at least one of the MJB_DYN_OUT_* bits and no other", (unsigned)outputs);
+	if (nvec < 0 || ((outputs & kDynVecOutputs) && nvec < 1)) return fail(MJB_EINVAL, "mjb_dyn_configure: nvec %d: at least 1 for MV, MINVV or ID, never negative", nvec);
+	const bool jdot = (outputs & MJB_DYN_OUT_JDOTV) != 0;
+	if (jdot && (npoint < 1 || !objtype || !objid)) return fail(MJB_EINVAL, "mjb_dyn_configure: JDOTV: npoint must be at least 1, with an object type and an id per point");
+	if (h.nv < 1) return fail(MJB_EINVAL, "mjb_dyn_configure: the model has no dofs");
+	if (!jdot) npoint = 0;  // (points without JDOTV are not looked at)
+	if (!(outputs & kDynVecOutputs)) nvec = 0;  // (nor vectors without an output of theirs)
+	std::vector<double> tab;
+	if (jdot)
+		if (int rc = resolve_points(b, "mjb_dyn_configure", npoint, objtype, objid, pnt, tab)) return rc;
+	std::vector<int> full((size_t)h.nv * h.nv);
+	mjb_dyn_full_adr(h.nv, h.dof_Madr, h.dof_parentid, full.data());
+	HIP_TRY(hipSetDevice(b->device));
+	HIP_TRY(hipStreamSynchronize(b->stream.get()));  // (an evaluation of the previous configuration may still read what goes now)
+	DynBufs db;
+	const size_t ne = (size_t)b->nenv, nv = (size_t)h.nv, nvv = ne * (size_t)nvec * nv;
+	if (!db.full_adr.alloc(full.size()) || (jdot && !db.tab.alloc(tab.size())) || (nvec > 0 && !db.V.alloc_zeroed(nvv)) || ((outputs & MJB_DYN_OUT_M) && !db.M.alloc_zeroed(ne * nv * nv)) ||
+	    ((outputs & MJB_DYN_OUT_MV) && !db.MV.alloc_zeroed(nvv)) || ((outputs & MJB_DYN_OUT_MINVV) && !db.MinvV.alloc_zeroed(nvv)) || ((outputs & MJB_DYN_OUT_ID) && !db.ID.alloc_zeroed(nvv)) ||
+	    (jdot && !db.Jdotv.alloc_zeroed(ne * (size_t)npoint * 6)))
+		return fail(MJB_ENOMEM, "mjb_dyn_configure: allocation failed for %d envs x %d vectors, %d points", b->nenv, nvec, npoint);
+	HIP_TRY(hipMemcpy(db.full_adr.get(), full.data(), full.size() * sizeof(int), hipMemcpyHostToDevice));
+	if (jdot) HIP_TRY(hipMemcpy(db.tab.get(), tab.data(), tab.size() * sizeof(double), hipMemcpyHostToDevice));
+	b->dyn = std::move(db);
+	b->dyn_nvec = nvec;
+	b->dyn_npoint = npoint;
+	b->dyn_outputs = outputs;
+	return MJB_OK;
+}
+
+int mjb_dyn_set_vectors(mjb_batch *b, int env_lo, int env_hi, const double *host)
+{
+	if (!b) return fail(MJB_EINVAL, "null batch");
+	if (b->dyn_outputs == 0) return fail(MJB_EINVAL, "mjb_dyn_set_vectors before mjb_dyn_configure");
+	if (b->dyn_nvec < 1) return fail(MJB_EINVAL, "mjb_dyn_set_vectors: the configuration has no vectors (none of MV, MINVV, ID)");
+	if (env_lo < 0 || env_hi > b->nenv || env_lo > env_hi) return fail(MJB_ERANGE, "env range [%d,%d) outside [0,%d)", env_lo, env_hi, b->nenv);
+	const size_t per_env = (size_t)b->dyn_nvec * b->model->h.nv, n = (size_t)(env_hi - env_lo) * per_env;
+	if (n && !host) return fail(MJB_EINVAL, "null host buffer");
+	HIP_TRY(hipSetDevice(b->device));
+	HIP_TRY(hipStreamSynchronize(b->stream.get()));  // (an evaluation in flight still reads the vectors)
+	if (n) HIP_TRY(hipMemcpy(b->dyn.V.get() + (size_t)env_lo * per_env, host, n * sizeof(double), hipMemcpyHostToDevice));
+	return MJB_OK;
+}
+
+int mjb_dyn_eval(mjb_batch *b)
+{
+	if (!b) return fail(MJB_EINVAL, "null batch");
+	if (b->dyn_outputs == 0) return fail(MJB_EINVAL, "mjb_dyn_eval before mjb_dyn_configure");
+	if (!b->frame_valid || !b->st.frame_ws || b->frame_hi < b->nenv)
+		return fail(MJB_EINVAL, "mjb_dyn_eval reads qM, its factor and the velocity stage of every env: only after mjb_forward / mjb_step1 / mjb_step2, or a fused step with keep_frame");
+	if (b->pose_written)
+		return fail(MJB_EINVAL, "mjb_dyn_eval: qpos or a mocap pose has been written since the frame was computed, its mass matrix belongs to the old poses: only after mjb_forward / mjb_step1 / "
+		                        "mjb_step2, or a fused step with keep_frame");
+	const bool reads_vel = (b->dyn_outputs & (MJB_DYN_OUT_ID | MJB_DYN_OUT_JDOTV)) != 0, jdot = (b->dyn_outputs & MJB_DYN_OUT_JDOTV) != 0;
+	if (reads_vel && b->vel_written)
+		return fail(MJB_EINVAL, "mjb_dyn_eval: qvel has been written since the frame was computed, qfrc_bias, qfrc_passive, cvel and cdof_dot (ID, JDOTV) belong to the old velocities: "
+		                        "only after mjb_forward / mjb_step1 / mjb_step2, or a fused step with keep_frame");
+	if (jdot && b->vel_integrated && b->model->h.integrator == MJB_INT_RK4)
+		return fail(MJB_EINVAL, "mjb_dyn_eval: JDOTV behind an RK4 step: the frame belongs to the step's last evaluation, whose velocities the batch no longer holds: only after "
+		                        "mjb_forward / mjb_step1");
+	HIP_TRY(hipSetDevice(b->device));
+	if (int rc = join_rest(b)) return rc;
+	if (int rc = sync_params(b)) return rc;
+	const int rc = mjb_launch_dyn(b->params_dev.get(), b->dyn.full_adr.get(), b->dyn.tab.get(), b->dyn.V.get(), b->nenv, b->dyn_nvec, b->dyn_npoint, b->model->h.nv, b->model->h.nM,
+	                              b->vel_integrated ? 1 : 0, b->dyn.M.get(), b->dyn.MV.get(), b->dyn.MinvV.get(), b->dyn.ID.get(), b->dyn.Jdotv.get(), b->stream.get());
+	if (rc != 0) return fail(MJB_ENODEVICE, "dynamics launch failed: %s", hipGetErrorString((hipError_t)rc));
+	return MJB_OK;
+}
+
+int mjb_dyn_get(mjb_batch *b, int which, int env_lo, int env_hi, double *host)
+{
+	if (!b) return fail(MJB_EINVAL, "null batch");
+	if (b->dyn_outputs == 0) return fail(MJB_EINVAL, "mjb_dyn_get before mjb_dyn_configure");
+	size_t per_env = 0;
+	DevBuf<double> *buf = which == MJB_DYN_IN_V ? nullptr : dyn_buffer(b, which, &per_env);
+	if (!buf) return fail(MJB_EINVAL, "mjb_dyn_get: output 0x%x is not one MJB_DYN_OUT_* bit of the configuration (0x%x)", (unsigned)which, (unsigned)b->dyn_outputs);
+	if (env_lo < 0 || env_hi > b->nenv || env_lo > env_hi) return fail(MJB_ERANGE, "env range [%d,%d) outside [0,%d)", env_lo, env_hi, b->nenv);
+	const size_t n = (size_t)(env_hi - env_lo) * per_env, off = (size_t)env_lo * per_env;
+	if (n && !host) return fail(MJB_EINVAL, "null host buffer");
+	HIP_TRY(hipSetDevice(b->device));
+	HIP_TRY(hipStreamSynchronize(b->stream.get()));
+	if (n) HIP_TRY(hipMemcpy(host, buf->get() + off, n * sizeof(double), hipMemcpyDeviceToHost));
+	return MJB_OK;
+}
+
+void *mjb_dyn_device_ptr(mjb_batch *b, int which)
+{
+	size_t per_env = 0;
+	DevBuf<double> *buf = (b && b->dyn_outputs != 0) ? dyn_buffer(b, which, &per_env) : nullptr;
+	if (!buf) {
+		fail(MJB_EINVAL, "mjb_dyn_device_ptr: bad argument, or an output (or the input MJB_DYN_IN_V) that mjb_dyn_configure was not asked for");
+		return nullptr;
+	}
+	return buf->get();
+}
+
+int mjb_dyn_count(const mjb_batch *b, int *nvec, int *npoint)
+{
+	if (!b) return fail(MJB_EINVAL, "null batch");
+	if (nvec) *nvec = b->dyn_nvec;
+	if (npoint) *npoint = b->dyn_npoint;
+	return MJB_OK;
+}
 
 // ---- batched contact wrenches (kernel in mjb_contact.hip) ----
 static const int kConOutputs = MJB_CON_OUT_WRENCH | MJB_CON_OUT_NORMAL | MJB_CON_OUT_COUNT | MJB_CON_OUT_DIST | MJB_CON_OUT_CONTACTS;

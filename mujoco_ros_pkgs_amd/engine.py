@@ -436,24 +436,30 @@ class Batch:
         nv = int(self.cm.model["nv"])
         return {"J": (n, npoint, 6, nv), "MinvJT": (n, npoint, 6, nv), "Ainv": (n, npoint, 6, 6), "vel": (n, npoint, 6)}[key]
 
-    def set_jac_points(self, points, outputs=("J",), pnt=None):
-        """The points whose Jacobians every env evaluates (mjb_jac_configure): `points` is a sequence of site names or ids, or of (kind, name_or_id)
-        pairs with kind one of "site", "body", "bodycom", "geom" (mj_jacSite / mj_jacBody / mj_jacBodyCom / mj_jacGeom).  pnt [npoint, 3], default 0,
-        moves a point off its object's origin, in the object's own frame.  outputs: any of "J", "MinvJT", "Ainv", "vel" -- only these are allocated
-        and computed.  A second call replaces the first."""
+    def _resolve_points(self, who, points):
+        """(object types, ids) as int32 arrays of a point list in set_jac_points' form"""
         pts = [("site", p) if isinstance(p, (str, int, np.integer)) else tuple(p) for p in points]
         n = len(pts)
         ty, oid = np.zeros(n, np.int32), np.zeros(n, np.int32)
         for k, (kind, ref) in enumerate(pts):
             if kind not in self._JAC_KINDS:
-                raise ValueError(f"set_jac_points: unknown kind {kind!r} (site, body, bodycom, geom)")
+                raise ValueError(f"{who}: unknown kind {kind!r} (site, body, bodycom, geom)")
             ty[k] = self._JAC_KINDS[kind]
             if isinstance(ref, str):
                 names = self.cm.model["names"]["body" if kind == "bodycom" else kind]
                 if ref not in names:
-                    raise ValueError(f"set_jac_points: no {kind} named {ref!r}")
+                    raise ValueError(f"{who}: no {kind} named {ref!r}")
                 ref = names.index(ref)
             oid[k] = int(ref)
+        return ty, oid
+
+    def set_jac_points(self, points, outputs=("J",), pnt=None):
+        """The points whose Jacobians every env evaluates (mjb_jac_configure): `points` is a sequence of site names or ids, or of (kind, name_or_id)
+        pairs with kind one of "site", "body", "bodycom", "geom" (mj_jacSite / mj_jacBody / mj_jacBodyCom / mj_jacGeom).  pnt [npoint, 3], default 0,
+        moves a point off its object's origin, in the object's own frame.  outputs: any of "J", "MinvJT", "Ainv", "vel" -- only these are allocated
+        and computed.  A second call replaces the first."""
+        ty, oid = self._resolve_points("set_jac_points", points)
+        n = len(ty)
         outs = (outputs,) if isinstance(outputs, str) else tuple(outputs)
         unknown = [o for o in outs if o not in self._JAC_OUTPUTS]
         if unknown:
@@ -492,6 +498,79 @@ class Batch:
         if isinstance(which, str) and which not in self._JAC_OUTPUTS:
             raise ValueError(f"jac_device_ptr: unknown output {which!r} (J, MinvJT, Ainv, vel)")
         p = self.lib.mjb_jac_device_ptr(self.ptr, self._JAC_OUTPUTS[which] if isinstance(which, str) else int(which))
+        if not p:
+            raise EngineError(self.lib.mjb_last_error().decode())
+        return p
+
+    # ---- batched joint-space dynamics (mjb_dyn_*) ----
+    _DYN_OUTPUTS = {"M": 1, "MV": 2, "MinvV": 4, "ID": 8, "Jdotv": 16}   # MJB_DYN_OUT_* of include/mjb.h
+    _DYN_IN_V = 256                                                       # MJB_DYN_IN_V
+
+    def _dyn_counts(self):
+        nvec, npoint = C.c_int(0), C.c_int(0)
+        _check(self.lib.mjb_dyn_count(self.ptr, C.byref(nvec), C.byref(npoint)), "mjb_dyn_count")
+        return nvec.value, npoint.value
+
+    def _dyn_shape(self, key, n):
+        nv = int(self.cm.model["nv"])
+        nvec, npoint = self._dyn_counts()
+        return (n, nv, nv) if key == "M" else ((n, npoint, 6) if key == "Jdotv" else (n, nvec, nv))
+
+    def set_dynamics(self, nvec=0, outputs=("M",), points=None, pnt=None):
+        """What every env evaluates of its joint-space dynamics (mjb_dyn_configure).  outputs: any of "M" (dense mass matrix, mj_fullM), "MV" (M V[k],
+        mj_mulM), "MinvV" (M^-1 V[k], mj_solveM), "ID" ((M V[k] + qfrc_bias) - qfrc_passive: the generalized force under which qacc = V[k]) and "Jdotv"
+        (Jdot qvel of the points, linear then angular) -- only these are allocated and computed.  nvec: vectors per env of the input block V, which the
+        batch owns, zero from here on (set_dyn_vectors, or dyn_device_ptr("V")).  points / pnt: the points of "Jdotv", as in set_jac_points.  A second call
+        replaces the first."""
+        outs = (outputs,) if isinstance(outputs, str) else tuple(outputs)
+        unknown = [o for o in outs if o not in self._DYN_OUTPUTS]
+        if unknown:
+            raise ValueError(f"set_dynamics: unknown output {unknown[0]!r} (M, MV, MinvV, ID, Jdotv)")
+        bits = 0
+        for o in outs:
+            bits |= self._DYN_OUTPUTS[o]
+        pi, pd = C.POINTER(C.c_int), C.POINTER(C.c_double)
+        n, ty, oid, p = 0, None, None, None
+        if points is not None:
+            ty, oid = self._resolve_points("set_dynamics", points)
+            n = len(ty)
+            p = None if pnt is None else np.ascontiguousarray(np.broadcast_to(np.asarray(pnt, dtype=np.float64), (n, 3)))
+        _check(self.lib.mjb_dyn_configure(self.ptr, int(nvec), n, None if ty is None else ty.ctypes.data_as(pi), None if oid is None else oid.ctypes.data_as(pi),
+                                          None if p is None else p.ctypes.data_as(pd), bits), "mjb_dyn_configure")
+        self._dyn_outputs = tuple(k for k in self._DYN_OUTPUTS if bits & self._DYN_OUTPUTS[k])
+
+    def set_dyn_vectors(self, V, lo=0, hi=None):
+        """Write the input vectors of envs [lo, hi) from the host (mjb_dyn_set_vectors): V [n, nvec, nv], or [n, nv] when nvec is 1."""
+        hi = self.nenv if hi is None else hi
+        nvec, _ = self._dyn_counts()
+        a = np.ascontiguousarray(np.asarray(V, dtype=np.float64).reshape(hi - lo, nvec, int(self.cm.model["nv"])))
+        _check(self.lib.mjb_dyn_set_vectors(self.ptr, lo, hi, a.ctypes.data_as(C.POINTER(C.c_double))), "mjb_dyn_set_vectors")
+
+    def eval_dynamics_async(self):
+        """Evaluate the configured outputs for every env on the batch's stream (mjb_dyn_eval); needs current frames: forward(), step1() / step2(), or
+        step() with set_keep_frame() -- after a step the frame belongs to the state before the integration.  "ID" and "Jdotv" also refuse a qvel written
+        since.  The results stay on the device (dyn_device_ptr) until dynamics() or the next evaluation."""
+        _check(self.lib.mjb_dyn_eval(self.ptr), "mjb_dyn_eval")
+
+    def dynamics(self, lo=0, hi=None):
+        """Evaluate, wait, and return the configured outputs of envs [lo, hi) as a dict of float64 arrays: "M" [n, nv, nv], "MV" / "MinvV" / "ID"
+        [n, nvec, nv] and "Jdotv" [n, npoint, 6] (linear, then angular, world axes)."""
+        hi = self.nenv if hi is None else hi
+        self.eval_dynamics_async()
+        out = {}
+        for key in getattr(self, "_dyn_outputs", ()):
+            a = np.empty(self._dyn_shape(key, hi - lo), dtype=np.float64)
+            _check(self.lib.mjb_dyn_get(self.ptr, self._DYN_OUTPUTS[key], lo, hi, a.ctypes.data_as(C.POINTER(C.c_double))), "mjb_dyn_get")
+            out[key] = a
+        return out
+
+    def dyn_device_ptr(self, which):
+        """Device address of one output by name ("M", "MV", "MinvV", "ID", "Jdotv") or MJB_DYN_OUT_* bit, or of the input block ("V", [nenv, nvec, nv]):
+        float64, env-major, the shapes of dynamics()."""
+        if isinstance(which, str) and which != "V" and which not in self._DYN_OUTPUTS:
+            raise ValueError(f"dyn_device_ptr: unknown name {which!r} (M, MV, MinvV, ID, Jdotv, V)")
+        bit = (self._DYN_IN_V if which == "V" else self._DYN_OUTPUTS[which]) if isinstance(which, str) else int(which)
+        p = self.lib.mjb_dyn_device_ptr(self.ptr, bit)
         if not p:
             raise EngineError(self.lib.mjb_last_error().decode())
         return p
